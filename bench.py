@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: fused homography-warp + variance cost volume (BASELINE.json config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one reference view: 5 views x 384 depth planes over 32 x 688 x 464 fp32 feature
@@ -195,6 +195,24 @@ def cpu_baseline(proj34_host, feats_host, depth_host, gpu_volume=None):
                   "tolerance_rel_l1": 5e-5, "against": "oracle/planesweep_oracle.c (restates module.py:516-557 + cas_mvsnet.py:45-60)",
                   "ok": bool(num / max(den, 1e-30) < 5e-5)}
     return cb, parity
+
+
+DUMP_SAMPLE_VOXELS = 1 << 22   # seeded uniform sample of the volume (16 MB)
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir, volume):
+    """What the timed path handed its caller in the last step -- the [C, D, h, w] fp32 variance volume (15.7 GB at the
+    headline size) -- as .npy files of at most ~58 MB: the whole middle depth plane [C, h, w] and a fixed, seeded sample of
+    voxels (flat indices into the volume, sorted; regenerated from DUMP_SAMPLE_SEED, so two runs or two builds with the same
+    arguments compare element for element)."""
+    os.makedirs(out_dir, exist_ok=True)
+    mid = volume.shape[1] // 2
+    plane = volume[:, mid].float().cpu().numpy()
+    idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, volume.numel(), DUMP_SAMPLE_VOXELS, dtype=np.int64))
+    sample = volume.reshape(-1)[torch.from_numpy(idx).to(volume.device)].float().cpu().numpy()
+    np.save(os.path.join(out_dir, "variance_volume_plane%d.npy" % mid), np.ascontiguousarray(plane, np.float32))
+    np.save(os.path.join(out_dir, "variance_volume_sample.npy"), np.ascontiguousarray(sample, np.float32))
 
 
 HEADLINE_KERNEL_PREFIX = "_ZN3d3d18sweep_tiled_kernelILi1ELi4ELi16EfLb0ELi4ELi4ELi2EEE"   # sweep_tiled_kernel<1,4,16,float,false,4,4,2>
@@ -442,7 +460,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the config-3 model timings appended after the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/*.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -520,6 +542,9 @@ def main():
     voxels = D * H_FEAT * W_FEAT
     value = world * args.steps * voxels / elapsed / 1e6
     achieved = algorithmic_bytes() / (kern_ms * 1e-3) / 1e9
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)   # outside every timed region; `out` holds the last timed step's volume
 
     if rank == 0:
         traffic, traffic_info, bound = profiled_traffic()
