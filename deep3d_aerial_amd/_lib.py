@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.environ.get("D3D_LIBRARY") or os.path.join(CSRC, "libdeep3d_planesweep.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "deep3d_planesweep.h")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -126,6 +126,7 @@ SIGNATURES = {
     "d3d_fusion_gather_points": [_vp, _vp, ctypes.POINTER(_vp), _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "d3d_flip_rows": [ctypes.POINTER(_vp), _i, _i, _i, _vp, _vp],
     "d3d_center_image_u8": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "d3d_normals_from_depth": [_vp, ctypes.POINTER(_f), _i, _i, _i, _i, _vp, _vp, _vp],
 }
 
 

@@ -20,7 +20,8 @@ MODELS = ("casmvsnet", "ucsnet", "msrednet", "adamvs")  # mvs_dl.py:45
 
 class MVS_Inference:
     def __init__(self, max_w, max_h, view_num=5, num_depth=384, min_interval=0.1, model_type="adamvs",
-                 pretrain_weight=None, display_depth=False, n_gpus=1, extra_args=()):
+                 pretrain_weight=None, display_depth=False, n_gpus=1, extra_args=(), save_normals=False, fuse_normals=False,
+                 normal_nei=1):
         self.max_w = max_w
         self.max_h = max_h
         self.view_num = view_num
@@ -31,6 +32,10 @@ class MVS_Inference:
         self.model_type = model_type.lower()
         self.n_gpus = int(n_gpus)
         self.extra_args = list(extra_args)
+        # normal maps (predict --save_normals / --fuse_normals / --normal_nei): formatted only when asked for
+        self.save_normals = bool(save_normals)
+        self.fuse_normals = bool(fuse_normals)
+        self.normal_nei = int(normal_nei)
 
     def default_weight(self):
         """mvs_dl.py:46-58: the last *.ckpt under mvs/mvs_cas/checkpoints/<model>/whu_omvs, if that folder exists."""
@@ -55,6 +60,12 @@ class MVS_Inference:
         elif not any(x == "--random_weights" or x.startswith("--synthetic_items") for x in self.extra_args):
             raise FileNotFoundError("no checkpoint: pretrain_weight is None and mvs/mvs_cas/checkpoints/%s/whu_omvs holds "
                                     "no *.ckpt" % self.model_type)
+        if self.save_normals:
+            args.append("--save_normals")
+        if self.fuse_normals:
+            args.append("--fuse_normals")
+        if self.normal_nei != 1:
+            args.append("--normal_nei=%d" % self.normal_nei)
         return args + self.extra_args
 
     def run(self, data_folder, mvs_path):
@@ -97,7 +108,9 @@ def fusion_settings(config):
             "photometric_threshold": float(f.get("photomatric_threshold", 0.2)),
             "position_threshold": float(f.get("position_threshold", 1)),
             "depth_threshold": float(f.get("depth_threshold", 0.01)),
-            "normal_threshold": float(f.get("normal_threshold", 90.0)), "pc_format": f.get("pc_format", "ply")}
+            "normal_threshold": float(f.get("normal_threshold", 90.0)), "pc_format": f.get("pc_format", "ply"),
+            # not in the reference's config.yaml: normals estimated from the depth maps (predict --fuse_normals), off by default
+            "estimate_normals": bool(f.get("estimate_normals", False)), "normal_nei": int(f.get("normal_nei", 1))}
 
 
 def fusion_checker(config):

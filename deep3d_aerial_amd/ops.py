@@ -2320,3 +2320,63 @@ def gru_cell_fused(x, h, w_gates, b_gates, w_cand, b_cand):
     if hn is None:
         hn = conv_fold(x, w_cand, None, b_cand, h, act=3, stride=1, x2=rh, aux1=u)
     return hn
+
+
+# ----------------------------------------------------------------------------------------
+# surface normals from depth (compute_normals.py:32-82)
+# ----------------------------------------------------------------------------------------
+def normals_kinv(K):
+    """inv(K) of [3,3] or [B,3,3] intrinsics (torch tensor or array) for d3d_normals_from_depth: a [B,9] float32 CPU tensor,
+    row-major per item.  The reference multiplies with torch.inverse's fp32 result (compute_normals.py:23), whose last bits
+    depend on the batch size and the memory layout of its argument; here every item is inverted alone, in float64 through the
+    adjugate (fixed IEEE operations: the same bits on every machine, for any batch), and rounded once -- within an ulp of it."""
+    import numpy as _np_k
+
+    if isinstance(K, torch.Tensor):
+        K = K.detach().cpu().numpy()
+    K = _np_k.asarray(K, dtype=_np_k.float32).astype(_np_k.float64)
+    if K.ndim == 2:
+        K = K[None]
+    if K.ndim != 3 or K.shape[1:] != (3, 3):
+        raise ValueError("K must be [3,3] or [B,3,3] (got %s)" % (K.shape,))
+    a, b, c = K[:, 0, 0], K[:, 0, 1], K[:, 0, 2]
+    d, e, f = K[:, 1, 0], K[:, 1, 1], K[:, 1, 2]
+    g, h, i = K[:, 2, 0], K[:, 2, 1], K[:, 2, 2]
+    adj = _np_k.stack([e * i - f * h, c * h - b * i, b * f - c * e,
+                       f * g - d * i, a * i - c * g, c * d - a * f,
+                       d * h - e * g, b * g - a * h, a * e - b * d], -1)
+    det = a * adj[:, 0] + b * adj[:, 3] + c * adj[:, 6]
+    if not _np_k.all(_np_k.isfinite(det)) or _np_k.any(det == 0):
+        raise ValueError("singular intrinsics")
+    return torch.from_numpy(_np_k.ascontiguousarray(adj / det[:, None], dtype=_np_k.float32))
+
+
+def normals_from_depth(depth, K, nei=1, encoded=False, normal=True):
+    """ComputeNormals.compute_normal_by_depth (compute_normals.py:32-82) on the GPU: depth [H,W] or [B,H,W] (device fp32),
+    K [3,3] or [B,3,3] (one per item) -> camera-space unit normals [..,H,W,3], 0 on the border band of width `nei`.
+    encoded=True also returns (normal + 1) / 2, the payload of {view}_normal.pfm (fusion_3d_normal.py:191-195 decodes it),
+    from the same launch: (normal, encoded); with normal=False as well, the encoded map alone (the normals are not stored).
+    One kernel, d3d_normals_from_depth; CPU tensors are refused."""
+    if not (normal or encoded):
+        raise ValueError("nothing to compute: normal=False and encoded=False")
+    p = _chk(depth, "depth")
+    squeeze = depth.dim() == 2
+    if depth.dim() not in (2, 3):
+        raise ValueError("depth must be [H,W] or [B,H,W] (got %s)" % (tuple(depth.shape),))
+    d3 = depth[None] if squeeze else depth
+    B, H, W = (int(s) for s in d3.shape)
+    kinv = normals_kinv(K)
+    if kinv.shape[0] != B:
+        raise ValueError("%d intrinsics for %d depth maps" % (kinv.shape[0], B))
+    out = torch.empty((B, H, W, 3), dtype=torch.float32, device=depth.device) if normal else None
+    enc = torch.empty((B, H, W, 3), dtype=torch.float32, device=depth.device) if encoded else None
+    kp = ctypes.cast(kinv.data_ptr(), ctypes.POINTER(ctypes.c_float))
+    rc = _lib.load().d3d_normals_from_depth(p, kp, B, H, W, int(nei), None if out is None else _chk(out, "normal"),
+                                            None if enc is None else _chk(enc, "encoded"), _stream())
+    _lib.check(rc, "d3d_normals_from_depth")
+    if squeeze:
+        out = None if out is None else out[0]
+        enc = None if enc is None else enc[0]
+    if not normal:
+        return enc
+    return (out, enc) if encoded else out

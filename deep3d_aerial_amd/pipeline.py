@@ -67,10 +67,17 @@ def _gather_objects(obj, world_size):
 
 def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checker=None, fusion_num=10, min_geo_consist_num=4,
                      filter_sources=True, partition="block", scene_range=None, skip_line=2, feature_cache_bytes=0,
-                     device="cuda", timings=None, display=False, fuse_partition="views", scene_blocks=None):
+                     device="cuda", timings=None, display=False, fuse_partition="views", scene_blocks=None,
+                     estimate_normals=False, normal_nei=1, save_normals=False):
     """Runs the three steps above for this rank.  Returns a list, one entry per reference view this rank owns, of
     {"ref", "final_mask" [H,W] bool, "avg_xyz_world" [3,H,W], "points": fuse.extract_points(...) dict} (device tensors).
-    timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s."""
+    timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s.
+    estimate_normals: the views' "normal" maps are estimated from their depth maps (ops.normals_from_depth, stencil step
+    normal_nei) -- what the reference's fusion reads from {view}_normal.pfm (fusion_3d_normal.py:437-443, 491-498) -- instead
+    of the default (0, 0, -1).  They are computed after the all-gather (the exchange is unchanged), from the unfiltered
+    gathered maps (the reference reads them from depth_path, not from its tmp folder), once per view this rank's fusion
+    touches; normals follow the view, so the fused arrays do not depend on the number of ranks any more than without them.
+    save_normals: predict_views also writes {name}_normal.pfm."""
     if checker is None:
         checker = fuse.ConsistencyChecker(1.0, 0.01, 90.0, 0.2)   # Fuse_Depth_Map's defaults (fusion_3d_normal.py:56-57)
     n = len(dataset)
@@ -79,7 +86,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     cams = {}
     t0 = time.perf_counter()
     maps = predict.predict_views(model, dataset, output_folder, rank, world_size, device=device, keep_maps=True,
-                                 feature_cache_bytes=feature_cache_bytes, display=display, partition=partition, cams=cams)
+                                 feature_cache_bytes=feature_cache_bytes, display=display, partition=partition, cams=cams,
+                                 save_normals=save_normals, normal_nei=normal_nei)
     names = [recs[i]["name"] for i in mine]
     if list(maps.keys()) != names:
         raise RuntimeError("the views predict_views produced %s are not this rank's %s" % (list(maps.keys()), names))
@@ -115,6 +123,12 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     if fuse_partition not in ("views", "scene_blocks"):
         raise ValueError("fuse_partition must be 'views' or 'scene_blocks'")
     pair_of = lambda i: {"ref": recs[i]["name"], "src": list(recs[i]["src"])[:fusion_num]}
+
+    def with_normals(pairs):
+        if estimate_normals:
+            add_estimated_normals(views, pairs, fusion_num, normal_nei)
+        return pairs
+
     out = []
     if fuse_partition == "scene_blocks":
         if not scene_blocks:
@@ -126,14 +140,14 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             # (a reference view listed in a block but absent from the view list -- it had no sources -- has no maps: skipped with the
             #  warning the reference gives for a missing PFM, fusion_3d_normal.py:420-422)
             pairs = [pair_of(by_image[i]) for i in blk["refs"] if i in by_image]
-            fused = fuse.fuse_block(views, pairs, checker, fusion_num=fusion_num, min_geo_consist_num=min_geo_consist_num,
+            fused = fuse.fuse_block(views, with_normals(pairs), checker, fusion_num=fusion_num, min_geo_consist_num=min_geo_consist_num,
                                     filter_sources=filter_sources)
             for f in fused:
                 pts = fuse.extract_points(f["avg_xyz_world"], f["final_mask"], f["vis_infos"], None, f["normal_world"],
                                           blk["scene_range"], skip_line)
                 out.append({"ref": f["ref"], "scene": b, "final_mask": f["final_mask"], "avg_xyz_world": f["avg_xyz_world"], "points": pts})
     else:
-        fused = fuse.fuse_block(views, [pair_of(i) for i in mine], checker, fusion_num=fusion_num,
+        fused = fuse.fuse_block(views, with_normals([pair_of(i) for i in mine]), checker, fusion_num=fusion_num,
                                 min_geo_consist_num=min_geo_consist_num, filter_sources=filter_sources)
         sr = scene_range if scene_range is not None else [-np.inf, np.inf, -np.inf, np.inf]
         for f in fused:
@@ -146,6 +160,20 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
                        allgather_bytes=int(all_maps.numel() * 4), fuse_s=t2 - g1, map_size=(H, W),
                        backend=dist.get_backend() if world_size > 1 else "none")
     return out
+
+
+def add_estimated_normals(views, pairs, fusion_num=10, nei=1):
+    """Sets views[name]["normal"] (ops.normals_from_depth of views[name]["depth"] with views[name]["K"]) for every view that
+    fuse.fuse_block(views, pairs, fusion_num=...) reads -- each reference view and its first fusion_num listed sources that
+    exist -- and has none yet.  Call it before fuse_block: the source-filtering chain then never reaches the normals."""
+    from . import ops
+
+    for pair in pairs:
+        for name in [pair["ref"]] + [n for n in pair["src"][:fusion_num] if n in views]:
+            v = views[name]
+            if v.get("normal") is None:
+                v["normal"] = ops.normals_from_depth(v["depth"], v["K"], nei=nei)
+    return views
 
 
 def save_fused(results, folder):

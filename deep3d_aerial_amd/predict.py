@@ -65,24 +65,29 @@ def _pfm_header(h, w, color=False, scale=1):
 
 
 class PfmWriter(object):
-    """Asynchronous writer of the per-view products (predict.py:176-180: {name}_init.pfm, {name}_prob.pfm) --
+    """Asynchronous writer of the per-view products (predict.py:176-180: {name}_init.pfm, {name}_prob.pfm; with
+    --save_normals the colour {name}_normal.pfm) --
     SURVEY.md 8f row N2.  The reference pulls each map to the host synchronously, flips it with NumPy and writes it
     before the next view starts.  Here `submit` (stream-ordered, returns at once) flips the maps on the device
     into a staging buffer in file order (`d3d_flip_rows`), a copy stream moves the buffer to pinned host memory with
     ONE asynchronous D2H transfer, and a writer thread puts header + payload on disk while the GPU runs the next
     view.  `depth` slots bound the memory in flight.  Files are byte-identical to save_pfm's."""
 
-    def __init__(self, h, w, n_maps=2, depth=2, device="cuda"):
+    def __init__(self, h, w, n_maps=2, depth=2, device="cuda", n_color=0):
+        """n_maps greyscale ('Pf') maps [h,w] and n_color colour ('PF') maps [h,w,3] per submit (e.g. {name}_normal.pfm)."""
         import queue
         import threading
 
         if not torch.cuda.is_available():
             raise RuntimeError("PfmWriter stages through the GPU (no CPU fallback); use save_pfm for host arrays")
-        self.h, self.w, self.n = int(h), int(w), int(n_maps)
+        self.h, self.w, self.n, self.n_color = int(h), int(w), int(n_maps), int(n_color)
         self.device = torch.device(device)
         self.copy_stream = torch.cuda.Stream(device=self.device)
+        cshape = (self.n_color, self.h, 3 * self.w)
         self.slots = [dict(dev=torch.empty((self.n, self.h, self.w), dtype=torch.float32, device=self.device),
                            host=torch.empty((self.n, self.h, self.w), dtype=torch.float32).pin_memory(),
+                           cdev=torch.empty(cshape, dtype=torch.float32, device=self.device) if self.n_color else None,
+                           chost=torch.empty(cshape, dtype=torch.float32).pin_memory() if self.n_color else None,
                            free=threading.Event()) for _ in range(depth)]
         for sl in self.slots:
             sl["free"].set()
@@ -92,10 +97,12 @@ class PfmWriter(object):
         self._thread = threading.Thread(target=self._run, name="pfm-writer", daemon=True)
         self._thread.start()
 
-    def submit(self, maps, paths, display=None):
+    def submit(self, maps, paths, display=None, color_maps=(), color_paths=()):
         """maps: n device tensors of h*w fp32 elements each; paths: n file names.  display = (output_folder, name) has the
         writer thread render the colour maps of predict.py:155-176 from the same host copy (maps[0] depth, maps[1]
-        confidence) after the files are written -- the GPU does not wait for the PNG encoder."""
+        confidence) after the files are written -- the GPU does not wait for the PNG encoder.  color_maps / color_paths:
+        the n_color colour products, device tensors of h*w*3 fp32 elements ([h,w,3] interleaved) -- flipped as [h,3w] rows,
+        which is save_pfm's np.flipud of the [h,w,3] array."""
         import ctypes
 
         from . import _lib
@@ -105,28 +112,37 @@ class PfmWriter(object):
             raise self._err
         if len(maps) != self.n or len(paths) != self.n:
             raise ValueError("expected %d maps and paths" % self.n)
+        if len(color_maps) != self.n_color or len(color_paths) != self.n_color:
+            raise ValueError("expected %d colour maps and paths" % self.n_color)
         maps = [m.reshape(self.h, self.w) for m in maps]
+        color_maps = [m.reshape(self.h, 3 * self.w) for m in color_maps]
         sl = self.slots[self._next]
         self._next = (self._next + 1) % len(self.slots)
         sl["free"].wait()
         sl["free"].clear()
+        lib = _lib.load()
         ptrs = (ctypes.c_void_p * self.n)(*[_chk(m, "map").value for m in maps])
-        _lib.check(_lib.load().d3d_flip_rows(ptrs, self.n, self.h, self.w, _chk(sl["dev"], "staging"), _stream()),
-                   "d3d_flip_rows")
+        _lib.check(lib.d3d_flip_rows(ptrs, self.n, self.h, self.w, _chk(sl["dev"], "staging"), _stream()), "d3d_flip_rows")
+        if self.n_color:
+            cptrs = (ctypes.c_void_p * self.n_color)(*[_chk(m, "colour map").value for m in color_maps])
+            _lib.check(lib.d3d_flip_rows(cptrs, self.n_color, self.h, 3 * self.w, _chk(sl["cdev"], "staging"), _stream()),
+                       "d3d_flip_rows")
         cur = torch.cuda.current_stream(self.device)
         self.copy_stream.wait_stream(cur)
         with torch.cuda.stream(self.copy_stream):
             sl["host"].copy_(sl["dev"], non_blocking=True)
+            if self.n_color:
+                sl["chost"].copy_(sl["cdev"], non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.copy_stream)
-        self._q.put((sl, done, list(paths), display))
+        self._q.put((sl, done, list(paths), display, list(color_paths)))
 
     def _run(self):
         while True:
             item = self._q.get()
             if item is None:
                 return
-            sl, done, paths, display = item
+            sl, done, paths, display, color_paths = item
             try:
                 done.synchronize()
                 payload = sl["host"].numpy()
@@ -134,6 +150,10 @@ class PfmWriter(object):
                     with open(path, "wb") as f:
                         f.write(_pfm_header(self.h, self.w))
                         payload[k].tofile(f)
+                for k, path in enumerate(color_paths):
+                    with open(path, "wb") as f:
+                        f.write(_pfm_header(self.h, self.w, color=True))
+                        sl["chost"].numpy()[k].tofile(f)
                 if display is not None:   # the staging buffer is in file order (bottom row first): flip back
                     write_display_maps(display[0], display[1], payload[0][::-1].copy(), payload[1][::-1].copy())
             except Exception as e:  # surfaced by the next submit() / close()
@@ -350,7 +370,8 @@ def _item_views(s, model, device):
 # the per-view loop of predict.py:126-183, sharded over ranks
 # ----------------------------------------------------------------------------------------
 def predict_views(model, dataset, output_folder, rank=0, world_size=1, device="cuda", keep_maps=False,
-                  feature_cache_bytes=0, display=False, partition="block", stats=None, cams=None):
+                  feature_cache_bytes=0, display=False, partition="block", stats=None, cams=None, save_normals=False,
+                  normal_nei=1):
     """Returns the names of the views this rank produced; with keep_maps=True a dict name -> (depth, confidence)
     of device tensors instead, so the fusion step (fuse.ViewFusion) can start without re-reading the PFM files.
     feature_cache_bytes > 0 keeps the feature pyramids of that many bytes of images resident across views (items must
@@ -358,7 +379,10 @@ def predict_views(model, dataset, output_folder, rank=0, world_size=1, device="c
     "block" keeps neighbouring views -- which share source images -- on one rank, so its cache keeps hitting).
     stats: a dict that receives this rank's view count, cache hits / misses and feature pyramids computed per view.
     cams: a dict that receives name -> the view's [2,4,4] camera (`outcam`: what write_red_cam puts into {name}.txt), for the
-    fusion step that follows in the same process (pipeline.predict_and_fuse)."""
+    fusion step that follows in the same process (pipeline.predict_and_fuse).
+    save_normals: also write {name}_normal.pfm -- the camera-space normals of the final depth map (ops.normals_from_depth
+    with the view's output intrinsics outcam[1][:3,:3] and stencil step normal_nei) encoded as (n + 1) / 2, the file the
+    reference's fusion step reads (fusion_3d_normal.py:437-443, 191-195)."""
     from .dataset import FeatureCache
 
     os.makedirs(output_folder, exist_ok=True)
@@ -389,12 +413,21 @@ def predict_views(model, dataset, output_folder, rank=0, world_size=1, device="c
                 name = os.path.splitext(s["outlocation"][3])[0]
                 paths = [os.path.join(output_folder, "%s_init.pfm" % name),
                          os.path.join(output_folder, "%s_prob.pfm" % name)]
-                if writer is None or (writer.h, writer.w) != tuple(depth.shape):
+                n_color = 1 if save_normals else 0
+                if writer is None or (writer.h, writer.w, writer.n_color) != tuple(depth.shape) + (n_color,):
                     if writer is not None:
                         writer.close()
-                    writer = PfmWriter(depth.shape[0], depth.shape[1], 2, device=depth.device)
+                    writer = PfmWriter(depth.shape[0], depth.shape[1], 2, device=depth.device, n_color=n_color)
+                color, color_paths = (), ()
+                if save_normals:
+                    from . import ops as _ops
+
+                    K = np.asarray(s["outcam"], dtype=np.float32)[1, :3, :3]
+                    color = (_ops.normals_from_depth(depth, K, nei=normal_nei, encoded=True, normal=False),)
+                    color_paths = (os.path.join(output_folder, "%s_normal.pfm" % name),)
                 # the files (and with --display the colour maps) land while the next view is computed
-                writer.submit([depth, prob], paths, display=(output_folder, name) if display else None)
+                writer.submit([depth, prob], paths, display=(output_folder, name) if display else None, color_maps=color,
+                              color_paths=color_paths)
                 write_red_cam(os.path.join(output_folder, "%s.txt" % name), s["outcam"], s["outlocation"],
                               s["ref_image_path"])
                 if cams is not None:
@@ -428,7 +461,7 @@ def _truthy(text):
 
 def parse_args(argv=None):
     """Every flag of the reference's harness (predict.py:30-58) with its default, plus --synthetic_items /
-    --random_weights / --feature_cache_gb of this package."""
+    --random_weights / --feature_cache_gb, the --fuse flags and the normal-map flags of this package."""
     ap = argparse.ArgumentParser(description="plane-sweep depth inference (predict.py-compatible flags)")
     ap.add_argument("--model", default="adamvs", help="casmvsnet | msrednet | adamvs | ucsnet")
     ap.add_argument("--dataset", default="cas_normal_eval", help="dataset class (only the inference dataset exists here)")
@@ -472,6 +505,12 @@ def parse_args(argv=None):
                     help="who fuses what: every rank the reference views it swept (balanced; the filtering chain restarts at rank seams), or "
                          "whole scene blocks of blocks.txt per rank (the reference's chains exactly, for any number of ranks)")
     ap.add_argument("--blocks_file", default=None, help="scene blocks (default <data_folder>/blocks.txt) for --fuse_partition scene_blocks")
+    # surface normals from the depth maps (ComputeNormals.compute_normal_by_depth, compute_normals.py:32-82): off by default
+    ap.add_argument("--save_normals", action="store_true",
+                    help="also write {name}_normal.pfm: camera-space normals of the depth map as (n + 1) / 2 (what fusion reads)")
+    ap.add_argument("--fuse_normals", action="store_true",
+                    help="with --fuse: estimate every fused view's normals from its gathered depth map instead of the default (0, 0, -1)")
+    ap.add_argument("--normal_nei", type=int, default=1, help="stencil step of the normal estimate (compute_normals.py forward: 1)")
     return ap.parse_args(argv)
 
 
@@ -543,14 +582,16 @@ def main(argv=None):
         res = pipeline.predict_and_fuse(model, ds, a.output_folder, rank, world, checker=checker, fusion_num=a.fusion_num,
                                         min_geo_consist_num=a.geo_consist_num, filter_sources=bool(a.fuse_filter_sources),
                                         partition=a.partition, feature_cache_bytes=cache_bytes, timings=tm, display=_truthy(a.display),
-                                        fuse_partition=a.fuse_partition, scene_blocks=blocks)
+                                        fuse_partition=a.fuse_partition, scene_blocks=blocks, estimate_normals=a.fuse_normals,
+                                        normal_nei=a.normal_nei, save_normals=a.save_normals)
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
         print("rank %d/%d: %d views in %.2f s, all-gather of %.1f MB in %.2f ms (%s), fusion of its %d reference views %.2f s, "
               "%d vertices" % (rank, world, tm["views"], tm["predict_s"], tm["allgather_bytes"] / 1e6, tm["allgather_ms"], tm["backend"],
                                len(res), tm["fuse_s"], sum(int(r["points"]["xyz"].shape[0]) for r in res)))
         return [r["ref"] for r in res]
     names = predict_views(model, ds, a.output_folder, rank, world, display=_truthy(a.display),
-                          feature_cache_bytes=cache_bytes, partition=a.partition, stats=st)
+                          feature_cache_bytes=cache_bytes, partition=a.partition, stats=st, save_normals=a.save_normals,
+                          normal_nei=a.normal_nei)
     acc = st.get("cache_hits", 0) + st.get("cache_misses", 0)
     print("rank %d/%d wrote %d views (%s partition): feature cache %d hits / %d lookups (%.0f %%), %.2f pyramids computed per view"
           % (rank, world, len(names), st.get("partition"), st.get("cache_hits", 0), acc,

@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define D3D_ABI_VERSION 10
+#define D3D_ABI_VERSION 11
 
 #define D3D_OK 0
 #define D3D_ERR_INVALID_ARG (-1)
@@ -805,6 +805,24 @@ int d3d_flip_rows(const float* const* maps, int n, int H, int W, float* out, d3d
  */
 int d3d_center_image_u8(const unsigned char* img, int h, int w, int channels, int y0, int x0, int H, int W, int mode,
                         unsigned long long* sums, float* out, d3d_stream_t stream);
+
+/*
+ * DESIGN.md §1 row N5 -- surface normals from depth: ComputeNormals.compute_normal_by_depth (mvs/mvs_cas/models/
+ * compute_normals.py:32-82; the reference defines it and never calls it), the producer of the {view}_normal.pfm that
+ * the fusion step reads (fuse/fusion_3d_normal.py:437-443, 491-498; read_normal :191-195 decodes x * 2 - 1).
+ *   depth [B,H,W] fp32 (device); kinv: HOST array of B x 9 fp32, inv(K) of every item row-major, the caller's fp32
+ *   inverse (the reference's torch.inverse(intrinsics), :23).  Per pixel at distance >= nei from every border, P = inv(K) (x d, y d, d); the
+ *   eight differences of the 3x3 stencil of step nei against the centre with the reference's signs (:51-58), the four
+ *   cross products (x1, y1), (x0, y0), (x0y1, x0y0), (x1y0, x1y1), each normalised (F.normalize: v / max(|v|, 1e-12)),
+ *   summed, normalised again.  The border band of width nei is 0 (:80); a map with H == 2 nei or W == 2 nei is all 0.
+ *   normal [B,H,W,3] interleaved (the layout d3d_fusion_* read); encoded [B,H,W,3] = (normal + 1) / 2, the payload of
+ *   {view}_normal.pfm.  Either output may be NULL, not both.  nei < 1, H < 2 nei or W < 2 nei: D3D_ERR_INVALID_ARG.
+ * The differences are formed as d_a inv(K) (dx, dy, 0) + (d_a - d_c) inv(K) (x, y, 1) -- the same quantity without the
+ * cancellation of two fp32 points (csrc/normals.hip); fp32, no atomics: bit-reproducible, and item b of a batched call
+ * equals a call on item b alone.
+ */
+int d3d_normals_from_depth(const float* depth, const float* kinv, int B, int H, int W, int nei, float* normal,
+                           float* encoded, d3d_stream_t stream);
 
 #ifdef __cplusplus
 }
