@@ -21,6 +21,7 @@ _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
 _f = ctypes.c_float
+_d = ctypes.c_double
 _sz = ctypes.c_size_t
 
 # name -> argtypes; restype is int except where noted.  Mirrors include/deep3d_planesweep.h.
@@ -127,6 +128,9 @@ SIGNATURES = {
     "d3d_flip_rows": [ctypes.POINTER(_vp), _i, _i, _i, _vp, _vp],
     "d3d_center_image_u8": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "d3d_normals_from_depth": [_vp, ctypes.POINTER(_f), _i, _i, _i, _i, _vp, _vp, _vp],
+    "d3d_dsm_scratch_bytes": [ctypes.c_longlong, _i, _i, _i],  # returns size_t
+    "d3d_dsm_from_points": [_vp, ctypes.c_longlong, _d, _d, _d, _d, _d, _d, _i, _i, _i, _d, _i, _vp, _sz, _vp, _vp, _vp],
+    "d3d_dsm_fill_moving_average": [_vp, _vp, _i, _i, _i, _vp],
 }
 
 
@@ -165,7 +169,8 @@ def load():
             raise LibraryMissing("symbol %s missing from %s" % (name, SO_PATH)) from e
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name in ("d3d_last_error", "d3d_build_flags", "d3d_h16_format") else
-                      ctypes.c_size_t if name in ("d3d_sweep_workspace_bytes", "d3d_sweep_workspace_bytes_for", "d3d_fusion_points_scratch_bytes") else ctypes.c_int)
+                      ctypes.c_size_t if name in ("d3d_sweep_workspace_bytes", "d3d_sweep_workspace_bytes_for", "d3d_fusion_points_scratch_bytes",
+                                                         "d3d_dsm_scratch_bytes") else ctypes.c_int)
     if lib.d3d_version() != ABI_VERSION:
         raise LibraryMissing("ABI version mismatch: library %d, binding %d" % (lib.d3d_version(), ABI_VERSION))
     _lib = lib

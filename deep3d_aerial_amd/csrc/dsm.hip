@@ -1,0 +1,431 @@
+// Digital surface model from a point cloud: the reference's run.py:234-240 calls pc2dsm.DSM_from_PC, which it
+// never shipped; the semantics are this project's (deep3d_aerial_amd/dsm.py states them, include/deep3d_planesweep.h too).
+//
+// Grid: cell (i, j) of point (x, y, z) is j = floor((x - x_min) / ux), i = floor((y_max - y) / uy) in fp64 with IEEE division;
+// row 0 is north.  A point is kept when x, y, z are finite, 0 <= i < H, 0 <= j < W and z_min <= z <= z_max.
+// Heights are compared through the order-preserving float -> uint32 key (IEEE total order, -0.0 < +0.0), so every selection is
+// exact and does not depend on the order of the points.
+//
+// Max:        bin (one atomicAdd on count + one atomicMax of the key per point) -> finalize per cell.
+// Robust_Max: bin (atomicAdd on count; the returned value is the point's rank in its cell, 4 B per point)
+//             -> exclusive scan of count (reduce, scan of the block sums, apply) -> scatter of the keys to offset[cell] + rank
+//             -> select the (t+1)-th largest key, t = floor(trim * n): cells of up to DSM_SMALL points one lane each, keys
+//                in registers; larger cells on a compacted list, one workgroup each, radix select over the key bytes with an
+//                LDS histogram (a persistent grid walks the list: a cell of 10^5 points holds one workgroup, not the launch).
+// MovingAverage: per empty cell, the mean of the non-empty cells of the (2r+1)^2 window (clipped to the raster), summed in
+//             fp64 in the order dy = -r..r, dx = -r..r, divided by the count and rounded once; one launch per iteration.
+// Every step is integer atomics or fixed-order arithmetic: the rasters are bit-reproducible for any point order or split.
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+
+namespace d3d {
+
+constexpr int DSM_BLOCK = 256;
+constexpr int DSM_SCAN_ITEMS = 16;                          // count elements per thread of the scan
+constexpr int DSM_SCAN_TILE = DSM_BLOCK * DSM_SCAN_ITEMS;   // count elements per scan workgroup
+constexpr int DSM_SMALL = 32;                               // cells of at most this many points: one lane, keys in registers
+constexpr int DSM_BIG_GRID = 1024;                          // workgroups walking the list of larger cells
+constexpr int DSM_FILL_TILE = 16;
+constexpr int DSM_MAX_RADIUS = 16;
+
+struct DsmGrid {
+    double x_min, y_max, ux, uy, z_min, z_max;
+    int W, H;
+};
+
+__device__ __forceinline__ unsigned dsm_key(float z) {
+    const unsigned u = __float_as_uint(z);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float dsm_unkey(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// The cell of point p, or -1.  Bin and scatter both call this, so they agree on every point.
+__device__ __forceinline__ int dsm_cell(const float* __restrict__ xyz, long p, const DsmGrid& g, float* z_out) {
+    const float x = xyz[3 * p], y = xyz[3 * p + 1], z = xyz[3 * p + 2];
+    *z_out = z;
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) return -1;
+    const double zd = (double)z;
+    if (!(zd >= g.z_min && zd <= g.z_max)) return -1;
+    const double fj = floor(((double)x - g.x_min) / g.ux);
+    const double fi = floor((g.y_max - (double)y) / g.uy);
+    if (!(fj >= 0.0 && fj < (double)g.W && fi >= 0.0 && fi < (double)g.H)) return -1;
+    return (int)fi * g.W + (int)fj;
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_bin_kernel(const float* __restrict__ xyz, int n, DsmGrid g, int* __restrict__ count,
+                                                            unsigned* __restrict__ keymax, int* __restrict__ rank) {
+    const long p = (long)blockIdx.x * DSM_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    float z;
+    const int c = dsm_cell(xyz, p, g, &z);
+    if (c < 0) return;
+    const int r = atomicAdd(count + c, 1);
+    if constexpr (ROBUST)
+        rank[p] = r;
+    else
+        atomicMax(keymax + c, dsm_key(z));
+}
+
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_max_finalize_kernel(const int* __restrict__ count, const unsigned* __restrict__ keymax,
+                                                                     int cells, int min_points, float* __restrict__ height) {
+    const int c = blockIdx.x * DSM_BLOCK + threadIdx.x;
+    if (c >= cells) return;
+    const int n = count[c];
+    height[c] = (n > 0 && n >= min_points) ? dsm_unkey(keymax[c]) : __builtin_nanf("");
+}
+
+// Exclusive block scan of one int per thread; returns the thread's prefix, *total the block's sum.
+__device__ __forceinline__ int dsm_block_exclusive_scan(int v, int* lds, int* total) {
+    const int t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = 1; s < DSM_BLOCK; s <<= 1) {
+        const int a = t >= s ? lds[t - s] : 0;
+        __syncthreads();
+        lds[t] += a;
+        __syncthreads();
+    }
+    const int incl = lds[t];
+    *total = lds[DSM_BLOCK - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+__device__ __forceinline__ void dsm_load_items(const int* __restrict__ count, long base, int cells, int* v) {
+    if (base + DSM_SCAN_ITEMS <= cells) {
+        const int4* q = reinterpret_cast<const int4*>(count + base);
+#pragma unroll
+        for (int k = 0; k < DSM_SCAN_ITEMS / 4; ++k) {
+            const int4 a = q[k];
+            v[4 * k] = a.x; v[4 * k + 1] = a.y; v[4 * k + 2] = a.z; v[4 * k + 3] = a.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < DSM_SCAN_ITEMS; ++k) v[k] = base + k < cells ? count[base + k] : 0;
+    }
+}
+
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_scan_reduce_kernel(const int* __restrict__ count, int cells, int* __restrict__ partial) {
+    __shared__ int lds[DSM_BLOCK];
+    const long base = (long)blockIdx.x * DSM_SCAN_TILE + threadIdx.x * DSM_SCAN_ITEMS;
+    int v[DSM_SCAN_ITEMS];
+    dsm_load_items(count, base, cells, v);
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < DSM_SCAN_ITEMS; ++k) s += v[k];
+    int total;
+    dsm_block_exclusive_scan(s, lds, &total);
+    if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+// One workgroup: exclusive scan of the nb block sums in place, chunk by chunk with a carry.
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_scan_partials_kernel(int* __restrict__ partial, int nb) {
+    __shared__ int lds[DSM_BLOCK];
+    int carry = 0;
+    for (int b0 = 0; b0 < nb; b0 += DSM_BLOCK) {
+        const int i = b0 + threadIdx.x;
+        const int v = i < nb ? partial[i] : 0;
+        int total;
+        const int ex = dsm_block_exclusive_scan(v, lds, &total);
+        if (i < nb) partial[i] = carry + ex;
+        carry += total;
+    }
+}
+
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_scan_apply_kernel(const int* __restrict__ count, int cells, const int* __restrict__ partial,
+                                                                   int* __restrict__ offset) {
+    __shared__ int lds[DSM_BLOCK];
+    const long base = (long)blockIdx.x * DSM_SCAN_TILE + threadIdx.x * DSM_SCAN_ITEMS;
+    int v[DSM_SCAN_ITEMS];
+    dsm_load_items(count, base, cells, v);
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < DSM_SCAN_ITEMS; ++k) s += v[k];
+    int total;
+    int run = partial[blockIdx.x] + dsm_block_exclusive_scan(s, lds, &total);
+#pragma unroll
+    for (int k = 0; k < DSM_SCAN_ITEMS; ++k) {
+        if (base + k < cells) offset[base + k] = run;
+        run += v[k];
+    }
+}
+
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_scatter_kernel(const float* __restrict__ xyz, int n, DsmGrid g, const int* __restrict__ offset,
+                                                                const int* __restrict__ rank, unsigned* __restrict__ keys) {
+    const long p = (long)blockIdx.x * DSM_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    float z;
+    const int c = dsm_cell(xyz, p, g, &z);
+    if (c < 0) return;
+    const int o = offset[c] + rank[p];
+    if (o < n) keys[o] = dsm_key(z);   // always true (the scan counts what the bin kept): a guard on the write
+}
+
+__device__ __forceinline__ int dsm_trim_count(double trim, int n) { return (int)floor(trim * (double)n); }
+
+// Cells of up to DSM_SMALL points: the keys in registers, the (t+1)-th largest found by walking down the distinct values
+// (t + 1 <= n rounds at most; t = 0 -- every cell of fewer than 1 / trim points -- is one round, the plain maximum).
+// Larger cells go on the list for dsm_select_big_kernel.
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_select_small_kernel(const int* __restrict__ count, const int* __restrict__ offset,
+                                                                     const unsigned* __restrict__ keys, int cells, double trim,
+                                                                     int min_points, float* __restrict__ height,
+                                                                     int* __restrict__ big, int* __restrict__ n_big) {
+    const int c = blockIdx.x * DSM_BLOCK + threadIdx.x;
+    if (c >= cells) return;
+    const int n = count[c];
+    if (n == 0 || n < min_points) {
+        height[c] = __builtin_nanf("");
+        return;
+    }
+    if (n > DSM_SMALL) {
+        big[atomicAdd(n_big, 1)] = c;
+        return;
+    }
+    const unsigned* b = keys + offset[c];
+    unsigned v[DSM_SMALL];
+#pragma unroll
+    for (int i = 0; i < DSM_SMALL; ++i) v[i] = i < n ? b[i] : 0u;   // valid keys are > 0: 0 is below every finite height
+    int remaining = dsm_trim_count(trim, n) + 1;
+    unsigned bound = 0xffffffffu, m = 0;
+    bool first = true;
+    for (;;) {
+        m = 0;
+        int eq = 0;
+#pragma unroll
+        for (int i = 0; i < DSM_SMALL; ++i) {
+            const unsigned x = v[i];
+            if (first || x < bound) {
+                if (x > m) {
+                    m = x;
+                    eq = 1;
+                } else if (x == m) {
+                    ++eq;
+                }
+            }
+        }
+        if (eq >= remaining || m == 0) break;   // m == 0 cannot happen for t < n; it only guards the loop
+        remaining -= eq;
+        bound = m;
+        first = false;
+    }
+    height[c] = dsm_unkey(m);
+}
+
+// One workgroup per listed cell: the key of rank t (descending) by four 8-bit radix passes, MSB first, LDS histogram.
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_select_big_kernel(const int* __restrict__ count, const int* __restrict__ offset,
+                                                                   const unsigned* __restrict__ keys, const int* __restrict__ big,
+                                                                   const int* __restrict__ n_big, double trim, float* __restrict__ height) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned s_prefix;
+    __shared__ int s_k;
+    const int nb = *n_big;
+    const int t = threadIdx.x;
+    for (int q = blockIdx.x; q < nb; q += gridDim.x) {
+        const int c = big[q];
+        const int n = count[c];
+        const unsigned* b = keys + offset[c];
+        unsigned prefix = 0, mask = 0;
+        int k = dsm_trim_count(trim, n);   // rank from the top, 0-based
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hist[t] = 0;
+            __syncthreads();
+            for (int i = t; i < n; i += DSM_BLOCK) {
+                const unsigned x = b[i];
+                if ((x & mask) == prefix) atomicAdd(hist + ((x >> shift) & 255u), 1u);
+            }
+            __syncthreads();
+            if (t == 0) {
+                int cum = 0;
+                for (int d = 255; d >= 0; --d) {
+                    const int h = (int)hist[d];
+                    if (cum + h > k) {
+                        s_k = k - cum;
+                        s_prefix = prefix | ((unsigned)d << shift);
+                        break;
+                    }
+                    cum += h;
+                }
+            }
+            __syncthreads();
+            prefix = s_prefix;
+            k = s_k;
+            mask |= 255u << shift;
+            __syncthreads();
+        }
+        if (t == 0) height[c] = dsm_unkey(prefix);
+    }
+}
+
+// MovingAverage: a 16 x 16 tile of cells per workgroup, the tile and its halo of r in LDS (NaN outside the raster).
+__global__ __launch_bounds__(DSM_FILL_TILE * DSM_FILL_TILE) void dsm_fill_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                                 int W, int H, int r) {
+    constexpr int S = DSM_FILL_TILE + 2 * DSM_MAX_RADIUS;
+    __shared__ float tile[S * S];
+    const int side = DSM_FILL_TILE + 2 * r;
+    const int x0 = blockIdx.x * DSM_FILL_TILE - r, y0 = blockIdx.y * DSM_FILL_TILE - r;
+    const int tid = threadIdx.y * DSM_FILL_TILE + threadIdx.x;
+    for (int idx = tid; idx < side * side; idx += DSM_FILL_TILE * DSM_FILL_TILE) {
+        const int ly = idx / side, lx = idx - ly * side;
+        const int gy = y0 + ly, gx = x0 + lx;
+        tile[ly * S + lx] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? in[(long)gy * W + gx] : __builtin_nanf("");
+    }
+    __syncthreads();
+    const int x = blockIdx.x * DSM_FILL_TILE + threadIdx.x, y = blockIdx.y * DSM_FILL_TILE + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const float* ctr = tile + (threadIdx.y + r) * S + threadIdx.x + r;
+    float v = *ctr;
+    if (isnan(v)) {
+        double sum = 0.0;
+        int cnt = 0;
+        for (int dy = -r; dy <= r; ++dy) {
+            const float* row = ctr + dy * S;
+            for (int dx = -r; dx <= r; ++dx) {
+                const float a = row[dx];
+                if (!isnan(a)) {
+                    sum += (double)a;
+                    ++cnt;
+                }
+            }
+        }
+        v = cnt > 0 ? (float)(sum / (double)cnt) : __builtin_nanf("");
+    }
+    out[(long)y * W + x] = v;
+}
+
+static size_t dsm_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct DsmScratch {
+    size_t keymax, rank, offset, partial, keys, big, n_big, total;
+};
+
+static DsmScratch dsm_layout(long long n, long long cells, int select) {
+    DsmScratch s = {};
+    size_t at = 0;
+    if (select == 0) {
+        s.keymax = at;
+        at += dsm_align((size_t)cells * 4);
+    } else {
+        const long long nb = (cells + DSM_SCAN_TILE - 1) / DSM_SCAN_TILE;
+        const long long cap = std::min(cells, n / (DSM_SMALL + 1) + 1);
+        s.rank = at;
+        at += dsm_align((size_t)n * 4);
+        s.offset = at;
+        at += dsm_align((size_t)cells * 4);
+        s.partial = at;
+        at += dsm_align((size_t)nb * 4);
+        s.keys = at;
+        at += dsm_align((size_t)n * 4);
+        s.big = at;
+        at += dsm_align((size_t)cap * 4);
+        s.n_big = at;
+        at += dsm_align(4);
+    }
+    s.total = at;
+    return s;
+}
+
+static bool dsm_dims_ok(long long n, int W, int H) {
+    return n >= 0 && n < (1ll << 31) && W >= 1 && H >= 1 && (long long)W * H < (1ll << 31);
+}
+
+}  // namespace d3d
+
+using namespace d3d;
+
+extern "C" size_t d3d_dsm_scratch_bytes(long long n_points, int W, int H, int select) {
+    if (!dsm_dims_ok(n_points, W, H) || (select != 0 && select != 1)) return 0;
+    return dsm_layout(n_points, (long long)W * H, select).total;
+}
+
+extern "C" int d3d_dsm_from_points(const float* xyz, long long n_points, double x_min, double y_max, double unit_x, double unit_y,
+                                   double z_min, double z_max, int W, int H, int select, double trim, int min_points, void* scratch,
+                                   size_t scratch_bytes, float* height, int* count, d3d_stream_t stream) {
+    D3D_REQUIRE(height && count, "null pointer (height, count)");
+    D3D_REQUIRE(xyz || n_points == 0, "null pointer (xyz) with %lld points", n_points);
+    D3D_REQUIRE(n_points >= 0 && n_points < (1ll << 31), "n_points=%lld (0 .. 2^31 - 1)", n_points);
+    D3D_REQUIRE(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "raster %d x %d: size must be >= 1 and W * H < 2^31", W, H);
+    D3D_REQUIRE(std::isfinite(unit_x) && std::isfinite(unit_y) && unit_x > 0.0 && unit_y > 0.0, "unit (%g, %g) must be finite and > 0",
+                unit_x, unit_y);
+    D3D_REQUIRE(std::isfinite(x_min) && std::isfinite(y_max), "border (x_min %g, y_max %g) must be finite", x_min, y_max);
+    D3D_REQUIRE(!std::isnan(z_min) && !std::isnan(z_max) && z_min <= z_max, "z bounds [%g, %g]", z_min, z_max);
+    D3D_REQUIRE(select == 0 || select == 1, "select=%d (0 Max, 1 Robust_Max)", select);
+    D3D_REQUIRE(trim >= 0.0 && trim < 1.0, "trim=%g outside [0, 1)", trim);
+    D3D_REQUIRE(min_points >= 1, "min_points=%d (>= 1)", min_points);
+    const long long cells = (long long)W * H;
+    const DsmScratch L = dsm_layout(n_points, cells, select);
+    D3D_REQUIRE(scratch || L.total == 0, "null pointer (scratch)");
+    D3D_REQUIRE(scratch_bytes >= L.total, "scratch of %zu bytes, %zu needed (d3d_dsm_scratch_bytes)", scratch_bytes, L.total);
+    const int n = (int)n_points, nc = (int)cells;
+    const DsmGrid g = {x_min, y_max, unit_x, unit_y, z_min, z_max, W, H};
+    hipStream_t st = (hipStream_t)stream;
+    char* s = (char*)scratch;
+    int rc = hip_status(hipMemsetAsync(count, 0, (size_t)cells * 4, st), "dsm: clear count");
+    if (rc != D3D_OK) return rc;
+    const int gp = ceil_div(n, DSM_BLOCK), gc = ceil_div(nc, DSM_BLOCK);
+    if (select == 0) {
+        unsigned* keymax = (unsigned*)(s + L.keymax);
+        rc = hip_status(hipMemsetAsync(keymax, 0, (size_t)cells * 4, st), "dsm: clear keys");
+        if (rc != D3D_OK) return rc;
+        if (n > 0) {
+            hipLaunchKernelGGL((dsm_bin_kernel<false>), dim3(gp), dim3(DSM_BLOCK), 0, st, xyz, n, g, count, keymax, (int*)nullptr);
+            D3D_LAUNCH_CHECK("dsm_bin_kernel launch");
+        }
+        hipLaunchKernelGGL(dsm_max_finalize_kernel, dim3(gc), dim3(DSM_BLOCK), 0, st, count, keymax, nc, min_points, height);
+        D3D_LAUNCH_CHECK("dsm_max_finalize_kernel launch");
+        return D3D_OK;
+    }
+    int* rank = (int*)(s + L.rank);
+    int* offset = (int*)(s + L.offset);
+    int* partial = (int*)(s + L.partial);
+    unsigned* keys = (unsigned*)(s + L.keys);
+    int* big = (int*)(s + L.big);
+    int* n_big = (int*)(s + L.n_big);
+    rc = hip_status(hipMemsetAsync(n_big, 0, 4, st), "dsm: clear list");
+    if (rc != D3D_OK) return rc;
+    if (n > 0) {
+        hipLaunchKernelGGL((dsm_bin_kernel<true>), dim3(gp), dim3(DSM_BLOCK), 0, st, xyz, n, g, count, (unsigned*)nullptr, rank);
+        D3D_LAUNCH_CHECK("dsm_bin_kernel launch");
+        const int nb = ceil_div(nc, DSM_SCAN_TILE);
+        hipLaunchKernelGGL(dsm_scan_reduce_kernel, dim3(nb), dim3(DSM_BLOCK), 0, st, count, nc, partial);
+        D3D_LAUNCH_CHECK("dsm_scan_reduce_kernel launch");
+        hipLaunchKernelGGL(dsm_scan_partials_kernel, dim3(1), dim3(DSM_BLOCK), 0, st, partial, nb);
+        D3D_LAUNCH_CHECK("dsm_scan_partials_kernel launch");
+        hipLaunchKernelGGL(dsm_scan_apply_kernel, dim3(nb), dim3(DSM_BLOCK), 0, st, count, nc, partial, offset);
+        D3D_LAUNCH_CHECK("dsm_scan_apply_kernel launch");
+        hipLaunchKernelGGL(dsm_scatter_kernel, dim3(gp), dim3(DSM_BLOCK), 0, st, xyz, n, g, offset, rank, keys);
+        D3D_LAUNCH_CHECK("dsm_scatter_kernel launch");
+    } else {
+        // no point: every count is 0, the select kernel reads neither offset nor keys
+    }
+    hipLaunchKernelGGL(dsm_select_small_kernel, dim3(gc), dim3(DSM_BLOCK), 0, st, count, offset, keys, nc, trim, min_points, height, big,
+                       n_big);
+    D3D_LAUNCH_CHECK("dsm_select_small_kernel launch");
+    if (n > DSM_SMALL) {
+        const long long cap = std::min(cells, n_points / (DSM_SMALL + 1) + 1);
+        const int grid = (int)std::min<long long>(cap, DSM_BIG_GRID);
+        hipLaunchKernelGGL(dsm_select_big_kernel, dim3(grid), dim3(DSM_BLOCK), 0, st, count, offset, keys, big, n_big, trim, height);
+        D3D_LAUNCH_CHECK("dsm_select_big_kernel launch");
+    }
+    return D3D_OK;
+}
+
+extern "C" int d3d_dsm_fill_moving_average(const float* in, float* out, int W, int H, int radius, d3d_stream_t stream) {
+    D3D_REQUIRE(in && out, "null pointer (in, out)");
+    D3D_REQUIRE(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "raster %d x %d: size must be >= 1 and W * H < 2^31", W, H);
+    D3D_REQUIRE(radius >= 1 && radius <= DSM_MAX_RADIUS, "radius=%d outside 1..%d", radius, DSM_MAX_RADIUS);
+    const size_t bytes = (size_t)W * H * 4;
+    D3D_REQUIRE((uintptr_t)in + bytes <= (uintptr_t)out || (uintptr_t)out + bytes <= (uintptr_t)in,
+                "out must not alias in (one launch per iteration ping-pongs two rasters)");
+    const dim3 grid(ceil_div(W, DSM_FILL_TILE), ceil_div(H, DSM_FILL_TILE)), block(DSM_FILL_TILE, DSM_FILL_TILE);
+    D3D_REQUIRE(grid.y <= 65535, "H=%d too large", H);
+    hipLaunchKernelGGL(dsm_fill_kernel, grid, block, 0, (hipStream_t)stream, in, out, W, H, radius);
+    D3D_LAUNCH_CHECK("dsm_fill_kernel launch");
+    return D3D_OK;
+}

@@ -21,7 +21,7 @@ MODELS = ("casmvsnet", "ucsnet", "msrednet", "adamvs")  # mvs_dl.py:45
 class MVS_Inference:
     def __init__(self, max_w, max_h, view_num=5, num_depth=384, min_interval=0.1, model_type="adamvs",
                  pretrain_weight=None, display_depth=False, n_gpus=1, extra_args=(), save_normals=False, fuse_normals=False,
-                 normal_nei=1):
+                 normal_nei=1, dsm=None):
         self.max_w = max_w
         self.max_h = max_h
         self.view_num = view_num
@@ -36,6 +36,8 @@ class MVS_Inference:
         self.save_normals = bool(save_normals)
         self.fuse_normals = bool(fuse_normals)
         self.normal_nei = int(normal_nei)
+        # DSM from the fused points (predict --dsm ...; needs --fuse in extra_args): dsm_settings(config) plus "path", or None
+        self.dsm = dict(dsm) if dsm is not None else None
 
     def default_weight(self):
         """mvs_dl.py:46-58: the last *.ckpt under mvs/mvs_cas/checkpoints/<model>/whu_omvs, if that folder exists."""
@@ -66,6 +68,8 @@ class MVS_Inference:
             args.append("--fuse_normals")
         if self.normal_nei != 1:
             args.append("--normal_nei=%d" % self.normal_nei)
+        if self.dsm is not None:
+            args += dsm_flags(self.dsm)
         return args + self.extra_args
 
     def run(self, data_folder, mvs_path):
@@ -111,6 +115,45 @@ def fusion_settings(config):
             "normal_threshold": float(f.get("normal_threshold", 90.0)), "pc_format": f.get("pc_format", "ply"),
             # not in the reference's config.yaml: normals estimated from the depth maps (predict --fuse_normals), off by default
             "estimate_normals": bool(f.get("estimate_normals", False)), "normal_nei": int(f.get("normal_nei", 1))}
+
+
+def dsm_settings(config):
+    """The CREATEDSM block of config.yaml (run.py:120-128, 209-247) as DSM settings (dsm.build_and_write without "path").
+    dsm_source "mesh" raises as the reference does for a source it lacks: meshing is out of scope here.  Robust_Max's trim,
+    min_points, the MovingAverage radius / iterations and nodata are not in the reference's config: read when present."""
+    d = config["CREATEDSM"] if "CREATEDSM" in config else config
+    source = d.get("dsm_source", "pc")
+    if source != "pc":
+        raise Exception("dsm source: {}? Not implemented yet!".format(source))
+    interp = d.get("pc_interpolation_method")
+    size = d.get("dsm_size")
+    return {"run_create_dsm": bool(d.get("run_create_dsm", True)), "border": d.get("bbx_border_dsm"),
+            "unit": list(d.get("dsm_uint") or [0.1, 0.1]),   # run.py:218
+            "size": list(size) if size is not None else None, "select": d.get("pc_select_method", "Max"),
+            "trim": float(d.get("trim", 0.1)), "min_points": int(d.get("min_points", 1)),
+            "interpolation": None if interp in (None, "none") else interp, "radius": int(d.get("radius", 2)),
+            "iterations": int(d.get("iterations", 1)), "nodata": float(d.get("nodata", -9999.0))}
+
+
+def dsm_flags(s):
+    """predict's --dsm flags for DSM settings s (dsm_settings + "path"); settings at their default are not formatted."""
+    join = lambda v: ",".join(repr(float(x)) for x in v)
+    if not s.get("path"):
+        raise ValueError("DSM settings need a 'path' (the .tif to write)")
+    if s.get("border") is None:
+        raise ValueError("DSM settings need a 'border' (bbx_border_dsm; scene_border.txt is not read here)")
+    args = ["--dsm=%s" % s["path"], "--dsm_border=%s" % join(s["border"])]
+    if s.get("unit") is not None:
+        args.append("--dsm_unit=%s" % join(s["unit"]))
+    if s.get("size") is not None:
+        args.append("--dsm_size=%s" % ",".join(str(int(x)) for x in s["size"]))
+    defaults = (("select", "Max", "%s"), ("trim", 0.1, "%r"), ("min_points", 1, "%d"), ("interpolation", None, "%s"),
+                ("radius", 2, "%d"), ("iterations", 1, "%d"), ("nodata", -9999.0, "%r"))
+    for key, default, fmt in defaults:
+        v = s.get(key, default)
+        if v is not None and v != default:
+            args.append(("--dsm_%s=" + fmt) % (key, v))
+    return args
 
 
 def fusion_checker(config):

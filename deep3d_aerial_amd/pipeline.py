@@ -68,7 +68,7 @@ def _gather_objects(obj, world_size):
 def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checker=None, fusion_num=10, min_geo_consist_num=4,
                      filter_sources=True, partition="block", scene_range=None, skip_line=2, feature_cache_bytes=0,
                      device="cuda", timings=None, display=False, fuse_partition="views", scene_blocks=None,
-                     estimate_normals=False, normal_nei=1, save_normals=False):
+                     estimate_normals=False, normal_nei=1, save_normals=False, dsm=None):
     """Runs the three steps above for this rank.  Returns a list, one entry per reference view this rank owns, of
     {"ref", "final_mask" [H,W] bool, "avg_xyz_world" [3,H,W], "points": fuse.extract_points(...) dict} (device tensors).
     timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s.
@@ -77,7 +77,10 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     of the default (0, 0, -1).  They are computed after the all-gather (the exchange is unchanged), from the unfiltered
     gathered maps (the reference reads them from depth_path, not from its tmp folder), once per view this rank's fusion
     touches; normals follow the view, so the fused arrays do not depend on the number of ranks any more than without them.
-    save_normals: predict_views also writes {name}_normal.pfm."""
+    save_normals: predict_views also writes {name}_normal.pfm.
+    dsm: None (nothing changes), or the DSM settings {"path", "border", "unit", "size", "select", "trim", "min_points",
+    "interpolation", "radius", "iterations", "nodata"} (dsm.build_and_write): the xyz of every result of this rank are
+    concatenated, gathered on rank 0 (sharding.gather_points) and the DSM is built and written there; timings gets dsm_s."""
     if checker is None:
         checker = fuse.ConsistencyChecker(1.0, 0.01, 90.0, 0.2)   # Fuse_Depth_Map's defaults (fusion_3d_normal.py:56-57)
     n = len(dataset)
@@ -159,7 +162,25 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         timings.update(views=len(mine), predict_s=t1 - t0, allgather_ms=(g1 - g0) * 1e3,
                        allgather_bytes=int(all_maps.numel() * 4), fuse_s=t2 - g1, map_size=(H, W),
                        backend=dist.get_backend() if world_size > 1 else "none")
+    if dsm is not None:
+        write_dsm_of(out, dsm, rank, world_size, xyz_device=all_maps.device, timings=timings)
     return out
+
+
+def write_dsm_of(results, settings, rank=0, world_size=1, xyz_device="cuda", timings=None):
+    """The DSM of the points of `results` (predict_and_fuse's list) over all ranks, written by rank 0 (dsm.build_and_write).
+    Every rank must call it.  Returns (height, count) on rank 0, None elsewhere."""
+    from . import dsm as _dsm
+
+    t0 = time.perf_counter()
+    parts = [r["points"]["xyz"] for r in results]
+    local = torch.cat(parts) if parts else torch.zeros((0, 3), dtype=torch.float32, device=xyz_device)
+    pts = sharding.gather_points(local.to(torch.float32).contiguous(), rank, world_size)
+    res = _dsm.build_and_write(pts, settings, device=local.device) if rank == 0 else None
+    torch.cuda.synchronize()
+    if timings is not None:
+        timings["dsm_s"] = time.perf_counter() - t0
+    return res
 
 
 def add_estimated_normals(views, pairs, fusion_num=10, nei=1):

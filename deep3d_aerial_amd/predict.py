@@ -461,7 +461,7 @@ def _truthy(text):
 
 def parse_args(argv=None):
     """Every flag of the reference's harness (predict.py:30-58) with its default, plus --synthetic_items /
-    --random_weights / --feature_cache_gb, the --fuse flags and the normal-map flags of this package."""
+    --random_weights / --feature_cache_gb, the --fuse flags, the normal-map flags and the --dsm flags of this package."""
     ap = argparse.ArgumentParser(description="plane-sweep depth inference (predict.py-compatible flags)")
     ap.add_argument("--model", default="adamvs", help="casmvsnet | msrednet | adamvs | ucsnet")
     ap.add_argument("--dataset", default="cas_normal_eval", help="dataset class (only the inference dataset exists here)")
@@ -511,7 +511,17 @@ def parse_args(argv=None):
     ap.add_argument("--fuse_normals", action="store_true",
                     help="with --fuse: estimate every fused view's normals from its gathered depth map instead of the default (0, 0, -1)")
     ap.add_argument("--normal_nei", type=int, default=1, help="stencil step of the normal estimate (compute_normals.py forward: 1)")
-    return ap.parse_args(argv)
+    # DSM from the fused points (run.py:209-247 CREATEDSM with dsm_source "pc"; deep3d_aerial_amd/dsm.py): off by default
+    from . import dsm as _dsm
+
+    ap.add_argument("--dsm", default=None, help="with --fuse: write the DSM of all ranks' fused points to this .tif (+ .tfw), on rank 0")
+    _dsm.add_arguments(ap, prefix="dsm_")
+    a = ap.parse_args(argv)
+    if a.dsm is not None and not a.fuse:
+        ap.error("--dsm needs --fuse (the DSM is built from the fused points)")
+    if a.dsm is not None and a.dsm_border is None:
+        ap.error("--dsm needs --dsm_border Xmin,Xmax,Ymin,Ymax[,Zmin,Zmax]")
+    return a
 
 
 def _display_backend():
@@ -535,6 +545,12 @@ def write_display_maps(output_folder, name, depth, prob):
     img[bad] = np.broadcast_to(colmin - 1, img.shape)[bad]
     plt.imsave(os.path.join(output_folder, "color", "%s_init.png" % name), img, format="png")
     plt.imsave(os.path.join(output_folder, "color", "%s_prob.png" % name), np.nan_to_num(prob).clip(0, 1), format="png")
+
+
+def _dsm_settings(a):
+    from . import dsm as _dsm
+
+    return _dsm.settings_from_args(a, a.dsm, prefix="dsm_")
 
 
 def main(argv=None):
@@ -583,8 +599,11 @@ def main(argv=None):
                                         min_geo_consist_num=a.geo_consist_num, filter_sources=bool(a.fuse_filter_sources),
                                         partition=a.partition, feature_cache_bytes=cache_bytes, timings=tm, display=_truthy(a.display),
                                         fuse_partition=a.fuse_partition, scene_blocks=blocks, estimate_normals=a.fuse_normals,
-                                        normal_nei=a.normal_nei, save_normals=a.save_normals)
+                                        normal_nei=a.normal_nei, save_normals=a.save_normals,
+                                        dsm=_dsm_settings(a) if a.dsm is not None else None)
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
+        if a.dsm is not None and rank == 0:
+            print("rank 0/%d: DSM %s in %.2f s" % (world, a.dsm, tm["dsm_s"]))
         print("rank %d/%d: %d views in %.2f s, all-gather of %.1f MB in %.2f ms (%s), fusion of its %d reference views %.2f s, "
               "%d vertices" % (rank, world, tm["views"], tm["predict_s"], tm["allgather_bytes"] / 1e6, tm["allgather_ms"], tm["backend"],
                                len(res), tm["fuse_s"], sum(int(r["points"]["xyz"].shape[0]) for r in res)))

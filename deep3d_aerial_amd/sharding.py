@@ -112,6 +112,40 @@ def all_gather_maps(local_maps, n_views, rank=None, world_size=None, policy="blo
     return out
 
 
+def gather_points(xyz_local, rank=None, world_size=None):
+    """All ranks' points [n_r, 3] on rank 0, in rank order (the DSM is built there, pipeline.predict_and_fuse(dsm=...)).
+
+    The counts go to every rank first (all_gather_object, as pipeline._gather_objects does for the map shapes), then ONE
+    padded all_gather moves the points -- through host memory when ranks share a card over gloo, as in all_gather_maps.
+    Returns the [sum n_r, 3] tensor on rank 0 (on xyz_local's device) and None on the other ranks."""
+    if world_size is None:
+        world_size = dist.get_world_size() if dist.is_initialized() else 1
+    if rank is None:
+        rank = dist.get_rank() if dist.is_initialized() else 0
+    if xyz_local.dim() != 2:
+        raise ValueError("xyz_local must be [n, C] (got %s)" % (tuple(xyz_local.shape),))
+    if world_size == 1:
+        return xyz_local
+    counts = [None] * world_size
+    dist.all_gather_object(counts, int(xyz_local.shape[0]))
+    per = max(counts)
+    if per == 0:
+        return xyz_local[:0] if rank == 0 else None
+    padded = xyz_local.new_zeros((per,) + tuple(xyz_local.shape[1:]))
+    padded[: xyz_local.shape[0]] = xyz_local
+    if dist.get_backend() == "gloo" and padded.is_cuda:
+        host = padded.cpu()
+        gathered = host.new_empty((world_size * per,) + tuple(host.shape[1:]))
+        dist.all_gather_into_tensor(gathered, host.contiguous())
+    else:
+        gathered = padded.new_empty((world_size * per,) + tuple(padded.shape[1:]))
+        dist.all_gather_into_tensor(gathered, padded.contiguous())
+    if rank != 0:
+        return None
+    out = torch.cat([gathered[r * per: r * per + counts[r]] for r in range(world_size)])
+    return out.to(xyz_local.device).contiguous()
+
+
 def run_sharded(process_view, n_views, rank=None, world_size=None, gather=False, policy="block"):
     """Sweep this rank's views with `process_view(i) -> tensor [2,H,W]` (depth, confidence).
 

@@ -824,6 +824,33 @@ int d3d_center_image_u8(const unsigned char* img, int h, int w, int channels, in
 int d3d_normals_from_depth(const float* depth, const float* kinv, int B, int H, int W, int nei, float* normal,
                            float* encoded, d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.8 -- digital surface model from a point cloud: the product of the reference's CREATEDSM step with
+ * dsm_source "pc" (run.py:209-247 calls pc2dsm.DSM_from_PC, which the reference never shipped; the semantics are this
+ * project's, deep3d_aerial_amd/dsm.py).
+ *   xyz [n_points,3] fp32 (device), n_points < 2^31; a W x H raster, W * H < 2^31, row 0 north: the cell of a point is
+ *   j = floor((x - x_min) / unit_x), i = floor((y_max - y) / unit_y), in fp64 with IEEE division.  A point is kept when
+ *   x, y, z are finite, 0 <= i < H, 0 <= j < W and z_min <= z <= z_max (pass -inf / +inf for no height bounds).
+ *   count [H,W] int32: the kept points per cell.  height [H,W] fp32: NaN where count < max(min_points, 1), else
+ *   select 0 (Max): the largest z; select 1 (Robust_Max): with the cell's n heights in descending IEEE total order
+ *   (-0.0 < +0.0), the (t+1)-th, t = floor(trim * n) (fp64), trim in [0, 1).
+ *   scratch: device memory of d3d_dsm_scratch_bytes(n_points, W, H, select) bytes (0 for an out-of-range argument).
+ *   Integer atomics and fixed-order selection only: the rasters are bit-identical for any order or split of the points.
+ */
+size_t d3d_dsm_scratch_bytes(long long n_points, int W, int H, int select);
+int d3d_dsm_from_points(const float* xyz, long long n_points, double x_min, double y_max, double unit_x, double unit_y,
+                        double z_min, double z_max, int W, int H, int select, double trim, int min_points, void* scratch,
+                        size_t scratch_bytes, float* height, int* count, d3d_stream_t stream);
+
+/*
+ * DESIGN.md §4.8 -- the MovingAverage hole fill of a DSM raster (pc_interpolation_method), one pass:
+ *   out = in where in is not NaN; a NaN cell gets the mean of the non-NaN cells of the (2 radius + 1)^2 window around it,
+ *   clipped to the raster, summed in fp64 in the order dy = -radius..radius (outer), dx = -radius..radius (inner), divided
+ *   by their number and rounded once to fp32; NaN when the window holds none.  radius in 1..16; in and out [H,W] fp32
+ *   (device), not overlapping.  Iterations are repeated calls, each reading the previous output.
+ */
+int d3d_dsm_fill_moving_average(const float* in, float* out, int W, int H, int radius, d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
