@@ -82,6 +82,20 @@ class DsmGrid(object):
         ux, uy = self.unit
         return str(ux) + "\n0\n0\n" + str(-uy) + "\n" + str(self.border[0]) + "\n" + str(self.border[3])
 
+    def _raster(self):
+        return (self.x_min, self.y_max, self.unit, self.width, self.height)
+
+    def __eq__(self, other):
+        """Equal rasters: the same origin (Xmin, Ymax), unit and size -- every cell and the .tfw agree.  The Z bounds only
+        filter points and are not compared."""
+        return isinstance(other, DsmGrid) and self._raster() == other._raster()
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self._raster())
+
     def __repr__(self):
         return "DsmGrid(border=%s, unit=%s, size=(%d, %d))" % (self.border, self.unit, self.width, self.height)
 
@@ -187,15 +201,25 @@ def tiff_bytes(height_map, grid, nodata=-9999.0):
     nodata_txt = _nodata_text(nodata).encode("ascii") + b"\0"
     row_bytes = 4 * W
     counts = [row_bytes * min(rps, H - k * rps) for k in range(n_strips)]
-    # GeoKeyDirectory: version 1.1.0, one key: GTRasterTypeGeoKey (1025) = RasterPixelIsArea (1); no CRS keys
-    geokeys = [1, 1, 0, 1, 1025, 0, 1, 1]
     tags = [(256, _LONG, [W]), (257, _LONG, [H]), (258, _SHORT, [32]), (259, _SHORT, [1]), (262, _SHORT, [1]),
             (273, _LONG, [0] * n_strips), (277, _SHORT, [1]), (278, _LONG, [rps]), (279, _LONG, counts), (284, _SHORT, [1]),
-            (339, _SHORT, [3]),
-            (33550, _DOUBLE, [grid.unit[0], grid.unit[1], 0.0]),                       # ModelPixelScaleTag
+            (339, _SHORT, [3])] + geo_tags(grid) + [(42113, _ASCII, nodata_txt)]                # GDAL_NODATA
+    return assemble_tiff(tags, counts, data.tobytes())
+
+
+def geo_tags(grid):
+    """The GeoTIFF tags of a raster on `grid`: pixel scale, tie point and a GeoKeyDirectory with PixelIsArea and no CRS."""
+    # GeoKeyDirectory: version 1.1.0, one key: GTRasterTypeGeoKey (1025) = RasterPixelIsArea (1); no CRS keys
+    geokeys = [1, 1, 0, 1, 1025, 0, 1, 1]
+    return [(33550, _DOUBLE, [grid.unit[0], grid.unit[1], 0.0]),                       # ModelPixelScaleTag
             (33922, _DOUBLE, [0.0, 0.0, 0.0, grid.border[0], grid.border[3], 0.0]),     # ModelTiepointTag: pixel (0, 0) -> (Xmin, Ymax)
-            (34735, _SHORT, geokeys),                                                   # GeoKeyDirectoryTag
-            (42113, _ASCII, nodata_txt)]                                                # GDAL_NODATA
+            (34735, _SHORT, geokeys)]                                                   # GeoKeyDirectoryTag
+
+
+def assemble_tiff(tags, counts, pixels):
+    """A little-endian classic TIFF: header, one IFD of `tags` [(tag, type, values)] in ascending tag order (StripOffsets, 273,
+    is filled in here), the tag data that does not fit an entry, then the strips of `counts` bytes each (`pixels`)."""
+    n_strips = len(counts)
     ifd_at = 8
     extra_at = ifd_at + 2 + 12 * len(tags) + 4
     blobs, entries, at = [], [], extra_at
@@ -220,7 +244,7 @@ def tiff_bytes(height_map, grid, nodata=-9999.0):
             at += len(blobs[-1])
     assert at == pixels_at
     head = b"II" + struct.pack("<HI", 42, ifd_at) + struct.pack("<H", len(tags)) + b"".join(entries) + struct.pack("<I", 0)
-    return head + b"".join(blobs) + data.tobytes()
+    return head + b"".join(blobs) + pixels
 
 
 def write_dsm(path, height, grid, nodata=-9999.0):
@@ -246,6 +270,66 @@ def write_dsm(path, height, grid, nodata=-9999.0):
     with open(tfw, "w") as f:
         f.write(grid.tfw_text())
     return str(path), tfw
+
+
+def _ifd(blob, what):
+    """{tag: values} of the first IFD of a little-endian classic TIFF (the layout tiff_bytes writes), else ValueError."""
+    if len(blob) < 8 or blob[:4] != b"II*\0":
+        raise ValueError("%s: not a little-endian classic TIFF (BigTIFF and big-endian files are not read)" % what)
+    ifd_at = struct.unpack_from("<I", blob, 4)[0]
+    if ifd_at + 2 > len(blob):
+        raise ValueError("%s: truncated TIFF" % what)
+    n = struct.unpack_from("<H", blob, ifd_at)[0]
+    if ifd_at + 2 + 12 * n > len(blob):
+        raise ValueError("%s: truncated TIFF" % what)
+    tags = {}
+    for k in range(n):
+        tag, typ, count = struct.unpack_from("<HHI", blob, ifd_at + 2 + 12 * k)
+        if typ not in _TYPE_SIZE:
+            raise ValueError("%s: tag %d has TIFF type %d, which this reader does not take" % (what, tag, typ))
+        size = count * _TYPE_SIZE[typ]
+        at = ifd_at + 2 + 12 * k + 8 if size <= 4 else struct.unpack_from("<I", blob, ifd_at + 2 + 12 * k + 8)[0]
+        if at + size > len(blob):
+            raise ValueError("%s: truncated TIFF (tag %d)" % (what, tag))
+        tags[tag] = blob[at:at + size] if typ == _ASCII else list(struct.unpack_from("<%d%s" % (count, _TYPE_FMT[typ]), blob, at))
+    return tags
+
+
+def read_dsm(path):
+    """A DSM file this project wrote (write_dsm) -> (height [H,W] float32 host array with NaN where the file holds its
+    GDAL_NODATA value, DsmGrid).  The grid comes from the size, the pixel scale and the tie point: border
+    [Xmin, Xmin + W ux, Ymax - H uy, Ymax], unit (ux, uy), size (W, H).  Any other TIFF layout (compression, tiles, several
+    bands, another sample type, no georeferencing) is refused with a ValueError."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    t = _ifd(blob, path)
+    want = {258: [32], 259: [1], 277: [1], 339: [3]}
+    for tag, v in want.items():
+        if t.get(tag, [1] if tag == 277 else None) != v:
+            raise ValueError("%s: not a DSM file of this project (tag %d is %s, expected %s: one uncompressed float32 band)"
+                             % (path, tag, t.get(tag), v))
+    if t.get(284, [1]) != [1] or 322 in t:
+        raise ValueError("%s: tiled or planar-separate TIFFs are not read" % path)
+    for tag, name in ((256, "ImageWidth"), (257, "ImageLength"), (273, "StripOffsets"), (279, "StripByteCounts"),
+                      (33550, "ModelPixelScale"), (33922, "ModelTiepoint")):
+        if tag not in t:
+            raise ValueError("%s: no %s tag: not a DSM file of this project" % (path, name))
+    W, H = int(t[256][0]), int(t[257][0])
+    scale, tie = t[33550], t[33922]
+    if len(scale) < 2 or len(tie) < 6 or tie[:3] != [0.0, 0.0, 0.0]:
+        raise ValueError("%s: the tie point must map pixel (0, 0); got %s" % (path, tie))
+    offsets, counts = t[273], t[279]
+    if len(offsets) != len(counts) or sum(counts) != 4 * W * H or any(o + c > len(blob) for o, c in zip(offsets, counts)):
+        raise ValueError("%s: the strips do not hold %d x %d float32 values" % (path, W, H))
+    data = b"".join(blob[o:o + c] for o, c in zip(offsets, counts))
+    height = np.frombuffer(data, dtype="<f4").reshape(H, W).astype(np.float32)
+    if 42113 in t:
+        nodata = np.float32(float(t[42113].rstrip(b"\0").decode("ascii")))
+        height = np.where(height == nodata, np.float32(np.nan), height).astype(np.float32)
+    ux, uy = float(scale[0]), float(scale[1])
+    x_min, y_max = float(tie[3]), float(tie[4])
+    grid = DsmGrid([x_min, x_min + W * ux, y_max - H * uy, y_max], [ux, uy], size=(W, H))
+    return height, grid
 
 
 def load_fused_xyz(folder):

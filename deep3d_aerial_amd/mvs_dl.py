@@ -21,7 +21,7 @@ MODELS = ("casmvsnet", "ucsnet", "msrednet", "adamvs")  # mvs_dl.py:45
 class MVS_Inference:
     def __init__(self, max_w, max_h, view_num=5, num_depth=384, min_interval=0.1, model_type="adamvs",
                  pretrain_weight=None, display_depth=False, n_gpus=1, extra_args=(), save_normals=False, fuse_normals=False,
-                 normal_nei=1, dsm=None):
+                 normal_nei=1, dsm=None, ortho=None):
         self.max_w = max_w
         self.max_h = max_h
         self.view_num = view_num
@@ -38,6 +38,8 @@ class MVS_Inference:
         self.normal_nei = int(normal_nei)
         # DSM from the fused points (predict --dsm ...; needs --fuse in extra_args): dsm_settings(config) plus "path", or None
         self.dsm = dict(dsm) if dsm is not None else None
+        # true orthophoto on that DSM (predict --ortho ...; needs dsm): {"path", "depth_tolerance", "views_per_batch"}, or None
+        self.ortho = dict(ortho) if ortho is not None else None
 
     def default_weight(self):
         """mvs_dl.py:46-58: the last *.ckpt under mvs/mvs_cas/checkpoints/<model>/whu_omvs, if that folder exists."""
@@ -70,6 +72,10 @@ class MVS_Inference:
             args.append("--normal_nei=%d" % self.normal_nei)
         if self.dsm is not None:
             args += dsm_flags(self.dsm)
+        if self.ortho is not None:
+            if self.dsm is None:
+                raise ValueError("ortho settings need dsm settings: the orthophoto is draped on the DSM")
+            args += ortho_flags(self.ortho)
         return args + self.extra_args
 
     def run(self, data_folder, mvs_path):
@@ -153,6 +159,20 @@ def dsm_flags(s):
         v = s.get(key, default)
         if v is not None and v != default:
             args.append(("--dsm_%s=" + fmt) % (key, v))
+    return args
+
+
+def ortho_flags(s):
+    """predict's --ortho flags for orthophoto settings s {"path", "depth_tolerance", "views_per_batch"}; settings at their
+    default are not formatted."""
+    if not s.get("path"):
+        raise ValueError("orthophoto settings need a 'path' (the .tif to write)")
+    args = ["--ortho=%s" % s["path"]]
+    tol = s.get("depth_tolerance")
+    if tol is not None and float(tol) != 0.01:
+        args.append("--ortho_depth_tolerance=%r" % float(tol))
+    if s.get("views_per_batch") is not None:
+        args.append("--ortho_views_per_batch=%d" % int(s["views_per_batch"]))
     return args
 
 

@@ -68,7 +68,7 @@ def _gather_objects(obj, world_size):
 def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checker=None, fusion_num=10, min_geo_consist_num=4,
                      filter_sources=True, partition="block", scene_range=None, skip_line=2, feature_cache_bytes=0,
                      device="cuda", timings=None, display=False, fuse_partition="views", scene_blocks=None,
-                     estimate_normals=False, normal_nei=1, save_normals=False, dsm=None):
+                     estimate_normals=False, normal_nei=1, save_normals=False, dsm=None, ortho=None):
     """Runs the three steps above for this rank.  Returns a list, one entry per reference view this rank owns, of
     {"ref", "final_mask" [H,W] bool, "avg_xyz_world" [3,H,W], "points": fuse.extract_points(...) dict} (device tensors).
     timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s.
@@ -80,17 +80,28 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     save_normals: predict_views also writes {name}_normal.pfm.
     dsm: None (nothing changes), or the DSM settings {"path", "border", "unit", "size", "select", "trim", "min_points",
     "interpolation", "radius", "iterations", "nodata"} (dsm.build_and_write): the xyz of every result of this rank are
-    concatenated, gathered on rank 0 (sharding.gather_points) and the DSM is built and written there; timings gets dsm_s."""
+    concatenated, gathered on rank 0 (sharding.gather_points) and the DSM is built and written there; timings gets dsm_s.
+    ortho: None (nothing changes), or the orthophoto settings {"path", "depth_tolerance", "views_per_batch"} (needs dsm): the
+    true orthophoto on that DSM (write_ortho_of) from the views' gathered depth maps, cameras and reference images; rank 0
+    writes it; timings gets ortho_s."""
+    if ortho is not None:
+        from . import ortho as _ortho
+
+        if dsm is None:
+            raise ValueError("ortho needs dsm: the orthophoto is draped on the DSM")
+        _ortho.check_tolerance(ortho.get("depth_tolerance", _ortho.DEFAULT_TOLERANCE))
+        _ortho.check_views_per_batch(ortho.get("views_per_batch"))
     if checker is None:
         checker = fuse.ConsistencyChecker(1.0, 0.01, 90.0, 0.2)   # Fuse_Depth_Map's defaults (fusion_3d_normal.py:56-57)
     n = len(dataset)
     recs = view_records(dataset, fusion_num)
     mine = sharding.shard_views(n, rank, world_size, partition)
     cams = {}
+    images = {} if ortho is not None else None
     t0 = time.perf_counter()
     maps = predict.predict_views(model, dataset, output_folder, rank, world_size, device=device, keep_maps=True,
                                  feature_cache_bytes=feature_cache_bytes, display=display, partition=partition, cams=cams,
-                                 save_normals=save_normals, normal_nei=normal_nei)
+                                 save_normals=save_normals, normal_nei=normal_nei, images=images)
     names = [recs[i]["name"] for i in mine]
     if list(maps.keys()) != names:
         raise RuntimeError("the views predict_views produced %s are not this rank's %s" % (list(maps.keys()), names))
@@ -163,8 +174,52 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
                        allgather_bytes=int(all_maps.numel() * 4), fuse_s=t2 - g1, map_size=(H, W),
                        backend=dist.get_backend() if world_size > 1 else "none")
     if dsm is not None:
-        write_dsm_of(out, dsm, rank, world_size, xyz_device=all_maps.device, timings=timings)
+        built = write_dsm_of(out, dsm, rank, world_size, xyz_device=all_maps.device, timings=timings)
+        if ortho is not None:
+            own = [(images[recs[i]["name"]][0], all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], images[recs[i]["name"]][1])
+                   for i in mine]
+            write_ortho_of(built[0] if built is not None else None, dsm, ortho, own, rank, world_size, device=all_maps.device,
+                           timings=timings)
     return out
+
+
+def write_ortho_of(height, dsm_settings, settings, views, rank=0, world_size=1, device="cuda", timings=None):
+    """The true orthophoto on the DSM `height` (rank 0's raster; None elsewhere) of every rank's views, written by rank 0
+    (ortho.write_ortho).  views: this rank's [(id, K, E, depth [H,W], image)].  Every rank must call it.
+    Rank 0 broadcasts the raster; each rank selects over its own views (ortho.select_views); one all_reduce(MIN) of the keys;
+    each rank colours its own winners; one all_reduce(SUM) of the packed RGBA raster and of id + 1 (0 where the rank has no
+    winner: one rank contributes per cell).  The exchange is O(raster) whatever the number of views.
+    Returns (rgba, view, key) on rank 0, None elsewhere."""
+    from . import dsm as _dsm, ortho as _ortho
+
+    t0 = time.perf_counter()
+    grid = _dsm.DsmGrid(dsm_settings["border"], dsm_settings.get("unit") or (0.1, 0.1), dsm_settings.get("size"))
+    if rank == 0:
+        h = height.to(device=device, dtype=torch.float32).contiguous()
+    else:
+        h = torch.empty(grid.shape, dtype=torch.float32, device=device)
+    if world_size > 1:
+        sharding.broadcast_raster(h, 0)
+    ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in views]
+    tol = settings.get("depth_tolerance", _ortho.DEFAULT_TOLERANCE)
+    vpb = settings.get("views_per_batch")
+    key = _ortho.select_views(h, grid, ov, tol, views_per_batch=vpb)
+    if world_size > 1:
+        sharding.all_reduce_raster(key, dist.ReduceOp.MIN)
+    rgba, view = _ortho.colorize(key, h, grid, ov, views_per_batch=vpb)
+    if world_size > 1:
+        both = torch.stack([rgba.view(torch.int32)[:, :, 0], view + 1])
+        sharding.all_reduce_raster(both, dist.ReduceOp.SUM)
+        rgba = both[0].contiguous().view(torch.uint8).reshape(grid.height, grid.width, 4)
+        view = both[1] - 1
+    res = None
+    if rank == 0:
+        _ortho.write_ortho(settings["path"], rgba, grid)
+        res = (rgba, view, key)
+    torch.cuda.synchronize()
+    if timings is not None:
+        timings["ortho_s"] = time.perf_counter() - t0
+    return res
 
 
 def write_dsm_of(results, settings, rank=0, world_size=1, xyz_device="cuda", timings=None):

@@ -225,6 +225,31 @@ def write_red_cam(file, cam, location, ref_path):
         f.write(str(ref_path) + "\n")
 
 
+def read_red_cam(file):
+    """The inverse of write_red_cam: (cam [2,4,4] float32, location [the words before the path], ref_path).  Every number
+    write_red_cam wrote is str(float32), which reads back exactly.  The location is the item's four `outlocation` words
+    (W, H, image id, name); the rest of the line is the path."""
+    with open(file) as f:
+        lines = f.read().split("\n")
+    if not lines or not lines[0].startswith("extrinsic"):
+        raise ValueError("%s: not a camera file write_red_cam wrote" % file)
+    cam = np.zeros((2, 4, 4), np.float32)
+    try:
+        for i in range(4):
+            cam[0, i] = [np.float32(x) for x in lines[1 + i].split()]
+        if lines[6].strip() != "intrinsic":
+            raise ValueError("no intrinsic block")
+        for i in range(3):
+            cam[1, i, :3] = [np.float32(x) for x in lines[7 + i].split()]
+        cam[1, 3] = [np.float32(x) for x in lines[11].split()]
+        words = lines[13].rstrip("\n").split(" ", 4)
+    except (IndexError, ValueError) as e:
+        raise ValueError("%s: not a camera file write_red_cam wrote (%s)" % (file, e))
+    if len(words) < 5:
+        raise ValueError("%s: the last line needs four location words and the image path" % file)
+    return cam, words[:4], words[4]
+
+
 # ----------------------------------------------------------------------------------------
 # model switch (predict.py:71-97) and checkpoint loading (predict.py:105-106)
 # ----------------------------------------------------------------------------------------
@@ -371,7 +396,7 @@ def _item_views(s, model, device):
 # ----------------------------------------------------------------------------------------
 def predict_views(model, dataset, output_folder, rank=0, world_size=1, device="cuda", keep_maps=False,
                   feature_cache_bytes=0, display=False, partition="block", stats=None, cams=None, save_normals=False,
-                  normal_nei=1):
+                  normal_nei=1, images=None):
     """Returns the names of the views this rank produced; with keep_maps=True a dict name -> (depth, confidence)
     of device tensors instead, so the fusion step (fuse.ViewFusion) can start without re-reading the PFM files.
     feature_cache_bytes > 0 keeps the feature pyramids of that many bytes of images resident across views (items must
@@ -382,7 +407,10 @@ def predict_views(model, dataset, output_folder, rank=0, world_size=1, device="c
     fusion step that follows in the same process (pipeline.predict_and_fuse).
     save_normals: also write {name}_normal.pfm -- the camera-space normals of the final depth map (ops.normals_from_depth
     with the view's output intrinsics outcam[1][:3,:3] and stencil step normal_nei) encoded as (n + 1) / 2, the file the
-    reference's fusion step reads (fusion_3d_normal.py:437-443, 191-195)."""
+    reference's fusion step reads (fusion_3d_normal.py:437-443, 191-195).
+    images: a dict that receives name -> (id, image) for the orthophoto step (pipeline.predict_and_fuse(ortho=...)): the id is
+    the item's outlocation[2], the image its reference crop as a device uint8 [H,W,C] tensor -- images_u8[0] cut by
+    crop_windows[0] for device items, outimage for items in the reference's layout.  An item with neither raises."""
     from .dataset import FeatureCache
 
     os.makedirs(output_folder, exist_ok=True)
@@ -432,6 +460,8 @@ def predict_views(model, dataset, output_folder, rank=0, world_size=1, device="c
                               s["ref_image_path"])
                 if cams is not None:
                     cams[name] = np.array(s["outcam"], dtype=np.float32)
+                if images is not None:
+                    images[name] = (int(s["outlocation"][2]), reference_crop(s, device))
                 if keep_maps:
                     done[name] = (depth, prob)
                 else:
@@ -450,6 +480,23 @@ def predict_views(model, dataset, output_folder, rank=0, world_size=1, device="c
         if feature_cache_bytes > 0:
             model.feature_cache = None
     return done
+
+
+def reference_crop(s, device):
+    """The reference view's 8-bit crop of item s on the device: images_u8[0] cut by crop_windows[0] (device items), else
+    outimage (the reference's layout).  Grey images come back [H,W,1]."""
+    if "images_u8" in s:
+        y0, x0, H, W = s["crop_windows"][0]
+        im = np.asarray(s["images_u8"][0])[y0:y0 + H, x0:x0 + W]
+    elif s.get("outimage") is not None:
+        im = np.asarray(s["outimage"])
+    else:
+        raise ValueError("item %s carries no image (images_u8 or outimage): the orthophoto needs it" % (s["outlocation"][3],))
+    if im.dtype != np.uint8:
+        raise TypeError("the reference image of %s is %s, not 8-bit" % (s["outlocation"][3], im.dtype))
+    if im.ndim == 2:
+        im = im[:, :, None]
+    return torch.from_numpy(np.ascontiguousarray(im)).to(device)
 
 
 def _truthy(text):
@@ -516,11 +563,22 @@ def parse_args(argv=None):
 
     ap.add_argument("--dsm", default=None, help="with --fuse: write the DSM of all ranks' fused points to this .tif (+ .tfw), on rank 0")
     _dsm.add_arguments(ap, prefix="dsm_")
+    # true orthophoto on the DSM (deep3d_aerial_amd/ortho.py): off by default
+    from . import ortho as _ortho
+
+    ap.add_argument("--ortho", default=None, help="with --fuse --dsm: write the true orthophoto on the DSM to this .tif (+ .tfw), on rank 0")
+    _ortho.add_arguments(ap, prefix="ortho_")
     a = ap.parse_args(argv)
     if a.dsm is not None and not a.fuse:
         ap.error("--dsm needs --fuse (the DSM is built from the fused points)")
     if a.dsm is not None and a.dsm_border is None:
         ap.error("--dsm needs --dsm_border Xmin,Xmax,Ymin,Ymax[,Zmin,Zmax]")
+    if a.ortho is not None and not a.fuse:
+        ap.error("--ortho needs --fuse (the orthophoto is draped on the DSM of the fused points)")
+    if a.ortho is not None and a.dsm is None:
+        ap.error("--ortho needs --dsm (the orthophoto is draped on the DSM)")
+    if a.ortho is not None:
+        _ortho.check_args(ap, a, prefix="ortho_")
     return a
 
 
@@ -551,6 +609,12 @@ def _dsm_settings(a):
     from . import dsm as _dsm
 
     return _dsm.settings_from_args(a, a.dsm, prefix="dsm_")
+
+
+def _ortho_settings(a):
+    from . import ortho as _ortho
+
+    return _ortho.settings_from_args(a, a.ortho, prefix="ortho_")
 
 
 def main(argv=None):
@@ -600,10 +664,13 @@ def main(argv=None):
                                         partition=a.partition, feature_cache_bytes=cache_bytes, timings=tm, display=_truthy(a.display),
                                         fuse_partition=a.fuse_partition, scene_blocks=blocks, estimate_normals=a.fuse_normals,
                                         normal_nei=a.normal_nei, save_normals=a.save_normals,
-                                        dsm=_dsm_settings(a) if a.dsm is not None else None)
+                                        dsm=_dsm_settings(a) if a.dsm is not None else None,
+                                        ortho=_ortho_settings(a) if a.ortho is not None else None)
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
         if a.dsm is not None and rank == 0:
             print("rank 0/%d: DSM %s in %.2f s" % (world, a.dsm, tm["dsm_s"]))
+        if a.ortho is not None and rank == 0:
+            print("rank 0/%d: orthophoto %s in %.2f s" % (world, a.ortho, tm["ortho_s"]))
         print("rank %d/%d: %d views in %.2f s, all-gather of %.1f MB in %.2f ms (%s), fusion of its %d reference views %.2f s, "
               "%d vertices" % (rank, world, tm["views"], tm["predict_s"], tm["allgather_bytes"] / 1e6, tm["allgather_ms"], tm["backend"],
                                len(res), tm["fuse_s"], sum(int(r["points"]["xyz"].shape[0]) for r in res)))

@@ -146,6 +146,37 @@ def gather_points(xyz_local, rank=None, world_size=None):
     return out.to(xyz_local.device).contiguous()
 
 
+def _through_host(t):
+    return dist.get_backend() == "gloo" and t.is_cuda
+
+
+def broadcast_raster(t, src=0):
+    """dist.broadcast of t (in place) from rank src -- through host memory when ranks share a card over gloo, as in
+    all_gather_maps.  Every rank passes a tensor of the same shape and dtype.  Returns t."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return t
+    if _through_host(t):
+        host = t.cpu()
+        dist.broadcast(host, src)
+        t.copy_(host)
+    else:
+        dist.broadcast(t, src)
+    return t
+
+
+def all_reduce_raster(t, op):
+    """dist.all_reduce of t (in place) with op (dist.ReduceOp.MIN, SUM, ...), through host memory over gloo.  Returns t."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return t
+    if _through_host(t):
+        host = t.cpu()
+        dist.all_reduce(host, op)
+        t.copy_(host)
+    else:
+        dist.all_reduce(t, op)
+    return t
+
+
 def run_sharded(process_view, n_views, rank=None, world_size=None, gather=False, policy="block"):
     """Sweep this rank's views with `process_view(i) -> tensor [2,H,W]` (depth, confidence).
 

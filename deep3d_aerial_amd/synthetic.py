@@ -205,3 +205,54 @@ def make_fusion_scene(h, w, n_src=3, seed=0, noise=0.004, src_scale=1.0):
         s["depth"][rng.uniform(size=(hs, ws)) < 0.02] = 0.0
         srcs.append(s)
     return ref, srcs
+
+
+def make_ortho_scene(W, H, unit, n_views, view_w, view_h, seed=0, device="cuda", nan_share=0.01):
+    """A terrain DSM and n_views views over it for the orthophoto (tools/ortho_bench.py, tests/test_ortho_gpu.py), built on the
+    GPU.  Z points away from the cameras (they sit near z = 0, the ground near z = 100): the DSM is rolling ground with boxes
+    (roofs nearer the cameras) and a share of NaN cells; half the views are nadir, half oblique (tilted 0.3..0.6 rad).  A view's
+    depth map is its ray cast onto the plane z = 100 with 2 % holes, so cells above that plane pass the depth test and cells
+    more than 1 % below it do not; its image is random 8-bit RGB.
+    Returns (height [H,W] fp32, DsmGrid, [(id, K [3,3] fp32, E [4,4] fp32, depth [h,w] fp32, image [h,w,3] uint8)])."""
+    import torch
+
+    from .dsm import DsmGrid
+
+    rng = np.random.default_rng(seed)
+    grid = DsmGrid([0.0, W * unit, 0.0, H * unit], [unit, unit], size=(W, H))
+    x = (torch.arange(W, dtype=torch.float64, device=device) + 0.5) * unit
+    y = H * unit - (torch.arange(H, dtype=torch.float64, device=device) + 0.5) * unit
+    Y, X = torch.meshgrid(y, x, indexing="ij")
+    h = 100.0 + 3.0 * torch.sin(X / 37.0) + 2.5 * torch.cos(Y / 29.0)
+    for _ in range(max(4, W * H // 200000)):
+        cx, cy = rng.uniform(0, W * unit), rng.uniform(0, H * unit)
+        sx, sy, top = rng.uniform(4, 20), rng.uniform(4, 20), rng.uniform(70, 95)
+        h = torch.where((X - cx).abs().le(sx) & (Y - cy).abs().le(sy), torch.full_like(h, top), h)
+    h = h.float()
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    h[torch.rand((H, W), generator=gen, device=device) < nan_share] = float("nan")
+    f = 0.5 * view_w   # about 90 degrees across
+    K = np.array([[f, 0, (view_w - 1) / 2.0], [0, f, (view_h - 1) / 2.0], [0, 0, 1]], np.float64)
+    Kinv = torch.from_numpy(np.linalg.inv(K)).to(device)
+    ys, xs = torch.meshgrid(torch.arange(view_h, dtype=torch.float64, device=device),
+                            torch.arange(view_w, dtype=torch.float64, device=device), indexing="ij")
+    pix = torch.stack([xs, ys, torch.ones_like(xs)], -1)
+    views = []
+    for v in range(n_views):
+        C = np.array([rng.uniform(-0.1, 1.1) * W * unit, rng.uniform(-0.1, 1.1) * H * unit, rng.uniform(-5.0, 5.0)])
+        tilt, az = (0.0, 0.0) if v % 2 == 0 else (rng.uniform(0.3, 0.6), rng.uniform(0, 2 * np.pi))
+        ax, ay = tilt * np.cos(az), tilt * np.sin(az)
+        Rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+        Ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+        Rcw = (Ry @ Rx).T
+        E = np.eye(4)
+        E[:3, :3] = Rcw
+        E[:3, 3] = -Rcw @ C
+        dz = pix @ (Kinv.T @ torch.from_numpy(Rcw).to(device))[:, 2]   # world z of each camera ray (z_cam = 1)
+        lam = (100.0 - C[2]) / dz
+        depth = torch.where(lam > 0, lam, torch.zeros_like(lam)).float()
+        depth[torch.rand((view_h, view_w), generator=gen, device=device) < 0.02] = 0.0
+        image = torch.randint(0, 256, (view_h, view_w, 3), generator=gen, device=device, dtype=torch.uint8)
+        views.append((v, K.astype(np.float32), E.astype(np.float32), depth.contiguous(), image))
+    return h, grid, views

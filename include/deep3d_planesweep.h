@@ -851,6 +851,50 @@ int d3d_dsm_from_points(const float* xyz, long long n_points, double x_min, doub
  */
 int d3d_dsm_fill_moving_average(const float* in, float* out, int W, int H, int radius, d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.9 -- true orthophoto on the DSM (the reference has no orthophoto step; the semantics are this project's,
+ * deep3d_aerial_amd/ortho.py).  The grid is the DSM's: cell (i, j) is X = (x_min + (j + 0.5) unit_x, y_max - (i + 0.5) unit_y, h),
+ * h = height[i,j] in fp64; a non-finite h is an empty cell.  A view is one d3d_ortho_view_t record in DEVICE memory, filled by
+ * the caller: R [3,3] row-major and t of E = Tcw, K [3,3], C = -R^T t, all fp64; depth [H,W] fp32 and rgba [H,W] RGBA8 (R in
+ * the low byte, one texel one 4-byte load) of the same size; id in 0 .. 2^31 - 2.
+ * Projection in fp64 without contraction: p = R X + t, q = K p, each row summed left to right, u = q0 / q2, v = q1 / q2.
+ * The view is a candidate for the cell when p2 > 0, q2 > 0, 0 <= u <= W-1, 0 <= v <= H-1, the depth D at pixel
+ * (floor(v + 0.5), floor(u + 0.5)) is finite and > 0, and p2 <= D * (1 + depth_tolerance).  Its score is
+ * s = (dx^2 + dy^2) / dz^2 in fp64, (dx, dy, dz) = X - C; a non-finite s rejects it.  The key is
+ * (bits(fp32(s)) << 32) | id (int64); the smallest wins, the empty key is INT64_MAX.
+ */
+typedef struct d3d_ortho_view {
+    double R[9];
+    double t[3];
+    double K[9];
+    double C[3];
+    const float* depth;
+    const unsigned int* rgba;
+    int W, H;
+    int id;
+    int pad;
+} d3d_ortho_view_t;
+
+/* d3d_ortho_select: MIN-MERGES the keys of n_views views into key [H,W] int64 (set it to INT64_MAX before the first call).
+ *   height [H,W] fp32 (device), W * H < 2^31; depth_tolerance finite, >= 0; n_views < 2^20.  scratch: device memory of
+ *   d3d_ortho_scratch_bytes(W, H, n_views) bytes (0 for an out-of-range argument).  A per-tile cull over the bounding box of
+ *   the tile's heights only skips work.  No atomics: the key raster is bit-identical for any batching, order or split of the
+ *   views. */
+size_t d3d_ortho_scratch_bytes(int W, int H, int n_views);
+int d3d_ortho_select(const float* height, double x_min, double y_max, double unit_x, double unit_y, int W, int H,
+                     const d3d_ortho_view_t* views, int n_views, double depth_tolerance, void* scratch, size_t scratch_bytes,
+                     long long* key, d3d_stream_t stream);
+
+/* d3d_ortho_colorize: for every cell whose key's id (its low 32 bits) is the id of one of this call's views, writes
+ *   rgba[i,j] = the bilinear sample of that view's image at the cell's (u, v) -- x0 = floor(u), fx = u - x0 (y alike), taps
+ *   clamped to the image, weights (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy summed in that order in fp64, each channel
+ *   floor(c + 0.5) clamped to 0..255, alpha 255 -- and view_out[i,j] = the id.  Every other cell is left untouched, so calls
+ *   over disjoint view sets colour one raster together.  The (u, v) are recomputed from height and the grid, which must be
+ *   the ones select ran on.  Ids must be unique within a call. */
+int d3d_ortho_colorize(const float* height, double x_min, double y_max, double unit_x, double unit_y, int W, int H,
+                       const long long* key, const d3d_ortho_view_t* views, int n_views, unsigned int* rgba, int* view_out,
+                       d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
