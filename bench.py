@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: fused homography-warp + variance cost volume (BASELINE.json config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-secondary]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one reference view: 5 views x 384 depth planes over 32 x 688 x 464 fp32 feature
@@ -11,12 +11,19 @@ features, converging cameras, deep3d_aerial_amd/synthetic.py) and resident in HB
 timed region.  With N > 1 every rank sweeps its own reference views (independent work, no
 collective on the data path): weak scaling, value = all ranks' voxels / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-  roofline      -- algorithmic HBM bytes per launch / mean kernel time from HIP events; `issue_floor_ms` = what the
-                   plane loop's instruction stream alone costs on this chip (measured replay, see issue_floor_ms)
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes the outputs when
+--dump-outputs is given and prints ONE JSON line on rank 0, including
+  roofline      -- algorithmic HBM bytes per launch / mean kernel time from the timed steps' HIP events; `issue_floor_ms` =
+                   what the plane loop's instruction stream alone costs on this chip (measured replay, see issue_floor_ms)
+  per_rank      -- every rank's kernel time, wall time and device (N > 1 only).
+--full also runs, after the timed steps, what the headline does not need, and adds it to the same line:
   parity        -- 16 planes of the volume just produced against the CPU oracle (N = 1 only)
-  cpu_baseline  -- the CPU oracle (oracle/planesweep_oracle.c, OpenMP) timed on a bounded
-                   sample of the same workload on this box's host cores (N = 1 only).
+  cpu_baseline  -- the CPU oracle (oracle/planesweep_oracle.c, OpenMP) timed on a bounded sample of the same workload on
+                   the host's cores, and the reference's op sequence in plain PyTorch CPU (N = 1 only; --no-cpu-baseline
+                   drops it and parity)
+  secondary     -- BASELINE config 3: the three cascades per view, the predict strip, the regulariser and the cascade-stage
+                   sweeps (N = 1 only; --no-secondary drops it)
+  exchange      -- BASELINE config 5's all-gather of the depth / confidence maps (N > 1 only).
 """
 import argparse
 import json
@@ -458,8 +465,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config-3 model timings appended after the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the parity check, the CPU baselines and the config-3 model timings "
+                         "(N = 1) or the config-5 exchange (N > 1), and add them to the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the parity check")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the config-3 model timings")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last step computed to DIR/*.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
@@ -534,7 +544,7 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
     exchange = None
-    if dist:
+    if dist and args.full:
         try:
             exchange = exchange_leg(dist, rank, world, shared)
         except Exception as e:   # the scaling line must survive a failure of the add-on leg (reported, not hidden)
@@ -578,7 +588,7 @@ def main():
             line["per_rank"] = per_rank
         if exchange is not None:
             line["exchange"] = exchange
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             p34_host = p34.cpu().numpy().reshape(-1, 3, 4)
             cb, parity = cpu_baseline(p34_host, feats_host, depth_host, gpu_volume=out)
             line["parity"] = parity
@@ -587,7 +597,7 @@ def main():
             cb["torch_ops_all_cores"] = torch_cpu_leg(proj, feats_host, depth_host, allc)
             cb["torch_ops_8_threads"] = torch_cpu_leg(proj, feats_host, depth_host, min(8, allc))
             line["cpu_baseline"] = cb
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             del out
             torch.cuda.empty_cache()
             try:

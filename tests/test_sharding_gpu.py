@@ -49,8 +49,9 @@ def test_all_gather_maps_on_devices(tmp_path, n_views):
 
 def test_bench_two_ranks(tmp_path):
     """bench.py's N > 1 path as the driver launches it (torch.distributed.run, one process per rank): process-group set-up,
-    the two barriers, the MAX over ranks and rank 0's JSON line.  With one GPU in the box the two ranks share it (gloo for
-    the control-plane collectives, noted in the line); with two or more it is the real one-process-per-GPU RCCL run."""
+    the two barriers, the MAX over ranks and rank 0's JSON line, with --full for the exchange leg.  With one GPU in the box the
+    two ranks share it (gloo for the control-plane collectives, noted in the line); with two or more it is the real
+    one-process-per-GPU RCCL run."""
     import json
     import subprocess
 
@@ -62,7 +63,8 @@ def test_bench_two_ranks(tmp_path):
     if torch.cuda.device_count() < 2:
         env["D3D_BENCH_SHARE_GPU"] = "1"    # bench.py refuses to share a card unless asked to
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--full"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -70,7 +72,7 @@ def test_bench_two_ranks(tmp_path):
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["roofline"]["bound"] == "valu+lds" and d["roofline"]["priced_against"] == "hbm" and "cpu_baseline" not in d and "secondary" not in d
-    # BASELINE config 5's exchange: the all-gather of the maps ahead of fusion, timed outside the step loop
+    # BASELINE config 5's exchange (--full): the all-gather of the maps ahead of fusion, timed outside the step loop
     ex = d["exchange"]
     assert ex["allgather_ms"] > 0 and ex["content_ok"] and ex["shape_per_rank"][1:] == [2, 3712, 2752]
     assert ex["backend"] == ("gloo" if torch.cuda.device_count() < 2 else "nccl")

@@ -8,7 +8,7 @@ R=${1:-r02}
 out=$GRAFT_REPO_ROOT/gpurun_out/$R
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
-python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 tail -1 $out/bench.json | cut -c1-300
 cd /tmp && export TMPDIR=/tmp
 B="python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary"
@@ -33,7 +33,7 @@ for f in glob.glob(out + "/pmc_*/*/*counter_collection.csv"):
             per[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
             per[k]["_name"] = r["Kernel_Name"]
 avg = {k: {c: sum(v) / len(v) for c, v in d.items() if c != "_name"} for k, d in per.items()}
-res = {"round": "$R", "command": "python bench.py --steps 20 --warmup 5 (rocprofv3 passes: --steps 3 --warmup 1 --no-cpu-baseline --no-secondary); tools/profile_round.sh",
+res = {"round": "$R", "command": "python bench.py --full --steps 20 --warmup 5 (rocprofv3 passes: --steps 3 --warmup 1 --no-cpu-baseline --no-secondary); tools/profile_round.sh",
        "kernel": per["sweep"].get("_name"), "staging_copy_kernel": per["staging_copy"].get("_name"),
        "kernel_symbol_prefix": PREFIX, "kernel_code_sha256": _lib.kernel_code_sha256(PREFIX)}
 for f in glob.glob(out + "/trace/*/*kernel_stats.csv"):

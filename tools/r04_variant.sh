@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: build ONE variant of the ring kernel (flags = $1) into a scratch library and run bench.py on it WITH the oracle
-# parity leg (bench.py --no-secondary), printing time, roofline fraction and parity; EXP=1 adds the per-workgroup statistics.
+# parity leg (bench.py --full --no-secondary), printing time, roofline fraction and parity; EXP=1 adds the per-workgroup statistics.
 #   tools/r04_variant.sh "-DD3D_DEV_ONLY_HEADLINE -DD3D_DEV_DEEP32" [more flag sets ...]
 [ -n "$GRAFT_REPO_ROOT" ] || { echo "GRAFT_REPO_ROOT is not set"; exit 2; }
 cd "$GRAFT_REPO_ROOT" || exit 2
@@ -16,7 +16,7 @@ for flags in "$@"; do
   export D3D_LIBRARY=$V
   echo "[$flags]"
   D3D_TILED_STATS=1 python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-secondary 2>&1 | grep -a "per-WG\|tiled stats" | head -2 | cut -c1-330
-  python bench.py --steps 10 --warmup 3 --no-secondary 2>/dev/null | python -c "
+  python bench.py --full --steps 10 --warmup 3 --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('  ', d['value'], 'Mvox/s', d['ms_per_step'], 'ms frac', d['roofline']['frac'], '| parity', d.get('parity',{}).get('variance_rel_l1'), d.get('parity',{}).get('ok'))"
