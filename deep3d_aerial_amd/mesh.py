@@ -1,0 +1,418 @@
+"""Surface mesh from the depth maps.
+
+The reference makes its mesh with OpenMVS binaries (Delaunay plus graph cut) that read a .mvs scene this project does not write,
+so the mesh is this project's own: a truncated signed distance field (TSDF) of every view's depth map in sparse bricks of 8^3
+voxels, and its zero surface by marching tetrahedra.
+
+* Grid.  border [Xmin, Xmax, Ymin, Ymax, Zmin, Zmax] (all six required) and an isotropic voxel size s.  Per axis
+  n = int((max - min + 1e-8) / s), as in DsmGrid.  Voxel (i, j, k) is centred at (Xmin + (i + .5) s, Ymin + (j + .5) s,
+  Zmin + (k + .5) s) in fp64.  Bricks are 8^3 voxels, ceil(n / 8) per axis; a brick at the grid's edge is partial (its voxels
+  outside the grid do not exist).  A grid whose brick count (with a one-brick border) does not fit in int32 is refused.
+* Views.  K [3,3] with K[1,0] = K[2,0] = K[2,1] = 0 and K[2,2] = 1, E = Tcw [4,4] (the fp32 `outcam`, used in fp64), depth and
+  confidence [H,W] fp32.  A pixel is valid when its depth D is finite and > 0 and its confidence >= conf_threshold (default
+  0.2, the reference's FUSION photomatric_threshold).
+* Allocation.  The centre of valid pixel (x, y) is back-projected in fp64 with no contraction: yn = (y - K12) / K11,
+  xn = ((x - K02) - K01 yn) / K00, c = (xn D - t0, yn D - t1, D - t2), X_a = R0a c0 + R1a c1 + R2a c2 (left to right).  Its
+  brick is floor(floor((X_a - min_a) / s) / 8) per axis.  The allocated set is the 3 x 3 x 3 dilation of those bricks, clipped
+  to the grid, numbered in increasing order of (bk by + bj) bx + bi by a scan (no atomic append: the numbering does not depend
+  on timing).  Voxels outside allocated bricks are unobserved.
+* Integration, per voxel of an allocated brick and per view in the given order.  In fp64 with no contraction p = R X + t,
+  q = K p, each row summed left to right (as ortho.py).  The view observes the voxel when p2 > 0, q2 > 0, the pixel
+  (floor(q1 / q2 + .5), floor(q0 / q2 + .5)) is inside the image and valid, and sdf = D - p2 >= -trunc.  It adds
+  d = fp32(min(1, sdf / trunc)) to the voxel's fp32 `sum` (in view order) and 1 to its int32 `n`.  The voxel's value is
+  tsdf = sum / n in fp32; it is observed when n >= min_views.  Defaults trunc = 3 s (0 < trunc <= 8 s: the truncation band
+  stays inside the allocated bricks), min_views = 2.  The running sums stay fp32 between calls, so the result is bit-identical
+  for any views_per_batch, but not for another view order.
+* Extraction.  Every voxel is the minimum corner of a cube, split into the 6 Kuhn (Freudenthal) tetrahedra around its main
+  diagonal (TETS: one per axis permutation, corners c = x | y << 1 | z << 2); every cube uses the same split, so neighbouring
+  cubes agree on every face.  A tetrahedron is meshed when its 4 corners are observed; a corner is inside when tsdf < 0.  An edge
+  a -> b (a its lower endpoint) that crosses the surface gets the vertex X_a + t (X_b - X_a), per component in fp64 with
+  t = f_a / (f_a - f_b), rounded to fp32.  The lower endpoint owns the edge; it has 7 edge types +x, +y, +z, +xy, +xz, +yz, +xyz.
+  Vertices come in (brick, voxel x-fastest, edge type) order, triangles in (brick, voxel, tetrahedron, triangle) order, and
+  only vertices some triangle uses are kept.  TRI, the 16-case table (bit i: tetrahedron corner i inside), orients every
+  triangle so that its right-hand normal points from the inside to the outside, toward the cameras.
+* File.  Binary little-endian PLY: `element vertex` with float x, y, z and `element face` with `property list uchar int
+  vertex_indices` (write_ply / read_ply).
+
+The passes are HIP kernels (csrc/mesh.hip) with no float atomics and no order-dependent integer atomics: the mesh is a function
+of the views and their order alone.
+
+    python -m deep3d_aerial_amd.mesh --mvs MVS_FOLDER --out mesh.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax --voxel S
+        [--trunc T] [--min_views 2] [--conf_threshold 0.2] [--views_per_batch N]
+"""
+import argparse
+import ctypes
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+
+DEFAULT_CONF = 0.2
+DEFAULT_MIN_VIEWS = 2
+BRICK = 8
+
+# the 6 Kuhn tetrahedra (positively oriented), the edges of a tetrahedron, the 16-case table (csrc/mesh.hip has the same)
+TETS = ((0, 1, 3, 7), (0, 5, 1, 7), (0, 3, 2, 7), (0, 2, 6, 7), (0, 4, 5, 7), (0, 6, 4, 7))
+TET_EDGES = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
+TRI = ((), ((0, 1, 2),), ((0, 4, 3),), ((1, 2, 4), (1, 4, 3)), ((1, 3, 5),), ((0, 5, 2), (0, 3, 5)), ((0, 4, 5), (0, 5, 1)),
+       ((2, 4, 5),), ((2, 5, 4),), ((0, 1, 5), (0, 5, 4)), ((0, 5, 3), (0, 2, 5)), ((1, 5, 3),), ((1, 3, 4), (1, 4, 2)),
+       ((0, 3, 4),), ((0, 2, 1),), ())
+# owned edge types in output order, as the corner at their far end
+TYPE_CORNER = (1, 2, 4, 3, 5, 6, 7)
+
+
+class _GridRecord(ctypes.Structure):
+    """d3d_mesh_grid_t (include/deep3d_planesweep.h)."""
+    _fields_ = [("x_min", ctypes.c_double), ("y_min", ctypes.c_double), ("z_min", ctypes.c_double), ("voxel", ctypes.c_double),
+                ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("nz", ctypes.c_int), ("bx", ctypes.c_int), ("by", ctypes.c_int),
+                ("bz", ctypes.c_int)]
+
+
+class _ViewRecord(ctypes.Structure):
+    """d3d_mesh_view_t (include/deep3d_planesweep.h)."""
+    _fields_ = [("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3), ("K", ctypes.c_double * 9), ("depth", ctypes.c_void_p),
+                ("conf", ctypes.c_void_p), ("W", ctypes.c_int), ("H", ctypes.c_int)]
+
+
+class MeshGrid(object):
+    """The voxel grid: border [Xmin, Xmax, Ymin, Ymax, Zmin, Zmax] and voxel size s."""
+
+    def __init__(self, border, voxel):
+        border = [float(b) for b in border]
+        if len(border) != 6:
+            raise ValueError("the mesh border needs all six values Xmin, Xmax, Ymin, Ymax, Zmin, Zmax (got %d)" % len(border))
+        if not all(math.isfinite(b) for b in border):
+            raise ValueError("border %s must be finite" % border)
+        s = float(voxel)
+        if not (math.isfinite(s) and s > 0):
+            raise ValueError("voxel size %r must be finite and > 0" % (voxel,))
+        self.border, self.voxel = border, s
+        self.min = (border[0], border[2], border[4])
+        self.n = tuple(int((border[2 * a + 1] - border[2 * a] + 1e-8) / s) for a in range(3))
+        if min(self.n) < 1:
+            raise ValueError("empty grid %d x %d x %d" % self.n)
+        self.bricks = tuple(-(-n // BRICK) for n in self.n)
+        bx, by, bz = self.bricks
+        if (bx + 2) * (by + 2) * (bz + 2) >= 1 << 31:
+            raise ValueError("grid of %d x %d x %d bricks: the brick count does not fit in int32" % self.bricks)
+
+    @property
+    def n_bricks(self):
+        return self.bricks[0] * self.bricks[1] * self.bricks[2]
+
+    def record(self):
+        return _GridRecord(self.min[0], self.min[1], self.min[2], self.voxel, *(self.n + self.bricks))
+
+    def __repr__(self):
+        return "MeshGrid(border=%s, voxel=%r, size=%s)" % (self.border, self.voxel, self.n)
+
+
+class MeshView(object):
+    """One view: K [3,3], E = Tcw [4,4] (host arrays, used in fp64), depth and confidence [H,W] fp32 on the GPU."""
+
+    def __init__(self, K, E, depth, confidence):
+        from .ops import _chk
+
+        K = np.asarray(K, np.float64)
+        E = np.asarray(E, np.float64)
+        if K.shape != (3, 3) or E.shape != (4, 4):
+            raise ValueError("K must be [3,3] and E [4,4] (got %s, %s)" % (K.shape, E.shape))
+        if not (K[1, 0] == 0 and K[2, 0] == 0 and K[2, 1] == 0 and K[2, 2] == 1 and K[0, 0] != 0 and K[1, 1] != 0):
+            raise ValueError("K must be [[fx, s, cx], [0, fy, cy], [0, 0, 1]] with fx, fy != 0 (got %s)" % K.tolist())
+        self.K, self.R, self.t = K.copy(), E[:3, :3].copy(), E[:3, 3].copy()
+        _chk(depth, "depth", 2)
+        _chk(confidence, "confidence", 2)
+        if tuple(depth.shape) != tuple(confidence.shape) or depth.device != confidence.device:
+            raise ValueError("depth %s and confidence %s must have one size and one device" % (tuple(depth.shape), tuple(confidence.shape)))
+        self.depth, self.confidence = depth, confidence
+        self.H, self.W = (int(s) for s in depth.shape)
+
+    def record(self):
+        r = _ViewRecord()
+        r.R[:] = list(self.R.ravel())
+        r.t[:] = list(self.t)
+        r.K[:] = list(self.K.ravel())
+        r.depth, r.conf = self.depth.data_ptr(), self.confidence.data_ptr()
+        r.W, r.H = self.W, self.H
+        return r
+
+
+def _stream():
+    from . import ops
+
+    return ops._stream()
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _records(views, device):
+    arr = (_ViewRecord * len(views))(*[v.record() for v in views])
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def check_settings(grid, trunc=None, min_views=DEFAULT_MIN_VIEWS, conf_threshold=DEFAULT_CONF, views_per_batch=None):
+    """(trunc, min_views, conf_threshold, views_per_batch) checked, trunc defaulting to 3 s."""
+    trunc = 3.0 * grid.voxel if trunc is None else float(trunc)
+    if not (math.isfinite(trunc) and 0 < trunc <= 8 * grid.voxel):
+        raise ValueError("trunc %r must satisfy 0 < trunc <= 8 voxel (%g)" % (trunc, 8 * grid.voxel))
+    if int(min_views) != min_views or int(min_views) < 1:
+        raise ValueError("min_views %r must be an integer >= 1" % (min_views,))
+    conf = float(conf_threshold)
+    if math.isnan(conf):
+        raise ValueError("conf_threshold is NaN")
+    if views_per_batch is not None and int(views_per_batch) < 1:
+        raise ValueError("views_per_batch must be >= 1 (got %r)" % (views_per_batch,))
+    return trunc, int(min_views), conf, None if views_per_batch is None else int(views_per_batch)
+
+
+def _batches(views, views_per_batch):
+    n = views_per_batch or max(len(views), 1)
+    return [views[k:k + n] for k in range(0, len(views), n)]
+
+
+def _check_views(views, device):
+    views = list(views)
+    if not all(isinstance(v, MeshView) for v in views):
+        raise TypeError("views must be MeshView records")
+    for v in views:
+        if v.depth.device != device:
+            raise ValueError("every view must be on %s (got %s)" % (device, v.depth.device))
+    return views
+
+
+def tsdf_volume(views, grid, trunc=None, conf_threshold=DEFAULT_CONF, views_per_batch=None, device=None):
+    """The sparse TSDF: {"brick_index" [bz,by,bx] int32 (-1: not allocated), "bricks" [nb] int32 linear brick indices,
+    "sum" [nb, 8, 8, 8] fp32, "count" [nb, 8, 8, 8] int32 (voxel [k, j, i] of the brick)} on the device."""
+    if not isinstance(grid, MeshGrid):
+        raise TypeError("grid must be a MeshGrid")
+    trunc, _, conf, vpb = check_settings(grid, trunc, DEFAULT_MIN_VIEWS, conf_threshold, views_per_batch)
+    if device is None:
+        if not views:
+            raise ValueError("no views and no device")
+        device = views[0].depth.device
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("the mesh is built on the GPU (no CPU fallback); got %s" % device)
+    views = _check_views(views, device)
+    lib = _lib.load()
+    g = grid.record()
+    bx, by, bz = grid.bricks
+    marks = torch.zeros(((bz + 2) * (by + 2) * (bx + 2),), dtype=torch.uint8, device=device)
+    batches = [(b, _records(b, device)) for b in _batches(views, vpb)]
+    for batch, recs in batches:
+        for v0 in range(0, len(batch), 65535):   # one launch row per view
+            part = batch[v0:v0 + 65535]
+            rc = lib.d3d_mesh_mark(ctypes.byref(g), ctypes.c_void_p(recs.data_ptr() + v0 * ctypes.sizeof(_ViewRecord)), len(part),
+                                   max(v.W * v.H for v in part), conf, _ptr(marks), _stream())
+            _lib.check(rc, "d3d_mesh_mark")
+    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(grid.n_bricks))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    index = torch.empty((bz, by, bx), dtype=torch.int32, device=device)
+    blist = torch.empty((grid.n_bricks,), dtype=torch.int32, device=device)
+    nb_dev = torch.empty((1,), dtype=torch.int64, device=device)
+    _lib.check(lib.d3d_mesh_bricks(ctypes.byref(g), _ptr(marks), _ptr(scratch), nbytes, _ptr(index), _ptr(blist), _ptr(nb_dev),
+                                   _stream()), "d3d_mesh_bricks")
+    nb = int(nb_dev.item())   # the brick count sizes the volume
+    if nb * BRICK ** 3 >= 1 << 31:
+        raise ValueError("%d allocated bricks: more voxels than int32 indexes" % nb)
+    blist = blist[:nb]
+    s = torch.zeros((nb, BRICK, BRICK, BRICK), dtype=torch.float32, device=device)
+    n = torch.zeros((nb, BRICK, BRICK, BRICK), dtype=torch.int32, device=device)
+    for batch, recs in (batches if nb else []):
+        rc = lib.d3d_mesh_integrate(ctypes.byref(g), _ptr(blist), nb, _ptr(recs), len(batch), trunc, conf, _ptr(s), _ptr(n), _stream())
+        _lib.check(rc, "d3d_mesh_integrate")
+    return {"brick_index": index, "bricks": blist, "sum": s, "count": n}
+
+
+def extract(volume, grid, min_views=DEFAULT_MIN_VIEWS):
+    """The surface of a tsdf_volume: (vertices [n,3] fp32, faces [m,3] int32) on the device."""
+    _, min_views, _, _ = check_settings(grid, None, min_views)
+    lib = _lib.load()
+    g = grid.record()
+    index, blist, s, n = volume["brick_index"], volume["bricks"], volume["sum"], volume["count"]
+    dev = s.device
+    nb = int(blist.shape[0])
+    if nb == 0:
+        return torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev)
+    nvox = nb * BRICK ** 3
+    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(nvox))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    edges = torch.empty((max(nvox, 1),), dtype=torch.uint8, device=dev)
+    vbase = torch.empty((max(nvox, 1),), dtype=torch.int32, device=dev)
+    fbase = torch.empty((max(nvox, 1),), dtype=torch.int32, device=dev)
+    totals = torch.empty((2,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_mesh_count(ctypes.byref(g), _ptr(blist), _ptr(index), nb, _ptr(s), _ptr(n), min_views, _ptr(scratch), nbytes,
+                                  _ptr(edges), _ptr(vbase), _ptr(fbase), _ptr(totals), _stream()), "d3d_mesh_count")
+    nv, nf = (int(x) for x in totals.cpu())   # the counts size the outputs
+    if nv >= 1 << 31 or nf >= 1 << 31:
+        raise ValueError("%d vertices, %d triangles: more than int32 indexes" % (nv, nf))
+    verts = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((max(nf, 1), 3), dtype=torch.int32, device=dev)
+    ref = torch.zeros((max(nv, 1),), dtype=torch.int32, device=dev)
+    _lib.check(lib.d3d_mesh_emit(ctypes.byref(g), _ptr(blist), _ptr(index), nb, _ptr(s), _ptr(n), min_views, _ptr(edges), _ptr(vbase),
+                                 _ptr(fbase), _ptr(verts), _ptr(faces), _ptr(ref), _stream()), "d3d_mesh_emit")
+    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(nv))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    remap = torch.empty((max(nv, 1),), dtype=torch.int32, device=dev)
+    out = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev)
+    kept = torch.empty((1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_mesh_compact(_ptr(verts), nv, _ptr(faces), nf, _ptr(ref), _ptr(scratch), nbytes, _ptr(remap), _ptr(out), _ptr(kept),
+                                    _stream()), "d3d_mesh_compact")
+    return out[:int(kept.item())], faces[:nf]
+
+
+def depth_to_mesh(views, grid, trunc=None, min_views=DEFAULT_MIN_VIEWS, conf_threshold=DEFAULT_CONF, views_per_batch=None):
+    """The mesh of `views` (MeshView, in this order) on `grid`: (vertices [n,3] fp32, faces [m,3] int32) on the device."""
+    check_settings(grid, trunc, min_views, conf_threshold, views_per_batch)
+    vol = tsdf_volume(views, grid, trunc, conf_threshold, views_per_batch)
+    return extract(vol, grid, min_views)
+
+
+# ----------------------------------------------------------------------------------------
+# PLY
+# ----------------------------------------------------------------------------------------
+FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def ply_header(n_vertices, n_faces):
+    return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (n_vertices, n_faces)).encode("ascii")
+
+
+def write_ply(path, vertices, faces):
+    """Writes the binary little-endian PLY.  vertices [n,3] fp32, faces [m,3] int32 (tensors on any device, or arrays)."""
+    if isinstance(vertices, torch.Tensor):
+        vertices = vertices.detach().cpu().numpy()
+    if isinstance(faces, torch.Tensor):
+        faces = faces.detach().cpu().numpy()
+    v = np.ascontiguousarray(vertices, "<f4").reshape(-1, 3)
+    f = np.asarray(faces).reshape(-1, 3)
+    rec = np.empty((f.shape[0],), FACE_DTYPE)
+    rec["n"] = 3
+    rec["v"] = f
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(ply_header(v.shape[0], f.shape[0]))
+        fh.write(v.tobytes())
+        fh.write(rec.tobytes())
+    return str(path)
+
+
+def read_ply(path):
+    """(vertices [n,3] float32, faces [m,3] int32) of a file write_ply wrote."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError("%s: not a PLY file" % path)
+    lines = data[:end].decode("ascii").split("\n")
+    counts = {}
+    for ln in lines:
+        w = ln.split()
+        if len(w) == 3 and w[0] == "element":
+            counts[w[1]] = int(w[2])
+    nv, nf = counts.get("vertex"), counts.get("face")
+    if nv is None or nf is None or data[:end + 11] != ply_header(nv, nf):
+        raise ValueError("%s: not a PLY file write_ply wrote" % path)
+    body = data[end + 11:]
+    if len(body) != nv * 12 + nf * FACE_DTYPE.itemsize:
+        raise ValueError("%s: %d bytes of data, %d expected" % (path, len(body), nv * 12 + nf * FACE_DTYPE.itemsize))
+    v = np.frombuffer(body[:nv * 12], "<f4").reshape(nv, 3).astype(np.float32)
+    rec = np.frombuffer(body[nv * 12:], FACE_DTYPE)
+    if nf and not (rec["n"] == 3).all():
+        raise ValueError("%s: only triangles are read" % path)
+    return v, rec["v"].astype(np.int32).reshape(nf, 3)
+
+
+# ----------------------------------------------------------------------------------------
+# predict's products -> views; settings; command line
+# ----------------------------------------------------------------------------------------
+def load_mvs_views(mvs_folder, device="cuda"):
+    """MeshView records of every {name}_init.pfm + {name}_prob.pfm + {name}.txt predict wrote under mvs_folder, in increasing
+    order of the image id in the camera file (then name): predict's view order when the view pair file lists its reference
+    views by increasing id, as it usually does."""
+    from . import predict
+
+    names = [f[:-len("_init.pfm")] for f in os.listdir(mvs_folder) if f.endswith("_init.pfm")]
+    if not names:
+        raise FileNotFoundError("no {name}_init.pfm under %s" % mvs_folder)
+    found = []
+    for name in names:
+        cam, location, _ = predict.read_red_cam(os.path.join(mvs_folder, name + ".txt"))
+        found.append((int(location[2]), name, cam))
+    views = []
+    for _, name, cam in sorted(found, key=lambda r: (r[0], r[1])):
+        depth, _ = predict.load_pfm(os.path.join(mvs_folder, name + "_init.pfm"))
+        prob, _ = predict.load_pfm(os.path.join(mvs_folder, name + "_prob.pfm"))
+        views.append(MeshView(cam[1, :3, :3], cam[0], torch.from_numpy(np.ascontiguousarray(depth)).to(device),
+                              torch.from_numpy(np.ascontiguousarray(prob)).to(device)))
+    return views
+
+
+def parse_border6(text):
+    vals = [float(v) for v in str(text).split(",")]
+    if len(vals) != 6:
+        raise argparse.ArgumentTypeError("the mesh border needs Xmin,Xmax,Ymin,Ymax,Zmin,Zmax (got %d values)" % len(vals))
+    return vals
+
+
+def add_arguments(ap, prefix=""):
+    """The mesh settings as flags (--<prefix>border, ...); used by this module's CLI and by predict (--mesh_*)."""
+    ap.add_argument("--%sborder" % prefix, type=parse_border6, default=None, help="Xmin,Xmax,Ymin,Ymax,Zmin,Zmax (world units)")
+    ap.add_argument("--%svoxel" % prefix, type=float, default=None, help="voxel size (world units)")
+    ap.add_argument("--%strunc" % prefix, type=float, default=None, help="truncation distance (default 3 voxels, at most 8)")
+    ap.add_argument("--%smin_views" % prefix, type=int, default=DEFAULT_MIN_VIEWS, help="views a voxel needs to be observed")
+    ap.add_argument("--%sconf_threshold" % prefix, type=float, default=DEFAULT_CONF, help="a pixel is used when its confidence >= this")
+    ap.add_argument("--%sviews_per_batch" % prefix, type=int, default=None, help="views per integration call (default: all)")
+
+
+def settings_from_args(a, path, prefix=""):
+    g = lambda k: getattr(a, prefix + k)
+    return {"path": path, "border": g("border"), "voxel": g("voxel"), "trunc": g("trunc"), "min_views": g("min_views"),
+            "conf_threshold": g("conf_threshold"), "views_per_batch": g("views_per_batch")}
+
+
+def check_args(ap, a, prefix=""):
+    """The argument errors of the mesh settings, reported through ap.error."""
+    if getattr(a, prefix + "border") is None:
+        ap.error("--%sborder Xmin,Xmax,Ymin,Ymax,Zmin,Zmax is required" % prefix)
+    if getattr(a, prefix + "voxel") is None:
+        ap.error("--%svoxel is required" % prefix)
+    try:
+        s = settings_from_args(a, None, prefix)
+        check_settings(MeshGrid(s["border"], s["voxel"]), s["trunc"], s["min_views"], s["conf_threshold"], s["views_per_batch"])
+    except ValueError as e:
+        ap.error("--%s*: %s" % (prefix, e))
+
+
+def build_and_write(views, settings):
+    """depth_to_mesh with the settings dict (settings_from_args) and write_ply to settings["path"]: (vertices, faces)."""
+    grid = MeshGrid(settings["border"], settings["voxel"])
+    v, f = depth_to_mesh(views, grid, settings.get("trunc"), settings.get("min_views", DEFAULT_MIN_VIEWS),
+                         settings.get("conf_threshold", DEFAULT_CONF), settings.get("views_per_batch"))
+    write_ply(settings["path"], v, f)
+    return v, f
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="surface mesh (binary PLY) from predict's depth maps, confidences and cameras")
+    ap.add_argument("--mvs", required=True, help="predict's output folder: {name}_init.pfm, {name}_prob.pfm and {name}.txt")
+    ap.add_argument("--out", required=True, help="mesh file (.ply)")
+    add_arguments(ap)
+    a = ap.parse_args(argv)
+    check_args(ap, a)
+    if not torch.cuda.is_available():
+        raise RuntimeError("the mesh is built on the GPU (no CPU fallback)")
+    views = load_mvs_views(a.mvs)
+    v, f = build_and_write(views, settings_from_args(a, a.out))
+    print("mesh %s: %d vertices, %d triangles from %d views" % (a.out, v.shape[0], f.shape[0], len(views)))
+    return a.out
+
+
+if __name__ == "__main__":
+    main()

@@ -68,7 +68,7 @@ def _gather_objects(obj, world_size):
 def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checker=None, fusion_num=10, min_geo_consist_num=4,
                      filter_sources=True, partition="block", scene_range=None, skip_line=2, feature_cache_bytes=0,
                      device="cuda", timings=None, display=False, fuse_partition="views", scene_blocks=None,
-                     estimate_normals=False, normal_nei=1, save_normals=False, dsm=None, ortho=None):
+                     estimate_normals=False, normal_nei=1, save_normals=False, dsm=None, ortho=None, mesh=None):
     """Runs the three steps above for this rank.  Returns a list, one entry per reference view this rank owns, of
     {"ref", "final_mask" [H,W] bool, "avg_xyz_world" [3,H,W], "points": fuse.extract_points(...) dict} (device tensors).
     timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s.
@@ -83,7 +83,17 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     concatenated, gathered on rank 0 (sharding.gather_points) and the DSM is built and written there; timings gets dsm_s.
     ortho: None (nothing changes), or the orthophoto settings {"path", "depth_tolerance", "views_per_batch"} (needs dsm): the
     true orthophoto on that DSM (write_ortho_of) from the views' gathered depth maps, cameras and reference images; rank 0
-    writes it; timings gets ortho_s."""
+    writes it; timings gets ortho_s.
+    mesh: None (nothing changes), or the mesh settings {"path", "border", "voxel", "trunc", "min_views", "conf_threshold",
+    "views_per_batch"} (mesh.settings_from_args): rank 0 builds the mesh of every gathered depth and confidence map with its
+    camera, in global view order, and writes the PLY; the other ranks do nothing (no collective: the file does not depend on
+    the number of ranks); timings gets mesh_s on rank 0."""
+    if mesh is not None:
+        from . import mesh as _mesh
+
+        _grid = _mesh.MeshGrid(mesh["border"], mesh["voxel"])
+        _mesh.check_settings(_grid, mesh.get("trunc"), mesh.get("min_views", _mesh.DEFAULT_MIN_VIEWS),
+                             mesh.get("conf_threshold", _mesh.DEFAULT_CONF), mesh.get("views_per_batch"))
     if ortho is not None:
         from . import ortho as _ortho
 
@@ -173,6 +183,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         timings.update(views=len(mine), predict_s=t1 - t0, allgather_ms=(g1 - g0) * 1e3,
                        allgather_bytes=int(all_maps.numel() * 4), fuse_s=t2 - g1, map_size=(H, W),
                        backend=dist.get_backend() if world_size > 1 else "none")
+    if mesh is not None and rank == 0:
+        write_mesh_of(all_maps, all_cams, mesh, timings=timings)
     if dsm is not None:
         built = write_dsm_of(out, dsm, rank, world_size, xyz_device=all_maps.device, timings=timings)
         if ortho is not None:
@@ -181,6 +193,20 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             write_ortho_of(built[0] if built is not None else None, dsm, ortho, own, rank, world_size, device=all_maps.device,
                            timings=timings)
     return out
+
+
+def write_mesh_of(all_maps, all_cams, settings, timings=None):
+    """The mesh of every view (all_maps [n,2,H,W] depth and confidence, all_cams [n,2,4,4], by global view index), written to
+    settings["path"] (mesh.build_and_write).  Returns (vertices, faces)."""
+    from . import mesh as _mesh
+
+    t0 = time.perf_counter()
+    views = [_mesh.MeshView(all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], all_maps[i, 1]) for i in range(all_maps.shape[0])]
+    res = _mesh.build_and_write(views, settings)
+    torch.cuda.synchronize()
+    if timings is not None:
+        timings["mesh_s"] = time.perf_counter() - t0
+    return res
 
 
 def write_ortho_of(height, dsm_settings, settings, views, rank=0, world_size=1, device="cuda", timings=None):

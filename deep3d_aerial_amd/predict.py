@@ -568,6 +568,11 @@ def parse_args(argv=None):
 
     ap.add_argument("--ortho", default=None, help="with --fuse --dsm: write the true orthophoto on the DSM to this .tif (+ .tfw), on rank 0")
     _ortho.add_arguments(ap, prefix="ortho_")
+    # surface mesh from the gathered depth maps (deep3d_aerial_amd/mesh.py): off by default
+    from . import mesh as _mesh
+
+    ap.add_argument("--mesh", default=None, help="with --fuse: write the surface mesh of all views' depth maps to this .ply, on rank 0")
+    _mesh.add_arguments(ap, prefix="mesh_")
     a = ap.parse_args(argv)
     if a.dsm is not None and not a.fuse:
         ap.error("--dsm needs --fuse (the DSM is built from the fused points)")
@@ -579,6 +584,12 @@ def parse_args(argv=None):
         ap.error("--ortho needs --dsm (the orthophoto is draped on the DSM)")
     if a.ortho is not None:
         _ortho.check_args(ap, a, prefix="ortho_")
+    if a.mesh is not None and not a.fuse:
+        ap.error("--mesh needs --fuse (the mesh is built from the gathered depth maps of the fusion step)")
+    if a.mesh is not None and a.mesh_border is None:
+        ap.error("--mesh needs --mesh_border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax")
+    if a.mesh is not None:
+        _mesh.check_args(ap, a, prefix="mesh_")
     return a
 
 
@@ -615,6 +626,12 @@ def _ortho_settings(a):
     from . import ortho as _ortho
 
     return _ortho.settings_from_args(a, a.ortho, prefix="ortho_")
+
+
+def _mesh_settings(a):
+    from . import mesh as _mesh
+
+    return _mesh.settings_from_args(a, a.mesh, prefix="mesh_")
 
 
 def main(argv=None):
@@ -665,12 +682,15 @@ def main(argv=None):
                                         fuse_partition=a.fuse_partition, scene_blocks=blocks, estimate_normals=a.fuse_normals,
                                         normal_nei=a.normal_nei, save_normals=a.save_normals,
                                         dsm=_dsm_settings(a) if a.dsm is not None else None,
-                                        ortho=_ortho_settings(a) if a.ortho is not None else None)
+                                        ortho=_ortho_settings(a) if a.ortho is not None else None,
+                                        mesh=_mesh_settings(a) if a.mesh is not None else None)
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
         if a.dsm is not None and rank == 0:
             print("rank 0/%d: DSM %s in %.2f s" % (world, a.dsm, tm["dsm_s"]))
         if a.ortho is not None and rank == 0:
             print("rank 0/%d: orthophoto %s in %.2f s" % (world, a.ortho, tm["ortho_s"]))
+        if a.mesh is not None and rank == 0:
+            print("rank 0/%d: mesh %s in %.2f s" % (world, a.mesh, tm["mesh_s"]))
         print("rank %d/%d: %d views in %.2f s, all-gather of %.1f MB in %.2f ms (%s), fusion of its %d reference views %.2f s, "
               "%d vertices" % (rank, world, tm["views"], tm["predict_s"], tm["allgather_bytes"] / 1e6, tm["allgather_ms"], tm["backend"],
                                len(res), tm["fuse_s"], sum(int(r["points"]["xyz"].shape[0]) for r in res)))

@@ -895,6 +895,78 @@ int d3d_ortho_colorize(const float* height, double x_min, double y_max, double u
                        const long long* key, const d3d_ortho_view_t* views, int n_views, unsigned int* rgba, int* view_out,
                        d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.10 -- surface mesh from the depth maps (the reference shells out to OpenMVS; the semantics are this project's,
+ * deep3d_aerial_amd/mesh.py states them in full).  A truncated signed distance field in sparse bricks of 8^3 voxels, then
+ * marching tetrahedra (6 Kuhn tetrahedra per cube).  Grid: nx x ny x nz voxels of size `voxel`, voxel (i, j, k) centred at
+ * (x_min + (i + 0.5) voxel, ...) in fp64; bx = ceil(nx / 8) bricks per axis (y, z alike), bx * by * bz < 2^31.  A voxel's slot
+ * is brick * 512 + (lz * 8 + ly) * 8 + lx, brick its number in the allocated list.  Every pointer below is DEVICE memory
+ * except `grid`, a host struct.  Integer atomics nowhere, float atomics nowhere: every pass is a fixed-order computation.
+ * A view is one d3d_mesh_view_t record: R [3,3] row-major and t of E = Tcw, K [3,3] with K[1,0] = K[2,0] = K[2,1] = 0 and
+ * K[2,2] = 1 (the caller checks it), depth and confidence [H,W] fp32.
+ */
+typedef struct d3d_mesh_grid {
+    double x_min, y_min, z_min, voxel;
+    int nx, ny, nz;
+    int bx, by, bz;
+} d3d_mesh_grid_t;
+
+typedef struct d3d_mesh_view {
+    double R[9];
+    double t[3];
+    double K[9];
+    const float* depth;
+    const float* conf;
+    int W, H;
+} d3d_mesh_view_t;
+
+/* Scratch of one exclusive scan over n int32 values (8 bytes per 4096 values; 0 for n < 0).  d3d_mesh_bricks needs it for
+ * n = bx * by * bz, d3d_mesh_count for n = n_bricks * 512, d3d_mesh_compact for n = n_vertices. */
+size_t d3d_mesh_scan_scratch_bytes(long long n);
+
+/* d3d_mesh_mark: one lane per pixel of each view sets marks[((bk + 1) * (by + 2) + bj + 1) * (bx + 2) + bi + 1] = 1 for the
+ *   brick (bi, bj, bk) in -1 .. b of the back-projected centre of every valid pixel (depth finite and > 0, confidence >=
+ *   conf_threshold).  marks: (bx + 2) (by + 2) (bz + 2) bytes, zeroed by the caller before the first batch; calls OR into
+ *   it.  max_pixels >= W * H of every view. */
+int d3d_mesh_mark(const d3d_mesh_grid_t* grid, const d3d_mesh_view_t* views, int n_views, int max_pixels, double conf_threshold,
+                  unsigned char* marks, d3d_stream_t stream);
+
+/* d3d_mesh_bricks: the 3 x 3 x 3 dilation of the marks, clipped to the grid, numbered in increasing linear index
+ *   (bk * by + bj) * bx + bi by a reduce-then-scan.  brick_index [bz,by,bx] int32 gets the number or -1, brick_list
+ *   (bx * by * bz int32) the linear index of each allocated brick, n_bricks (one int64) their count. */
+int d3d_mesh_bricks(const d3d_mesh_grid_t* grid, const unsigned char* marks, void* scratch, size_t scratch_bytes, int* brick_index,
+                    int* brick_list, long long* n_bricks, d3d_stream_t stream);
+
+/* d3d_mesh_integrate: adds the views, in the order given, to sum [n_bricks * 512] fp32 and count [n_bricks * 512] int32
+ *   (zeroed by the caller before the first batch).  Per voxel and view, fp64 without contraction: p = R X + t, q = K p;
+ *   observed when p2 > 0, q2 > 0, pixel (floor(q1 / q2 + 0.5), floor(q0 / q2 + 0.5)) is inside and valid and
+ *   sdf = D - p2 >= -trunc; then sum += fp32(min(1, sdf / trunc)), count += 1.  0 < trunc <= 8 voxel.  One workgroup per
+ *   brick; views are culled per brick by the projection of its box, which only skips work. */
+int d3d_mesh_integrate(const d3d_mesh_grid_t* grid, const int* brick_list, int n_bricks, const d3d_mesh_view_t* views, int n_views,
+                       double trunc, double conf_threshold, float* sum, int* count, d3d_stream_t stream);
+
+/* d3d_mesh_count: per voxel, the mask of its crossed owned edges (7 bits: +x, +y, +z, +xy, +xz, +yz, +xyz) into edges
+ *   [n_bricks * 512] uint8 and the exclusive scans of their vertex and triangle counts into vert_base and face_base
+ *   [n_bricks * 512] int32; totals [2] int64 gets (vertices, triangles).  The offsets are valid when both totals are below
+ *   2^31.  A voxel is observed when count >= min_views (>= 1); its value is sum / count in fp32.  scratch:
+ *   d3d_mesh_scan_scratch_bytes(n_bricks * 512). */
+int d3d_mesh_count(const d3d_mesh_grid_t* grid, const int* brick_list, const int* brick_index, int n_bricks, const float* sum,
+                   const int* count, int min_views, void* scratch, size_t scratch_bytes, unsigned char* edges, int* vert_base,
+                   int* face_base, long long* totals, d3d_stream_t stream);
+
+/* d3d_mesh_emit: the vertices [totals[0], 3] fp32 and triangles [totals[1], 3] int32 d3d_mesh_count sized, in (brick, voxel,
+ *   edge type) and (brick, voxel, tetrahedron, triangle) order; referenced [totals[0]] int32, zeroed by the caller, gets 1 for
+ *   every vertex a triangle uses. */
+int d3d_mesh_emit(const d3d_mesh_grid_t* grid, const int* brick_list, const int* brick_index, int n_bricks, const float* sum,
+                  const int* count, int min_views, const unsigned char* edges, const int* vert_base, const int* face_base,
+                  float* vertices, int* faces, int* referenced, d3d_stream_t stream);
+
+/* d3d_mesh_compact: drops the unreferenced vertices: out_vertices [n_vertices, 3] gets the referenced ones in order (the first
+ *   n_kept rows), faces [n_faces, 3] are renumbered in place, remap [n_vertices] int32 is scratch, n_kept one int64.
+ *   n_vertices, n_faces < 2^31; scratch: d3d_mesh_scan_scratch_bytes(n_vertices). */
+int d3d_mesh_compact(const float* vertices, long long n_vertices, int* faces, long long n_faces, const int* referenced, void* scratch,
+                     size_t scratch_bytes, int* remap, float* out_vertices, long long* n_kept, d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
