@@ -131,6 +131,8 @@ SIGNATURES = {
     "d3d_dsm_scratch_bytes": [ctypes.c_longlong, _i, _i, _i],  # returns size_t
     "d3d_dsm_from_points": [_vp, ctypes.c_longlong, _d, _d, _d, _d, _d, _d, _i, _i, _i, _d, _i, _vp, _sz, _vp, _vp, _vp],
     "d3d_dsm_fill_moving_average": [_vp, _vp, _i, _i, _i, _vp],
+    "d3d_dsm_mesh_scratch_bytes": [ctypes.c_longlong, _i, _i],  # returns size_t
+    "d3d_dsm_from_mesh": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _sz, _vp, _vp],
     "d3d_ortho_scratch_bytes": [_i, _i, _i],  # returns size_t
     "d3d_ortho_select": [_vp, _d, _d, _d, _d, _i, _i, _vp, _i, _d, _vp, _sz, _vp, _vp],
     "d3d_ortho_colorize": [_vp, _d, _d, _d, _d, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
@@ -180,7 +182,7 @@ def load():
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name in ("d3d_last_error", "d3d_build_flags", "d3d_h16_format") else
                       ctypes.c_size_t if name in ("d3d_sweep_workspace_bytes", "d3d_sweep_workspace_bytes_for", "d3d_fusion_points_scratch_bytes",
-                                                         "d3d_dsm_scratch_bytes", "d3d_ortho_scratch_bytes",
+                                                         "d3d_dsm_scratch_bytes", "d3d_dsm_mesh_scratch_bytes", "d3d_ortho_scratch_bytes",
                                                          "d3d_mesh_scan_scratch_bytes") else ctypes.c_int)
     if lib.d3d_version() != ABI_VERSION:
         raise LibraryMissing("ABI version mismatch: library %d, binding %d" % (lib.d3d_version(), ABI_VERSION))

@@ -15,6 +15,7 @@
 // MovingAverage: per empty cell, the mean of the non-empty cells of the (2r+1)^2 window (clipped to the raster), summed in
 //             fp64 in the order dy = -r..r, dx = -r..r, divided by the count and rounded once; one launch per iteration.
 // Every step is integer atomics or fixed-order arithmetic: the rasters are bit-reproducible for any point order or split.
+// The DSM from a triangle mesh shares the grid, the key and the fill; its kernels follow the point kernels.
 #include <algorithm>
 #include <cmath>
 
@@ -299,7 +300,221 @@ __global__ __launch_bounds__(DSM_FILL_TILE * DSM_FILL_TILE) void dsm_fill_kernel
     out[(long)y * W + x] = v;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// DSM from a triangle mesh (deep3d_aerial_amd/dsm.py states the semantics, tests/test_dsm_mesh.py restates them).
+// A triangle's vertices are put in lexicographic (x, y, z) order (IEEE total order per component: the order of the weighted sum
+// then depends on the triangle alone, not on its winding or first vertex).  Edge p -> q has endpoints (u, v) in lexicographic
+// (x, y) order and s = +1 if (u, v) == (p, q), else -1; E(p, q, P) = s ((v.x - u.x)(P.y - u.y) - (v.y - u.y)(P.x - u.x)), fp64,
+// no contraction: two triangles sharing an edge evaluate the same magnitudes on it (watertight).  D = E(a, b, c); 0 or
+// non-finite D: no contribution.  w_a = sigma E(b, c, P), w_b = sigma E(c, a, P), w_c = sigma E(a, b, P), sigma = sign(D);
+// the centre is covered when all w >= 0 and W = (w_a + w_b) + w_c > 0, and the sample is
+// fp32(((w_a z_a + w_b z_b) + w_c z_c) / W), dropped outside [z_min, z_max].  A cell keeps the largest sample (atomicMax of
+// dsm_key); cells with none are NaN.
+//
+// small: one lane per triangle tests the centres of its cell range (the XY box's centre range with a one-cell margin, clipped)
+//        when that holds at most DSM_TRI_SMALL cells; larger ranges are appended to the big list (slot order does not matter:
+//        every update is an integer max).
+// big:   a persistent grid of DSM_TRI_GRID workgroups walks the list; chunk k (DSM_TRI_CHUNK consecutive cells of the range, row-major) of
+//        listed triangle q belongs to workgroup (q + k) mod G.  A workgroup reads the list 256 entries at a time and skips the
+//        entries with no chunk of its own, so a triangle over the whole raster costs ceil(W H / 256) chunks spread over every
+//        workgroup (2900 x 2900: 32851 chunks, at most 33 per workgroup), and a list of many barely-big triangles costs each
+//        workgroup one coalesced read per 256 entries plus its own chunks.  The grid is launched whole whatever the list holds
+//        (the host does not read the list's length).
+constexpr int DSM_TRI_SMALL = 64;      // cell ranges of at most this many cells: one lane, no list
+constexpr int DSM_TRI_GRID = 1024;     // workgroups walking the list of larger triangles
+constexpr int DSM_TRI_CHUNK = 256;     // cells of a listed triangle's range per chunk: one per lane
+
+struct DsmTri {
+    double ox[3], oy[3], ex[3], ey[3], t[3];   // edge k (opposite vertex k): origin u, direction v - u, s * sigma
+    double z[3];
+    double x_lo, x_hi, y_lo, y_hi;
+};
+
+__device__ __forceinline__ bool dsm_vtx_less(const float* p, const float* q) {
+    const unsigned px = dsm_key(p[0]), qx = dsm_key(q[0]), py = dsm_key(p[1]), qy = dsm_key(q[1]);
+    return px < qx || (px == qx && (py < qy || (py == qy && dsm_key(p[2]) < dsm_key(q[2]))));
+}
+
+__device__ __forceinline__ void dsm_vtx_swap(float* p, float* q) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float a = p[k];
+        p[k] = q[k];
+        q[k] = a;
+    }
+}
+
+// Edge p -> q of the triangle (slot k): origin, direction and s.
+__device__ __forceinline__ void dsm_edge(const float* p, const float* q, int k, DsmTri& T, double* s) {
+    const bool fwd = p[0] < q[0] || (p[0] == q[0] && p[1] <= q[1]);
+    const float* u = fwd ? p : q;
+    const float* v = fwd ? q : p;
+    T.ox[k] = (double)u[0];
+    T.oy[k] = (double)u[1];
+    T.ex[k] = (double)v[0] - (double)u[0];
+    T.ey[k] = (double)v[1] - (double)u[1];
+    *s = fwd ? 1.0 : -1.0;
+}
+
+__device__ __forceinline__ double dsm_edge_eval(const DsmTri& T, int k, double px, double py) {
+    return T.ex[k] * (py - T.oy[k]) - T.ey[k] * (px - T.ox[k]);
+}
+
+// Face f -> its coverage data; false when the face contributes nothing (an index out of range, a non-finite coordinate, D 0
+// or not finite).
+__device__ __forceinline__ bool dsm_tri_setup(const float* __restrict__ vertices, int n_vertices, const int* __restrict__ faces, long f,
+                                              DsmTri& T) {
+    float v[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int id = faces[3 * f + c];
+        if (id < 0 || id >= n_vertices) return false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            v[c][a] = vertices[3 * (long)id + a];
+            if (!isfinite(v[c][a])) return false;
+        }
+    }
+    if (dsm_vtx_less(v[1], v[0])) dsm_vtx_swap(v[0], v[1]);
+    if (dsm_vtx_less(v[2], v[1])) dsm_vtx_swap(v[1], v[2]);
+    if (dsm_vtx_less(v[1], v[0])) dsm_vtx_swap(v[0], v[1]);
+    double s[3];
+    dsm_edge(v[1], v[2], 0, T, s + 0);   // b -> c
+    dsm_edge(v[2], v[0], 1, T, s + 1);   // c -> a
+    dsm_edge(v[0], v[1], 2, T, s + 2);   // a -> b
+    const double D = s[2] * dsm_edge_eval(T, 2, (double)v[2][0], (double)v[2][1]);
+    if (!(D != 0.0 && isfinite(D))) return false;
+    const double sigma = D > 0.0 ? 1.0 : -1.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        T.t[k] = s[k] * sigma;   // (s sigma) X == sigma (s X) exactly: both only set the sign
+        T.z[k] = (double)v[k][2];
+    }
+    T.x_lo = (double)fminf(fminf(v[0][0], v[1][0]), v[2][0]);
+    T.x_hi = (double)fmaxf(fmaxf(v[0][0], v[1][0]), v[2][0]);
+    T.y_lo = (double)fminf(fminf(v[0][1], v[1][1]), v[2][1]);
+    T.y_hi = (double)fmaxf(fmaxf(v[0][1], v[1][1]), v[2][1]);
+    return true;
+}
+
+// The cell range (columns j0..j1, rows i0..i1) whose centres are tested; false when it misses the raster.
+__device__ __forceinline__ bool dsm_tri_range(const DsmTri& T, const DsmGrid& g, int* j0, int* j1, int* i0, int* i1) {
+    const double a = fmax(floor((T.x_lo - g.x_min) / g.ux) - 1.0, 0.0);
+    const double b = fmin(floor((T.x_hi - g.x_min) / g.ux) + 1.0, (double)(g.W - 1));
+    const double c = fmax(floor((g.y_max - T.y_hi) / g.uy) - 1.0, 0.0);
+    const double d = fmin(floor((g.y_max - T.y_lo) / g.uy) + 1.0, (double)(g.H - 1));
+    if (!(a <= b && c <= d)) return false;
+    *j0 = (int)a;
+    *j1 = (int)b;
+    *i0 = (int)c;
+    *i1 = (int)d;
+    return true;
+}
+
+// The sample of the triangle at the centre of cell (i, j), if it covers it and the sample is inside the Z bounds.
+__device__ __forceinline__ bool dsm_tri_sample(const DsmTri& T, const DsmGrid& g, int i, int j, float* z) {
+    const double px = g.x_min + ((double)j + 0.5) * g.ux;
+    const double py = g.y_max - ((double)i + 0.5) * g.uy;
+    const double w0 = T.t[0] * dsm_edge_eval(T, 0, px, py);
+    const double w1 = T.t[1] * dsm_edge_eval(T, 1, px, py);
+    const double w2 = T.t[2] * dsm_edge_eval(T, 2, px, py);
+    if (!(w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0)) return false;
+    const double W = (w0 + w1) + w2;
+    if (!(W > 0.0)) return false;
+    const float s = (float)(((w0 * T.z[0] + w1 * T.z[1]) + w2 * T.z[2]) / W);
+    const double sd = (double)s;
+    if (!(sd >= g.z_min && sd <= g.z_max)) return false;
+    *z = s;
+    return true;
+}
+
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_tri_small_kernel(const float* __restrict__ vertices, int n_vertices,
+                                                                  const int* __restrict__ faces, int n_faces, DsmGrid g,
+                                                                  unsigned* __restrict__ keymax, int4* __restrict__ big,
+                                                                  int* __restrict__ n_big) {
+    const long f = (long)blockIdx.x * DSM_BLOCK + threadIdx.x;
+    if (f >= n_faces) return;
+    DsmTri T;
+    int j0, j1, i0, i1;
+    if (!dsm_tri_setup(vertices, n_vertices, faces, f, T) || !dsm_tri_range(T, g, &j0, &j1, &i0, &i1)) return;
+    const int nj = j1 - j0 + 1, ni = i1 - i0 + 1;
+    if ((long)nj * ni > DSM_TRI_SMALL) {
+        const int q = atomicAdd(n_big, 1);
+        if (q < n_faces) big[q] = make_int4((int)f, i0 * g.W + j0, nj, ni);   // always true (one slot per face): a guard on the write
+        return;
+    }
+    for (int i = i0; i <= i1; ++i)
+        for (int j = j0; j <= j1; ++j) {
+            float z;
+            if (dsm_tri_sample(T, g, i, j, &z)) atomicMax(keymax + (long)i * g.W + j, dsm_key(z));
+        }
+}
+
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_tri_big_kernel(const float* __restrict__ vertices, int n_vertices,
+                                                                const int* __restrict__ faces, int n_faces, DsmGrid g,
+                                                                const int4* __restrict__ big, const int* __restrict__ n_big,
+                                                                unsigned* __restrict__ keymax) {
+    __shared__ int4 ent[DSM_BLOCK];
+    __shared__ int first[DSM_BLOCK];
+    const int nb = min(*n_big, n_faces);
+    const int G = gridDim.x, b = blockIdx.x, t = threadIdx.x;
+    for (int base = 0; base < nb; base += DSM_BLOCK) {
+        const int q = base + t;
+        int k0 = -1;
+        if (q < nb) {
+            const int4 e = big[q];
+            ent[t] = e;
+            const long chunks = ((long)e.z * e.w + DSM_TRI_CHUNK - 1) / DSM_TRI_CHUNK;
+            const int k = (b - q % G + G) % G;   // this workgroup's first chunk of entry q: (q + k) mod G == b
+            k0 = k < chunks ? k : -1;
+        }
+        first[t] = k0;
+        __syncthreads();
+        const int m = min(DSM_BLOCK, nb - base);
+        for (int e = 0; e < m; ++e) {
+            const int k1 = first[e];   // uniform across the workgroup
+            if (k1 < 0) continue;
+            const int4 en = ent[e];
+            DsmTri T;
+            if (!dsm_tri_setup(vertices, n_vertices, faces, en.x, T)) continue;   // listed faces passed it: a guard
+            const int cells = en.z * en.w;
+            const int j0 = en.y % g.W, i0 = en.y / g.W;
+            for (long k = k1; k * DSM_TRI_CHUNK < cells; k += G)
+                for (int u = 0; u < DSM_TRI_CHUNK; u += DSM_BLOCK) {
+                    const long idx = k * DSM_TRI_CHUNK + u + t;
+                    if (idx >= cells) break;
+                    const int r = (int)(idx / en.z), c = (int)(idx - (long)r * en.z);
+                    const int i = i0 + r, j = j0 + c;
+                    float z;
+                    if (i < g.H && j < g.W && dsm_tri_sample(T, g, i, j, &z)) atomicMax(keymax + (long)i * g.W + j, dsm_key(z));
+                }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(DSM_BLOCK) void dsm_key_finalize_kernel(const unsigned* __restrict__ keymax, int cells,
+                                                                     float* __restrict__ height) {
+    const int c = blockIdx.x * DSM_BLOCK + threadIdx.x;
+    if (c >= cells) return;
+    const unsigned k = keymax[c];
+    height[c] = k ? dsm_unkey(k) : __builtin_nanf("");   // key 0 is the unkeyed NaN: no finite sample has it
+}
+
 static size_t dsm_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct DsmMeshScratch {
+    size_t keymax, n_big, big, total;
+};
+
+static DsmMeshScratch dsm_mesh_layout(long long n_faces, long long cells) {
+    DsmMeshScratch s = {};
+    s.keymax = 0;
+    s.n_big = dsm_align((size_t)cells * 4);
+    s.big = s.n_big + dsm_align(4);
+    s.total = s.big + dsm_align((size_t)n_faces * 16);
+    return s;
+}
 
 struct DsmScratch {
     size_t keymax, rank, offset, partial, keys, big, n_big, total;
@@ -427,5 +642,52 @@ extern "C" int d3d_dsm_fill_moving_average(const float* in, float* out, int W, i
     D3D_REQUIRE(grid.y <= 65535, "H=%d too large", H);
     hipLaunchKernelGGL(dsm_fill_kernel, grid, block, 0, (hipStream_t)stream, in, out, W, H, radius);
     D3D_LAUNCH_CHECK("dsm_fill_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" size_t d3d_dsm_mesh_scratch_bytes(long long n_faces, int W, int H) {
+    if (!dsm_dims_ok(n_faces, W, H)) return 0;
+    return dsm_mesh_layout(n_faces, (long long)W * H).total;
+}
+
+extern "C" int d3d_dsm_from_mesh(const float* vertices, long long n_vertices, const int* faces, long long n_faces, double x_min,
+                                 double y_max, double unit_x, double unit_y, double z_min, double z_max, int W, int H, void* scratch,
+                                 size_t scratch_bytes, float* height, d3d_stream_t stream) {
+    D3D_REQUIRE(height && scratch, "null pointer (height, scratch)");
+    D3D_REQUIRE(vertices || n_vertices == 0, "null pointer (vertices) with %lld vertices", n_vertices);
+    D3D_REQUIRE(faces || n_faces == 0, "null pointer (faces) with %lld faces", n_faces);
+    D3D_REQUIRE(n_vertices >= 0 && n_vertices < (1ll << 31), "n_vertices=%lld (0 .. 2^31 - 1)", n_vertices);
+    D3D_REQUIRE(n_faces >= 0 && n_faces < (1ll << 31), "n_faces=%lld (0 .. 2^31 - 1)", n_faces);
+    D3D_REQUIRE(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "raster %d x %d: size must be >= 1 and W * H < 2^31", W, H);
+    D3D_REQUIRE(std::isfinite(unit_x) && std::isfinite(unit_y) && unit_x > 0.0 && unit_y > 0.0, "unit (%g, %g) must be finite and > 0",
+                unit_x, unit_y);
+    D3D_REQUIRE(std::isfinite(x_min) && std::isfinite(y_max), "border (x_min %g, y_max %g) must be finite", x_min, y_max);
+    D3D_REQUIRE(!std::isnan(z_min) && !std::isnan(z_max) && z_min <= z_max, "z bounds [%g, %g]", z_min, z_max);
+    const long long cells = (long long)W * H;
+    const DsmMeshScratch L = dsm_mesh_layout(n_faces, cells);
+    D3D_REQUIRE(scratch_bytes >= L.total, "scratch of %zu bytes, %zu needed (d3d_dsm_mesh_scratch_bytes)", scratch_bytes, L.total);
+    const uintptr_t h0 = (uintptr_t)height, h1 = h0 + (size_t)cells * 4, s0 = (uintptr_t)scratch, s1 = s0 + scratch_bytes;
+    D3D_REQUIRE(h1 <= s0 || s1 <= h0, "height must not alias scratch");
+    const int nf = (int)n_faces, nc = (int)cells;
+    const DsmGrid g = {x_min, y_max, unit_x, unit_y, z_min, z_max, W, H};
+    hipStream_t st = (hipStream_t)stream;
+    char* s = (char*)scratch;
+    unsigned* keymax = (unsigned*)(s + L.keymax);
+    int* n_big = (int*)(s + L.n_big);
+    int4* big = (int4*)(s + L.big);
+    int rc = hip_status(hipMemsetAsync(keymax, 0, (size_t)cells * 4, st), "dsm mesh: clear keys");
+    if (rc != D3D_OK) return rc;
+    rc = hip_status(hipMemsetAsync(n_big, 0, 4, st), "dsm mesh: clear list");
+    if (rc != D3D_OK) return rc;
+    if (nf > 0) {
+        hipLaunchKernelGGL(dsm_tri_small_kernel, dim3(ceil_div(nf, DSM_BLOCK)), dim3(DSM_BLOCK), 0, st, vertices, (int)n_vertices, faces, nf,
+                           g, keymax, big, n_big);
+        D3D_LAUNCH_CHECK("dsm_tri_small_kernel launch");
+        hipLaunchKernelGGL(dsm_tri_big_kernel, dim3(DSM_TRI_GRID), dim3(DSM_BLOCK), 0, st, vertices, (int)n_vertices, faces,
+                           nf, g, big, n_big, keymax);
+        D3D_LAUNCH_CHECK("dsm_tri_big_kernel launch");
+    }
+    hipLaunchKernelGGL(dsm_key_finalize_kernel, dim3(ceil_div(nc, DSM_BLOCK)), dim3(DSM_BLOCK), 0, st, keymax, nc, height);
+    D3D_LAUNCH_CHECK("dsm_key_finalize_kernel launch");
     return D3D_OK;
 }

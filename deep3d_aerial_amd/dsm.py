@@ -24,9 +24,31 @@ reference wherever it says anything:
 The binning, the per-cell selection and the fill are HIP kernels (csrc/dsm.hip); the results are bit-reproducible for any
 order or split of the points.
 
-    python -m deep3d_aerial_amd.dsm --fused DIR --out FILE.tif --border Xmin,Xmax,Ymin,Ymax[,Zmin,Zmax] --unit ux,uy
-        [--size W,H] [--select Max|Robust_Max] [--trim 0.1] [--min_points 1] [--interpolation none|MovingAverage]
-        [--radius 2] [--iterations 1] [--nodata -9999]
+DSM from a triangle mesh: the reference's default dsm_source "mesh" (run.py:226-232 calls
+mesh2dsm.DSM_from_Mesh, also never shipped).  mesh_to_dsm rasterises vertices [n,3] fp32 and faces [m,3] int32 on the same
+grid, origin, row order and files:
+
+* Samples.  Cell (i, j) samples its centre cx = Xmin + (j + .5) ux, cy = Ymax - (i + .5) uy, in fp64.
+* Triangles.  A face (a, b, c) is used when its indices are in range (mesh_to_dsm refuses others with a ValueError before any
+  launch) and its nine coordinates are finite; its vertices are first put in lexicographic (x, y, z) order (IEEE total order
+  per component), so nothing below depends on the winding or on which vertex comes first.  Everything is fp64 with no
+  contraction.  For a directed edge p -> q with endpoints (u, v) in lexicographic (x, y) order and s = +1 if (u, v) == (p, q),
+  else -1: E(p, q, P) = s ((v.x - u.x)(P.y - u.y) - (v.y - u.y)(P.x - u.x)).  Two triangles that share an edge evaluate the
+  same magnitudes on it, so with the inclusive rule below the raster has no cracks along shared edges.
+* Coverage.  D = E(a, b, c); a triangle whose D is 0 or not finite (vertical walls, degenerate triangles) contributes nothing.
+  Else sigma = sign(D), w_a = sigma E(b, c, P), w_b = sigma E(c, a, P), w_c = sigma E(a, b, P); the centre is covered when
+  all three are >= 0 and W = (w_a + w_b) + w_c > 0, and the sample is z = ((w_a z_a + w_b z_b) + w_c z_c) / W rounded once to
+  fp32.  Only the centres of the triangle's cell range are tested: columns floor((x_lo - Xmin) / ux) - 1 ..
+  floor((x_hi - Xmin) / ux) + 1 and rows floor((Ymax - y_hi) / uy) - 1 .. floor((Ymax - y_lo) / uy) + 1 of its XY box,
+  clipped to the raster (a one-cell margin around every centre the box holds).
+* Selection.  A sample outside [Zmin, Zmax] (when the border has Z bounds) is dropped; a cell's height is its largest sample
+  in the IEEE total order, NaN when it has none.  Only "Max" exists for this source (min_points is 1).  The optional
+  MovingAverage fill is the one above, applied after the raster.
+* The raster is a function of the set of triangles: not of their order, their winding or how the list is split.
+
+    python -m deep3d_aerial_amd.dsm (--fused DIR | --mesh FILE.ply) --out FILE.tif --border Xmin,Xmax,Ymin,Ymax[,Zmin,Zmax]
+        --unit ux,uy [--size W,H] [--select Max|Robust_Max] [--trim 0.1] [--min_points 1]
+        [--interpolation none|MovingAverage] [--radius 2] [--iterations 1] [--nodata -9999]
 """
 import argparse
 import ctypes
@@ -42,6 +64,8 @@ from . import _lib
 SELECT = {"Max": 0, "Robust_Max": 1}
 INTERPOLATION = (None, "none", "MovingAverage")
 MAX_RADIUS = 16
+DSM_TRI_SMALL = 64     # csrc/dsm.hip: triangles whose cell range holds at most this many cells take one lane and no list
+SOURCES = ("pc", "mesh")
 TIFF_LIMIT = 1 << 32   # classic TIFF: 32-bit offsets
 
 
@@ -141,13 +165,7 @@ def points_to_dsm(xyz, grid, select="Max", trim=0.1, min_points=1, interpolation
         raise TypeError("grid must be a DsmGrid")
     if select not in SELECT:
         raise ValueError("select %r: one of %s" % (select, ", ".join(SELECT)))
-    if interpolation not in INTERPOLATION:
-        raise ValueError("interpolation %r: None, 'none' or 'MovingAverage'" % (interpolation,))
-    fill = interpolation == "MovingAverage"
-    if fill and not 1 <= int(radius) <= MAX_RADIUS:   # before any launch
-        raise ValueError("radius %d outside 1..%d" % (radius, MAX_RADIUS))
-    if fill and int(iterations) < 1:
-        raise ValueError("iterations must be >= 1")
+    fill = _check_fill(interpolation, radius, iterations)
     p = _chk(xyz, "xyz", 2)
     if xyz.shape[1] != 3:
         raise ValueError("xyz must be [N,3] (got %s)" % (tuple(xyz.shape),))
@@ -167,6 +185,58 @@ def points_to_dsm(xyz, grid, select="Max", trim=0.1, min_points=1, interpolation
     if fill:
         height = fill_moving_average(height, radius, iterations)
     return height, count
+
+
+def _check_fill(interpolation, radius, iterations):
+    if interpolation not in INTERPOLATION:
+        raise ValueError("interpolation %r: None, 'none' or 'MovingAverage'" % (interpolation,))
+    fill = interpolation == "MovingAverage"
+    if fill and not 1 <= int(radius) <= MAX_RADIUS:   # before any launch
+        raise ValueError("radius %d outside 1..%d" % (radius, MAX_RADIUS))
+    if fill and int(iterations) < 1:
+        raise ValueError("iterations must be >= 1")
+    return fill
+
+
+def mesh_to_dsm(vertices, faces, grid, interpolation=None, radius=2, iterations=1):
+    """vertices [n,3] fp32 and faces [m,3] int32 device tensors -> height [H,W] fp32 with NaN for empty cells (the mesh
+    semantics of this module's docstring), queued on the caller's stream.  interpolation None | "none" | "MovingAverage"
+    (radius 1..16, iterations >= 1).  CPU tensors are refused; so are face indices outside 0..n-1 (ValueError, before any
+    launch: this check reads the index range back to the host)."""
+    from .ops import _chk
+
+    if not isinstance(grid, DsmGrid):
+        raise TypeError("grid must be a DsmGrid")
+    fill = _check_fill(interpolation, radius, iterations)
+    if not isinstance(vertices, torch.Tensor) or not isinstance(faces, torch.Tensor):
+        raise TypeError("vertices and faces must be torch.Tensors")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [n,3] (got %s)" % (tuple(vertices.shape),))
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise ValueError("faces must be a contiguous [m,3] int32 tensor (got %s %s)" % (faces.dtype, tuple(faces.shape)))
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    if nv >= 1 << 31 or nf >= 1 << 31:
+        raise ValueError("%d vertices, %d faces: at most 2^31 - 1 of each" % (nv, nf))
+    if nf:
+        lo, hi = torch.stack([faces.min(), faces.max()]).tolist()
+        if lo < 0 or hi >= nv:
+            raise ValueError("face indices span %d..%d: outside the %d vertices" % (lo, hi, nv))
+    pv = _chk(vertices, "vertices", 2)
+    if not faces.is_cuda:
+        raise RuntimeError("faces is on %s: the DSM is built on the GPU (no CPU fallback)" % faces.device)
+    if faces.device != vertices.device:
+        raise ValueError("vertices on %s, faces on %s" % (vertices.device, faces.device))
+    H, W = grid.shape
+    lib = _lib.load()
+    height = torch.empty((H, W), dtype=torch.float32, device=vertices.device)
+    nbytes = int(lib.d3d_dsm_mesh_scratch_bytes(nf, W, H))
+    scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=vertices.device)
+    rc = lib.d3d_dsm_from_mesh(pv if nv else None, nv, _ptr(faces) if nf else None, nf, grid.x_min, grid.y_max, grid.unit[0],
+                               grid.unit[1], grid.z_min, grid.z_max, W, H, _ptr(scratch), nbytes, _ptr(height), _stream())
+    _lib.check(rc, "d3d_dsm_from_mesh")
+    if fill:
+        height = fill_moving_average(height, radius, iterations)
+    return height
 
 
 # ----------------------------------------------------------------------------------------
@@ -381,6 +451,27 @@ def build_and_write(xyz, settings, device="cuda"):
     return h, c
 
 
+def check_mesh_settings(settings):
+    """The settings a mesh DSM cannot honour, refused before any work: only "Max" exists and min_points is 1."""
+    if settings.get("select", "Max") != "Max":
+        raise ValueError("a DSM from the mesh has only select 'Max' (got %r)" % (settings.get("select"),))
+    if int(settings.get("min_points", 1)) != 1:
+        raise ValueError("a DSM from the mesh has no min_points (got %d; leave it at 1)" % int(settings.get("min_points")))
+
+
+def build_and_write_mesh(vertices, faces, settings, device="cuda"):
+    """The DSM of a mesh (vertices [n,3], faces [m,3]; tensors or arrays) with the settings of build_and_write ("select" Max,
+    "min_points" 1; "trim" is ignored) -> writes the .tif / .tfw; returns height."""
+    check_mesh_settings(settings)
+    grid = DsmGrid(settings["border"], settings.get("unit") or (0.1, 0.1), settings.get("size"))
+    to = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(device=device, dtype=dt).contiguous()
+    h = mesh_to_dsm(to(vertices, torch.float32).reshape(-1, 3), to(faces, torch.int32).reshape(-1, 3), grid,
+                    interpolation=settings.get("interpolation"), radius=settings.get("radius", 2),
+                    iterations=settings.get("iterations", 1))
+    write_dsm(settings["path"], h, grid, nodata=settings.get("nodata", -9999.0))
+    return h
+
+
 def add_arguments(ap, prefix=""):
     """The DSM settings as flags (--<prefix>border, ...); used by this module's CLI and by predict (--dsm_*)."""
     ap.add_argument("--%sborder" % prefix, type=parse_border, default=None, help="Xmin,Xmax,Ymin,Ymax[,Zmin,Zmax] (world units)")
@@ -404,16 +495,36 @@ def settings_from_args(a, path, prefix=""):
             "iterations": g("iterations"), "nodata": g("nodata")}
 
 
+def check_mesh_args(ap, a, prefix=""):
+    """Argument errors for a DSM from the mesh: the point-only settings away from their defaults."""
+    if getattr(a, prefix + "select") != "Max":
+        ap.error("a DSM from the mesh has only --%sselect Max" % prefix)
+    if getattr(a, prefix + "min_points") != 1:
+        ap.error("a DSM from the mesh has no --%smin_points (leave it at 1)" % prefix)
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="DSM from the fused point cloud (pipeline.save_fused's .npz arrays)")
-    ap.add_argument("--fused", required=True, help="folder of the fused arrays (scene sub-folders included)")
+    ap = argparse.ArgumentParser(description="DSM from the fused point cloud (pipeline.save_fused's .npz arrays) or from a mesh")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--fused", help="folder of the fused arrays (scene sub-folders included)")
+    src.add_argument("--mesh", help="mesh file (.ply, as mesh.write_ply writes it)")
     ap.add_argument("--out", required=True, help="DSM file (.tif; the .tfw is written beside it)")
     add_arguments(ap)
     a = ap.parse_args(argv)
     if a.border is None:
         ap.error("--border is required")
+    if a.mesh is not None:
+        check_mesh_args(ap, a)
     if not torch.cuda.is_available():
         raise RuntimeError("the DSM is built on the GPU (no CPU fallback)")
+    if a.mesh is not None:
+        from . import mesh as _mesh
+
+        v, f = _mesh.read_ply(a.mesh)
+        h = build_and_write_mesh(v, f, settings_from_args(a, a.out))
+        print("DSM %s: %d x %d, %d triangles, %d cells filled" % (a.out, h.shape[1], h.shape[0], f.shape[0],
+                                                                 int(torch.isfinite(h).sum())))
+        return a.out
     xyz = load_fused_xyz(a.fused)
     h, c = build_and_write(xyz, settings_from_args(a, a.out))
     print("DSM %s: %d x %d, %d points, %d cells filled" % (a.out, h.shape[1], h.shape[0], xyz.shape[0],

@@ -154,7 +154,7 @@ def dsm_flags(s):
     if s.get("size") is not None:
         args.append("--dsm_size=%s" % ",".join(str(int(x)) for x in s["size"]))
     defaults = (("select", "Max", "%s"), ("trim", 0.1, "%r"), ("min_points", 1, "%d"), ("interpolation", None, "%s"),
-                ("radius", 2, "%d"), ("iterations", 1, "%d"), ("nodata", -9999.0, "%r"))
+                ("radius", 2, "%d"), ("iterations", 1, "%d"), ("nodata", -9999.0, "%r"), ("source", "pc", "%s"))
     for key, default, fmt in defaults:
         v = s.get(key, default)
         if v is not None and v != default:

@@ -81,6 +81,9 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     dsm: None (nothing changes), or the DSM settings {"path", "border", "unit", "size", "select", "trim", "min_points",
     "interpolation", "radius", "iterations", "nodata"} (dsm.build_and_write): the xyz of every result of this rank are
     concatenated, gathered on rank 0 (sharding.gather_points) and the DSM is built and written there; timings gets dsm_s.
+    With "source": "mesh" (needs mesh; select Max, min_points 1) rank 0 rasterises the mesh it has just built instead
+    (dsm.build_and_write_mesh): no point is gathered and there is no collective, so the file does not depend on the number of
+    ranks; timings gets dsm_s on rank 0.  Without "source" (or with "pc") nothing of the above changes.
     ortho: None (nothing changes), or the orthophoto settings {"path", "depth_tolerance", "views_per_batch"} (needs dsm): the
     true orthophoto on that DSM (write_ortho_of) from the views' gathered depth maps, cameras and reference images; rank 0
     writes it; timings gets ortho_s.
@@ -94,6 +97,16 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         _grid = _mesh.MeshGrid(mesh["border"], mesh["voxel"])
         _mesh.check_settings(_grid, mesh.get("trunc"), mesh.get("min_views", _mesh.DEFAULT_MIN_VIEWS),
                              mesh.get("conf_threshold", _mesh.DEFAULT_CONF), mesh.get("views_per_batch"))
+    dsm_source = dsm.get("source", "pc") if dsm is not None else None
+    if dsm is not None:
+        from . import dsm as _dsm
+
+        if dsm_source not in _dsm.SOURCES:
+            raise ValueError("dsm source %r: 'pc' or 'mesh'" % (dsm_source,))
+        if dsm_source == "mesh":
+            if mesh is None:
+                raise ValueError("a DSM from the mesh needs mesh settings: the DSM is rasterised from the mesh")
+            _dsm.check_mesh_settings(dsm)
     if ortho is not None:
         from . import ortho as _ortho
 
@@ -183,10 +196,14 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         timings.update(views=len(mine), predict_s=t1 - t0, allgather_ms=(g1 - g0) * 1e3,
                        allgather_bytes=int(all_maps.numel() * 4), fuse_s=t2 - g1, map_size=(H, W),
                        backend=dist.get_backend() if world_size > 1 else "none")
+    built_mesh = None
     if mesh is not None and rank == 0:
-        write_mesh_of(all_maps, all_cams, mesh, timings=timings)
+        built_mesh = write_mesh_of(all_maps, all_cams, mesh, timings=timings)
     if dsm is not None:
-        built = write_dsm_of(out, dsm, rank, world_size, xyz_device=all_maps.device, timings=timings)
+        if dsm_source == "mesh":
+            built = write_mesh_dsm_of(built_mesh, dsm, device=all_maps.device, timings=timings) if rank == 0 else None
+        else:
+            built = write_dsm_of(out, dsm, rank, world_size, xyz_device=all_maps.device, timings=timings)
         if ortho is not None:
             own = [(images[recs[i]["name"]][0], all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], images[recs[i]["name"]][1])
                    for i in mine]
@@ -262,6 +279,20 @@ def write_dsm_of(results, settings, rank=0, world_size=1, xyz_device="cuda", tim
     if timings is not None:
         timings["dsm_s"] = time.perf_counter() - t0
     return res
+
+
+def write_mesh_dsm_of(built_mesh, settings, device="cuda", timings=None):
+    """Rank 0's DSM of the mesh write_mesh_of returned ((vertices, faces)), written there (dsm.build_and_write_mesh).
+    Returns (height, None): the shape of write_dsm_of's result, with no point count."""
+    from . import dsm as _dsm
+
+    t0 = time.perf_counter()
+    vertices, faces = built_mesh
+    h = _dsm.build_and_write_mesh(vertices, faces, settings, device=device)
+    torch.cuda.synchronize()
+    if timings is not None:
+        timings["dsm_s"] = time.perf_counter() - t0
+    return h, None
 
 
 def add_estimated_normals(views, pairs, fusion_num=10, nei=1):

@@ -563,6 +563,8 @@ def parse_args(argv=None):
 
     ap.add_argument("--dsm", default=None, help="with --fuse: write the DSM of all ranks' fused points to this .tif (+ .tfw), on rank 0")
     _dsm.add_arguments(ap, prefix="dsm_")
+    ap.add_argument("--dsm_source", default="pc", choices=list(_dsm.SOURCES),
+                    help="pc: the fused points; mesh: the surface mesh of --mesh (run.py:226-232 dsm_source)")
     # true orthophoto on the DSM (deep3d_aerial_amd/ortho.py): off by default
     from . import ortho as _ortho
 
@@ -590,6 +592,10 @@ def parse_args(argv=None):
         ap.error("--mesh needs --mesh_border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax")
     if a.mesh is not None:
         _mesh.check_args(ap, a, prefix="mesh_")
+    if a.dsm is not None and a.dsm_source == "mesh":
+        if a.mesh is None:
+            ap.error("--dsm_source mesh needs --mesh (the DSM is rasterised from the mesh)")
+        _dsm.check_mesh_args(ap, a, prefix="dsm_")
     return a
 
 
@@ -619,7 +625,10 @@ def write_display_maps(output_folder, name, depth, prob):
 def _dsm_settings(a):
     from . import dsm as _dsm
 
-    return _dsm.settings_from_args(a, a.dsm, prefix="dsm_")
+    s = _dsm.settings_from_args(a, a.dsm, prefix="dsm_")
+    if getattr(a, "dsm_source", "pc") != "pc":
+        s["source"] = a.dsm_source
+    return s
 
 
 def _ortho_settings(a):

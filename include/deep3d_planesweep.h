@@ -852,6 +852,28 @@ int d3d_dsm_from_points(const float* xyz, long long n_points, double x_min, doub
 int d3d_dsm_fill_moving_average(const float* in, float* out, int W, int H, int radius, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.11 -- digital surface model from a triangle mesh: the reference's CREATEDSM step with dsm_source "mesh"
+ * (run.py:226-232 calls mesh2dsm.DSM_from_Mesh, which the reference never shipped; the semantics are this project's,
+ * deep3d_aerial_amd/dsm.py).  The raster is the one of d3d_dsm_from_points.
+ *   vertices [n_vertices,3] fp32 and faces [n_faces,3] int32 (device), both counts < 2^31.  Cell (i, j) samples its centre
+ *   (x_min + (j + .5) unit_x, y_max - (i + .5) unit_y) in fp64.  A face is used when its indices are in range and its nine
+ *   coordinates finite (others are skipped; the Python layer refuses out-of-range indices), its vertices put in lexicographic
+ *   (x, y, z) order.  Edge p -> q, endpoints (u, v) in lexicographic (x, y) order, s = +1 if (u, v) == (p, q) else -1:
+ *   E(p, q, P) = s ((v.x - u.x)(P.y - u.y) - (v.y - u.y)(P.x - u.x)), fp64, no contraction.  D = E(a, b, c); a face with D 0
+ *   or not finite contributes nothing.  w_a = sigma E(b, c, P), w_b = sigma E(c, a, P), w_c = sigma E(a, b, P), sigma = sign(D);
+ *   the centre is covered when every w >= 0 and W = (w_a + w_b) + w_c > 0; the sample fp32(((w_a z_a + w_b z_b) + w_c z_c) / W)
+ *   is kept when z_min <= z <= z_max.  Only centres in the face's range are tested: columns floor((x_lo - x_min) / unit_x) - 1
+ *   .. floor((x_hi - x_min) / unit_x) + 1, rows floor((y_max - y_hi) / unit_y) - 1 .. floor((y_max - y_lo) / unit_y) + 1 of its
+ *   XY box, clipped to the raster.  height [H,W] fp32: the largest sample in IEEE total order, NaN where there is none.
+ *   scratch: device memory of d3d_dsm_mesh_scratch_bytes(n_faces, W, H) bytes (0 for an out-of-range argument), not
+ *   overlapping height.  Integer atomics only: the raster depends on the set of faces, not on their order or winding.
+ */
+size_t d3d_dsm_mesh_scratch_bytes(long long n_faces, int W, int H);
+int d3d_dsm_from_mesh(const float* vertices, long long n_vertices, const int* faces, long long n_faces, double x_min, double y_max,
+                      double unit_x, double unit_y, double z_min, double z_max, int W, int H, void* scratch, size_t scratch_bytes,
+                      float* height, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.9 -- true orthophoto on the DSM (the reference has no orthophoto step; the semantics are this project's,
  * deep3d_aerial_amd/ortho.py).  The grid is the DSM's: cell (i, j) is X = (x_min + (j + 0.5) unit_x, y_max - (i + 0.5) unit_y, h),
  * h = height[i,j] in fp64; a non-finite h is an empty cell.  A view is one d3d_ortho_view_t record in DEVICE memory, filled by
