@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "mesh_shared.h"
 
 namespace d3d {
 
@@ -35,15 +36,6 @@ struct DsmGrid {
     double x_min, y_max, ux, uy, z_min, z_max;
     int W, H;
 };
-
-__device__ __forceinline__ unsigned dsm_key(float z) {
-    const unsigned u = __float_as_uint(z);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float dsm_unkey(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // The cell of point p, or -1.  Bin and scatter both call this, so they agree on every point.
 __device__ __forceinline__ int dsm_cell(const float* __restrict__ xyz, long p, const DsmGrid& g, float* z_out) {

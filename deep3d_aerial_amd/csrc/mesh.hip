@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "mesh_shared.h"
 
 namespace d3d {
 
@@ -51,29 +52,6 @@ __device__ __forceinline__ long mesh_pad_index(const d3d_mesh_grid_t& g, int bi,
 // ---------------------------------------------------------------------------------------------------------------------------
 // exclusive scan of int32 values: tile sums (int64), one workgroup over the tile sums, then each tile with its offset
 // ---------------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ T mesh_block_exclusive(T x, T* lds, T* total) {
-    // lds: one T per wave
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    T inc = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += y;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    T before = 0, all = 0;
-    for (int w = 0; w < n_waves; ++w) {
-        const T v = lds[w];
-        if (w < wave) before += v;
-        all += v;
-    }
-    __syncthreads();
-    *total = all;
-    return before + inc - x;
-}
-
 __global__ __launch_bounds__(SCAN_BLOCK) void mesh_scan_reduce_kernel(const int* __restrict__ in, long n, long long* __restrict__ tile_sums) {
     __shared__ int lds[SCAN_BLOCK / 64];
     const long base = (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_PER;
@@ -123,7 +101,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void mesh_scan_apply_kernel(const int* 
 
 static long long mesh_scan_tiles(long long n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 
-static int mesh_scan(const int* in, int* out, long long n, void* scratch, long long* total, hipStream_t st) {
+int mesh_scan(const int* in, int* out, long long n, void* scratch, long long* total, hipStream_t st) {
     const long long tiles = mesh_scan_tiles(n);
     long long* sums = (long long*)scratch;
     if (tiles > 0) {

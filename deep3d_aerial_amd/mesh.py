@@ -37,8 +37,31 @@ voxels, and its zero surface by marching tetrahedra.
 The passes are HIP kernels (csrc/mesh.hip) with no float atomics and no order-dependent integer atomics: the mesh is a function
 of the views and their order alone.
 
+Cleaning (clean(); csrc/mesh_clean.hip).  The steps are named after the reference's ReconstructMesh clean
+options (fRemoveSpurious, nSmoothMesh) but the rules are this project's; they do not claim to match OpenMVS / VCG.  The input is
+vertices [n,3] fp32 and faces [m,3] int32 (extract, read_ply); every index must lie in 0 .. n - 1.
+* Edges and adjacency.  The edges of face (a, b, c) are the pairs (a,b), (b,c), (c,a); a pair with equal ends is skipped and an
+  unordered pair counts once per face (a face (a, a, b) has the one edge {a, b}).  N(v) is the set of distinct vertices sharing an
+  edge with v, in increasing index order.  An edge is manifold when exactly two faces have it; a vertex is fixed when one of its
+  edges is not manifold (boundary or non-manifold), or when it has no neighbour.
+* Components.  Faces connect through shared vertices; a vertex no face uses is a component of its own.  A component's label is
+  its smallest vertex index.  Per component: its face count, the fp32 box of its vertices and the box diagonal, in fp64 from the
+  fp32 box: sqrt((dx dx + dy dy) + dz dz).
+* Removal (min_faces > 0 or spurious > 0).  A component goes when min_faces > 0 and its face count is below min_faces, or when
+  spurious > 0 and its diagonal is below D / spurious (fp64), D the diagonal of the box of every vertex some face uses.  The
+  kept faces stay in input order and are renumbered; the kept vertices are those a kept face uses, in input order.
+* Smoothing (smooth = k > 0).  k Jacobi iterations on the kept mesh, its adjacency rebuilt.  A fixed vertex stays; any other moves,
+  per component in fp32 without contraction: s = the sum of x_u over N(v) added in increasing u (from 0),
+  m = s / fp32(|N(v)|), x' = x + lambda (m - x), lambda = fp32(smooth_lambda) in (0, 1] (default 0.5).  Each iteration reads
+  only the previous one's positions.
+* Order: removal, then smoothing (the reference's order).  With every step off the input comes back unchanged.
+The result is a function of the input arrays: shuffling the face list gives the same vertices bit for bit and the same set of
+faces.  Integer atomics only, no float atomics.
+
     python -m deep3d_aerial_amd.mesh --mvs MVS_FOLDER --out mesh.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax --voxel S
         [--trunc T] [--min_views 2] [--conf_threshold 0.2] [--views_per_batch N]
+        [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L]
+    python -m deep3d_aerial_amd.mesh --clean IN.ply --out OUT.ply [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L]
 """
 import argparse
 import ctypes
@@ -52,6 +75,7 @@ from . import _lib
 
 DEFAULT_CONF = 0.2
 DEFAULT_MIN_VIEWS = 2
+DEFAULT_SMOOTH_LAMBDA = 0.5
 BRICK = 8
 
 # the 6 Kuhn tetrahedra (positively oriented), the edges of a tetrahedron, the 16-case table (csrc/mesh.hip has the same)
@@ -274,6 +298,148 @@ def depth_to_mesh(views, grid, trunc=None, min_views=DEFAULT_MIN_VIEWS, conf_thr
 
 
 # ----------------------------------------------------------------------------------------
+# cleaning
+# ----------------------------------------------------------------------------------------
+def check_clean_settings(min_faces=0, spurious=0.0, smooth=0, smooth_lambda=DEFAULT_SMOOTH_LAMBDA):
+    """(min_faces, spurious, smooth, smooth_lambda) checked; 0 turns a step off."""
+    if int(min_faces) != min_faces or int(min_faces) < 0:
+        raise ValueError("min_faces %r must be an integer >= 0" % (min_faces,))
+    spurious = float(spurious)
+    if not (math.isfinite(spurious) and spurious >= 0):
+        raise ValueError("spurious %r must be finite and >= 0" % (spurious,))
+    if int(smooth) != smooth or int(smooth) < 0:
+        raise ValueError("smooth %r must be an integer >= 0" % (smooth,))
+    lam = float(smooth_lambda)
+    if not (0 < lam <= 1):
+        raise ValueError("smooth_lambda %r must lie in (0, 1]" % (smooth_lambda,))
+    return int(min_faces), spurious, int(smooth), lam
+
+
+def _mesh_arrays(vertices, faces):
+    if not (isinstance(vertices, torch.Tensor) and isinstance(faces, torch.Tensor)):
+        raise TypeError("vertices and faces must be tensors")
+    if vertices.device.type != "cuda" or faces.device != vertices.device:
+        raise RuntimeError("the mesh is cleaned on the GPU (no CPU fallback); got %s and %s" % (vertices.device, faces.device))
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [n,3] float32 (got %s %s)" % (tuple(vertices.shape), vertices.dtype))
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces must be [m,3] int32 (got %s %s)" % (tuple(faces.shape), faces.dtype))
+    n, m = int(vertices.shape[0]), int(faces.shape[0])
+    if n >= 1 << 31 or 6 * m >= 1 << 31:
+        raise ValueError("%d vertices, %d faces: at most 2^31 - 1 vertices and 6 m < 2^31" % (n, m))
+    if m and (int(faces.min()) < 0 or int(faces.max()) >= n):
+        raise ValueError("a face index lies outside 0 .. %d" % (n - 1))
+    return vertices.contiguous(), faces.contiguous(), n, m
+
+
+def adjacency(faces, n_vertices):
+    """The CSR of the distinct neighbours: (offset [n+1] int64, nbr [offset[n]] int32, fixed [n] uint8) on the device."""
+    lib = _lib.load()
+    n, m = int(n_vertices), int(faces.shape[0])
+    dev = faces.device
+    nbytes = int(lib.d3d_mesh_adjacency_scratch_bytes(n, m))
+    if nbytes == 0:
+        raise ValueError("%d vertices, %d faces: out of range" % (n, m))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    offset = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    nbr = torch.empty((max(6 * m, 1),), dtype=torch.int32, device=dev)
+    fixed = torch.empty((max(n, 1),), dtype=torch.uint8, device=dev)
+    _lib.check(lib.d3d_mesh_adjacency(_ptr(faces), m, n, _ptr(scratch), nbytes, _ptr(offset), _ptr(nbr), _ptr(fixed), _stream()),
+               "d3d_mesh_adjacency")
+    return offset, nbr, fixed[:n]
+
+
+def components(faces, n_vertices):
+    """(labels [n] int32 on the device: the smallest vertex index of each vertex's component, rounds: hooking launches)."""
+    lib = _lib.load()
+    n, m = int(n_vertices), int(faces.shape[0])
+    label = torch.empty((max(n, 1),), dtype=torch.int32, device=faces.device)
+    flag = torch.zeros((1,), dtype=torch.int32, device=faces.device)
+    rounds = ctypes.c_int(0)
+    _lib.check(lib.d3d_mesh_components(_ptr(faces), m, n, _ptr(label), _ptr(flag), ctypes.byref(rounds), _stream()), "d3d_mesh_components")
+    return label[:n], int(rounds.value)
+
+
+def component_stats(vertices, faces, labels):
+    """Per-label stats, indexed by label (entries of indices that are no label are 0 faces and a NaN box):
+    {"face_count" [n] int32, "box" [n,6] fp32 (min x, y, z, max x, y, z), "diag" [n] fp64, "global_box" [6] fp32,
+    "global_diag" [1] fp64 (the box of every vertex some face uses)} on the device."""
+    lib = _lib.load()
+    n, m = int(vertices.shape[0]), int(faces.shape[0])
+    dev = vertices.device
+    nbytes = int(lib.d3d_mesh_stats_scratch_bytes(n))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    out = {"face_count": torch.empty((max(n, 1),), dtype=torch.int32, device=dev),
+           "box": torch.empty((max(n, 1), 6), dtype=torch.float32, device=dev),
+           "diag": torch.empty((max(n, 1),), dtype=torch.float64, device=dev),
+           "global_box": torch.empty((6,), dtype=torch.float32, device=dev),
+           "global_diag": torch.empty((1,), dtype=torch.float64, device=dev)}
+    _lib.check(lib.d3d_mesh_component_stats(_ptr(vertices), n, _ptr(faces), m, _ptr(labels), _ptr(scratch), nbytes, _ptr(out["face_count"]),
+                                            _ptr(out["box"]), _ptr(out["diag"]), _ptr(out["global_box"]), _ptr(out["global_diag"]),
+                                            _stream()), "d3d_mesh_component_stats")
+    for k in ("face_count", "box", "diag"):
+        out[k] = out[k][:n]
+    return out
+
+
+def remove_components(vertices, faces, min_faces=0, spurious=0.0, info=None):
+    """The removal step alone: (vertices, faces) of the kept components, compacted.  info (a dict) gets rounds and
+    faces_removed."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    min_faces, spurious, _, _ = check_clean_settings(min_faces, spurious)
+    lib = _lib.load()
+    dev = vertices.device
+    labels, rounds = components(faces, n)
+    st = component_stats(vertices, faces, labels)
+    nbytes = int(lib.d3d_mesh_filter_scratch_bytes(m))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    out_faces = torch.empty((max(m, 1), 3), dtype=torch.int32, device=dev)
+    referenced = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    kept = torch.empty((1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_mesh_filter(_ptr(faces), m, n, _ptr(labels), _ptr(st["face_count"]), _ptr(st["diag"]), _ptr(st["global_diag"]),
+                                   min_faces, spurious, _ptr(scratch), nbytes, _ptr(out_faces), _ptr(referenced), _ptr(kept), _stream()),
+               "d3d_mesh_filter")
+    mk = int(kept.item())   # the kept face count sizes the renumbering
+    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(n))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    remap = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    out_v = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev)
+    nk = torch.empty((1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_mesh_compact(_ptr(vertices), n, _ptr(out_faces), mk, _ptr(referenced), _ptr(scratch), nbytes, _ptr(remap), _ptr(out_v),
+                                    _ptr(nk), _stream()), "d3d_mesh_compact")
+    if info is not None:
+        info.update(rounds=rounds, faces_removed=m - mk)
+    return out_v[:int(nk.item())], out_faces[:mk]
+
+
+def smooth_vertices(vertices, faces, iterations, smooth_lambda=DEFAULT_SMOOTH_LAMBDA, csr=None):
+    """The smoothing step alone: the vertices after `iterations` Jacobi iterations (faces unchanged).  csr: adjacency(faces, n)
+    when the caller has it."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    _, _, iterations, lam = check_clean_settings(0, 0.0, iterations, smooth_lambda)
+    if iterations == 0 or n == 0:
+        return vertices.clone()
+    offset, nbr, fixed = csr if csr is not None else adjacency(faces, n)
+    work = torch.empty_like(vertices)
+    out = torch.empty_like(vertices)
+    _lib.check(_lib.load().d3d_mesh_smooth(_ptr(vertices), n, _ptr(offset), _ptr(nbr), _ptr(fixed), lam, iterations, _ptr(work), _ptr(out),
+                                           _stream()), "d3d_mesh_smooth")
+    return out
+
+
+def clean(vertices, faces, min_faces=0, spurious=0.0, smooth=0, smooth_lambda=DEFAULT_SMOOTH_LAMBDA, info=None):
+    """Removal of small components (min_faces, spurious), then `smooth` smoothing iterations, on the device: (vertices, faces).
+    With every step off the input tensors come back as they are."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    min_faces, spurious, smooth, lam = check_clean_settings(min_faces, spurious, smooth, smooth_lambda)
+    if min_faces > 0 or spurious > 0:
+        vertices, faces = remove_components(vertices, faces, min_faces, spurious, info=info)
+    if smooth > 0:
+        vertices = smooth_vertices(vertices, faces, smooth, lam)
+    return vertices, faces
+
+
+# ----------------------------------------------------------------------------------------
 # PLY
 # ----------------------------------------------------------------------------------------
 FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
@@ -369,12 +535,34 @@ def add_arguments(ap, prefix=""):
     ap.add_argument("--%smin_views" % prefix, type=int, default=DEFAULT_MIN_VIEWS, help="views a voxel needs to be observed")
     ap.add_argument("--%sconf_threshold" % prefix, type=float, default=DEFAULT_CONF, help="a pixel is used when its confidence >= this")
     ap.add_argument("--%sviews_per_batch" % prefix, type=int, default=None, help="views per integration call (default: all)")
+    add_clean_arguments(ap, prefix)
+
+
+def add_clean_arguments(ap, prefix=""):
+    """The clean steps as flags (--<prefix>min_faces, ...); all off by default."""
+    ap.add_argument("--%smin_faces" % prefix, type=int, default=0, help="remove components of fewer faces (0: off)")
+    ap.add_argument("--%sspurious" % prefix, type=float, default=0.0,
+                    help="remove components whose box diagonal is below the mesh's divided by this (0: off)")
+    ap.add_argument("--%ssmooth" % prefix, type=int, default=0, help="Laplacian smoothing iterations (0: off)")
+    ap.add_argument("--%ssmooth_lambda" % prefix, type=float, default=DEFAULT_SMOOTH_LAMBDA, help="smoothing step in (0, 1]")
 
 
 def settings_from_args(a, path, prefix=""):
     g = lambda k: getattr(a, prefix + k)
     return {"path": path, "border": g("border"), "voxel": g("voxel"), "trunc": g("trunc"), "min_views": g("min_views"),
-            "conf_threshold": g("conf_threshold"), "views_per_batch": g("views_per_batch")}
+            "conf_threshold": g("conf_threshold"), "views_per_batch": g("views_per_batch"), "min_faces": g("min_faces"),
+            "spurious": g("spurious"), "smooth": g("smooth"), "smooth_lambda": g("smooth_lambda")}
+
+
+def clean_settings(settings):
+    """(min_faces, spurious, smooth, smooth_lambda) of a settings dict, checked; missing keys mean "off"."""
+    return check_clean_settings(settings.get("min_faces") or 0, settings.get("spurious") or 0.0, settings.get("smooth") or 0,
+                                settings.get("smooth_lambda", DEFAULT_SMOOTH_LAMBDA))
+
+
+def clean_requested(settings):
+    min_faces, spurious, smooth, _ = clean_settings(settings)
+    return min_faces > 0 or spurious > 0 or smooth > 0
 
 
 def check_args(ap, a, prefix=""):
@@ -386,28 +574,47 @@ def check_args(ap, a, prefix=""):
     try:
         s = settings_from_args(a, None, prefix)
         check_settings(MeshGrid(s["border"], s["voxel"]), s["trunc"], s["min_views"], s["conf_threshold"], s["views_per_batch"])
+        clean_settings(s)
     except ValueError as e:
         ap.error("--%s*: %s" % (prefix, e))
 
 
 def build_and_write(views, settings):
-    """depth_to_mesh with the settings dict (settings_from_args) and write_ply to settings["path"]: (vertices, faces)."""
+    """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on, and write_ply to
+    settings["path"]: (vertices, faces)."""
     grid = MeshGrid(settings["border"], settings["voxel"])
     v, f = depth_to_mesh(views, grid, settings.get("trunc"), settings.get("min_views", DEFAULT_MIN_VIEWS),
                          settings.get("conf_threshold", DEFAULT_CONF), settings.get("views_per_batch"))
+    if clean_requested(settings):
+        v, f = clean(v, f, *clean_settings(settings))
     write_ply(settings["path"], v, f)
     return v, f
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="surface mesh (binary PLY) from predict's depth maps, confidences and cameras")
-    ap.add_argument("--mvs", required=True, help="predict's output folder: {name}_init.pfm, {name}_prob.pfm and {name}.txt")
+    ap = argparse.ArgumentParser(description="surface mesh (binary PLY) from predict's depth maps, confidences and cameras; or --clean "
+                                             "an existing mesh")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--mvs", help="predict's output folder: {name}_init.pfm, {name}_prob.pfm and {name}.txt")
+    src.add_argument("--clean", metavar="IN_PLY", help="clean this mesh (a PLY write_ply wrote) instead of building one")
     ap.add_argument("--out", required=True, help="mesh file (.ply)")
     add_arguments(ap)
     a = ap.parse_args(argv)
-    check_args(ap, a)
+    if a.clean is not None:
+        try:
+            check_clean_settings(a.min_faces, a.spurious, a.smooth, a.smooth_lambda)
+        except ValueError as e:
+            ap.error("--clean: %s" % e)
+    else:
+        check_args(ap, a)
     if not torch.cuda.is_available():
         raise RuntimeError("the mesh is built on the GPU (no CPU fallback)")
+    if a.clean is not None:
+        v, f = read_ply(a.clean)
+        v, f = clean(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), a.min_faces, a.spurious, a.smooth, a.smooth_lambda)
+        write_ply(a.out, v, f)
+        print("mesh %s: %d vertices, %d triangles cleaned from %s" % (a.out, v.shape[0], f.shape[0], a.clean))
+        return a.out
     views = load_mvs_views(a.mvs)
     v, f = build_and_write(views, settings_from_args(a, a.out))
     print("mesh %s: %d vertices, %d triangles from %d views" % (a.out, v.shape[0], f.shape[0], len(views)))

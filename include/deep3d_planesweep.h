@@ -989,6 +989,58 @@ int d3d_mesh_emit(const d3d_mesh_grid_t* grid, const int* brick_list, const int*
 int d3d_mesh_compact(const float* vertices, long long n_vertices, int* faces, long long n_faces, const int* referenced, void* scratch,
                      size_t scratch_bytes, int* remap, float* out_vertices, long long* n_kept, d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.12 -- cleaning a triangle mesh: adjacency, connected components, removal of small components and Laplacian
+ * smoothing (the reference's ReconstructMesh clean options, with this project's own semantics: deep3d_aerial_amd/mesh.py states
+ * them in full).  A mesh is vertices [n_vertices, 3] fp32 and faces [n_faces, 3] int32; every pointer is DEVICE memory except
+ * `rounds`; faces (and vertices) may be null when there are none.  n_vertices < 2^31 and 6 n_faces < 2^31.  Faces with an index outside 0 .. n_vertices - 1 are skipped (the caller
+ * refuses them).  Integer atomics only: every output is a function of the inputs, whatever the order the lanes run in.
+ */
+/* Scratch of d3d_mesh_adjacency (0 for out-of-range sizes). */
+size_t d3d_mesh_adjacency_scratch_bytes(long long n_vertices, long long n_faces);
+
+/* d3d_mesh_adjacency: the edges of a face are the distinct unordered pairs among (a,b) (b,c) (c,a) with unequal ends; an edge's
+ *   multiplicity is the number of faces it is an edge of.  offset [n_vertices + 1] int64 and nbr (room for 6 n_faces int32,
+ *   offset[n_vertices] written) get the CSR of the distinct neighbours of every vertex in increasing order; fixed [n_vertices]
+ *   uint8 gets 1 where some edge of the vertex does not have multiplicity 2, or the vertex has no edge. */
+int d3d_mesh_adjacency(const int* faces, long long n_faces, long long n_vertices, void* scratch, size_t scratch_bytes, long long* offset,
+                       int* nbr, unsigned char* fixed, d3d_stream_t stream);
+
+/* d3d_mesh_components: label [n_vertices] int32 gets the smallest vertex index of each vertex's component (faces connect
+ *   through shared vertices; a vertex no face uses is its own component).  Hooking and pointer jumping, repeated until a
+ *   hooking launch changes nothing; the host reads flag (one device int32) once per round and waits on the stream.  rounds
+ *   (host, may be null) gets the number of hooking launches. */
+int d3d_mesh_components(const int* faces, long long n_faces, long long n_vertices, int* label, int* flag, int* rounds, d3d_stream_t stream);
+
+/* Scratch of d3d_mesh_component_stats (0 for an out-of-range size). */
+size_t d3d_mesh_stats_scratch_bytes(long long n_vertices);
+
+/* d3d_mesh_component_stats: per label c (a d3d_mesh_components label), face_count [n_vertices] int32 at c: the faces whose first
+ *   vertex has label c; box [n_vertices, 6] fp32 at c: (min x, y, z, max x, y, z) of the vertices labelled c, NaN where no
+ *   vertex has label c; diag [n_vertices] fp64: the box diagonal sqrt((dx dx + dy dy) + dz dz), d = hi - lo in fp64.
+ *   global_box [6] fp32 and global_diag (one fp64) the same for every vertex some face uses (NaN when there is none). */
+int d3d_mesh_component_stats(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* label,
+                             void* scratch, size_t scratch_bytes, int* face_count, float* box, double* diag, float* global_box,
+                             double* global_diag, d3d_stream_t stream);
+
+/* Scratch of d3d_mesh_filter (0 for an out-of-range size). */
+size_t d3d_mesh_filter_scratch_bytes(long long n_faces);
+
+/* d3d_mesh_filter: removes the faces of component c = label[face[0]] when min_faces > 0 and face_count[c] < min_faces, or
+ *   spurious > 0 and diag[c] < *global_diag / spurious (fp64).  out_faces [n_faces, 3] gets the kept faces in input order (the
+ *   first *n_kept, one int64), referenced [n_vertices] int32 gets 1 for every vertex a kept face uses and 0 elsewhere: the
+ *   input of d3d_mesh_compact.  min_faces >= 0, spurious finite and >= 0. */
+int d3d_mesh_filter(const int* faces, long long n_faces, long long n_vertices, const int* label, const int* face_count, const double* diag,
+                    const double* global_diag, long long min_faces, double spurious, void* scratch, size_t scratch_bytes, int* out_faces,
+                    int* referenced, long long* n_kept, d3d_stream_t stream);
+
+/* d3d_mesh_smooth: `iterations` Jacobi steps of the umbrella Laplacian over the CSR of d3d_mesh_adjacency.  A fixed vertex
+ *   stays; any other, per component in fp32 without contraction: s = the sum of its neighbours' values in CSR order (from 0),
+ *   x' = x + lambda (s / fp32(count) - x).  Each step reads the previous step's positions.  out [n_vertices, 3] gets the result,
+ *   work [n_vertices, 3] is the other buffer; vertices, work and out are distinct.  0 < lambda <= 1, iterations >= 0. */
+int d3d_mesh_smooth(const float* vertices, long long n_vertices, const long long* offset, const int* nbr, const unsigned char* fixed,
+                    float lambda, int iterations, float* work, float* out, d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
