@@ -151,6 +151,15 @@ SIGNATURES = {
     "d3d_mesh_filter_scratch_bytes": [ctypes.c_longlong],  # returns size_t
     "d3d_mesh_filter": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_longlong, _d, _vp, _sz, _vp, _vp, _vp, _vp],
     "d3d_mesh_smooth": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp],
+    "d3d_texture_scratch_bytes": [ctypes.c_longlong, _i],  # returns size_t
+    "d3d_texture_select": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _d, _vp, _sz, _vp, _vp],
+    "d3d_texture_edges": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
+    "d3d_texture_charts": [_vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _vp],
+    "d3d_texture_rects": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp],
+    "d3d_texture_fill": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp, _vp],
+    "d3d_texture_empty": [_vp, ctypes.c_longlong, ctypes.c_uint, _vp],
+    "d3d_texture_texcoords": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp,
+                              _vp, _vp],
 }
 
 
@@ -192,7 +201,8 @@ def load():
                       ctypes.c_size_t if name in ("d3d_sweep_workspace_bytes", "d3d_sweep_workspace_bytes_for", "d3d_fusion_points_scratch_bytes",
                                                          "d3d_dsm_scratch_bytes", "d3d_dsm_mesh_scratch_bytes", "d3d_ortho_scratch_bytes",
                                                          "d3d_mesh_scan_scratch_bytes", "d3d_mesh_adjacency_scratch_bytes",
-                                                         "d3d_mesh_stats_scratch_bytes", "d3d_mesh_filter_scratch_bytes") else ctypes.c_int)
+                                                         "d3d_mesh_stats_scratch_bytes", "d3d_mesh_filter_scratch_bytes",
+                                                         "d3d_texture_scratch_bytes") else ctypes.c_int)
     if lib.d3d_version() != ABI_VERSION:
         raise LibraryMissing("ABI version mismatch: library %d, binding %d" % (lib.d3d_version(), ABI_VERSION))
     _lib = lib

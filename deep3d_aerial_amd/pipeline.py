@@ -68,7 +68,7 @@ def _gather_objects(obj, world_size):
 def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checker=None, fusion_num=10, min_geo_consist_num=4,
                      filter_sources=True, partition="block", scene_range=None, skip_line=2, feature_cache_bytes=0,
                      device="cuda", timings=None, display=False, fuse_partition="views", scene_blocks=None,
-                     estimate_normals=False, normal_nei=1, save_normals=False, dsm=None, ortho=None, mesh=None):
+                     estimate_normals=False, normal_nei=1, save_normals=False, dsm=None, ortho=None, mesh=None, texture=None):
     """Runs the three steps above for this rank.  Returns a list, one entry per reference view this rank owns, of
     {"ref", "final_mask" [H,W] bool, "avg_xyz_world" [3,H,W], "points": fuse.extract_points(...) dict} (device tensors).
     timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s.
@@ -91,7 +91,10 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     "views_per_batch"} and optionally the clean steps {"min_faces", "spurious", "smooth", "smooth_lambda"} (absent: off)
     (mesh.settings_from_args): rank 0 builds the mesh of every gathered depth and confidence map with its camera, in global view
     order, cleans it when a clean step is on (mesh.clean), and writes the PLY; the DSM from the mesh uses that mesh.  The
-    other ranks do nothing (no collective: the file does not depend on the number of ranks); timings gets mesh_s on rank 0."""
+    other ranks do nothing (no collective: the file does not depend on the number of ranks); timings gets mesh_s on rank 0.
+    texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad"}
+    (needs mesh; texture.settings_from_args): the mesh rank 0 wrote (after cleaning) textured from every rank's views and
+    reference images (write_texture_of); rank 0 writes the textured PLY and its pages; timings gets texture_s."""
     if mesh is not None:
         from . import mesh as _mesh
 
@@ -116,13 +119,19 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             raise ValueError("ortho needs dsm: the orthophoto is draped on the DSM")
         _ortho.check_tolerance(ortho.get("depth_tolerance", _ortho.DEFAULT_TOLERANCE))
         _ortho.check_views_per_batch(ortho.get("views_per_batch"))
+    if texture is not None:
+        from . import texture as _texture
+
+        if mesh is None:
+            raise ValueError("texture needs mesh: the texture is laid on the mesh")
+        _texture.check_settings(texture)
     if checker is None:
         checker = fuse.ConsistencyChecker(1.0, 0.01, 90.0, 0.2)   # Fuse_Depth_Map's defaults (fusion_3d_normal.py:56-57)
     n = len(dataset)
     recs = view_records(dataset, fusion_num)
     mine = sharding.shard_views(n, rank, world_size, partition)
     cams = {}
-    images = {} if ortho is not None else None
+    images = {} if ortho is not None or texture is not None else None
     t0 = time.perf_counter()
     maps = predict.predict_views(model, dataset, output_folder, rank, world_size, device=device, keep_maps=True,
                                  feature_cache_bytes=feature_cache_bytes, display=display, partition=partition, cams=cams,
@@ -211,6 +220,14 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
                    for i in mine]
             write_ortho_of(built[0] if built is not None else None, dsm, ortho, own, rank, world_size, device=all_maps.device,
                            timings=timings)
+    if texture is not None:
+        own = [(images[recs[i]["name"]][0], all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], images[recs[i]["name"]][1])
+               for i in mine]
+        ids = {}
+        for per in _gather_objects({i: images[recs[i]["name"]][0] for i in mine}, world_size):
+            ids.update(per)
+        cameras = [(ids[i], all_cams[i, 1, :3, :3], all_cams[i, 0], W, H) for i in range(n)]
+        write_texture_of(built_mesh, texture, own, cameras, rank, world_size, device=all_maps.device, timings=timings)
     return out
 
 
@@ -264,6 +281,54 @@ def write_ortho_of(height, dsm_settings, settings, views, rank=0, world_size=1, 
     torch.cuda.synchronize()
     if timings is not None:
         timings["ortho_s"] = time.perf_counter() - t0
+    return res
+
+
+def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1, device="cuda", timings=None):
+    """The mesh rank 0 built ((vertices, faces); None elsewhere) textured from every rank's views, written by rank 0
+    (texture.write_textured_ply).  views: this rank's [(id, K, E, depth [H,W], image)]; cameras: every view's
+    (id, K, E, W, H).  Every rank must call it.
+    Rank 0 broadcasts the mesh (sizes first); each rank selects over its own views (texture.select_faces); one all_reduce(MIN)
+    of the keys; rank 0 lays out the charts, rects and pages (texture.layout) and broadcasts the chart table and page heights;
+    each rank fills the charts of its own views; one all_reduce(SUM) of the pages as packed int32 texels (one rank contributes
+    per texel), then the empty colour.  Returns texture.texture_mesh's dict on rank 0 (without "labels"), None elsewhere."""
+    from . import ortho as _ortho, texture as _tx
+
+    t0 = time.perf_counter()
+    tol, vpb, P, pad = _tx.check_settings(settings)
+    v = f = None
+    if rank == 0:
+        v = built_mesh[0].to(device=device, dtype=torch.float32).contiguous()
+        f = built_mesh[1].to(device=device, dtype=torch.int32).contiguous()
+    v = sharding.broadcast_rows(v, (3,), torch.float32, device)
+    f = sharding.broadcast_rows(f, (3,), torch.int32, device)
+    ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in views]
+    key = _tx.select_faces(v, f, ov, tol, views_per_batch=vpb)
+    if world_size > 1:
+        sharding.all_reduce_raster(key, dist.ReduceOp.MIN)
+    res = None
+    table = heights = None
+    if rank == 0:
+        cams = [_tx.Camera(*c) for c in cameras]
+        chart, _, rects, packing, table_np = _tx.layout(v, f, key, cams, P, pad)
+        table = torch.from_numpy(table_np).to(device)
+        heights = torch.tensor(packing.heights, dtype=torch.int64, device=device)
+        res = {"key": key, "chart": chart, "rects": rects, "packing": packing, "table": table_np}
+    table = sharding.broadcast_rows(table, (8,), torch.int32, device)
+    heights = sharding.broadcast_rows(heights, (), torch.int64, device)
+    table_np = table.cpu().numpy()
+    packing = res["packing"] if rank == 0 else _tx.Packing(table_np[:, [6, 4, 5]].astype(np.int64), heights.cpu().tolist(), P)
+    atlas = _tx.fill_pages(table_np, packing, ov, _tx.new_atlas(packing, device))
+    if world_size > 1:
+        sharding.all_reduce_raster(atlas, dist.ReduceOp.SUM)
+    _tx.finish_pages(atlas)
+    if rank == 0:
+        tc, tn = _tx.texcoords(v, f, key, res["chart"], table_np, packing, cams)
+        res.update(pages=_tx.split_pages(atlas, packing), texcoord=tc, texnumber=tn)
+        _tx.write_textured_ply(settings["path"], v, f, tc, tn, res["pages"])
+    torch.cuda.synchronize()
+    if timings is not None:
+        timings["texture_s"] = time.perf_counter() - t0
     return res
 
 

@@ -575,6 +575,12 @@ def parse_args(argv=None):
 
     ap.add_argument("--mesh", default=None, help="with --fuse: write the surface mesh of all views' depth maps to this .ply, on rank 0")
     _mesh.add_arguments(ap, prefix="mesh_")
+    # texture of the mesh from the views (deep3d_aerial_amd/texture.py): off by default
+    from . import texture as _texture
+
+    ap.add_argument("--texture", default=None,
+                    help="with --fuse --mesh: write the mesh textured from the views to this .ply (+ <stem>_<k>.png pages), on rank 0")
+    _texture.add_arguments(ap, prefix="texture_")
     a = ap.parse_args(argv)
     if a.dsm is not None and not a.fuse:
         ap.error("--dsm needs --fuse (the DSM is built from the fused points)")
@@ -596,6 +602,14 @@ def parse_args(argv=None):
         if a.mesh is None:
             ap.error("--dsm_source mesh needs --mesh (the DSM is rasterised from the mesh)")
         _dsm.check_mesh_args(ap, a, prefix="dsm_")
+    if a.texture is not None and not a.fuse:
+        ap.error("--texture needs --fuse (the mesh is textured from the views of the fusion step)")
+    if a.texture is not None and a.mesh is None:
+        ap.error("--texture needs --mesh (the texture is laid on the mesh)")
+    if a.texture is not None:
+        if not a.texture.endswith(".ply"):
+            ap.error("--texture must end in .ply")
+        _texture.check_args(ap, a, prefix="texture_")
     return a
 
 
@@ -641,6 +655,12 @@ def _mesh_settings(a):
     from . import mesh as _mesh
 
     return _mesh.settings_from_args(a, a.mesh, prefix="mesh_")
+
+
+def _texture_settings(a):
+    from . import texture as _texture
+
+    return _texture.settings_from_args(a, a.texture, prefix="texture_")
 
 
 def main(argv=None):
@@ -692,7 +712,8 @@ def main(argv=None):
                                         normal_nei=a.normal_nei, save_normals=a.save_normals,
                                         dsm=_dsm_settings(a) if a.dsm is not None else None,
                                         ortho=_ortho_settings(a) if a.ortho is not None else None,
-                                        mesh=_mesh_settings(a) if a.mesh is not None else None)
+                                        mesh=_mesh_settings(a) if a.mesh is not None else None,
+                                        texture=_texture_settings(a) if a.texture is not None else None)
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
         if a.dsm is not None and rank == 0:
             print("rank 0/%d: DSM %s in %.2f s" % (world, a.dsm, tm["dsm_s"]))
@@ -700,6 +721,8 @@ def main(argv=None):
             print("rank 0/%d: orthophoto %s in %.2f s" % (world, a.ortho, tm["ortho_s"]))
         if a.mesh is not None and rank == 0:
             print("rank 0/%d: mesh %s in %.2f s" % (world, a.mesh, tm["mesh_s"]))
+        if a.texture is not None and rank == 0:
+            print("rank 0/%d: textured mesh %s in %.2f s" % (world, a.texture, tm["texture_s"]))
         print("rank %d/%d: %d views in %.2f s, all-gather of %.1f MB in %.2f ms (%s), fusion of its %d reference views %.2f s, "
               "%d vertices" % (rank, world, tm["views"], tm["predict_s"], tm["allgather_bytes"] / 1e6, tm["allgather_ms"], tm["backend"],
                                len(res), tm["fuse_s"], sum(int(r["points"]["xyz"].shape[0]) for r in res)))

@@ -177,6 +177,21 @@ def all_reduce_raster(t, op):
     return t
 
 
+def broadcast_rows(t, row_shape, dtype, device, src=0):
+    """A tensor [n, *row_shape] from rank src to every rank: the row count first, then the data (broadcast_raster).  t is the
+    tensor on src (ignored elsewhere).  Returns the tensor on every rank (t itself on src)."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return t
+    rank = dist.get_rank()
+    n = torch.tensor([int(t.shape[0]) if rank == src else 0], dtype=torch.int64, device=device)
+    broadcast_raster(n, src)
+    if rank != src:
+        t = torch.empty((int(n.item()),) + tuple(row_shape), dtype=dtype, device=device)
+    if t.numel():
+        broadcast_raster(t, src)
+    return t
+
+
 def run_sharded(process_view, n_views, rank=None, world_size=None, gather=False, policy="block"):
     """Sweep this rank's views with `process_view(i) -> tensor [2,H,W]` (depth, confidence).
 

@@ -1,0 +1,528 @@
+"""Texturing the surface mesh from the views.
+
+The reference runs OpenMVS's TextureMesh after ReconstructMesh and RefineMesh.  The rules below are this project's own and do
+not claim to match OpenMVS: there is no smoothness term, no photo-consistency test and no seam levelling.
+
+* Input.  vertices [n,3] fp32 and faces [m,3] int32 on the GPU (mesh.extract, mesh.clean, mesh.read_ply), every index in
+  0 .. n - 1; views: ortho.OrthoView records (id, K, E, depth, image) with distinct ids.
+* Face geometry.  Corners a, b, c in fp64; nrm = (b - a) x (c - a) and g = ((a + b) + c) / 3, in fp64 with no contraction, each
+  sum left to right.  A face with nrm = 0 gets no view.
+* Candidate.  ortho's projection (p = R X + t, q = K p, u = q0 / q2, v = q1 / q2).  A view is a candidate for a face when every
+  corner has p2 > 0, q2 > 0, 0 <= u <= W-1 and 0 <= v <= H-1; nrm . (C - g) > 0 (C = ortho.camera_center: the face is
+  front-facing); the depth D at g's pixel (floor(v + .5), floor(u + .5)) is finite and > 0; and p2(g) <= D (1 + depth_tolerance)
+  (default 0.01, as in ortho).
+* Choice.  A = 0.5 |(ub - ua)(vc - va) - (uc - ua)(vb - va)| in fp64, the projected area in pixels; s = 1 / A; the view is
+  rejected when A = 0 or s is not finite.  key = (bits(fp32(s)) << 32) | id; the smallest key wins (the view that sees the face
+  largest, ties to the lower id); the empty key is INT64_MAX.  A minimum does not depend on view order, batching or ranks.
+* Charts.  Two faces are in one chart when they share an edge (an unordered vertex pair, as mesh_clean's edges: (a,b) (b,c)
+  (c,a) with unequal ends) and have the same winning id.  A face with no winner is in no chart (chart -1).  A chart's label is
+  its smallest face index; charts are numbered in increasing label order.
+* Rect.  Each corner's (u, v) in the chart's view with the selection's arithmetic; over the chart's corners
+  x0 = max(0, floor(min u) - pad), x1 = min(W-1, ceil(max u) + pad), y0, y1 alike, all inclusive.  pad >= 1 (default 2), so
+  bilinear taps at any texcoord stay inside the rect.
+* Packing (host, deterministic).  Pages are page_size wide (default 8192, at least every view's W and H).  Page 0 reserves a
+  2 x 2 block of the empty colour at (0, 0): it opens page 0's first shelf.  Charts are sorted by (rect height desc, width desc,
+  label asc) and shelf-packed left to right, top to bottom; a shelf is as tall as its first chart (page 0's first at least 2);
+  a shelf that does not fit under the last one opens a new page.  A page is as tall as the bottom of its last shelf.
+* Atlas.  Texel (ox + dx, oy + dy) of a chart's rect is the RGB of pixel (x0 + dx, y0 + dy) of the chart's view, copied; every
+  other texel is empty_color (default (166, 166, 166), the reference's nColEmpty 0x00A6A6A6).
+* Texcoords.  Per face corner s = (u - x0 + ox + 0.5) / page_width, t = 1 - (v - y0 + oy + 0.5) / page_height, in fp64 (sums
+  left to right), rounded to fp32; texnumber is the page.  A face with no winner gets (1 / page_width, 1 - 1 / H0) at its three
+  corners on page 0, the centre of the empty block (H0 the height of page 0).
+* Files.  <stem>.ply, binary little-endian: one `comment TextureFile <stem>_<k>.png` per page, `element vertex` (float x, y,
+  z), `element face` with `property list uchar int vertex_indices`, `property list uchar float texcoord` (6 values) and
+  `property int texnumber` -- the layout MeshLab reads and OpenMVS writes.  Pages are RGB8 PNGs beside it.
+
+Faces are never reordered or renumbered: a shuffled face list gives the same key per face.  Chart labels, and so the packing,
+follow the face order.  The hot passes are HIP kernels (csrc/texture.hip): select, charts (hooking and pointer jumping over
+(edge, face) pairs that torch.sort orders), rects, fill and texcoords.  No float atomics; the integer atomics are min / max.
+
+    python -m deep3d_aerial_amd.texture --mesh IN.ply --mvs MVS_FOLDER --out OUT.ply [--image_root DIR]
+        [--depth_tolerance 0.01] [--views_per_batch N] [--page_size 8192] [--pad 2]
+"""
+import argparse
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .ortho import (DEFAULT_TOLERANCE, EMPTY_KEY, OrthoView, _ViewRecord, _batches, _check_views, camera_center, check_tolerance,
+                    check_views_per_batch)
+
+DEFAULT_PAGE = 8192
+DEFAULT_PAD = 2
+EMPTY_COLOR = (166, 166, 166)
+BAND = 8   # atlas rows per fill work item (csrc/texture.hip TX_BAND)
+_NONE = EMPTY_KEY
+
+
+class Camera(object):
+    """A view's camera alone: id, K [3,3], E = Tcw [4,4] and the image size.  The rects and texcoords need no more, so rank 0
+    computes them for views whose maps it does not hold.  OrthoView has the same attributes."""
+
+    def __init__(self, id, K, E, W, H):
+        self.id = int(id)
+        K, E = np.asarray(K, np.float64), np.asarray(E, np.float64)
+        if K.shape != (3, 3) or E.shape != (4, 4):
+            raise ValueError("K must be [3,3] and E [4,4] (got %s, %s)" % (K.shape, E.shape))
+        self.K, self.R, self.t = K.copy(), E[:3, :3].copy(), E[:3, 3].copy()
+        self.C = camera_center(self.R, self.t)
+        self.W, self.H = int(W), int(H)
+
+
+def _record(v):
+    r = _ViewRecord()
+    r.R[:] = list(v.R.ravel())
+    r.t[:] = list(v.t)
+    r.K[:] = list(v.K.ravel())
+    r.C[:] = list(v.C)
+    held = isinstance(v, OrthoView)
+    r.depth = v.depth.data_ptr() if held else 0
+    r.rgba = v.rgba.data_ptr() if held else 0
+    r.W, r.H, r.id = v.W, v.H, v.id
+    return r
+
+
+def _table(views, device):
+    """The d3d_ortho_view_t records of `views` sorted by id, in device memory (the kernels look ids up by bisection)."""
+    views = sorted(views, key=lambda v: v.id)
+    ids = [v.id for v in views]
+    if len(set(ids)) != len(ids):
+        raise ValueError("view ids must be unique (got %s)" % ids)
+    arr = (_ViewRecord * max(len(views), 1))(*[_record(v) for v in views])
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device), len(views)
+
+
+def _stream():
+    from . import ops
+
+    return ops._stream()
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _mesh_arrays(vertices, faces):
+    if not (isinstance(vertices, torch.Tensor) and isinstance(faces, torch.Tensor)):
+        raise TypeError("vertices and faces must be tensors")
+    if vertices.device.type != "cuda" or faces.device != vertices.device:
+        raise RuntimeError("the mesh is textured on the GPU (no CPU fallback); got %s and %s" % (vertices.device, faces.device))
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [n,3] float32 (got %s %s)" % (tuple(vertices.shape), vertices.dtype))
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces must be [m,3] int32 (got %s %s)" % (tuple(faces.shape), faces.dtype))
+    n, m = int(vertices.shape[0]), int(faces.shape[0])
+    if n >= 1 << 31 or 3 * m >= 1 << 31:
+        raise ValueError("%d vertices, %d faces: at most 2^31 - 1 vertices and 3 m < 2^31" % (n, m))
+    if m and (int(faces.min()) < 0 or int(faces.max()) >= n):
+        raise ValueError("a face index lies outside 0 .. %d" % (n - 1))
+    return vertices.contiguous(), faces.contiguous(), n, m
+
+
+def _check_key(key, m, device):
+    if not (isinstance(key, torch.Tensor) and key.dtype == torch.int64 and tuple(key.shape) == (m,) and key.is_contiguous()):
+        raise ValueError("key must be a contiguous int64 tensor of shape (%d,)" % m)
+    if key.device != device:
+        raise RuntimeError("key is on %s, the mesh on %s (no CPU fallback)" % (key.device, device))
+
+
+def check_page_size(page_size, views=()):
+    P = int(page_size)
+    if P != page_size or P < 2 or P >= 1 << 20:
+        raise ValueError("page_size %r must be an integer in 2 .. 2^20 - 1" % (page_size,))
+    for v in views:
+        if v.W > P or v.H > P:
+            raise ValueError("page_size %d is smaller than view %d's %d x %d image" % (P, v.id, v.W, v.H))
+    return P
+
+
+def check_pad(pad):
+    if int(pad) != pad or not 1 <= int(pad) < 1 << 20:
+        raise ValueError("pad %r must be an integer >= 1" % (pad,))
+    return int(pad)
+
+
+def check_empty_color(color):
+    c = tuple(int(x) for x in color)
+    if len(c) != 3 or not all(0 <= x <= 255 for x in c):
+        raise ValueError("empty_color %r must be three integers in 0..255" % (color,))
+    return c
+
+
+# ----------------------------------------------------------------------------------------
+# the passes
+# ----------------------------------------------------------------------------------------
+def select_faces(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, views_per_batch=None, key=None):
+    """Min-merges the keys of `views` (OrthoView) into key [m] int64 (a new INT64_MAX vector when None) and returns it.  The
+    result does not depend on the batching or the order of the views."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    tol = check_tolerance(depth_tolerance)
+    vpb = check_views_per_batch(views_per_batch)
+    views = _check_views(views)
+    if key is None:
+        key = torch.full((m,), EMPTY_KEY, dtype=torch.int64, device=vertices.device)
+    _check_key(key, m, vertices.device)
+    lib = _lib.load()
+    for batch in _batches(views, vpb):
+        recs, nv = _table(batch, vertices.device)
+        nbytes = int(lib.d3d_texture_scratch_bytes(m, nv))
+        scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=vertices.device)
+        rc = lib.d3d_texture_select(_ptr(vertices), n, _ptr(faces), m, _ptr(recs), nv, tol, _ptr(scratch), nbytes, _ptr(key), _stream())
+        _lib.check(rc, "d3d_texture_select")
+    return key
+
+
+def charts(faces, key, n_vertices=None):
+    """(chart [m] int32 -- the chart number of each face, -1 without a winner --, labels [n_charts] int64 -- each chart's
+    smallest face index, increasing).  n_vertices: any bound above the largest index (default: faces.max() + 1)."""
+    if not (isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError("faces must be [m,3] int32")
+    if faces.device.type != "cuda":
+        raise RuntimeError("faces are on %s (no CPU fallback)" % faces.device)
+    faces = faces.contiguous()
+    m = int(faces.shape[0])
+    _check_key(key, m, faces.device)
+    if 3 * m >= 1 << 31:
+        raise ValueError("%d faces: 3 m < 2^31" % m)
+    n = int(n_vertices) if n_vertices is not None else (int(faces.max()) + 1 if m else 1)
+    dev = faces.device
+    lib = _lib.load()
+    edge = torch.empty((3 * m,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_texture_edges(_ptr(faces), m, n, _ptr(key), _ptr(edge), _stream()), "d3d_texture_edges")
+    live = torch.nonzero(edge != _NONE).flatten()
+    pair_face = torch.div(live, 3, rounding_mode="floor")
+    pair_edge = edge[live]
+    # order by (edge, winner id): a stable sort by id, then a stable sort by edge
+    o1 = torch.argsort(key[pair_face] & 0xffffffff, stable=True)
+    o2 = torch.argsort(pair_edge[o1], stable=True)
+    perm = o1[o2]
+    edge_sorted = pair_edge[perm].contiguous()
+    face_sorted = pair_face[perm].to(torch.int32).contiguous()
+    del edge, live, pair_face, pair_edge, o1, o2, perm
+    nbytes = int(lib.d3d_texture_scratch_bytes(m, 0))
+    scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    label = torch.empty((max(m, 1),), dtype=torch.int32, device=dev)
+    chart = torch.empty((m,), dtype=torch.int32, device=dev)
+    flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+    total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    rounds = ctypes.c_int(0)
+    rc = lib.d3d_texture_charts(_ptr(edge_sorted), _ptr(face_sorted), int(edge_sorted.shape[0]), _ptr(key), m, _ptr(scratch), nbytes,
+                                _ptr(label), _ptr(chart), _ptr(flag), _ptr(total), ctypes.byref(rounds), _stream())
+    _lib.check(rc, "d3d_texture_charts")
+    labels = torch.nonzero((chart >= 0) & (label[:m] == torch.arange(m, dtype=torch.int32, device=dev))).flatten()
+    if int(labels.shape[0]) != int(total.item()):
+        raise RuntimeError("d3d_texture_charts: %d roots, %d charts" % (int(labels.shape[0]), int(total.item())))
+    return chart, labels
+
+
+def chart_views(key, labels):
+    """The winning id of each chart [n_charts] int32 (the low 32 bits of its label face's key)."""
+    return (key[labels] & 0xffffffff).to(torch.int32)
+
+
+def chart_rects(vertices, faces, key, chart, n_charts, cameras, pad=DEFAULT_PAD):
+    """rect [n_charts, 4] int32 (x0, y0, x1, y1), inclusive, of every chart in its view.  cameras: Camera or OrthoView records
+    of every winning view (ids looked up)."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    pad = check_pad(pad)
+    _check_key(key, m, vertices.device)
+    recs, nc = _table(cameras, vertices.device)
+    rect = torch.empty((max(int(n_charts), 1), 4), dtype=torch.int32, device=vertices.device)
+    rc = _lib.load().d3d_texture_rects(_ptr(vertices), n, _ptr(faces), m, _ptr(key), _ptr(chart.contiguous()), int(n_charts), _ptr(recs),
+                                       nc, pad, _ptr(rect), _stream())
+    _lib.check(rc, "d3d_texture_rects")
+    rect = rect[:int(n_charts)]
+    if n_charts and int(rect[:, 0].max()) == 2 ** 31 - 1:
+        raise ValueError("a chart's view is missing from the cameras")
+    return rect
+
+
+class Packing(object):
+    """place [n_charts, 3] int64 (page, ox, oy) and the page heights; every page is page_size wide."""
+
+    def __init__(self, place, heights, page_size):
+        self.place = place
+        self.heights = [int(h) for h in heights]
+        self.page_size = int(page_size)
+        self.page_row = np.concatenate([[0], np.cumsum(self.heights)]).astype(np.int64)
+
+    @property
+    def n_pages(self):
+        return len(self.heights)
+
+
+def pack(rects, page_size=DEFAULT_PAGE):
+    """Shelf packing of the rects (see the module docstring) on the host.  rects: [n_charts, 4] (x0, y0, x1, y1) inclusive."""
+    r = np.asarray(rects.cpu().numpy() if isinstance(rects, torch.Tensor) else rects, np.int64).reshape(-1, 4)
+    P = check_page_size(page_size)
+    w, h = r[:, 2] - r[:, 0] + 1, r[:, 3] - r[:, 1] + 1
+    nc = r.shape[0]
+    if nc and (w.min() < 1 or h.min() < 1 or w.max() > P or h.max() > P):
+        raise ValueError("rects must be non-empty and at most page_size %d on a side" % P)
+    place = np.zeros((nc, 3), np.int64)
+    order = np.lexsort((np.arange(nc), -w, -h))
+    ws, hs = w[order], h[order]
+    cw = np.concatenate([[0], np.cumsum(ws)])
+    heights, page, y, i, first = [], 0, 0, 0, True
+    while i < nc:   # one iteration per shelf
+        x0 = 2 if first else 0
+        j = int(np.searchsorted(cw, cw[i] + (P - x0), side="right")) - 1   # charts i .. j-1 fit: cw[j] - cw[i] <= P - x0
+        if j == i:   # only on page 0's first shelf: the block alone
+            y, first = 2, False
+            continue
+        sh = max(int(hs[i]), 2) if first else int(hs[i])
+        if y + sh > P:
+            heights.append(y)
+            page, y = page + 1, 0
+        place[order[i:j], 0] = page
+        place[order[i:j], 1] = x0 + cw[i:j] - cw[i]
+        place[order[i:j], 2] = y
+        y += sh
+        i, first = j, False
+    heights.append(max(y, 2))
+    return Packing(place, heights, P)
+
+
+def chart_table(rects, packing, views_of_charts):
+    """The kernels' chart table [n_charts, 8] int32: x0, y0, w, h, ox, oy, page, id (host array)."""
+    r = np.asarray(rects.cpu().numpy() if isinstance(rects, torch.Tensor) else rects, np.int64).reshape(-1, 4)
+    ids = np.asarray(views_of_charts.cpu().numpy() if isinstance(views_of_charts, torch.Tensor) else views_of_charts, np.int64)
+    t = np.stack([r[:, 0], r[:, 1], r[:, 2] - r[:, 0] + 1, r[:, 3] - r[:, 1] + 1, packing.place[:, 1], packing.place[:, 2],
+                  packing.place[:, 0], ids], 1) if r.shape[0] else np.zeros((0, 8), np.int64)
+    return np.ascontiguousarray(t, np.int32)
+
+
+def new_atlas(packing, device):
+    """All pages as one zeroed int32 buffer [sum of heights, page_size] (packed RGBA8 texels)."""
+    return torch.zeros((int(packing.page_row[-1]), packing.page_size), dtype=torch.int32, device=device)
+
+
+def fill_pages(table, packing, views, atlas=None):
+    """Copies the rects of the charts whose view is among `views` (OrthoView) into atlas (new_atlas when None); other texels are
+    left as they are.  table: chart_table.  Returns the atlas."""
+    views = _check_views(views)
+    dev = views[0].depth.device if views else (atlas.device if atlas is not None else torch.device("cuda"))
+    if atlas is None:
+        atlas = new_atlas(packing, dev)
+    if tuple(atlas.shape) != (int(packing.page_row[-1]), packing.page_size) or atlas.dtype != torch.int32 or not atlas.is_contiguous():
+        raise ValueError("atlas must be a contiguous int32 tensor of shape (%d, %d)" % (int(packing.page_row[-1]), packing.page_size))
+    table = np.ascontiguousarray(table, np.int32).reshape(-1, 8)
+    held = np.isin(table[:, 7], [v.id for v in views])
+    nb = np.where(held, (table[:, 3].astype(np.int64) + BAND - 1) // BAND, 0)
+    work = np.stack([np.repeat(np.arange(table.shape[0]), nb), np.arange(int(nb.sum())) - np.repeat(np.cumsum(nb) - nb, nb)], 1)
+    if not work.shape[0] or not views:
+        return atlas
+    check_page_size(packing.page_size, views)
+    recs, nv = _table(views, atlas.device)
+    w = torch.from_numpy(np.ascontiguousarray(work, np.int32)).to(atlas.device)
+    t = torch.from_numpy(table).to(atlas.device)
+    pr = torch.from_numpy(packing.page_row).to(atlas.device)
+    rc = _lib.load().d3d_texture_fill(_ptr(w), int(w.shape[0]), _ptr(t), int(t.shape[0]), _ptr(pr), packing.n_pages, _ptr(recs), nv,
+                                      packing.page_size, _ptr(atlas), _stream())
+    _lib.check(rc, "d3d_texture_fill")
+    return atlas
+
+
+def finish_pages(atlas, empty_color=EMPTY_COLOR):
+    """Every texel no fill wrote becomes the empty colour (alpha 255); in place.  Returns atlas."""
+    c = check_empty_color(empty_color)
+    rc = _lib.load().d3d_texture_empty(_ptr(atlas), int(atlas.numel()), c[0] | c[1] << 8 | c[2] << 16, _stream())
+    _lib.check(rc, "d3d_texture_empty")
+    return atlas
+
+
+def split_pages(atlas, packing):
+    """The pages as host RGB8 arrays [[H_k, page_size, 3] uint8]."""
+    rgb = atlas.contiguous().view(torch.uint8).reshape(atlas.shape[0], atlas.shape[1], 4)[:, :, :3].cpu().numpy()
+    return [np.ascontiguousarray(rgb[packing.page_row[k]:packing.page_row[k + 1]]) for k in range(packing.n_pages)]
+
+
+def texcoords(vertices, faces, key, chart, table, packing, cameras):
+    """(texcoord [m, 6] fp32, texnumber [m] int32) on the GPU."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    _check_key(key, m, vertices.device)
+    dev = vertices.device
+    recs, nc = _table(cameras, dev)
+    table = np.ascontiguousarray(table, np.int32).reshape(-1, 8)
+    t = torch.from_numpy(table if table.shape[0] else np.zeros((1, 8), np.int32)).to(dev)
+    pr = torch.from_numpy(packing.page_row).to(dev)
+    tc = torch.empty((m, 6), dtype=torch.float32, device=dev)
+    tn = torch.empty((m,), dtype=torch.int32, device=dev)
+    rc = _lib.load().d3d_texture_texcoords(_ptr(vertices), n, _ptr(faces), m, _ptr(key), _ptr(chart.contiguous()), _ptr(t),
+                                           int(table.shape[0]), _ptr(pr), packing.n_pages, _ptr(recs), nc, packing.page_size, _ptr(tc),
+                                           _ptr(tn), _stream())
+    _lib.check(rc, "d3d_texture_texcoords")
+    return tc, tn
+
+
+def layout(vertices, faces, key, cameras, page_size=DEFAULT_PAGE, pad=DEFAULT_PAD):
+    """Charts, rects and packing of the selected keys: (chart, labels, rects, packing, table).  cameras: every winning view."""
+    P = check_page_size(page_size, cameras)
+    chart, labels = charts(faces, key, int(vertices.shape[0]))
+    n_charts = int(labels.shape[0])
+    rects = chart_rects(vertices, faces, key, chart, n_charts, cameras, pad)
+    packing = pack(rects, P)
+    table = chart_table(rects, packing, chart_views(key, labels))
+    return chart, labels, rects, packing, table
+
+
+def texture_mesh(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, views_per_batch=None, page_size=DEFAULT_PAGE,
+                 pad=DEFAULT_PAD, empty_color=EMPTY_COLOR):
+    """Every pass on one process: {"key", "chart", "labels", "rects", "packing", "table", "pages" (host RGB8 arrays),
+    "texcoord", "texnumber"}."""
+    views = _check_views(views)
+    check_page_size(page_size, views)
+    key = select_faces(vertices, faces, views, depth_tolerance, views_per_batch)
+    chart, labels, rects, packing, table = layout(vertices, faces, key, views, page_size, pad)
+    atlas = finish_pages(fill_pages(table, packing, views, new_atlas(packing, vertices.device)), empty_color)
+    tc, tn = texcoords(vertices, faces, key, chart, table, packing, views)
+    return {"key": key, "chart": chart, "labels": labels, "rects": rects, "packing": packing, "table": table,
+            "pages": split_pages(atlas, packing), "texcoord": tc, "texnumber": tn}
+
+
+# ----------------------------------------------------------------------------------------
+# files
+# ----------------------------------------------------------------------------------------
+FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,)), ("nt", "u1"), ("t", "<f4", (6,)), ("k", "<i4")])
+
+
+def texture_names(path, n_pages):
+    stem = os.path.basename(str(path))
+    stem = stem[:-4] if stem.endswith(".ply") else stem
+    return ["%s_%d.png" % (stem, k) for k in range(n_pages)]
+
+
+def textured_ply_header(n_vertices, n_faces, texture_files):
+    comments = "".join("comment TextureFile %s\n" % f for f in texture_files)
+    return ("ply\nformat binary_little_endian 1.0\n%selement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "element face %d\nproperty list uchar int vertex_indices\nproperty list uchar float texcoord\nproperty int texnumber\n"
+            "end_header\n" % (comments, n_vertices, n_faces)).encode("ascii")
+
+
+def write_textured_ply(path, vertices, faces, texcoord, texnumber, pages):
+    """Writes <path> (.ply) and its pages <stem>_<k>.png beside it.  Tensors on any device, or arrays; pages: [H_k, W, 3]
+    uint8 arrays.  Returns the paths written (PLY first)."""
+    from PIL import Image
+
+    if not str(path).endswith(".ply"):
+        raise ValueError("the textured mesh path must end in .ply (got %s)" % path)
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    v = np.ascontiguousarray(host(vertices), "<f4").reshape(-1, 3)
+    f = host(faces).reshape(-1, 3)
+    rec = np.empty((f.shape[0],), FACE_DTYPE)
+    rec["n"], rec["v"], rec["nt"] = 3, f, 6
+    rec["t"] = host(texcoord).reshape(-1, 6)
+    rec["k"] = host(texnumber).reshape(-1)
+    names = texture_names(path, len(pages))
+    folder = os.path.dirname(os.path.abspath(str(path)))
+    os.makedirs(folder, exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(textured_ply_header(v.shape[0], f.shape[0], names))
+        fh.write(v.tobytes())
+        fh.write(rec.tobytes())
+    out = [str(path)]
+    for name, page in zip(names, pages):
+        p = os.path.join(folder, name)
+        Image.fromarray(np.ascontiguousarray(page, np.uint8), "RGB").save(p, format="PNG")
+        out.append(p)
+    return out
+
+
+def read_textured_ply(path):
+    """(vertices [n,3] fp32, faces [m,3] int32, texcoord [m,6] fp32, texnumber [m] int32, texture file names) of a file
+    write_textured_ply wrote."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError("%s: not a PLY file" % path)
+    lines = data[:end].decode("ascii").split("\n")
+    counts, files = {}, []
+    for ln in lines:
+        w = ln.split()
+        if len(w) == 3 and w[0] == "element":
+            counts[w[1]] = int(w[2])
+        if len(w) == 3 and w[:2] == ["comment", "TextureFile"]:
+            files.append(w[2])
+    nv, nf = counts.get("vertex"), counts.get("face")
+    if nv is None or nf is None or data[:end + 11] != textured_ply_header(nv, nf, files):
+        raise ValueError("%s: not a PLY file write_textured_ply wrote" % path)
+    body = data[end + 11:]
+    if len(body) != nv * 12 + nf * FACE_DTYPE.itemsize:
+        raise ValueError("%s: %d bytes of data, %d expected" % (path, len(body), nv * 12 + nf * FACE_DTYPE.itemsize))
+    v = np.frombuffer(body[:nv * 12], "<f4").reshape(nv, 3).astype(np.float32)
+    rec = np.frombuffer(body[nv * 12:], FACE_DTYPE)
+    if nf and not ((rec["n"] == 3).all() and (rec["nt"] == 6).all()):
+        raise ValueError("%s: only triangles with 6 texcoords are read" % path)
+    return (v, rec["v"].astype(np.int32).reshape(nf, 3), rec["t"].astype(np.float32).reshape(nf, 6), rec["k"].astype(np.int32),
+            files)
+
+
+# ----------------------------------------------------------------------------------------
+# settings and command line
+# ----------------------------------------------------------------------------------------
+def add_arguments(ap, prefix=""):
+    ap.add_argument("--%sdepth_tolerance" % prefix, type=float, default=DEFAULT_TOLERANCE,
+                    help="a face is hidden from a view when its centroid's depth exceeds the view's depth map by more than this share")
+    ap.add_argument("--%sviews_per_batch" % prefix, type=int, default=None, help="views per selection call (default: all)")
+    ap.add_argument("--%spage_size" % prefix, type=int, default=DEFAULT_PAGE, help="texture page width (>= every image's width and height)")
+    ap.add_argument("--%spad" % prefix, type=int, default=DEFAULT_PAD, help="pixels of margin around every chart's rect (>= 1)")
+
+
+def check_settings(settings):
+    """The settings dict checked: (depth_tolerance, views_per_batch, page_size, pad)."""
+    return (check_tolerance(settings.get("depth_tolerance", DEFAULT_TOLERANCE)), check_views_per_batch(settings.get("views_per_batch")),
+            check_page_size(settings.get("page_size", DEFAULT_PAGE)), check_pad(settings.get("pad", DEFAULT_PAD)))
+
+
+def check_args(ap, a, prefix=""):
+    """The argument errors of the texture settings, reported through ap.error."""
+    try:
+        check_settings(settings_from_args(a, None, prefix))
+    except ValueError as e:
+        ap.error("--%s*: %s" % (prefix, e))
+
+
+def settings_from_args(a, path, prefix=""):
+    g = lambda k: getattr(a, prefix + k)
+    return {"path": path, "depth_tolerance": g("depth_tolerance"), "views_per_batch": g("views_per_batch"), "page_size": g("page_size"),
+            "pad": g("pad")}
+
+
+def build_and_write(vertices, faces, views, settings):
+    """texture_mesh with the settings dict, written to settings["path"]: the result dict."""
+    tol, vpb, P, pad = check_settings(settings)
+    res = texture_mesh(vertices, faces, views, tol, vpb, P, pad)
+    write_textured_ply(settings["path"], vertices, faces, res["texcoord"], res["texnumber"], res["pages"])
+    return res
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="texture a surface mesh (binary PLY) from predict's depth maps, cameras and images")
+    ap.add_argument("--mesh", required=True, help="the mesh (a PLY mesh.write_ply wrote)")
+    ap.add_argument("--mvs", required=True, help="predict's output folder: {name}_init.pfm and {name}.txt")
+    ap.add_argument("--out", required=True, help="textured mesh file (.ply; the <stem>_<k>.png pages are written beside it)")
+    ap.add_argument("--image_root", default=None, help="folder the camera files' relative image paths start from")
+    add_arguments(ap)
+    a = ap.parse_args(argv)
+    check_args(ap, a)
+    if not a.out.endswith(".ply"):
+        ap.error("--out must end in .ply")
+    if not torch.cuda.is_available():
+        raise RuntimeError("the mesh is textured on the GPU (no CPU fallback)")
+    from .mesh import read_ply
+    from .ortho import load_mvs_views
+
+    v, f = read_ply(a.mesh)
+    views = load_mvs_views(a.mvs, a.image_root)
+    res = build_and_write(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), views, settings_from_args(a, a.out))
+    print("textured mesh %s: %d faces, %d charts, %d pages, %d views" % (a.out, f.shape[0], int(res["labels"].shape[0]),
+                                                                        res["packing"].n_pages, len(views)))
+    return a.out
+
+
+if __name__ == "__main__":
+    main()

@@ -1041,6 +1041,66 @@ int d3d_mesh_filter(const int* faces, long long n_faces, long long n_vertices, c
 int d3d_mesh_smooth(const float* vertices, long long n_vertices, const long long* offset, const int* nbr, const unsigned char* fixed,
                     float lambda, int iterations, float* work, float* out, d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.13 -- texturing the surface mesh from the views (the semantics are this project's, deep3d_aerial_amd/texture.py
+ * states them in full; they do not claim to match OpenMVS's TextureMesh).  A mesh is vertices [n_vertices, 3] fp32 and faces
+ * [n_faces, 3] int32, n_vertices < 2^31, 3 n_faces < 2^31; faces with an index outside 0 .. n_vertices - 1 are skipped (the
+ * caller refuses them).  A view is a d3d_ortho_view_t record (ortho's fp64 projection); views and camera tables are DEVICE
+ * arrays, and a camera table (rects, texcoords: depth and rgba unused) or a fill's view list is sorted by increasing id.  Every
+ * pointer is DEVICE memory except `rounds`.  No float atomics; the integer atomics are min / max.
+ */
+/* Scratch of d3d_texture_select and d3d_texture_charts (the larger of the two; 0 for an out-of-range argument). */
+size_t d3d_texture_scratch_bytes(long long n_faces, int n_views);
+
+/* d3d_texture_select: MIN-MERGES the keys of n_views views into key [n_faces] int64 (INT64_MAX before the first call).  Per
+ *   face, in fp64 without contraction: corners a, b, c; nrm = (b - a) x (c - a), g = ((a + b) + c) / 3; a face with nrm = 0 gets
+ *   nothing.  A view is a candidate when every corner has p2 > 0, q2 > 0, 0 <= u <= W-1, 0 <= v <= H-1; nrm . (C - g) > 0; the
+ *   depth D at (floor(v(g) + 0.5), floor(u(g) + 0.5)) is finite and > 0; p2(g) <= D (1 + depth_tolerance).  A =
+ *   0.5 |(ub - ua)(vc - va) - (uc - ua)(vb - va)|, s = 1 / A (rejected when A = 0 or s is not finite), key = (bits(fp32(s)) << 32)
+ *   | id.  A per-block cull over the box of 256 faces only skips work. */
+int d3d_texture_select(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const d3d_ortho_view_t* views,
+                       int n_views, double depth_tolerance, void* scratch, size_t scratch_bytes, long long* key, d3d_stream_t stream);
+
+/* d3d_texture_edges: edge_key [3 n_faces] int64: slot 3 f + k holds the k-th distinct edge {i, j} of face f (the pairs (a,b) (b,c)
+ *   (c,a) with unequal ends, each unordered pair once) as min(i,j) * n_vertices + max(i,j) when key[f] is not INT64_MAX, and
+ *   INT64_MAX otherwise. */
+int d3d_texture_edges(const int* faces, long long n_faces, long long n_vertices, const long long* key, long long* edge_key,
+                      d3d_stream_t stream);
+
+/* d3d_texture_charts: edge_sorted / face_sorted [n_pairs]: the (edge key, face) pairs sorted by edge key, and by the winner's id
+ *   within equal edge keys.  Faces with a winner join when they share an edge and the winner's id; label [n_faces] int32 gets the
+ *   smallest face index of each face's chart (hooking and pointer jumping; the host reads flag, one device int32, once per
+ *   round), chart [n_faces] int32 the chart number (roots numbered in increasing label order) or -1 for a face with no winner,
+ *   n_charts (one device int64) their count.  rounds (host, may be null) gets the number of hooking launches. */
+int d3d_texture_charts(const long long* edge_sorted, const int* face_sorted, long long n_pairs, const long long* key, long long n_faces,
+                       void* scratch, size_t scratch_bytes, int* label, int* chart, int* flag, long long* n_charts, int* rounds,
+                       d3d_stream_t stream);
+
+/* d3d_texture_rects: rect [n_charts, 4] int32 gets (x0, y0, x1, y1), inclusive: over the corners of the chart's faces projected in
+ *   the winner's view (camera table cams, looked up by id), x0 = max(0, floor(min u) - pad), x1 = min(W-1, ceil(max u) + pad), y
+ *   alike.  pad >= 1. */
+int d3d_texture_rects(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const long long* key,
+                      const int* chart, long long n_charts, const d3d_ortho_view_t* cams, int n_cams, int pad, int* rect,
+                      d3d_stream_t stream);
+
+/* d3d_texture_fill: table [n_charts, 8] int32 (x0, y0, w, h, ox, oy, page, id), page_row [n_pages + 1] int64 (page k's rows of
+ *   the atlas are page_row[k] .. page_row[k+1] - 1), atlas [page_row[n_pages], page_width] RGBA8.  work [n_work, 2] int32 lists
+ *   (chart, band): rows 8 band .. 8 band + 7 of the chart's rect.  Texel (ox + dx, oy + dy) of the chart's page gets pixel
+ *   (x0 + dx, y0 + dy) of the view of `id` among this call's views; charts of other views are left as they are. */
+int d3d_texture_fill(const int* work, long long n_work, const int* table, long long n_charts, const long long* page_row, int n_pages,
+                     const d3d_ortho_view_t* views, int n_views, int page_width, unsigned int* atlas, d3d_stream_t stream);
+
+/* d3d_texture_empty: every texel of atlas [n_texels] RGBA8 whose alpha is 0 (no fill wrote it) becomes empty_rgba with alpha 255. */
+int d3d_texture_empty(unsigned int* atlas, long long n_texels, unsigned int empty_rgba, d3d_stream_t stream);
+
+/* d3d_texture_texcoords: texcoord [n_faces, 6] fp32 and texnumber [n_faces] int32.  Corner (u, v) in the chart's view:
+ *   s = (((u - x0) + ox) + 0.5) / page_width, t = 1 - (((v - y0) + oy) + 0.5) / page_height in fp64, rounded to fp32; texnumber the
+ *   page.  A face with no chart gets (1 / page_width, 1 - 1 / height of page 0) at every corner and page 0. */
+int d3d_texture_texcoords(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const long long* key,
+                          const int* chart, const int* table, long long n_charts, const long long* page_row, int n_pages,
+                          const d3d_ortho_view_t* cams, int n_cams, int page_width, float* texcoord, int* texnumber,
+                          d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,148 @@
+"""The texturing kernels (csrc/texture.hip) at survey size: the meshes of tools/mesh_bench.py's scenes (0.5 m and 0.25 m voxels,
+V = 32 and V = 128 views of 2752 x 1856) textured from the same views with synthetic images.  Device-event times of select,
+charts, rects, fill (with the empty-colour pass) and texcoords; faces, charts, pages and candidate views per face; and a per-view
+fp64 torch version of select, checked for the same keys.
+
+    python tools/texture_bench.py [--iters 3] [--views 32,128] [--voxels 0.5,0.25] [--out profiles/texture_bench.json]"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (ROOT, HERE):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import mesh_bench as MB  # noqa: E402
+from deep3d_aerial_amd import mesh, ortho, texture  # noqa: E402
+
+
+def ortho_views(mviews):
+    """OrthoView records of mesh_bench's views, with an 8-bit image that is a function of the pixel (the fill copies it)."""
+    out = []
+    for i, v in enumerate(mviews):
+        ys, xs = torch.meshgrid(torch.arange(MB.H, device="cuda"), torch.arange(MB.W, device="cuda"), indexing="ij")
+        img = torch.stack([(xs + 7 * i) & 255, ys & 255, (xs ^ ys) & 255], -1).to(torch.uint8)
+        E = torch.eye(4, dtype=torch.float64).numpy()
+        E[:3, :3], E[:3, 3] = v.R, v.t
+        out.append(ortho.OrthoView(i, v.K, E, v.depth, img))
+    return out
+
+
+def torch_select(vertices, faces, views, tol=texture.DEFAULT_TOLERANCE):
+    """The comparator: texture.py's selection in fp64 torch, one view at a time over every face."""
+    V = vertices.double()
+    a, b, c = V[faces[:, 0].long()], V[faces[:, 1].long()], V[faces[:, 2].long()]
+    e1, e2 = b - a, c - a
+    nrm = torch.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                       e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+    g = ((a + b) + c) / 3.0
+    live = (nrm != 0).any(1)
+    key = torch.full((faces.shape[0],), texture.EMPTY_KEY, dtype=torch.int64, device=vertices.device)
+    for v in views:
+        R, t, K, C = v.R.tolist(), v.t.tolist(), v.K.tolist(), v.C.tolist()
+
+        def proj(X):
+            p = [R[r][0] * X[:, 0] + R[r][1] * X[:, 1] + R[r][2] * X[:, 2] + t[r] for r in range(3)]
+            q = [K[r][0] * p[0] + K[r][1] * p[1] + K[r][2] * p[2] for r in range(3)]
+            return p[2], q[2], q[0] / q[2], q[1] / q[2]
+
+        ok = live & (nrm[:, 0] * (C[0] - g[:, 0]) + nrm[:, 1] * (C[1] - g[:, 1]) + nrm[:, 2] * (C[2] - g[:, 2]) > 0)
+        uv = []
+        for X in (a, b, c):
+            p2, q2, u, w = proj(X)
+            ok &= (p2 > 0) & (q2 > 0) & (u >= 0) & (u <= v.W - 1) & (w >= 0) & (w <= v.H - 1)
+            uv.append((u, w))
+        p2g, _, ug, vg = proj(g)
+        px = torch.floor((ug + 0.5).nan_to_num(0.0).clamp(0, v.W)).clamp(0, v.W - 1).long()
+        py = torch.floor((vg + 0.5).nan_to_num(0.0).clamp(0, v.H)).clamp(0, v.H - 1).long()
+        D = v.depth.reshape(-1)[py * v.W + px].double()
+        ok &= torch.isfinite(D) & (D > 0) & (p2g <= D * (1.0 + tol))
+        (ua, va), (ub, vb), (uc, vc) = uv
+        A = 0.5 * ((ub - ua) * (vc - va) - (uc - ua) * (vb - va)).abs()
+        ok &= A != 0
+        s = 1.0 / torch.where(ok, A, torch.ones_like(A))
+        ok &= torch.isfinite(s)
+        k = (s.float().view(torch.int32).long() << 32) | v.id
+        key = torch.where(ok & (k < key), k, key)
+    return key
+
+
+def run(views, voxel, iters):
+    grid = mesh.MeshGrid(MB.BORDER, voxel)
+    mviews = views
+    vertices, faces = mesh.depth_to_mesh(mviews, grid)
+    ov = ortho_views(mviews)
+    m = int(faces.shape[0])
+    n = int(vertices.shape[0])
+    lib = texture._lib.load()
+    P = texture._ptr
+    key = torch.empty((m,), dtype=torch.int64, device="cuda")
+    recs, nv = texture._table(ov, "cuda")
+    nbytes = int(lib.d3d_texture_scratch_bytes(m, nv))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device="cuda")
+
+    def select():
+        key.fill_(texture.EMPTY_KEY)
+        texture._lib.check(lib.d3d_texture_select(P(vertices), n, P(faces), m, P(recs), nv, texture.DEFAULT_TOLERANCE, P(scratch), nbytes,
+                                                  P(key), texture._stream()), "select")
+
+    t_select = MB.timed_ms(select, iters)
+    out = {}
+    t_charts = MB.timed_ms(lambda: out.update(c=texture.charts(faces, key, n)), iters)   # includes its flag reads and one sync
+    chart, labels = out["c"]
+    nc = int(labels.shape[0])
+    t_rects = MB.timed_ms(lambda: out.update(r=texture.chart_rects(vertices, faces, key, chart, nc, ov)), iters)
+    rects = out["r"]
+    packing = texture.pack(rects)
+    table = texture.chart_table(rects, packing, texture.chart_views(key, labels))
+    atlas = texture.new_atlas(packing, "cuda")
+    t_fill = MB.timed_ms(lambda: texture.finish_pages(texture.fill_pages(table, packing, ov, atlas.zero_())), iters)
+    t_tc = MB.timed_ms(lambda: texture.texcoords(vertices, faces, key, chart, table, packing, ov), iters)
+    # candidates per face: the views whose tests pass (select over each view alone)
+    cand = torch.zeros((m,), dtype=torch.int32, device="cuda")
+    for v in ov:
+        cand += (texture.select_faces(vertices, faces, [v]) != texture.EMPTY_KEY).int()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    tk = torch_select(vertices, faces, ov)
+    e1.record()
+    torch.cuda.synchronize()
+    return {"views": len(ov), "voxel_m": voxel, "faces": m, "vertices": n, "seen_faces": int((key != texture.EMPTY_KEY).sum()),
+            "charts": nc, "pages": packing.n_pages, "atlas_texels": int(atlas.numel()), "mean_candidates_per_face": round(float(cand.double().mean()), 3),
+            "select_ms": round(t_select, 3), "charts_ms": round(t_charts, 3), "rects_ms": round(t_rects, 3), "fill_ms": round(t_fill, 3),
+            "texcoords_ms": round(t_tc, 3), "torch_select_ms": round(e0.elapsed_time(e1), 1), "torch_same_keys": bool(torch.equal(tk, key)),
+            "face_view_tests": m * len(ov)}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--views", default="32,128")
+    ap.add_argument("--voxels", default="0.5,0.25")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "texture_bench.json"))
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("tools/texture_bench.py measures the GPU kernels: no GPU here")
+    rows = []
+    for nv in [int(x) for x in a.views.split(",")]:
+        views = MB.make_views(nv, "cuda")
+        for voxel in [float(x) for x in a.voxels.split(",")]:
+            r = run(views, voxel, a.iters)
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+        del views
+        torch.cuda.empty_cache()
+    res = {"device": torch.cuda.get_device_name(0), "image": [MB.W, MB.H], "border": MB.BORDER, "runs": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    return res
+
+
+if __name__ == "__main__":
+    main()
