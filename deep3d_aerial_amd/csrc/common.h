@@ -49,9 +49,14 @@ __device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
 // intervals of error on its own in bf16 and they add in quadrature to 0.9 - 1.4 -- against the 0.25 the parity bar allows; no
 // subset of sites kept in fp32 helps (profiles/r05_bf16_ablation.txt).  Half has the same bytes, the same matrix-core rate
 // (v_mfma_f32_16x16x32_f16), single-instruction conversions both ways (v_cvt_pk_f16_f32, v_cvt_f32_f16) and an eighth of the
-// rounding error.  Its range (6e-8 .. 65504) covers BN-normalised activations and weights; the one operand whose magnitude the
-// data decides, the variance volume, saturates instead of overflowing (sweep_device.h).  The split-operand kernels (fp32 mode,
-// "bf16x3") keep their three bf16 pieces: 24 significand bits need bf16's exponent range in the low pieces.
+// rounding error.  Its range (6e-8 .. 65504) covers BN-normalised activations and weights, but not every value the data decides:
+// feature maps leave their nets without a normalisation, so a variance volume, a correlation plane and the layers after them can
+// pass 65504.  The contract: every conversion of a DATA value to h16 saturates to +-(largest finite value) instead of becoming
+// inf (pack_h16x2_sat below; round to nearest even below that), so one large value cannot turn a GroupNorm or a softmax into
+// NaN.  A bare pack_h16x2 / cvt_h16x4 is left only where the value is bounded by construction or is a weight, and that line
+// says why with an "h16-raw:" comment (tests/test_h16_range.py holds the sources to this).  What +-inf and NaN become is not
+// part of the contract.  The split-operand kernels (fp32 mode, "bf16x3") keep their three bf16 pieces: 24 significand bits
+// need bf16's exponent range in the low pieces.
 // ---------------------------------------------------------------------------------------
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 #ifdef D3D_H16_BF16
@@ -83,12 +88,29 @@ __device__ __forceinline__ f32x4_t mfma_h16(h16x8 a, h16x8 b, f32x4_t c) { retur
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4_t mfma_h16_k16(h16x4 a, h16x4 b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
 #endif
+// fp32 clamped to IEEE half's finite range, one v_med3_f32: RNE of the result is the saturating conversion (a plain
+// v_cvt_f16_f32 turns anything from 65520 on into inf).  Also what the fp16 storage volume of config 5 stores through.
+__device__ __forceinline__ float sat_f16(float v) { return __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f); }
+// The saturating form of pack_h16x2 (the contract above).  bfloat16 has fp32's exponent range (no fp32 value of a model comes
+// near its limit): there it is the plain conversion.
+__device__ __forceinline__ unsigned pack_h16x2_sat(float a, float b) {
+#ifdef D3D_H16_BF16
+    return pack_h16x2(a, b);
+#else
+    return pack_h16x2(sat_f16(a), sat_f16(b));
+#endif
+}
 __device__ __forceinline__ h16x4 cvt_h16x4(float a, float b, float c, float d) {   // two packed conversions
     typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(h16x4, (u32x2_t){pack_h16x2(a, b), pack_h16x2(c, d)});
 }
-// one value rounded to the format and back (what a kernel that keeps fp32 values "as the matrix cores see them" applies)
-__device__ __forceinline__ float round_h16(float v) { return h16_lo(pack_h16x2(v, 0.0f)); }
+__device__ __forceinline__ h16x4 cvt_h16x4_sat(float a, float b, float c, float d) {
+    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(h16x4, (u32x2_t){pack_h16x2_sat(a, b), pack_h16x2_sat(c, d)});
+}
+// one data value rounded to the format and back, saturating as the stores do (what a kernel that keeps fp32 values "as the
+// matrix cores see them" applies)
+__device__ __forceinline__ float round_h16(float v) { return h16_lo(pack_h16x2_sat(v, 0.0f)); }
 
 // sigmoid and tanh of the conv-GRU epilogues (adamvs.py:60-72 / module.py ConvGRUCell: torch.sigmoid, torch.tanh): one v_exp_f32
 // and one v_rcp_f32 each, ~2e-7 of the exact value (relative for the sigmoid, absolute for the tanh) -- far inside what the

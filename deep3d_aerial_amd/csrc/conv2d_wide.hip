@@ -53,7 +53,7 @@ struct WideParams {
 };
 
 __device__ __forceinline__ unsigned pack_h16_w(float a, float b) {
-    return pack_h16x2(a, b);   // one packed conversion (common.h: pack_h16x2)
+    return pack_h16x2_sat(a, b);   // one med3 per value + one packed conversion (common.h: pack_h16x2_sat)
 }
 
 template <int NW, bool GN = false>

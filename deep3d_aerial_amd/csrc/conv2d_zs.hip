@@ -68,7 +68,7 @@ __device__ __forceinline__ unsigned pack_bf16_z2(float a, float b) {   // the sp
     return pack_bf16x2(a, b);   // one v_cvt_pk_bf16_f32 (common.h)
 }
 __device__ __forceinline__ unsigned pack_h16_z2(float a, float b) {    // the single 16-bit operand (common.h)
-    return pack_h16x2(a, b);
+    return pack_h16x2_sat(a, b);
 }
 // Global memory through buffer instructions: a raw buffer from `origin` on (which may lie before the tensor) + a 32-bit per-lane
 // byte offset + a scalar offset.  A lane whose pixels are outside the image carries OOBZ: the load returns zeros, the store is

@@ -53,7 +53,7 @@ __device__ __forceinline__ unsigned pack_bf16(float a, float b) {   // the split
     return pack_bf16x2(a, b);   // one v_cvt_pk_bf16_f32 (common.h)
 }
 __device__ __forceinline__ unsigned pack_h16(float a, float b) {    // the single 16-bit operand / stored activation (common.h)
-    return pack_h16x2(a, b);
+    return pack_h16x2_sat(a, b);
 }
 
 // waves per SIMD the register budget is sized for: two workgroups per CU (the second one's loads and stores fly while the

@@ -40,7 +40,7 @@ struct S2Params {
 };
 
 __device__ __forceinline__ unsigned pack_h16_cl(float a, float b) {
-    return pack_h16x2(a, b);   // one packed conversion (common.h: pack_h16x2)
+    return pack_h16x2_sat(a, b);   // one med3 per value + one packed conversion (common.h: pack_h16x2_sat)
 }
 __device__ __forceinline__ f4 unpack_h16x4_cl(uint2 u) {
     return (f4){h16_lo(u.x), h16_hi(u.x),

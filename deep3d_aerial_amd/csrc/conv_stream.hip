@@ -154,7 +154,7 @@ __global__ __launch_bounds__(SPLIT ? 512 : 256) void conv_stream_kernel(ConvZPar
                     const float w = p.wpack[((long)(ok ? tt : 0) * Ci + (ok ? ci : 0)) * MP + m];
                     v[q] = ok ? w : 0.0f;
                 }
-                wl16[r1 * WS + m] = cvt_h16x4(v[0], v[1], v[2], v[3]);
+                wl16[r1 * WS + m] = cvt_h16x4(v[0], v[1], v[2], v[3]);   // h16-raw: a weight fragment
             }
         }
         const int rows = BF16 ? 0 : p.ntaps * CiP;
@@ -470,7 +470,7 @@ __global__ __launch_bounds__(SPLIT ? 512 : 256) void conv_stream_kernel(ConvZPar
         asm volatile("" : "+v"(grpo), "+v"(xso), "+s"(nit));
         if constexpr (BF16) {
             bf4v* xw8 = reinterpret_cast<bf4v*>(xw);
-            auto pack = [](float a0, float a1, float a2, float a3) { return cvt_h16x4(a0, a1, a2, a3); };
+            auto pack = [](float a0, float a1, float a2, float a3) { return cvt_h16x4_sat(a0, a1, a2, a3); };   // the data operand: saturates
 #pragma unroll
             for (int b = 0; b < PF / 16; ++b) {
                 if (b < nit) {

@@ -44,7 +44,7 @@ __device__ __forceinline__ unsigned pack_bf16_t2(float a, float b) {   // the sp
     return pack_bf16x2(a, b);   // one v_cvt_pk_bf16_f32 (common.h)
 }
 __device__ __forceinline__ unsigned pack_h16_t2(float a, float b) {    // the single 16-bit operand / stored activation (common.h)
-    return pack_h16x2(a, b);
+    return pack_h16x2_sat(a, b);
 }
 
 constexpr int ntaps(int pz, int py, int px) { return (1 + pz) * (1 + py) * (1 + px); }

@@ -68,7 +68,7 @@ struct T2PParams {
 };
 
 __device__ __forceinline__ unsigned pack_h16_p(float a, float b) {
-    return pack_h16x2(a, b);   // one packed conversion (common.h: pack_h16x2)
+    return pack_h16x2_sat(a, b);   // one med3 per value + one packed conversion (common.h: pack_h16x2_sat)
 }
 
 __device__ __forceinline__ f4 unpack_h16x4_p(uint2 u) {

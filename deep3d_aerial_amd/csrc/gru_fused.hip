@@ -68,7 +68,7 @@ struct GruParams {
 };
 
 __device__ __forceinline__ unsigned pack_h16_g(float a, float b) {
-    return pack_h16x2(a, b);   // one packed conversion (common.h: pack_h16x2)
+    return pack_h16x2_sat(a, b);   // one med3 per value + one packed conversion (common.h: pack_h16x2_sat)
 }
 // raw buffer over a tensor from `origin` on (which may lie before the tensor: lanes that would read there carry OOB offsets)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tensor_rsrc(const void* origin) {
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(GNT, (GruGeom<CP, HID, S, MG, TY>::LDS <= 80 * 1024
             if (hcell[r] < 0) continue;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                *reinterpret_cast<u2*>(XA + hcell[r] + i * XC) = (u2){pack_h16_g(sh[r][0][i], sh[r][1][i]), pack_h16_g(sh[r][2][i], sh[r][3][i])};
+                *reinterpret_cast<u2*>(XA + hcell[r] + i * XC) = (u2){pack_h16x2(sh[r][0][i], sh[r][1][i]), pack_h16x2(sh[r][2][i], sh[r][3][i])};   // h16-raw: the GRU state, |h| <= 1
         }
     };
 
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(GNT, (GruGeom<CP, HID, S, MG, TY>::LDS <= 80 * 1024
                 }
                 if (lane_h) {
                     const f4 rh = rgate * hh[t];
-                    const unsigned p01 = pack_h16_g(rh[0], rh[1]), p23 = pack_h16_g(rh[2], rh[3]);
+                    const unsigned p01 = pack_h16x2(rh[0], rh[1]), p23 = pack_h16x2(rh[2], rh[3]);   // h16-raw: r * h, r in (0, 1), |h| <= 1
                     unsigned char* dst = XA + (t < NCT ? rwr_c + t * (2 * PITCH * XC) : rwr_h);
                     *reinterpret_cast<unsigned short*>(dst) = (unsigned short)p01;
                     *reinterpret_cast<unsigned short*>(dst + XC) = (unsigned short)(p01 >> 16);

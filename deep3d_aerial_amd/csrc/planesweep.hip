@@ -161,7 +161,9 @@ __device__ __forceinline__ TapD make_tap_direct(float u, float v, int h, int w) 
 __device__ __forceinline__ float ldf(const float* p) { return *p; }
 __device__ __forceinline__ float ldf(const __half* p) { return __half2float(*p); }
 __device__ __forceinline__ void stf(float* p, float v) { *p = v; }
-__device__ __forceinline__ void stf(__half* p, float v) { *p = __float2half_rn(v); }
+__device__ __forceinline__ void stf(__half* p, float v) {   // RNE, saturating at +-65504 like every h16 data store (common.h)
+    *p = __float2half_rn(sat_f16(v));
+}
 
 template <typename T>
 __device__ __forceinline__ float gather4(const T* __restrict__ f, const TapD& t) {

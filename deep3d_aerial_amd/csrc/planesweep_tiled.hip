@@ -252,7 +252,7 @@ __device__ __forceinline__ TapL geo_ring(const Ray& r, float tx, float ty, float
 
 // fp16 storage: one 2-byte store per lane (a wave writes two 64-byte row segments per channel and plane)
 __device__ __forceinline__ void store_sbase_h(unsigned long long sb, unsigned byte_off, float v) {
-    const _Float16 hv = (_Float16)v;   // RNE
+    const _Float16 hv = (_Float16)sat_f16(v);   // RNE, saturating like every h16 data store (common.h)
     const unsigned bits = __builtin_bit_cast(unsigned short, hv);
     asm volatile("global_store_short %0, %1, %2 nt" : : "v"(byte_off), "v"(bits), "s"(sb));
 }

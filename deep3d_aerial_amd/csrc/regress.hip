@@ -509,8 +509,8 @@ __global__ __launch_bounds__(tail::NT, 2) void slice_tail_kernel(tail::Params p)
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r)
             if (scell[r] >= 0)
-                *reinterpret_cast<u4t*>(dst + scell[r]) = (u4t){pack_h16x2(stg[r][0], stg[r][1]), pack_h16x2(stg[r][2], stg[r][3]),
-                                                                 pack_h16x2(stg[r][4], stg[r][5]), pack_h16x2(stg[r][6], stg[r][7])};
+                *reinterpret_cast<u4t*>(dst + scell[r]) = (u4t){pack_h16x2_sat(stg[r][0], stg[r][1]), pack_h16x2_sat(stg[r][2], stg[r][3]),
+                                                                 pack_h16x2_sat(stg[r][4], stg[r][5]), pack_h16x2_sat(stg[r][6], stg[r][7])};
     };
 
     // ---- upconv1 on the matrix cores: wave = state2 row, two 16-pixel groups; K offsets per (parity class, K block) once -------
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(tail::NT, 2) void slice_tail_kernel(tail::Params p)
                 lo = __builtin_elementwise_max(lo, (f4t){0, 0, 0, 0}); hi = __builtin_elementwise_max(hi, (f4t){0, 0, 0, 0});
                 if (p.skip_after) { lo = slo + lo; hi = shi + hi; }   // (ConvTransReLU, then the skip: the tile kernel's `skip + y`)
                 // zeros outside the image: what the head's bounds tests read there
-                unsigned q0 = pack_h16x2(lo[0], lo[1]), q1 = pack_h16x2(lo[2], lo[3]), q2 = pack_h16x2(hi[0], hi[1]), q3 = pack_h16x2(hi[2], hi[3]);
+                unsigned q0 = pack_h16x2_sat(lo[0], lo[1]), q1 = pack_h16x2_sat(lo[2], lo[3]), q2 = pack_h16x2_sat(hi[0], hi[1]), q3 = pack_h16x2_sat(hi[2], hi[3]);
                 if (!rowin || kvo[mg][0] == OOB) q0 = 0;
                 if (!rowin || kvo[mg][1] == OOB) q1 = 0;
                 if (!rowin || kvo[mg][2] == OOB) q2 = 0;

@@ -107,12 +107,7 @@ __device__ __forceinline__ void store_sbase(unsigned long long sb, unsigned byte
 // their nets without a normalisation), and so is the weighted correlation of the slice models: in the half format they SATURATE
 // at the largest finite magnitude instead of becoming inf (one v_med3_f32 per value).
 __device__ __forceinline__ unsigned long long pack_h16x4(const float __attribute__((ext_vector_type(4)))& v) {
-#ifdef D3D_H16_BF16
-    const unsigned a = pack_h16x2(v[0], v[1]), b = pack_h16x2(v[2], v[3]);
-#else
-    auto sat = [](float x) { return __builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f); };   // (a correlation can be negative)
-    const unsigned a = pack_h16x2(sat(v[0]), sat(v[1])), b = pack_h16x2(sat(v[2]), sat(v[3]));
-#endif
+    const unsigned a = pack_h16x2_sat(v[0], v[1]), b = pack_h16x2_sat(v[2], v[3]);   // (a correlation can be negative)
     return (unsigned long long)a | ((unsigned long long)b << 32);
 }
 // ... and EIGHT of them (two finished quads) as one 16-byte store: a lane's stores are 64 cells apart from its

@@ -164,6 +164,27 @@ def sharpen_state_dict_(state_dict, gain):
     return n
 
 
+FEATURE_OUTPUT_SUFFIXES = ("feature.out1.weight", "feature.out2.weight", "feature.out3.weight")
+
+
+def scale_features_state_dict_(state_dict, gain):
+    """Multiplies the linear output layers of the feature net (feature.out1 .. out3: the 1 x 1 / 3 x 3 convolutions without a
+    normalisation or activation behind them, cas_mvsnet.py, adamvs.py, msrednet.py) by `gain`, in place, so every feature map
+    the cost volumes are built from is `gain` times larger.  A trained network's features are not normalised, and the variance
+    / correlation of features of magnitude ~256 passes the largest finite value of IEEE half (65504): the h16-range tests
+    (tests/test_h16_range_gpu.py) use this to put production-size volumes past that limit.  Returns the number of tensors
+    scaled."""
+    import torch
+
+    n = 0
+    with torch.no_grad():
+        for k, t in state_dict.items():
+            if k.endswith(FEATURE_OUTPUT_SUFFIXES):
+                t.mul_(float(gain))
+                n += 1
+    return n
+
+
 def make_fusion_scene(h, w, n_src=3, seed=0, noise=0.004, src_scale=1.0):
     """A reference view and n_src source views of one tilted ground plane, as the fusion step reads them
     (fuse/fusion_3d_normal.py:425-505): per view a depth map [h,w], a camera-space normal map [h,w,3], K [3,3] and
