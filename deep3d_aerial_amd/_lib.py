@@ -151,6 +151,18 @@ SIGNATURES = {
     "d3d_mesh_filter_scratch_bytes": [ctypes.c_longlong],  # returns size_t
     "d3d_mesh_filter": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_longlong, _d, _vp, _sz, _vp, _vp, _vp, _vp],
     "d3d_mesh_smooth": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp],
+    "d3d_mesh_decimate_incidence_scratch_bytes": [ctypes.c_longlong, ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_decimate_incidence": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _sz, _vp, _vp, _vp],
+    "d3d_mesh_decimate_quadrics": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
+    "d3d_mesh_decimate_edges_scratch_bytes": [ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_decimate_edges": [_vp, _vp, ctypes.c_longlong, _vp, _sz, ctypes.c_longlong, _vp, _vp, _vp],
+    "d3d_mesh_decimate_candidates": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
+    "d3d_mesh_decimate_select_scratch_bytes": [],  # returns size_t
+    "d3d_mesh_decimate_select": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _sz, _vp, _vp],
+    "d3d_mesh_decimate_claim": [_vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
+    "d3d_mesh_decimate_apply": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "d3d_mesh_decimate_faces_scratch_bytes": [ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_decimate_faces": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
     "d3d_texture_scratch_bytes": [ctypes.c_longlong, _i],  # returns size_t
     "d3d_texture_select": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _d, _vp, _sz, _vp, _vp],
     "d3d_texture_edges": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
@@ -202,6 +214,8 @@ def load():
                                                          "d3d_dsm_scratch_bytes", "d3d_dsm_mesh_scratch_bytes", "d3d_ortho_scratch_bytes",
                                                          "d3d_mesh_scan_scratch_bytes", "d3d_mesh_adjacency_scratch_bytes",
                                                          "d3d_mesh_stats_scratch_bytes", "d3d_mesh_filter_scratch_bytes",
+                                                         "d3d_mesh_decimate_incidence_scratch_bytes", "d3d_mesh_decimate_edges_scratch_bytes",
+                                                         "d3d_mesh_decimate_select_scratch_bytes", "d3d_mesh_decimate_faces_scratch_bytes",
                                                          "d3d_texture_scratch_bytes") else ctypes.c_int)
     if lib.d3d_version() != ABI_VERSION:
         raise LibraryMissing("ABI version mismatch: library %d, binding %d" % (lib.d3d_version(), ABI_VERSION))

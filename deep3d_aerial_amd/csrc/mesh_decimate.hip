@@ -1,0 +1,693 @@
+// Mesh decimation: memoryless quadric-error edge collapse in rounds of independent collapses.  The rule is
+// this project's (deep3d_aerial_amd/mesh.py states it, include/deep3d_planesweep.h too); one round is a function mesh -> mesh.
+//
+// incidence:  vertex -> face CSR.  One lane per face counts its three corners (integer atomicAdd), a scan gives the row
+//             starts, a second pass scatters the face indices (the atomic's return value is the slot), and one lane per
+//             (face, corner) ranks its face among the entries of its row and writes it at that rank: every row ends sorted,
+//             so the arrival order of the scatter never reaches the output.  Rows of any length take the same path.
+// quadrics:   one lane per vertex walks its row in increasing face index and adds the face quadrics in fp64.
+// edges:      one lane per vertex counts its neighbours of larger index, a scan numbers the undirected edges in (a, b)
+//             lexicographic order, a second pass writes them.
+// candidates: one lane per edge: target, cost, validity (link condition by a merge of the two sorted neighbour rows, degree,
+//             flips over the two face rows), key.
+// select:     the K-th smallest key by an 8 x 8-bit radix select (histograms by integer atomicAdd).
+// claim:      64-bit atomicMin of the key into every vertex of the candidate's neighbourhood.
+// apply:      a candidate that reads its own key back everywhere wins: the survivor moves, the other endpoint is remapped.
+// faces:      faces through the remap, the collapsed ones dropped, kept ones scattered in input order (then d3d_mesh_compact).
+// Integer atomics only (add / min whose return value never reaches the output); every float result is a fixed-order fp64
+// computation without contraction, so nothing depends on the order lanes run in.
+#include <climits>
+#include <cmath>
+#include <cstdint>
+
+#include "common.h"
+#include "mesh_shared.h"
+
+namespace d3d {
+
+constexpr int DQ_BLOCK = 256;
+constexpr int DQ_SELECT_GRID = 1024;   // workgroups of a histogram pass (grid-stride)
+constexpr unsigned DQ_HASH = 2654435761u;
+
+static size_t dq_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// A face the passes use: three distinct indices in range (mesh.py refuses any other; here it is ignored, and dropped by faces).
+__device__ __forceinline__ bool dq_face(const int* __restrict__ faces, long f, long long n, int* a, int* b, int* c) {
+    *a = faces[3 * f];
+    *b = faces[3 * f + 1];
+    *c = faces[3 * f + 2];
+    return *a >= 0 && *a < n && *b >= 0 && *b < n && *c >= 0 && *c < n && *a != *b && *b != *c && *c != *a;
+}
+
+__device__ __forceinline__ void dq_load(const float* __restrict__ v, long i, double* p) {
+    p[0] = (double)v[3 * i];
+    p[1] = (double)v[3 * i + 1];
+    p[2] = (double)v[3 * i + 2];
+}
+
+// nrm = (p1 - p0) x (p2 - p0)
+__device__ __forceinline__ void dq_normal(const double* p0, const double* p1, const double* p2, double* nrm) {
+    const double ux = p1[0] - p0[0], uy = p1[1] - p0[1], uz = p1[2] - p0[2];
+    const double vx = p2[0] - p0[0], vy = p2[1] - p0[1], vz = p2[2] - p0[2];
+    nrm[0] = uy * vz - uz * vy;
+    nrm[1] = uz * vx - ux * vz;
+    nrm[2] = ux * vy - uy * vx;
+}
+
+// q(x) = x^T Q x for the homogeneous x = (x, y, z, 1); q = (aa, ab, ac, ad, bb, bc, bd, cc, cd, dd).
+__device__ __forceinline__ double dq_eval(const double* q, double x, double y, double z) {
+    const double r0 = ((q[0] * x + q[1] * y) + q[2] * z) + q[3];
+    const double r1 = ((q[1] * x + q[4] * y) + q[5] * z) + q[6];
+    const double r2 = ((q[2] * x + q[5] * y) + q[7] * z) + q[8];
+    const double r3 = ((q[3] * x + q[6] * y) + q[8] * z) + q[9];
+    return ((x * r0 + y * r1) + z * r2) + r3;
+}
+
+__device__ __forceinline__ double dq_cost(const double* q, double x, double y, double z) {
+    const double c = dq_eval(q, x, y, z);
+    return c > 0.0 ? c : 0.0;   // a NaN counts as 0
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// incidence
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(DQ_BLOCK) void dq_fcount_kernel(const int* __restrict__ faces, long m, long long n, int* __restrict__ cnt) {
+    const long f = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    int a, b, c;
+    if (f >= m || !dq_face(faces, f, n, &a, &b, &c)) return;
+    atomicAdd(cnt + a, 1);
+    atomicAdd(cnt + b, 1);
+    atomicAdd(cnt + c, 1);
+}
+
+__global__ __launch_bounds__(DQ_BLOCK) void dq_fscatter_kernel(const int* __restrict__ faces, long m, long long n, const int* __restrict__ start,
+                                                               int* __restrict__ fill, int* __restrict__ ent) {
+    const long f = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    int a, b, c;
+    if (f >= m || !dq_face(faces, f, n, &a, &b, &c)) return;
+    ent[(long)start[a] + atomicAdd(fill + a, 1)] = (int)f;
+    ent[(long)start[b] + atomicAdd(fill + b, 1)] = (int)f;
+    ent[(long)start[c] + atomicAdd(fill + c, 1)] = (int)f;
+}
+
+// One lane per (face, corner): the face's rank in the row of its vertex is the number of smaller entries (a row holds a face
+// once: its corners are distinct).
+__global__ __launch_bounds__(DQ_BLOCK) void dq_frank_kernel(const int* __restrict__ faces, long m, long long n, const int* __restrict__ start,
+                                                            const int* __restrict__ cnt, const int* __restrict__ ent, int* __restrict__ finc) {
+    const long k = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (k >= 3 * m) return;
+    const long f = k / 3;
+    int a, b, c;
+    if (!dq_face(faces, f, n, &a, &b, &c)) return;
+    const int v = k - 3 * f == 0 ? a : (k - 3 * f == 1 ? b : c);
+    const long s = start[v];
+    const int L = cnt[v];
+    int r = 0;
+    for (int j = 0; j < L; ++j) r += ent[s + j] < (int)f ? 1 : 0;
+    finc[s + r] = (int)f;
+}
+
+__global__ __launch_bounds__(DQ_BLOCK) void dq_foff_kernel(const int* __restrict__ start, const long long* __restrict__ total, long long n,
+                                                           int* __restrict__ foff) {
+    const long v = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (v > n) return;
+    foff[v] = v == n ? (int)*total : start[v];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// quadrics
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(DQ_BLOCK) void dq_quadric_kernel(const float* __restrict__ vertices, long long n, const int* __restrict__ faces,
+                                                              const int* __restrict__ foff, const int* __restrict__ finc,
+                                                              double* __restrict__ quadric) {
+    const long v = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    double q[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) q[k] = 0.0;
+    const int o1 = foff[v + 1];
+    for (int o = foff[v]; o < o1; ++o) {
+        const long f = finc[o];
+        double p0[3], p1[3], p2[3], nrm[3];
+        dq_load(vertices, faces[3 * f], p0);
+        dq_load(vertices, faces[3 * f + 1], p1);
+        dq_load(vertices, faces[3 * f + 2], p2);
+        dq_normal(p0, p1, p2, nrm);
+        const double len = sqrt((nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2]);
+        if (!(len > 0.0)) continue;
+        const double a = nrm[0] / len, b = nrm[1] / len, c = nrm[2] / len;
+        const double d = -((a * p0[0] + b * p0[1]) + c * p0[2]);
+        const double w = len * 0.5;
+        q[0] += w * (a * a);
+        q[1] += w * (a * b);
+        q[2] += w * (a * c);
+        q[3] += w * (a * d);
+        q[4] += w * (b * b);
+        q[5] += w * (b * c);
+        q[6] += w * (b * d);
+        q[7] += w * (c * c);
+        q[8] += w * (c * d);
+        q[9] += w * (d * d);
+    }
+#pragma unroll
+    for (int k = 0; k < 10; ++k) quadric[10 * v + k] = q[k];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// edges
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(DQ_BLOCK) void dq_ucount_kernel(const long long* __restrict__ offset, const int* __restrict__ nbr, long long n,
+                                                             int* __restrict__ ucnt) {
+    const long v = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    int u = 0;
+    for (long long k = offset[v]; k < offset[v + 1]; ++k) u += nbr[k] > v ? 1 : 0;
+    ucnt[v] = u;
+}
+
+__global__ __launch_bounds__(DQ_BLOCK) void dq_edges_kernel(const long long* __restrict__ offset, const int* __restrict__ nbr, long long n,
+                                                            const int* __restrict__ ebase, long long max_edges, int* __restrict__ edges) {
+    const long v = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    long e = ebase[v];
+    for (long long k = offset[v]; k < offset[v + 1]; ++k) {
+        const int u = nbr[k];
+        if (u <= v) continue;
+        if (e < max_edges) {
+            edges[2 * e] = (int)v;
+            edges[2 * e + 1] = u;
+        }
+        ++e;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// candidates
+// ---------------------------------------------------------------------------------------------------------------------------
+// The faces of row v that do not hold `other`, with v (and other) at position t: true when one of them turns over or collapses.
+__device__ __forceinline__ bool dq_flips(const float* __restrict__ vertices, const int* __restrict__ faces, const int* __restrict__ foff,
+                                         const int* __restrict__ finc, int v, int other, const double* t) {
+    const int o1 = foff[v + 1];
+    for (int o = foff[v]; o < o1; ++o) {
+        const long f = finc[o];
+        const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+        if (i0 == other || i1 == other || i2 == other) continue;
+        double p0[3], p1[3], p2[3], n0[3], n1[3];
+        dq_load(vertices, i0, p0);
+        dq_load(vertices, i1, p1);
+        dq_load(vertices, i2, p2);
+        dq_normal(p0, p1, p2, n0);
+        double* moved = i0 == v ? p0 : (i1 == v ? p1 : p2);
+        moved[0] = t[0], moved[1] = t[1], moved[2] = t[2];
+        dq_normal(p0, p1, p2, n1);
+        const double dot = (n0[0] * n1[0] + n0[1] * n1[1]) + n0[2] * n1[2];
+        if (!(dot > 0.0)) return true;
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(DQ_BLOCK) void dq_candidates_kernel(const float* __restrict__ vertices, const int* __restrict__ faces,
+                                                                 const long long* __restrict__ offset, const int* __restrict__ nbr,
+                                                                 const unsigned char* __restrict__ fixed, const int* __restrict__ foff,
+                                                                 const int* __restrict__ finc, const double* __restrict__ quadric,
+                                                                 const int* __restrict__ edges, const long long* __restrict__ n_edges,
+                                                                 long long max_edges, float* __restrict__ target, float* __restrict__ cost,
+                                                                 long long* __restrict__ key) {
+    const long e = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (e >= max_edges) return;
+    float tx = 0.0f, ty = 0.0f, tz = 0.0f, c32 = 0.0f;
+    long long k = -1;
+    const int a = e < *n_edges ? edges[2 * e] : 0, b = e < *n_edges ? edges[2 * e + 1] : 0;
+    const bool fa = e < *n_edges ? fixed[a] != 0 : true, fb = e < *n_edges ? fixed[b] != 0 : true;
+    if (!(fa && fb)) {
+        double q[10], xa[3], xb[3], x[3];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) q[i] = quadric[10l * a + i] + quadric[10l * b + i];
+        dq_load(vertices, a, xa);
+        dq_load(vertices, b, xb);
+        if (fa || fb) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) x[i] = fa ? xa[i] : xb[i];
+        } else {
+            const double mx = 0.5 * (xa[0] + xb[0]), my = 0.5 * (xa[1] + xb[1]), mz = 0.5 * (xa[2] + xb[2]);
+            const double ex = xb[0] - xa[0], ey = xb[1] - xa[1], ez = xb[2] - xa[2];
+            const double len2 = (ex * ex + ey * ey) + ez * ez;
+            const double r0 = -q[3], r1 = -q[6], r2 = -q[8];
+            const double c00 = q[4] * q[7] - q[5] * q[5], c01 = q[1] * q[7] - q[5] * q[2], c02 = q[1] * q[5] - q[4] * q[2];
+            const double det = (q[0] * c00 - q[1] * c01) + q[2] * c02;
+            const double m0 = r1 * q[7] - q[5] * r2, m1 = r1 * q[5] - q[4] * r2, m2 = q[1] * r2 - r1 * q[2];
+            const double sx = ((r0 * c00 - q[1] * m0) + q[2] * m1) / det;
+            const double sy = ((q[0] * m0 - r0 * c01) + q[2] * m2) / det;
+            const double sz = ((-(q[0] * m1) - q[1] * m2) + r0 * c02) / det;
+            const double dx = sx - mx, dy = sy - my, dz = sz - mz;
+            const double dist2 = (dx * dx + dy * dy) + dz * dz;
+            if (isfinite(det) && det != 0.0 && dist2 <= len2) {   // a NaN or infinite solution fails dist2 <= len2
+                x[0] = sx, x[1] = sy, x[2] = sz;
+            } else {
+                double best = dq_cost(q, xa[0], xa[1], xa[2]);
+                x[0] = xa[0], x[1] = xa[1], x[2] = xa[2];
+                const double cb = dq_cost(q, xb[0], xb[1], xb[2]);
+                if (cb < best) best = cb, x[0] = xb[0], x[1] = xb[1], x[2] = xb[2];
+                const double cm = dq_cost(q, mx, my, mz);
+                if (cm < best) best = cm, x[0] = mx, x[1] = my, x[2] = mz;
+            }
+        }
+        tx = (float)x[0], ty = (float)x[1], tz = (float)x[2];
+        c32 = (float)dq_cost(q, x[0], x[1], x[2]);
+        // (i) the link condition: exactly two common neighbours; (ii) the survivor keeps at least three neighbours
+        const long long a0 = offset[a], a1 = offset[a + 1], b0 = offset[b], b1 = offset[b + 1];
+        int shared = 0;
+        for (long long i = a0, j = b0; i < a1 && j < b1;) {
+            const int u = nbr[i], w = nbr[j];
+            shared += u == w ? 1 : 0;
+            i += u <= w ? 1 : 0;
+            j += w <= u ? 1 : 0;
+        }
+        bool valid = shared == 2 && (a1 - a0) + (b1 - b0) - 4 >= 3;
+        // (iii) no face turns over, judged at the fp32 position the survivor takes
+        const double t[3] = {(double)tx, (double)ty, (double)tz};
+        if (valid) valid = !dq_flips(vertices, faces, foff, finc, a, b, t);
+        if (valid) valid = !dq_flips(vertices, faces, foff, finc, b, a, t);
+        if (valid) k = (long long)(((unsigned long long)__float_as_uint(c32) << 32) | (unsigned long long)((unsigned)e * DQ_HASH));
+    }
+    target[3 * e] = tx;
+    target[3 * e + 1] = ty;
+    target[3 * e + 2] = tz;
+    cost[e] = c32;
+    key[e] = k;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// select: state[0] = the prefix of the K-th smallest key found so far, state[1] = the rank still looked for inside the prefix
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(DQ_BLOCK) void dq_hist_kernel(const long long* __restrict__ key, long long max_edges, const long long* __restrict__ state,
+                                                           int shift, unsigned* __restrict__ hist) {
+    __shared__ unsigned lds[256];
+    lds[threadIdx.x] = 0u;
+    __syncthreads();
+    const unsigned long long prefix = (unsigned long long)state[0];
+    const unsigned long long mask = shift >= 56 ? 0ull : ~0ull << (shift + 8);
+    for (long e = (long)blockIdx.x * DQ_BLOCK + threadIdx.x; e < max_edges; e += (long)gridDim.x * DQ_BLOCK) {
+        const long long k = key[e];
+        if (k < 0 || (((unsigned long long)k ^ prefix) & mask) != 0ull) continue;
+        atomicAdd(lds + (unsigned)(((unsigned long long)k >> shift) & 255ull), 1u);
+    }
+    __syncthreads();
+    if (lds[threadIdx.x]) atomicAdd(hist + threadIdx.x, lds[threadIdx.x]);
+}
+
+// One workgroup: the digit whose bin holds the rank; the first pass clips the rank to the number of valid keys.
+__global__ __launch_bounds__(DQ_BLOCK) void dq_pick_kernel(unsigned* __restrict__ hist, long long* __restrict__ state, int shift,
+                                                           long long* __restrict__ threshold) {
+    __shared__ long long lds[DQ_BLOCK / 64];
+    const long long h = hist[threadIdx.x];
+    long long total;
+    const long long before = mesh_block_exclusive<long long>(h, lds, &total);
+    hist[threadIdx.x] = 0u;
+    long long rank = state[1];
+    if (shift == 56 && rank > total) rank = total;
+    __syncthreads();
+    if (rank <= 0) {   // nothing wanted, or no valid key: no key is <= -1
+        if (threadIdx.x == 0) {
+            state[1] = 0;
+            *threshold = -1;
+        }
+        return;
+    }
+    if (before < rank && rank <= before + h) {
+        const long long prefix = (long long)((unsigned long long)state[0] | ((unsigned long long)threadIdx.x << shift));
+        state[0] = prefix;
+        state[1] = rank - before;
+        if (shift == 0) *threshold = prefix;
+    }
+}
+
+__global__ void dq_select_init_kernel(long long* __restrict__ state, unsigned* __restrict__ hist, long long k) {
+    hist[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) {
+        state[0] = 0;
+        state[1] = k;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// claim, apply
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(DQ_BLOCK) void dq_claim_init_kernel(long long* __restrict__ claim, long long n, long long* __restrict__ n_win) {
+    const long v = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (v < n) claim[v] = LLONG_MAX;
+    if (v == 0) *n_win = 0;
+}
+
+__global__ __launch_bounds__(DQ_BLOCK) void dq_claim_kernel(const long long* __restrict__ offset, const int* __restrict__ nbr,
+                                                            const int* __restrict__ edges, const long long* __restrict__ key,
+                                                            const long long* __restrict__ n_edges, long long max_edges,
+                                                            const long long* __restrict__ threshold, long long* __restrict__ claim) {
+    const long e = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (e >= max_edges || e >= *n_edges) return;
+    const long long k = key[e];
+    if (k < 0 || k > *threshold) return;
+    const int a = edges[2 * e], b = edges[2 * e + 1];
+    atomicMin(claim + a, k);
+    atomicMin(claim + b, k);
+    for (long long i = offset[a]; i < offset[a + 1]; ++i) atomicMin(claim + nbr[i], k);
+    for (long long i = offset[b]; i < offset[b + 1]; ++i) atomicMin(claim + nbr[i], k);
+}
+
+__global__ __launch_bounds__(DQ_BLOCK) void dq_apply_kernel(const long long* __restrict__ offset, const int* __restrict__ nbr,
+                                                            const unsigned char* __restrict__ fixed, const int* __restrict__ edges,
+                                                            const long long* __restrict__ key, const float* __restrict__ target,
+                                                            const long long* __restrict__ n_edges, long long max_edges,
+                                                            const long long* __restrict__ threshold, const long long* __restrict__ claim,
+                                                            float* __restrict__ out_vertices, int* __restrict__ remap,
+                                                            unsigned char* __restrict__ win, long long* __restrict__ n_win) {
+    const long e = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (e >= max_edges) return;
+    bool w = false;
+    if (e < *n_edges) {
+        const long long k = key[e];
+        if (k >= 0 && k <= *threshold) {
+            const int a = edges[2 * e], b = edges[2 * e + 1];
+            w = claim[a] == k && claim[b] == k;
+            for (long long i = offset[a]; w && i < offset[a + 1]; ++i) w = claim[nbr[i]] == k;
+            for (long long i = offset[b]; w && i < offset[b + 1]; ++i) w = claim[nbr[i]] == k;
+            if (w) {   // winners own disjoint vertex sets: plain stores
+                const bool keep_b = fixed[b] != 0 && fixed[a] == 0;
+                const int s = keep_b ? b : a, r = keep_b ? a : b;
+                out_vertices[3l * s] = target[3 * e];
+                out_vertices[3l * s + 1] = target[3 * e + 1];
+                out_vertices[3l * s + 2] = target[3 * e + 2];
+                remap[r] = s;
+                atomicAdd((unsigned long long*)n_win, 1ull);
+            }
+        }
+    }
+    win[e] = w ? 1 : 0;
+}
+
+__global__ __launch_bounds__(DQ_BLOCK) void dq_iota_kernel(int* __restrict__ remap, long long n) {
+    const long v = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (v < n) remap[v] = (int)v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// faces
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(DQ_BLOCK) void dq_fkeep_kernel(const int* __restrict__ faces, long m, long long n, const int* __restrict__ remap,
+                                                            int* __restrict__ keep) {
+    const long f = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (f >= m) return;
+    int a, b, c;
+    bool k = dq_face(faces, f, n, &a, &b, &c);
+    if (k) {
+        a = remap[a], b = remap[b], c = remap[c];
+        k = a != b && b != c && c != a;
+    }
+    keep[f] = k ? 1 : 0;
+}
+
+__global__ __launch_bounds__(DQ_BLOCK) void dq_fscatter_kept_kernel(const int* __restrict__ faces, long m, const int* __restrict__ remap,
+                                                                    const int* __restrict__ keep, const int* __restrict__ pos,
+                                                                    int* __restrict__ out_faces, int* __restrict__ referenced) {
+    const long f = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
+    if (f >= m || !keep[f]) return;
+    const long o = pos[f];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const int x = remap[faces[3 * f + e]];
+        out_faces[3 * o + e] = x;
+        referenced[x] = 1;
+    }
+}
+
+// scratch layouts
+struct DqIncScratch {
+    size_t cnt, start, fill, ent, total, scan, bytes;
+};
+
+static DqIncScratch dq_inc_layout(long long n, long long m) {
+    DqIncScratch s;
+    const size_t nv = (size_t)(n > 0 ? n : 1), ne = (size_t)(3 * m > 0 ? 3 * m : 1);
+    size_t o = 0;
+    s.cnt = o, o += dq_align(nv * 4);
+    s.start = o, o += dq_align(nv * 4);
+    s.fill = o, o += dq_align(nv * 4);
+    s.ent = o, o += dq_align(ne * 4);
+    s.total = o, o += dq_align(8);
+    s.scan = o, o += dq_align(d3d_mesh_scan_scratch_bytes(n));
+    s.bytes = o;
+    return s;
+}
+
+struct DqEdgeScratch {
+    size_t ucnt, ebase, scan, bytes;
+};
+
+static DqEdgeScratch dq_edge_layout(long long n) {
+    DqEdgeScratch s;
+    const size_t nv = (size_t)(n > 0 ? n : 1);
+    size_t o = 0;
+    s.ucnt = o, o += dq_align(nv * 4);
+    s.ebase = o, o += dq_align(nv * 4);
+    s.scan = o, o += dq_align(d3d_mesh_scan_scratch_bytes(n));
+    s.bytes = o;
+    return s;
+}
+
+struct DqSelectScratch {
+    size_t state, hist, bytes;
+};
+
+static DqSelectScratch dq_select_layout() {
+    DqSelectScratch s;
+    size_t o = 0;
+    s.state = o, o += dq_align(16);
+    s.hist = o, o += dq_align(256 * 4);
+    s.bytes = o;
+    return s;
+}
+
+struct DqFaceScratch {
+    size_t keep, pos, scan, bytes;
+};
+
+static DqFaceScratch dq_face_layout(long long m) {
+    DqFaceScratch s;
+    const size_t nf = (size_t)(m > 0 ? m : 1);
+    size_t o = 0;
+    s.keep = o, o += dq_align(nf * 4);
+    s.pos = o, o += dq_align(nf * 4);
+    s.scan = o, o += dq_align(d3d_mesh_scan_scratch_bytes(m));
+    s.bytes = o;
+    return s;
+}
+
+static bool dq_sizes_ok(long long n, long long m) { return n >= 0 && n < (1ll << 31) && m >= 0 && 6 * m < (1ll << 31); }
+
+}  // namespace d3d
+
+using namespace d3d;
+
+#define DQ_CHECK_SIZES()                                                                                                  \
+    D3D_REQUIRE(dq_sizes_ok(n_vertices, n_faces), "n_vertices=%lld, n_faces=%lld (0 .. 2^31 - 1 vertices, 6 n_faces < 2^31)", \
+                n_vertices, n_faces)
+
+#define DQ_CHECK_SCRATCH(need)                                                                                            \
+    D3D_REQUIRE(scratch_bytes >= (need), "scratch of %zu bytes, %zu needed", scratch_bytes, (size_t)(need))
+
+#define DQ_CHECK_EDGES()                                                                                                  \
+    D3D_REQUIRE(max_edges >= 0 && max_edges < (1ll << 31), "max_edges=%lld (0 .. 2^31 - 1)", max_edges)
+
+extern "C" size_t d3d_mesh_decimate_incidence_scratch_bytes(long long n_vertices, long long n_faces) {
+    if (!dq_sizes_ok(n_vertices, n_faces)) return 0;
+    return dq_inc_layout(n_vertices, n_faces).bytes;
+}
+
+extern "C" int d3d_mesh_decimate_incidence(const int* faces, long long n_faces, long long n_vertices, void* scratch, size_t scratch_bytes,
+                                           int* face_offset, int* face_index, d3d_stream_t stream) {
+    D3D_REQUIRE((faces || n_faces == 0) && scratch && face_offset && face_index, "null pointer (faces, scratch, face_offset, face_index)");
+    DQ_CHECK_SIZES();
+    const DqIncScratch L = dq_inc_layout(n_vertices, n_faces);
+    DQ_CHECK_SCRATCH(L.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)scratch;
+    int *cnt = (int*)(w + L.cnt), *start = (int*)(w + L.start), *fill = (int*)(w + L.fill), *ent = (int*)(w + L.ent);
+    long long* total = (long long*)(w + L.total);
+    const long long n = n_vertices, m = n_faces;
+    int rc = hip_status(hipMemsetAsync(cnt, 0, (size_t)(n > 0 ? n : 1) * 4, st), "mesh decimate incidence: clear counts");
+    if (rc != D3D_OK) return rc;
+    rc = hip_status(hipMemsetAsync(fill, 0, (size_t)(n > 0 ? n : 1) * 4, st), "mesh decimate incidence: clear fill");
+    if (rc != D3D_OK) return rc;
+    if (m > 0) {
+        hipLaunchKernelGGL(dq_fcount_kernel, dim3(ceil_div(m, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, faces, (long)m, n, cnt);
+        D3D_LAUNCH_CHECK("dq_fcount_kernel launch");
+    }
+    rc = mesh_scan(cnt, start, n, w + L.scan, total, st);   // the total is at most 3 n_faces < 2^31
+    if (rc != D3D_OK) return rc;
+    if (m > 0) {
+        hipLaunchKernelGGL(dq_fscatter_kernel, dim3(ceil_div(m, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, faces, (long)m, n, start, fill, ent);
+        D3D_LAUNCH_CHECK("dq_fscatter_kernel launch");
+        hipLaunchKernelGGL(dq_frank_kernel, dim3(ceil_div(3 * m, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, faces, (long)m, n, start, cnt, ent, face_index);
+        D3D_LAUNCH_CHECK("dq_frank_kernel launch");
+    }
+    hipLaunchKernelGGL(dq_foff_kernel, dim3(ceil_div(n + 1, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, start, total, n, face_offset);
+    D3D_LAUNCH_CHECK("dq_foff_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_decimate_quadrics(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* face_offset,
+                                          const int* face_index, double* quadric, d3d_stream_t stream) {
+    D3D_REQUIRE((vertices || n_vertices == 0) && (faces || n_faces == 0) && face_offset && face_index && quadric,
+                "null pointer (vertices, faces, face_offset, face_index, quadric)");
+    DQ_CHECK_SIZES();
+    if (n_vertices == 0) return D3D_OK;
+    hipLaunchKernelGGL(dq_quadric_kernel, dim3(ceil_div(n_vertices, DQ_BLOCK)), dim3(DQ_BLOCK), 0, (hipStream_t)stream, vertices, n_vertices, faces,
+                       face_offset, face_index, quadric);
+    D3D_LAUNCH_CHECK("dq_quadric_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" size_t d3d_mesh_decimate_edges_scratch_bytes(long long n_vertices) {
+    if (!dq_sizes_ok(n_vertices, 0)) return 0;
+    return dq_edge_layout(n_vertices).bytes;
+}
+
+extern "C" int d3d_mesh_decimate_edges(const long long* offset, const int* nbr, long long n_vertices, void* scratch, size_t scratch_bytes,
+                                       long long max_edges, int* edges, long long* n_edges, d3d_stream_t stream) {
+    D3D_REQUIRE(offset && nbr && scratch && edges && n_edges, "null pointer (offset, nbr, scratch, edges, n_edges)");
+    D3D_REQUIRE(n_vertices >= 0 && n_vertices < (1ll << 31), "n_vertices=%lld (0 .. 2^31 - 1)", n_vertices);
+    DQ_CHECK_EDGES();
+    const DqEdgeScratch L = dq_edge_layout(n_vertices);
+    DQ_CHECK_SCRATCH(L.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)scratch;
+    int *ucnt = (int*)(w + L.ucnt), *ebase = (int*)(w + L.ebase);
+    const long long n = n_vertices;
+    if (n > 0) {
+        hipLaunchKernelGGL(dq_ucount_kernel, dim3(ceil_div(n, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, offset, nbr, n, ucnt);
+        D3D_LAUNCH_CHECK("dq_ucount_kernel launch");
+    }
+    const int rc = mesh_scan(ucnt, ebase, n, w + L.scan, n_edges, st);
+    if (rc != D3D_OK) return rc;
+    if (n > 0) {
+        hipLaunchKernelGGL(dq_edges_kernel, dim3(ceil_div(n, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, offset, nbr, n, ebase, max_edges, edges);
+        D3D_LAUNCH_CHECK("dq_edges_kernel launch");
+    }
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_decimate_candidates(const float* vertices, long long n_vertices, const int* faces, long long n_faces,
+                                            const long long* offset, const int* nbr, const unsigned char* fixed, const int* face_offset,
+                                            const int* face_index, const double* quadric, const int* edges, const long long* n_edges,
+                                            long long max_edges, float* target, float* cost, long long* key, d3d_stream_t stream) {
+    D3D_REQUIRE(vertices && faces && offset && nbr && fixed && face_offset && face_index && quadric && edges && n_edges && target && cost && key,
+                "null pointer (vertices, faces, offset, nbr, fixed, face_offset, face_index, quadric, edges, n_edges, target, cost, key)");
+    DQ_CHECK_SIZES();
+    DQ_CHECK_EDGES();
+    if (max_edges == 0) return D3D_OK;
+    hipLaunchKernelGGL(dq_candidates_kernel, dim3(ceil_div(max_edges, DQ_BLOCK)), dim3(DQ_BLOCK), 0, (hipStream_t)stream, vertices, faces, offset,
+                       nbr, fixed, face_offset, face_index, quadric, edges, n_edges, max_edges, target, cost, key);
+    D3D_LAUNCH_CHECK("dq_candidates_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" size_t d3d_mesh_decimate_select_scratch_bytes(void) { return dq_select_layout().bytes; }
+
+extern "C" int d3d_mesh_decimate_select(const long long* key, long long max_edges, long long k, void* scratch, size_t scratch_bytes,
+                                        long long* threshold, d3d_stream_t stream) {
+    D3D_REQUIRE(key && scratch && threshold, "null pointer (key, scratch, threshold)");
+    DQ_CHECK_EDGES();
+    D3D_REQUIRE(k >= 0, "k=%lld must be >= 0", k);
+    const DqSelectScratch L = dq_select_layout();
+    DQ_CHECK_SCRATCH(L.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)scratch;
+    long long* state = (long long*)(w + L.state);
+    unsigned* hist = (unsigned*)(w + L.hist);
+    hipLaunchKernelGGL(dq_select_init_kernel, dim3(1), dim3(256), 0, st, state, hist, k);
+    D3D_LAUNCH_CHECK("dq_select_init_kernel launch");
+    const int grid = (int)(ceil_div(max_edges > 0 ? max_edges : 1, DQ_BLOCK) < DQ_SELECT_GRID ? ceil_div(max_edges > 0 ? max_edges : 1, DQ_BLOCK)
+                                                                                             : DQ_SELECT_GRID);
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(dq_hist_kernel, dim3(grid), dim3(DQ_BLOCK), 0, st, key, max_edges, state, shift, hist);
+        D3D_LAUNCH_CHECK("dq_hist_kernel launch");
+        hipLaunchKernelGGL(dq_pick_kernel, dim3(1), dim3(DQ_BLOCK), 0, st, hist, state, shift, threshold);
+        D3D_LAUNCH_CHECK("dq_pick_kernel launch");
+    }
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_decimate_claim(const long long* offset, const int* nbr, long long n_vertices, const int* edges, const long long* key,
+                                       const long long* n_edges, long long max_edges, const long long* threshold, long long* claim,
+                                       long long* n_winners, d3d_stream_t stream) {
+    D3D_REQUIRE(offset && nbr && edges && key && n_edges && threshold && claim && n_winners,
+                "null pointer (offset, nbr, edges, key, n_edges, threshold, claim, n_winners)");
+    D3D_REQUIRE(n_vertices >= 0 && n_vertices < (1ll << 31), "n_vertices=%lld (0 .. 2^31 - 1)", n_vertices);
+    DQ_CHECK_EDGES();
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(dq_claim_init_kernel, dim3(ceil_div(n_vertices > 0 ? n_vertices : 1, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, claim, n_vertices,
+                       n_winners);
+    D3D_LAUNCH_CHECK("dq_claim_init_kernel launch");
+    if (max_edges == 0) return D3D_OK;
+    hipLaunchKernelGGL(dq_claim_kernel, dim3(ceil_div(max_edges, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, offset, nbr, edges, key, n_edges, max_edges,
+                       threshold, claim);
+    D3D_LAUNCH_CHECK("dq_claim_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_decimate_apply(const float* vertices, long long n_vertices, const long long* offset, const int* nbr,
+                                       const unsigned char* fixed, const int* edges, const long long* key, const float* target,
+                                       const long long* n_edges, long long max_edges, const long long* threshold, const long long* claim,
+                                       float* out_vertices, int* remap, unsigned char* win, long long* n_winners, d3d_stream_t stream) {
+    D3D_REQUIRE((vertices || n_vertices == 0) && offset && nbr && fixed && edges && key && target && n_edges && threshold && claim && out_vertices &&
+                    remap && win && n_winners,
+                "null pointer (vertices, offset, nbr, fixed, edges, key, target, n_edges, threshold, claim, out_vertices, remap, win, n_winners)");
+    D3D_REQUIRE(n_vertices >= 0 && n_vertices < (1ll << 31), "n_vertices=%lld (0 .. 2^31 - 1)", n_vertices);
+    DQ_CHECK_EDGES();
+    D3D_REQUIRE(vertices != out_vertices, "vertices and out_vertices must be distinct buffers");
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = n_vertices;
+    if (n > 0) {
+        const int rc = hip_status(hipMemcpyAsync(out_vertices, vertices, (size_t)n * 12, hipMemcpyDeviceToDevice, st), "mesh decimate apply: copy");
+        if (rc != D3D_OK) return rc;
+        hipLaunchKernelGGL(dq_iota_kernel, dim3(ceil_div(n, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, remap, n);
+        D3D_LAUNCH_CHECK("dq_iota_kernel launch");
+    }
+    if (max_edges == 0) return D3D_OK;
+    hipLaunchKernelGGL(dq_apply_kernel, dim3(ceil_div(max_edges, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, offset, nbr, fixed, edges, key, target, n_edges,
+                       max_edges, threshold, claim, out_vertices, remap, win, n_winners);
+    D3D_LAUNCH_CHECK("dq_apply_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" size_t d3d_mesh_decimate_faces_scratch_bytes(long long n_faces) {
+    if (!dq_sizes_ok(0, n_faces)) return 0;
+    return dq_face_layout(n_faces).bytes;
+}
+
+extern "C" int d3d_mesh_decimate_faces(const int* faces, long long n_faces, long long n_vertices, const int* remap, void* scratch,
+                                       size_t scratch_bytes, int* out_faces, int* referenced, long long* n_kept, d3d_stream_t stream) {
+    D3D_REQUIRE((faces || n_faces == 0) && remap && scratch && out_faces && referenced && n_kept,
+                "null pointer (faces, remap, scratch, out_faces, referenced, n_kept)");
+    DQ_CHECK_SIZES();
+    const DqFaceScratch L = dq_face_layout(n_faces);
+    DQ_CHECK_SCRATCH(L.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)scratch;
+    int *keep = (int*)(w + L.keep), *pos = (int*)(w + L.pos);
+    const long long n = n_vertices, m = n_faces;
+    int rc = hip_status(hipMemsetAsync(referenced, 0, (size_t)(n > 0 ? n : 1) * 4, st), "mesh decimate faces: clear flags");
+    if (rc != D3D_OK) return rc;
+    if (m > 0) {
+        hipLaunchKernelGGL(dq_fkeep_kernel, dim3(ceil_div(m, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, faces, (long)m, n, remap, keep);
+        D3D_LAUNCH_CHECK("dq_fkeep_kernel launch");
+    }
+    rc = mesh_scan(keep, pos, m, w + L.scan, n_kept, st);
+    if (rc != D3D_OK) return rc;
+    if (m > 0) {
+        hipLaunchKernelGGL(dq_fscatter_kept_kernel, dim3(ceil_div(m, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, faces, (long)m, remap, keep, pos, out_faces,
+                           referenced);
+        D3D_LAUNCH_CHECK("dq_fscatter_kept_kernel launch");
+    }
+    return D3D_OK;
+}

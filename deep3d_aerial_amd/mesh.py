@@ -58,10 +58,54 @@ vertices [n,3] fp32 and faces [m,3] int32 (extract, read_ply); every index must 
 The result is a function of the input arrays: shuffling the face list gives the same vertices bit for bit and the same set of
 faces.  Integer atomics only, no float atomics.
 
+Decimation (decimate(); csrc/mesh_decimate.hip): memoryless quadric-error edge collapse in rounds of
+independent collapses, off by default.  The rule is this project's; it does not claim to match OpenMVS / VCG.  The input is
+vertices [n,3] fp32 and faces [m,3] int32, every face with three distinct indices in 0 .. n - 1 (anything else is refused).  One
+round is a function mesh -> mesh and no state is carried between rounds.  All arithmetic is fp64 without contraction, rounded to
+fp32 only where said.
+1. Face quadric.  nrm = (p1 - p0) x (p2 - p0), len = sqrt((nx nx + ny ny) + nz nz); a face contributes nothing unless len > 0;
+   else (a, b, c) = nrm / len, d = -((a x0 + b y0) + c z0), w = len / 2 and q = (aa, ab, ac, ad, bb, bc, bd, cc, cd, dd), each term
+   w * (u * v).
+2. Vertex quadric Q_v: the sum of the quadrics of the faces at v, added in increasing face index, from 0 (face_incidence: the
+   vertex -> face CSR, rows of any length).
+3. Fixed vertices are adjacency()'s `fixed` flag.  A fixed vertex is never moved and never removed, so the mesh boundary comes
+   through unchanged.
+4. Candidates: one per undirected edge {a, b}, a < b, with a free endpoint (every edge at a free vertex is manifold).  Edges are
+   numbered e = 0, 1, .. in (a, b) lexicographic order over all undirected edges; 3 m < 2^31 bounds their count.  Q = Q_a + Q_b.
+   One endpoint fixed: it survives and the target x is its position.  Both free: a survives; with r = -(Q3, Q6, Q8),
+   c00 = Q4 Q7 - Q5 Q5, c01 = Q1 Q7 - Q5 Q2, c02 = Q1 Q5 - Q4 Q2, det = (Q0 c00 - Q1 c01) + Q2 c02, m0 = r1 Q7 - Q5 r2,
+   m1 = r1 Q5 - Q4 r2, m2 = Q1 r2 - r1 Q2 the minimiser is sx = ((r0 c00 - Q1 m0) + Q2 m1) / det,
+   sy = ((Q0 m0 - r0 c01) + Q2 m2) / det, sz = ((-(Q0 m1) - Q1 m2) + r0 c02) / det (Cramer's rule).  x = s when det is finite and
+   not 0 and |s - mid|^2 <= |x_b - x_a|^2 (mid = 0.5 (x_a + x_b), squared norms (dx dx + dy dy) + dz dz); otherwise the
+   cheapest of x_a, x_b, mid (a later one only when strictly cheaper).  The distance test keeps near-planar regions (rank-1 A)
+   from throwing vertices away; it is scale-free.  q(x) = ((x r0 + y r1) + z r2) + r3 with r_i = ((Q_i0 x + Q_i1 y) + Q_i2 z) + Q_i3
+   the rows of the symmetric 4 x 4 matrix; the cost is c = q(x) if q(x) > 0 else 0, as fp32, and the survivor would take
+   t = fp32(x).  key = (bits(fp32(c)) << 32) | (e * 2654435761 mod 2^32): the hash (a bijection of 32-bit words) spreads equal
+   costs, on flat ground all of them 0, over the mesh instead of leaving the cheapest keys in one cluster that blocks itself.
+5. A candidate is valid when (i) N(a) and N(b) share exactly two vertices (link condition), (ii) |N(a)| + |N(b)| - 4 >= 3 (the
+   survivor keeps three neighbours: a closed tetrahedron comes back unchanged), (iii) for every face at a or b that does not
+   hold both, the old normal dotted with the normal after the endpoint moves to t (the fp32 target, so the test sees the
+   position really taken) is > 0: no flip, no face of zero area.
+6. With T the target face count and K = ceil((m - T) / 2) collapses still needed, only the K valid candidates with the smallest
+   keys are eligible this round.  A collapse removes exactly two faces, so the result has T or T - 1 faces unless it stalls.
+7. Every eligible candidate writes its key by a 64-bit integer minimum into claim[w] for every w of {a, b} U N(a) U N(b); it
+   wins when it reads its own key back from all of them.  Winners touch disjoint face sets; the smallest key always wins.
+8. The survivor takes t, the other endpoint is re-indexed to it, the faces that held both are dropped, the others stay in input
+   order, and vertices no face uses go (d3d_mesh_compact).  Adjacency is rebuilt for the next round.
+9. Stop when m <= T, when a round has no winner (stalled: reported, not an error) or after max_rounds rounds (a cap on host round
+   trips, reported when hit).  One small device-to-host read per round.
+T = target_faces when given, else ceil(ratio m); ratio in (0, 1], 1 = off; giving both is an error.  The result is a function of
+the input arrays (same bits run to run); integer atomics only.  Unlike cleaning it is NOT invariant under a shuffle of the face
+list: the quadric sums run in face-index order and the kept faces keep their input order.
+Order in build_and_write and the command line: removal, smoothing, then decimation (smoothing first takes the TSDF staircase out,
+so flat areas have zero-cost edges).
+
     python -m deep3d_aerial_amd.mesh --mvs MVS_FOLDER --out mesh.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax --voxel S
         [--trunc T] [--min_views 2] [--conf_threshold 0.2] [--views_per_batch N]
         [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L]
+        [--decimate R] [--target_faces N] [--decimate_max_rounds K]
     python -m deep3d_aerial_amd.mesh --clean IN.ply --out OUT.ply [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L]
+        [--decimate R] [--target_faces N] [--decimate_max_rounds K]
 """
 import argparse
 import ctypes
@@ -76,6 +120,8 @@ from . import _lib
 DEFAULT_CONF = 0.2
 DEFAULT_MIN_VIEWS = 2
 DEFAULT_SMOOTH_LAMBDA = 0.5
+DEFAULT_DECIMATE_MAX_ROUNDS = 1000   # a cap on host round trips, far above the rounds a target needs
+DECIMATE_HASH = 2654435761
 BRICK = 8
 
 # the 6 Kuhn tetrahedra (positively oriented), the edges of a tetrahedron, the 16-case table (csrc/mesh.hip has the same)
@@ -440,6 +486,151 @@ def clean(vertices, faces, min_faces=0, spurious=0.0, smooth=0, smooth_lambda=DE
 
 
 # ----------------------------------------------------------------------------------------
+# decimation
+# ----------------------------------------------------------------------------------------
+def check_decimate_settings(ratio=1.0, target_faces=0, max_rounds=DEFAULT_DECIMATE_MAX_ROUNDS):
+    """(ratio, target_faces, max_rounds) checked; ratio 1 and target_faces 0 mean "off", giving both is an error."""
+    ratio = float(ratio)
+    if not (0 < ratio <= 1):
+        raise ValueError("decimate ratio %r must lie in (0, 1]" % (ratio,))
+    if int(target_faces) != target_faces or int(target_faces) < 0:
+        raise ValueError("target_faces %r must be an integer >= 0" % (target_faces,))
+    if ratio < 1 and int(target_faces) > 0:
+        raise ValueError("decimate ratio %r and target_faces %r: give one of them" % (ratio, target_faces))
+    if int(max_rounds) != max_rounds or int(max_rounds) < 1:
+        raise ValueError("decimate max_rounds %r must be an integer >= 1" % (max_rounds,))
+    return ratio, int(target_faces), int(max_rounds)
+
+
+def _decimate_arrays(vertices, faces):
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    if m and bool(((faces[:, 0] == faces[:, 1]) | (faces[:, 1] == faces[:, 2]) | (faces[:, 2] == faces[:, 0])).any()):
+        raise ValueError("a face has a repeated index: decimation needs three distinct indices per face")
+    return vertices, faces, n, m
+
+
+def face_incidence(faces, n_vertices):
+    """The vertex -> face CSR: (face_offset [n+1] int32, face_index [3 m] int32), every row in increasing face index."""
+    lib = _lib.load()
+    n, m = int(n_vertices), int(faces.shape[0])
+    dev = faces.device
+    nbytes = int(lib.d3d_mesh_decimate_incidence_scratch_bytes(n, m))
+    if nbytes == 0:
+        raise ValueError("%d vertices, %d faces: out of range" % (n, m))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    foff = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    finc = torch.empty((max(3 * m, 1),), dtype=torch.int32, device=dev)
+    _lib.check(lib.d3d_mesh_decimate_incidence(_ptr(faces), m, n, _ptr(scratch), nbytes, _ptr(foff), _ptr(finc), _stream()),
+               "d3d_mesh_decimate_incidence")
+    return foff, finc[:3 * m]
+
+
+def vertex_quadrics(vertices, faces, incidence=None):
+    """[n,10] fp64: the quadric of every vertex (rule 2).  incidence: face_incidence(faces, n) when the caller has it."""
+    n, m = int(vertices.shape[0]), int(faces.shape[0])
+    foff, finc = incidence if incidence is not None else face_incidence(faces, n)
+    q = torch.empty((max(n, 1), 10), dtype=torch.float64, device=vertices.device)
+    _lib.check(_lib.load().d3d_mesh_decimate_quadrics(_ptr(vertices), n, _ptr(faces), m, _ptr(foff), _ptr(finc), _ptr(q), _stream()),
+               "d3d_mesh_decimate_quadrics")
+    return q[:n]
+
+
+def decimate_round(vertices, faces, target_faces, detail=None):
+    """One round (rules 1-8) toward target_faces: (vertices, faces, winners); with no winner the input tensors come back.
+    detail (a dict) gets every pass's output: face_offset, face_index, quadric, offset, nbr, fixed, edges [E,2], target [E,3],
+    cost [E], key [E] (-1: not valid), threshold, claim [n], win [E]."""
+    lib = _lib.load()
+    n, m = int(vertices.shape[0]), int(faces.shape[0])
+    dev = vertices.device
+    k = max(0, -(-(m - int(target_faces)) // 2))
+    if m == 0 or n == 0 or k == 0:
+        return vertices, faces, 0
+    st = _stream()
+    u8 = lambda b: torch.empty((int(b),), dtype=torch.uint8, device=dev)
+    offset, nbr, fixed = adjacency(faces, n)
+    foff, finc = face_incidence(faces, n)
+    quadric = vertex_quadrics(vertices, faces, (foff, finc))
+    emax = 3 * m
+    counts = torch.zeros((4,), dtype=torch.int64, device=dev)   # edges, winners, kept faces, kept vertices
+    p_count = lambda i: ctypes.c_void_p(counts.data_ptr() + 8 * i)
+    edges = torch.empty((emax, 2), dtype=torch.int32, device=dev)
+    nbytes = int(lib.d3d_mesh_decimate_edges_scratch_bytes(n))
+    scratch = u8(nbytes)
+    _lib.check(lib.d3d_mesh_decimate_edges(_ptr(offset), _ptr(nbr), n, _ptr(scratch), nbytes, emax, _ptr(edges), p_count(0), st),
+               "d3d_mesh_decimate_edges")
+    target = torch.empty((emax, 3), dtype=torch.float32, device=dev)
+    cost = torch.empty((emax,), dtype=torch.float32, device=dev)
+    key = torch.empty((emax,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_mesh_decimate_candidates(_ptr(vertices), n, _ptr(faces), m, _ptr(offset), _ptr(nbr), _ptr(fixed), _ptr(foff), _ptr(finc),
+                                                _ptr(quadric), _ptr(edges), p_count(0), emax, _ptr(target), _ptr(cost), _ptr(key), st),
+               "d3d_mesh_decimate_candidates")
+    nbytes = int(lib.d3d_mesh_decimate_select_scratch_bytes())
+    scratch = u8(nbytes)
+    threshold = torch.empty((1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_mesh_decimate_select(_ptr(key), emax, k, _ptr(scratch), nbytes, _ptr(threshold), st), "d3d_mesh_decimate_select")
+    claim = torch.empty((n,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_mesh_decimate_claim(_ptr(offset), _ptr(nbr), n, _ptr(edges), _ptr(key), p_count(0), emax, _ptr(threshold), _ptr(claim),
+                                           p_count(1), st), "d3d_mesh_decimate_claim")
+    moved = torch.empty_like(vertices)
+    remap = torch.empty((n,), dtype=torch.int32, device=dev)
+    win = torch.empty((emax,), dtype=torch.uint8, device=dev)
+    _lib.check(lib.d3d_mesh_decimate_apply(_ptr(vertices), n, _ptr(offset), _ptr(nbr), _ptr(fixed), _ptr(edges), _ptr(key), _ptr(target),
+                                           p_count(0), emax, _ptr(threshold), _ptr(claim), _ptr(moved), _ptr(remap), _ptr(win), p_count(1), st),
+               "d3d_mesh_decimate_apply")
+    nbytes = int(lib.d3d_mesh_decimate_faces_scratch_bytes(m))
+    scratch = u8(nbytes)
+    out_faces = torch.zeros((m, 3), dtype=torch.int32, device=dev)   # rows past the kept ones stay 0: a valid index
+    referenced = torch.empty((n,), dtype=torch.int32, device=dev)
+    _lib.check(lib.d3d_mesh_decimate_faces(_ptr(faces), m, n, _ptr(remap), _ptr(scratch), nbytes, _ptr(out_faces), _ptr(referenced), p_count(2),
+                                           st), "d3d_mesh_decimate_faces")
+    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(n))
+    scratch = u8(nbytes)
+    renum = torch.empty((n,), dtype=torch.int32, device=dev)
+    out_v = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    # the kept count is still on the device, so all m rows are renumbered; the round's one read comes after
+    _lib.check(lib.d3d_mesh_compact(_ptr(moved), n, _ptr(out_faces), m, _ptr(referenced), _ptr(scratch), nbytes, _ptr(renum), _ptr(out_v),
+                                    p_count(3), st), "d3d_mesh_compact")
+    ne, nw, mk, nk = (int(x) for x in counts.cpu())   # the round's one device-to-host read: it sizes the next round
+    if detail is not None:
+        detail.update(face_offset=foff, face_index=finc, quadric=quadric, offset=offset, nbr=nbr[:2 * ne], fixed=fixed, edges=edges[:ne],
+                      target=target[:ne], cost=cost[:ne], key=key[:ne], threshold=threshold, claim=claim, win=win[:ne], eligible=k)
+    if nw == 0:
+        return vertices, faces, 0
+    return out_v[:nk], out_faces[:mk], nw
+
+
+def decimate(vertices, faces, ratio=1.0, target_faces=0, max_rounds=DEFAULT_DECIMATE_MAX_ROUNDS, info=None):
+    """Quadric-error edge collapse toward T = target_faces (when > 0) or ceil(ratio m) faces, on the device: (vertices, faces).
+    With ratio 1 and target_faces 0, or T >= m, the input tensors come back as they are.  info (a dict) gets target_faces, rounds,
+    collapses (per round), faces_in, faces_out, vertices_out, stalled and hit_max_rounds."""
+    ratio, target_faces, max_rounds = check_decimate_settings(ratio, target_faces, max_rounds)
+    m0 = int(faces.shape[0]) if isinstance(faces, torch.Tensor) and faces.dim() == 2 else 0
+    goal = target_faces if target_faces > 0 else int(math.ceil(ratio * m0))
+    rec = {"target_faces": goal, "rounds": 0, "collapses": [], "faces_in": m0, "faces_out": m0, "stalled": False, "hit_max_rounds": False}
+    if (ratio == 1.0 and target_faces == 0) or goal >= m0:
+        _mesh_arrays(vertices, faces)
+        rec["vertices_out"] = int(vertices.shape[0])
+        if info is not None:
+            info.update(rec)
+        return vertices, faces
+    v, f, n, m = _decimate_arrays(vertices, faces)
+    while int(f.shape[0]) > goal:
+        if rec["rounds"] >= max_rounds:
+            rec["hit_max_rounds"] = True
+            break
+        v, f, won = decimate_round(v, f, goal)
+        rec["rounds"] += 1
+        rec["collapses"].append(won)
+        if won == 0:
+            rec["stalled"] = True
+            break
+    rec.update(faces_out=int(f.shape[0]), vertices_out=int(v.shape[0]))
+    if info is not None:
+        info.update(rec)
+    return v, f
+
+
+# ----------------------------------------------------------------------------------------
 # PLY
 # ----------------------------------------------------------------------------------------
 FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
@@ -536,6 +727,16 @@ def add_arguments(ap, prefix=""):
     ap.add_argument("--%sconf_threshold" % prefix, type=float, default=DEFAULT_CONF, help="a pixel is used when its confidence >= this")
     ap.add_argument("--%sviews_per_batch" % prefix, type=int, default=None, help="views per integration call (default: all)")
     add_clean_arguments(ap, prefix)
+    add_decimate_arguments(ap, prefix)
+
+
+def add_decimate_arguments(ap, prefix=""):
+    """The decimation step as flags (--<prefix>decimate, --<prefix>target_faces, --<prefix>decimate_max_rounds); off by default."""
+    ap.add_argument("--%sdecimate" % prefix, type=float, default=1.0, metavar="R",
+                    help="decimate to ceil(R m) faces by quadric-error edge collapse, R in (0, 1] (1: off)")
+    ap.add_argument("--%starget_faces" % prefix, type=int, default=0, metavar="N", help="decimate to N faces instead of a ratio (0: off)")
+    ap.add_argument("--%sdecimate_max_rounds" % prefix, type=int, default=DEFAULT_DECIMATE_MAX_ROUNDS, metavar="K",
+                    help="cap on the collapse rounds (host round trips); reaching it is reported")
 
 
 def add_clean_arguments(ap, prefix=""):
@@ -551,7 +752,8 @@ def settings_from_args(a, path, prefix=""):
     g = lambda k: getattr(a, prefix + k)
     return {"path": path, "border": g("border"), "voxel": g("voxel"), "trunc": g("trunc"), "min_views": g("min_views"),
             "conf_threshold": g("conf_threshold"), "views_per_batch": g("views_per_batch"), "min_faces": g("min_faces"),
-            "spurious": g("spurious"), "smooth": g("smooth"), "smooth_lambda": g("smooth_lambda")}
+            "spurious": g("spurious"), "smooth": g("smooth"), "smooth_lambda": g("smooth_lambda"), "decimate": g("decimate"),
+            "target_faces": g("target_faces"), "decimate_max_rounds": g("decimate_max_rounds")}
 
 
 def clean_settings(settings):
@@ -565,6 +767,17 @@ def clean_requested(settings):
     return min_faces > 0 or spurious > 0 or smooth > 0
 
 
+def decimate_settings(settings):
+    """(ratio, target_faces, max_rounds) of a settings dict, checked; missing keys mean "off"."""
+    return check_decimate_settings(1.0 if settings.get("decimate") is None else settings["decimate"], settings.get("target_faces") or 0,
+                                   DEFAULT_DECIMATE_MAX_ROUNDS if settings.get("decimate_max_rounds") is None else settings["decimate_max_rounds"])
+
+
+def decimate_requested(settings):
+    ratio, target_faces, _ = decimate_settings(settings)
+    return ratio < 1 or target_faces > 0
+
+
 def check_args(ap, a, prefix=""):
     """The argument errors of the mesh settings, reported through ap.error."""
     if getattr(a, prefix + "border") is None:
@@ -575,18 +788,30 @@ def check_args(ap, a, prefix=""):
         s = settings_from_args(a, None, prefix)
         check_settings(MeshGrid(s["border"], s["voxel"]), s["trunc"], s["min_views"], s["conf_threshold"], s["views_per_batch"])
         clean_settings(s)
+        decimate_settings(s)
     except ValueError as e:
         ap.error("--%s*: %s" % (prefix, e))
 
 
+def _decimate_and_report(v, f, ratio, target_faces, max_rounds):
+    info = {}
+    v, f = decimate(v, f, ratio, target_faces, max_rounds, info=info)
+    if info["stalled"] or info["hit_max_rounds"]:
+        print("mesh decimation %s after %d rounds at %d faces (target %d)" % ("stalled" if info["stalled"] else "reached max_rounds",
+                                                                              info["rounds"], info["faces_out"], info["target_faces"]))
+    return v, f
+
+
 def build_and_write(views, settings):
-    """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on, and write_ply to
-    settings["path"]: (vertices, faces)."""
+    """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on (removal, smoothing), then
+    decimate when it is on, and write_ply to settings["path"]: (vertices, faces) as written."""
     grid = MeshGrid(settings["border"], settings["voxel"])
     v, f = depth_to_mesh(views, grid, settings.get("trunc"), settings.get("min_views", DEFAULT_MIN_VIEWS),
                          settings.get("conf_threshold", DEFAULT_CONF), settings.get("views_per_batch"))
     if clean_requested(settings):
         v, f = clean(v, f, *clean_settings(settings))
+    if decimate_requested(settings):
+        v, f = _decimate_and_report(v, f, *decimate_settings(settings))
     write_ply(settings["path"], v, f)
     return v, f
 
@@ -596,13 +821,14 @@ def main(argv=None):
                                              "an existing mesh")
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--mvs", help="predict's output folder: {name}_init.pfm, {name}_prob.pfm and {name}.txt")
-    src.add_argument("--clean", metavar="IN_PLY", help="clean this mesh (a PLY write_ply wrote) instead of building one")
+    src.add_argument("--clean", metavar="IN_PLY", help="clean and / or decimate this mesh (a PLY write_ply wrote) instead of building one")
     ap.add_argument("--out", required=True, help="mesh file (.ply)")
     add_arguments(ap)
     a = ap.parse_args(argv)
     if a.clean is not None:
         try:
             check_clean_settings(a.min_faces, a.spurious, a.smooth, a.smooth_lambda)
+            check_decimate_settings(a.decimate, a.target_faces, a.decimate_max_rounds)
         except ValueError as e:
             ap.error("--clean: %s" % e)
     else:
@@ -612,6 +838,8 @@ def main(argv=None):
     if a.clean is not None:
         v, f = read_ply(a.clean)
         v, f = clean(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), a.min_faces, a.spurious, a.smooth, a.smooth_lambda)
+        if a.decimate < 1 or a.target_faces > 0:
+            v, f = _decimate_and_report(v, f, a.decimate, a.target_faces, a.decimate_max_rounds)
         write_ply(a.out, v, f)
         print("mesh %s: %d vertices, %d triangles cleaned from %s" % (a.out, v.shape[0], f.shape[0], a.clean))
         return a.out

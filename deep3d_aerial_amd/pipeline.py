@@ -88,9 +88,10 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     true orthophoto on that DSM (write_ortho_of) from the views' gathered depth maps, cameras and reference images; rank 0
     writes it; timings gets ortho_s.
     mesh: None (nothing changes), or the mesh settings {"path", "border", "voxel", "trunc", "min_views", "conf_threshold",
-    "views_per_batch"} and optionally the clean steps {"min_faces", "spurious", "smooth", "smooth_lambda"} (absent: off)
-    (mesh.settings_from_args): rank 0 builds the mesh of every gathered depth and confidence map with its camera, in global view
-    order, cleans it when a clean step is on (mesh.clean), and writes the PLY; the DSM from the mesh uses that mesh.  The
+    "views_per_batch"} and optionally the clean steps {"min_faces", "spurious", "smooth", "smooth_lambda"} and the decimation
+    {"decimate", "target_faces", "decimate_max_rounds"} (absent: off) (mesh.settings_from_args): rank 0 builds the mesh of every
+    gathered depth and confidence map with its camera, in global view order, cleans it when a clean step is on (mesh.clean),
+    decimates it when asked (mesh.decimate), and writes the PLY; the DSM from the mesh and the texture use that mesh.  The
     other ranks do nothing (no collective: the file does not depend on the number of ranks); timings gets mesh_s on rank 0.
     texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad"}
     (needs mesh; texture.settings_from_args): the mesh rank 0 wrote (after cleaning) textured from every rank's views and
@@ -102,6 +103,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         _mesh.check_settings(_grid, mesh.get("trunc"), mesh.get("min_views", _mesh.DEFAULT_MIN_VIEWS),
                              mesh.get("conf_threshold", _mesh.DEFAULT_CONF), mesh.get("views_per_batch"))
         _mesh.clean_settings(mesh)
+        _mesh.decimate_settings(mesh)
     dsm_source = dsm.get("source", "pc") if dsm is not None else None
     if dsm is not None:
         from . import dsm as _dsm
@@ -233,7 +235,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
 
 def write_mesh_of(all_maps, all_cams, settings, timings=None):
     """The mesh of every view (all_maps [n,2,H,W] depth and confidence, all_cams [n,2,4,4], by global view index), written to
-    settings["path"] (mesh.build_and_write, cleaned when a clean step is on).  Returns (vertices, faces) as written."""
+    settings["path"] (mesh.build_and_write: cleaned when a clean step is on, then decimated when asked).  Returns (vertices, faces) as written."""
     from . import mesh as _mesh
 
     t0 = time.perf_counter()

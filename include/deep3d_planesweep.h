@@ -1042,6 +1042,79 @@ int d3d_mesh_smooth(const float* vertices, long long n_vertices, const long long
                     float lambda, int iterations, float* work, float* out, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.14 -- decimating the surface mesh: memoryless quadric-error edge collapse in rounds of independent collapses
+ * (the rule is this project's, deep3d_aerial_amd/mesh.py states it in full; it does not claim to match OpenMVS / VCG).  A mesh
+ * is vertices [n_vertices, 3] fp32 and faces [n_faces, 3] int32, n_vertices < 2^31, 6 n_faces < 2^31.  A face with an index
+ * outside 0 .. n_vertices - 1 or with a repeated index is ignored by every pass and dropped by d3d_mesh_decimate_faces (the
+ * caller refuses such a mesh).  offset / nbr / fixed are d3d_mesh_adjacency's outputs for the same mesh.  The undirected edges
+ * a < b are numbered in (a, b) lexicographic order; there are at most 3 n_faces, the count is a DEVICE value (n_edges) and
+ * the per-edge arrays have max_edges >= n_edges entries (entries from n_edges on are written as "no candidate" or left
+ * alone).  Every pointer is DEVICE memory.  All arithmetic is fp64 without contraction unless said; no float atomics; the
+ * integer atomics are add and min, and their return values never reach an output.
+ */
+/* Scratch of d3d_mesh_decimate_incidence (0 for an out-of-range size). */
+size_t d3d_mesh_decimate_incidence_scratch_bytes(long long n_vertices, long long n_faces);
+
+/* d3d_mesh_decimate_incidence: the vertex -> face CSR.  face_offset [n_vertices + 1] int32, face_index [3 n_faces] int32: row
+ *   v holds the faces with a corner at v in increasing face index. */
+int d3d_mesh_decimate_incidence(const int* faces, long long n_faces, long long n_vertices, void* scratch, size_t scratch_bytes,
+                                int* face_offset, int* face_index, d3d_stream_t stream);
+
+/* d3d_mesh_decimate_quadrics: quadric [n_vertices, 10] fp64 = (aa, ab, ac, ad, bb, bc, bd, cc, cd, dd) summed over the faces of
+ *   the vertex's row in row order, from 0.  A face: nrm = (p1 - p0) x (p2 - p0), len = sqrt((nx nx + ny ny) + nz nz); nothing
+ *   unless len > 0; (a, b, c) = nrm / len, d = -((a x0 + b y0) + c z0), w = len / 2, each term w * (u * v). */
+int d3d_mesh_decimate_quadrics(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* face_offset,
+                               const int* face_index, double* quadric, d3d_stream_t stream);
+
+/* Scratch of d3d_mesh_decimate_edges (0 for an out-of-range size). */
+size_t d3d_mesh_decimate_edges_scratch_bytes(long long n_vertices);
+
+/* d3d_mesh_decimate_edges: edges [max_edges, 2] int32 = (a, b), a < b, in lexicographic order; *n_edges (int64) their count.
+ *   Edges beyond max_edges are counted but not written. */
+int d3d_mesh_decimate_edges(const long long* offset, const int* nbr, long long n_vertices, void* scratch, size_t scratch_bytes,
+                            long long max_edges, int* edges, long long* n_edges, d3d_stream_t stream);
+
+/* d3d_mesh_decimate_candidates: per edge e with a free endpoint the collapse target [max_edges, 3] fp32, its cost [max_edges]
+ *   fp32 and key [max_edges] int64 = (bits(cost) << 32) | (e * 2654435761 mod 2^32), or -1 when the collapse is not valid
+ *   (link condition, survivor degree, flips judged at the fp32 target).  An edge with both ends fixed, and every entry from
+ *   *n_edges on, gets target 0, cost 0, key -1. */
+int d3d_mesh_decimate_candidates(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const long long* offset,
+                                 const int* nbr, const unsigned char* fixed, const int* face_offset, const int* face_index,
+                                 const double* quadric, const int* edges, const long long* n_edges, long long max_edges, float* target,
+                                 float* cost, long long* key, d3d_stream_t stream);
+
+/* Scratch of d3d_mesh_decimate_select. */
+size_t d3d_mesh_decimate_select_scratch_bytes(void);
+
+/* d3d_mesh_decimate_select: *threshold (int64) = the k-th smallest of the keys >= 0 among key [max_edges] (the largest when
+ *   there are fewer than k; -1 when k == 0 or no key is >= 0). */
+int d3d_mesh_decimate_select(const long long* key, long long max_edges, long long k, void* scratch, size_t scratch_bytes,
+                             long long* threshold, d3d_stream_t stream);
+
+/* d3d_mesh_decimate_claim: claim [n_vertices] int64 = the smallest key among the eligible candidates (0 <= key <= *threshold)
+ *   whose neighbourhood {a, b} U N(a) U N(b) holds the vertex (LLONG_MAX when none does); clears *n_winners. */
+int d3d_mesh_decimate_claim(const long long* offset, const int* nbr, long long n_vertices, const int* edges, const long long* key,
+                            const long long* n_edges, long long max_edges, const long long* threshold, long long* claim,
+                            long long* n_winners, d3d_stream_t stream);
+
+/* d3d_mesh_decimate_apply: win [max_edges] uint8 = 1 for the eligible candidates that hold the claim of every vertex of their
+ *   neighbourhood.  out_vertices [n_vertices, 3] = vertices with every winner's survivor (b when only b is fixed, else a) at
+ *   its target; remap [n_vertices] int32 = the survivor for a winner's other endpoint, the vertex itself otherwise;
+ *   *n_winners (int64, cleared by d3d_mesh_decimate_claim) counts the winners.  vertices and out_vertices are distinct. */
+int d3d_mesh_decimate_apply(const float* vertices, long long n_vertices, const long long* offset, const int* nbr, const unsigned char* fixed,
+                            const int* edges, const long long* key, const float* target, const long long* n_edges, long long max_edges,
+                            const long long* threshold, const long long* claim, float* out_vertices, int* remap, unsigned char* win,
+                            long long* n_winners, d3d_stream_t stream);
+
+/* Scratch of d3d_mesh_decimate_faces (0 for an out-of-range size). */
+size_t d3d_mesh_decimate_faces_scratch_bytes(long long n_faces);
+
+/* d3d_mesh_decimate_faces: out_faces = the faces through remap, without those two of whose corners meet, in input order;
+ *   *n_kept (int64) their count; referenced [n_vertices] int32 = 1 for the vertices they use (for d3d_mesh_compact). */
+int d3d_mesh_decimate_faces(const int* faces, long long n_faces, long long n_vertices, const int* remap, void* scratch, size_t scratch_bytes,
+                            int* out_faces, int* referenced, long long* n_kept, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.13 -- texturing the surface mesh from the views (the semantics are this project's, deep3d_aerial_amd/texture.py
  * states them in full; they do not claim to match OpenMVS's TextureMesh).  A mesh is vertices [n_vertices, 3] fp32 and faces
  * [n_faces, 3] int32, n_vertices < 2^31, 3 n_faces < 2^31; faces with an index outside 0 .. n_vertices - 1 are skipped (the
