@@ -24,19 +24,19 @@ _f = ctypes.c_float
 _d = ctypes.c_double
 _sz = ctypes.c_size_t
 
-# name -> argtypes; restype is int except where noted.  Mirrors include/deep3d_planesweep.h.
+# name -> argtypes, or (argtypes, restype) where the function does not return int.  Mirrors include/deep3d_planesweep.h.
 SIGNATURES = {
     "d3d_version": [],
-    "d3d_last_error": [],
+    "d3d_last_error": ([], ctypes.c_char_p),
     "d3d_compose_projections": [_vp, _i, _vp, _vp],
     "d3d_debug_force_path": [_i],
     "d3d_debug_dispatch_counts": [_vp, _i],
-    "d3d_build_flags": [],
-    "d3d_h16_format": [],
+    "d3d_build_flags": ([], ctypes.c_char_p),
+    "d3d_h16_format": ([], ctypes.c_char_p),
     "d3d_compose_projections_f64": [_vp, _i, _vp, _vp],
     "d3d_homo_warp_f64coord": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_sweep_workspace_bytes": [_i, _i, _i, _i, _i, _i],  # returns size_t
-    "d3d_sweep_workspace_bytes_for": [_i, _i, _i, _i, _i, _i, _i],  # returns size_t
+    "d3d_sweep_workspace_bytes": ([_i, _i, _i, _i, _i, _i], _sz),
+    "d3d_sweep_workspace_bytes_for": ([_i, _i, _i, _i, _i, _i, _i], _sz),
     "d3d_homo_warp": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
     "d3d_variance_volume": [ctypes.POINTER(_vp), _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
     "d3d_variance_volume_planes": [ctypes.POINTER(_vp), _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
@@ -122,48 +122,48 @@ SIGNATURES = {
     "d3d_fusion_accumulate": [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double), _i, _i, _i, _i,
                               ctypes.c_double, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "d3d_fusion_finalize": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
-    "d3d_fusion_points_scratch_bytes": [_i, _i],  # returns size_t
+    "d3d_fusion_points_scratch_bytes": ([_i, _i], _sz),
     "d3d_fusion_mark_points": [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_double), _vp, _vp, _vp, _vp],
     "d3d_fusion_gather_points": [_vp, _vp, ctypes.POINTER(_vp), _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "d3d_flip_rows": [ctypes.POINTER(_vp), _i, _i, _i, _vp, _vp],
     "d3d_center_image_u8": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "d3d_normals_from_depth": [_vp, ctypes.POINTER(_f), _i, _i, _i, _i, _vp, _vp, _vp],
-    "d3d_dsm_scratch_bytes": [ctypes.c_longlong, _i, _i, _i],  # returns size_t
+    "d3d_dsm_scratch_bytes": ([ctypes.c_longlong, _i, _i, _i], _sz),
     "d3d_dsm_from_points": [_vp, ctypes.c_longlong, _d, _d, _d, _d, _d, _d, _i, _i, _i, _d, _i, _vp, _sz, _vp, _vp, _vp],
     "d3d_dsm_fill_moving_average": [_vp, _vp, _i, _i, _i, _vp],
-    "d3d_dsm_mesh_scratch_bytes": [ctypes.c_longlong, _i, _i],  # returns size_t
+    "d3d_dsm_mesh_scratch_bytes": ([ctypes.c_longlong, _i, _i], _sz),
     "d3d_dsm_from_mesh": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _sz, _vp, _vp],
-    "d3d_ortho_scratch_bytes": [_i, _i, _i],  # returns size_t
+    "d3d_ortho_scratch_bytes": ([_i, _i, _i], _sz),
     "d3d_ortho_select": [_vp, _d, _d, _d, _d, _i, _i, _vp, _i, _d, _vp, _sz, _vp, _vp],
     "d3d_ortho_colorize": [_vp, _d, _d, _d, _d, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
-    "d3d_mesh_scan_scratch_bytes": [ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_scan_scratch_bytes": ([ctypes.c_longlong], _sz),
     "d3d_mesh_mark": [_vp, _vp, _i, _i, _d, _vp, _vp],
     "d3d_mesh_bricks": [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
     "d3d_mesh_integrate": [_vp, _vp, _i, _vp, _i, _d, _d, _vp, _vp, _vp],
     "d3d_mesh_count": [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "d3d_mesh_emit": [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "d3d_mesh_compact": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
-    "d3d_mesh_adjacency_scratch_bytes": [ctypes.c_longlong, ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_adjacency_scratch_bytes": ([ctypes.c_longlong, ctypes.c_longlong], _sz),
     "d3d_mesh_adjacency": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _sz, _vp, _vp, _vp, _vp],
     "d3d_mesh_components": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, ctypes.POINTER(_i), _vp],
-    "d3d_mesh_stats_scratch_bytes": [ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_stats_scratch_bytes": ([ctypes.c_longlong], _sz),
     "d3d_mesh_component_stats": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_filter_scratch_bytes": [ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_filter_scratch_bytes": ([ctypes.c_longlong], _sz),
     "d3d_mesh_filter": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_longlong, _d, _vp, _sz, _vp, _vp, _vp, _vp],
     "d3d_mesh_smooth": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp],
-    "d3d_mesh_decimate_incidence_scratch_bytes": [ctypes.c_longlong, ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_decimate_incidence_scratch_bytes": ([ctypes.c_longlong, ctypes.c_longlong], _sz),
     "d3d_mesh_decimate_incidence": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _sz, _vp, _vp, _vp],
     "d3d_mesh_decimate_quadrics": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
-    "d3d_mesh_decimate_edges_scratch_bytes": [ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_decimate_edges_scratch_bytes": ([ctypes.c_longlong], _sz),
     "d3d_mesh_decimate_edges": [_vp, _vp, ctypes.c_longlong, _vp, _sz, ctypes.c_longlong, _vp, _vp, _vp],
     "d3d_mesh_decimate_candidates": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
-    "d3d_mesh_decimate_select_scratch_bytes": [],  # returns size_t
+    "d3d_mesh_decimate_select_scratch_bytes": ([], _sz),
     "d3d_mesh_decimate_select": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _sz, _vp, _vp],
     "d3d_mesh_decimate_claim": [_vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
     "d3d_mesh_decimate_apply": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_decimate_faces_scratch_bytes": [ctypes.c_longlong],  # returns size_t
+    "d3d_mesh_decimate_faces_scratch_bytes": ([ctypes.c_longlong], _sz),
     "d3d_mesh_decimate_faces": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
-    "d3d_texture_scratch_bytes": [ctypes.c_longlong, _i],  # returns size_t
+    "d3d_texture_scratch_bytes": ([ctypes.c_longlong, _i], _sz),
     "d3d_texture_select": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _d, _vp, _sz, _vp, _vp],
     "d3d_texture_edges": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
     "d3d_texture_charts": [_vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _vp],
@@ -203,20 +203,12 @@ def load():
             "%s not found -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C deep3d_aerial_amd/csrc`. There is no CPU fallback." % SO_PATH)
     lib = ctypes.CDLL(SO_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, sig in SIGNATURES.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
             raise LibraryMissing("symbol %s missing from %s" % (name, SO_PATH)) from e
-        fn.argtypes = argtypes
-        fn.restype = (ctypes.c_char_p if name in ("d3d_last_error", "d3d_build_flags", "d3d_h16_format") else
-                      ctypes.c_size_t if name in ("d3d_sweep_workspace_bytes", "d3d_sweep_workspace_bytes_for", "d3d_fusion_points_scratch_bytes",
-                                                         "d3d_dsm_scratch_bytes", "d3d_dsm_mesh_scratch_bytes", "d3d_ortho_scratch_bytes",
-                                                         "d3d_mesh_scan_scratch_bytes", "d3d_mesh_adjacency_scratch_bytes",
-                                                         "d3d_mesh_stats_scratch_bytes", "d3d_mesh_filter_scratch_bytes",
-                                                         "d3d_mesh_decimate_incidence_scratch_bytes", "d3d_mesh_decimate_edges_scratch_bytes",
-                                                         "d3d_mesh_decimate_select_scratch_bytes", "d3d_mesh_decimate_faces_scratch_bytes",
-                                                         "d3d_texture_scratch_bytes") else ctypes.c_int)
+        fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, ctypes.c_int)
     if lib.d3d_version() != ABI_VERSION:
         raise LibraryMissing("ABI version mismatch: library %d, binding %d" % (lib.d3d_version(), ABI_VERSION))
     _lib = lib

@@ -8,7 +8,7 @@
 //
 // Max:        bin (one atomicAdd on count + one atomicMax of the key per point) -> finalize per cell.
 // Robust_Max: bin (atomicAdd on count; the returned value is the point's rank in its cell, 4 B per point)
-//             -> exclusive scan of count (reduce, scan of the block sums, apply) -> scatter of the keys to offset[cell] + rank
+//             -> exclusive scan of count (the shared scan, geom_shared.h) -> scatter of the keys to offset[cell] + rank
 //             -> select the (t+1)-th largest key, t = floor(trim * n): cells of up to DSM_SMALL points one lane each, keys
 //                in registers; larger cells on a compacted list, one workgroup each, radix select over the key bytes with an
 //                LDS histogram (a persistent grid walks the list: a cell of 10^5 points holds one workgroup, not the launch).
@@ -20,13 +20,11 @@
 #include <cmath>
 
 #include "common.h"
-#include "mesh_shared.h"
+#include "geom_shared.h"
 
 namespace d3d {
 
 constexpr int DSM_BLOCK = 256;
-constexpr int DSM_SCAN_ITEMS = 16;                          // count elements per thread of the scan
-constexpr int DSM_SCAN_TILE = DSM_BLOCK * DSM_SCAN_ITEMS;   // count elements per scan workgroup
 constexpr int DSM_SMALL = 32;                               // cells of at most this many points: one lane, keys in registers
 constexpr int DSM_BIG_GRID = 1024;                          // workgroups walking the list of larger cells
 constexpr int DSM_FILL_TILE = 16;
@@ -71,83 +69,6 @@ __global__ __launch_bounds__(DSM_BLOCK) void dsm_max_finalize_kernel(const int* 
     if (c >= cells) return;
     const int n = count[c];
     height[c] = (n > 0 && n >= min_points) ? dsm_unkey(keymax[c]) : __builtin_nanf("");
-}
-
-// Exclusive block scan of one int per thread; returns the thread's prefix, *total the block's sum.
-__device__ __forceinline__ int dsm_block_exclusive_scan(int v, int* lds, int* total) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 1; s < DSM_BLOCK; s <<= 1) {
-        const int a = t >= s ? lds[t - s] : 0;
-        __syncthreads();
-        lds[t] += a;
-        __syncthreads();
-    }
-    const int incl = lds[t];
-    *total = lds[DSM_BLOCK - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-__device__ __forceinline__ void dsm_load_items(const int* __restrict__ count, long base, int cells, int* v) {
-    if (base + DSM_SCAN_ITEMS <= cells) {
-        const int4* q = reinterpret_cast<const int4*>(count + base);
-#pragma unroll
-        for (int k = 0; k < DSM_SCAN_ITEMS / 4; ++k) {
-            const int4 a = q[k];
-            v[4 * k] = a.x; v[4 * k + 1] = a.y; v[4 * k + 2] = a.z; v[4 * k + 3] = a.w;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < DSM_SCAN_ITEMS; ++k) v[k] = base + k < cells ? count[base + k] : 0;
-    }
-}
-
-__global__ __launch_bounds__(DSM_BLOCK) void dsm_scan_reduce_kernel(const int* __restrict__ count, int cells, int* __restrict__ partial) {
-    __shared__ int lds[DSM_BLOCK];
-    const long base = (long)blockIdx.x * DSM_SCAN_TILE + threadIdx.x * DSM_SCAN_ITEMS;
-    int v[DSM_SCAN_ITEMS];
-    dsm_load_items(count, base, cells, v);
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < DSM_SCAN_ITEMS; ++k) s += v[k];
-    int total;
-    dsm_block_exclusive_scan(s, lds, &total);
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// One workgroup: exclusive scan of the nb block sums in place, chunk by chunk with a carry.
-__global__ __launch_bounds__(DSM_BLOCK) void dsm_scan_partials_kernel(int* __restrict__ partial, int nb) {
-    __shared__ int lds[DSM_BLOCK];
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += DSM_BLOCK) {
-        const int i = b0 + threadIdx.x;
-        const int v = i < nb ? partial[i] : 0;
-        int total;
-        const int ex = dsm_block_exclusive_scan(v, lds, &total);
-        if (i < nb) partial[i] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ __launch_bounds__(DSM_BLOCK) void dsm_scan_apply_kernel(const int* __restrict__ count, int cells, const int* __restrict__ partial,
-                                                                   int* __restrict__ offset) {
-    __shared__ int lds[DSM_BLOCK];
-    const long base = (long)blockIdx.x * DSM_SCAN_TILE + threadIdx.x * DSM_SCAN_ITEMS;
-    int v[DSM_SCAN_ITEMS];
-    dsm_load_items(count, base, cells, v);
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < DSM_SCAN_ITEMS; ++k) s += v[k];
-    int total;
-    int run = partial[blockIdx.x] + dsm_block_exclusive_scan(s, lds, &total);
-#pragma unroll
-    for (int k = 0; k < DSM_SCAN_ITEMS; ++k) {
-        if (base + k < cells) offset[base + k] = run;
-        run += v[k];
-    }
 }
 
 __global__ __launch_bounds__(DSM_BLOCK) void dsm_scatter_kernel(const float* __restrict__ xyz, int n, DsmGrid g, const int* __restrict__ offset,
@@ -493,18 +414,17 @@ __global__ __launch_bounds__(DSM_BLOCK) void dsm_key_finalize_kernel(const unsig
     height[c] = k ? dsm_unkey(k) : __builtin_nanf("");   // key 0 is the unkeyed NaN: no finite sample has it
 }
 
-static size_t dsm_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct DsmMeshScratch {
     size_t keymax, n_big, big, total;
 };
 
 static DsmMeshScratch dsm_mesh_layout(long long n_faces, long long cells) {
+    ScratchLayout L;
     DsmMeshScratch s = {};
-    s.keymax = 0;
-    s.n_big = dsm_align((size_t)cells * 4);
-    s.big = s.n_big + dsm_align(4);
-    s.total = s.big + dsm_align((size_t)n_faces * 16);
+    s.keymax = L.take((size_t)cells * 4);
+    s.n_big = L.take(4);
+    s.big = L.take((size_t)n_faces * 16);
+    s.total = L.bytes;
     return s;
 }
 
@@ -513,28 +433,19 @@ struct DsmScratch {
 };
 
 static DsmScratch dsm_layout(long long n, long long cells, int select) {
+    ScratchLayout L;
     DsmScratch s = {};
-    size_t at = 0;
     if (select == 0) {
-        s.keymax = at;
-        at += dsm_align((size_t)cells * 4);
+        s.keymax = L.take((size_t)cells * 4);
     } else {
-        const long long nb = (cells + DSM_SCAN_TILE - 1) / DSM_SCAN_TILE;
-        const long long cap = std::min(cells, n / (DSM_SMALL + 1) + 1);
-        s.rank = at;
-        at += dsm_align((size_t)n * 4);
-        s.offset = at;
-        at += dsm_align((size_t)cells * 4);
-        s.partial = at;
-        at += dsm_align((size_t)nb * 4);
-        s.keys = at;
-        at += dsm_align((size_t)n * 4);
-        s.big = at;
-        at += dsm_align((size_t)cap * 4);
-        s.n_big = at;
-        at += dsm_align(4);
+        s.rank = L.take((size_t)n * 4);
+        s.offset = L.take((size_t)cells * 4);
+        s.partial = L.take((size_t)geom_scan_tiles(cells) * 4);   // the scan's tile sums as int32
+        s.keys = L.take((size_t)n * 4);
+        s.big = L.take((size_t)std::min(cells, n / (DSM_SMALL + 1) + 1) * 4);
+        s.n_big = L.take(4);
     }
-    s.total = at;
+    s.total = L.bytes;
     return s;
 }
 
@@ -599,13 +510,8 @@ extern "C" int d3d_dsm_from_points(const float* xyz, long long n_points, double 
     if (n > 0) {
         hipLaunchKernelGGL((dsm_bin_kernel<true>), dim3(gp), dim3(DSM_BLOCK), 0, st, xyz, n, g, count, (unsigned*)nullptr, rank);
         D3D_LAUNCH_CHECK("dsm_bin_kernel launch");
-        const int nb = ceil_div(nc, DSM_SCAN_TILE);
-        hipLaunchKernelGGL(dsm_scan_reduce_kernel, dim3(nb), dim3(DSM_BLOCK), 0, st, count, nc, partial);
-        D3D_LAUNCH_CHECK("dsm_scan_reduce_kernel launch");
-        hipLaunchKernelGGL(dsm_scan_partials_kernel, dim3(1), dim3(DSM_BLOCK), 0, st, partial, nb);
-        D3D_LAUNCH_CHECK("dsm_scan_partials_kernel launch");
-        hipLaunchKernelGGL(dsm_scan_apply_kernel, dim3(nb), dim3(DSM_BLOCK), 0, st, count, nc, partial, offset);
-        D3D_LAUNCH_CHECK("dsm_scan_apply_kernel launch");
+        rc = geom_scan_sums<int>(count, offset, cells, partial, nullptr, st);   // the total is at most n_points < 2^31
+        if (rc != D3D_OK) return rc;
         hipLaunchKernelGGL(dsm_scatter_kernel, dim3(gp), dim3(DSM_BLOCK), 0, st, xyz, n, g, offset, rank, keys);
         D3D_LAUNCH_CHECK("dsm_scatter_kernel launch");
     } else {

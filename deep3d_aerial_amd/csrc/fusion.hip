@@ -15,6 +15,7 @@
 // Contraction is off (csrc/Makefile: -ffp-contract=off) so that products and sums round separately as in the
 // oracle (oracle/fusion_oracle.c).
 #include "common.h"
+#include "geom_shared.h"
 
 namespace d3d {
 
@@ -241,8 +242,7 @@ __global__ __launch_bounds__(256) void flag_count_kernel(const unsigned char* __
     unsigned c = 0;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) c += (base + k < n && flags[base + k]) ? 1u : 0u;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) block_sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -275,14 +275,8 @@ __device__ __forceinline__ unsigned thread_prefix(const unsigned char* __restric
     unsigned c = 0;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) { mine[k] = (base + k < n && flags[base + k]) ? 1u : 0u; c += mine[k]; }
-    unsigned incl = c;
-#pragma unroll
-    for (int sft = 1; sft < 64; sft <<= 1) { const unsigned o = __shfl_up(incl, sft); if ((int)(threadIdx.x & 63) >= sft) incl += o; }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    unsigned woff = 0;
-    for (int wv = 0; wv < (int)(threadIdx.x >> 6); ++wv) woff += wsum[wv];
-    return block_offs[blockIdx.x] + woff + incl - c;
+    unsigned total;
+    return block_offs[blockIdx.x] + block_exclusive<unsigned>(c, wsum, &total);
 }
 
 // valid pixel with ordinal i (among the valid ones) is kept iff i % skip == 0 and it lies inside the block in x and y

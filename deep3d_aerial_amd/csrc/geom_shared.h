@@ -1,0 +1,214 @@
+// The primitives the geometry stages share (fusion, dsm, ortho, mesh, mesh_clean, mesh_decimate, texture); not part of the
+// public ABI.  The kernels behind the host functions declared here are in geom.hip.
+#pragma once
+#include "common.h"
+
+namespace d3d {
+
+// Order-preserving fp32 -> uint32 key: for non-NaN a, b, a < b exactly when dsm_key(a) < dsm_key(b), so integer atomicMin /
+// atomicMax of keys give the float minimum / maximum whatever the order of the lanes.
+__device__ __forceinline__ unsigned dsm_key(float z) {
+    const unsigned u = __float_as_uint(z);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float dsm_unkey(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// wave and workgroup
+// ---------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float geom_min(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ float geom_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ int geom_min(int a, int b) { return min(a, b); }
+__device__ __forceinline__ int geom_max(int a, int b) { return max(a, b); }
+__device__ __forceinline__ unsigned geom_min(unsigned a, unsigned b) { return min(a, b); }
+__device__ __forceinline__ unsigned geom_max(unsigned a, unsigned b) { return max(a, b); }
+
+// The minimum / maximum / sum of x over the 64 lanes of the wave, in every lane.
+template <typename T>
+__device__ __forceinline__ T wave_min(T x) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) x = geom_min(x, __shfl_xor(x, o, 64));
+    return x;
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_max(T x) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) x = geom_max(x, __shfl_xor(x, o, 64));
+    return x;
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// Exclusive scan of one value per lane over the workgroup (blockDim.x a multiple of 64); *total gets the sum.
+template <typename T>
+__device__ __forceinline__ T block_exclusive(T x, T* lds, T* total) {
+    // lds: one T per wave
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    T inc = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += y;
+    }
+    if (lane == 63) lds[wave] = inc;
+    __syncthreads();
+    T before = 0, all = 0;
+    for (int w = 0; w < n_waves; ++w) {
+        const T v = lds[w];
+        if (w < wave) before += v;
+        all += v;
+    }
+    __syncthreads();
+    *total = all;
+    return before + inc - x;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// device scan
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int GEOM_SCAN_TILE = 256 * 16;   // values per workgroup of the scan: 256 lanes of 16
+
+inline long long geom_scan_tiles(long long n) { return (n + GEOM_SCAN_TILE - 1) / GEOM_SCAN_TILE; }
+
+// Exclusive scan of n int32 values into out (out may be in), *total (device int64, or null) their sum; tile_sums: one S per
+// tile of GEOM_SCAN_TILE values.  S is int64 where the caller checks that the total fits in int32, int32 where it is known to
+// (the DSM's scratch has 4 bytes per tile, and its total is at most n_points < 2^31).
+template <typename S>
+int geom_scan_sums(const int* in, int* out, long long n, S* tile_sums, long long* total, hipStream_t st);
+
+// d3d_mesh_scan_scratch_bytes(n) for n >= 0: the int64 tile sums
+inline size_t geom_scan_bytes(long long n) { return (size_t)(geom_scan_tiles(n) > 0 ? geom_scan_tiles(n) : 1) * 8; }
+
+// The scan with a scratch of geom_scan_bytes(n) bytes.
+inline int geom_scan(const int* in, int* out, long long n, void* scratch, long long* total, hipStream_t st) {
+    return geom_scan_sums(in, out, n, (long long*)scratch, total, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// scratch layout: `at = L.take(bytes)` hands out consecutive 256-byte aligned offsets, L.bytes is the size so far
+// ---------------------------------------------------------------------------------------------------------------------------
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct ScratchLayout {
+    size_t bytes = 0;
+    size_t take(size_t b) {
+        const size_t at = bytes;
+        bytes += align256(b);
+        return at;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// union-find by hooking and pointer jumping
+// ---------------------------------------------------------------------------------------------------------------------------
+// parent[i] = i
+int geom_iota(int* parent, long long n, hipStream_t st);
+// parent[i] = the root of i
+int geom_jump(int* parent, long long n, hipStream_t st);
+
+// Joins the sets of two elements whose parents the caller has loaded as pa and pb: the larger parent gets the smaller one
+// (atomicMin), so parents only decrease and stay in their set, and the fixed point of hooking and jumping in turn is the
+// smallest index of each set.  The caller's plain loads may return a parent that another workgroup has already lowered, or not
+// yet: either is a member of the same set no larger than the element, so a stale read only costs a round.  A launch that sets
+// no flag has made no atomic, so its loads saw the previous launch's values, and they agree on every pair.
+__device__ __forceinline__ void geom_hook(int* parent, int pa, int pb, int* changed) {
+    if (pa != pb) {
+        atomicMin(parent + max(pa, pb), min(pa, pb));
+        *changed = 1;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// faces
+// ---------------------------------------------------------------------------------------------------------------------------
+// The indices of face f; false when one is out of range or, with DISTINCT, two are equal (the Python side refuses such faces;
+// the kernels skip them).
+template <bool DISTINCT>
+__device__ __forceinline__ bool geom_face(const int* __restrict__ faces, long f, long long n, int* a, int* b, int* c) {
+    *a = faces[3 * f];
+    *b = faces[3 * f + 1];
+    *c = faces[3 * f + 2];
+    const bool ok = *a >= 0 && *a < n && *b >= 0 && *b < n && *c >= 0 && *c < n;
+    return DISTINCT ? ok && *a != *b && *b != *c && *c != *a : ok;
+}
+
+// The distinct edges of face (a, b, c): the pairs (a,b) (b,c) (c,a) with unequal ends, each unordered pair once.
+__device__ __forceinline__ int geom_face_edges(int a, int b, int c, int* x, int* y) {
+    if (a == b && b == c) return 0;
+    if (a == b || c == a) {   // (a, a, c) or (a, b, a): one edge
+        x[0] = a;
+        y[0] = a == b ? c : b;
+        return 1;
+    }
+    if (b == c) {
+        x[0] = a;
+        y[0] = b;
+        return 1;
+    }
+    x[0] = a, y[0] = b;
+    x[1] = b, y[1] = c;
+    x[2] = c, y[2] = a;
+    return 3;
+}
+
+// Compaction of the faces with keep[f] != 0, in input order: pos = the exclusive scan of keep, *n_kept its total, the kept
+// faces' indices (through remap when it is not null) to out_faces, and referenced[v] = 1 for each of them.
+struct KeepScratch {
+    size_t keep, pos, scan, bytes;
+};
+
+inline KeepScratch geom_keep_layout(long long m) {
+    const size_t nf = (size_t)(m > 0 ? m : 1);
+    ScratchLayout L;
+    KeepScratch s;
+    s.keep = L.take(nf * 4);
+    s.pos = L.take(nf * 4);
+    s.scan = L.take(geom_scan_bytes(m));
+    s.bytes = L.bytes;
+    return s;
+}
+
+int geom_scatter_kept(const int* faces, long long m, const int* remap, void* scratch, const KeepScratch& L, int* out_faces,
+                      int* referenced, long long* n_kept, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// fp64 pinhole projection of a d3d_mesh_view_t or d3d_ortho_view_t: p = R X + t, q = K p, each row summed left to right,
+// u = q0 / q2, v = q1 / q2 (built with -ffp-contract=off: no contraction)
+// ---------------------------------------------------------------------------------------------------------------------------
+struct GeomPq {
+    double p2, q0, q1, q2;
+};
+
+template <typename View>
+__device__ __forceinline__ GeomPq geom_project(const View& V, double X0, double X1, double X2) {
+    const double p0 = V.R[0] * X0 + V.R[1] * X1 + V.R[2] * X2 + V.t[0];
+    const double p1 = V.R[3] * X0 + V.R[4] * X1 + V.R[5] * X2 + V.t[1];
+    const double p2 = V.R[6] * X0 + V.R[7] * X1 + V.R[8] * X2 + V.t[2];
+    GeomPq r;
+    r.p2 = p2;
+    r.q0 = V.K[0] * p0 + V.K[1] * p1 + V.K[2] * p2;
+    r.q1 = V.K[3] * p0 + V.K[4] * p1 + V.K[5] * p2;
+    r.q2 = V.K[6] * p0 + V.K[7] * p1 + V.K[8] * p2;
+    return r;
+}
+
+// (u, v) of X in view V when it lies in front of the view and inside its image, else false.
+__device__ __forceinline__ bool ortho_uv(const d3d_ortho_view_t& V, double X0, double X1, double X2, double* u, double* v, double* p2) {
+    const GeomPq r = geom_project(V, X0, X1, X2);
+    if (!(r.p2 > 0.0 && r.q2 > 0.0)) return false;
+    *u = r.q0 / r.q2;
+    *v = r.q1 / r.q2;
+    *p2 = r.p2;
+    return *u >= 0.0 && *u <= (double)(V.W - 1) && *v >= 0.0 && *v <= (double)(V.H - 1);
+}
+
+}  // namespace d3d

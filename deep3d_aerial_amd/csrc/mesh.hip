@@ -3,7 +3,7 @@
 //
 // mark:      one lane per pixel; the back-projected pixel centre's brick gets a byte flag in a grid padded by one brick.
 //            Idempotent stores, no atomics.
-// bricks:    the 3^3 dilation of the flags per brick, a reduce-then-scan, then the brick list and the dense index grid.
+// bricks:    the 3^3 dilation of the flags per brick, the shared scan (geom_shared.h), then the brick list and the dense index grid.
 // integrate: one workgroup per allocated brick, one lane per voxel.  Every wave tests 64 views at a time against the brick's
 //            box (8 corners, one ballot) and walks the set bits in increasing view order; sums stay in registers, one store per
 //            voxel per call.
@@ -16,12 +16,11 @@
 #include <cstdint>
 
 #include "common.h"
-#include "mesh_shared.h"
+#include "geom_shared.h"
 
 namespace d3d {
 
 constexpr int MESH_BRICK = 512;   // 8^3 voxels, one lane each
-constexpr int SCAN_BLOCK = 256, SCAN_PER = 16, SCAN_TILE = SCAN_BLOCK * SCAN_PER;
 static_assert(sizeof(d3d_mesh_view_t) == 192, "d3d_mesh_view_t: the layout deep3d_aerial_amd/mesh.py fills");
 
 // The 6 Kuhn tetrahedra of a cube around its diagonal 0 -> 7 (corner c = x | y << 1 | z << 2), one per axis permutation in
@@ -47,74 +46,6 @@ __device__ __forceinline__ double mesh_coord(double lo, double s, int i) { retur
 // linear brick index of padded / unpadded grids
 __device__ __forceinline__ long mesh_pad_index(const d3d_mesh_grid_t& g, int bi, int bj, int bk) {
     return ((long)(bk + 1) * (g.by + 2) + (bj + 1)) * (g.bx + 2) + (bi + 1);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// exclusive scan of int32 values: tile sums (int64), one workgroup over the tile sums, then each tile with its offset
-// ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SCAN_BLOCK) void mesh_scan_reduce_kernel(const int* __restrict__ in, long n, long long* __restrict__ tile_sums) {
-    __shared__ int lds[SCAN_BLOCK / 64];
-    const long base = (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_PER;
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; ++k)
-        if (base + k < n) s += in[base + k];
-    int total;
-    mesh_block_exclusive<int>(s, lds, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void mesh_scan_tiles_kernel(long long* __restrict__ tile_sums, int n_tiles, long long* __restrict__ total) {
-    __shared__ long long lds[1024 / 64];
-    long long carry = 0;
-    for (int base = 0; base < n_tiles; base += 1024) {
-        const int i = base + threadIdx.x;
-        const long long x = i < n_tiles ? tile_sums[i] : 0;
-        long long all;
-        const long long ex = mesh_block_exclusive<long long>(x, lds, &all);
-        if (i < n_tiles) tile_sums[i] = carry + ex;
-        carry += all;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-// out may be in: each lane reads its values before it writes them
-__global__ __launch_bounds__(SCAN_BLOCK) void mesh_scan_apply_kernel(const int* in, long n, const long long* __restrict__ tile_sums, int* out) {
-    __shared__ int lds[SCAN_BLOCK / 64];
-    const long base = (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_PER;
-    int v[SCAN_PER];
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; ++k) {
-        v[k] = base + k < n ? in[base + k] : 0;
-        s += v[k];
-    }
-    int total;
-    const int ex = mesh_block_exclusive<int>(s, lds, &total);
-    long long run = tile_sums[blockIdx.x] + ex;
-#pragma unroll
-    for (int k = 0; k < SCAN_PER; ++k) {
-        if (base + k < n) out[base + k] = (int)run;   // the totals decide whether these fit; the caller checks them
-        run += v[k];
-    }
-}
-
-static long long mesh_scan_tiles(long long n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
-
-int mesh_scan(const int* in, int* out, long long n, void* scratch, long long* total, hipStream_t st) {
-    const long long tiles = mesh_scan_tiles(n);
-    long long* sums = (long long*)scratch;
-    if (tiles > 0) {
-        hipLaunchKernelGGL(mesh_scan_reduce_kernel, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, st, in, (long)n, sums);
-        D3D_LAUNCH_CHECK("mesh_scan_reduce_kernel launch");
-    }
-    hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(1), dim3(1024), 0, st, sums, (int)tiles, total);
-    D3D_LAUNCH_CHECK("mesh_scan_tiles_kernel launch");
-    if (tiles > 0) {
-        hipLaunchKernelGGL(mesh_scan_apply_kernel, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, st, in, (long)n, sums, out);
-        D3D_LAUNCH_CHECK("mesh_scan_apply_kernel launch");
-    }
-    return D3D_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -176,29 +107,13 @@ __global__ __launch_bounds__(256) void mesh_list_kernel(d3d_mesh_grid_t g, const
 // ---------------------------------------------------------------------------------------------------------------------------
 // integration
 // ---------------------------------------------------------------------------------------------------------------------------
-struct MeshPq {
-    double p2, q0, q1, q2;
-};
-
-__device__ __forceinline__ MeshPq mesh_project(const d3d_mesh_view_t& V, double X0, double X1, double X2) {
-    const double p0 = V.R[0] * X0 + V.R[1] * X1 + V.R[2] * X2 + V.t[0];
-    const double p1 = V.R[3] * X0 + V.R[4] * X1 + V.R[5] * X2 + V.t[1];
-    const double p2 = V.R[6] * X0 + V.R[7] * X1 + V.R[8] * X2 + V.t[2];
-    MeshPq r;
-    r.p2 = p2;
-    r.q0 = V.K[0] * p0 + V.K[1] * p1 + V.K[2] * p2;
-    r.q1 = V.K[3] * p0 + V.K[4] * p1 + V.K[5] * p2;
-    r.q2 = V.K[6] * p0 + V.K[7] * p1 + V.K[8] * p2;
-    return r;
-}
-
 // May view V observe a voxel centre in the box [lo, hi]?  False only when all 8 corners lie in front of the view and their
 // projections' bounding box misses the image by more than a pixel (a projective map keeps convexity where q2 > 0).
 __device__ __forceinline__ bool mesh_box_visible(const d3d_mesh_view_t& V, const double* lo, const double* hi) {
     double umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const MeshPq r = mesh_project(V, (k & 1) ? hi[0] : lo[0], (k & 2) ? hi[1] : lo[1], (k & 4) ? hi[2] : lo[2]);
+        const GeomPq r = geom_project(V, (k & 1) ? hi[0] : lo[0], (k & 2) ? hi[1] : lo[1], (k & 4) ? hi[2] : lo[2]);
         if (!(r.p2 > 0.0 && r.q2 > 0.0)) return true;
         const double u = r.q0 / r.q2, v = r.q1 / r.q2;
         if (!(isfinite(u) && isfinite(v))) return true;
@@ -236,7 +151,7 @@ __global__ __launch_bounds__(MESH_BRICK) void mesh_integrate_kernel(d3d_mesh_gri
             bits &= bits - 1;
             if (!exists) continue;
             const d3d_mesh_view_t& V = views[vi];
-            const MeshPq r = mesh_project(V, X0, X1, X2);
+            const GeomPq r = geom_project(V, X0, X1, X2);
             if (!(r.p2 > 0.0 && r.q2 > 0.0)) continue;
             const double px = floor(r.q0 / r.q2 + 0.5), py = floor(r.q1 / r.q2 + 0.5);
             if (!(px >= 0.0 && px <= (double)(V.W - 1) && py >= 0.0 && py <= (double)(V.H - 1))) continue;
@@ -420,11 +335,6 @@ using namespace d3d;
         D3D_REQUIRE(_e == nullptr, "mesh grid: %s", _e);   \
     } while (0)
 
-extern "C" size_t d3d_mesh_scan_scratch_bytes(long long n) {
-    if (n < 0) return 0;
-    return (size_t)(mesh_scan_tiles(n) > 0 ? mesh_scan_tiles(n) : 1) * 8;
-}
-
 extern "C" int d3d_mesh_mark(const d3d_mesh_grid_t* grid, const d3d_mesh_view_t* views, int n_views, int max_pixels, double conf_threshold,
                              unsigned char* marks, d3d_stream_t stream) {
     D3D_REQUIRE(grid && marks, "null pointer (grid, marks)");
@@ -451,7 +361,7 @@ extern "C" int d3d_mesh_bricks(const d3d_mesh_grid_t* grid, const unsigned char*
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(mesh_dilate_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, *grid, marks, (long)n, brick_index);
     D3D_LAUNCH_CHECK("mesh_dilate_kernel launch");
-    const int rc = mesh_scan(brick_index, brick_index, n, scratch, n_bricks, st);
+    const int rc = geom_scan(brick_index, brick_index, n, scratch, n_bricks, st);
     if (rc != D3D_OK) return rc;
     hipLaunchKernelGGL(mesh_list_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, *grid, marks, (long)n, brick_index, brick_list);
     D3D_LAUNCH_CHECK("mesh_list_kernel launch");
@@ -496,9 +406,9 @@ extern "C" int d3d_mesh_count(const d3d_mesh_grid_t* grid, const int* brick_list
                            edges, vert_base, face_base);
         D3D_LAUNCH_CHECK("mesh_count_kernel launch");
     }
-    int rc = mesh_scan(vert_base, vert_base, n, scratch, totals, st);
+    int rc = geom_scan(vert_base, vert_base, n, scratch, totals, st);
     if (rc != D3D_OK) return rc;
-    return mesh_scan(face_base, face_base, n, scratch, totals + 1, st);
+    return geom_scan(face_base, face_base, n, scratch, totals + 1, st);
 }
 
 extern "C" int d3d_mesh_emit(const d3d_mesh_grid_t* grid, const int* brick_list, const int* brick_index, int n_bricks, const float* sum,
@@ -525,7 +435,7 @@ extern "C" int d3d_mesh_compact(const float* vertices, long long n_vertices, int
     D3D_REQUIRE(scratch_bytes >= d3d_mesh_scan_scratch_bytes(n_vertices), "scratch of %zu bytes, %zu needed (d3d_mesh_scan_scratch_bytes)",
                 scratch_bytes, d3d_mesh_scan_scratch_bytes(n_vertices));
     hipStream_t st = (hipStream_t)stream;
-    const int rc = mesh_scan(referenced, remap, n_vertices, scratch, n_kept, st);
+    const int rc = geom_scan(referenced, remap, n_vertices, scratch, n_kept, st);
     if (rc != D3D_OK) return rc;
     if (n_vertices > 0) {
         hipLaunchKernelGGL(mesh_scatter_kernel, dim3(ceil_div(n_vertices, 256)), dim3(256), 0, st, vertices, (long)n_vertices, referenced, remap,

@@ -7,9 +7,8 @@
 //             and writes the distinct neighbours in place.  Longer rows go to a list that workgroups walk: a rank sort and a
 //             scan of the run starts.  A scan of the distinct counts and a copy give the CSR.  Every row is sorted, so the
 //             arrival order of the scatter never reaches the output.
-// components: parent[v] = v; hooking (one lane per face, atomicMin of the smaller parent into the larger one) and full pointer
-//             jumping in separate launches until a hooking launch changes nothing.  Parents only decrease and stay in their
-//             component; a stale read only costs a round, and the host reads one flag per round.  The fixed point is the
+// components: parent[v] = v; hooking (one lane per face, geom_hook of its corners) and full pointer jumping in separate
+//             launches until a hooking launch changes nothing; the host reads one flag per round.  The fixed point is the
 //             smallest vertex index of each component.
 // stats:      per-component face counts (atomicAdd) and boxes (atomicMin / atomicMax of dsm_key), each wave folding a run of
 //             equal labels before its atomics; the box of the referenced vertices by the same keys.
@@ -22,7 +21,7 @@
 #include <cstdint>
 
 #include "common.h"
-#include "mesh_shared.h"
+#include "geom_shared.h"
 
 namespace d3d {
 
@@ -32,43 +31,15 @@ constexpr int MC_SLOW_GRID = 256;    // workgroups walking the list of longer ro
 constexpr int MC_CHUNK = 64 * 64;    // faces / vertices per wave in the stats passes (64 steps of 64)
 constexpr long long MC_MAX_ENTRIES = (1ll << 31) - 1;
 
-static size_t mc_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// The distinct edges of face (a, b, c): the pairs (a,b) (b,c) (c,a) with unequal ends, each unordered pair once.
-__device__ __forceinline__ int mc_face_edges(int a, int b, int c, int* x, int* y) {
-    if (a == b && b == c) return 0;
-    if (a == b || c == a) {   // (a, a, c) or (a, b, a): one edge
-        x[0] = a;
-        y[0] = a == b ? c : b;
-        return 1;
-    }
-    if (b == c) {
-        x[0] = a;
-        y[0] = b;
-        return 1;
-    }
-    x[0] = a, y[0] = b;
-    x[1] = b, y[1] = c;
-    x[2] = c, y[2] = a;
-    return 3;
-}
-
-__device__ __forceinline__ bool mc_face(const int* __restrict__ faces, long f, long long n, int* a, int* b, int* c) {
-    *a = faces[3 * f];
-    *b = faces[3 * f + 1];
-    *c = faces[3 * f + 2];
-    return *a >= 0 && *a < n && *b >= 0 && *b < n && *c >= 0 && *c < n;   // out-of-range faces are skipped (mesh.py refuses them)
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // adjacency
 // ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MC_BLOCK) void mc_count_kernel(const int* __restrict__ faces, long m, long long n, int* __restrict__ cnt) {
     const long f = (long)blockIdx.x * MC_BLOCK + threadIdx.x;
     int a, b, c;
-    if (f >= m || !mc_face(faces, f, n, &a, &b, &c)) return;
+    if (f >= m || !geom_face<false>(faces, f, n, &a, &b, &c)) return;
     int x[3], y[3];
-    const int ne = mc_face_edges(a, b, c, x, y);
+    const int ne = geom_face_edges(a, b, c, x, y);
 #pragma unroll
     for (int e = 0; e < 3; ++e)
         if (e < ne) {
@@ -81,9 +52,9 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_scatter_kernel(const int* __restr
                                                               int* __restrict__ fill, int* __restrict__ ent) {
     const long f = (long)blockIdx.x * MC_BLOCK + threadIdx.x;
     int a, b, c;
-    if (f >= m || !mc_face(faces, f, n, &a, &b, &c)) return;
+    if (f >= m || !geom_face<false>(faces, f, n, &a, &b, &c)) return;
     int x[3], y[3];
-    const int ne = mc_face_edges(a, b, c, x, y);
+    const int ne = geom_face_edges(a, b, c, x, y);
 #pragma unroll
     for (int e = 0; e < 3; ++e)
         if (e < ne) {
@@ -178,7 +149,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_rows_slow_kernel(const int* __res
                 if (first) fx |= !(k + 1 < L && out[k + 1] == x && (k + 2 >= L || out[k + 2] != x));
             }
             int total;
-            const int ex = mesh_block_exclusive<int>(first ? 1 : 0, lds, &total);
+            const int ex = block_exclusive<int>(first ? 1 : 0, lds, &total);
             if (first) row[carry + ex] = x;   // row is only read before the barrier above
             carry += total;
         }
@@ -209,61 +180,18 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_csr_kernel(const int* __restrict_
 // ---------------------------------------------------------------------------------------------------------------------------
 // components
 // ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MC_BLOCK) void mc_iota_kernel(int* __restrict__ parent, long long n) {
-    const long v = (long)blockIdx.x * MC_BLOCK + threadIdx.x;
-    if (v < n) parent[v] = (int)v;
-}
-
-// Plain loads may return a parent that another workgroup has already lowered, or not yet: either is a vertex of the same
-// component no larger than the vertex.  A launch that sets no flag has made no atomic, so its loads saw the previous launch's
-// values, and they agree on every face.
 __global__ __launch_bounds__(MC_BLOCK) void mc_hook_kernel(const int* __restrict__ faces, long m, long long n, int* parent, int* changed) {
     const long f = (long)blockIdx.x * MC_BLOCK + threadIdx.x;
     int a, b, c;
-    if (f >= m || !mc_face(faces, f, n, &a, &b, &c)) return;
-    const int pa = parent[a], pb = parent[b], pc = parent[c];
-    bool ch = false;
-    if (pa != pb) {
-        atomicMin(parent + max(pa, pb), min(pa, pb));
-        ch = true;
-    }
-    if (pa != pc) {
-        atomicMin(parent + max(pa, pc), min(pa, pc));
-        ch = true;
-    }
-    if (ch) *changed = 1;
-}
-
-__global__ __launch_bounds__(MC_BLOCK) void mc_jump_kernel(int* parent, long long n) {
-    const long v = (long)blockIdx.x * MC_BLOCK + threadIdx.x;
-    if (v >= n) return;
-    const int p0 = parent[v];
-    int p = p0;
-    for (int q = parent[p]; q != p; q = parent[p]) p = q;
-    if (p != p0) parent[v] = p;
+    if (f >= m || !geom_face<false>(faces, f, n, &a, &b, &c)) return;
+    const int pa = parent[a], pb = parent[b], pc = parent[c];   // one snapshot for both hooks
+    geom_hook(parent, pa, pb, changed);
+    geom_hook(parent, pa, pc, changed);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // component stats
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned mc_wave_min(unsigned x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = min(x, (unsigned)__shfl_xor((int)x, o, 64));
-    return x;
-}
-
-__device__ __forceinline__ unsigned mc_wave_max(unsigned x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = max(x, (unsigned)__shfl_xor((int)x, o, 64));
-    return x;
-}
-
-__device__ __forceinline__ int mc_wave_sum(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 // Each wave takes MC_CHUNK consecutive faces.  The faces whose label is lane 0's are counted together and folded into a
 // running count while that label repeats; one atomicAdd per run, one per face of any other label.  The referenced flags are
 // idempotent stores.
@@ -276,12 +204,12 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_face_stats_kernel(const int* __re
         const long f = base + step * 64 + lane;
         if (base + step * 64 >= m) break;   // wave-uniform
         int a, b, c;
-        const bool ok = f < m && mc_face(faces, f, n, &a, &b, &c);
+        const bool ok = f < m && geom_face<false>(faces, f, n, &a, &b, &c);
         const int r = ok ? label[a] : -1;
         if (ok) referenced[a] = referenced[b] = referenced[c] = 1;
         const int lead = __shfl(r, 0, 64);
         const bool same = ok && r == lead;
-        const int k = mc_wave_sum(same ? 1 : 0);
+        const int k = wave_sum(same ? 1 : 0);
         if (lead != cur) {
             if (lane == 0 && cur >= 0) atomicAdd(face_count + cur, run);
             cur = lead;
@@ -323,8 +251,8 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_vertex_stats_kernel(const float* 
         unsigned wlo[3], whi[3];
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            wlo[d] = mc_wave_min(same ? k[d] : UINT_MAX);
-            whi[d] = mc_wave_max(same ? k[d] : 0u);
+            wlo[d] = wave_min(same ? k[d] : UINT_MAX);
+            whi[d] = wave_max(same ? k[d] : 0u);
         }
         if (lead != cur) {
             if (lane == 0 && cur >= 0)
@@ -351,8 +279,8 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_vertex_stats_kernel(const float* 
     }
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        glo[d] = mc_wave_min(glo[d]);
-        ghi[d] = mc_wave_max(ghi[d]);
+        glo[d] = wave_min(glo[d]);
+        ghi[d] = wave_max(ghi[d]);
     }
     if (lane == 0) {
 #pragma unroll
@@ -422,27 +350,13 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_keep_kernel(const int* __restrict
     const long f = (long)blockIdx.x * MC_BLOCK + threadIdx.x;
     if (f >= m) return;
     int a, b, c;
-    bool k = mc_face(faces, f, n, &a, &b, &c);
+    bool k = geom_face<false>(faces, f, n, &a, &b, &c);
     if (k) {
         const int r = label[a];
         if (min_faces > 0 && (long long)face_count[r] < min_faces) k = false;
         if (spurious > 0.0 && diag[r] < *global_diag / spurious) k = false;
     }
     keep[f] = k ? 1 : 0;
-}
-
-__global__ __launch_bounds__(MC_BLOCK) void mc_keep_scatter_kernel(const int* __restrict__ faces, long m, const int* __restrict__ keep,
-                                                                   const int* __restrict__ pos, int* __restrict__ out_faces,
-                                                                   int* __restrict__ referenced) {
-    const long f = (long)blockIdx.x * MC_BLOCK + threadIdx.x;
-    if (f >= m || !keep[f]) return;
-    const long o = pos[f];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const int x = faces[3 * f + e];
-        out_faces[3 * o + e] = x;
-        referenced[x] = 1;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -479,19 +393,19 @@ struct McAdjScratch {
 };
 
 static McAdjScratch mc_adj_layout(long long n, long long m) {
-    McAdjScratch s;
     const size_t nv = (size_t)(n > 0 ? n : 1), ne = (size_t)(6 * m > 0 ? 6 * m : 1);
-    size_t o = 0;
-    s.cnt = o, o += mc_align(nv * 4);
-    s.start = o, o += mc_align(nv * 4);
-    s.ucnt = o, o += mc_align(nv * 4);
-    s.uoff = o, o += mc_align(nv * 4);
-    s.ent = o, o += mc_align(ne * 4);
-    s.list = o, o += mc_align(nv * 4);
-    s.n_long = o, o += mc_align(8);
-    s.total = o, o += mc_align(8);
-    s.scan = o, o += mc_align(d3d_mesh_scan_scratch_bytes(n));
-    s.bytes = o;
+    ScratchLayout L;
+    McAdjScratch s;
+    s.cnt = L.take(nv * 4);
+    s.start = L.take(nv * 4);
+    s.ucnt = L.take(nv * 4);
+    s.uoff = L.take(nv * 4);
+    s.ent = L.take(ne * 4);
+    s.list = L.take(nv * 4);
+    s.n_long = L.take(8);
+    s.total = L.take(8);
+    s.scan = L.take(geom_scan_bytes(n));
+    s.bytes = L.bytes;
     return s;
 }
 
@@ -500,28 +414,13 @@ struct McStatsScratch {
 };
 
 static McStatsScratch mc_stats_layout(long long n) {
-    McStatsScratch s;
     const size_t nv = (size_t)(n > 0 ? n : 1);
-    size_t o = 0;
-    s.keys = o, o += mc_align(nv * 24);
-    s.global_keys = o, o += mc_align(24);
-    s.referenced = o, o += mc_align(nv * 4);
-    s.bytes = o;
-    return s;
-}
-
-struct McFilterScratch {
-    size_t keep, pos, scan, bytes;
-};
-
-static McFilterScratch mc_filter_layout(long long m) {
-    McFilterScratch s;
-    const size_t nf = (size_t)(m > 0 ? m : 1);
-    size_t o = 0;
-    s.keep = o, o += mc_align(nf * 4);
-    s.pos = o, o += mc_align(nf * 4);
-    s.scan = o, o += mc_align(d3d_mesh_scan_scratch_bytes(m));
-    s.bytes = o;
+    ScratchLayout L;
+    McStatsScratch s;
+    s.keys = L.take(nv * 24);
+    s.global_keys = L.take(24);
+    s.referenced = L.take(nv * 4);
+    s.bytes = L.bytes;
     return s;
 }
 
@@ -563,7 +462,7 @@ extern "C" int d3d_mesh_adjacency(const int* faces, long long n_faces, long long
         hipLaunchKernelGGL(mc_count_kernel, dim3(ceil_div(m, MC_BLOCK)), dim3(MC_BLOCK), 0, st, faces, (long)m, n, cnt);
         D3D_LAUNCH_CHECK("mc_count_kernel launch");
     }
-    rc = mesh_scan(cnt, start, n, w + L.scan, total, st);   // the total is at most 6 n_faces < 2^31
+    rc = geom_scan(cnt, start, n, w + L.scan, total, st);   // the total is at most 6 n_faces < 2^31
     if (rc != D3D_OK) return rc;
     rc = hip_status(hipMemsetAsync(ucnt, 0, (size_t)(n > 0 ? n : 1) * 4, st), "mesh adjacency: clear fill");
     if (rc != D3D_OK) return rc;
@@ -577,7 +476,7 @@ extern "C" int d3d_mesh_adjacency(const int* faces, long long n_faces, long long
         hipLaunchKernelGGL(mc_rows_slow_kernel, dim3(MC_SLOW_GRID), dim3(MC_BLOCK), 0, st, start, cnt, list, n_long, ent, nbr, ucnt, fixed);
         D3D_LAUNCH_CHECK("mc_rows_slow_kernel launch");
     }
-    rc = mesh_scan(ucnt, uoff, n, w + L.scan, total, st);
+    rc = geom_scan(ucnt, uoff, n, w + L.scan, total, st);
     if (rc != D3D_OK) return rc;
     hipLaunchKernelGGL(mc_csr_kernel, dim3(ceil_div(n + 1, MC_BLOCK)), dim3(MC_BLOCK), 0, st, start, ucnt, uoff, total, n, ent, offset, nbr);
     D3D_LAUNCH_CHECK("mc_csr_kernel launch");
@@ -590,13 +489,11 @@ extern "C" int d3d_mesh_components(const int* faces, long long n_faces, long lon
     MC_CHECK_SIZES();
     hipStream_t st = (hipStream_t)stream;
     const long long n = n_vertices, m = n_faces;
-    if (n > 0) {
-        hipLaunchKernelGGL(mc_iota_kernel, dim3(ceil_div(n, MC_BLOCK)), dim3(MC_BLOCK), 0, st, label, n);
-        D3D_LAUNCH_CHECK("mc_iota_kernel launch");
-    }
+    int rc = geom_iota(label, n, st);
+    if (rc != D3D_OK) return rc;
     int r = 0;
     while (m > 0 && n > 0) {
-        int rc = hip_status(hipMemsetAsync(flag, 0, 4, st), "mesh components: clear flag");
+        rc = hip_status(hipMemsetAsync(flag, 0, 4, st), "mesh components: clear flag");
         if (rc != D3D_OK) return rc;
         hipLaunchKernelGGL(mc_hook_kernel, dim3(ceil_div(m, MC_BLOCK)), dim3(MC_BLOCK), 0, st, faces, (long)m, n, label, flag);
         D3D_LAUNCH_CHECK("mc_hook_kernel launch");
@@ -607,8 +504,8 @@ extern "C" int d3d_mesh_components(const int* faces, long long n_faces, long lon
         rc = hip_status(hipStreamSynchronize(st), "mesh components: sync");
         if (rc != D3D_OK) return rc;
         if (!h) break;
-        hipLaunchKernelGGL(mc_jump_kernel, dim3(ceil_div(n, MC_BLOCK)), dim3(MC_BLOCK), 0, st, label, n);
-        D3D_LAUNCH_CHECK("mc_jump_kernel launch");
+        rc = geom_jump(label, n, st);
+        if (rc != D3D_OK) return rc;
     }
     if (rounds) *rounds = r;
     return D3D_OK;
@@ -653,7 +550,7 @@ extern "C" int d3d_mesh_component_stats(const float* vertices, long long n_verti
 
 extern "C" size_t d3d_mesh_filter_scratch_bytes(long long n_faces) {
     if (!mc_sizes_ok(0, n_faces)) return 0;
-    return mc_filter_layout(n_faces).bytes;
+    return geom_keep_layout(n_faces).bytes;
 }
 
 extern "C" int d3d_mesh_filter(const int* faces, long long n_faces, long long n_vertices, const int* label, const int* face_count,
@@ -664,27 +561,20 @@ extern "C" int d3d_mesh_filter(const int* faces, long long n_faces, long long n_
     MC_CHECK_SIZES();
     D3D_REQUIRE(min_faces >= 0, "min_faces=%lld must be >= 0", min_faces);
     D3D_REQUIRE(std::isfinite(spurious) && spurious >= 0.0, "spurious=%g must be finite and >= 0", spurious);
-    const McFilterScratch L = mc_filter_layout(n_faces);
+    const KeepScratch L = geom_keep_layout(n_faces);
     MC_CHECK_SCRATCH(L.bytes);
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)scratch;
-    int *keep = (int*)(w + L.keep), *pos = (int*)(w + L.pos);
+    int* keep = (int*)(w + L.keep);
     const long long n = n_vertices, m = n_faces;
-    int rc = hip_status(hipMemsetAsync(referenced, 0, (size_t)(n > 0 ? n : 1) * 4, st), "mesh filter: clear flags");
+    const int rc = hip_status(hipMemsetAsync(referenced, 0, (size_t)(n > 0 ? n : 1) * 4, st), "mesh filter: clear flags");
     if (rc != D3D_OK) return rc;
     if (m > 0) {
         hipLaunchKernelGGL(mc_keep_kernel, dim3(ceil_div(m, MC_BLOCK)), dim3(MC_BLOCK), 0, st, faces, (long)m, n, label, face_count, diag,
                            global_diag, min_faces, spurious, keep);
         D3D_LAUNCH_CHECK("mc_keep_kernel launch");
     }
-    rc = mesh_scan(keep, pos, m, w + L.scan, n_kept, st);
-    if (rc != D3D_OK) return rc;
-    if (m > 0) {
-        hipLaunchKernelGGL(mc_keep_scatter_kernel, dim3(ceil_div(m, MC_BLOCK)), dim3(MC_BLOCK), 0, st, faces, (long)m, keep, pos, out_faces,
-                           referenced);
-        D3D_LAUNCH_CHECK("mc_keep_scatter_kernel launch");
-    }
-    return D3D_OK;
+    return geom_scatter_kept(faces, m, nullptr, scratch, L, out_faces, referenced, n_kept, st);
 }
 
 extern "C" int d3d_mesh_smooth(const float* vertices, long long n_vertices, const long long* offset, const int* nbr, const unsigned char* fixed,

@@ -21,7 +21,7 @@
 #include <cstdint>
 
 #include "common.h"
-#include "mesh_shared.h"
+#include "geom_shared.h"
 
 namespace d3d {
 
@@ -29,16 +29,8 @@ constexpr int DQ_BLOCK = 256;
 constexpr int DQ_SELECT_GRID = 1024;   // workgroups of a histogram pass (grid-stride)
 constexpr unsigned DQ_HASH = 2654435761u;
 
-static size_t dq_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// A face the passes use: three distinct indices in range (mesh.py refuses any other; here it is ignored, and dropped by faces).
-__device__ __forceinline__ bool dq_face(const int* __restrict__ faces, long f, long long n, int* a, int* b, int* c) {
-    *a = faces[3 * f];
-    *b = faces[3 * f + 1];
-    *c = faces[3 * f + 2];
-    return *a >= 0 && *a < n && *b >= 0 && *b < n && *c >= 0 && *c < n && *a != *b && *b != *c && *c != *a;
-}
-
+// The passes use a face of three distinct indices in range: geom_face<true> (mesh.py refuses any other; here it is ignored,
+// and dropped by faces).
 __device__ __forceinline__ void dq_load(const float* __restrict__ v, long i, double* p) {
     p[0] = (double)v[3 * i];
     p[1] = (double)v[3 * i + 1];
@@ -74,7 +66,7 @@ __device__ __forceinline__ double dq_cost(const double* q, double x, double y, d
 __global__ __launch_bounds__(DQ_BLOCK) void dq_fcount_kernel(const int* __restrict__ faces, long m, long long n, int* __restrict__ cnt) {
     const long f = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
     int a, b, c;
-    if (f >= m || !dq_face(faces, f, n, &a, &b, &c)) return;
+    if (f >= m || !geom_face<true>(faces, f, n, &a, &b, &c)) return;
     atomicAdd(cnt + a, 1);
     atomicAdd(cnt + b, 1);
     atomicAdd(cnt + c, 1);
@@ -84,7 +76,7 @@ __global__ __launch_bounds__(DQ_BLOCK) void dq_fscatter_kernel(const int* __rest
                                                                int* __restrict__ fill, int* __restrict__ ent) {
     const long f = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
     int a, b, c;
-    if (f >= m || !dq_face(faces, f, n, &a, &b, &c)) return;
+    if (f >= m || !geom_face<true>(faces, f, n, &a, &b, &c)) return;
     ent[(long)start[a] + atomicAdd(fill + a, 1)] = (int)f;
     ent[(long)start[b] + atomicAdd(fill + b, 1)] = (int)f;
     ent[(long)start[c] + atomicAdd(fill + c, 1)] = (int)f;
@@ -98,7 +90,7 @@ __global__ __launch_bounds__(DQ_BLOCK) void dq_frank_kernel(const int* __restric
     if (k >= 3 * m) return;
     const long f = k / 3;
     int a, b, c;
-    if (!dq_face(faces, f, n, &a, &b, &c)) return;
+    if (!geom_face<true>(faces, f, n, &a, &b, &c)) return;
     const int v = k - 3 * f == 0 ? a : (k - 3 * f == 1 ? b : c);
     const long s = start[v];
     const int L = cnt[v];
@@ -302,7 +294,7 @@ __global__ __launch_bounds__(DQ_BLOCK) void dq_pick_kernel(unsigned* __restrict_
     __shared__ long long lds[DQ_BLOCK / 64];
     const long long h = hist[threadIdx.x];
     long long total;
-    const long long before = mesh_block_exclusive<long long>(h, lds, &total);
+    const long long before = block_exclusive<long long>(h, lds, &total);
     hist[threadIdx.x] = 0u;
     long long rank = state[1];
     if (shift == 56 && rank > total) rank = total;
@@ -385,11 +377,6 @@ __global__ __launch_bounds__(DQ_BLOCK) void dq_apply_kernel(const long long* __r
     win[e] = w ? 1 : 0;
 }
 
-__global__ __launch_bounds__(DQ_BLOCK) void dq_iota_kernel(int* __restrict__ remap, long long n) {
-    const long v = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
-    if (v < n) remap[v] = (int)v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // faces
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -398,26 +385,12 @@ __global__ __launch_bounds__(DQ_BLOCK) void dq_fkeep_kernel(const int* __restric
     const long f = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
     if (f >= m) return;
     int a, b, c;
-    bool k = dq_face(faces, f, n, &a, &b, &c);
+    bool k = geom_face<true>(faces, f, n, &a, &b, &c);
     if (k) {
         a = remap[a], b = remap[b], c = remap[c];
         k = a != b && b != c && c != a;
     }
     keep[f] = k ? 1 : 0;
-}
-
-__global__ __launch_bounds__(DQ_BLOCK) void dq_fscatter_kept_kernel(const int* __restrict__ faces, long m, const int* __restrict__ remap,
-                                                                    const int* __restrict__ keep, const int* __restrict__ pos,
-                                                                    int* __restrict__ out_faces, int* __restrict__ referenced) {
-    const long f = (long)blockIdx.x * DQ_BLOCK + threadIdx.x;
-    if (f >= m || !keep[f]) return;
-    const long o = pos[f];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const int x = remap[faces[3 * f + e]];
-        out_faces[3 * o + e] = x;
-        referenced[x] = 1;
-    }
 }
 
 // scratch layouts
@@ -426,16 +399,16 @@ struct DqIncScratch {
 };
 
 static DqIncScratch dq_inc_layout(long long n, long long m) {
-    DqIncScratch s;
     const size_t nv = (size_t)(n > 0 ? n : 1), ne = (size_t)(3 * m > 0 ? 3 * m : 1);
-    size_t o = 0;
-    s.cnt = o, o += dq_align(nv * 4);
-    s.start = o, o += dq_align(nv * 4);
-    s.fill = o, o += dq_align(nv * 4);
-    s.ent = o, o += dq_align(ne * 4);
-    s.total = o, o += dq_align(8);
-    s.scan = o, o += dq_align(d3d_mesh_scan_scratch_bytes(n));
-    s.bytes = o;
+    ScratchLayout L;
+    DqIncScratch s;
+    s.cnt = L.take(nv * 4);
+    s.start = L.take(nv * 4);
+    s.fill = L.take(nv * 4);
+    s.ent = L.take(ne * 4);
+    s.total = L.take(8);
+    s.scan = L.take(geom_scan_bytes(n));
+    s.bytes = L.bytes;
     return s;
 }
 
@@ -444,13 +417,13 @@ struct DqEdgeScratch {
 };
 
 static DqEdgeScratch dq_edge_layout(long long n) {
-    DqEdgeScratch s;
     const size_t nv = (size_t)(n > 0 ? n : 1);
-    size_t o = 0;
-    s.ucnt = o, o += dq_align(nv * 4);
-    s.ebase = o, o += dq_align(nv * 4);
-    s.scan = o, o += dq_align(d3d_mesh_scan_scratch_bytes(n));
-    s.bytes = o;
+    ScratchLayout L;
+    DqEdgeScratch s;
+    s.ucnt = L.take(nv * 4);
+    s.ebase = L.take(nv * 4);
+    s.scan = L.take(geom_scan_bytes(n));
+    s.bytes = L.bytes;
     return s;
 }
 
@@ -459,26 +432,11 @@ struct DqSelectScratch {
 };
 
 static DqSelectScratch dq_select_layout() {
+    ScratchLayout L;
     DqSelectScratch s;
-    size_t o = 0;
-    s.state = o, o += dq_align(16);
-    s.hist = o, o += dq_align(256 * 4);
-    s.bytes = o;
-    return s;
-}
-
-struct DqFaceScratch {
-    size_t keep, pos, scan, bytes;
-};
-
-static DqFaceScratch dq_face_layout(long long m) {
-    DqFaceScratch s;
-    const size_t nf = (size_t)(m > 0 ? m : 1);
-    size_t o = 0;
-    s.keep = o, o += dq_align(nf * 4);
-    s.pos = o, o += dq_align(nf * 4);
-    s.scan = o, o += dq_align(d3d_mesh_scan_scratch_bytes(m));
-    s.bytes = o;
+    s.state = L.take(16);
+    s.hist = L.take(256 * 4);
+    s.bytes = L.bytes;
     return s;
 }
 
@@ -522,7 +480,7 @@ extern "C" int d3d_mesh_decimate_incidence(const int* faces, long long n_faces, 
         hipLaunchKernelGGL(dq_fcount_kernel, dim3(ceil_div(m, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, faces, (long)m, n, cnt);
         D3D_LAUNCH_CHECK("dq_fcount_kernel launch");
     }
-    rc = mesh_scan(cnt, start, n, w + L.scan, total, st);   // the total is at most 3 n_faces < 2^31
+    rc = geom_scan(cnt, start, n, w + L.scan, total, st);   // the total is at most 3 n_faces < 2^31
     if (rc != D3D_OK) return rc;
     if (m > 0) {
         hipLaunchKernelGGL(dq_fscatter_kernel, dim3(ceil_div(m, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, faces, (long)m, n, start, fill, ent);
@@ -567,7 +525,7 @@ extern "C" int d3d_mesh_decimate_edges(const long long* offset, const int* nbr, 
         hipLaunchKernelGGL(dq_ucount_kernel, dim3(ceil_div(n, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, offset, nbr, n, ucnt);
         D3D_LAUNCH_CHECK("dq_ucount_kernel launch");
     }
-    const int rc = mesh_scan(ucnt, ebase, n, w + L.scan, n_edges, st);
+    const int rc = geom_scan(ucnt, ebase, n, w + L.scan, n_edges, st);
     if (rc != D3D_OK) return rc;
     if (n > 0) {
         hipLaunchKernelGGL(dq_edges_kernel, dim3(ceil_div(n, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, offset, nbr, n, ebase, max_edges, edges);
@@ -650,8 +608,8 @@ extern "C" int d3d_mesh_decimate_apply(const float* vertices, long long n_vertic
     if (n > 0) {
         const int rc = hip_status(hipMemcpyAsync(out_vertices, vertices, (size_t)n * 12, hipMemcpyDeviceToDevice, st), "mesh decimate apply: copy");
         if (rc != D3D_OK) return rc;
-        hipLaunchKernelGGL(dq_iota_kernel, dim3(ceil_div(n, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, remap, n);
-        D3D_LAUNCH_CHECK("dq_iota_kernel launch");
+        const int ri = geom_iota(remap, n, st);
+        if (ri != D3D_OK) return ri;
     }
     if (max_edges == 0) return D3D_OK;
     hipLaunchKernelGGL(dq_apply_kernel, dim3(ceil_div(max_edges, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, offset, nbr, fixed, edges, key, target, n_edges,
@@ -662,7 +620,7 @@ extern "C" int d3d_mesh_decimate_apply(const float* vertices, long long n_vertic
 
 extern "C" size_t d3d_mesh_decimate_faces_scratch_bytes(long long n_faces) {
     if (!dq_sizes_ok(0, n_faces)) return 0;
-    return dq_face_layout(n_faces).bytes;
+    return geom_keep_layout(n_faces).bytes;
 }
 
 extern "C" int d3d_mesh_decimate_faces(const int* faces, long long n_faces, long long n_vertices, const int* remap, void* scratch,
@@ -670,24 +628,17 @@ extern "C" int d3d_mesh_decimate_faces(const int* faces, long long n_faces, long
     D3D_REQUIRE((faces || n_faces == 0) && remap && scratch && out_faces && referenced && n_kept,
                 "null pointer (faces, remap, scratch, out_faces, referenced, n_kept)");
     DQ_CHECK_SIZES();
-    const DqFaceScratch L = dq_face_layout(n_faces);
+    const KeepScratch L = geom_keep_layout(n_faces);
     DQ_CHECK_SCRATCH(L.bytes);
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)scratch;
-    int *keep = (int*)(w + L.keep), *pos = (int*)(w + L.pos);
+    int* keep = (int*)(w + L.keep);
     const long long n = n_vertices, m = n_faces;
-    int rc = hip_status(hipMemsetAsync(referenced, 0, (size_t)(n > 0 ? n : 1) * 4, st), "mesh decimate faces: clear flags");
+    const int rc = hip_status(hipMemsetAsync(referenced, 0, (size_t)(n > 0 ? n : 1) * 4, st), "mesh decimate faces: clear flags");
     if (rc != D3D_OK) return rc;
     if (m > 0) {
         hipLaunchKernelGGL(dq_fkeep_kernel, dim3(ceil_div(m, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, faces, (long)m, n, remap, keep);
         D3D_LAUNCH_CHECK("dq_fkeep_kernel launch");
     }
-    rc = mesh_scan(keep, pos, m, w + L.scan, n_kept, st);
-    if (rc != D3D_OK) return rc;
-    if (m > 0) {
-        hipLaunchKernelGGL(dq_fscatter_kept_kernel, dim3(ceil_div(m, DQ_BLOCK)), dim3(DQ_BLOCK), 0, st, faces, (long)m, remap, keep, pos, out_faces,
-                           referenced);
-        D3D_LAUNCH_CHECK("dq_fscatter_kept_kernel launch");
-    }
-    return D3D_OK;
+    return geom_scatter_kept(faces, m, remap, scratch, L, out_faces, referenced, n_kept, st);
 }

@@ -18,7 +18,7 @@
 #include <cstdint>
 
 #include "common.h"
-#include "ortho_shared.h"
+#include "geom_shared.h"
 
 namespace d3d {
 
@@ -34,18 +34,6 @@ struct OrthoGrid {
 
 __device__ __forceinline__ double ortho_x(const OrthoGrid& g, int j) { return g.x_min + ((double)j + 0.5) * g.ux; }
 __device__ __forceinline__ double ortho_y(const OrthoGrid& g, int i) { return g.y_max - ((double)i + 0.5) * g.uy; }
-
-__device__ __forceinline__ float ortho_wave_min(float x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = fminf(x, __shfl_xor(x, o, 64));
-    return x;
-}
-
-__device__ __forceinline__ float ortho_wave_max(float x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-    return x;
-}
 
 // One wave per (tile, word): lane l decides view 64 word + l.  mask [n_tiles, n_words] uint64.
 __global__ __launch_bounds__(ORTHO_BLOCK) void ortho_cull_kernel(const float* __restrict__ height, OrthoGrid g, int tiles_x, int n_tiles,
@@ -72,8 +60,8 @@ __global__ __launch_bounds__(ORTHO_BLOCK) void ortho_cull_kernel(const float* __
             }
         }
     }
-    lo = ortho_wave_min(lo);
-    hi = ortho_wave_max(hi);
+    lo = wave_min(lo);
+    hi = wave_max(hi);
     const int vi = word * 64 + lane;
     bool cand = false;
     if (vi < n_views && lo <= hi) {
@@ -83,7 +71,7 @@ __global__ __launch_bounds__(ORTHO_BLOCK) void ortho_cull_kernel(const float* __
         bool keep = false;   // a corner behind the view (or a non-finite projection): no bound, the view stays
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const OrthoPq r = ortho_project(V, xs[k & 1], ys[(k >> 1) & 1], zs[k >> 2]);
+            const GeomPq r = geom_project(V, xs[k & 1], ys[(k >> 1) & 1], zs[k >> 2]);
             if (!(r.p2 > 0.0 && r.q2 > 0.0)) {
                 keep = true;
                 continue;

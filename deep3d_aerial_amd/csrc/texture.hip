@@ -6,8 +6,8 @@
 //            keeps the view; culling only skips work).  Then one workgroup per block: each lane owns a face, walks the set bits
 //            (wave-uniform), runs the candidate tests in fp64 and keeps its best key in registers; one min-merge into `key`.
 // charts:    (edge key, face) pairs sorted by (edge, winner) by the caller; hooking over adjacent pairs of equal edge and winner
-//            (atomicMin of the smaller parent into the larger one) and pointer jumping until a hooking launch changes nothing,
-//            as mesh_clean.hip's components.  The fixed point is the smallest face index; a scan numbers the roots.
+//            (geom_hook) and pointer jumping until a hooking launch changes nothing, as mesh_clean.hip's components.  The fixed
+//            point is the smallest face index; a scan numbers the roots.
 // rects:     one lane per face projects its corners in its winner's view; integer atomicMin / atomicMax into its chart's rect,
 //            folded over the wave when every lane of it has the same chart.
 // fill:      one wave per (chart, band of rows): coalesced 4-byte copies of the view's RGBA8 rows into the atlas.
@@ -19,8 +19,7 @@
 #include <cstdint>
 
 #include "common.h"
-#include "mesh_shared.h"
-#include "ortho_shared.h"
+#include "geom_shared.h"
 
 namespace d3d {
 
@@ -29,15 +28,13 @@ constexpr int TX_BAND = 8;      // atlas rows per fill work item
 constexpr long long TX_EMPTY = 0x7fffffffffffffffll;
 constexpr long long TX_EDGE_NONE = 0x7fffffffffffffffll;
 
-static size_t tx_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct TxFace {
     double a[3], b[3], c[3];
 };
 
 __device__ __forceinline__ bool tx_face(const float* __restrict__ vertices, const int* __restrict__ faces, long f, long long n, TxFace* F) {
-    const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-    if (!(ia >= 0 && ia < n && ib >= 0 && ib < n && ic >= 0 && ic < n)) return false;   // texture.py refuses them
+    int ia, ib, ic;
+    if (!geom_face<false>(faces, f, n, &ia, &ib, &ic)) return false;   // texture.py refuses them
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         F->a[k] = (double)vertices[3l * ia + k];
@@ -60,18 +57,6 @@ __device__ __forceinline__ int tx_find(const d3d_ortho_view_t* __restrict__ view
     return lo < n_views && views[lo].id == id ? lo : -1;
 }
 
-__device__ __forceinline__ float tx_wave_min(float x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = fminf(x, __shfl_xor(x, o, 64));
-    return x;
-}
-
-__device__ __forceinline__ float tx_wave_max(float x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-    return x;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // select
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -86,8 +71,8 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_cull_kernel(const float* __restri
     for (int k = 0; k < TX_BLOCK / 64; ++k) {
         const long f = block * TX_BLOCK + k * 64 + lane;
         if (f >= m) break;
-        const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-        if (!(ia >= 0 && ia < n && ib >= 0 && ib < n && ic >= 0 && ic < n)) continue;
+        int ia, ib, ic;
+        if (!geom_face<false>(faces, f, n, &ia, &ib, &ic)) continue;
         const int idx[3] = {ia, ib, ic};
 #pragma unroll
         for (int q = 0; q < 3; ++q)
@@ -100,8 +85,8 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_cull_kernel(const float* __restri
     }
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) {
-        lo[ax] = tx_wave_min(lo[ax]);
-        hi[ax] = tx_wave_max(hi[ax]);
+        lo[ax] = wave_min(lo[ax]);
+        hi[ax] = wave_max(hi[ax]);
     }
     const bool any = lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2];
     for (int w = 0; w < n_words; ++w) {
@@ -113,7 +98,7 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_cull_kernel(const float* __restri
             bool keep = false;   // a corner behind the view (or a non-finite projection): no bound, the view stays
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const OrthoPq r = ortho_project(V, (double)(k & 1 ? hi[0] : lo[0]), (double)(k & 2 ? hi[1] : lo[1]),
+                const GeomPq r = geom_project(V, (double)(k & 1 ? hi[0] : lo[0]), (double)(k & 2 ? hi[1] : lo[1]),
                                                 (double)(k & 4 ? hi[2] : lo[2]));
                 if (!(r.p2 > 0.0 && r.q2 > 0.0)) {
                     keep = true;
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_select_kernel(const float* __rest
             if (!ortho_uv(V, F.a[0], F.a[1], F.a[2], &ua, &va, &p2)) continue;
             if (!ortho_uv(V, F.b[0], F.b[1], F.b[2], &ub, &vb, &p2)) continue;
             if (!ortho_uv(V, F.c[0], F.c[1], F.c[2], &uc, &vc, &p2)) continue;
-            const OrthoPq r = ortho_project(V, g[0], g[1], g[2]);
+            const GeomPq r = geom_project(V, g[0], g[1], g[2]);
             const double ug = r.q0 / r.q2, vg = r.q1 / r.q2;
             const int px = min(max((int)floor(fmin(fmax(ug + 0.5, 0.0), (double)V.W)), 0), V.W - 1);
             const int py = min(max((int)floor(fmin(fmax(vg + 0.5, 0.0), (double)V.H)), 0), V.H - 1);
@@ -190,37 +175,23 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_select_kernel(const float* __rest
 // charts
 // ---------------------------------------------------------------------------------------------------------------------------
 // edge_key [3 m]: slot 3 f + k holds the k-th distinct edge of face f as min(i, j) * n + max(i, j) when f has a winner, else
-// TX_EDGE_NONE (the edges of mesh_clean.hip: (a,b) (b,c) (c,a) with unequal ends, each unordered pair once).
+// TX_EDGE_NONE (geom_face_edges: (a,b) (b,c) (c,a) with unequal ends, each unordered pair once).
 __global__ __launch_bounds__(TX_BLOCK) void tx_edges_kernel(const int* __restrict__ faces, long m, long long n, const long long* __restrict__ key,
                                                             long long* __restrict__ edge_key) {
     const long f = (long)blockIdx.x * TX_BLOCK + threadIdx.x;
     if (f >= m) return;
     long long e[3] = {TX_EDGE_NONE, TX_EDGE_NONE, TX_EDGE_NONE};
-    const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    if (key[f] != TX_EMPTY && a >= 0 && a < n && b >= 0 && b < n && c >= 0 && c < n) {
-        int x[3], y[3], ne = 0;
-        if (a == b && b == c) {
-            ne = 0;
-        } else if (a == b || c == a) {
-            x[0] = a, y[0] = a == b ? c : b, ne = 1;
-        } else if (b == c) {
-            x[0] = a, y[0] = b, ne = 1;
-        } else {
-            x[0] = a, y[0] = b, x[1] = b, y[1] = c, x[2] = c, y[2] = a, ne = 3;
-        }
+    int a, b, c;
+    if (geom_face<false>(faces, f, n, &a, &b, &c) && key[f] != TX_EMPTY) {
+        int x[3], y[3];
+        const int ne = geom_face_edges(a, b, c, x, y);
         for (int k = 0; k < ne; ++k) e[k] = (long long)min(x[k], y[k]) * n + max(x[k], y[k]);
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) edge_key[3 * f + k] = e[k];
 }
 
-__global__ __launch_bounds__(TX_BLOCK) void tx_iota_kernel(int* __restrict__ parent, long m) {
-    const long f = (long)blockIdx.x * TX_BLOCK + threadIdx.x;
-    if (f < m) parent[f] = (int)f;
-}
-
-// Pairs sorted by (edge, winner): pair i joins pair i - 1 when both have the same edge and the same winner.  Plain loads of a
-// parent may be stale; any value seen is a face of the same chart no larger than the face, as in mesh_clean.hip's hooking.
+// Pairs sorted by (edge, winner): pair i joins pair i - 1 when both have the same edge and the same winner.
 __global__ __launch_bounds__(TX_BLOCK) void tx_hook_kernel(const long long* __restrict__ edge_sorted, const int* __restrict__ face_sorted,
                                                            long n_pairs, const long long* __restrict__ key, int* parent, int* changed) {
     const long i = (long)blockIdx.x * TX_BLOCK + threadIdx.x + 1;
@@ -229,20 +200,7 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_hook_kernel(const long long* __re
     if (e == TX_EDGE_NONE || e != edge_sorted[i - 1]) return;
     const int fa = face_sorted[i], fb = face_sorted[i - 1];
     if ((unsigned)key[fa] != (unsigned)key[fb]) return;   // the winners' ids (both faces have one: their edges are listed)
-    const int pa = parent[fa], pb = parent[fb];
-    if (pa != pb) {
-        atomicMin(parent + max(pa, pb), min(pa, pb));
-        *changed = 1;
-    }
-}
-
-__global__ __launch_bounds__(TX_BLOCK) void tx_jump_kernel(int* parent, long m) {
-    const long f = (long)blockIdx.x * TX_BLOCK + threadIdx.x;
-    if (f >= m) return;
-    const int p0 = parent[f];
-    int p = p0;
-    for (int q = parent[p]; q != p; q = parent[p]) p = q;
-    if (p != p0) parent[f] = p;
+    geom_hook(parent, parent[fa], parent[fb], changed);
 }
 
 __global__ __launch_bounds__(TX_BLOCK) void tx_roots_kernel(const long long* __restrict__ key, const int* __restrict__ label, long m,
@@ -271,7 +229,7 @@ __device__ __forceinline__ bool tx_corner_uv(const d3d_ortho_view_t& V, const Tx
     const double* P[3] = {F.a, F.b, F.c};
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const OrthoPq r = ortho_project(V, P[k][0], P[k][1], P[k][2]);
+        const GeomPq r = geom_project(V, P[k][0], P[k][1], P[k][2]);
         if (!(r.p2 > 0.0 && r.q2 > 0.0)) return false;
         u[k] = r.q0 / r.q2;
         v[k] = r.q1 / r.q2;
@@ -310,13 +268,7 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_rects_kernel(const float* __restr
     const int lead = __builtin_ctzll(act);
     const int c0 = __shfl(c, lead, 64);
     if (__all(c < 0 || c == c0)) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            r0 = min(r0, __shfl_xor(r0, o, 64));
-            r1 = min(r1, __shfl_xor(r1, o, 64));
-            r2 = max(r2, __shfl_xor(r2, o, 64));
-            r3 = max(r3, __shfl_xor(r3, o, 64));
-        }
+        r0 = wave_min(r0), r1 = wave_min(r1), r2 = wave_max(r2), r3 = wave_max(r3);
         if (lane != lead) return;
     } else if (c < 0) {
         return;
@@ -405,13 +357,13 @@ struct TxScratch {
 };
 
 static TxScratch tx_chart_layout(long long m) {
-    TxScratch s;
     const size_t nf = (size_t)(m > 0 ? m : 1);
-    size_t o = 0;
-    s.root = o, o += tx_align(nf * 4);
-    s.number = o, o += tx_align(nf * 4);
-    s.scan = o, o += tx_align(d3d_mesh_scan_scratch_bytes(m));
-    s.bytes = o;
+    ScratchLayout L;
+    TxScratch s;
+    s.root = L.take(nf * 4);
+    s.number = L.take(nf * 4);
+    s.scan = L.take(geom_scan_bytes(m));
+    s.bytes = L.bytes;
     return s;
 }
 
@@ -484,12 +436,10 @@ extern "C" int d3d_texture_charts(const long long* edge_sorted, const int* face_
     hipStream_t st = (hipStream_t)stream;
     const long m = (long)n_faces;
     int r = 0;
-    if (m > 0) {
-        hipLaunchKernelGGL(tx_iota_kernel, dim3(ceil_div(m, TX_BLOCK)), dim3(TX_BLOCK), 0, st, label, m);
-        D3D_LAUNCH_CHECK("tx_iota_kernel launch");
-    }
+    int rc = geom_iota(label, m, st);
+    if (rc != D3D_OK) return rc;
     while (n_pairs > 1) {
-        int rc = hip_status(hipMemsetAsync(flag, 0, 4, st), "texture charts: clear flag");
+        rc = hip_status(hipMemsetAsync(flag, 0, 4, st), "texture charts: clear flag");
         if (rc != D3D_OK) return rc;
         hipLaunchKernelGGL(tx_hook_kernel, dim3(ceil_div(n_pairs - 1, TX_BLOCK)), dim3(TX_BLOCK), 0, st, edge_sorted, face_sorted,
                            (long)n_pairs, key, label, flag);
@@ -501,8 +451,8 @@ extern "C" int d3d_texture_charts(const long long* edge_sorted, const int* face_
         rc = hip_status(hipStreamSynchronize(st), "texture charts: sync");
         if (rc != D3D_OK) return rc;
         if (!h) break;
-        hipLaunchKernelGGL(tx_jump_kernel, dim3(ceil_div(m, TX_BLOCK)), dim3(TX_BLOCK), 0, st, label, m);
-        D3D_LAUNCH_CHECK("tx_jump_kernel launch");
+        rc = geom_jump(label, m, st);
+        if (rc != D3D_OK) return rc;
     }
     if (rounds) *rounds = r;
     char* w = (char*)scratch;
@@ -511,7 +461,7 @@ extern "C" int d3d_texture_charts(const long long* edge_sorted, const int* face_
         hipLaunchKernelGGL(tx_roots_kernel, dim3(ceil_div(m, TX_BLOCK)), dim3(TX_BLOCK), 0, st, key, label, m, root);
         D3D_LAUNCH_CHECK("tx_roots_kernel launch");
     }
-    int rc = mesh_scan(root, number, m, w + L.scan, n_charts, st);
+    rc = geom_scan(root, number, m, w + L.scan, n_charts, st);
     if (rc != D3D_OK) return rc;
     if (m > 0) {
         hipLaunchKernelGGL(tx_number_kernel, dim3(ceil_div(m, TX_BLOCK)), dim3(TX_BLOCK), 0, st, key, label, m, number, chart);

@@ -51,7 +51,6 @@ grid, origin, row order and files:
         [--interpolation none|MovingAverage] [--radius 2] [--iterations 1] [--nodata -9999]
 """
 import argparse
-import ctypes
 import math
 import os
 import struct
@@ -59,7 +58,8 @@ import struct
 import numpy as np
 import torch
 
-from . import _lib
+from . import _geom, _lib
+from ._geom import ptr as _ptr, stream as _stream
 
 SELECT = {"Max": 0, "Robust_Max": 1}
 INTERPOLATION = (None, "none", "MovingAverage")
@@ -124,16 +124,6 @@ class DsmGrid(object):
         return "DsmGrid(border=%s, unit=%s, size=(%d, %d))" % (self.border, self.unit, self.width, self.height)
 
 
-def _stream():
-    from . import ops
-
-    return ops._stream()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def fill_moving_average(height, radius=2, iterations=1):
     """MovingAverage hole fill of an [H,W] fp32 device raster (NaN = empty): `iterations` launches of
     d3d_dsm_fill_moving_average, ping-ponging two rasters.  Returns a new tensor; the input is not changed."""
@@ -175,10 +165,9 @@ def points_to_dsm(xyz, grid, select="Max", trim=0.1, min_points=1, interpolation
     mode = SELECT[select]
     height = torch.empty((H, W), dtype=torch.float32, device=xyz.device)
     count = torch.empty((H, W), dtype=torch.int32, device=xyz.device)
-    nbytes = int(lib.d3d_dsm_scratch_bytes(n, W, H, mode))
+    scratch, nbytes = _geom.scratch(lib.d3d_dsm_scratch_bytes, n, W, H, mode, device=xyz.device)
     if nbytes == 0 and n >= 1 << 31:
         raise ValueError("%d points: at most 2^31 - 1" % n)
-    scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=xyz.device)
     rc = lib.d3d_dsm_from_points(p if n else None, n, grid.x_min, grid.y_max, grid.unit[0], grid.unit[1], grid.z_min, grid.z_max,
                                  W, H, mode, float(trim), int(min_points), _ptr(scratch), nbytes, _ptr(height), _ptr(count), _stream())
     _lib.check(rc, "d3d_dsm_from_points")
@@ -229,8 +218,7 @@ def mesh_to_dsm(vertices, faces, grid, interpolation=None, radius=2, iterations=
     H, W = grid.shape
     lib = _lib.load()
     height = torch.empty((H, W), dtype=torch.float32, device=vertices.device)
-    nbytes = int(lib.d3d_dsm_mesh_scratch_bytes(nf, W, H))
-    scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=vertices.device)
+    scratch, nbytes = _geom.scratch(lib.d3d_dsm_mesh_scratch_bytes, nf, W, H, device=vertices.device)
     rc = lib.d3d_dsm_from_mesh(pv if nv else None, nv, _ptr(faces) if nf else None, nf, grid.x_min, grid.y_max, grid.unit[0],
                                grid.unit[1], grid.z_min, grid.z_max, W, H, _ptr(scratch), nbytes, _ptr(height), _stream())
     _lib.check(rc, "d3d_dsm_from_mesh")

@@ -23,8 +23,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
-from .ops import _chk, _stream
+from . import _geom, _lib
+from ._geom import ptr as _ptr, stream as _stream
+from .ops import _chk
 
 _CAM_DOUBLES = 94  # D3D_FUSION_CAM_DOUBLES
 
@@ -91,7 +92,7 @@ class ConsistencyChecker(object):
         xyz_world_src = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         angle = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         rc = _lib.load().d3d_consistency_check(
-            *args, cam, H, W, Hs, Ws, *self._thresholds(), ctypes.c_void_p(mask.data_ptr()),
+            *args, cam, H, W, Hs, Ws, *self._thresholds(), _ptr(mask),
             _chk(depth_reprojected, "depth_reprojected"), _chk(depth_src_out, "depth_src_out"),
             _chk(xyz_world_src, "xyz_world_src"), _chk(angle, "angle_confidence"), _stream())
         _lib.check(rc, "d3d_consistency_check")
@@ -127,7 +128,7 @@ class ViewFusion(object):
         rc = _lib.load().d3d_fusion_ref_init(
             _map(depth_ref, "depth_ref"), _map(normal_ref, "normal_ref", (H, W, 3)), cam, H, W,
             _chk(self.all_xyz_world, "all_xyz_world"), _chk(self.xyz_confidence, "xyz_confidence"),
-            ctypes.c_void_p(self.geo_mask_sum.data_ptr()), _chk(self.normal_world, "normal_world"), _stream())
+            _ptr(self.geo_mask_sum), _chk(self.normal_world, "normal_world"), _stream())
         _lib.check(rc, "d3d_fusion_ref_init")
         self.vis_infos = [torch.full((H, W), int(ref_idx), dtype=torch.int32, device=dev)]  # :473
 
@@ -146,9 +147,9 @@ class ViewFusion(object):
         rc = _lib.load().d3d_fusion_accumulate(
             _map(self.depth_ref, "depth_ref"), _map(self.normal_ref, "normal_ref"), _map(self.confidence, "confidence"),
             _map(depth_src, "depth_src"), _map(normal_src, "normal_src", (Hs, Ws, 3)), cam, H, W, Hs, Ws,
-            *self.checker._thresholds(), int(src_idx), ctypes.c_void_p(self.geo_mask_sum.data_ptr()),
+            *self.checker._thresholds(), int(src_idx), _ptr(self.geo_mask_sum),
             _chk(self.all_xyz_world, "all_xyz_world"), _chk(self.xyz_confidence, "xyz_confidence"),
-            ctypes.c_void_p(vis.data_ptr()), None if out is None else _chk(out, "depth_src_out"), _stream())
+            _ptr(vis), None if out is None else _chk(out, "depth_src_out"), _stream())
         _lib.check(rc, "d3d_fusion_accumulate")
         self.vis_infos.append(vis)
         return out
@@ -161,8 +162,8 @@ class ViewFusion(object):
         fm = torch.empty((H, W), dtype=torch.uint8, device=dev)
         rc = _lib.load().d3d_fusion_finalize(
             _chk(self.all_xyz_world, "all_xyz_world"), _chk(self.xyz_confidence, "xyz_confidence"),
-            ctypes.c_void_p(self.geo_mask_sum.data_ptr()), H, W, int(min_geo_consist_num), _chk(avg, "avg_xyz_world"),
-            ctypes.c_void_p(fm.data_ptr()), _stream())
+            _ptr(self.geo_mask_sum), H, W, int(min_geo_consist_num), _chk(avg, "avg_xyz_world"), _ptr(fm),
+            _stream())
         _lib.check(rc, "d3d_fusion_finalize")
         return avg, fm.bool()
 
@@ -191,13 +192,12 @@ def extract_points(avg_xyz_world, final_mask, vis_infos, ref_img, normal_world, 
     for v in vis_infos:
         if v.dtype != torch.int32 or tuple(v.shape) != (H, W) or not v.is_cuda or not v.is_contiguous():
             raise TypeError("vis_infos must be contiguous CUDA int32 [H,W] tensors")
-    scratch = torch.empty((int(lib.d3d_fusion_points_scratch_bytes(H, W)),), dtype=torch.uint8, device=dev)
+    scratch, _ = _geom.scratch(lib.d3d_fusion_points_scratch_bytes, H, W, device=dev)
     keep = torch.empty((H, W), dtype=torch.uint8, device=dev)
     counts = torch.zeros((2,), dtype=torch.int32, device=dev)
     sr = (ctypes.c_double * 4)(*[float(x) for x in list(scene_range)[:4]])
-    rc = lib.d3d_fusion_mark_points(_chk(avg_xyz_world, "avg_xyz_world"), ctypes.c_void_p(fm.data_ptr()), H, W, int(skip_line), sr,
-                                    ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(keep.data_ptr()),
-                                    ctypes.c_void_p(counts.data_ptr()), _stream())
+    rc = lib.d3d_fusion_mark_points(_chk(avg_xyz_world, "avg_xyz_world"), _ptr(fm), H, W, int(skip_line), sr,
+                                    _ptr(scratch), _ptr(keep), _ptr(counts), _stream())
     _lib.check(rc, "d3d_fusion_mark_points")
     n_valid, n = (int(x) for x in counts.tolist())   # the one host read: the caller sizes the outputs
     if n_valid < 10 or n_valid <= 1:                 # :541-543 ("no points left"), :555
@@ -210,13 +210,11 @@ def extract_points(avg_xyz_world, final_mask, vis_infos, ref_img, normal_world, 
     if n == 0:
         return out
     vp = (ctypes.c_void_p * n_vis)(*[v.data_ptr() for v in vis_infos])
-    opt = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-    rc = lib.d3d_fusion_gather_points(_chk(avg_xyz_world, "avg_xyz_world"), ctypes.c_void_p(keep.data_ptr()), vp, n_vis,
+    rc = lib.d3d_fusion_gather_points(_chk(avg_xyz_world, "avg_xyz_world"), _ptr(keep), vp, n_vis,
                                       None if ref_img is None else _map(ref_img, "ref_img", (H, W, 3)),
                                       None if normal_world is None else _map(normal_world, "normal_world", (H, W, 3)), H, W,
-                                      ctypes.c_void_p(scratch.data_ptr()), _chk(out["xyz"], "xyz"), opt(out["color"]),
-                                      opt(out["normal"]), ctypes.c_void_p(out["views"].data_ptr()),
-                                      ctypes.c_void_p(out["nviews"].data_ptr()), _stream())
+                                      _ptr(scratch), _chk(out["xyz"], "xyz"), _ptr(out["color"]), _ptr(out["normal"]),
+                                      _ptr(out["views"]), _ptr(out["nviews"]), _stream())
     _lib.check(rc, "d3d_fusion_gather_points")
     return out
 

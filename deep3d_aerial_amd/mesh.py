@@ -115,7 +115,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _geom, _lib
+from ._geom import batches as _batches, ptr as _ptr, stream as _stream
 
 DEFAULT_CONF = 0.2
 DEFAULT_MIN_VIEWS = 2
@@ -180,19 +181,16 @@ class MeshGrid(object):
         return "MeshGrid(border=%s, voxel=%r, size=%s)" % (self.border, self.voxel, self.n)
 
 
-class MeshView(object):
+class MeshView(_geom.Camera):
     """One view: K [3,3], E = Tcw [4,4] (host arrays, used in fp64), depth and confidence [H,W] fp32 on the GPU."""
 
     def __init__(self, K, E, depth, confidence):
         from .ops import _chk
 
-        K = np.asarray(K, np.float64)
-        E = np.asarray(E, np.float64)
-        if K.shape != (3, 3) or E.shape != (4, 4):
-            raise ValueError("K must be [3,3] and E [4,4] (got %s, %s)" % (K.shape, E.shape))
+        _geom.Camera.__init__(self, K, E)
+        K = self.K
         if not (K[1, 0] == 0 and K[2, 0] == 0 and K[2, 1] == 0 and K[2, 2] == 1 and K[0, 0] != 0 and K[1, 1] != 0):
             raise ValueError("K must be [[fx, s, cx], [0, fy, cy], [0, 0, 1]] with fx, fy != 0 (got %s)" % K.tolist())
-        self.K, self.R, self.t = K.copy(), E[:3, :3].copy(), E[:3, 3].copy()
         _chk(depth, "depth", 2)
         _chk(confidence, "confidence", 2)
         if tuple(depth.shape) != tuple(confidence.shape) or depth.device != confidence.device:
@@ -201,28 +199,13 @@ class MeshView(object):
         self.H, self.W = (int(s) for s in depth.shape)
 
     def record(self):
-        r = _ViewRecord()
-        r.R[:] = list(self.R.ravel())
-        r.t[:] = list(self.t)
-        r.K[:] = list(self.K.ravel())
+        r = self.fill(_ViewRecord())
         r.depth, r.conf = self.depth.data_ptr(), self.confidence.data_ptr()
-        r.W, r.H = self.W, self.H
         return r
 
 
-def _stream():
-    from . import ops
-
-    return ops._stream()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def _records(views, device):
-    arr = (_ViewRecord * len(views))(*[v.record() for v in views])
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    return _geom.records((_ViewRecord * len(views))(*[v.record() for v in views]), device)
 
 
 def check_settings(grid, trunc=None, min_views=DEFAULT_MIN_VIEWS, conf_threshold=DEFAULT_CONF, views_per_batch=None):
@@ -235,14 +218,7 @@ def check_settings(grid, trunc=None, min_views=DEFAULT_MIN_VIEWS, conf_threshold
     conf = float(conf_threshold)
     if math.isnan(conf):
         raise ValueError("conf_threshold is NaN")
-    if views_per_batch is not None and int(views_per_batch) < 1:
-        raise ValueError("views_per_batch must be >= 1 (got %r)" % (views_per_batch,))
-    return trunc, int(min_views), conf, None if views_per_batch is None else int(views_per_batch)
-
-
-def _batches(views, views_per_batch):
-    n = views_per_batch or max(len(views), 1)
-    return [views[k:k + n] for k in range(0, len(views), n)]
+    return trunc, int(min_views), conf, _geom.check_views_per_batch(views_per_batch)
 
 
 def _check_views(views, device):
@@ -280,8 +256,7 @@ def tsdf_volume(views, grid, trunc=None, conf_threshold=DEFAULT_CONF, views_per_
             rc = lib.d3d_mesh_mark(ctypes.byref(g), ctypes.c_void_p(recs.data_ptr() + v0 * ctypes.sizeof(_ViewRecord)), len(part),
                                    max(v.W * v.H for v in part), conf, _ptr(marks), _stream())
             _lib.check(rc, "d3d_mesh_mark")
-    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(grid.n_bricks))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_scan_scratch_bytes, grid.n_bricks, device=device)
     index = torch.empty((bz, by, bx), dtype=torch.int32, device=device)
     blist = torch.empty((grid.n_bricks,), dtype=torch.int32, device=device)
     nb_dev = torch.empty((1,), dtype=torch.int64, device=device)
@@ -310,8 +285,7 @@ def extract(volume, grid, min_views=DEFAULT_MIN_VIEWS):
     if nb == 0:
         return torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev)
     nvox = nb * BRICK ** 3
-    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(nvox))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_scan_scratch_bytes, nvox, device=dev)
     edges = torch.empty((max(nvox, 1),), dtype=torch.uint8, device=dev)
     vbase = torch.empty((max(nvox, 1),), dtype=torch.int32, device=dev)
     fbase = torch.empty((max(nvox, 1),), dtype=torch.int32, device=dev)
@@ -326,8 +300,7 @@ def extract(volume, grid, min_views=DEFAULT_MIN_VIEWS):
     ref = torch.zeros((max(nv, 1),), dtype=torch.int32, device=dev)
     _lib.check(lib.d3d_mesh_emit(ctypes.byref(g), _ptr(blist), _ptr(index), nb, _ptr(s), _ptr(n), min_views, _ptr(edges), _ptr(vbase),
                                  _ptr(fbase), _ptr(verts), _ptr(faces), _ptr(ref), _stream()), "d3d_mesh_emit")
-    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(nv))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_scan_scratch_bytes, nv, device=dev)
     remap = torch.empty((max(nv, 1),), dtype=torch.int32, device=dev)
     out = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev)
     kept = torch.empty((1,), dtype=torch.int64, device=dev)
@@ -362,20 +335,7 @@ def check_clean_settings(min_faces=0, spurious=0.0, smooth=0, smooth_lambda=DEFA
 
 
 def _mesh_arrays(vertices, faces):
-    if not (isinstance(vertices, torch.Tensor) and isinstance(faces, torch.Tensor)):
-        raise TypeError("vertices and faces must be tensors")
-    if vertices.device.type != "cuda" or faces.device != vertices.device:
-        raise RuntimeError("the mesh is cleaned on the GPU (no CPU fallback); got %s and %s" % (vertices.device, faces.device))
-    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError("vertices must be [n,3] float32 (got %s %s)" % (tuple(vertices.shape), vertices.dtype))
-    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be [m,3] int32 (got %s %s)" % (tuple(faces.shape), faces.dtype))
-    n, m = int(vertices.shape[0]), int(faces.shape[0])
-    if n >= 1 << 31 or 6 * m >= 1 << 31:
-        raise ValueError("%d vertices, %d faces: at most 2^31 - 1 vertices and 6 m < 2^31" % (n, m))
-    if m and (int(faces.min()) < 0 or int(faces.max()) >= n):
-        raise ValueError("a face index lies outside 0 .. %d" % (n - 1))
-    return vertices.contiguous(), faces.contiguous(), n, m
+    return _geom.mesh_arrays(vertices, faces, 6, "cleaned")
 
 
 def adjacency(faces, n_vertices):
@@ -383,10 +343,9 @@ def adjacency(faces, n_vertices):
     lib = _lib.load()
     n, m = int(n_vertices), int(faces.shape[0])
     dev = faces.device
-    nbytes = int(lib.d3d_mesh_adjacency_scratch_bytes(n, m))
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_adjacency_scratch_bytes, n, m, device=dev)
     if nbytes == 0:
         raise ValueError("%d vertices, %d faces: out of range" % (n, m))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     offset = torch.empty((n + 1,), dtype=torch.int64, device=dev)
     nbr = torch.empty((max(6 * m, 1),), dtype=torch.int32, device=dev)
     fixed = torch.empty((max(n, 1),), dtype=torch.uint8, device=dev)
@@ -413,8 +372,7 @@ def component_stats(vertices, faces, labels):
     lib = _lib.load()
     n, m = int(vertices.shape[0]), int(faces.shape[0])
     dev = vertices.device
-    nbytes = int(lib.d3d_mesh_stats_scratch_bytes(n))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_stats_scratch_bytes, n, device=dev)
     out = {"face_count": torch.empty((max(n, 1),), dtype=torch.int32, device=dev),
            "box": torch.empty((max(n, 1), 6), dtype=torch.float32, device=dev),
            "diag": torch.empty((max(n, 1),), dtype=torch.float64, device=dev),
@@ -437,8 +395,7 @@ def remove_components(vertices, faces, min_faces=0, spurious=0.0, info=None):
     dev = vertices.device
     labels, rounds = components(faces, n)
     st = component_stats(vertices, faces, labels)
-    nbytes = int(lib.d3d_mesh_filter_scratch_bytes(m))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_filter_scratch_bytes, m, device=dev)
     out_faces = torch.empty((max(m, 1), 3), dtype=torch.int32, device=dev)
     referenced = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
     kept = torch.empty((1,), dtype=torch.int64, device=dev)
@@ -446,8 +403,7 @@ def remove_components(vertices, faces, min_faces=0, spurious=0.0, info=None):
                                    min_faces, spurious, _ptr(scratch), nbytes, _ptr(out_faces), _ptr(referenced), _ptr(kept), _stream()),
                "d3d_mesh_filter")
     mk = int(kept.item())   # the kept face count sizes the renumbering
-    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(n))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_scan_scratch_bytes, n, device=dev)
     remap = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
     out_v = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev)
     nk = torch.empty((1,), dtype=torch.int64, device=dev)
@@ -514,10 +470,9 @@ def face_incidence(faces, n_vertices):
     lib = _lib.load()
     n, m = int(n_vertices), int(faces.shape[0])
     dev = faces.device
-    nbytes = int(lib.d3d_mesh_decimate_incidence_scratch_bytes(n, m))
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_decimate_incidence_scratch_bytes, n, m, device=dev)
     if nbytes == 0:
         raise ValueError("%d vertices, %d faces: out of range" % (n, m))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     foff = torch.empty((n + 1,), dtype=torch.int32, device=dev)
     finc = torch.empty((max(3 * m, 1),), dtype=torch.int32, device=dev)
     _lib.check(lib.d3d_mesh_decimate_incidence(_ptr(faces), m, n, _ptr(scratch), nbytes, _ptr(foff), _ptr(finc), _stream()),
@@ -546,7 +501,6 @@ def decimate_round(vertices, faces, target_faces, detail=None):
     if m == 0 or n == 0 or k == 0:
         return vertices, faces, 0
     st = _stream()
-    u8 = lambda b: torch.empty((int(b),), dtype=torch.uint8, device=dev)
     offset, nbr, fixed = adjacency(faces, n)
     foff, finc = face_incidence(faces, n)
     quadric = vertex_quadrics(vertices, faces, (foff, finc))
@@ -554,8 +508,7 @@ def decimate_round(vertices, faces, target_faces, detail=None):
     counts = torch.zeros((4,), dtype=torch.int64, device=dev)   # edges, winners, kept faces, kept vertices
     p_count = lambda i: ctypes.c_void_p(counts.data_ptr() + 8 * i)
     edges = torch.empty((emax, 2), dtype=torch.int32, device=dev)
-    nbytes = int(lib.d3d_mesh_decimate_edges_scratch_bytes(n))
-    scratch = u8(nbytes)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_decimate_edges_scratch_bytes, n, device=dev)
     _lib.check(lib.d3d_mesh_decimate_edges(_ptr(offset), _ptr(nbr), n, _ptr(scratch), nbytes, emax, _ptr(edges), p_count(0), st),
                "d3d_mesh_decimate_edges")
     target = torch.empty((emax, 3), dtype=torch.float32, device=dev)
@@ -564,8 +517,7 @@ def decimate_round(vertices, faces, target_faces, detail=None):
     _lib.check(lib.d3d_mesh_decimate_candidates(_ptr(vertices), n, _ptr(faces), m, _ptr(offset), _ptr(nbr), _ptr(fixed), _ptr(foff), _ptr(finc),
                                                 _ptr(quadric), _ptr(edges), p_count(0), emax, _ptr(target), _ptr(cost), _ptr(key), st),
                "d3d_mesh_decimate_candidates")
-    nbytes = int(lib.d3d_mesh_decimate_select_scratch_bytes())
-    scratch = u8(nbytes)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_decimate_select_scratch_bytes, device=dev)
     threshold = torch.empty((1,), dtype=torch.int64, device=dev)
     _lib.check(lib.d3d_mesh_decimate_select(_ptr(key), emax, k, _ptr(scratch), nbytes, _ptr(threshold), st), "d3d_mesh_decimate_select")
     claim = torch.empty((n,), dtype=torch.int64, device=dev)
@@ -577,14 +529,12 @@ def decimate_round(vertices, faces, target_faces, detail=None):
     _lib.check(lib.d3d_mesh_decimate_apply(_ptr(vertices), n, _ptr(offset), _ptr(nbr), _ptr(fixed), _ptr(edges), _ptr(key), _ptr(target),
                                            p_count(0), emax, _ptr(threshold), _ptr(claim), _ptr(moved), _ptr(remap), _ptr(win), p_count(1), st),
                "d3d_mesh_decimate_apply")
-    nbytes = int(lib.d3d_mesh_decimate_faces_scratch_bytes(m))
-    scratch = u8(nbytes)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_decimate_faces_scratch_bytes, m, device=dev)
     out_faces = torch.zeros((m, 3), dtype=torch.int32, device=dev)   # rows past the kept ones stay 0: a valid index
     referenced = torch.empty((n,), dtype=torch.int32, device=dev)
     _lib.check(lib.d3d_mesh_decimate_faces(_ptr(faces), m, n, _ptr(remap), _ptr(scratch), nbytes, _ptr(out_faces), _ptr(referenced), p_count(2),
                                            st), "d3d_mesh_decimate_faces")
-    nbytes = int(lib.d3d_mesh_scan_scratch_bytes(n))
-    scratch = u8(nbytes)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_scan_scratch_bytes, n, device=dev)
     renum = torch.empty((n,), dtype=torch.int32, device=dev)
     out_v = torch.empty((n, 3), dtype=torch.float32, device=dev)
     # the kept count is still on the device, so all m rows are renumbered; the round's one read comes after
@@ -693,21 +643,10 @@ def load_mvs_views(mvs_folder, device="cuda"):
     """MeshView records of every {name}_init.pfm + {name}_prob.pfm + {name}.txt predict wrote under mvs_folder, in increasing
     order of the image id in the camera file (then name): predict's view order when the view pair file lists its reference
     views by increasing id, as it usually does."""
-    from . import predict
-
-    names = [f[:-len("_init.pfm")] for f in os.listdir(mvs_folder) if f.endswith("_init.pfm")]
-    if not names:
-        raise FileNotFoundError("no {name}_init.pfm under %s" % mvs_folder)
-    found = []
-    for name in names:
-        cam, location, _ = predict.read_red_cam(os.path.join(mvs_folder, name + ".txt"))
-        found.append((int(location[2]), name, cam))
     views = []
-    for _, name, cam in sorted(found, key=lambda r: (r[0], r[1])):
-        depth, _ = predict.load_pfm(os.path.join(mvs_folder, name + "_init.pfm"))
-        prob, _ = predict.load_pfm(os.path.join(mvs_folder, name + "_prob.pfm"))
-        views.append(MeshView(cam[1, :3, :3], cam[0], torch.from_numpy(np.ascontiguousarray(depth)).to(device),
-                              torch.from_numpy(np.ascontiguousarray(prob)).to(device)))
+    for name, cam, _, _ in sorted(_geom.mvs_cameras(mvs_folder), key=lambda r: (int(r[2][2]), r[0])):
+        views.append(MeshView(cam[1, :3, :3], cam[0], _geom.load_map(mvs_folder, name, "_init", device),
+                              _geom.load_map(mvs_folder, name, "_prob", device)))
     return views
 
 

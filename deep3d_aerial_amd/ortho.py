@@ -37,7 +37,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _geom, _lib
+from ._geom import batches as _batches, camera_center, check_views_per_batch, ptr as _ptr, stream as _stream
 from .dsm import TIFF_LIMIT, DsmGrid, _LONG, _SHORT, assemble_tiff, geo_tags
 
 EMPTY_KEY = (1 << 63) - 1
@@ -50,12 +51,6 @@ class _ViewRecord(ctypes.Structure):
     _fields_ = [("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3), ("K", ctypes.c_double * 9), ("C", ctypes.c_double * 3),
                 ("depth", ctypes.c_void_p), ("rgba", ctypes.c_void_p), ("W", ctypes.c_int), ("H", ctypes.c_int), ("id", ctypes.c_int),
                 ("pad", ctypes.c_int)]
-
-
-def camera_center(R, t):
-    """C = -R^T t in fp64, each component summed left to right (the C of the semantics above)."""
-    R, t = np.asarray(R, np.float64), np.asarray(t, np.float64)
-    return np.array([-(R[0, k] * t[0] + R[1, k] * t[1] + R[2, k] * t[2]) for k in range(3)], np.float64)
 
 
 def rgba_image(image):
@@ -76,7 +71,7 @@ def rgba_image(image):
     return torch.cat([rgb, alpha], 2).contiguous()
 
 
-class OrthoView(object):
+class OrthoView(_geom.IdCamera):
     """One view offered to the orthophoto: id, K [3,3], E = Tcw [4,4] (host arrays, used in fp64), depth [H,W] fp32 and image
     [H,W(,C)] uint8 on the GPU.  The RGBA8 copy the kernels read is made here."""
 
@@ -85,13 +80,7 @@ class OrthoView(object):
 
         if int(id) != id or not 0 <= int(id) <= MAX_ID:
             raise ValueError("view id %r must be an integer in 0..%d" % (id, MAX_ID))
-        self.id = int(id)
-        K = np.asarray(K, np.float64)
-        E = np.asarray(E, np.float64)
-        if K.shape != (3, 3) or E.shape != (4, 4):
-            raise ValueError("K must be [3,3] and E [4,4] (got %s, %s)" % (K.shape, E.shape))
-        self.K, self.R, self.t = K.copy(), E[:3, :3].copy(), E[:3, 3].copy()
-        self.C = camera_center(self.R, self.t)
+        _geom.IdCamera.__init__(self, id, K, E)
         _chk(depth, "depth", 2)
         self.depth = depth
         self.rgba = rgba_image(image)
@@ -103,31 +92,14 @@ class OrthoView(object):
         self.H, self.W = (int(s) for s in depth.shape)
 
     def record(self):
-        r = _ViewRecord()
-        r.R[:] = list(self.R.ravel())
-        r.t[:] = list(self.t)
-        r.K[:] = list(self.K.ravel())
-        r.C[:] = list(self.C)
+        r = self.fill(_ViewRecord())
         r.depth, r.rgba = self.depth.data_ptr(), self.rgba.data_ptr()
-        r.W, r.H, r.id = self.W, self.H, self.id
         return r
 
 
-def _stream():
-    from . import ops
-
-    return ops._stream()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def _records(views, device):
-    """The views' d3d_ortho_view_t records in device memory (one host-to-device copy, ordered on the current stream)."""
-    arr = (_ViewRecord * len(views))(*[v.record() for v in views])
-    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-    return host.to(device)
+    """The views' d3d_ortho_view_t records in device memory."""
+    return _geom.records((_ViewRecord * len(views))(*[v.record() for v in views]), device)
 
 
 def _check_views(views):
@@ -164,17 +136,6 @@ def check_tolerance(depth_tolerance):
     return tol
 
 
-def check_views_per_batch(views_per_batch):
-    if views_per_batch is not None and int(views_per_batch) < 1:
-        raise ValueError("views_per_batch must be >= 1 (got %r)" % (views_per_batch,))
-    return None if views_per_batch is None else int(views_per_batch)
-
-
-def _batches(views, views_per_batch):
-    n = views_per_batch or max(len(views), 1)
-    return [views[k:k + n] for k in range(0, len(views), n)]
-
-
 def select_views(height, grid, views, depth_tolerance=DEFAULT_TOLERANCE, key=None, views_per_batch=None):
     """Min-merges the keys of `views` (OrthoView) into key [H,W] int64 (a new INT64_MAX raster when None) and returns it.
     height: the DSM [H,W] fp32 on the GPU (NaN = empty); views_per_batch: views per d3d_ortho_select call (None: all in one).
@@ -190,8 +151,7 @@ def select_views(height, grid, views, depth_tolerance=DEFAULT_TOLERANCE, key=Non
     lib = _lib.load()
     for batch in _batches(views, vpb):
         recs = _records(batch, height.device)
-        nbytes = int(lib.d3d_ortho_scratch_bytes(W, H, len(batch)))
-        scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=height.device)
+        scratch, nbytes = _geom.scratch(lib.d3d_ortho_scratch_bytes, W, H, len(batch), device=height.device)
         rc = lib.d3d_ortho_select(_ptr(height), grid.x_min, grid.y_max, grid.unit[0], grid.unit[1], W, H, _ptr(recs), len(batch), tol,
                                   _ptr(scratch), nbytes, _ptr(key), _stream())
         _lib.check(rc, "d3d_ortho_select")
@@ -295,22 +255,16 @@ def load_mvs_views(mvs_folder, image_root=None, device="cuda"):
     """OrthoView records of every {name}_init.pfm + {name}.txt predict wrote under mvs_folder: the camera and the id from the
     camera file (predict.read_red_cam), the image it names (relative paths under image_root, else beside the camera file)
     centre-cropped to the depth map."""
-    from . import dataset, predict
+    from . import dataset
 
-    names = sorted(f[:-len("_init.pfm")] for f in os.listdir(mvs_folder) if f.endswith("_init.pfm"))
-    if not names:
-        raise FileNotFoundError("no {name}_init.pfm under %s" % mvs_folder)
     views = []
-    for name in names:
-        cam, location, path = predict.read_red_cam(os.path.join(mvs_folder, name + ".txt"))
-        depth, _ = predict.load_pfm(os.path.join(mvs_folder, name + "_init.pfm"))
+    for name, cam, location, path in _geom.mvs_cameras(mvs_folder):
+        depth = _geom.load_map(mvs_folder, name, "_init", device)
         if not os.path.isabs(path):
             path = os.path.join(image_root if image_root is not None else mvs_folder, path)
-        image = dataset.read_image_u8(path)
         H, W = depth.shape
-        crop = np.ascontiguousarray(center_crop(image, H, W, path))
-        views.append(OrthoView(int(location[2]), cam[1, :3, :3], cam[0], torch.from_numpy(np.ascontiguousarray(depth)).to(device),
-                               torch.from_numpy(crop).to(device)))
+        crop = np.ascontiguousarray(center_crop(dataset.read_image_u8(path), H, W, path))
+        views.append(OrthoView(int(location[2]), cam[1, :3, :3], cam[0], depth, torch.from_numpy(crop).to(device)))
     return views
 
 

@@ -47,7 +47,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _geom, _lib
+from ._geom import ptr as _ptr, stream as _stream
 from .ortho import (DEFAULT_TOLERANCE, EMPTY_KEY, OrthoView, _ViewRecord, _batches, _check_views, camera_center, check_tolerance,
                     check_views_per_batch)
 
@@ -58,31 +59,17 @@ BAND = 8   # atlas rows per fill work item (csrc/texture.hip TX_BAND)
 _NONE = EMPTY_KEY
 
 
-class Camera(object):
+class Camera(_geom.IdCamera):
     """A view's camera alone: id, K [3,3], E = Tcw [4,4] and the image size.  The rects and texcoords need no more, so rank 0
     computes them for views whose maps it does not hold.  OrthoView has the same attributes."""
 
     def __init__(self, id, K, E, W, H):
-        self.id = int(id)
-        K, E = np.asarray(K, np.float64), np.asarray(E, np.float64)
-        if K.shape != (3, 3) or E.shape != (4, 4):
-            raise ValueError("K must be [3,3] and E [4,4] (got %s, %s)" % (K.shape, E.shape))
-        self.K, self.R, self.t = K.copy(), E[:3, :3].copy(), E[:3, 3].copy()
-        self.C = camera_center(self.R, self.t)
+        _geom.IdCamera.__init__(self, id, K, E)
         self.W, self.H = int(W), int(H)
 
 
 def _record(v):
-    r = _ViewRecord()
-    r.R[:] = list(v.R.ravel())
-    r.t[:] = list(v.t)
-    r.K[:] = list(v.K.ravel())
-    r.C[:] = list(v.C)
-    held = isinstance(v, OrthoView)
-    r.depth = v.depth.data_ptr() if held else 0
-    r.rgba = v.rgba.data_ptr() if held else 0
-    r.W, r.H, r.id = v.W, v.H, v.id
-    return r
+    return v.record() if isinstance(v, OrthoView) else v.fill(_ViewRecord())   # a camera alone: no maps
 
 
 def _table(views, device):
@@ -92,34 +79,11 @@ def _table(views, device):
     if len(set(ids)) != len(ids):
         raise ValueError("view ids must be unique (got %s)" % ids)
     arr = (_ViewRecord * max(len(views), 1))(*[_record(v) for v in views])
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device), len(views)
-
-
-def _stream():
-    from . import ops
-
-    return ops._stream()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    return _geom.records(arr, device), len(views)
 
 
 def _mesh_arrays(vertices, faces):
-    if not (isinstance(vertices, torch.Tensor) and isinstance(faces, torch.Tensor)):
-        raise TypeError("vertices and faces must be tensors")
-    if vertices.device.type != "cuda" or faces.device != vertices.device:
-        raise RuntimeError("the mesh is textured on the GPU (no CPU fallback); got %s and %s" % (vertices.device, faces.device))
-    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError("vertices must be [n,3] float32 (got %s %s)" % (tuple(vertices.shape), vertices.dtype))
-    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("faces must be [m,3] int32 (got %s %s)" % (tuple(faces.shape), faces.dtype))
-    n, m = int(vertices.shape[0]), int(faces.shape[0])
-    if n >= 1 << 31 or 3 * m >= 1 << 31:
-        raise ValueError("%d vertices, %d faces: at most 2^31 - 1 vertices and 3 m < 2^31" % (n, m))
-    if m and (int(faces.min()) < 0 or int(faces.max()) >= n):
-        raise ValueError("a face index lies outside 0 .. %d" % (n - 1))
-    return vertices.contiguous(), faces.contiguous(), n, m
+    return _geom.mesh_arrays(vertices, faces, 3, "textured")
 
 
 def _check_key(key, m, device):
@@ -168,8 +132,7 @@ def select_faces(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, view
     lib = _lib.load()
     for batch in _batches(views, vpb):
         recs, nv = _table(batch, vertices.device)
-        nbytes = int(lib.d3d_texture_scratch_bytes(m, nv))
-        scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=vertices.device)
+        scratch, nbytes = _geom.scratch(lib.d3d_texture_scratch_bytes, m, nv, device=vertices.device)
         rc = lib.d3d_texture_select(_ptr(vertices), n, _ptr(faces), m, _ptr(recs), nv, tol, _ptr(scratch), nbytes, _ptr(key), _stream())
         _lib.check(rc, "d3d_texture_select")
     return key
@@ -202,8 +165,7 @@ def charts(faces, key, n_vertices=None):
     edge_sorted = pair_edge[perm].contiguous()
     face_sorted = pair_face[perm].to(torch.int32).contiguous()
     del edge, live, pair_face, pair_edge, o1, o2, perm
-    nbytes = int(lib.d3d_texture_scratch_bytes(m, 0))
-    scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    scratch, nbytes = _geom.scratch(lib.d3d_texture_scratch_bytes, m, 0, device=dev)
     label = torch.empty((max(m, 1),), dtype=torch.int32, device=dev)
     chart = torch.empty((m,), dtype=torch.int32, device=dev)
     flag = torch.zeros((1,), dtype=torch.int32, device=dev)
