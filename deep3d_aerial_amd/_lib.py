@@ -163,6 +163,13 @@ SIGNATURES = {
     "d3d_mesh_decimate_apply": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "d3d_mesh_decimate_faces_scratch_bytes": ([ctypes.c_longlong], _sz),
     "d3d_mesh_decimate_faces": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
+    "d3d_mesh_holes_scratch_bytes": ([ctypes.c_longlong], _sz),
+    "d3d_mesh_boundary": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "d3d_mesh_boundary_loops": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _vp],
+    "d3d_mesh_holes_plan": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _vp, _vp],
+    "d3d_mesh_holes_emit": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong,
+                            ctypes.c_longlong, _vp, _vp, _vp],
     "d3d_texture_scratch_bytes": ([ctypes.c_longlong, _i], _sz),
     "d3d_texture_select": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _d, _vp, _sz, _vp, _vp],
     "d3d_texture_edges": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],

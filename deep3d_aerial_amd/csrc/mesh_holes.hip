@@ -1,0 +1,382 @@
+// Closing the small holes of the surface mesh: every small boundary loop whose faces lie outside it gets a
+// fan around one new vertex.  The rule is this project's (deep3d_aerial_amd/mesh.py states it, include/deep3d_planesweep.h too).
+//
+// boundary: one lane per face corner walks the vertex -> face row of its directed edge's tail (d3d_mesh_decimate_incidence)
+//           and counts the faces that hold the head: exactly one makes it a boundary half-edge.  The lane counts it at its
+//           tail (out) and head (in) by integer atomicAdd and stores the head and the owning face at the tail: that store has
+//           one writer exactly when the tail's out-count is 1, and a second pass sets every other vertex's entry to -1, so no
+//           arrival order reaches the output.
+// loops:    parent[v] = v; hooking over the boundary half-edges only (one lane per corner, geom_hook of tail and head) and
+//           full pointer jumping in separate launches until a hooking launch changes nothing; the host reads one flag per
+//           round.  Half-edge counts per label by atomicAdd, `bad` (some vertex of the component is not simple) by atomicOr.
+// plan:     one lane per label vertex of a component that is not bad and has 3 .. max_edges half-edges walks its cycle once,
+//           in the rule's order, summing in fp64; it writes s, the centroid, the qualify flag and every tail's walk position.
+//           Two scans number the new vertices and faces in label order and give the totals.
+// emit:     the input comes through first (two copies); one lane per vertex writes the fan face of its outgoing half-edge at
+//           (label offset + walk position), and a label vertex writes the new vertex.
+// Integer atomics only (add / or / min whose return values never reach an output); every float result is a fixed-order fp64
+// computation without contraction, so nothing depends on the order lanes run in.
+#include <climits>
+#include <cmath>
+#include <cstdint>
+
+#include "common.h"
+#include "geom_shared.h"
+
+namespace d3d {
+
+constexpr int MH_BLOCK = 256;
+
+// The corner c = k - 3 f of lane k: tail and head of its directed edge; false for a face the passes ignore.
+__device__ __forceinline__ bool mh_corner(const int* __restrict__ faces, long k, long long n, long* f, int* a, int* b) {
+    *f = k / 3;
+    const int c = (int)(k - 3 * *f);
+    int v0, v1, v2;
+    if (!geom_face<true>(faces, *f, n, &v0, &v1, &v2)) return false;
+    *a = c == 0 ? v0 : (c == 1 ? v1 : v2);
+    *b = c == 0 ? v1 : (c == 1 ? v2 : v0);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// boundary
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MH_BLOCK) void mh_boundary_kernel(const int* __restrict__ faces, long m, long long n, const int* __restrict__ foff,
+                                                               const int* __restrict__ finc, int* __restrict__ out_count,
+                                                               int* __restrict__ in_count, int* __restrict__ successor, int* __restrict__ owner,
+                                                               unsigned char* __restrict__ boundary) {
+    const long k = (long)blockIdx.x * MH_BLOCK + threadIdx.x;
+    if (k >= 3 * m) return;
+    long f;
+    int a, b;
+    bool hit = false;
+    if (mh_corner(faces, k, n, &f, &a, &b)) {
+        const long j0 = max(foff[a], 0), j1 = min((long)foff[a + 1], 3 * m);
+        int holders = 0;
+        for (long j = j0; j < j1; ++j) {
+            const long g = finc[j];
+            if (g < 0 || g >= m) continue;   // not a row of this mesh: ignored
+            holders += (faces[3 * g] == b || faces[3 * g + 1] == b || faces[3 * g + 2] == b) ? 1 : 0;
+        }
+        hit = holders == 1;
+        if (hit) {
+            atomicAdd(out_count + a, 1);
+            atomicAdd(in_count + b, 1);
+            successor[a] = b;   // one writer when out_count[a] ends at 1; mh_unique_kernel drops every other entry
+            owner[a] = (int)f;
+        }
+    }
+    boundary[k] = hit ? 1 : 0;
+}
+
+__global__ __launch_bounds__(MH_BLOCK) void mh_unique_kernel(const int* __restrict__ out_count, long long n, int* __restrict__ successor,
+                                                             int* __restrict__ owner) {
+    const long v = (long)blockIdx.x * MH_BLOCK + threadIdx.x;
+    if (v >= n || out_count[v] == 1) return;
+    successor[v] = -1;
+    owner[v] = -1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// loops
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MH_BLOCK) void mh_hook_kernel(const int* __restrict__ faces, long m, long long n,
+                                                           const unsigned char* __restrict__ boundary, int* parent, int* changed) {
+    const long k = (long)blockIdx.x * MH_BLOCK + threadIdx.x;
+    if (k >= 3 * m || !boundary[k]) return;
+    long f;
+    int a, b;
+    if (!mh_corner(faces, k, n, &f, &a, &b)) return;
+    geom_hook(parent, parent[a], parent[b], changed);
+}
+
+__global__ __launch_bounds__(MH_BLOCK) void mh_count_kernel(const int* __restrict__ faces, long m, long long n,
+                                                            const unsigned char* __restrict__ boundary, const int* __restrict__ label,
+                                                            int* __restrict__ count) {
+    const long k = (long)blockIdx.x * MH_BLOCK + threadIdx.x;
+    if (k >= 3 * m || !boundary[k]) return;
+    long f;
+    int a, b;
+    if (!mh_corner(faces, k, n, &f, &a, &b)) return;
+    atomicAdd(count + label[a], 1);
+}
+
+__global__ __launch_bounds__(MH_BLOCK) void mh_bad_kernel(const int* __restrict__ out_count, const int* __restrict__ in_count, long long n,
+                                                          const int* __restrict__ label, int* __restrict__ bad) {
+    const long v = (long)blockIdx.x * MH_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    const int o = out_count[v], i = in_count[v];
+    if ((o != 0 || i != 0) && !(o == 1 && i == 1)) atomicOr(bad + label[v], 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// plan
+// ---------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void mh_load(const float* __restrict__ v, long i, double* p) {
+    p[0] = (double)v[3 * i];
+    p[1] = (double)v[3 * i + 1];
+    p[2] = (double)v[3 * i + 2];
+}
+
+// out += u x w
+__device__ __forceinline__ void mh_add_cross(const double* u, const double* w, double* out) {
+    out[0] += u[1] * w[2] - u[2] * w[1];
+    out[1] += u[2] * w[0] - u[0] * w[2];
+    out[2] += u[0] * w[1] - u[1] * w[0];
+}
+
+__global__ __launch_bounds__(MH_BLOCK) void mh_plan_kernel(const float* __restrict__ vertices, long long n, const int* __restrict__ faces, long m,
+                                                           const int* __restrict__ successor, const int* __restrict__ owner,
+                                                           const int* __restrict__ label, const int* __restrict__ count,
+                                                           const int* __restrict__ bad, int max_edges, double* __restrict__ s_out,
+                                                           float* __restrict__ centroid, int* __restrict__ qualify, int* __restrict__ new_faces,
+                                                           int* __restrict__ position) {
+    const long v = (long)blockIdx.x * MH_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    double s = 0.0;
+    float c[3] = {0.0f, 0.0f, 0.0f};
+    const int k = count[v];
+    bool walked = label[v] == (int)v && k >= 3 && k <= max_edges && !bad[v];
+    if (walked) {
+        double A[3] = {0.0, 0.0, 0.0}, N[3] = {0.0, 0.0, 0.0}, S[3] = {0.0, 0.0, 0.0};
+        int a = (int)v;
+        for (int i = 0; i < k; ++i) {
+            const int b = successor[a], f = owner[a];
+            int f0, f1, f2;
+            // a component that is not bad is one cycle of simple vertices; anything else is not this mesh's data
+            if (b < 0 || b >= n || f < 0 || f >= m || !geom_face<true>(faces, f, n, &f0, &f1, &f2)) {
+                walked = false;
+                break;
+            }
+            double xa[3], xb[3], p0[3], p1[3], p2[3];
+            mh_load(vertices, a, xa);
+            mh_load(vertices, b, xb);
+            mh_add_cross(xa, xb, A);
+            mh_load(vertices, f0, p0);
+            mh_load(vertices, f1, p1);
+            mh_load(vertices, f2, p2);
+            const double u[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]}, w[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+            mh_add_cross(u, w, N);
+            S[0] += xa[0];
+            S[1] += xa[1];
+            S[2] += xa[2];
+            position[a] = i;
+            a = b;
+        }
+        walked = walked && a == (int)v;
+        if (walked) {
+            s = (A[0] * N[0] + A[1] * N[1]) + A[2] * N[2];
+            const double d = (double)k;
+            c[0] = (float)(S[0] / d);
+            c[1] = (float)(S[1] / d);
+            c[2] = (float)(S[2] / d);
+        }
+    }
+    const bool q = walked && s < 0.0;
+    s_out[v] = s;
+    centroid[3 * v] = c[0];
+    centroid[3 * v + 1] = c[1];
+    centroid[3 * v + 2] = c[2];
+    qualify[v] = q ? 1 : 0;
+    new_faces[v] = q ? k : 0;
+}
+
+// totals[0] = the new vertices, totals[1] = the new faces
+__global__ void mh_totals_kernel(const long long* __restrict__ holes, const long long* __restrict__ added, long long* __restrict__ totals) {
+    totals[0] = *holes;
+    totals[1] = *added;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// emit
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MH_BLOCK) void mh_emit_kernel(long long n, long long m, const int* __restrict__ successor,
+                                                           const int* __restrict__ label, const int* __restrict__ qualify,
+                                                           const int* __restrict__ position, const int* __restrict__ vertex_offset,
+                                                           const int* __restrict__ face_offset, const float* __restrict__ centroid,
+                                                           long long n_holes, long long n_added, float* __restrict__ out_vertices,
+                                                           int* __restrict__ out_faces) {
+    const long v = (long)blockIdx.x * MH_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    const int L = label[v];
+    if (L < 0 || L >= n || !qualify[L]) return;
+    const long long nv = vertex_offset[L];
+    if (nv < 0 || nv >= n_holes) return;   // not this plan's offsets
+    const int p = position[v], b = successor[v];
+    if (p >= 0 && b >= 0 && b < n) {
+        const long long g = (long long)face_offset[L] + p;
+        if (g >= 0 && g < n_added) {
+            int* t = out_faces + 3 * (m + g);
+            t[0] = b;
+            t[1] = (int)v;
+            t[2] = (int)(n + nv);
+        }
+    }
+    if (L == (int)v) {
+        float* x = out_vertices + 3 * (n + nv);
+        x[0] = centroid[3 * v];
+        x[1] = centroid[3 * v + 1];
+        x[2] = centroid[3 * v + 2];
+    }
+}
+
+// scratch of the plan
+struct MhPlanScratch {
+    size_t new_faces, holes, added, scan, bytes;
+};
+
+static MhPlanScratch mh_plan_layout(long long n) {
+    const size_t nv = (size_t)(n > 0 ? n : 1);
+    ScratchLayout L;
+    MhPlanScratch s;
+    s.new_faces = L.take(nv * 4);
+    s.holes = L.take(8);
+    s.added = L.take(8);
+    s.scan = L.take(geom_scan_bytes(n));
+    s.bytes = L.bytes;
+    return s;
+}
+
+static bool mh_sizes_ok(long long n, long long m) { return n >= 0 && n < (1ll << 31) && m >= 0 && 6 * m < (1ll << 31); }
+
+}  // namespace d3d
+
+using namespace d3d;
+
+#define MH_CHECK_SIZES()                                                                                                  \
+    D3D_REQUIRE(mh_sizes_ok(n_vertices, n_faces), "n_vertices=%lld, n_faces=%lld (0 .. 2^31 - 1 vertices, 6 n_faces < 2^31)", \
+                n_vertices, n_faces)
+
+extern "C" size_t d3d_mesh_holes_scratch_bytes(long long n_vertices) {
+    if (!mh_sizes_ok(n_vertices, 0)) return 0;
+    return mh_plan_layout(n_vertices).bytes;
+}
+
+extern "C" int d3d_mesh_boundary(const int* faces, long long n_faces, long long n_vertices, const int* face_offset, const int* face_index,
+                                 int* out_count, int* in_count, int* successor, int* owner, unsigned char* boundary, d3d_stream_t stream) {
+    D3D_REQUIRE((faces || n_faces == 0) && face_offset && face_index && out_count && in_count && successor && owner && boundary,
+                "null pointer (faces, face_offset, face_index, out_count, in_count, successor, owner, boundary)");
+    MH_CHECK_SIZES();
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = n_vertices, m = n_faces;
+    const size_t nb = (size_t)(n > 0 ? n : 1) * 4;
+    int rc = hip_status(hipMemsetAsync(out_count, 0, nb, st), "mesh boundary: clear out counts");
+    if (rc != D3D_OK) return rc;
+    rc = hip_status(hipMemsetAsync(in_count, 0, nb, st), "mesh boundary: clear in counts");
+    if (rc != D3D_OK) return rc;
+    rc = hip_status(hipMemsetAsync(successor, 0xff, nb, st), "mesh boundary: clear successors");
+    if (rc != D3D_OK) return rc;
+    rc = hip_status(hipMemsetAsync(owner, 0xff, nb, st), "mesh boundary: clear owners");
+    if (rc != D3D_OK) return rc;
+    if (m > 0) {
+        hipLaunchKernelGGL(mh_boundary_kernel, dim3(ceil_div(3 * m, MH_BLOCK)), dim3(MH_BLOCK), 0, st, faces, (long)m, n, face_offset, face_index,
+                           out_count, in_count, successor, owner, boundary);
+        D3D_LAUNCH_CHECK("mh_boundary_kernel launch");
+    }
+    if (n > 0) {
+        hipLaunchKernelGGL(mh_unique_kernel, dim3(ceil_div(n, MH_BLOCK)), dim3(MH_BLOCK), 0, st, out_count, n, successor, owner);
+        D3D_LAUNCH_CHECK("mh_unique_kernel launch");
+    }
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_boundary_loops(const int* faces, long long n_faces, long long n_vertices, const unsigned char* boundary,
+                                       const int* out_count, const int* in_count, int* label, int* count, int* bad, int* flag, int* rounds,
+                                       d3d_stream_t stream) {
+    D3D_REQUIRE((faces || n_faces == 0) && boundary && out_count && in_count && label && count && bad && flag,
+                "null pointer (faces, boundary, out_count, in_count, label, count, bad, flag)");
+    MH_CHECK_SIZES();
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = n_vertices, m = n_faces;
+    const size_t nb = (size_t)(n > 0 ? n : 1) * 4;
+    int rc = geom_iota(label, n, st);
+    if (rc != D3D_OK) return rc;
+    rc = hip_status(hipMemsetAsync(count, 0, nb, st), "mesh boundary loops: clear counts");
+    if (rc != D3D_OK) return rc;
+    rc = hip_status(hipMemsetAsync(bad, 0, nb, st), "mesh boundary loops: clear bad");
+    if (rc != D3D_OK) return rc;
+    int r = 0;
+    while (m > 0 && n > 0) {
+        rc = hip_status(hipMemsetAsync(flag, 0, 4, st), "mesh boundary loops: clear flag");
+        if (rc != D3D_OK) return rc;
+        hipLaunchKernelGGL(mh_hook_kernel, dim3(ceil_div(3 * m, MH_BLOCK)), dim3(MH_BLOCK), 0, st, faces, (long)m, n, boundary, label, flag);
+        D3D_LAUNCH_CHECK("mh_hook_kernel launch");
+        ++r;
+        int h = 0;
+        rc = hip_status(hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, st), "mesh boundary loops: read flag");
+        if (rc != D3D_OK) return rc;
+        rc = hip_status(hipStreamSynchronize(st), "mesh boundary loops: sync");
+        if (rc != D3D_OK) return rc;
+        if (!h) break;
+        rc = geom_jump(label, n, st);
+        if (rc != D3D_OK) return rc;
+    }
+    if (rounds) *rounds = r;
+    if (m > 0 && n > 0) {
+        hipLaunchKernelGGL(mh_count_kernel, dim3(ceil_div(3 * m, MH_BLOCK)), dim3(MH_BLOCK), 0, st, faces, (long)m, n, boundary, label, count);
+        D3D_LAUNCH_CHECK("mh_count_kernel launch");
+        hipLaunchKernelGGL(mh_bad_kernel, dim3(ceil_div(n, MH_BLOCK)), dim3(MH_BLOCK), 0, st, out_count, in_count, n, label, bad);
+        D3D_LAUNCH_CHECK("mh_bad_kernel launch");
+    }
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_holes_plan(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* successor,
+                                   const int* owner, const int* label, const int* count, const int* bad, int max_edges, void* scratch,
+                                   size_t scratch_bytes, double* s, float* centroid, int* qualify, int* position, int* vertex_offset,
+                                   int* face_offset, long long* totals, d3d_stream_t stream) {
+    D3D_REQUIRE((vertices || n_vertices == 0) && (faces || n_faces == 0) && successor && owner && label && count && bad && scratch && s &&
+                    centroid && qualify && position && vertex_offset && face_offset && totals,
+                "null pointer (vertices, faces, successor, owner, label, count, bad, scratch, s, centroid, qualify, position, "
+                "vertex_offset, face_offset, totals)");
+    MH_CHECK_SIZES();
+    D3D_REQUIRE(max_edges >= 3 && max_edges <= D3D_MESH_HOLE_MAX_EDGES, "max_edges=%d (3 .. %d)", max_edges, D3D_MESH_HOLE_MAX_EDGES);
+    const MhPlanScratch L = mh_plan_layout(n_vertices);
+    D3D_REQUIRE(scratch_bytes >= L.bytes, "scratch of %zu bytes, %zu needed", scratch_bytes, L.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)scratch;
+    int* new_faces = (int*)(w + L.new_faces);
+    long long *holes = (long long*)(w + L.holes), *added = (long long*)(w + L.added);
+    const long long n = n_vertices, m = n_faces;
+    int rc = hip_status(hipMemsetAsync(position, 0xff, (size_t)(n > 0 ? n : 1) * 4, st), "mesh holes plan: clear positions");
+    if (rc != D3D_OK) return rc;
+    if (n > 0) {
+        hipLaunchKernelGGL(mh_plan_kernel, dim3(ceil_div(n, MH_BLOCK)), dim3(MH_BLOCK), 0, st, vertices, n, faces, (long)m, successor, owner, label,
+                           count, bad, max_edges, s, centroid, qualify, new_faces, position);
+        D3D_LAUNCH_CHECK("mh_plan_kernel launch");
+    }
+    rc = geom_scan(qualify, vertex_offset, n, w + L.scan, holes, st);   // at most n_vertices
+    if (rc != D3D_OK) return rc;
+    rc = geom_scan(new_faces, face_offset, n, w + L.scan, added, st);   // at most 3 n_faces < 2^31
+    if (rc != D3D_OK) return rc;
+    hipLaunchKernelGGL(mh_totals_kernel, dim3(1), dim3(1), 0, st, holes, added, totals);
+    D3D_LAUNCH_CHECK("mh_totals_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_holes_emit(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* successor,
+                                   const int* label, const int* qualify, const int* position, const int* vertex_offset,
+                                   const int* face_offset, const float* centroid, long long n_holes, long long n_added, float* out_vertices,
+                                   int* out_faces, d3d_stream_t stream) {
+    D3D_REQUIRE((vertices || n_vertices == 0) && (faces || n_faces == 0) && successor && label && qualify && position && vertex_offset &&
+                    face_offset && centroid && out_vertices && out_faces,
+                "null pointer (vertices, faces, successor, label, qualify, position, vertex_offset, face_offset, centroid, out_vertices, "
+                "out_faces)");
+    MH_CHECK_SIZES();
+    D3D_REQUIRE(n_holes >= 0 && n_added >= 0 && n_vertices + n_holes < (1ll << 31) && n_faces + n_added < (1ll << 31),
+                "n_holes=%lld, n_added=%lld (>= 0, n_vertices + n_holes and n_faces + n_added below 2^31)", n_holes, n_added);
+    D3D_REQUIRE(vertices != out_vertices && faces != out_faces, "the outputs must not be the inputs");
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = n_vertices, m = n_faces;
+    int rc = D3D_OK;
+    if (n > 0) rc = hip_status(hipMemcpyAsync(out_vertices, vertices, (size_t)n * 12, hipMemcpyDeviceToDevice, st), "mesh holes emit: copy vertices");
+    if (rc != D3D_OK) return rc;
+    if (m > 0) rc = hip_status(hipMemcpyAsync(out_faces, faces, (size_t)m * 12, hipMemcpyDeviceToDevice, st), "mesh holes emit: copy faces");
+    if (rc != D3D_OK) return rc;
+    if (n > 0 && n_holes > 0) {
+        hipLaunchKernelGGL(mh_emit_kernel, dim3(ceil_div(n, MH_BLOCK)), dim3(MH_BLOCK), 0, st, n, m, successor, label, qualify, position,
+                           vertex_offset, face_offset, centroid, n_holes, n_added, out_vertices, out_faces);
+        D3D_LAUNCH_CHECK("mh_emit_kernel launch");
+    }
+    return D3D_OK;
+}

@@ -100,12 +100,44 @@ list: the quadric sums run in face-index order and the kept faces keep their inp
 Order in build_and_write and the command line: removal, smoothing, then decimation (smoothing first takes the TSDF staircase out,
 so flat areas have zero-cost edges).
 
+Hole closing (close_holes(); csrc/mesh_holes.hip): every small boundary loop that is a hole gets a fan around
+one new vertex, off by default.  Named after the reference's nCloseHoles, but the rule is this project's; it does not claim to
+match OpenMVS / VCG.  All arithmetic is fp64 without contraction, rounded to fp32 only where said.
+1. Input.  vertices [n,3] fp32 and faces [m,3] int32, every face with three distinct indices in 0 .. n - 1 (anything else is
+   refused, as decimate refuses it).  max_edges is an integer: 0 means off, otherwise 3 <= max_edges <= HOLE_MAX_EDGES = 1024
+   (any other value is a ValueError).
+2. Boundary half-edges.  Face (a, b, c) has the directed edges a->b, b->c, c->a.  A directed edge is a boundary half-edge when
+   exactly one face holds its undirected edge; its owner is that face.
+3. Simple vertices.  out(v) and in(v) count the boundary half-edges that leave and enter v.  A vertex is simple when out = in
+   = 1.  The successor of a->b is the outgoing boundary half-edge of b, when b is simple.
+4. Boundary components.  Vertices are joined by boundary half-edges (a vertex on none is a component of its own, with nothing
+   in it).  A component's label is its smallest vertex index.  Per component: its half-edge count k, and `bad`, set when any of
+   its vertices is not simple.  A component that is not bad is one cycle.
+5. Loop sums.  The cycle is walked from the half-edge whose tail is the label, following successors.  In walk order, starting
+   from 0, with x_v the position of v in fp64: A += x_a x x_b (the cross product, per component u_y w_z - u_z w_y, u_z w_x -
+   u_x w_z, u_x w_y - u_y w_x), N += (p1 - p0) x (p2 - p0) of the half-edge's owner face in that face's own corner order,
+   S += x_a.  Then s = (A_x N_x + A_y N_y) + A_z N_z.
+6. Which loops qualify.  A component qualifies when it is not bad, 3 <= k <= max_edges and s < 0.  The owner of a->b lies to the
+   left of a->b seen from its normal's side, so A, twice the loop's area vector, points along the normals for the outer border
+   of a piece (s > 0: never capped) and against them when the faces lie outside the loop (s < 0: a hole).  s == 0 or NaN is left
+   alone.  A loop whose owning faces fold back by more than a right angle reads as an outer border and stays open: an open
+   tetrahedron (three faces around an apex) is such a case.
+7. Output.  The input vertices and faces come through first, unchanged and in place.  Each qualifying component adds one vertex
+   fp32(S / k), the new vertices in increasing label order, and k faces (b, a, new), one per half-edge a->b, the new faces in
+   (label, walk position) order.  One pass: the step is not iterated.  A result with n + holes or m + added faces at or above
+   2^31 is refused.  With nothing to close the input tensors come back as they are.
+The result is a function of the input arrays.  Shuffling the face list (without rotating corners) gives the same new vertices
+bit for bit and the same set of faces.  A second call with the same max_edges closes nothing: every boundary edge of a closed
+loop has become manifold, and no other loop has changed.  Integer atomics only, no float atomics.
+Order in clean, build_and_write and the command line: removal, hole closing, smoothing (the smoothing relaxes the fans), then
+decimation (a vertex on a closed hole is no longer fixed, so the collapse is free around it).
+
     python -m deep3d_aerial_amd.mesh --mvs MVS_FOLDER --out mesh.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax --voxel S
         [--trunc T] [--min_views 2] [--conf_threshold 0.2] [--views_per_batch N]
-        [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L]
+        [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L] [--close_holes N]
         [--decimate R] [--target_faces N] [--decimate_max_rounds K]
     python -m deep3d_aerial_amd.mesh --clean IN.ply --out OUT.ply [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L]
-        [--decimate R] [--target_faces N] [--decimate_max_rounds K]
+        [--close_holes N] [--decimate R] [--target_faces N] [--decimate_max_rounds K]
 """
 import argparse
 import ctypes
@@ -123,6 +155,7 @@ DEFAULT_MIN_VIEWS = 2
 DEFAULT_SMOOTH_LAMBDA = 0.5
 DEFAULT_DECIMATE_MAX_ROUNDS = 1000   # a cap on host round trips, far above the rounds a target needs
 DECIMATE_HASH = 2654435761
+HOLE_MAX_EDGES = 1024                # the longest loop close_holes walks (D3D_MESH_HOLE_MAX_EDGES)
 BRICK = 8
 
 # the 6 Kuhn tetrahedra (positively oriented), the edges of a tetrahedron, the 16-case table (csrc/mesh.hip has the same)
@@ -429,13 +462,20 @@ def smooth_vertices(vertices, faces, iterations, smooth_lambda=DEFAULT_SMOOTH_LA
     return out
 
 
-def clean(vertices, faces, min_faces=0, spurious=0.0, smooth=0, smooth_lambda=DEFAULT_SMOOTH_LAMBDA, info=None):
-    """Removal of small components (min_faces, spurious), then `smooth` smoothing iterations, on the device: (vertices, faces).
-    With every step off the input tensors come back as they are."""
+def clean(vertices, faces, min_faces=0, spurious=0.0, smooth=0, smooth_lambda=DEFAULT_SMOOTH_LAMBDA, info=None, close_holes=0):
+    """Removal of small components (min_faces, spurious), then hole closing (close_holes = max_edges > 0), then `smooth` smoothing
+    iterations, on the device: (vertices, faces).  With every step off the input tensors come back as they are.  info (a dict)
+    gets the removal's rounds and faces_removed, and under "close_holes" the dict close_holes() fills."""
+    max_edges = check_close_holes_setting(close_holes)
     vertices, faces, n, m = _mesh_arrays(vertices, faces)
     min_faces, spurious, smooth, lam = check_clean_settings(min_faces, spurious, smooth, smooth_lambda)
     if min_faces > 0 or spurious > 0:
         vertices, faces = remove_components(vertices, faces, min_faces, spurious, info=info)
+    if max_edges > 0:
+        hinfo = {}
+        vertices, faces = _close_holes(vertices, faces, max_edges, info=hinfo)
+        if info is not None:
+            info["close_holes"] = hinfo
     if smooth > 0:
         vertices = smooth_vertices(vertices, faces, smooth, lam)
     return vertices, faces
@@ -458,10 +498,10 @@ def check_decimate_settings(ratio=1.0, target_faces=0, max_rounds=DEFAULT_DECIMA
     return ratio, int(target_faces), int(max_rounds)
 
 
-def _decimate_arrays(vertices, faces):
+def _decimate_arrays(vertices, faces, what="decimation"):
     vertices, faces, n, m = _mesh_arrays(vertices, faces)
     if m and bool(((faces[:, 0] == faces[:, 1]) | (faces[:, 1] == faces[:, 2]) | (faces[:, 2] == faces[:, 0])).any()):
-        raise ValueError("a face has a repeated index: decimation needs three distinct indices per face")
+        raise ValueError("a face has a repeated index: %s needs three distinct indices per face" % what)
     return vertices, faces, n, m
 
 
@@ -581,6 +621,139 @@ def decimate(vertices, faces, ratio=1.0, target_faces=0, max_rounds=DEFAULT_DECI
 
 
 # ----------------------------------------------------------------------------------------
+# hole closing
+# ----------------------------------------------------------------------------------------
+def check_close_holes_setting(max_edges=0):
+    """max_edges checked: 0 (off) or an integer in 3 .. HOLE_MAX_EDGES."""
+    try:
+        whole = int(max_edges) == max_edges
+    except (TypeError, ValueError):
+        whole = False
+    if not whole or not (int(max_edges) == 0 or 3 <= int(max_edges) <= HOLE_MAX_EDGES):
+        raise ValueError("close_holes %r must be 0 (off) or an integer in 3 .. %d" % (max_edges, HOLE_MAX_EDGES))
+    return int(max_edges)
+
+
+def _boundary(faces, n, incidence=None):
+    """d3d_mesh_boundary on checked arrays: boundary, out, in, successor, owner (full-size tensors)."""
+    lib = _lib.load()
+    m = int(faces.shape[0])
+    dev = faces.device
+    foff, finc = incidence if incidence is not None else face_incidence(faces, n)
+    i32 = lambda: torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    d = {"out": i32(), "in": i32(), "successor": i32(), "owner": i32(), "boundary": torch.empty((max(3 * m, 1),), dtype=torch.uint8, device=dev)}
+    _lib.check(lib.d3d_mesh_boundary(_ptr(faces), m, n, _ptr(foff), _ptr(finc), _ptr(d["out"]), _ptr(d["in"]), _ptr(d["successor"]),
+                                     _ptr(d["owner"]), _ptr(d["boundary"]), _stream()), "d3d_mesh_boundary")
+    return d
+
+
+def _loops(faces, n, d):
+    """d3d_mesh_boundary_loops on _boundary's dict: adds label, count, bad and rounds."""
+    lib = _lib.load()
+    m = int(faces.shape[0])
+    dev = faces.device
+    i32 = lambda: torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    d.update(label=i32(), count=i32(), bad=i32())
+    flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+    rounds = ctypes.c_int(0)
+    _lib.check(lib.d3d_mesh_boundary_loops(_ptr(faces), m, n, _ptr(d["boundary"]), _ptr(d["out"]), _ptr(d["in"]), _ptr(d["label"]),
+                                           _ptr(d["count"]), _ptr(d["bad"]), _ptr(flag), ctypes.byref(rounds), _stream()),
+               "d3d_mesh_boundary_loops")
+    d["rounds"] = int(rounds.value)
+    return d
+
+
+def _boundary_loops(faces, n, incidence=None):
+    m = int(faces.shape[0])
+    d = _loops(faces, n, _boundary(faces, n, incidence))
+    for k in ("out", "in", "successor", "owner", "label", "count", "bad"):
+        d[k] = d[k][:n]
+    d["boundary"] = d["boundary"][:3 * m].view(m, 3)
+    return d
+
+
+def boundary_loops(faces, n_vertices):
+    """The boundary of a mesh (hole closing, rules 2-4), on the device: {"boundary" [m,3] uint8 (corner c: the edge from corner c
+    to the next is a boundary half-edge), "out", "in" [n] int32, "successor", "owner" [n] int32 (the head and the owning face of
+    the vertex's outgoing boundary half-edge where out is 1, else -1), "label" [n] int32, "count", "bad" [n] int32 (at a label,
+    0 elsewhere), "rounds": hooking launches (the one entry that may differ from run to run: a launch may or may not see a
+    parent lowered in the same launch)}."""
+    n = int(n_vertices)
+    _, faces, _, _ = _decimate_arrays(torch.empty((n, 3), dtype=torch.float32, device=faces.device), faces, "hole closing")
+    return _boundary_loops(faces, n)
+
+
+def plan_holes(vertices, faces, max_edges, loops=None):
+    """The loops close_holes would close (rules 5-6), on the device: boundary_loops' dict plus {"s" [n] fp64, "centroid" [n,3]
+    fp32, "qualify" [n] int32 (at the label of every walked loop, 0 elsewhere), "position" [n] int32 (the walk position of the
+    vertex's outgoing half-edge, -1: not walked), "vertex_offset", "face_offset" [n] int32, "holes", "faces_added": the totals}.
+    One device-to-host read."""
+    vertices, faces, n, m = _decimate_arrays(vertices, faces, "hole closing")
+    max_edges = check_close_holes_setting(max_edges)
+    if max_edges == 0 or m == 0:
+        raise ValueError("plan_holes needs faces and max_edges in 3 .. %d" % HOLE_MAX_EDGES)
+    return _plan_holes(vertices, faces, n, m, max_edges, loops)
+
+
+def _plan_holes(vertices, faces, n, m, max_edges, loops=None):
+    lib = _lib.load()
+    dev = vertices.device
+    d = dict(loops) if loops is not None else _boundary_loops(faces, n)
+    scratch, nbytes = _geom.scratch(lib.d3d_mesh_holes_scratch_bytes, n, device=dev)
+    i32 = lambda: torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    s = torch.empty((max(n, 1),), dtype=torch.float64, device=dev)
+    centroid = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev)
+    qualify, position, voff, foff = i32(), i32(), i32(), i32()
+    totals = torch.empty((2,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_mesh_holes_plan(_ptr(vertices), n, _ptr(faces), m, _ptr(d["successor"]), _ptr(d["owner"]), _ptr(d["label"]),
+                                       _ptr(d["count"]), _ptr(d["bad"]), max_edges, _ptr(scratch), nbytes, _ptr(s), _ptr(centroid),
+                                       _ptr(qualify), _ptr(position), _ptr(voff), _ptr(foff), _ptr(totals), _stream()), "d3d_mesh_holes_plan")
+    holes, added = (int(x) for x in totals.cpu())   # the totals size the outputs
+    d.update(s=s[:n], centroid=centroid[:n], qualify=qualify[:n], position=position[:n], vertex_offset=voff[:n], face_offset=foff[:n],
+             holes=holes, faces_added=added)
+    return d
+
+
+def close_holes(vertices, faces, max_edges, info=None):
+    """Closes every boundary loop of at most max_edges edges that is a hole with a fan around one new vertex, on the device:
+    (vertices, faces), the input first and unchanged.  With max_edges 0, or nothing to close, the input tensors come back as they
+    are.  info (a dict) gets loops (boundary components), holes_closed, faces_added, skipped_outer (walked, s not below 0),
+    skipped_large (more than max_edges edges), skipped_not_simple (bad) and rounds."""
+    max_edges = check_close_holes_setting(max_edges)
+    if max_edges == 0:
+        _mesh_arrays(vertices, faces)
+        if info is not None:
+            info.update(loops=0, holes_closed=0, faces_added=0, skipped_outer=0, skipped_large=0, skipped_not_simple=0, rounds=0)
+        return vertices, faces
+    vertices, faces, n, m = _decimate_arrays(vertices, faces, "hole closing")
+    if m == 0:
+        if info is not None:
+            info.update(loops=0, holes_closed=0, faces_added=0, skipped_outer=0, skipped_large=0, skipped_not_simple=0, rounds=0)
+        return vertices, faces
+    p = _plan_holes(vertices, faces, n, m, max_edges)
+    holes, added = p["holes"], p["faces_added"]
+    if info is not None:
+        count, bad = p["count"], p["bad"] != 0
+        small = (count >= 3) & (count <= max_edges)
+        info.update(loops=int((count > 0).sum()), holes_closed=holes, faces_added=added,
+                    skipped_outer=int(((count > 0) & ~bad & small).sum()) - holes, skipped_large=int((~bad & (count > max_edges)).sum()),
+                    skipped_not_simple=int(((count > 0) & bad).sum()), rounds=p["rounds"])
+    if holes == 0:
+        return vertices, faces
+    if n + holes >= 1 << 31 or m + added >= 1 << 31:
+        raise ValueError("%d + %d vertices, %d + %d faces: more than int32 indexes" % (n, holes, m, added))
+    out_v = torch.empty((n + holes, 3), dtype=torch.float32, device=vertices.device)
+    out_f = torch.empty((m + added, 3), dtype=torch.int32, device=vertices.device)
+    _lib.check(_lib.load().d3d_mesh_holes_emit(_ptr(vertices), n, _ptr(faces), m, _ptr(p["successor"]), _ptr(p["label"]), _ptr(p["qualify"]),
+                                               _ptr(p["position"]), _ptr(p["vertex_offset"]), _ptr(p["face_offset"]), _ptr(p["centroid"]),
+                                               holes, added, _ptr(out_v), _ptr(out_f), _stream()), "d3d_mesh_holes_emit")
+    return out_v, out_f
+
+
+_close_holes = close_holes   # clean() has a keyword of the same name
+
+
+# ----------------------------------------------------------------------------------------
 # PLY
 # ----------------------------------------------------------------------------------------
 FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
@@ -685,6 +858,8 @@ def add_clean_arguments(ap, prefix=""):
                     help="remove components whose box diagonal is below the mesh's divided by this (0: off)")
     ap.add_argument("--%ssmooth" % prefix, type=int, default=0, help="Laplacian smoothing iterations (0: off)")
     ap.add_argument("--%ssmooth_lambda" % prefix, type=float, default=DEFAULT_SMOOTH_LAMBDA, help="smoothing step in (0, 1]")
+    ap.add_argument("--%sclose_holes" % prefix, type=int, default=0, metavar="N",
+                    help="close the holes of at most N boundary edges, 3 .. %d, after the removal and before the smoothing (0: off)" % HOLE_MAX_EDGES)
 
 
 def settings_from_args(a, path, prefix=""):
@@ -692,7 +867,7 @@ def settings_from_args(a, path, prefix=""):
     return {"path": path, "border": g("border"), "voxel": g("voxel"), "trunc": g("trunc"), "min_views": g("min_views"),
             "conf_threshold": g("conf_threshold"), "views_per_batch": g("views_per_batch"), "min_faces": g("min_faces"),
             "spurious": g("spurious"), "smooth": g("smooth"), "smooth_lambda": g("smooth_lambda"), "decimate": g("decimate"),
-            "target_faces": g("target_faces"), "decimate_max_rounds": g("decimate_max_rounds")}
+            "target_faces": g("target_faces"), "decimate_max_rounds": g("decimate_max_rounds"), "close_holes": g("close_holes")}
 
 
 def clean_settings(settings):
@@ -704,6 +879,15 @@ def clean_settings(settings):
 def clean_requested(settings):
     min_faces, spurious, smooth, _ = clean_settings(settings)
     return min_faces > 0 or spurious > 0 or smooth > 0
+
+
+def close_holes_setting(settings):
+    """max_edges of a settings dict ("close_holes"), checked; a missing key means "off"."""
+    return check_close_holes_setting(0 if settings.get("close_holes") is None else settings["close_holes"])
+
+
+def close_holes_requested(settings):
+    return close_holes_setting(settings) > 0
 
 
 def decimate_settings(settings):
@@ -727,6 +911,7 @@ def check_args(ap, a, prefix=""):
         s = settings_from_args(a, None, prefix)
         check_settings(MeshGrid(s["border"], s["voxel"]), s["trunc"], s["min_views"], s["conf_threshold"], s["views_per_batch"])
         clean_settings(s)
+        close_holes_setting(s)
         decimate_settings(s)
     except ValueError as e:
         ap.error("--%s*: %s" % (prefix, e))
@@ -742,13 +927,13 @@ def _decimate_and_report(v, f, ratio, target_faces, max_rounds):
 
 
 def build_and_write(views, settings):
-    """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on (removal, smoothing), then
-    decimate when it is on, and write_ply to settings["path"]: (vertices, faces) as written."""
+    """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on (removal, hole closing, smoothing),
+    then decimate when it is on, and write_ply to settings["path"]: (vertices, faces) as written."""
     grid = MeshGrid(settings["border"], settings["voxel"])
     v, f = depth_to_mesh(views, grid, settings.get("trunc"), settings.get("min_views", DEFAULT_MIN_VIEWS),
                          settings.get("conf_threshold", DEFAULT_CONF), settings.get("views_per_batch"))
-    if clean_requested(settings):
-        v, f = clean(v, f, *clean_settings(settings))
+    if clean_requested(settings) or close_holes_requested(settings):
+        v, f = clean(v, f, *clean_settings(settings), close_holes=close_holes_setting(settings))
     if decimate_requested(settings):
         v, f = _decimate_and_report(v, f, *decimate_settings(settings))
     write_ply(settings["path"], v, f)
@@ -767,6 +952,7 @@ def main(argv=None):
     if a.clean is not None:
         try:
             check_clean_settings(a.min_faces, a.spurious, a.smooth, a.smooth_lambda)
+            check_close_holes_setting(a.close_holes)
             check_decimate_settings(a.decimate, a.target_faces, a.decimate_max_rounds)
         except ValueError as e:
             ap.error("--clean: %s" % e)
@@ -776,7 +962,8 @@ def main(argv=None):
         raise RuntimeError("the mesh is built on the GPU (no CPU fallback)")
     if a.clean is not None:
         v, f = read_ply(a.clean)
-        v, f = clean(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), a.min_faces, a.spurious, a.smooth, a.smooth_lambda)
+        v, f = clean(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), a.min_faces, a.spurious, a.smooth, a.smooth_lambda,
+                     close_holes=a.close_holes)
         if a.decimate < 1 or a.target_faces > 0:
             v, f = _decimate_and_report(v, f, a.decimate, a.target_faces, a.decimate_max_rounds)
         write_ply(a.out, v, f)

@@ -88,7 +88,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     true orthophoto on that DSM (write_ortho_of) from the views' gathered depth maps, cameras and reference images; rank 0
     writes it; timings gets ortho_s.
     mesh: None (nothing changes), or the mesh settings {"path", "border", "voxel", "trunc", "min_views", "conf_threshold",
-    "views_per_batch"} and optionally the clean steps {"min_faces", "spurious", "smooth", "smooth_lambda"} and the decimation
+    "views_per_batch"} and optionally the clean steps {"min_faces", "spurious", "smooth", "smooth_lambda"}, the hole closing
+    {"close_holes": the longest boundary loop closed, 3 .. 1024, between the removal and the smoothing} and the decimation
     {"decimate", "target_faces", "decimate_max_rounds"} (absent: off) (mesh.settings_from_args): rank 0 builds the mesh of every
     gathered depth and confidence map with its camera, in global view order, cleans it when a clean step is on (mesh.clean),
     decimates it when asked (mesh.decimate), and writes the PLY; the DSM from the mesh and the texture use that mesh.  The
@@ -103,6 +104,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         _mesh.check_settings(_grid, mesh.get("trunc"), mesh.get("min_views", _mesh.DEFAULT_MIN_VIEWS),
                              mesh.get("conf_threshold", _mesh.DEFAULT_CONF), mesh.get("views_per_batch"))
         _mesh.clean_settings(mesh)
+        _mesh.close_holes_setting(mesh)
         _mesh.decimate_settings(mesh)
     dsm_source = dsm.get("source", "pc") if dsm is not None else None
     if dsm is not None:

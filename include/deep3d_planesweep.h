@@ -1115,6 +1115,61 @@ int d3d_mesh_decimate_faces(const int* faces, long long n_faces, long long n_ver
                             int* out_faces, int* referenced, long long* n_kept, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.16 -- closing the small holes of the surface mesh: every boundary loop of at most max_edges edges whose faces
+ * lie outside it gets a fan around one new vertex (the rule is this project's, deep3d_aerial_amd/mesh.py states it in full; it
+ * does not claim to match OpenMVS / VCG).  A mesh is vertices [n_vertices, 3] fp32 and faces [n_faces, 3] int32, n_vertices <
+ * 2^31, 6 n_faces < 2^31.  A face with an index outside 0 .. n_vertices - 1 or with a repeated index is ignored by every pass
+ * (the caller refuses such a mesh).  Face (a, b, c) has the directed edges a->b, b->c, c->a; one is a boundary half-edge when
+ * exactly one face holds its undirected edge, and that face owns it.  A vertex is simple when it has exactly one outgoing and
+ * one incoming boundary half-edge.  Every pointer is DEVICE memory except `rounds`.  All arithmetic is fp64 without
+ * contraction, rounded to fp32 only where said; no float atomics; the integer atomics are add, or and min, and their return
+ * values never reach an output.
+ */
+#define D3D_MESH_HOLE_MAX_EDGES 1024
+
+/* Scratch of d3d_mesh_holes_plan (0 for an out-of-range size). */
+size_t d3d_mesh_holes_scratch_bytes(long long n_vertices);
+
+/* d3d_mesh_boundary: face_offset / face_index are d3d_mesh_decimate_incidence's outputs for the same mesh.  boundary
+ *   [3 n_faces] uint8 = 1 where corner c of face f (entry 3 f + c, the edge from corner c to corner c + 1 mod 3) is a boundary
+ *   half-edge; out_count / in_count [n_vertices] int32 = the boundary half-edges leaving / entering the vertex; successor and
+ *   owner [n_vertices] int32 = the head and the owning face of the vertex's outgoing boundary half-edge where out_count is 1,
+ *   -1 elsewhere. */
+int d3d_mesh_boundary(const int* faces, long long n_faces, long long n_vertices, const int* face_offset, const int* face_index,
+                      int* out_count, int* in_count, int* successor, int* owner, unsigned char* boundary, d3d_stream_t stream);
+
+/* d3d_mesh_boundary_loops: label [n_vertices] int32 gets the smallest vertex index of each vertex's boundary component
+ *   (vertices joined by boundary half-edges; a vertex on none is its own).  count [n_vertices] int32 at a label: the
+ *   component's half-edges; bad [n_vertices] int32 at a label: 1 when some vertex of the component is not simple (a component
+ *   that is not bad is one cycle); both 0 at every index that is no label.  Hooking and pointer jumping as
+ *   d3d_mesh_components: the host reads flag (one device int32) once per round and waits on the stream; rounds (host, may be
+ *   null) gets the number of hooking launches, which may differ from run to run; the outputs do not. */
+int d3d_mesh_boundary_loops(const int* faces, long long n_faces, long long n_vertices, const unsigned char* boundary, const int* out_count,
+                            const int* in_count, int* label, int* count, int* bad, int* flag, int* rounds, d3d_stream_t stream);
+
+/* d3d_mesh_holes_plan: every label vertex L of a component that is not bad with 3 <= count <= max_edges walks its cycle from
+ *   the half-edge whose tail is L along the successors and sums, in walk order from 0: A += x_a x x_b, N += (p1 - p0) x
+ *   (p2 - p0) of the half-edge's owner in that face's corner order, S += x_a.  s [n_vertices] fp64 at L = (A_x N_x + A_y N_y) +
+ *   A_z N_z; centroid [n_vertices, 3] fp32 at L = fp32(S / count); position [n_vertices] int32 = the walk position of the
+ *   half-edge leaving the vertex (-1: not walked); qualify [n_vertices] int32 at L = 1 when s < 0 (the faces lie outside the
+ *   loop: a hole).  s, centroid and qualify are 0 everywhere else.  vertex_offset / face_offset [n_vertices] int32 = the
+ *   exclusive scans of qualify and of qualify * count; totals [2] int64 = the new vertices and the new faces.
+ *   3 <= max_edges <= D3D_MESH_HOLE_MAX_EDGES. */
+int d3d_mesh_holes_plan(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* successor,
+                        const int* owner, const int* label, const int* count, const int* bad, int max_edges, void* scratch,
+                        size_t scratch_bytes, double* s, float* centroid, int* qualify, int* position, int* vertex_offset, int* face_offset,
+                        long long* totals, d3d_stream_t stream);
+
+/* d3d_mesh_holes_emit: out_vertices [n_vertices + n_holes, 3] = vertices, then centroid[L] of every qualifying label L at
+ *   n_vertices + vertex_offset[L]; out_faces [n_faces + n_added, 3] = faces, then for every half-edge a->b of such a component
+ *   the face (b, a, n_vertices + vertex_offset[L]) at n_faces + face_offset[L] + position[a].  n_holes, n_added: the plan's
+ *   totals, read by the host; n_vertices + n_holes and n_faces + n_added stay below 2^31.  The outputs are not the inputs. */
+int d3d_mesh_holes_emit(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* successor,
+                        const int* label, const int* qualify, const int* position, const int* vertex_offset, const int* face_offset,
+                        const float* centroid, long long n_holes, long long n_added, float* out_vertices, int* out_faces,
+                        d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.13 -- texturing the surface mesh from the views (the semantics are this project's, deep3d_aerial_amd/texture.py
  * states them in full; they do not claim to match OpenMVS's TextureMesh).  A mesh is vertices [n_vertices, 3] fp32 and faces
  * [n_faces, 3] int32, n_vertices < 2^31, 3 n_faces < 2^31; faces with an index outside 0 .. n_vertices - 1 are skipped (the
