@@ -1,20 +1,54 @@
-"""Tensor-level front end of the C-ABI kernels (one function per entry point).
+"""Tensor-level front end of the C-ABI kernels (one function per entry point): the operators and their dispatch.
 
 PyTorch is plumbing here: it owns device memory and the current HIP stream; all arithmetic
 happens in libdeep3d_planesweep.so.  Tensors must be fp32, contiguous and on the GPU --
 anything else raises (no CPU path exists).  Shapes are unbatched, as in the header.
-"""
-import collections
-import ctypes
-import os
 
+What lives where: this module keeps every operator, the conditions under which each kernel is chosen (with the measurements
+that set them) and the constants those conditions read.  The weight layouts the kernels read are in _packing.py; streams,
+argument checks, precision state, dispatch counters and the weight caches are in _runtime.py.  Both are imported by name
+below, so `ops._pack_z2_bf16`, `ops._stream`, `ops.dispatch_counts` ... resolve as before.
+"""
+import ctypes
+
+import numpy as _np
 import torch
 
 from . import _lib
 from . import config as _cfg
+from ._packing import (  # noqa: F401  (every packer stays reachable as ops._pack_*)
+    _conv_fold_choice, _dim_conv, _dim_convT, _fold_pack, _mpad, _pack_c11, _pack_c2s, _pack_c8_bf16, _pack_c8_bf16x3,
+    _pack_c8_kzfold_bf16, _pack_c8_kzfold_bf16x3, _pack_co8, _pack_coT8, _pack_k1, _pack_t2_bf16, _pack_t2_bf16x3,
+    _pack_t2_fold_bf16, _pack_t2d_bf16, _pack_t2d_bf16x3, _pack_t2d_f32, _pack_t2d_k4_bf16, _pack_t2d_k4_bf16x3,
+    _pack_t2d_k4fold_bf16, _pack_t2flip, _pack_z2_bf16, _pack_z2_bf16x3, _pack_z2_f32, _round_h16, _split3_bf16, h16_dtype,
+    upsampled_conv_weight)
+from ._runtime import (  # noqa: F401  (one object each: ops.dispatch_counts IS _runtime.dispatch_counts, and so on)
+    AFFINE, H16_NAMES, PER_PIXEL, PER_PLANE, _chk, _chk16, _depth_ranges, _derived_cache, _dptr, _gn_arenas, _norm_precision,
+    _opt, _pack_cache, _packed, _packed_fold, _ptr_array, _side_streams, _stream, _sync_force_path, _use_mfma, _workspace,
+    clear_weight_cache, conv_precision, depth_range_host, derived_weight, dispatch_counts, fp32_convs, h16_convs, hand_over,
+    note_depth_range, on_streams, publish_prepared, set_conv_precision, side_streams)
 
-PER_PLANE, PER_PIXEL, AFFINE = 0, 1, 2
 
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _launch(name, out, skip, args, counts=(), device=None, must=False):
+    """One call of the entry point `name`.  `out`: the output tensor, or a shape to allocate (fp32, on `device`); `skip`: a
+    tensor that must have the output's shape, or None; `args(out)` -> the argument tuple (built after those checks).  Returns
+    `out`, or None when the kernel does not take the call (D3D_ERR_UNSUPPORTED: nothing was launched; with must=True that is
+    an error like any other).  `counts`: the dispatch_counts keys a served call bumps."""
+    if not isinstance(out, torch.Tensor):
+        out = torch.empty(out, dtype=torch.float32, device=device)
+    if skip is not None and skip.shape != out.shape:
+        raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
+    rc = getattr(_lib.load(), name)(*args(out))
+    if rc == _lib.ERR_UNSUPPORTED and not must:
+        return None
+    _lib.check(rc, name)
+    for key in counts:
+        dispatch_counts[key] += 1
+    return out
 
 class AffineDepth:
     """Per-pixel depth hypotheses in their generating form (include/deep3d_planesweep.h, D3D_DEPTH_AFFINE): `maps` is
@@ -34,76 +68,11 @@ class AffineDepth:
         return (self.maps[0:1] + k * self.maps[1:2]).contiguous()
 
 
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_raw_device = getattr(torch._C, "_cuda_getDevice", None)
-
-
-def _stream():
-    """The HIP stream torch currently queues work on.  torch.cuda.current_stream() builds a Stream object through several
-    Python layers (8 us; an AdaMVS view makes 860 launches: tools/host_profile.py); the raw handle is one C call."""
-    if _raw_stream is not None and _raw_device is not None:
-        return ctypes.c_void_p(_raw_stream(_raw_device()))
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-# Which kernels served the calls so far: name -> count.  The model-level parity tests clear it, run a forward and assert that
-# the production kernels (tile convolutions, fused conv-GRU cell, channel-last volumes, window / ring sweeps) were the ones
-# dispatched -- not a fallback that happens to give the same numbers.
-dispatch_counts = collections.Counter()
-CONV2D_ZS_MINPIX = 256 * 256   # smallest image (pixels) conv2d_k3 hands to the 2-D tile kernel
-
-
 def sweep_dispatch_counts(reset=False):
     """{'direct': n, 'tiled': n, 'window': n}: sweep calls served by each kernel family (the C dispatcher's own counters)."""
     buf = (ctypes.c_ulonglong * 4)()
     _lib.check(_lib.load().d3d_debug_dispatch_counts(buf, int(bool(reset))), "d3d_debug_dispatch_counts")
     return {"direct": int(buf[1]), "tiled": int(buf[2]), "window": int(buf[3])}
-
-
-def _chk(t, name, ndim=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if not t.is_cuda:
-        raise RuntimeError("%s is on %s: the plane-sweep engine only runs on the GPU (no CPU fallback)"
-                           % (name, t.device))
-    if t.dtype != torch.float32:
-        raise TypeError("%s must be float32 (got %s)" % (name, t.dtype))
-    if not t.is_contiguous():
-        raise ValueError("%s must be contiguous" % name)
-    if ndim is not None and t.dim() != ndim:
-        raise ValueError("%s must have %d dims (got shape %s)" % (name, ndim, tuple(t.shape)))
-    return ctypes.c_void_p(t.data_ptr())
-
-
-_forced = [None]
-
-
-def _sync_force_path():
-    """D3D_FORCE_PATH = direct | tiled (tests, profiling): forwarded to the library's test hook when it changes."""
-    want = _cfg.get("D3D_FORCE_PATH")
-    if want != _forced[0]:
-        code = {"": 0, "auto": 0, "direct": 1, "tiled": 2, "window": 3}.get(want)
-        if code is None:
-            raise ValueError("D3D_FORCE_PATH must be direct, tiled, window or unset (got %r)" % want)
-        _lib.check(_lib.load().d3d_debug_force_path(code), "d3d_debug_force_path")
-        _forced[0] = want
-
-
-def _workspace(n_views, C, D, h, w, elem_bytes, device, mode=PER_PIXEL):
-    """Scratch for one sweep call, sized by the library FOR THE CALL'S DEPTH MODE (the window kernel's channel-last copy -- 650 MB
-    at the last cascade stage -- serves hypothesis volumes only: (lo, step) maps and per-plane depths do not ask for it) and owned
-    by torch's caching allocator: the allocator hands the block back only after the work queued on the current stream (this call)
-    has been ordered, so calls never share it."""
-    _sync_force_path()
-    n = int(_lib.load().d3d_sweep_workspace_bytes_for(n_views, C, D, h, w, elem_bytes, mode))
-    if n == 0:
-        return None, ctypes.c_void_p(0), 0
-    buf = torch.empty((n,), dtype=torch.uint8, device=device)
-    return buf, ctypes.c_void_p(buf.data_ptr()), n
-
-
-def _opt(t, name):
-    return None if t is None else _chk(t, name)
 
 
 def _depth(depth, h, w, affine_ok=True, op=""):
@@ -122,13 +91,9 @@ def _depth(depth, h, w, affine_ok=True, op=""):
     raise ValueError("depth must be [D] or [D,h,w] (got %s)" % (tuple(depth.shape),))
 
 
-def _ptr_array(tensors, name):
-    arr = (ctypes.c_void_p * len(tensors))()
-    for i, t in enumerate(tensors):
-        arr[i] = t.data_ptr() if _chk(t, "%s[%d]" % (name, i), 3) is not None else None
-    return arr
-
-
+# ----------------------------------------------------------------------------------------
+# Plane sweeps: projections, warps, cost volumes
+# ----------------------------------------------------------------------------------------
 def compose_projections(proj44):
     """[V,4,4] (index 0 = reference) -> [V-1,12] composed [rot|trans] (module.py:528-530)."""
     p = _chk(proj44, "proj44", 3)
@@ -164,10 +129,10 @@ def homo_warp_double(src, src_proj, ref_proj, depth):
     p44 = torch.stack([ref_proj, src_proj]).contiguous()
     p34 = torch.empty((1, 12), dtype=torch.float64, device=src.device)
     lib = _lib.load()
-    _lib.check(lib.d3d_compose_projections_f64(ctypes.c_void_p(p44.data_ptr()), 2, ctypes.c_void_p(p34.data_ptr()),
+    _lib.check(lib.d3d_compose_projections_f64(_ptr(p44), 2, _ptr(p34),
                                                _stream()), "d3d_compose_projections_f64")
     out = torch.empty((C, D, h, w), dtype=torch.float32, device=src.device)
-    rc = lib.d3d_homo_warp_f64coord(_chk(src, "src", 3), ctypes.c_void_p(p34.data_ptr()), dp, mode, C, D, h, w,
+    rc = lib.d3d_homo_warp_f64coord(_chk(src, "src", 3), _ptr(p34), dp, mode, C, D, h, w,
                                     _chk(out, "out", 4), _stream())
     _lib.check(rc, "d3d_homo_warp_f64coord")
     return out
@@ -183,12 +148,6 @@ def _check_feats(feats, proj34):
     if proj34.numel() != 12 * (len(feats) - 1):
         raise ValueError("proj34 must hold %d x 12 floats" % (len(feats) - 1))
     return shape
-
-
-def _chk16(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float16 and t.is_contiguous()):
-        raise TypeError("%s must be a contiguous CUDA float16 tensor" % name)
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def variance_volume(feats, proj34, depth, out=None, plane_major=False):
@@ -244,12 +203,10 @@ def variance_volume_cl(feats, proj34, depth, layout="cl"):
         arr = _ptr_array(feats, "feats")
         ws, wp, wn = _workspace(len(feats), C, D, h, w, 4, feats[0].device, mode)
         name = "d3d_variance_volume_cl8_h16" if layout == "cl8" else "d3d_variance_volume_cl_h16"
-        rc = getattr(_lib.load(), name)(arr, _chk(proj34, "proj34"), dp, mode, len(feats), C, D, h, w,
-                                        ctypes.c_void_p(out.data_ptr()), wp, wn, _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, name)
-            dispatch_counts["variance_" + layout] += 1
-            return out
+        y = _launch(name, out, None, lambda out: (arr, _chk(proj34, "proj34"), dp, mode, len(feats), C, D, h, w, _ptr(out), wp, wn, _stream()),
+                    ("variance_" + layout,))
+        if y is not None:
+            return y
     dispatch_counts["variance_cl_fallback"] += 1
     y = to_cl(variance_volume(feats, proj34, depth))
     return cl_to_cl8(y) if layout == "cl8" else y
@@ -301,13 +258,9 @@ def weighted_corr_cl8(feats, proj34, weights, depth, out=None):
         raise ValueError("out must be a contiguous %s tensor of ops.h16_dtype()" % (shape,))
     arr = _ptr_array(feats, "feats")
     ws, wp, wn = _workspace(len(feats), C, D, h, w, 4, feats[0].device, mode)
-    rc = _lib.load().d3d_weighted_corr_cl8_h16(arr, _chk(proj34, "proj34"), _chk(weights, "weights", 3), dp, mode, len(feats), C, D, h, w,
-                                               ctypes.c_void_p(out.data_ptr()), wp, wn, _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_weighted_corr_cl8_h16")
-    dispatch_counts["weighted_corr_cl8"] += 1
-    return out
+    return _launch("d3d_weighted_corr_cl8_h16", out, None,
+                   lambda out: (arr, _chk(proj34, "proj34"), _chk(weights, "weights", 3), dp, mode, len(feats), C, D, h, w,
+                                _ptr(out), wp, wn, _stream()), ("weighted_corr_cl8",))
 
 
 def pair_corr_mean(ref, src, proj34, depth, out=None):
@@ -323,6 +276,9 @@ def pair_corr_mean(ref, src, proj34, depth, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------------------
+# Depth regression, hypothesis sampling, the online regression of the slice regularisers
+# ----------------------------------------------------------------------------------------
 def softargmin_conf4(cost, depth):
     """cost [D,h,w] -> (depth [h,w], confidence [h,w]) (cas_mvsnet.py:69-76)."""
     D, h, w = cost.shape
@@ -416,7 +372,7 @@ def slice_head_regress(up, weight, bias, transposed, dplane, max_p, sum_d, sum_p
     if w % (2 if transposed else 4):
         return False
     hd, wd = dplane.shape
-    wr = derived_weight(weight, "h16round", lambda t: t.to(h16_dtype()).float().contiguous())   # the matrix cores' rounding, once
+    wr = derived_weight(weight, "h16round", _round_h16)   # the matrix cores' rounding, once
     rc = _lib.load().d3d_slice_head_regress_h16(_chk(up, "up", 3), _chk(wr, "weight"), _chk(bias, "bias"), int(bool(transposed)),
                                                  _chk(dplane, "dplane", 2), hd, wd, h, w, _chk(max_p, "max_p", 2),
                                                  _chk(sum_d, "sum_d", 2), _chk(sum_p, "sum_p", 2), _stream())
@@ -439,8 +395,8 @@ def slice_tail_regress_same(state2, w_up, b_up, state1, skip_after_act, w_head, 
         return False
     hd, wd = dplane.shape
     wp = derived_weight(w_up, "t2dbf16", _pack_t2d_bf16)
-    wr = derived_weight(w_head, "h16round", lambda t: t.to(h16_dtype()).float().contiguous())
-    rc = _lib.load().d3d_slice_tail_regress_same_h16(_chk(state2, "state2", 3), ctypes.c_void_p(wp.data_ptr()), _opt(b_up, "b_up"),
+    wr = derived_weight(w_head, "h16round", _round_h16)
+    rc = _lib.load().d3d_slice_tail_regress_same_h16(_chk(state2, "state2", 3), _ptr(wp), _opt(b_up, "b_up"),
                                                       _chk(state1, "state1", 3), int(bool(skip_after_act)), _chk(wr, "w_head"),
                                                       _chk(b_head, "b_head"), _chk(dplane, "dplane", 2), hd, wd, h, w,
                                                       _chk(max_p, "max_p", 2), _chk(sum_d, "sum_d", 2), _chk(sum_p, "sum_p", 2), _stream())
@@ -464,8 +420,8 @@ def slice_tail_regress(state2, w_up, b_up, state1, w_head, b_head, dplane, max_p
         return False
     hd, wd = dplane.shape
     wp = derived_weight(w_up, "t2dbf16", _pack_t2d_bf16)
-    wr = derived_weight(w_head, "h16round", lambda t: t.to(h16_dtype()).float().contiguous())
-    rc = _lib.load().d3d_slice_tail_regress_h16(_chk(state2, "state2", 3), ctypes.c_void_p(wp.data_ptr()), _chk(b_up, "b_up"),
+    wr = derived_weight(w_head, "h16round", _round_h16)
+    rc = _lib.load().d3d_slice_tail_regress_h16(_chk(state2, "state2", 3), _ptr(wp), _chk(b_up, "b_up"),
                                                  _chk(state1, "state1", 3), _chk(wr, "w_head"), _chk(b_head, "b_head"),
                                                  _chk(dplane, "dplane", 2), hd, wd, h, w, _chk(max_p, "max_p", 2),
                                                  _chk(sum_d, "sum_d", 2), _chk(sum_p, "sum_p", 2), _stream())
@@ -523,55 +479,21 @@ def resize_bilinear(x, H, W):
     return out
 
 
-def _pack_c8_bf16(w, dt=None):
-    """[8,Ci,3,3,3] -> the B operands of v_mfma_f32_16x16x32_bf16 for d3d_conv3d_k3_c8_h16: [kz][K block][lane][8] bf16
-    with K = (ky, kx, ci) padded to a multiple of 32 and the 8 output channels in columns 0..7 of 16 (rest zero);
-    lane l holds column l & 15, rows 8 * (l >> 4) .. + 7 of its block.  Returned as int16 bits."""
-    Co, Ci = w.shape[0], w.shape[1]
-    K = 9 * Ci
-    nkb = (K + 31) // 32
-    ntn = (max(Co, 16) + 15) // 16
-    b = torch.zeros((3, nkb * 32, ntn * 16), dtype=torch.float32, device=w.device)
-    # w[n, ci, kz, ky, kx] -> b[kz, (ky*3+kx)*Ci + ci, n]
-    b[:, :K, :Co] = w.permute(2, 3, 4, 1, 0).reshape(3, K, Co)
-    b = b.reshape(3, nkb, 4, 8, ntn, 16).permute(0, 1, 4, 2, 5, 3)      # [kz][kb][ntile][kgroup][n][j]
-    return b.reshape(3, nkb, ntn, 64, 8).to(dt or h16_dtype()).view(torch.int16).contiguous()
-
-
-def _pack_c8_kzfold_bf16x3(w):
-    """[1,Ci,3,3,3] -> the B operands of d3d_conv3d_k3_c1_bf16x3: [hi | mid | lo] x _pack_c8_kzfold_bf16."""
-    return torch.stack([_pack_c8_kzfold_bf16(part, torch.bfloat16) for part in _split3_bf16(w)]).contiguous()
-
-
-def _pack_t2_bf16x3(w):
-    """nn.ConvTranspose3d weight [Ci,Co,3,3,3] -> the B operands of d3d_convtranspose3d_k3s2_zs_bf16x3: [hi | mid | lo] x _pack_t2_bf16."""
-    return torch.stack([_pack_t2_bf16(part, torch.bfloat16) for part in _split3_bf16(w)]).contiguous()
-
-
-def _pack_c8_bf16x3(w):
-    """[Co,Ci,3,3,3] -> the B operands of d3d_conv3d_k3_zs_bf16x3: [hi | mid | lo] x _pack_c8_bf16 (the exact three-way bf16 split)."""
-    return torch.stack([_pack_c8_bf16(part, torch.bfloat16) for part in _split3_bf16(w)]).contiguous()
-
-
-def _pack_c8_kzfold_bf16(w, dt=None):
-    """nn.Conv3d weight [1,Ci,3,3,3] -> B operands of d3d_conv3d_k3_c1_cl_h16: ONE tile per K block whose columns 0, 1, 2 are
-    the k_z = 0, 1, 2 slices (K = (k_y, k_x, c_in), padded to a multiple of 32); [K block][lane][8], lane l = column l & 15,
-    K rows 8 * (l >> 4) .. + 7.  int16 bits (bf16)."""
-    Ci = w.shape[1]
-    K = 9 * Ci
-    nkb = (K + 31) // 32
-    b = torch.zeros((nkb * 32, 16), dtype=torch.float32, device=w.device)
-    b[:K, :3] = w[0].permute(2, 3, 0, 1).reshape(K, 3)          # [ci, kz, ky, kx] -> [ky, kx, ci, kz] -> rows (ky*3+kx)*Ci + ci, column kz
-    b = b.reshape(nkb, 4, 8, 16).permute(0, 1, 3, 2)            # [kb][kgroup][n][j]
-    return b.reshape(nkb, 64, 8).to(dt or h16_dtype()).view(torch.int16).contiguous()
-
-
+# ----------------------------------------------------------------------------------------
+# 3-D convolutions on planar fp32 volumes (CostRegNet)
+# ----------------------------------------------------------------------------------------
 def conv3d_k3(x, weight, scale=None, shift=None, skip=None, relu=True, stride=1):
     """x [Ci,D,H,W], weight [Co,Ci,3,3,3] -> [Co,Do,Ho,Wo] with folded-BN affine, ReLU, skip (after ReLU)."""
     Ci, D, H, W = x.shape
     Co = weight.shape[0]
     if tuple(weight.shape) != (Co, Ci, 3, 3, 3):
         raise ValueError("weight must be [Co,%d,3,3,3] (got %s)" % (Ci, tuple(weight.shape)))
+    o = lambda n: (n - 1) // stride + 1
+    oshape, dev = (Co, o(D), o(H), o(W)), x.device
+
+    def args(w, wname, *dims):   # every entry point of this layer: x, weights (fp32 ones checked by name), epilogue, dims, out, stream
+        return lambda out: (_chk(x, "x", 4), _chk(w, wname) if wname else _ptr(w), _opt(scale, "scale"), _opt(shift, "shift"),
+                            _opt(skip, "skip"), int(relu)) + dims + (_chk(out, "out"), _stream())
     # C_out = 1 (the probability layer, cas_mvsnet.py:110) has its own streaming VALU kernel behind d3d_conv3d_k3: a
     # single output channel fills 1/16 of a matrix-core tile (D3D_CONV_CO1=0 sends it through the folded MFMA form)
     if stride == 1 and ((Ci in (8, 16, 32) and Co in (8, 16)) or (Ci, Co) in ((32, 32), (64, 64))) and W % 4 == 0 and _use_mfma() \
@@ -581,134 +503,45 @@ def conv3d_k3(x, weight, scale=None, shift=None, skip=None, relu=True, stride=1)
         # (tools/x3_bench.py): conv0 32 -> 8 / 16 -> 8 / 8 -> 8 at the three stage volumes 2.65 / 3.22 / 1.85 -> 2.47 / 2.84 / 1.69 ms,
         # conv2 16 -> 16 0.49 / 0.99 / 0.83 -> 0.18 / 0.43 / 0.44 ms
         wp = derived_weight(weight, "c8bf16x3", _pack_c8_bf16x3)
-        out = torch.empty((Co, D, H, W), dtype=torch.float32, device=x.device)
-        if skip is not None and skip.shape != out.shape:
-            raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-        rc = _lib.load().d3d_conv3d_k3_zs_bf16x3(_chk(x, "x", 4), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"),
-                                                 _opt(shift, "shift"), _opt(skip, "skip"), int(relu), Ci, Co, D, H, W,
-                                                 _chk(out, "out"), _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_conv3d_k3_zs_bf16x3")
-            return out
+        y = _launch("d3d_conv3d_k3_zs_bf16x3", oshape, skip, args(wp, None, Ci, Co, D, H, W), device=dev)
+        if y is not None:
+            return y
     if Co == 8 and stride == 1 and Ci % 8 == 0 and _use_mfma() and not _cfg.off("co8") \
             and conv_precision() != "h16" and 7 * D * H * W * 4 + H * W * 4 < 2 ** 31:
         # C_out = 8 (conv0 of every CostRegNet): z-streaming kernel on the fp32 vector units (same peak as the fp32 matrix
         # cores, which an 8-row GEMM half fills); weights re-laid out [Ci][ky][kx][kz][8] once per parameter version
-        wp = derived_weight(weight, "co8", lambda w: w.permute(1, 3, 4, 2, 0))
-        out = torch.empty((8, D, H, W), dtype=torch.float32, device=x.device)
-        if skip is not None and skip.shape != out.shape:
-            raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-        rc = _lib.load().d3d_conv3d_k3_co8(_chk(x, "x", 4), _chk(wp, "wpacked"), _opt(scale, "scale"), _opt(shift, "shift"),
-                                           _opt(skip, "skip"), int(relu), Ci, D, H, W, _chk(out, "out"), _stream())
-        _lib.check(rc, "d3d_conv3d_k3_co8")
-        return out
+        wp = derived_weight(weight, "co8", _pack_co8)
+        return _launch("d3d_conv3d_k3_co8", oshape, skip, args(wp, "wpacked", Ci, D, H, W), device=dev, must=True)
     if stride == 1 and Ci in (8, 16, 32) and (Co in (8, 16) or (Co == 32 and Ci == 32)) and W % 4 == 0 and _use_mfma() \
             and conv_precision() == "h16" and not _cfg.off("c8"):
         # conv0 / conv2 / conv4 of every CostRegNet with bf16 operands: z-streaming matrix-core kernel (each plane read once)
         wp = derived_weight(weight, "c8bf16", _pack_c8_bf16)
-        out = torch.empty((Co, D, H, W), dtype=torch.float32, device=x.device)
-        if skip is not None and skip.shape != out.shape:
-            raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-        rc = _lib.load().d3d_conv3d_k3_zs_h16(_chk(x, "x", 4), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"),
-                                               _opt(shift, "shift"), _opt(skip, "skip"), int(relu), Ci, Co, D, H, W,
-                                               _chk(out, "out"), _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_conv3d_k3_zs_h16")
-            return out
+        y = _launch("d3d_conv3d_k3_zs_h16", oshape, skip, args(wp, None, Ci, Co, D, H, W), device=dev)
+        if y is not None:
+            return y
     if Co == 1 and stride == 1 and Ci == 8 and W % 4 == 0 and _use_mfma() and conv_precision() != "h16" \
             and _cfg.get("D3D_CONV_C8X3") == "all":
         # fp32 mode of the probability layer (cas_mvsnet.py:110) on the k_z-folded matrix-core kernel with split operands: built
         # and tested, but SLOWER than the vector-unit kernel it would replace (0.25 / 0.59 / 0.61 -> 0.34 / 0.87 / 0.85 ms at the
         # three stage volumes: one output channel fills 3 of 16 columns), so only D3D_CONV_C8X3=all routes here
         wf = derived_weight(weight, "c8kzfoldx3", _pack_c8_kzfold_bf16x3)
-        out = torch.empty((1, D, H, W), dtype=torch.float32, device=x.device)
-        if skip is not None and skip.shape != out.shape:
-            raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-        rc = _lib.load().d3d_conv3d_k3_c1_bf16x3(_chk(x, "x", 4), ctypes.c_void_p(wf.data_ptr()), _opt(scale, "scale"),
-                                                 _opt(shift, "shift"), _opt(skip, "skip"), int(relu), Ci, D, H, W,
-                                                 _chk(out, "out"), _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_conv3d_k3_c1_bf16x3")
-            return out
+        y = _launch("d3d_conv3d_k3_c1_bf16x3", oshape, skip, args(wf, None, Ci, D, H, W), device=dev)
+        if y is not None:
+            return y
     if stride == 2 and (Ci, Co) in ((8, 16), (16, 32), (32, 64)) and ((W - 1) // 2 + 1) % 4 == 0 and _use_mfma() \
             and conv_precision() != "h16" and _cfg.get("D3D_CONV_C8X3") != "0":
         # fp32 mode of conv1 / conv3 / conv5 (cas_mvsnet.py:86,89,92): the stride-2 z-streaming kernel on three-way bf16 splits
         # (csrc/conv_s2x3.hip) instead of the vector-unit stream kernels
         wp = derived_weight(weight, "c8bf16x3", _pack_c8_bf16x3)
-        o = lambda n: (n - 1) // 2 + 1
-        out = torch.empty((Co, o(D), o(H), o(W)), dtype=torch.float32, device=x.device)
-        if skip is not None and skip.shape != out.shape:
-            raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-        rc = _lib.load().d3d_conv3d_k3s2_zs_bf16x3(_chk(x, "x", 4), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"),
-                                                   _opt(shift, "shift"), _opt(skip, "skip"), int(relu), Ci, Co, D, H, W,
-                                                   _chk(out, "out"), _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_conv3d_k3s2_zs_bf16x3")
-            dispatch_counts["conv3d_s2_x3"] += 1
-            return out
+        y = _launch("d3d_conv3d_k3s2_zs_bf16x3", oshape, skip, args(wp, None, Ci, Co, D, H, W), ("conv3d_s2_x3",), device=dev)
+        if y is not None:
+            return y
     co1 = Co == 1 and stride == 1 and Ci == 8 and not _cfg.off("co1")
     if _use_mfma() and Co <= 64 and not co1:
         y = conv_k3_mfma(x, weight, scale, shift, skip, act=1 if relu else 0, stride=stride)
         if y is not None:
             return y
-    o = lambda n: (n - 1) // stride + 1
-    out = torch.empty((Co, o(D), o(H), o(W)), dtype=torch.float32, device=x.device)
-    if skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-    rc = _lib.load().d3d_conv3d_k3(_chk(x, "x", 4), _chk(weight, "weight"), _opt(scale, "scale"),
-                                   _opt(shift, "shift"), _opt(skip, "skip"), int(relu), Ci, Co, D, H, W, stride,
-                                   _chk(out, "out"), _stream())
-    _lib.check(rc, "d3d_conv3d_k3")
-    return out
-
-
-def _pack_t2_bf16(w, dt=None):
-    """nn.ConvTranspose3d weight [Ci,Co,3,3,3] -> B operands of v_mfma_f32_16x16x32_bf16 for d3d_convtranspose3d_k3s2_zs_h16.
-    Output parity class (pz,py,px), in the order pz*4 + py*2 + px: taps (dz,dy,dx), d <= p per dimension, enumerated dz-major;
-    an even output coordinate uses kernel index 1 (d = 0), an odd one index 2 (d = 0) and 0 (d = 1).  K = (tap, ci) padded to
-    a multiple of 32, output channels padded to a multiple of 16; per class [K block][N tile][lane][8] with lane l holding
-    column l & 15 and rows 8 * (l >> 4) .. + 7 of its block.  Returned as int16 bits (bf16)."""
-    Ci, Co = w.shape[0], w.shape[1]
-    ntn = (max(Co, 16) + 15) // 16
-    kmap = {(0, 0): 1, (1, 0): 2, (1, 1): 0}
-    parts = []
-    for p in range(8):
-        pz, py, px = p >> 2, (p >> 1) & 1, p & 1
-        taps = [(dz, dy, dx) for dz in range(1 + pz) for dy in range(1 + py) for dx in range(1 + px)]
-        K = len(taps) * Ci
-        nkb = (K + 31) // 32
-        b = torch.zeros((nkb * 32, ntn * 16), dtype=torch.float32, device=w.device)
-        for t, (dz, dy, dx) in enumerate(taps):
-            b[t * Ci:(t + 1) * Ci, :Co] = w[:, :, kmap[(pz, dz)], kmap[(py, dy)], kmap[(px, dx)]]
-        # [kb][kgroup][j][nt][n] -> [kb][nt][kgroup][n][j]
-        b = b.reshape(nkb, 4, 8, ntn, 16).permute(0, 3, 1, 4, 2)
-        parts.append(b.reshape(nkb * ntn * 64, 8))
-    return torch.cat(parts).to(dt or h16_dtype()).view(torch.int16).contiguous()
-
-
-def _pack_t2_fold_bf16(w, dt=None):
-    """ConvTranspose3d weight [Ci,8,3,3,3] -> A operands of the x-folded form of d3d_convtranspose3d_k3s2_cl_h16: per output
-    parity class (pz,py), K = (taps (dz,dy,dx) with dx in {0,1}, dz-major) x ci, GEMM row r = px * 8 + channel: the even
-    column (px = 0) uses kernel column 1 of the dx = 0 taps (its dx = 1 entries are zero), the odd one column 2 (dx = 0)
-    and 0 (dx = 1).  [class][K block][lane][8], lane l = row l & 15, K rows 8 * (l >> 4) .. + 7.  int16 bits (bf16)."""
-    Ci, Co = w.shape[0], w.shape[1]
-    assert Co == 8
-    kmap = {(0, 0): 1, (1, 0): 2, (1, 1): 0}
-    parts = []
-    for c in range(4):
-        pz, py = c >> 1, c & 1
-        taps = [(dz, dy, dx) for dz in range(1 + pz) for dy in range(1 + py) for dx in range(2)]
-        K = len(taps) * Ci
-        nkb = (K + 31) // 32
-        b = torch.zeros((nkb * 32, 16), dtype=torch.float32, device=w.device)
-        for t, (dz, dy, dx) in enumerate(taps):
-            kz, ky = kmap[(pz, dz)], kmap[(py, dy)]
-            if dx == 0:
-                b[t * Ci:(t + 1) * Ci, 0:8] = w[:, :, kz, ky, 1]
-            b[t * Ci:(t + 1) * Ci, 8:16] = w[:, :, kz, ky, kmap[(1, dx)]]
-        b = b.reshape(nkb, 4, 8, 16).permute(0, 1, 3, 2)      # [kb][kgroup][row][j]
-        parts.append(b.reshape(nkb * 64, 8))
-    return torch.cat(parts).to(dt or h16_dtype()).view(torch.int16).contiguous()
+    return _launch("d3d_conv3d_k3", oshape, skip, args(weight, "weight", Ci, Co, D, H, W, stride), device=dev, must=True)
 
 
 def convtranspose3d_k3s2(x, weight, scale=None, shift=None, skip=None, relu=True):
@@ -717,56 +550,35 @@ def convtranspose3d_k3s2(x, weight, scale=None, shift=None, skip=None, relu=True
     Co = weight.shape[1]
     if tuple(weight.shape) != (Ci, Co, 3, 3, 3):
         raise ValueError("weight must be [%d,Co,3,3,3] (got %s)" % (Ci, tuple(weight.shape)))
+    oshape, dev = (Co, 2 * D, 2 * H, 2 * W), x.device
+
+    def args(w, wname, *dims):   # (as in conv3d_k3)
+        return lambda out: (_chk(x, "x", 4), _chk(w, wname) if wname else _ptr(w), _opt(scale, "scale"), _opt(shift, "shift"),
+                            _opt(skip, "skip"), int(relu)) + dims + (_chk(out, "out"), _stream())
     if (Ci, Co) in ((16, 8), (16, 16), (32, 16), (64, 32)) and _use_mfma() and conv_precision() != "h16" and _cfg.get("D3D_CONV_C8X3") != "0":
         # fp32 mode of conv11, conv9 and conv7 (cas_mvsnet.py:103, 100, 97: 16 -> 8 to the full-resolution volume, 32 -> 16, 64 -> 32): the per-parity matrix-core kernel on
         # three-way bf16 splits of both operands (fp32 accuracy, see conv3d_k3)
         wp = derived_weight(weight, "t2bf16x3", _pack_t2_bf16x3)
-        out = torch.empty((Co, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-        if skip is not None and skip.shape != out.shape:
-            raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-        rc = _lib.load().d3d_convtranspose3d_k3s2_zs_bf16x3(_chk(x, "x", 4), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"),
-                                                            _opt(shift, "shift"), _opt(skip, "skip"), int(relu), Ci, Co, D, H, W,
-                                                            _chk(out, "out"), _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_convtranspose3d_k3s2_zs_bf16x3")
-            return out
+        y = _launch("d3d_convtranspose3d_k3s2_zs_bf16x3", oshape, skip, args(wp, None, Ci, Co, D, H, W), device=dev)
+        if y is not None:
+            return y
     if Co == 8 and Ci % 8 == 0 and _use_mfma() and not _cfg.off("co8") \
             and conv_precision() != "h16" and 7 * D * H * W * 4 + H * W * 4 < 2 ** 31:
         # C_out = 8 (conv11 of every CostRegNet): z-streaming kernel on the fp32 vector units, weights [Ci][kz][ky][kx][8]
-        wp = derived_weight(weight, "coT8", lambda w: w.permute(0, 2, 3, 4, 1))
-        out = torch.empty((8, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-        if skip is not None and skip.shape != out.shape:
-            raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-        rc = _lib.load().d3d_convtranspose3d_k3s2_co8(_chk(x, "x", 4), _chk(wp, "wpacked"), _opt(scale, "scale"),
-                                                      _opt(shift, "shift"), _opt(skip, "skip"), int(relu), Ci, D, H, W,
-                                                      _chk(out, "out"), _stream())
-        _lib.check(rc, "d3d_convtranspose3d_k3s2_co8")
-        return out
+        wp = derived_weight(weight, "coT8", _pack_coT8)
+        return _launch("d3d_convtranspose3d_k3s2_co8", oshape, skip, args(wp, "wpacked", Ci, D, H, W), device=dev, must=True)
     if (Ci, Co) in ((16, 8), (16, 16), (32, 16), (64, 32)) and _use_mfma() and conv_precision() == "h16" \
             and not _cfg.off("t2"):
         # decoder layers of CostRegNet with bf16 operands: eight per-parity dense convolutions on the matrix cores, z-streaming
         wp = derived_weight(weight, "t2bf16", _pack_t2_bf16)
-        out = torch.empty((Co, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-        if skip is not None and skip.shape != out.shape:
-            raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-        rc = _lib.load().d3d_convtranspose3d_k3s2_zs_h16(_chk(x, "x", 4), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"),
-                                                          _opt(shift, "shift"), _opt(skip, "skip"), int(relu), Ci, Co, D, H, W,
-                                                          _chk(out, "out"), _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_convtranspose3d_k3s2_zs_h16")
-            return out
+        y = _launch("d3d_convtranspose3d_k3s2_zs_h16", oshape, skip, args(wp, None, Ci, Co, D, H, W), device=dev)
+        if y is not None:
+            return y
     if _use_mfma() and Co <= 64:
         y = convtranspose_k3s2_mfma(x, weight, scale, shift, skip, act=1 if relu else 0)
         if y is not None:
             return y
-    out = torch.empty((Co, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-    if skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape %s != output shape %s" % (tuple(skip.shape), tuple(out.shape)))
-    rc = _lib.load().d3d_convtranspose3d_k3s2(_chk(x, "x", 4), _chk(weight, "weight"), _opt(scale, "scale"),
-                                              _opt(shift, "shift"), _opt(skip, "skip"), int(relu), Ci, Co, D, H, W,
-                                              _chk(out, "out"), _stream())
-    _lib.check(rc, "d3d_convtranspose3d_k3s2")
-    return out
+    return _launch("d3d_convtranspose3d_k3s2", oshape, skip, args(weight, "weight", Ci, Co, D, H, W), device=dev, must=True)
 
 
 # ----------------------------------------------------------------------------------------
@@ -781,7 +593,7 @@ def _chk_cl(t, name, cl8=False):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == h16_dtype() and t.is_contiguous()
             and (t.dim() == 4 or (cl8 and t.dim() == 5 and t.shape[4] == 8))):
         raise TypeError("%s must be a contiguous CUDA 16-bit (ops.h16_dtype()) tensor [D,H,W,C]%s" % (name, " or [D,C/8,H,W,8]" if cl8 else ""))
-    return ctypes.c_void_p(t.data_ptr())
+    return _ptr(t)
 
 
 def to_cl(x):
@@ -831,29 +643,23 @@ def conv3d_k3_cl(x, weight, scale=None, shift=None, skip=None, relu=True, stride
     fmt = 2 if cl8 else int(in_cl)
     sp = None if skip is None else (_chk_cl(skip, "skip") if out_cl else _chk(skip, "skip"))
     wp = derived_weight(weight, "c8bf16", _pack_c8_bf16)
-    wptr = ctypes.c_void_p(wp.data_ptr())
     out = torch.empty(oshape, dtype=h16_dtype() if out_cl else torch.float32, device=x.device)
-    optr = ctypes.c_void_p(out.data_ptr())
-    rc = _lib.ERR_UNSUPPORTED
+    ep = lambda: (_opt(scale, "scale"), _opt(shift, "shift"), sp, int(relu))
     if stride == 1 and Co == 1 and not out_cl and not _cfg.off("kzfold"):
         # the probability layer: k_z folded into the columns of one operand tile
         wf = derived_weight(weight, "c8kzfold", _pack_c8_kzfold_bf16)
-        rc = _lib.load().d3d_conv3d_k3_c1_cl_h16(xp, fmt, ctypes.c_void_p(wf.data_ptr()), _opt(scale, "scale"),
-                                                  _opt(shift, "shift"), sp, int(relu), Ci, D, H, W, optr, _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_conv3d_k3_c1_cl_h16")
-            dispatch_counts["conv3d_cl"] += 1
-            return out
+        y = _launch("d3d_conv3d_k3_c1_cl_h16", out, None, lambda out: (xp, fmt, _ptr(wf)) + ep() + (Ci, D, H, W, _ptr(out), _stream()),
+                    ("conv3d_cl",))
+        if y is not None:
+            return y
+    y, counts = None, ("conv3d_cl8_in" if cl8 else "conv3d_cl",)
     if stride == 1:
-        rc = _lib.load().d3d_conv3d_k3_cl_h16(xp, fmt, wptr, _opt(scale, "scale"), _opt(shift, "shift"), sp, int(relu),
-                                               Ci, Co, D, H, W, optr, int(out_cl), _stream())
+        y = _launch("d3d_conv3d_k3_cl_h16", out, None,
+                    lambda out: (xp, fmt, _ptr(wp)) + ep() + (Ci, Co, D, H, W, _ptr(out), int(out_cl), _stream()), counts)
     elif stride == 2 and in_cl and out_cl:
-        rc = _lib.load().d3d_conv3d_k3s2_cl_h16(xp, wptr, _opt(scale, "scale"), _opt(shift, "shift"), sp, int(relu), Ci, Co,
-                                                 D, H, W, optr, _stream())
-    if rc != _lib.ERR_UNSUPPORTED:
-        _lib.check(rc, "d3d_conv3d_k3_cl_h16" if stride == 1 else "d3d_conv3d_k3s2_cl_h16")
-        dispatch_counts["conv3d_cl8_in" if cl8 else "conv3d_cl"] += 1
-        return out
+        y = _launch("d3d_conv3d_k3s2_cl_h16", out, None, lambda out: (xp, _ptr(wp)) + ep() + (Ci, Co, D, H, W, _ptr(out), _stream()), counts)
+    if y is not None:
+        return y
     dispatch_counts["conv3d_cl_fallback"] += 1
     saved = _cfg.state.conv_precision
     _cfg.state.conv_precision = "h16"
@@ -876,15 +682,12 @@ def convtranspose3d_k3s2_cl(x, weight, scale=None, shift=None, skip=None, relu=T
     if (Ci, Co) in ((16, 8), (16, 16), (32, 16), (64, 32)):
         fold = (Ci, Co) == (16, 8) and not _cfg.off("t2fold")   # conv11: both column parities in one GEMM
         wp = derived_weight(weight, "t2foldbf16", _pack_t2_fold_bf16) if fold else derived_weight(weight, "t2bf16", _pack_t2_bf16)
-        out = torch.empty(oshape, dtype=h16_dtype(), device=x.device)
-        rc = _lib.load().d3d_convtranspose3d_k3s2_cl_h16(_chk_cl(x, "x"), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"),
-                                                          _opt(shift, "shift"), None if skip is None else _chk_cl(skip, "skip"),
-                                                          int(relu), Ci, Co, D, H, W, ctypes.c_void_p(out.data_ptr()),
-                                                          2 if fold else 1, _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_convtranspose3d_k3s2_cl_h16")
-            dispatch_counts["convtranspose3d_cl"] += 1
-            return out
+        y = _launch("d3d_convtranspose3d_k3s2_cl_h16", torch.empty(oshape, dtype=h16_dtype(), device=x.device), None,
+                    lambda out: (_chk_cl(x, "x"), _ptr(wp), _opt(scale, "scale"), _opt(shift, "shift"),
+                                 None if skip is None else _chk_cl(skip, "skip"), int(relu), Ci, Co, D, H, W, _ptr(out),
+                                 2 if fold else 1, _stream()), ("convtranspose3d_cl",))
+        if y is not None:
+            return y
     dispatch_counts["conv3d_cl_fallback"] += 1
     saved = _cfg.state.conv_precision
     _cfg.state.conv_precision = "h16"
@@ -909,18 +712,15 @@ def convtranspose3d_prob_cl(x, weight, scale, shift, skip, prob_weight, prob_bia
         raise ValueError("skip %s %s does not match the output %s" % (skip.dtype, tuple(skip.shape), oshape + (8,)))
     wt = derived_weight(weight, "t2foldbf16", _pack_t2_fold_bf16)
     wp = derived_weight(prob_weight, "c8kzfold", _pack_c8_kzfold_bf16)
-    out = torch.empty(oshape, dtype=torch.float32, device=x.device)
-    rc = _lib.load().d3d_convtranspose3d_prob_cl_h16(
-        _chk_cl(x, "x"), ctypes.c_void_p(wt.data_ptr()), _opt(scale, "scale"), _opt(shift, "shift"),
-        None if skip is None else _chk_cl(skip, "skip"), int(relu), ctypes.c_void_p(wp.data_ptr()), _opt(prob_bias, "prob_bias"),
-        D, H, W, ctypes.c_void_p(out.data_ptr()), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_convtranspose3d_prob_cl_h16")
-    dispatch_counts["convtranspose3d_prob_cl"] += 1
-    return out
+    return _launch("d3d_convtranspose3d_prob_cl_h16", oshape, None,
+                   lambda out: (_chk_cl(x, "x"), _ptr(wt), _opt(scale, "scale"), _opt(shift, "shift"),
+                                None if skip is None else _chk_cl(skip, "skip"), int(relu), _ptr(wp), _opt(prob_bias, "prob_bias"),
+                                D, H, W, _ptr(out), _stream()), ("convtranspose3d_prob_cl",), device=x.device)
 
 
+# ----------------------------------------------------------------------------------------
+# 2-D convolutions (feature pyramids, slice regularisers, the pair-visibility UNet)
+# ----------------------------------------------------------------------------------------
 def conv1x1_upskip(x, weight, bias, coarse):
     """conv1x1(x) + bias + nearest-x2 upsampling of `coarse` (FPN lateral, module.py:736-747) in one pass.
     x [Ci,H,W], weight [Co,Ci,1,1], coarse [Co,H/2,W/2].  Returns None for shapes the kernel does not take."""
@@ -929,7 +729,7 @@ def conv1x1_upskip(x, weight, bias, coarse):
     if (Ci, Co) not in ((8, 32), (16, 32)) or H % 2 or W % 2 or tuple(coarse.shape) != (Co, H // 2, W // 2) \
             or tuple(weight.shape) != (Co, Ci, 1, 1) or _cfg.off("upskip"):
         return None
-    wp = derived_weight(weight, "c11", lambda w: w.reshape(Co, Ci).t())
+    wp = derived_weight(weight, "c11", _pack_c11)
     out = torch.empty((Co, H, W), dtype=torch.float32, device=x.device)
     rc = _lib.load().d3d_conv1x1_upskip(_chk(x, "x", 3), Ci, _chk(wp, "wpacked"), _opt(bias, "bias"), _chk(coarse, "coarse", 3),
                                         Co, H, W, _chk(out, "out"), _stream())
@@ -951,46 +751,11 @@ def conv2d_stream(x, weight, scale, shift, skip, act, x2=None, aux1=None, ep_spl
             or 8 * H * W * 4 >= 2 ** 31 or _cfg.off("conv2d_stream")
             or (x2 is not None and Ci0 % 8 != 0) or tuple(weight.shape) != (Co, Ci0 + Ci1, 3, 3)):
         return None
-
-    def pack(w):
-        ci = Ci0 + Ci1
-        wp = w.new_zeros(((ci + 7) // 8 * 8, 3, 3, Co))
-        wp[:ci] = w.permute(1, 2, 3, 0)
-        return wp
-    wp = derived_weight(weight, "c2s", pack)
-    out = torch.empty((Co, H, W), dtype=torch.float32, device=x.device)
-    if act <= 1 and skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape mismatch")
-    rc = _lib.load().d3d_conv2d_k3_stream(_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, _chk(wp, "wpacked"),
-                                          _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"), _opt(aux1, "aux1"),
-                                          int(ep_split), int(act), Co, H, W, _chk(out, "out"), _stream())
-    _lib.check(rc, "d3d_conv2d_k3_stream")
-    return out  # pixels from which the vector-unit streaming form of conv2d_k3 is used
-
-
-def _pack_z2_bf16(w, dt=None):
-    """nn.Conv2d weight [Co,Ci,3,3] -> B operands of v_mfma_f32_16x16x32_bf16 for d3d_conv2d_k3_zs_h16: K = (k_y, k_x, c_in)
-    padded to a multiple of 32, output channels to a multiple of 16; [K block][N tile][lane][8], lane l = column l & 15,
-    K rows 8 * (l >> 4) .. + 7 of its block.  int16 bits (bf16)."""
-    Co, Ci = w.shape[0], w.shape[1]
-    K = w.shape[2] * w.shape[3] * Ci                                   # (3 x 3; 5 x 5 for d3d_conv2d_k5s2_zs_bf16x3)
-    nkb = (K + 31) // 32
-    ntn = (max(Co, 16) + 15) // 16
-    b = torch.zeros((nkb * 32, ntn * 16), dtype=torch.float32, device=w.device)
-    b[:K, :Co] = w.permute(2, 3, 1, 0).reshape(K, Co)                  # [ky, kx, ci, co]
-    b = b.reshape(nkb, 4, 8, ntn, 16).permute(0, 3, 1, 4, 2)           # [kb][ntile][kgroup][n][j]
-    return b.reshape(nkb, ntn, 64, 8).to(dt or h16_dtype()).view(torch.int16).contiguous()
-
-
-def _pack_z2_f32(w):
-    """nn.Conv2d weight [Co,Ci,3,3] -> fp32 B operands of v_mfma_f32_16x16x4_f32 for d3d_conv2d_k3_zs_f32: K = (k_y, k_x, c_in)
-    in blocks of 4, output channels padded to a multiple of 16; [K block][N tile][lane], lane l = column l & 15, K row l >> 4."""
-    Co, Ci = w.shape[0], w.shape[1]
-    K = 9 * Ci
-    ntn = (max(Co, 16) + 15) // 16
-    b = torch.zeros((K, ntn * 16), dtype=torch.float32, device=w.device)
-    b[:, :Co] = w.permute(2, 3, 1, 0).reshape(K, Co)
-    return b.reshape(K // 4, 4, ntn, 16).permute(0, 2, 1, 3).reshape(K // 4, ntn, 64).contiguous()
+    wp = derived_weight(weight, "c2s", _pack_c2s)
+    return _launch("d3d_conv2d_k3_stream", (Co, H, W), skip if act <= 1 else None,   # (act 2 | 3: `skip` is the GRU state)
+                   lambda out: (_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, _chk(wp, "wpacked"), _opt(scale, "scale"), _opt(shift, "shift"),
+                                _opt(skip, "skip"), _opt(aux1, "aux1"), int(ep_split), int(act), Co, H, W, _chk(out, "out"), _stream()),
+                   device=x.device, must=True)
 
 
 def avgpool_4_8(x):
@@ -1016,13 +781,9 @@ def conv1x1_context(f, weight, a, b):
     if (tuple(weight.shape) != (Co, Ci) or Ci != Co or Ci not in (8, 16, 32) or W % 4 or a.shape[0] != Co or b.shape[0] != Co
             or 3 * a.shape[2] > W or 3 * b.shape[2] > W or _cfg.off("context_fused")):
         return None
-    out = torch.empty((Co, H, W), dtype=torch.float32, device=f.device)
-    rc = _lib.load().d3d_conv1x1_context(_chk(f, "f", 3), Ci, _chk(weight, "weight"), _chk(a, "a", 3), a.shape[1], a.shape[2],
-                                         _chk(b, "b", 3), b.shape[1], b.shape[2], Co, H, W, _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_conv1x1_context")
-    return out
+    return _launch("d3d_conv1x1_context", (Co, H, W), None,
+                   lambda out: (_chk(f, "f", 3), Ci, _chk(weight, "weight"), _chk(a, "a", 3), a.shape[1], a.shape[2],
+                                _chk(b, "b", 3), b.shape[1], b.shape[2], Co, H, W, _chk(out, "out"), _stream()), device=f.device)
 
 
 def conv3x3_bias_border_(out, taps):
@@ -1036,79 +797,6 @@ def conv3x3_bias_border_(out, taps):
     return out
 
 
-def _split3_bf16(w):
-    """fp32 tensor -> its exact three-way bf16 split (hi, mid, lo as fp32 tensors; hi + mid + lo == w in fp32)."""
-    w = w.to(torch.float32)
-    hi = w.to(torch.bfloat16).to(torch.float32)
-    mid = (w - hi).to(torch.bfloat16).to(torch.float32)
-    lo = (w - hi - mid).to(torch.bfloat16).to(torch.float32)
-    return hi, mid, lo
-
-
-def _pack_z2_bf16x3(w):
-    """nn.Conv2d weight [Co,Ci,3,3] -> the B operands of d3d_conv2d_k3_zs_bf16x3: [hi | mid | lo] x _pack_z2_bf16."""
-    return torch.stack([_pack_z2_bf16(part, torch.bfloat16) for part in _split3_bf16(w)]).contiguous()
-
-
-def _pack_t2d_bf16x3(w):
-    """nn.ConvTranspose2d weight [Ci,Co,3,3] -> the B operands of d3d_convtranspose2d_k3s2_zs_bf16x3: [hi | mid | lo] x _pack_t2d_bf16."""
-    return torch.stack([_pack_t2d_bf16(part, torch.bfloat16) for part in _split3_bf16(w)]).contiguous()
-
-
-def _pack_t2d_k4_bf16(w, dt=None):
-    """nn.ConvTranspose2d weight [Ci,Co,4,4] (stride 2, padding 1) -> B operands of the k = 4 transposed tile kernel: per output
-    parity class (py,px), order py*2 + px, taps (dy,dx) in {0,1}^2 dy-major; output 2i + p reads input i - 1 + p + d through
-    kernel index 3 - p - 2d.  K = (tap, ci), 16 output columns; [K block][lane][8] (bf16 bits)."""
-    Ci, Co = w.shape[0], w.shape[1]
-    parts = []
-    for c in range(4):
-        py, px = c >> 1, c & 1
-        K = 4 * Ci
-        nkb = (K + 31) // 32
-        b = torch.zeros((nkb * 32, 16), dtype=torch.float32, device=w.device)
-        for t, (dy, dx) in enumerate([(0, 0), (0, 1), (1, 0), (1, 1)]):
-            b[t * Ci:(t + 1) * Ci, :Co] = w[:, :, 3 - py - 2 * dy, 3 - px - 2 * dx]
-        b = b.reshape(nkb, 4, 8, 16).permute(0, 1, 3, 2)                 # [kb][kgroup][n][j]
-        parts.append(b.reshape(nkb * 64, 8))
-    return torch.cat(parts).to(dt or h16_dtype()).view(torch.int16).contiguous()
-
-
-def _pack_t2d_k4fold_bf16(w, dt=None):
-    """The k = 4 transposed weight [Ci,Co<=8,4,4] with both column parities in one 16-column tile: per row parity py, K =
-    (dy in {0,1}, patch column dxx in {0,1,2}, ci); columns 0..7 = even output column (dxx = dx), 8..15 = odd one (dxx = 1 + dx)."""
-    Ci, Co = w.shape[0], w.shape[1]
-    parts = []
-    for py in range(2):
-        nkb = (6 * Ci + 31) // 32
-        b = torch.zeros((nkb * 32, 16), dtype=torch.float32, device=w.device)
-        for dy in range(2):
-            for dxx in range(3):
-                t = dy * 3 + dxx
-                for px in range(2):
-                    dx = dxx - px
-                    if dx in (0, 1):
-                        b[t * Ci:(t + 1) * Ci, px * 8:px * 8 + Co] = w[:, :, 3 - py - 2 * dy, 3 - px - 2 * dx]
-        b = b.reshape(nkb, 4, 8, 16).permute(0, 1, 3, 2)
-        parts.append(b.reshape(nkb * 64, 8))
-    return torch.cat(parts).to(dt or h16_dtype()).view(torch.int16).contiguous()
-
-
-def _pack_t2d_k4_bf16x3(w):
-    """[hi | mid | lo] x the k = 4 packing d3d_convtranspose2d_k4s2_zs_bf16x3 takes: column-folded for C_out <= 8."""
-    pack = _pack_t2d_k4fold_bf16 if w.shape[1] <= 8 else _pack_t2d_k4_bf16
-    return torch.stack([pack(part, torch.bfloat16) for part in _split3_bf16(w)]).contiguous()
-
-
-def upsampled_conv_weight(w3):
-    """Conv2d weight [Co,Ci,3,3] (padding 1) -> the ConvTranspose2d weight [Ci,Co,4,4] (stride 2, padding 1) with
-    conv_transpose2d(f, .) == conv2d(nearest_x2(f), w3): the three taps of an output pixel along an axis fall on two cells
-    of f, and the weights of taps sharing a cell add (kernel index 3: tap 0; 1: taps 1 + 2; 0: tap 2; 2: taps 0 + 1)."""
-    w = w3.detach().to(torch.float64)
-    rows = torch.stack([w[:, :, 2], w[:, :, 1] + w[:, :, 2], w[:, :, 0] + w[:, :, 1], w[:, :, 0]], 2)          # [Co,Ci,4(ky),3]
-    full = torch.stack([rows[..., 2], rows[..., 1] + rows[..., 2], rows[..., 0] + rows[..., 1], rows[..., 0]], 3)   # [Co,Ci,4,4]
-    return full.permute(1, 0, 2, 3).to(torch.float32).contiguous()
-
-
 def convtranspose2d_k4_zs(x, weight, scale=None, shift=None, skip=None, act=0, skip_after_act=False):
     """ConvTranspose2d(k 4, stride 2, pad 1): x [Ci,H,W], weight [Ci,Co,4,4] -> [Co,2H,2W] on the transposed tile kernel with
     split operands (fp32 accuracy; d3d_convtranspose2d_k4s2_zs_bf16x3); None for shapes it does not take."""
@@ -1118,16 +806,9 @@ def convtranspose2d_k4_zs(x, weight, scale=None, shift=None, skip=None, act=0, s
             or _cfg.off("conv2d_zs"):
         return None
     wp = derived_weight(weight, "t2dk4x3", _pack_t2d_k4_bf16x3)
-    out = torch.empty((Co, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-    if skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape mismatch")
-    rc = _lib.load().d3d_convtranspose2d_k4s2_zs_bf16x3(
-        _chk(x, "x", 3), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"), int(act),
-        int(bool(skip_after_act)), Ci, Co, H, W, _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_convtranspose2d_k4s2_zs_bf16x3")
-    return out
+    return _launch("d3d_convtranspose2d_k4s2_zs_bf16x3", (Co, 2 * H, 2 * W), skip,
+                   lambda out: (_chk(x, "x", 3), _ptr(wp), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"), int(act),
+                                int(bool(skip_after_act)), Ci, Co, H, W, _chk(out, "out"), _stream()), device=x.device)
 
 
 def _z2_fp32_entry():
@@ -1155,19 +836,16 @@ def conv2d_zs(x, weight, scale=None, shift=None, skip=None, act=0, x2=None, aux1
         return None
     if tuple(weight.shape) != (Co, Ci0 + Ci1, 3, 3):
         raise ValueError("weight must be [Co,%d,3,3] (got %s)" % (Ci0 + Ci1, tuple(weight.shape)))
-    lib = _lib.load()
     if bf16 and gn is not None and aux1 is None and Ci in (16, 24, 32, 40) and shift is not None:
         ga = _gn_args(gn, Co, act, scale, skip, x.device)
         if ga is not None:   # the layer and the GroupNorm statistics of its output in one launch
             wp = derived_weight(weight, "z2bf16", _pack_z2_bf16)
-            out = torch.empty((Co, H, W), dtype=torch.float32, device=x.device)
-            rc = lib.d3d_conv2d_k3_zs_h16_gn(_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, ctypes.c_void_p(wp.data_ptr()), _chk(shift, "shift"),
-                                              Co, H, W, _chk(out, "out"), ctypes.c_void_p(ga[0].data_ptr()), int(ga[1]), _stream())
-            if rc != _lib.ERR_UNSUPPORTED:
-                _lib.check(rc, "d3d_conv2d_k3_zs_h16_gn")
-                dispatch_counts["conv2d_tile"] += 1
-                dispatch_counts["conv2d_gn_fused"] += 1
-                return out
+            y = _launch("d3d_conv2d_k3_zs_h16_gn", (Co, H, W), None,
+                        lambda out: (_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, _ptr(wp), _chk(shift, "shift"),
+                                     Co, H, W, _chk(out, "out"), _ptr(ga[0]), int(ga[1]), _stream()),
+                        ("conv2d_tile", "conv2d_gn_fused"), device=x.device)
+            if y is not None:
+                return y
             gn.slot = None   # (not taken: nothing was launched, the slot stays zero for the next request of this lap)
             _gn_arenas[(x.device.index, torch.cuda.current_stream(x.device).cuda_stream)][1] -= 1
     if bf16:
@@ -1176,15 +854,11 @@ def conv2d_zs(x, weight, scale=None, shift=None, skip=None, act=0, x2=None, aux1
         name, wp = "d3d_conv2d_k3_zs_bf16x3", derived_weight(weight, "z2bf16x3", _pack_z2_bf16x3)
     else:
         name, wp = "d3d_conv2d_k3_zs_f32", derived_weight(weight, "z2f32", _pack_z2_f32)
-    out = torch.empty((Co, H, W), dtype=torch.float32, device=x.device)
-    rc = getattr(lib, name)(_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"),
-                            _opt(shift, "shift"), _opt(skip, "skip"), _opt(aux1, "aux1"), int(act), int(ep_split),
-                            int(bool(skip_after_act)), Co, H, W, _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, name)
-    dispatch_counts["conv2d_tile"] += 1
-    return out
+    # (no shape check of `skip` here: with act 2 | 3 it is the GRU state, not a tensor of the output's shape)
+    return _launch(name, (Co, H, W), None,
+                   lambda out: (_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, _ptr(wp), _opt(scale, "scale"),
+                                _opt(shift, "shift"), _opt(skip, "skip"), _opt(aux1, "aux1"), int(act), int(ep_split),
+                                int(bool(skip_after_act)), Co, H, W, _chk(out, "out"), _stream()), ("conv2d_tile",), device=x.device)
 
 
 def conv2d_k3_pair3(x, w0, scale0, shift0, act0, w1, scale1, shift1, act1):
@@ -1199,29 +873,17 @@ def conv2d_k3_pair3(x, w0, scale0, shift0, act0, w1, scale1, shift1, act1):
     if tuple(w0.shape) != (8, 3, 3, 3) or tuple(w1.shape) != (8, 8, 3, 3) or W % 4 or H * W < _CONV2D_STREAM_MIN \
             or 8 * H * W * 4 >= 2 ** 31 or act0 not in (0, 1) or act1 not in (0, 1):
         return None
-
-    def pack0(w):
-        wp = w.new_zeros((8, 3, 3, 8))
-        wp[:3] = w.permute(1, 2, 3, 0)
-        return wp
-    wp0 = derived_weight(w0, "c2s", pack0)   # (the packing of conv2d_stream: same key, same tensor)
+    wp0 = derived_weight(w0, "c2s", _pack_c2s)   # (the packing of conv2d_stream: same key, same tensor)
     wp1 = derived_weight(w1, "z2bf16x3", _pack_z2_bf16x3)
-    out = torch.empty((8, H, W), dtype=torch.float32, device=x.device)
-    rc = _lib.load().d3d_conv2d_k3_pair3_bf16x3(_chk(x, "x", 3), _chk(wp0, "w0packed"), _opt(scale0, "scale0"), _opt(shift0, "shift0"),
-                                                int(act0), ctypes.c_void_p(wp1.data_ptr()), _opt(scale1, "scale1"),
-                                                _opt(shift1, "shift1"), int(act1), 8, H, W, _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_conv2d_k3_pair3_bf16x3")
-    dispatch_counts["conv2d_pair3"] += 1
-    return out
+    return _launch("d3d_conv2d_k3_pair3_bf16x3", (8, H, W), None,
+                   lambda out: (_chk(x, "x", 3), _chk(wp0, "w0packed"), _opt(scale0, "scale0"), _opt(shift0, "shift0"),
+                                int(act0), _ptr(wp1), _opt(scale1, "scale1"), _opt(shift1, "shift1"), int(act1), 8, H, W,
+                                _chk(out, "out"), _stream()), ("conv2d_pair3",), device=x.device)
 
 
 # In the default fp32 precision the tile kernels serve the slice regularisers only (the feature pyramids keep their tuned
 # vector-unit kernels: a FeatureNet forward is 2.12 ms on those, 2.19 ms on the fp32 tile kernel): the regulariser
 # modules switch them on around their forward.
-
-
 class slice_tile_kernels:
     """Context manager: stride-2 / transposed 2-D layers inside may use the fp32 tile kernels."""
 
@@ -1248,20 +910,14 @@ def conv2d_s2_zs(x, weight, scale=None, shift=None, skip=None, act=0, skip_after
     if tuple(weight.shape) != (Co, Ci, 3, 3):
         raise ValueError("weight must be [Co,%d,3,3] (got %s)" % (Ci, tuple(weight.shape)))
     if bf16:
-        fn, wp = _lib.load().d3d_conv2d_k3s2_zs_h16, derived_weight(weight, "z2bf16", _pack_z2_bf16)
+        name, wp = "d3d_conv2d_k3s2_zs_h16", derived_weight(weight, "z2bf16", _pack_z2_bf16)
     elif x3:
-        fn, wp = _lib.load().d3d_conv2d_k3s2_zs_bf16x3, derived_weight(weight, "z2bf16x3", _pack_z2_bf16x3)
+        name, wp = "d3d_conv2d_k3s2_zs_bf16x3", derived_weight(weight, "z2bf16x3", _pack_z2_bf16x3)
     else:
-        fn, wp = _lib.load().d3d_conv2d_k3s2_zs_f32, derived_weight(weight, "z2f32", _pack_z2_f32)
-    out = torch.empty((Co, Ho, Wo), dtype=torch.float32, device=x.device)
-    if skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape mismatch")
-    rc = fn(_chk(x, "x", 3), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"),
-            int(act), int(bool(skip_after_act)), Ci, Co, H, W, _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_conv2d_k3s2_zs")
-    return out
+        name, wp = "d3d_conv2d_k3s2_zs_f32", derived_weight(weight, "z2f32", _pack_z2_f32)
+    return _launch(name, (Co, Ho, Wo), skip,
+                   lambda out: (_chk(x, "x", 3), _ptr(wp), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"),
+                                int(act), int(bool(skip_after_act)), Ci, Co, H, W, _chk(out, "out"), _stream()), device=x.device)
 
 
 def conv2d_s2_zs_batched(x, weight, act=1):
@@ -1279,51 +935,9 @@ def conv2d_s2_zs_batched(x, weight, act=1):
     if tuple(weight.shape) != (Co, Ci, 3, 3):
         raise ValueError("weight must be [Co,%d,3,3] (got %s)" % (Ci, tuple(weight.shape)))
     wp = derived_weight(weight, "z2bf16", _pack_z2_bf16)
-    out = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=x.device)
-    rc = _lib.load().d3d_conv2d_k3s2_zs_h16_batched(_chk(x, "x", 4), ctypes.c_void_p(wp.data_ptr()), None, None, int(act), Ci, Co, H, W, B,
-                                                     Ci * H * W, Co * Ho * Wo, _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_conv2d_k3s2_zs_h16_batched")
-    dispatch_counts["conv2d_s2_batched"] += 1
-    return out
-
-
-def _pack_t2d_bf16(w, dt=None):
-    """nn.ConvTranspose2d weight [Ci,Co,3,3] -> B operands for d3d_convtranspose2d_k3s2_zs_h16: per output parity class
-    (py,px), order py*2 + px, taps (dy,dx) with d <= p per dimension, dy-major; an even output coordinate uses kernel index 1
-    (d = 0), an odd one index 2 (d = 0) and 0 (d = 1).  K = (tap, ci) padded to 32, 16 output columns; [K block][lane][8]."""
-    Ci, Co = w.shape[0], w.shape[1]
-    kmap = {(0, 0): 1, (1, 0): 2, (1, 1): 0}
-    parts = []
-    for c in range(4):
-        py, px = c >> 1, c & 1
-        taps = [(dy, dx) for dy in range(1 + py) for dx in range(1 + px)]
-        K = len(taps) * Ci
-        nkb = (K + 31) // 32
-        b = torch.zeros((nkb * 32, 16), dtype=torch.float32, device=w.device)
-        for t, (dy, dx) in enumerate(taps):
-            b[t * Ci:(t + 1) * Ci, :Co] = w[:, :, kmap[(py, dy)], kmap[(px, dx)]]
-        b = b.reshape(nkb, 4, 8, 16).permute(0, 1, 3, 2)                 # [kb][kgroup][n][j]
-        parts.append(b.reshape(nkb * 64, 8))
-    return torch.cat(parts).to(dt or h16_dtype()).view(torch.int16).contiguous()
-
-
-def _pack_t2d_f32(w):
-    """_pack_t2d_bf16 in fp32 for d3d_convtranspose2d_k3s2_zs_f32: per parity class, K = (tap, ci) in blocks of 4, [K block][lane]
-    with lane l = column l & 15, K row l >> 4."""
-    Ci, Co = w.shape[0], w.shape[1]
-    kmap = {(0, 0): 1, (1, 0): 2, (1, 1): 0}
-    parts = []
-    for c in range(4):
-        py, px = c >> 1, c & 1
-        taps = [(dy, dx) for dy in range(1 + py) for dx in range(1 + px)]
-        K = len(taps) * Ci
-        b = torch.zeros((K, 16), dtype=torch.float32, device=w.device)
-        for t, (dy, dx) in enumerate(taps):
-            b[t * Ci:(t + 1) * Ci, :Co] = w[:, :, kmap[(py, dy)], kmap[(px, dx)]]
-        parts.append(b.reshape(K // 4, 64))
-    return torch.cat(parts).contiguous()
+    return _launch("d3d_conv2d_k3s2_zs_h16_batched", (B, Co, Ho, Wo), None,
+                   lambda out: (_chk(x, "x", 4), _ptr(wp), None, None, int(act), Ci, Co, H, W, B,
+                                Ci * H * W, Co * Ho * Wo, _chk(out, "out"), _stream()), ("conv2d_s2_batched",), device=x.device)
 
 
 def convtranspose2d_zs(x, weight, scale=None, shift=None, skip=None, act=0, skip_after_act=False):
@@ -1336,21 +950,15 @@ def convtranspose2d_zs(x, weight, scale=None, shift=None, skip=None, act=0, skip
     if tuple(weight.shape) != (Ci, Co, 3, 3):
         raise ValueError("weight must be [%d,Co,3,3] (got %s)" % (Ci, tuple(weight.shape)))
     if conv_precision() == "h16":
-        fn, wp = _lib.load().d3d_convtranspose2d_k3s2_zs_h16, derived_weight(weight, "t2dbf16", _pack_t2d_bf16)
+        name, wp = "d3d_convtranspose2d_k3s2_zs_h16", derived_weight(weight, "t2dbf16", _pack_t2d_bf16)
     elif _z2_fp32_entry() == "x3":
-        fn, wp = _lib.load().d3d_convtranspose2d_k3s2_zs_bf16x3, derived_weight(weight, "t2dbf16x3", _pack_t2d_bf16x3)
+        name, wp = "d3d_convtranspose2d_k3s2_zs_bf16x3", derived_weight(weight, "t2dbf16x3", _pack_t2d_bf16x3)
     else:
-        fn, wp = _lib.load().d3d_convtranspose2d_k3s2_zs_f32, derived_weight(weight, "t2df32", _pack_t2d_f32)
-    out = torch.empty((Co, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-    if skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape mismatch")
-    rc = fn(_chk(x, "x", 3), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"),
-            int(act), int(bool(skip_after_act)), Ci, Co, H, W, _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_convtranspose2d_k3s2_zs")
-    dispatch_counts["convtranspose2d_tile"] += 1
-    return out
+        name, wp = "d3d_convtranspose2d_k3s2_zs_f32", derived_weight(weight, "t2df32", _pack_t2d_f32)
+    return _launch(name, (Co, 2 * H, 2 * W), skip,
+                   lambda out: (_chk(x, "x", 3), _ptr(wp), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"),
+                                int(act), int(bool(skip_after_act)), Ci, Co, H, W, _chk(out, "out"), _stream()),
+                   ("convtranspose2d_tile",), device=x.device)
 
 
 def conv2d_wide(x, weight, scale=None, shift=None, skip=None, act=0, x2=None, gn=None):
@@ -1367,24 +975,20 @@ def conv2d_wide(x, weight, scale=None, shift=None, skip=None, act=0, x2=None, gn
     out = torch.empty((Co, H, W), dtype=torch.float32, device=x.device)
     ga = _gn_args(gn, Co, act, scale, skip, x.device) if shift is not None else None
     if ga is not None:   # the layer and the GroupNorm statistics of its output in one launch
-        rc = _lib.load().d3d_conv2d_k3_wide_h16_gn(_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, ctypes.c_void_p(wp.data_ptr()),
-                                                    _chk(shift, "shift"), Co, H, W, _chk(out, "out"), ctypes.c_void_p(ga[0].data_ptr()),
-                                                    int(ga[1]), _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_conv2d_k3_wide_h16_gn")
-            dispatch_counts["conv2d_wide"] += 1
-            dispatch_counts["conv2d_gn_fused"] += 1
-            return out
+        y = _launch("d3d_conv2d_k3_wide_h16_gn", out, None,
+                    lambda out: (_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, _ptr(wp), _chk(shift, "shift"), Co, H, W, _chk(out, "out"),
+                                 _ptr(ga[0]), int(ga[1]), _stream()), ("conv2d_wide", "conv2d_gn_fused"))
+        if y is not None:
+            return y
         gn.slot = None
         _gn_arenas[(x.device.index, torch.cuda.current_stream(x.device).cuda_stream)][1] -= 1
-    rc = _lib.load().d3d_conv2d_k3_wide_h16(_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, ctypes.c_void_p(wp.data_ptr()),
-                                             _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"), int(act), Co, H, W,
-                                             _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_conv2d_k3_wide_h16")
-    dispatch_counts["conv2d_wide"] += 1
-    return out
+    # (as before the split, `skip` is not checked against the output here)
+    return _launch("d3d_conv2d_k3_wide_h16", out, None,
+                   lambda out: (_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, _ptr(wp), _opt(scale, "scale"), _opt(shift, "shift"),
+                                _opt(skip, "skip"), int(act), Co, H, W, _chk(out, "out"), _stream()), ("conv2d_wide",))
+
+
+CONV2D_ZS_MINPIX = 256 * 256   # smallest image (pixels) conv2d_k3 hands to the 2-D tile kernel
 
 
 def conv2d_k3(x, weight, scale=None, shift=None, skip=None, act=0, stride=1, x2=None, gn=None):
@@ -1443,14 +1047,9 @@ def conv2d_k3(x, weight, scale=None, shift=None, skip=None, act=0, stride=1, x2=
         if all(q is not None for q in parts):
             return torch.cat(parts, 0)
     o = lambda n: (n - 1) // stride + 1
-    out = torch.empty((Co, o(H), o(W)), dtype=torch.float32, device=x.device)
-    if skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape mismatch")
-    rc = _lib.load().d3d_conv2d_k3(_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, _chk(weight, "weight"),
-                                   _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"), int(act), Co, H,
-                                   W, stride, _chk(out, "out"), _stream())
-    _lib.check(rc, "d3d_conv2d_k3")
-    return out
+    return _launch("d3d_conv2d_k3", (Co, o(H), o(W)), skip,
+                   lambda out: (_chk(x, "x", 3), Ci0, _opt(x2, "x2"), Ci1, _chk(weight, "weight"), _opt(scale, "scale"), _opt(shift, "shift"),
+                                _opt(skip, "skip"), int(act), Co, H, W, stride, _chk(out, "out"), _stream()), device=x.device, must=True)
 
 
 def convtranspose2d_k3s2(x, weight, scale=None, shift=None, skip=None, skip_after_act=False, act=0):
@@ -1471,7 +1070,7 @@ def convtranspose2d_k3s2(x, weight, scale=None, shift=None, skip=None, skip_afte
         # of the tile kernel (three quarters of its products are zeros)
         z = x.new_zeros((Ci, 2 * H, 2 * W))
         z[:, ::2, ::2] = x
-        wf = derived_weight(weight, "t2flip", lambda w: w.flip(2, 3).transpose(0, 1))
+        wf = derived_weight(weight, "t2flip", _pack_t2flip)
         y = conv2d_zs(z, wf, scale, shift, skip, act, skip_after_act=skip_after_act)
         if y is not None:
             return y
@@ -1482,32 +1081,25 @@ def convtranspose2d_k3s2(x, weight, scale=None, shift=None, skip=None, skip_afte
         # order).  167 / 102 us per call on the round-1 stream kernel -- 12.6 ms of a 66 ms view
         # -- the stuffed image formed in the kernel's staging: no fill + strided copy of a [64,2H,2W] tensor per call (two of a
         # slice's 33 launches; stage 1 replays its captured loop at ~9 us per node)
-        wf = derived_weight(weight, "t2flip", lambda w: w.flip(2, 3).transpose(0, 1))
+        wf = derived_weight(weight, "t2flip", _pack_t2flip)
         wp = derived_weight(wf, "z2bf16", _pack_z2_bf16)
-        if skip is not None and tuple(skip.shape) != (Co, 2 * H, 2 * W):
-            raise ValueError("skip shape mismatch")
-        out = torch.empty((Co, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-        rc = _lib.load().d3d_convtranspose2d_k3s2_wide_h16(_chk(x, "x", 3), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"),
-                                                            _opt(shift, "shift"), _opt(skip, "skip"), int(act), Ci, Co, H, W,
-                                                            _chk(out, "out"), _stream())
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "d3d_convtranspose2d_k3s2_wide_h16")
-            dispatch_counts["convtranspose2d_wide"] += 1
-            return out
+        y = _launch("d3d_convtranspose2d_k3s2_wide_h16", (Co, 2 * H, 2 * W), skip,
+                    lambda out: (_chk(x, "x", 3), _ptr(wp), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"), int(act),
+                                 Ci, Co, H, W, _chk(out, "out"), _stream()), ("convtranspose2d_wide",), device=x.device)
+        if y is not None:
+            return y
     if _use_mfma() and Co <= 64:
         y = convtranspose_k3s2_mfma(x, weight, scale, shift, skip, act=act, skip_after_act=skip_after_act)
         if y is not None:
             return y
-    out = torch.empty((Co, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-    if skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape mismatch")
-    rc = _lib.load().d3d_convtranspose2d_k3s2(_chk(x, "x", 3), _chk(weight, "weight"), _opt(scale, "scale"),
-                                              _opt(shift, "shift"), _opt(skip, "skip"), int(skip_after_act),
-                                              int(act), Ci, Co, H, W, _chk(out, "out"), _stream())
-    _lib.check(rc, "d3d_convtranspose2d_k3s2")
-    return out
+    return _launch("d3d_convtranspose2d_k3s2", (Co, 2 * H, 2 * W), skip,
+                   lambda out: (_chk(x, "x", 3), _chk(weight, "weight"), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"),
+                                int(skip_after_act), int(act), Ci, Co, H, W, _chk(out, "out"), _stream()), device=x.device, must=True)
 
 
+# ----------------------------------------------------------------------------------------
+# conv-GRU passes and GroupNorm statistics
+# ----------------------------------------------------------------------------------------
 def gru_gates(gates, h):
     """gates [2Hc,H,W] (pre-activation), h [Hc,H,W] -> (r*h, u)."""
     Hc = h.shape[0]
@@ -1530,7 +1122,6 @@ def gru_update(u, h, convc):
     return out
 
 
-_gn_arenas = {}
 _GN_SLOTS = 2048
 
 
@@ -1573,7 +1164,7 @@ def groupnorm_stats(x, ngroups=1):
     """(sum, sum of squares) of each of `ngroups` equal consecutive parts of x as device fp64 pairs [ngroups,2],
     for GroupNorm(1, C) (module.py:62-67); ngroups = 1 returns the single pair [2]."""
     st = torch.empty((ngroups, 2), dtype=torch.float64, device=x.device)
-    rc = _lib.load().d3d_groupnorm_stats(_chk(x, "x"), x.numel() // ngroups, ngroups, ctypes.c_void_p(st.data_ptr()),
+    rc = _lib.load().d3d_groupnorm_stats(_chk(x, "x"), x.numel() // ngroups, ngroups, _ptr(st),
                                          _stream())
     _lib.check(rc, "d3d_groupnorm_stats")
     return st[0] if ngroups == 1 else st
@@ -1583,13 +1174,9 @@ def gru_reset_gn(gates, h, gamma_r, beta_r, eps, stats_r):
     """The reset half of ConvGRUCell2's gates alone (module.py:71-76,85): rh = sigmoid(GroupNorm(gates[:Hc])) * h.  None when the
     kernel does not take the shape (the caller then runs gru_gates_gn)."""
     Hc, plane = h.shape[0], h[0].numel()
-    rh = torch.empty_like(h)
-    rc = _lib.load().d3d_gru_reset_gn(_chk(gates, "gates"), _dptr(stats_r), _chk(gamma_r, "gamma_r"), _chk(beta_r, "beta_r"), _chk(h, "h"),
-                                      Hc, plane, float(eps), int(conv_precision() == "h16"), _chk(rh, "rh"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_gru_reset_gn")
-    return rh
+    return _launch("d3d_gru_reset_gn", torch.empty_like(h), None,
+                   lambda rh: (_chk(gates, "gates"), _dptr(stats_r), _chk(gamma_r, "gamma_r"), _chk(beta_r, "beta_r"), _chk(h, "h"),
+                               Hc, plane, float(eps), int(conv_precision() == "h16"), _chk(rh, "rh"), _stream()))
 
 
 def gru_update_gates_gn(o, gates, h, gamma, beta, gamma_u, beta_u, eps, stats_o, stats_u):
@@ -1637,7 +1224,7 @@ def gru2_cell_gn(x, h, w_gates, b_gates, w_cand, b_cand, norm_r, norm_u, norm_o)
     wc = derived_weight(w_cand, "z2bf16", _pack_z2_bf16)
     sg, so = GnStats(2).take_slot(dev), GnStats(1).take_slot(dev)
     out = torch.empty_like(h)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = lambda t: _ptr(t)
     rc = _lib.load().d3d_gru2_cell_gn_h16(_chk(x, "x", 3), Cx, _chk(h, "h", 3), Hc, H, W, p(wg), _chk(b_gates, "b_gates"), p(wc), _chk(b_cand, "b_cand"),
                                           _chk(norm_r.weight, "gamma_r"), _chk(norm_r.bias, "beta_r"), _chk(norm_u.weight, "gamma_u"),
                                           _chk(norm_u.bias, "beta_u"), _chk(norm_o.weight, "gamma_o"), _chk(norm_o.bias, "beta_o"),
@@ -1650,12 +1237,6 @@ def gru2_cell_gn(x, h, w_gates, b_gates, w_cand, b_cand, norm_r, norm_u, norm_o)
     dispatch_counts["conv2d_gn_fused"] += 2
     dispatch_counts["conv2d_wide" if Ci >= 64 else "conv2d_tile"] += 2
     return out
-
-
-def _dptr(t):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.numel() == 2):
-        raise TypeError("statistics must be a CUDA float64 pair")
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def gru_gates_gn(gates, h, gamma_r, beta_r, gamma_u, beta_u, eps=1e-5, stats=None):
@@ -1687,257 +1268,9 @@ def gru_update_gn(o, u, h, gamma, beta, eps=1e-5, stats=None):
     return out
 
 
-_derived_cache = {}
-
-
-_side_streams = {}   # (device index, caller stream, owner) -> side streams
-_side_lock = __import__("threading").Lock()
-
-
-def side_streams(device, n, owner="ops"):
-    """`n` side streams for the forward that runs on the CALLER'S CURRENT stream of `device` -- one set per (device, caller stream,
-    owner), created on first use.  Two forwards in flight on different streams (two host threads) therefore never
-    share a side stream: their forks / joins do not serialise on each other, the GroupNorm slot arenas (keyed by stream) are
-    not shared, and a block the caching allocator frees on a side stream is reused behind THAT caller's next fork only."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream, owner)
-    with _side_lock:
-        side = _side_streams.get(key)
-        if side is None or len(side) < n:
-            side = _side_streams[key] = [torch.cuda.Stream(device) for _ in range(n)]
-    return side[:n]
-
-
-def hand_over(outs, stream):
-    """Tensors produced on a side stream and consumed on `stream` from now on: tell the caching allocator (record_stream), so
-    that their blocks -- allocated in the side stream's pool -- are not handed out again on the side stream while `stream` still
-    reads them.  Walks lists / tuples / dicts.  (Ordering is the join event's job; this is the allocator's bookkeeping.)"""
-    if isinstance(outs, torch.Tensor):
-        if outs.is_cuda and not _cfg.off("hand_over"):
-            outs.record_stream(stream)
-    elif isinstance(outs, (list, tuple)):
-        for o in outs:
-            hand_over(o, stream)
-    elif isinstance(outs, dict):
-        for o in outs.values():
-            hand_over(o, stream)
-
-
-def on_streams(thunks, device, switch):
-    """[f() for f in thunks] with the INDEPENDENT pieces of work going round-robin over the caller's stream and two side streams
-    (fork event before, one join event per side piece after): chains of small launches that leave most of the chip idle overlap.
-    Same kernels, same operands; `switch` (a key of config.KERNELS) in D3D_KERNELS_OFF keeps everything on the caller's stream.
-    The side streams belong to the caller's stream (side_streams), and what the side pieces return is handed over to it."""
-    if len(thunks) < 2 or device.type != "cuda" or _cfg.off(switch):
-        return [f() for f in thunks]
-    main = torch.cuda.current_stream(device)
-    side = side_streams(device, 2)
-    fork = main.record_event()
-    outs, joins = [], []
-    for i, f in enumerate(thunks):
-        st = (None, side[0], side[1])[i % 3]
-        if st is None:
-            outs.append(f())
-            continue
-        with torch.cuda.stream(st):
-            st.wait_event(fork)
-            outs.append(f())
-            joins.append(st.record_event())
-        hand_over(outs[-1], main)
-    for e in joins:
-        main.wait_event(e)
-    return outs
-
-
-# The drivers need the depth range (depth_values[0, 0], depth_values[0, -1]) as host numbers (adamvs.py:565-566 and its siblings
-# read it with .item()): on a device tensor that is a device -> host copy, i.e. the host waits for every kernel of the PREVIOUS
-# view before it launches the first one of this view.  A caller that built the tensor from host data says so once
-# (note_depth_range: predict_views, bench.py) and the forward then never touches the device for it.
-_depth_ranges = {}
-
-
-def note_depth_range(depth_values, dmin, dmax):
-    """`depth_values` (a device tensor about to be passed to an Infer_* forward) holds [dmin .. dmax] in its first row: keep the
-    host copy of the two numbers (until the tensor is written to or dies)."""
-    import weakref
-
-    key = id(depth_values)
-    ref = weakref.ref(depth_values, lambda _r, key=key: _depth_ranges.pop(key, None))
-    _depth_ranges[key] = (ref, depth_values._version, float(dmin), float(dmax))
-    return depth_values
-
-
-def depth_range_host(depth_values):
-    """(dmin, dmax) of an Infer_* forward's depth_values [B,2] | [B,D] as host floats: the noted pair if the caller left one
-    (no device access), else read from the tensor (one host sync)."""
-    hit = _depth_ranges.get(id(depth_values))
-    if hit is not None and hit[0]() is depth_values and hit[1] == depth_values._version:
-        return hit[2], hit[3]
-    dmin, dmax = (float(v) for v in depth_values[0, [0, -1]].tolist())
-    return dmin, dmax
-
-
-def publish_prepared(weight):
-    """A freshly prepared (packed / folded) operand goes into a cache that EVERY stream reads: the forwards run some layers on
-    side streams (feature pyramids, RED-Net's conv-GRU levels), so the stream that prepared it waits for the preparation once --
-    a cache miss happens at the first forward after a weight changes -- and whoever finds the entry later finds finished data."""
-    if isinstance(weight, torch.Tensor) and weight.is_cuda:
-        torch.cuda.current_stream(weight.device).synchronize()
-
-
-def derived_weight(weight, tag, fn):
-    """A tensor computed from a parameter (negated / flipped / re-laid-out weights), cached per parameter
-    version like the packed GEMM operands; host-side weight preparation, not data-path arithmetic."""
-    key = (id(weight), tag)
-    hit = _derived_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == (weight.data_ptr(), weight._version):
-        return hit[2]
-    with torch.no_grad():
-        out = fn(weight.detach())
-        out = tuple(t.contiguous() for t in out) if isinstance(out, tuple) else out.contiguous()
-    publish_prepared(weight)
-    if len(_derived_cache) > 4096:
-        _derived_cache.clear()
-    _derived_cache[key] = (_weakref.ref(weight), (weight.data_ptr(), weight._version), out)
-    return out
-
-
 # ----------------------------------------------------------------------------------------
-# MFMA implicit-GEMM convolution (d3d_conv_gemm_f32): weight packing, tap lists, dispatch
+# MFMA implicit-GEMM convolution (d3d_conv_gemm_f32) and its z-streaming folded form (d3d_conv_fold_f32)
 # ----------------------------------------------------------------------------------------
-import os as _os
-import weakref as _weakref
-
-import numpy as _np
-
-_pack_cache = {}
-
-
-def _mpad(co):
-    mt = (co + 15) // 16
-    return 16 * (4 if mt == 3 else mt)
-
-
-
-
-H16_NAMES = ("h16", "f16", "bf16")
-
-
-def h16_dtype():
-    """torch dtype of the library's 16-bit operand format (d3d_h16_format: "f16" by default, "bf16" in a -DD3D_H16_BF16 build):
-    what channel-last "h16" volumes and packed 16-bit weight fragments are made of."""
-    return torch.float16 if _lib.h16_format() == "f16" else torch.bfloat16
-
-
-def _norm_precision(mode):
-    """"h16" is the fast mode in whatever 16-bit format the library was built with; "f16" / "bf16" name a format and are
-    accepted only when the loaded library IS that format -- asking an f16 build for bf16 must not silently run f16."""
-    if mode in (None, "fp32", "h16"):
-        return mode
-    if mode in ("f16", "bf16"):
-        if _lib.h16_format() != mode:
-            raise ValueError("precision %r asked of a library whose 16-bit operand format is %r (d3d_h16_format; rebuild with "
-                             "`make -C deep3d_aerial_amd/csrc H16=%s` or ask for 'h16')" % (mode, _lib.h16_format(), mode))
-        return "h16"
-    raise ValueError("precision must be 'fp32' or 'h16' (or the library's format by name: %r)" % _lib.h16_format())
-
-
-def set_conv_precision(mode):
-    """"fp32" (default; fp32 accuracy: exact fp32 MFMA or split bf16x3 operands) or "h16" (16-bit matrix-core operands in the
-    library's format -- IEEE half unless built otherwise, see _lib.h16_format() -- with fp32 accumulation: BASELINE config 3's
-    fast mode) for the regularisers' convolutions.  None = follow the switch table (D3D_CONV_PRECISION).
-    PER THREAD (config.state is a threading.local): a forward run in a worker thread follows the switch table's
-    D3D_CONV_PRECISION unless that thread calls this itself; to change the process-wide default set
-    config.switches["D3D_CONV_PRECISION"]."""
-    _cfg.state.conv_precision = _norm_precision(mode)
-
-
-def conv_precision():
-    return _cfg.state.conv_precision or _norm_precision(_cfg.get("D3D_CONV_PRECISION"))
-
-
-class fp32_convs:
-    """Context manager: exact fp32 convolutions inside, whatever the global precision (feature pyramids)."""
-
-    def __enter__(self):
-        self.saved = _cfg.state.conv_precision
-        _cfg.state.conv_precision = "fp32"
-
-    def __exit__(self, *exc):
-        _cfg.state.conv_precision = self.saved
-        return False
-
-
-class h16_convs(fp32_convs):
-    """Context manager: 16-bit matrix-core operands inside (BASELINE config 3's fast mode), whatever the global precision."""
-
-    def __enter__(self):
-        self.saved = _cfg.state.conv_precision
-        _cfg.state.conv_precision = "h16"
-
-
-def _use_mfma():
-    return _cfg.get("D3D_CONV") != "direct"
-
-
-def _packed(weight, transposed):
-    """Packed GEMM operands of a k=3 conv weight, cached per parameter version.
-
-    conv  [Co,Ci,(3,)3,3] -> one (wpack [T*Ci, mpad], taps int8 [T,3]) with offsets -1..1.
-    convT [Ci,Co,(3,)3,3] -> one entry per output-parity class: (parity zyx, wpack, taps) with
-    offsets 0/+1 (even outputs: kernel index 1 at o/2; odd: index 0 at (o+1)/2, index 2 at (o-1)/2).
-    """
-    # keyed by the tensor OBJECT (weak), validated by storage address and in-place version counter:
-    # load_state_dict / copy_ / optimizer steps bump the version; writes through `.data` do not --
-    # call clear_weight_cache() after those.
-    key = (id(weight), transposed)
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == (weight.data_ptr(), weight._version):
-        return hit[2]
-    nd = weight.dim() - 2
-    with torch.no_grad():
-        w = weight.detach().float()
-        if nd == 2:
-            w = w.unsqueeze(2)  # [.., 1, 3, 3]: z kernel of size 1
-        kz_n = w.shape[2]
-        if not transposed:
-            Co, Ci = w.shape[0], w.shape[1]
-            taps = [(kz - (kz_n // 2), ky - 1, kx - 1) for kz in range(kz_n) for ky in range(3) for kx in range(3)]
-            wp = w.reshape(Co, Ci, -1).permute(2, 1, 0).reshape(-1, Co)
-            pad = torch.zeros((wp.shape[0], _mpad(Co)), dtype=torch.float32, device=w.device)
-            pad[:, :Co] = wp
-            out = (pad.contiguous(), _np.array(taps, _np.int8).tobytes(), len(taps))
-        else:
-            Ci, Co = w.shape[0], w.shape[1]
-            dim_opts = {0: [(1, 0)], 1: [(0, 1), (2, 0)]}  # parity -> [(kernel index, input offset)]
-            out = []
-            zpar = [0] if kz_n == 1 else [0, 1]
-            for pz in zpar:
-                for py in (0, 1):
-                    for px in (0, 1):
-                        zl = [(0, 0)] if kz_n == 1 else dim_opts[pz]
-                        taps, cols = [], []
-                        for (kz, oz) in zl:
-                            for (ky, oy) in dim_opts[py]:
-                                for (kx, ox) in dim_opts[px]:
-                                    taps.append((oz, oy, ox))
-                                    cols.append(w[:, :, kz, ky, kx])  # [Ci, Co]
-                        wp = torch.stack(cols, 0).reshape(-1, Co)      # [T*Ci, Co]
-                        pad = torch.zeros((wp.shape[0], _mpad(Co)), dtype=torch.float32, device=w.device)
-                        pad[:, :Co] = wp
-                        out.append(((pz, py, px), pad.contiguous(), _np.array(taps, _np.int8).tobytes(), len(taps)))
-    publish_prepared(weight)
-    if len(_pack_cache) > 4096:
-        _pack_cache.clear()
-    _pack_cache[key] = (_weakref.ref(weight), (weight.data_ptr(), weight._version), out)
-    return out
-
-
-def clear_weight_cache():
-    """Drop every packed / derived weight entry (needed only after writing weights through `.data`)."""
-    _pack_cache.clear()
-    _derived_cache.clear()
-
-
 def _gemm(x, x2, wpack, taps, ntaps, Co, scale, shift, skip, skip_after_act, act, in_dims, grid, out, istride,
           ostride, ooff):
     D, H, W = in_dims
@@ -1993,130 +1326,6 @@ def convtranspose_k3s2_mfma(x, weight, scale=None, shift=None, skip=None, act=0,
         if not _gemm(x, None, wpack, taps, nt, Co, scale, shift, skip, skip_after_act, act, dims, dims, out, 1, 2, par):
             return None
     return out
-
-
-# ----------------------------------------------------------------------------------------
-# z-streaming folded implicit GEMM (d3d_conv_fold_f32): tap lists / packed weights per layer
-# ----------------------------------------------------------------------------------------
-def _dim_conv(K, stride, fold):
-    """One dimension of an ordinary convolution (odd kernel size K, padding K // 2) folded over `fold`
-    neighbouring outputs: (tap offsets, fold positions, k(tap, fold) -> kernel index or -1, input step, output
-    step, base).  K = 0 marks the degenerate row dimension of an image (a single tap, a single position)."""
-    if K == 0:
-        return [0], [0], (lambda t, f: 0), 1, 1, 0
-    pad = K // 2
-    taps = list(range(-pad, (fold - 1) * stride + pad + 1))
-    k = lambda t, f: (t - f * stride + pad) if 0 <= t - f * stride + pad < K else -1
-    return taps, list(range(fold)), k, fold * stride, fold, 0
-
-
-def _dim_convT(K, parities):
-    """One dimension of a k=3 stride-2 pad-1 output_pad-1 transposed convolution: output 2g+p reads input
-    g+o with kernel index k(o,p): p even -> (o=0: 1); p odd -> (o=0: 2, o=1: 0)."""
-    if K == 0:
-        return [0], [0], (lambda t, f: 0), 1, 1, 0
-    table = {(0, 0): 1, (0, 1): 2, (1, 1): 0}
-    k = lambda o, f: table.get((o, parities[f]), -1)
-    return [0, 1], list(range(len(parities))), k, 1, 2, (parities[0] if len(parities) == 1 else 0)
-
-
-def _fold_pack(wk, dims, Co, ksizes):
-    """wk [Co,Ci,K0*K1*K2] (kernel sizes ksizes, in the streaming/row/column order of `dims`) ->
-    (wpack [T,Ci,mpad], taps bytes (sorted by the first dimension), T, M, mpad, [c,s,b,f per dim])."""
-    (t0, f0, k0, c0, s0, b0), (t1, f1, k1, c1, s1, b1), (t2, f2, k2, c2, s2, b2) = dims
-    K1, K2 = ksizes[1], ksizes[2]
-    F = len(f0) * len(f1) * len(f2)
-    M = Co * F
-    if M > 64:
-        raise ValueError("fold %dx%dx%d of %d channels exceeds 64 GEMM rows" % (len(f0), len(f1), len(f2), Co))
-    mpad = 16 if M <= 16 else (32 if M <= 32 else 64)
-    nk = wk.shape[2]
-    taps, kidx = [], []
-    for o0 in t0:
-        for o1 in t1:
-            for o2 in t2:
-                row = []
-                for a in f0:
-                    for b in f1:
-                        for c in f2:
-                            i, jj, l = k0(o0, a), k1(o1, b), k2(o2, c)
-                            row.append(nk if min(i, jj, l) < 0 else (i * K1 + jj) * K2 + l)
-                if any(r != nk for r in row):
-                    taps.append((o0, o1, o2))
-                    kidx.append(row)
-    T = len(taps)
-    Ci = wk.shape[1]
-    wz = torch.cat([wk, torch.zeros((Co, Ci, 1), dtype=wk.dtype, device=wk.device)], 2)
-    idx = torch.tensor(kidx, dtype=torch.long, device=wk.device)        # [T, F]
-    a = wz[:, :, idx]                                                    # [Co, Ci, T, F]
-    a = a.permute(2, 1, 3, 0).reshape(T, Ci, M)                          # row m = fold*Co + co
-    wpack = torch.zeros((T, Ci, mpad), dtype=torch.float32, device=wk.device)
-    wpack[:, :, :M] = a
-    tail = [c0, c1, c2, s0, s1, s2, b0, b1, b2, len(f0), len(f1), len(f2)]
-    return wpack.contiguous(), _np.array(taps, _np.int8).tobytes(), T, M, mpad, tail
-
-
-def _conv_fold_choice(Co, Ci, three_d, stride, K=3):
-    """Fold (f_y, f_x) that fills the 16 GEMM rows of a narrow layer.  Limits: the kernel's 128 taps, and resident
-    weights (ntaps * Ci * 16 floats) small enough that two workgroups still share a CU's LDS -- a wide-C_in layer
-    is faster unfolded at twice the occupancy (stage-1 conv0 32->8: 9.4 ms folded, 5.3 ms unfolded)."""
-    budget = 48 * 1024
-    ntaps = lambda f: (K if three_d else 1) * ((f[0] - 1) * stride + K) * ((f[1] - 1) * stride + K)
-    for f in [(4, 4), (2, 4), (2, 2), (1, 2)]:
-        # (the kernel's column step f_x * stride must be 1, 2 or 4)
-        if Co * f[0] * f[1] <= 16 and f[1] * stride <= 4 and ntaps(f) <= 128 and ntaps(f) * Ci * 64 <= budget:
-            return f
-    return (1, 1)
-
-
-def _packed_fold(weight, transposed, stride):
-    """List of launches [(wpack, taps, T, M, mpad, geom tail)] for one layer, cached like _packed.
-
-    Dimension order of the kernel is (streamed, row, column).  A volume [C,D,H,W] maps (z, y, x) onto it; an
-    image [C,H,W] is handed over as [C, H, 1, W] -- its rows are the streamed planes, so every input row is
-    staged once and the kernel's z machinery (open accumulator sets, z fold) serves the image's y axis."""
-    key = (id(weight), "fold", transposed, stride)
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == (weight.data_ptr(), weight._version):
-        return hit[2]
-    with torch.no_grad():
-        w = weight.detach().float()
-        three_d = w.dim() == 5
-        if transposed:
-            w = w.transpose(0, 1)
-        Co, Ci = w.shape[0], w.shape[1]
-        wk = w.reshape(Co, Ci, -1).contiguous()
-        K = w.shape[-1]  # cubic / square kernels, odd size, padding K // 2 (1, 3 and 5 occur in the reference)
-        if K % 2 == 0 or any(d != K for d in w.shape[2:]) or (transposed and K != 3):
-            raise ValueError("unsupported kernel shape %s" % (tuple(w.shape[2:]),))
-        ks = (K, K, K) if three_d else (K, 1, K)
-        launches = []
-        if not transposed:
-            fy, fx = _conv_fold_choice(Co, Ci, three_d, stride, K)
-            if three_d:
-                dims = (_dim_conv(K, stride, 1), _dim_conv(K, stride, fy), _dim_conv(K, stride, fx))
-            else:
-                dims = (_dim_conv(K, stride, fy), _dim_conv(0, 1, 1), _dim_conv(K, stride, fx))
-            launches.append(_fold_pack(wk, dims, Co, ks))
-        else:
-            # all output parities as GEMM rows while they fit 64 rows; otherwise one launch per parity of the
-            # leading dimensions
-            ks0 = [k if k == 3 else 0 for k in ks]
-            sets = [[[0, 1]] if k == 3 else [None] for k in ks]
-            rows = lambda: Co * int(_np.prod([len(ss[0]) if ss[0] else 1 for ss in sets]))
-            for d in range(3):
-                if rows() > 64 and ks[d] == 3:
-                    sets[d] = [[0], [1]]
-            for p0 in sets[0]:
-                for p1 in sets[1]:
-                    for p2 in sets[2]:
-                        dims = tuple(_dim_convT(ks0[d], pp) for d, pp in enumerate((p0, p1, p2)))
-                        launches.append(_fold_pack(wk, dims, Co, ks))
-    publish_prepared(weight)
-    if len(_pack_cache) > 4096:
-        _pack_cache.clear()
-    _pack_cache[key] = (_weakref.ref(weight), (weight.data_ptr(), weight._version), launches)
-    return launches
 
 
 def conv_fold(x, weight, scale=None, shift=None, skip=None, act=0, stride=1, x2=None, skip_after_act=True,
@@ -2183,15 +1392,6 @@ def conv2d_same(x, weight, scale=None, shift=None, skip=None, act=0, stride=1):
     return conv_fold(x, weight, scale, shift, skip, act, stride, None, True, transposed=False)
 
 
-def _pack_k1(w):
-    """[Co,Ci,1,1] -> [ceil(Co / 8)][Ci][8]: blocks of 8 output channels, zero-padded (d3d_conv2d_k1_f32)."""
-    Co, Ci = w.shape[0], w.shape[1]
-    nb = (Co + 7) // 8
-    wp = w.new_zeros((nb * 8, Ci))
-    wp[:Co] = w.reshape(Co, Ci)
-    return wp.reshape(nb, 8, Ci).permute(0, 2, 1).contiguous()
-
-
 def conv2d_k1(x, weight, scale=None, shift=None, skip=None, act=0):
     """Conv2d(k 1) in exact fp32 as a streaming kernel (d3d_conv2d_k1_f32: the 1 x 1 output layers of the feature pyramids);
     act(scale * conv + shift) + skip.  None for shapes it does not take."""
@@ -2200,16 +1400,9 @@ def conv2d_k1(x, weight, scale=None, shift=None, skip=None, act=0):
     if Ci not in (8, 16, 32) or (H * W) % 4 or act not in (0, 1) or tuple(weight.shape) != (Co, Ci, 1, 1):
         return None
     wp = derived_weight(weight, "k1f32", _pack_k1)
-    out = torch.empty((Co, H, W), dtype=torch.float32, device=x.device)
-    if skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape mismatch")
-    rc = _lib.load().d3d_conv2d_k1_f32(_chk(x, "x", 3), _chk(wp, "wpacked"), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"),
-                                       int(act), Ci, Co, H, W, _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_conv2d_k1_f32")
-    dispatch_counts["conv2d_k1"] += 1
-    return out
+    return _launch("d3d_conv2d_k1_f32", (Co, H, W), skip,
+                   lambda out: (_chk(x, "x", 3), _chk(wp, "wpacked"), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"),
+                                int(act), Ci, Co, H, W, _chk(out, "out"), _stream()), ("conv2d_k1",), device=x.device)
 
 
 def conv2d_k5s2_zs(x, weight, scale=None, shift=None, skip=None, act=0, skip_after_act=True):
@@ -2223,16 +1416,9 @@ def conv2d_k5s2_zs(x, weight, scale=None, shift=None, skip=None, act=0, skip_aft
             or _cfg.off("conv2d_k5"):
         return None
     wp = derived_weight(weight, "z2k5bf16x3", _pack_z2_bf16x3)
-    out = torch.empty((Co, Ho, Wo), dtype=torch.float32, device=x.device)
-    if skip is not None and skip.shape != out.shape:
-        raise ValueError("skip shape mismatch")
-    rc = _lib.load().d3d_conv2d_k5s2_zs_bf16x3(_chk(x, "x", 3), ctypes.c_void_p(wp.data_ptr()), _opt(scale, "scale"), _opt(shift, "shift"),
-                                               _opt(skip, "skip"), int(act), int(bool(skip_after_act)), Ci, Co, H, W, _chk(out, "out"),
-                                               _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_conv2d_k5s2_zs_bf16x3")
-    return out
+    return _launch("d3d_conv2d_k5s2_zs_bf16x3", (Co, Ho, Wo), skip,
+                   lambda out: (_chk(x, "x", 3), _ptr(wp), _opt(scale, "scale"), _opt(shift, "shift"), _opt(skip, "skip"), int(act),
+                                int(bool(skip_after_act)), Ci, Co, H, W, _chk(out, "out"), _stream()), device=x.device)
 
 
 def gru_cell_conv_fused(cost, h, w_pre, w_gates, b_gates, w_cand, b_cand, stride=1, out=None):
@@ -2242,38 +1428,25 @@ def gru_cell_conv_fused(cost, h, w_pre, w_gates, b_gates, w_cand, b_cand, stride
     kernel does not take (the caller then runs the separate launches)."""
     if conv_precision() != "h16" or not _use_mfma() or _cfg.off("gru_fused") or cost.dim() not in (3, 4):
         return None
+    HID, H, W = h.shape
     if cost.dim() == 4:   # a CL8 plane [C/8, H, W, 8] of 16-bit cells (weighted_corr_cl8): the stride-1 cell's own entry point
         G8, HI, WI, _ = cost.shape
-        HID, H, W = h.shape
         CP = 8 * G8
         if cost.dtype != h16_dtype() or cost.shape[3] != 8 or not cost.is_contiguous() or stride != 1 or (HI, WI) != (H, W) \
                 or CP not in (8, 16, 32) or HID != 8 or b_gates is None or b_cand is None:
             return None
-        w1 = derived_weight(w_pre, "z2bf16", _pack_z2_bf16)
-        wg = derived_weight(w_gates, "z2bf16", _pack_z2_bf16)
-        wc = derived_weight(w_cand, "z2bf16", _pack_z2_bf16)
-        if out is None:
-            out = torch.empty_like(h)
-        elif out.shape != h.shape or out.dtype != h.dtype or out.data_ptr() == h.data_ptr():
-            raise ValueError("out must be a separate tensor of the state's shape")
-        rc = _lib.load().d3d_gru_cell_fused_cl8_h16(ctypes.c_void_p(cost.data_ptr()), CP, _chk(h, "h", 3), HID, H, W,
-                                                    ctypes.c_void_p(w1.data_ptr()), ctypes.c_void_p(wg.data_ptr()), _chk(b_gates, "b_gates"),
-                                                    ctypes.c_void_p(wc.data_ptr()), _chk(b_cand, "b_cand"), _chk(out, "out"), _stream())
-        if rc == _lib.ERR_UNSUPPORTED:
-            return None
-        _lib.check(rc, "d3d_gru_cell_fused_cl8_h16")
-        dispatch_counts["gru_cell_fused"] += 1
-        return out
-    CP, HI, WI = cost.shape
-    HID, H, W = h.shape
-    if stride == 1:
-        ok = CP in (8, 16, 32) and HID == 8 and (HI, WI) == (H, W)
+        name, head = "d3d_gru_cell_fused_cl8_h16", lambda: (_ptr(cost), CP)
     else:
-        ok = stride == 2 and CP == 8 and HID == 16 and (H, W) == ((HI - 1) // 2 + 1, (WI - 1) // 2 + 1)
-    if not ok or b_gates is None or b_cand is None:
-        return None
-    if tuple(w_pre.shape) != (HID, CP, 3, 3) or tuple(w_gates.shape) != (2 * HID, 2 * HID, 3, 3) or tuple(w_cand.shape) != (HID, 2 * HID, 3, 3):
-        raise ValueError("conv-GRU cell weights do not match C = %d, hidden = %d" % (CP, HID))
+        CP, HI, WI = cost.shape
+        if stride == 1:
+            ok = CP in (8, 16, 32) and HID == 8 and (HI, WI) == (H, W)
+        else:
+            ok = stride == 2 and CP == 8 and HID == 16 and (H, W) == ((HI - 1) // 2 + 1, (WI - 1) // 2 + 1)
+        if not ok or b_gates is None or b_cand is None:
+            return None
+        if tuple(w_pre.shape) != (HID, CP, 3, 3) or tuple(w_gates.shape) != (2 * HID, 2 * HID, 3, 3) or tuple(w_cand.shape) != (HID, 2 * HID, 3, 3):
+            raise ValueError("conv-GRU cell weights do not match C = %d, hidden = %d" % (CP, HID))
+        name, head = "d3d_gru_cell_fused_h16", lambda: (_chk(cost, "cost", 3), CP, HI, WI, int(stride))
     w1 = derived_weight(w_pre, "z2bf16", _pack_z2_bf16)
     wg = derived_weight(w_gates, "z2bf16", _pack_z2_bf16)
     wc = derived_weight(w_cand, "z2bf16", _pack_z2_bf16)
@@ -2281,14 +1454,9 @@ def gru_cell_conv_fused(cost, h, w_pre, w_gates, b_gates, w_cand, b_cand, stride
         out = torch.empty_like(h)
     elif out.shape != h.shape or out.dtype != h.dtype or out.data_ptr() == h.data_ptr():
         raise ValueError("out must be a separate tensor of the state's shape")
-    rc = _lib.load().d3d_gru_cell_fused_h16(_chk(cost, "cost", 3), CP, HI, WI, int(stride), _chk(h, "h", 3), HID, H, W,
-                                             ctypes.c_void_p(w1.data_ptr()), ctypes.c_void_p(wg.data_ptr()), _chk(b_gates, "b_gates"),
-                                             ctypes.c_void_p(wc.data_ptr()), _chk(b_cand, "b_cand"), _chk(out, "out"), _stream())
-    if rc == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "d3d_gru_cell_fused_h16")
-    dispatch_counts["gru_cell_fused"] += 1
-    return out
+    return _launch(name, out, None,
+                   lambda out: head() + (_chk(h, "h", 3), HID, H, W, _ptr(w1), _ptr(wg), _chk(b_gates, "b_gates"), _ptr(wc),
+                                         _chk(b_cand, "b_cand"), _chk(out, "out"), _stream()), ("gru_cell_fused",))
 
 
 def gru_cell_fused(x, h, w_gates, b_gates, w_cand, b_cand):
@@ -2330,11 +1498,9 @@ def normals_kinv(K):
     row-major per item.  The reference multiplies with torch.inverse's fp32 result (compute_normals.py:23), whose last bits
     depend on the batch size and the memory layout of its argument; here every item is inverted alone, in float64 through the
     adjugate (fixed IEEE operations: the same bits on every machine, for any batch), and rounded once -- within an ulp of it."""
-    import numpy as _np_k
-
     if isinstance(K, torch.Tensor):
         K = K.detach().cpu().numpy()
-    K = _np_k.asarray(K, dtype=_np_k.float32).astype(_np_k.float64)
+    K = _np.asarray(K, dtype=_np.float32).astype(_np.float64)
     if K.ndim == 2:
         K = K[None]
     if K.ndim != 3 or K.shape[1:] != (3, 3):
@@ -2342,13 +1508,13 @@ def normals_kinv(K):
     a, b, c = K[:, 0, 0], K[:, 0, 1], K[:, 0, 2]
     d, e, f = K[:, 1, 0], K[:, 1, 1], K[:, 1, 2]
     g, h, i = K[:, 2, 0], K[:, 2, 1], K[:, 2, 2]
-    adj = _np_k.stack([e * i - f * h, c * h - b * i, b * f - c * e,
+    adj = _np.stack([e * i - f * h, c * h - b * i, b * f - c * e,
                        f * g - d * i, a * i - c * g, c * d - a * f,
                        d * h - e * g, b * g - a * h, a * e - b * d], -1)
     det = a * adj[:, 0] + b * adj[:, 3] + c * adj[:, 6]
-    if not _np_k.all(_np_k.isfinite(det)) or _np_k.any(det == 0):
+    if not _np.all(_np.isfinite(det)) or _np.any(det == 0):
         raise ValueError("singular intrinsics")
-    return torch.from_numpy(_np_k.ascontiguousarray(adj / det[:, None], dtype=_np_k.float32))
+    return torch.from_numpy(_np.ascontiguousarray(adj / det[:, None], dtype=_np.float32))
 
 
 def normals_from_depth(depth, K, nei=1, encoded=False, normal=True):

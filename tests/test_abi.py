@@ -56,6 +56,34 @@ def test_operators_refuse_cpu_tensors():
         ops.softargmin_conf4(torch.zeros(4, 8, 8), torch.zeros(4))
 
 
+
+# every public name ops.py defined before its packers and runtime helpers moved to _packing.py / _runtime.py
+_OPS_PUBLIC = """AFFINE AffineDepth CONV2D_ZS_MINPIX GnStats H16_NAMES PER_PIXEL PER_PLANE avgpool_4_8 channel_last_enabled cl8_to_cl cl_to_cl8
+clear_weight_cache compose_projections conv1x1_context conv1x1_upskip conv2d_k1 conv2d_k3 conv2d_k3_pair3 conv2d_k5s2_zs conv2d_s2_zs
+conv2d_s2_zs_batched conv2d_same conv2d_stream conv2d_wide conv2d_zs conv3d_k3 conv3d_k3_cl conv3x3_bias_border_ conv_fold conv_k3_mfma
+conv_precision convtranspose2d_k3s2 convtranspose2d_k4_zs convtranspose2d_zs convtranspose3d_k3s2 convtranspose3d_k3s2_cl
+convtranspose3d_prob_cl convtranspose_k3s2_mfma depth_range_affine depth_range_host depth_range_samples derived_weight dispatch_counts
+fp32_convs from_cl groupnorm_stats gru2_cell_gn gru_cell_conv_fused gru_cell_fused gru_gates gru_gates_gn gru_reset_gn gru_update
+gru_update_gates_gn gru_update_gn h16_convs h16_dtype hand_over homo_warp homo_warp_double normals_from_depth normals_kinv note_depth_range
+on_streams online_regress_finalize online_regress_update pair_corr_mean pair_softmax_max publish_prepared resize_bilinear
+set_conv_precision side_streams slice_head_regress slice_tail_regress slice_tail_regress_same slice_tile_kernels softargmin_conf4
+softargmin_conf4_var sweep_dispatch_counts to_cl uncertainty_aware_samples upsampled_conv_weight variance_volume variance_volume_cl
+weighted_corr weighted_corr_cl8""".split()
+
+
+def test_ops_keeps_its_names_and_shares_its_state():
+    from deep3d_aerial_amd import _packing, _runtime, ops
+
+    assert len(_OPS_PUBLIC) == 86 and [n for n in _OPS_PUBLIC if not hasattr(ops, n)] == []
+    for name in ("dispatch_counts", "_gn_arenas", "_derived_cache", "_pack_cache", "_side_streams", "_depth_ranges"):
+        assert getattr(ops, name) is getattr(_runtime, name), name   # one object each: imported, never copied
+    assert ops._stream is _runtime._stream and ops._lib is _lib and ops.h16_dtype is _packing.h16_dtype
+    assert ops._pack_z2_bf16 is _packing._pack_z2_bf16 and ops._packed_fold is _runtime._packed_fold
+    # the monkeypatched constants and the operators stay defined in ops itself, next to the code that reads them
+    for name in ("_CONV2D_STREAM_MIN", "CONV2D_ZS_MINPIX", "conv2d_k3", "conv3d_k3", "variance_volume_cl"):
+        assert name in vars(ops) and not hasattr(_runtime, name) and not hasattr(_packing, name), name
+
+
 @pytest.mark.parametrize("tag", ["model_casmvsnet_v3", "model_adamvs_v3", "model_msrednet_v3"])
 def test_state_dict_is_checkpoint_compatible(tag):
     """Same keys, same order, same shapes as the reference module (recorded in the golden file)."""
