@@ -179,6 +179,19 @@ SIGNATURES = {
     "d3d_texture_empty": [_vp, ctypes.c_longlong, ctypes.c_uint, _vp],
     "d3d_texture_texcoords": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp,
                               _vp, _vp],
+    "d3d_texture_level_scratch_bytes": ([ctypes.c_longlong], _sz),
+    "d3d_texture_level_incidence": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp],
+    "d3d_texture_level_pairs": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp,
+                                _vp, _vp],
+    "d3d_texture_level_csr": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, ctypes.c_longlong, _f, _vp, _vp, _vp, _vp],
+    "d3d_texture_level_samples": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp,
+                                  _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "d3d_texture_level_solve": [_vp, _vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _f, _d, _i, _vp, _sz, _vp, ctypes.POINTER(_i),
+                                ctypes.POINTER(_i), _vp],
+    "d3d_texture_level_cover": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp,
+                                _vp],
+    "d3d_texture_level_apply": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong,
+                                _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp, _vp, _vp],
 }
 
 

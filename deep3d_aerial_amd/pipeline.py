@@ -94,7 +94,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     gathered depth and confidence map with its camera, in global view order, cleans it when a clean step is on (mesh.clean),
     decimates it when asked (mesh.decimate), and writes the PLY; the DSM from the mesh and the texture use that mesh.  The
     other ranks do nothing (no collective: the file does not depend on the number of ranks); timings gets mesh_s on rank 0.
-    texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad"}
+    texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad",
+    "level" (optional: None, or the seam levelling's settings)}
     (needs mesh; texture.settings_from_args): the mesh rank 0 wrote (after cleaning) textured from every rank's views and
     reference images (write_texture_of); rank 0 writes the textured PLY and its pages; timings gets texture_s."""
     if mesh is not None:
@@ -129,6 +130,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         if mesh is None:
             raise ValueError("texture needs mesh: the texture is laid on the mesh")
         _texture.check_settings(texture)
+        if texture.get("level") is not None:
+            _texture.check_level_settings(texture["level"])
     if checker is None:
         checker = fuse.ConsistencyChecker(1.0, 0.01, 90.0, 0.2)   # Fuse_Depth_Map's defaults (fusion_3d_normal.py:56-57)
     n = len(dataset)
@@ -295,11 +298,13 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     Rank 0 broadcasts the mesh (sizes first); each rank selects over its own views (texture.select_faces); one all_reduce(MIN)
     of the keys; rank 0 lays out the charts, rects and pages (texture.layout) and broadcasts the chart table and page heights;
     each rank fills the charts of its own views; one all_reduce(SUM) of the pages as packed int32 texels (one rank contributes
-    per texel), then the empty colour.  Returns texture.texture_mesh's dict on rank 0 (without "labels"), None elsewhere."""
+    per texel); with settings["level"] rank 0 levels the seams of the merged pages (texture.level_pages); then the empty
+    colour.  Returns texture.texture_mesh's dict on rank 0 (without "labels"), None elsewhere."""
     from . import ortho as _ortho, texture as _tx
 
     t0 = time.perf_counter()
     tol, vpb, P, pad = _tx.check_settings(settings)
+    level = _tx.check_level_settings(settings["level"]) if settings.get("level") is not None else None
     v = f = None
     if rank == 0:
         v = built_mesh[0].to(device=device, dtype=torch.float32).contiguous()
@@ -325,6 +330,8 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     atlas = _tx.fill_pages(table_np, packing, ov, _tx.new_atlas(packing, device))
     if world_size > 1:
         sharding.all_reduce_raster(atlas, dist.ReduceOp.SUM)
+    if level is not None and rank == 0:   # the merged atlas, the mesh, keys, table and every camera are here: no new collective
+        res["level"] = _tx.level_pages(v, f, key, res["chart"], table_np, packing, cams, atlas, *level)
     _tx.finish_pages(atlas)
     if rank == 0:
         tc, tn = _tx.texcoords(v, f, key, res["chart"], table_np, packing, cams)

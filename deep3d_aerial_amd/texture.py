@@ -1,7 +1,8 @@
 """Texturing the surface mesh from the views.
 
 The reference runs OpenMVS's TextureMesh after ReconstructMesh and RefineMesh.  The rules below are this project's own and do
-not claim to match OpenMVS: there is no smoothness term, no photo-consistency test and no seam levelling.
+not claim to match OpenMVS: there is no smoothness term and no photo-consistency test; global seam levelling (below) is off
+by default, local (Poisson) seam levelling is not offered.
 
 * Input.  vertices [n,3] fp32 and faces [m,3] int32 on the GPU (mesh.extract, mesh.clean, mesh.read_ply), every index in
   0 .. n - 1; views: ortho.OrthoView records (id, K, E, depth, image) with distinct ids.
@@ -33,12 +34,42 @@ not claim to match OpenMVS: there is no smoothness term, no photo-consistency te
   z), `element face` with `property list uchar int vertex_indices`, `property list uchar float texcoord` (6 values) and
   `property int texnumber` -- the layout MeshLab reads and OpenMVS writes.  Pages are RGB8 PNGs beside it.
 
+Seam levelling (level=..., --level): one smooth additive colour correction per chart that makes charts of
+different views agree along their common border.  It runs after the fill and the rank merge and before the empty colour.
+* Node.  A distinct (chart, vertex) pair over the corners of faces that have a winner, numbered in increasing (chart, vertex)
+  order.
+* Sample.  f[node] (RGB): the bilinear tap of the filled atlas at x = (u - x0) + ox, y = ((v - y0) + oy) + page_row, u and v the
+  texcoord pass's projection of the vertex in the chart's view; in fp64, per channel ((w00 c00 + w10 c10) + w01 c01) + w11 c11
+  with w00 = (1 - tx)(1 - ty), w10 = tx (1 - ty), w01 = (1 - tx) ty, w11 = tx ty, rounded to fp32.  pad >= 1 keeps the four taps
+  inside the rect; at a rect the image's border cut, a tap past the rect repeats the rect's last texel (its weight is 0).
+* Seam pair.  A distinct (vertex, chart c1 < chart c2) such that the vertex is an end of a seam edge between c1 and c2.  A seam
+  edge is an edge shared by exactly two faces (of all faces, mesh_clean's edges) that both have winners and lie in different
+  charts: an edge of three or more faces, or next to a face with no winner, makes no seam.
+* Smoothness edge.  A distinct (chart, unordered vertex pair) over the edges of the chart's faces.
+* Energy.  g[node] (RGB, the channels independent) minimises the sum over seam pairs of ((f_i + g_i) - (f_j + g_j))^2 + smooth *
+  the sum over smoothness edges of (g_a - g_b)^2 + anchor * the sum over nodes of g^2: (L + anchor I) g = b, L the graph
+  Laplacian with weight 1 on seam pairs and smooth on smoothness edges, b_i = the sum over i's seam pairs of f_j - f_i (fp32, in
+  increasing j).  anchor > 0 makes the system positive definite.  Defaults smooth = 0.1, anchor = 1e-3: settings, not
+  measurements.
+* Solve.  Conjugate gradients from g = 0 on fp32 vectors, dot products in fp64; a channel stops (and is frozen) once
+  |r| <= level_tolerance |b| (default 1e-4), all stop after level_iterations (default 500).  A p is kept as A r + beta A p_old.
+* Coverage.  A texel of a chart's rect is a candidate of a face of that chart when d2 <= 2, d2 the squared distance in fp64, in
+  texel coordinates (X = (u - x0) + ox, Y = (v - y0) + oy), from its centre to the face's projected triangle, 0 inside or on it:
+  exactly the texels a bilinear tap at a point of the triangle can read.  The texel takes the face with the smallest int64 key
+  (bits(fp32(d2)) << 32) | face; a texel that is no face's candidate keeps its colour.
+* Apply.  With w the barycentric weights of the closest point of the covering triangle (fp64, rounded to fp32) the correction is
+  (w0 g0 + w1 g1) + w2 g2 in fp32 and each channel becomes clamp(rint(colour + correction), 0, 255); alpha is unchanged.
+The dot products are folded from fixed slots in a fixed order, so two runs give the same bits; the levelled pages do not depend
+on view order or batching.
+
 Faces are never reordered or renumbered: a shuffled face list gives the same key per face.  Chart labels, and so the packing,
 follow the face order.  The hot passes are HIP kernels (csrc/texture.hip): select, charts (hooking and pointer jumping over
-(edge, face) pairs that torch.sort orders), rects, fill and texcoords.  No float atomics; the integer atomics are min / max.
+(edge, face) pairs that torch.sort orders), rects, fill and texcoords; the levelling's kernels are in csrc/texture_level.hip.  No float atomics; the integer atomics are
+min / max.
 
     python -m deep3d_aerial_amd.texture --mesh IN.ply --mvs MVS_FOLDER --out OUT.ply [--image_root DIR]
         [--depth_tolerance 0.01] [--views_per_batch N] [--page_size 8192] [--pad 2]
+        [--level [--level_smooth 0.1] [--level_anchor 1e-3] [--level_tolerance 1e-4] [--level_iterations 500]]
 """
 import argparse
 import ctypes
@@ -55,7 +86,11 @@ from .ortho import (DEFAULT_TOLERANCE, EMPTY_KEY, OrthoView, _ViewRecord, _batch
 DEFAULT_PAGE = 8192
 DEFAULT_PAD = 2
 EMPTY_COLOR = (166, 166, 166)
-BAND = 8   # atlas rows per fill work item (csrc/texture.hip TX_BAND)
+BAND = 8   # atlas rows per fill work item (csrc/texture_shared.h TX_BAND)
+DEFAULT_LEVEL_SMOOTH = 0.1
+DEFAULT_LEVEL_ANCHOR = 1e-3
+DEFAULT_LEVEL_TOLERANCE = 1e-4
+DEFAULT_LEVEL_ITERATIONS = 500
 _NONE = EMPTY_KEY
 
 
@@ -302,6 +337,215 @@ def split_pages(atlas, packing):
     return [np.ascontiguousarray(rgb[packing.page_row[k]:packing.page_row[k + 1]]) for k in range(packing.n_pages)]
 
 
+# ----------------------------------------------------------------------------------------
+# seam levelling
+# ----------------------------------------------------------------------------------------
+def check_level_settings(level):
+    """The level settings dict checked: (smooth, anchor, tolerance, iterations)."""
+    smooth = float(level.get("smooth", DEFAULT_LEVEL_SMOOTH))
+    anchor = float(level.get("anchor", DEFAULT_LEVEL_ANCHOR))
+    tol = float(level.get("tolerance", DEFAULT_LEVEL_TOLERANCE))
+    it = level.get("iterations", DEFAULT_LEVEL_ITERATIONS)
+    if not (np.isfinite(smooth) and smooth >= 0):
+        raise ValueError("level_smooth %r must be finite and >= 0" % (smooth,))
+    if not (np.isfinite(anchor) and anchor > 0):
+        raise ValueError("level_anchor %r must be finite and > 0" % (anchor,))
+    if not 0 < tol < 1:
+        raise ValueError("level_tolerance %r must lie in (0, 1)" % (tol,))
+    if int(it) != it or int(it) < 1:
+        raise ValueError("level_iterations %r must be an integer >= 1" % (it,))
+    return smooth, anchor, tol, int(it)
+
+
+class LevelGraph(object):
+    """nodes [N] int64 (chart * n_vertices + vertex, increasing), face_nodes [m, 3] int32 (-1: no chart), seams [S] and smooth
+    [E] int64 ((i << 32) | j, i < j, distinct and increasing), and the CSR of the undirected weighted graph: row_ptr [N + 1],
+    column [nnz] int32 (increasing within a row), weight [nnz] fp32.  All on the GPU."""
+
+    def __init__(self, n_vertices, nodes, face_nodes, seams, smooth, row_ptr, column, weight):
+        self.n_vertices = int(n_vertices)
+        self.nodes, self.face_nodes, self.seams, self.smooth = nodes, face_nodes, seams, smooth
+        self.row_ptr, self.column, self.weight = row_ptr, column, weight
+
+    @property
+    def n_nodes(self):
+        return int(self.nodes.shape[0])
+
+
+def _live(keys):
+    return keys[keys != _NONE]
+
+
+def level_graph(faces, chart, n_vertices, smooth=DEFAULT_LEVEL_SMOOTH):
+    """The nodes, seam pairs, smoothness edges and CSR (LevelGraph) of the charts of `faces`."""
+    if not (isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError("faces must be [m,3] int32")
+    if faces.device.type != "cuda":
+        raise RuntimeError("faces are on %s (no CPU fallback)" % faces.device)
+    faces = faces.contiguous()
+    m, n, dev = int(faces.shape[0]), max(int(n_vertices), 1), faces.device
+    if not (isinstance(chart, torch.Tensor) and chart.dtype == torch.int32 and tuple(chart.shape) == (m,) and chart.device == dev):
+        raise ValueError("chart must be an int32 tensor of shape (%d,) on %s" % (m, dev))
+    if 3 * m >= 1 << 31:
+        raise ValueError("%d faces: 3 m < 2^31" % m)
+    chart = chart.contiguous()
+    lib = _lib.load()
+    inc = torch.empty((3 * m,), dtype=torch.int64, device=dev)
+    edge = torch.empty((3 * m,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_texture_level_incidence(_ptr(faces), m, n, _ptr(chart), _ptr(inc), _ptr(edge), _stream()),
+               "d3d_texture_level_incidence")
+    nodes = torch.unique(_live(inc))
+    live = torch.nonzero(edge != _NONE).flatten()
+    order = torch.argsort(edge[live], stable=True)
+    edge_sorted = edge[live][order].contiguous()
+    face_sorted = torch.div(live[order], 3, rounding_mode="floor").to(torch.int32).contiguous()
+    n_pairs, N = int(edge_sorted.shape[0]), int(nodes.shape[0])
+    del inc, edge, live, order
+    face_nodes = torch.empty((m, 3), dtype=torch.int32, device=dev)
+    seam = torch.empty((2 * n_pairs,), dtype=torch.int64, device=dev)
+    smooth_keys = torch.empty((3 * m,), dtype=torch.int64, device=dev)
+    _lib.check(lib.d3d_texture_level_pairs(_ptr(faces), m, n, _ptr(chart), _ptr(nodes), N, _ptr(edge_sorted), _ptr(face_sorted), n_pairs,
+                                           _ptr(face_nodes), _ptr(seam), _ptr(smooth_keys), _stream()), "d3d_texture_level_pairs")
+    seams, smooths = torch.unique(_live(seam)), torch.unique(_live(smooth_keys))
+    both = torch.cat([seams, smooths])
+    swapped = ((both & 0xffffffff) << 32) | (both >> 32)
+    entry = torch.sort(torch.cat([both, swapped])).values.contiguous()
+    nnz = int(entry.shape[0])
+    if nnz >= 1 << 31:
+        raise ValueError("%d graph entries: at most 2^31 - 1" % nnz)
+    row_ptr = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+    column = torch.empty((nnz,), dtype=torch.int32, device=dev)
+    weight = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    _lib.check(lib.d3d_texture_level_csr(_ptr(entry), nnz, _ptr(nodes), N, n, float(smooth), _ptr(row_ptr), _ptr(column), _ptr(weight),
+                                         _stream()), "d3d_texture_level_csr")
+    return LevelGraph(n, nodes, face_nodes, seams, smooths, row_ptr, column, weight)
+
+
+def _check_chart(chart, m, device):
+    """The faces' chart numbers checked, contiguous."""
+    if not (isinstance(chart, torch.Tensor) and chart.dtype == torch.int32 and tuple(chart.shape) == (m,)):
+        raise ValueError("chart must be an int32 tensor of shape (%d,)" % m)
+    if chart.device != device:
+        raise RuntimeError("chart is on %s, the mesh on %s (no CPU fallback)" % (chart.device, device))
+    return chart.contiguous()
+
+
+def _check_atlas(atlas, packing, device):
+    if not isinstance(atlas, torch.Tensor):
+        raise TypeError("atlas must be a tensor")
+    if atlas.device.type != "cuda" or atlas.device != device:
+        raise RuntimeError("atlas is on %s, the mesh on %s (no CPU fallback)" % (atlas.device, device))
+    if tuple(atlas.shape) != (int(packing.page_row[-1]), packing.page_size) or atlas.dtype != torch.int32 or not atlas.is_contiguous():
+        raise ValueError("atlas must be a contiguous int32 tensor of shape (%d, %d)" % (int(packing.page_row[-1]), packing.page_size))
+
+
+def _level_tables(table, packing, cameras, device):
+    """(table tensor, n_charts, page_row tensor, camera records, n_cams) for the levelling kernels."""
+    table = np.ascontiguousarray(table, np.int32).reshape(-1, 8)
+    t = torch.from_numpy(table if table.shape[0] else np.zeros((1, 8), np.int32)).to(device)
+    recs, nc = _table(cameras, device)
+    return t, int(table.shape[0]), torch.from_numpy(packing.page_row).to(device), recs, nc
+
+
+def level_samples(vertices, graph, table, packing, cameras, atlas):
+    """(f [N, 4], b [N, 4]) fp32 (R, G, B, 0): the nodes' taps of the filled atlas and the right-hand side."""
+    if not (isinstance(vertices, torch.Tensor) and vertices.dtype == torch.float32 and vertices.dim() == 2 and vertices.shape[1] == 3):
+        raise ValueError("vertices must be [n,3] float32")
+    if vertices.device.type != "cuda":
+        raise RuntimeError("vertices are on %s (no CPU fallback)" % vertices.device)
+    vertices, dev = vertices.contiguous(), vertices.device
+    _check_atlas(atlas, packing, dev)
+    N = graph.n_nodes
+    if N and int(vertices.shape[0]) < graph.n_vertices:
+        raise ValueError("%d vertices, the graph was built for %d" % (int(vertices.shape[0]), graph.n_vertices))
+    t, n_charts, pr, recs, nc = _level_tables(table, packing, cameras, dev)
+    f = torch.zeros((N, 4), dtype=torch.float32, device=dev)
+    b = torch.zeros((N, 4), dtype=torch.float32, device=dev)
+    rc = _lib.load().d3d_texture_level_samples(_ptr(vertices), graph.n_vertices, _ptr(graph.nodes), N, _ptr(graph.row_ptr),
+                                               _ptr(graph.column), int(graph.column.shape[0]), _ptr(t), n_charts, _ptr(pr), packing.n_pages,
+                                               _ptr(recs), nc, packing.page_size, _ptr(atlas), _ptr(f), _ptr(b), _stream())
+    _lib.check(rc, "d3d_texture_level_samples")
+    return f, b
+
+
+def level_solve(graph, b, anchor=DEFAULT_LEVEL_ANCHOR, tolerance=DEFAULT_LEVEL_TOLERANCE, iterations=DEFAULT_LEVEL_ITERATIONS):
+    """(g [N, 4] fp32, iterations run, True when every channel met the tolerance): conjugate gradients for (L + anchor I) g = b."""
+    N, dev = graph.n_nodes, graph.nodes.device
+    if not (isinstance(b, torch.Tensor) and b.dtype == torch.float32 and tuple(b.shape) == (N, 4) and b.is_contiguous()):
+        raise ValueError("b must be a contiguous float32 tensor of shape (%d, 4)" % N)
+    if b.device != dev:
+        raise RuntimeError("b is on %s, the graph on %s (no CPU fallback)" % (b.device, dev))
+    _, anchor, tolerance, iterations = check_level_settings({"anchor": anchor, "tolerance": tolerance, "iterations": iterations})
+    lib = _lib.load()
+    scratch, nbytes = _geom.scratch(lib.d3d_texture_level_scratch_bytes, N, device=dev)
+    g = torch.zeros((N, 4), dtype=torch.float32, device=dev)
+    it, ok = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib.d3d_texture_level_solve(_ptr(graph.row_ptr), _ptr(graph.column), _ptr(graph.weight), int(graph.column.shape[0]), _ptr(b), N,
+                                     anchor, tolerance, iterations, _ptr(scratch), nbytes, _ptr(g), ctypes.byref(it), ctypes.byref(ok),
+                                     _stream())
+    _lib.check(rc, "d3d_texture_level_solve")
+    return g, it.value, bool(ok.value)
+
+
+def level_coverage(vertices, faces, chart, table, packing, cameras):
+    """cover [atlas rows, page_size] int64: per texel the smallest (bits(fp32(d2)) << 32) | face, INT64_MAX where no face covers."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    dev = vertices.device
+    chart = _check_chart(chart, m, dev)
+    t, n_charts, pr, recs, nc = _level_tables(table, packing, cameras, dev)
+    cover = torch.full((int(packing.page_row[-1]), packing.page_size), EMPTY_KEY, dtype=torch.int64, device=dev)
+    rc = _lib.load().d3d_texture_level_cover(_ptr(vertices), n, _ptr(faces), m, _ptr(chart), _ptr(t), n_charts, _ptr(pr),
+                                             packing.n_pages, _ptr(recs), nc, packing.page_size, _ptr(cover), _stream())
+    _lib.check(rc, "d3d_texture_level_cover")
+    return cover
+
+
+def level_apply(vertices, faces, chart, graph, g, cover, table, packing, cameras, atlas):
+    """Adds the correction to every covered texel of atlas, in place.  Returns atlas."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    dev = vertices.device
+    chart = _check_chart(chart, m, dev)
+    _check_atlas(atlas, packing, dev)
+    N = graph.n_nodes
+    if not (isinstance(g, torch.Tensor) and g.dtype == torch.float32 and tuple(g.shape) == (N, 4) and g.is_contiguous() and g.device == dev):
+        raise ValueError("g must be a contiguous float32 tensor of shape (%d, 4) on %s" % (N, dev))
+    if not (isinstance(cover, torch.Tensor) and cover.dtype == torch.int64 and cover.shape == atlas.shape and cover.is_contiguous() and
+            cover.device == dev):
+        raise ValueError("cover must be a contiguous int64 tensor of the atlas's shape on %s" % dev)
+    tb = np.ascontiguousarray(table, np.int32).reshape(-1, 8)
+    nb = (tb[:, 3].astype(np.int64) + BAND - 1) // BAND
+    work = np.stack([np.repeat(np.arange(tb.shape[0]), nb), np.arange(int(nb.sum())) - np.repeat(np.cumsum(nb) - nb, nb)], 1)
+    if not work.shape[0] or not N:
+        return atlas
+    t, n_charts, pr, recs, nc = _level_tables(table, packing, cameras, dev)
+    w = torch.from_numpy(np.ascontiguousarray(work, np.int32)).to(dev)
+    rc = _lib.load().d3d_texture_level_apply(_ptr(w), int(w.shape[0]), _ptr(vertices), n, _ptr(faces), m, _ptr(chart),
+                                             _ptr(graph.face_nodes), _ptr(g), N, _ptr(t), n_charts, _ptr(pr), packing.n_pages, _ptr(recs),
+                                             nc, packing.page_size, _ptr(cover), _ptr(atlas), _stream())
+    _lib.check(rc, "d3d_texture_level_apply")
+    return atlas
+
+
+def level_pages(vertices, faces, key, chart, table, packing, cameras, atlas, smooth=DEFAULT_LEVEL_SMOOTH, anchor=DEFAULT_LEVEL_ANCHOR,
+                tolerance=DEFAULT_LEVEL_TOLERANCE, iterations=DEFAULT_LEVEL_ITERATIONS):
+    """Levels the seams of the filled (and merged) atlas in place, before finish_pages.  cameras: every winning view.  Returns
+    {"nodes", "seams", "iterations", "converged"}."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    _check_key(key, m, vertices.device)
+    _check_atlas(atlas, packing, vertices.device)
+    smooth, anchor, tolerance, iterations = check_level_settings({"smooth": smooth, "anchor": anchor, "tolerance": tolerance,
+                                                                  "iterations": iterations})
+    graph = level_graph(faces, chart, n, smooth)
+    info = {"nodes": graph.n_nodes, "seams": int(graph.seams.shape[0]), "iterations": 0, "converged": True}
+    if not info["seams"]:   # b = 0: g = 0, every texel keeps its colour
+        return info
+    _, b = level_samples(vertices, graph, table, packing, cameras, atlas)
+    g, info["iterations"], info["converged"] = level_solve(graph, b, anchor, tolerance, iterations)
+    cover = level_coverage(vertices, faces, chart, table, packing, cameras)
+    level_apply(vertices, faces, chart, graph, g, cover, table, packing, cameras, atlas)
+    return info
+
+
 def texcoords(vertices, faces, key, chart, table, packing, cameras):
     """(texcoord [m, 6] fp32, texnumber [m] int32) on the GPU."""
     vertices, faces, n, m = _mesh_arrays(vertices, faces)
@@ -332,17 +576,25 @@ def layout(vertices, faces, key, cameras, page_size=DEFAULT_PAGE, pad=DEFAULT_PA
 
 
 def texture_mesh(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, views_per_batch=None, page_size=DEFAULT_PAGE,
-                 pad=DEFAULT_PAD, empty_color=EMPTY_COLOR):
+                 pad=DEFAULT_PAD, empty_color=EMPTY_COLOR, level=None):
     """Every pass on one process: {"key", "chart", "labels", "rects", "packing", "table", "pages" (host RGB8 arrays),
-    "texcoord", "texnumber"}."""
+    "texcoord", "texnumber"}.  level: None, or the seam levelling's settings {"smooth", "anchor", "tolerance", "iterations"}
+    (check_level_settings; {} for the defaults); the result then has "level" (level_pages' dict)."""
     views = _check_views(views)
     check_page_size(page_size, views)
+    if level is not None:
+        smooth, anchor, tolerance, iterations = check_level_settings(level)
     key = select_faces(vertices, faces, views, depth_tolerance, views_per_batch)
     chart, labels, rects, packing, table = layout(vertices, faces, key, views, page_size, pad)
-    atlas = finish_pages(fill_pages(table, packing, views, new_atlas(packing, vertices.device)), empty_color)
+    atlas = fill_pages(table, packing, views, new_atlas(packing, vertices.device))
+    res = {}
+    if level is not None:
+        res["level"] = level_pages(vertices, faces, key, chart, table, packing, views, atlas, smooth, anchor, tolerance, iterations)
+    atlas = finish_pages(atlas, empty_color)
     tc, tn = texcoords(vertices, faces, key, chart, table, packing, views)
-    return {"key": key, "chart": chart, "labels": labels, "rects": rects, "packing": packing, "table": table,
-            "pages": split_pages(atlas, packing), "texcoord": tc, "texnumber": tn}
+    res.update({"key": key, "chart": chart, "labels": labels, "rects": rects, "packing": packing, "table": table,
+                "pages": split_pages(atlas, packing), "texcoord": tc, "texnumber": tn})
+    return res
 
 
 # ----------------------------------------------------------------------------------------
@@ -432,6 +684,14 @@ def add_arguments(ap, prefix=""):
     ap.add_argument("--%sviews_per_batch" % prefix, type=int, default=None, help="views per selection call (default: all)")
     ap.add_argument("--%spage_size" % prefix, type=int, default=DEFAULT_PAGE, help="texture page width (>= every image's width and height)")
     ap.add_argument("--%spad" % prefix, type=int, default=DEFAULT_PAD, help="pixels of margin around every chart's rect (>= 1)")
+    ap.add_argument("--%slevel" % prefix, action="store_true",
+                    help="level the colour seams between charts of different views (one smooth additive correction per chart)")
+    ap.add_argument("--%slevel_smooth" % prefix, type=float, default=DEFAULT_LEVEL_SMOOTH,
+                    help="weight of the correction's smoothness inside a chart (>= 0)")
+    ap.add_argument("--%slevel_anchor" % prefix, type=float, default=DEFAULT_LEVEL_ANCHOR, help="weight that pulls the correction to 0 (> 0)")
+    ap.add_argument("--%slevel_tolerance" % prefix, type=float, default=DEFAULT_LEVEL_TOLERANCE,
+                    help="the solve stops at |r| <= this * |b| (in (0, 1))")
+    ap.add_argument("--%slevel_iterations" % prefix, type=int, default=DEFAULT_LEVEL_ITERATIONS, help="at most this many iterations (>= 1)")
 
 
 def check_settings(settings):
@@ -450,14 +710,16 @@ def check_args(ap, a, prefix=""):
 
 def settings_from_args(a, path, prefix=""):
     g = lambda k: getattr(a, prefix + k)
+    level = {"smooth": g("level_smooth"), "anchor": g("level_anchor"), "tolerance": g("level_tolerance"), "iterations": g("level_iterations")}
+    check_level_settings(level)   # the numbers are checked whether or not --level is given
     return {"path": path, "depth_tolerance": g("depth_tolerance"), "views_per_batch": g("views_per_batch"), "page_size": g("page_size"),
-            "pad": g("pad")}
+            "pad": g("pad"), "level": level if g("level") else None}
 
 
 def build_and_write(vertices, faces, views, settings):
     """texture_mesh with the settings dict, written to settings["path"]: the result dict."""
     tol, vpb, P, pad = check_settings(settings)
-    res = texture_mesh(vertices, faces, views, tol, vpb, P, pad)
+    res = texture_mesh(vertices, faces, views, tol, vpb, P, pad, level=settings.get("level"))
     write_textured_ply(settings["path"], vertices, faces, res["texcoord"], res["texnumber"], res["pages"])
     return res
 
@@ -483,6 +745,9 @@ def main(argv=None):
     res = build_and_write(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), views, settings_from_args(a, a.out))
     print("textured mesh %s: %d faces, %d charts, %d pages, %d views" % (a.out, f.shape[0], int(res["labels"].shape[0]),
                                                                         res["packing"].n_pages, len(views)))
+    if "level" in res:
+        print("levelled %d seam pairs over %d nodes in %d iterations%s" % (res["level"]["seams"], res["level"]["nodes"], res["level"]["iterations"],
+                                                                          "" if res["level"]["converged"] else " (not converged)"))
     return a.out
 
 

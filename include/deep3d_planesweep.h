@@ -1229,6 +1229,70 @@ int d3d_texture_texcoords(const float* vertices, long long n_vertices, const int
                           const d3d_ortho_view_t* cams, int n_cams, int page_width, float* texcoord, int* texnumber,
                           d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.18 -- levelling the colour seams between the texture's charts (deep3d_aerial_amd/texture.py states the rules in
+ * full; they are this project's).  A node is a distinct (chart, vertex) pair over the corners of faces with a chart, its key
+ * chart * n_vertices + vertex (int64); nodes [n_nodes] holds the keys in increasing order and a node's number is its index.
+ * f, b and g are [n_nodes, 4] fp32 records (R, G, B, 0).  table, page_row, cams and atlas are d3d_texture_fill's.  Every pointer
+ * is DEVICE memory except d3d_texture_level_solve's `iterations` and `converged`.  No float atomics; the one integer atomic is
+ * the coverage's 64-bit min.
+ */
+/* Scratch of d3d_texture_level_solve (0 for an out-of-range argument). */
+size_t d3d_texture_level_scratch_bytes(long long n_nodes);
+
+/* d3d_texture_level_incidence: incidence [3 n_faces] int64 = the node key of each corner of a face with chart[f] >= 0, INT64_MAX
+ *   otherwise; edge_key [3 n_faces] int64 = the distinct edges of EVERY face as min(i,j) * n_vertices + max(i,j) (d3d_texture_edges
+ *   lists only faces with a winner), INT64_MAX in unused slots. */
+int d3d_texture_level_incidence(const int* faces, long long n_faces, long long n_vertices, const int* chart, long long* incidence,
+                                long long* edge_key, d3d_stream_t stream);
+
+/* d3d_texture_level_pairs: face_node [3 n_faces] int32 = the node of each corner (-1: no chart).  edge_sorted / face_sorted
+ *   [n_pairs]: the (edge key, face) pairs sorted by edge key.  seam [2 n_pairs] int64: the first pair of a run of exactly two
+ *   pairs whose faces have different charts c1 < c2 (both >= 0) writes (node(c1, v) << 32) | node(c2, v) for the edge's two ends
+ *   v; every other slot gets INT64_MAX.  smooth [3 n_faces] int64: (min << 32) | max over the distinct edges between the corner
+ *   nodes of a face with a chart, INT64_MAX otherwise.  The caller makes each list distinct and sorted. */
+int d3d_texture_level_pairs(const int* faces, long long n_faces, long long n_vertices, const int* chart, const long long* nodes,
+                            long long n_nodes, const long long* edge_sorted, const int* face_sorted, long long n_pairs, int* face_node,
+                            long long* seam, long long* smooth, d3d_stream_t stream);
+
+/* d3d_texture_level_csr: entry [n_entries] int64 = (row << 32) | column, sorted: every seam pair and smoothness edge in both
+ *   directions.  row_ptr [n_nodes + 1], column [n_entries] int32, weight [n_entries] fp32 = 1 between nodes of different charts,
+ *   `smooth` (lambda >= 0) inside a chart. */
+int d3d_texture_level_csr(const long long* entry, long long n_entries, const long long* nodes, long long n_nodes, long long n_vertices,
+                          float smooth, int* row_ptr, int* column, float* weight, d3d_stream_t stream);
+
+/* d3d_texture_level_samples: f[node] = the bilinear tap of atlas at x = (u - x0) + ox, y = ((v - y0) + oy) + page_row of the
+ *   node's vertex in its chart's view, in fp64 ((w00 c00 + w10 c10) + w01 c01) + w11 c11 per channel, rounded to fp32; the taps
+ *   are clamped to the chart's rect.  b[i] = the sum over row i's entries j of another chart, in column order, of f[j] - f[i],
+ *   in fp32. */
+int d3d_texture_level_samples(const float* vertices, long long n_vertices, const long long* nodes, long long n_nodes, const int* row_ptr,
+                              const int* column, long long n_entries, const int* table, long long n_charts, const long long* page_row,
+                              int n_pages, const d3d_ortho_view_t* cams, int n_cams, int page_width, const unsigned int* atlas, float* f,
+                              float* b, d3d_stream_t stream);
+
+/* d3d_texture_level_solve: conjugate gradients for (L + anchor I) g = b from g = 0, per channel, on fp32 vectors with fp64 dot
+ *   products folded from fixed slots in slot order (the same bits on every run).  A channel stops, and is frozen, once
+ *   r . r <= tolerance^2 b . b; the solve stops when every channel has, or after max_iterations.  The host reads the state once
+ *   per 16 iterations.  iterations, converged: HOST ints.  scratch: d3d_texture_level_scratch_bytes(n_nodes) bytes. */
+int d3d_texture_level_solve(const int* row_ptr, const int* column, const float* weight, long long n_entries, const float* b,
+                            long long n_nodes, float anchor, double tolerance, int max_iterations, void* scratch, size_t scratch_bytes,
+                            float* g, int* iterations, int* converged, d3d_stream_t stream);
+
+/* d3d_texture_level_cover: MIN-MERGES into cover [atlas rows, page_width] int64 (INT64_MAX before) the key
+ *   (bits(fp32(d2)) << 32) | face of every face with a chart at every texel of its chart's rect whose centre lies within d2 <= 2
+ *   of the face's projected triangle (fp64, texel coordinates X = (u - x0) + ox, Y = (v - y0) + oy; d2 = 0 inside). */
+int d3d_texture_level_cover(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* chart,
+                            const int* table, long long n_charts, const long long* page_row, int n_pages, const d3d_ortho_view_t* cams,
+                            int n_cams, int page_width, long long* cover, d3d_stream_t stream);
+
+/* d3d_texture_level_apply: work [n_work, 2] int32 lists (chart, band) as d3d_texture_fill's.  A covered texel's channels become
+ *   clamp(rint(colour + ((w0 g0 + w1 g1) + w2 g2)), 0, 255) in fp32, w the barycentric weights (fp64, rounded to fp32) of the
+ *   closest point of the covering face, g0 .. g2 its corner nodes' g; alpha is unchanged. */
+int d3d_texture_level_apply(const int* work, long long n_work, const float* vertices, long long n_vertices, const int* faces,
+                            long long n_faces, const int* chart, const int* face_node, const float* g, long long n_nodes, const int* table,
+                            long long n_charts, const long long* page_row, int n_pages, const d3d_ortho_view_t* cams, int n_cams,
+                            int page_width, const long long* cover, unsigned int* atlas, d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,9 @@
 """The texturing kernels (csrc/texture.hip) at survey size: the meshes of tools/mesh_bench.py's scenes (0.5 m and 0.25 m voxels,
 V = 32 and V = 128 views of 2752 x 1856) textured from the same views with synthetic images.  Device-event times of select,
 charts, rects, fill (with the empty-colour pass) and texcoords; faces, charts, pages and candidate views per face; and a per-view
-fp64 torch version of select, checked for the same keys.
+fp64 torch version of select, checked for the same keys.  The `level` entry times the seam levelling (csrc/texture_level.hip) on the
+same atlas: graph, samples, solve (with its iteration count), coverage and apply, and beside the solve a torch restatement of the
+same iteration (index_add per iteration) on the same graph, per iteration.
 
     python tools/texture_bench.py [--iters 3] [--views 32,128] [--voxels 0.5,0.25] [--out profiles/texture_bench.json]"""
 import argparse
@@ -72,6 +74,49 @@ def torch_select(vertices, faces, views, tol=texture.DEFAULT_TOLERANCE):
     return key
 
 
+def torch_cg(graph, b, anchor, iterations):
+    """The comparator: the solve's iteration in torch on the same CSR (fp32 vectors, fp64 dots, index_add for the row sums), for
+    a fixed number of iterations.  Returns x."""
+    N = graph.n_nodes
+    row = torch.repeat_interleave(torch.arange(N, device=b.device), (graph.row_ptr[1:] - graph.row_ptr[:-1]).long())
+    col, w = graph.column.long(), graph.weight[:, None]
+    dm = torch.zeros((N, 1), device=b.device).index_add_(0, row, w) + anchor
+    x, r = torch.zeros_like(b), b.clone()
+    p, q = torch.zeros_like(b), torch.zeros_like(b)
+    rr = (r.double() * r.double()).sum(0)
+    beta = torch.zeros((4,), device=b.device)
+    for _ in range(iterations):
+        s = dm * r - torch.zeros_like(r).index_add_(0, row, w * r[col])
+        q = s + beta * q
+        p = r + beta * p
+        alpha = torch.nan_to_num(rr / (p.double() * q.double()).sum(0)).float()
+        x = x + alpha * p
+        r = r - alpha * q
+        t = (r.double() * r.double()).sum(0)
+        beta, rr = torch.nan_to_num(t / rr).float(), t
+    return x
+
+
+def level_times(vertices, faces, key, chart, table, packing, ov, atlas, iters):
+    """Device-event times of the levelling's passes on the filled atlas (which the apply changes; it is not used afterwards)."""
+    out = {}
+    n = int(vertices.shape[0])
+    t_graph = MB.timed_ms(lambda: out.update(g=texture.level_graph(faces, chart, n)), iters)   # includes torch's sorts and uniques
+    graph = out["g"]
+    t_samples = MB.timed_ms(lambda: out.update(fb=texture.level_samples(vertices, graph, table, packing, ov, atlas)), iters)
+    b = out["fb"][1]
+    t_solve = MB.timed_ms(lambda: out.update(s=texture.level_solve(graph, b)), iters)   # includes its state reads and syncs
+    g, it, ok = out["s"]
+    t_cover = MB.timed_ms(lambda: out.update(c=texture.level_coverage(vertices, faces, chart, table, packing, ov)), iters)
+    t_apply = MB.timed_ms(lambda: texture.level_apply(vertices, faces, chart, graph, g, out["c"], table, packing, ov, atlas), iters)
+    k = 16
+    t_torch = MB.timed_ms(lambda: torch_cg(graph, b, texture.DEFAULT_LEVEL_ANCHOR, k), iters)
+    return {"nodes": graph.n_nodes, "seam_pairs": int(graph.seams.shape[0]), "entries": int(graph.column.shape[0]),
+            "graph_ms": round(t_graph, 3), "samples_ms": round(t_samples, 3), "solve_ms": round(t_solve, 3), "solve_iterations": it,
+            "solve_converged": ok, "solve_ms_per_iteration": round(t_solve / max(it, 1), 4), "coverage_ms": round(t_cover, 3),
+            "apply_ms": round(t_apply, 3), "torch_ms_per_iteration": round(t_torch / k, 4)}
+
+
 def run(views, voxel, iters):
     grid = mesh.MeshGrid(MB.BORDER, voxel)
     mviews = views
@@ -112,7 +157,9 @@ def run(views, voxel, iters):
     tk = torch_select(vertices, faces, ov)
     e1.record()
     torch.cuda.synchronize()
-    return {"views": len(ov), "voxel_m": voxel, "faces": m, "vertices": n, "seen_faces": int((key != texture.EMPTY_KEY).sum()),
+    texture.fill_pages(table, packing, ov, atlas.zero_())
+    level = level_times(vertices, faces, key, chart, table, packing, ov, atlas, iters)
+    return {"level": level, "views": len(ov), "voxel_m": voxel, "faces": m, "vertices": n, "seen_faces": int((key != texture.EMPTY_KEY).sum()),
             "charts": nc, "pages": packing.n_pages, "atlas_texels": int(atlas.numel()), "mean_candidates_per_face": round(float(cand.double().mean()), 3),
             "select_ms": round(t_select, 3), "charts_ms": round(t_charts, 3), "rects_ms": round(t_rects, 3), "fill_ms": round(t_fill, 3),
             "texcoords_ms": round(t_tc, 3), "torch_select_ms": round(e0.elapsed_time(e1), 1), "torch_same_keys": bool(torch.equal(tk, key)),
