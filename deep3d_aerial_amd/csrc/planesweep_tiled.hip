@@ -8,6 +8,8 @@
 //   * One workgroup (10 compute + 2 loader waves) = a 32 x 4 patch of reference pixels x a segment
 //     of depth planes x a group of CH channels.  It walks the segment in STEPS of SP = NSUB*m
 //     planes: compute wave (pw, sub) owns two patch rows and the planes d = step*SP + sub + NSUB*j.
+//     A last patch column with at most 16 real pixels per row is swept in 16 x 8 patches instead (half as many workgroups
+//     there, none of them half empty): same lanes, same loop, another lane -> pixel map.
 //   * The source footprint of (patch x step) is bounded per view by projecting the 8 corners of
 //     the frustum slab (valid because the map is projective and p.z > 0 at every corner).  All
 //     step windows of the segment are planned ONCE in the prologue, one lane per step.
@@ -121,6 +123,7 @@ struct TiledArgs {
     int cap_floats;  // floats available for the rings
     int nseg;        // segments along depth
     int tiles_x, tiles_y;
+    int tall;        // 1: the last patch column holds at most TW/2 real pixels per row and is swept in TALL patches (see the block decode)
     const float* cl;  // channel-last copy of the source maps [view][group][h*w][CH] (pack_channel_last_kernel), or null
     unsigned long long* tstats;  // debug timing (cycles, wave 0): [0] prologue [1] barrierA+write+barrierB [2] issue [3] compute [4] total
     unsigned* stats;  // debug (D3D_TILED_STATS): [0] ring wgs [1] fallback wgs [2] sum m [3] sum nsteps [4] sum ring floats [5] overflow items
@@ -326,25 +329,38 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
     // Within an XCD's run, vertically adjacent patches come first: they share most of their source
     // rows (same depth segment, same channel group), so the windows of the ~32 workgroups an XCD runs
     // concurrently overlap in its L2 instead of each being fetched from HBM.
-    const int ty = b % a.tiles_y;
-    const int seg = (b / a.tiles_y) % a.nseg;
-    const int tx = b / (a.tiles_y * a.nseg);
+    // TALL patches: when the last patch column holds at most TW/2 real pixels per row (a.tall; 464 = 14 * 32 + 16), a TW-wide
+    // patch there would issue every instruction of the plane loop for half a patch of EXEC-masked lanes.  Two vertically
+    // adjacent half-empty patches are folded into one patch of TW/2 x 2 TH pixels instead: the column takes ceil(tiles_y / 2)
+    // workgroups per segment, which follow the wide columns in the logical order (vertically adjacent ones still adjacent).
+    // `tall` is wave-uniform and only read here and by the planner: the plane loop sees nothing but its lanes' pixels.
+    const int nwide = a.tall ? (a.tiles_x - 1) * a.tiles_y * a.nseg : 0x7fffffff;
+    const bool tall = b >= nwide;
+    if (tall) b -= nwide;
+    const int tyn = tall ? (a.tiles_y + 1) >> 1 : a.tiles_y;   // patches per column
+    const int PW = tall ? TW / 2 : TW, PH = tall ? 2 * TH : TH;   // this workgroup's patch rectangle
+    const int pwsh = tall ? 4 : 5;   // log2(PW)
+    const int ty = b % tyn;
+    const int seg = (b / tyn) % a.nseg;
+    const int tx = tall ? a.tiles_x - 1 : b / (tyn * a.nseg);
     // The workgroup sweeps ALL channel groups of its (patch, depth segment), one after the other: the plan (windows,
     // step size, staging rectangles) does not depend on the channels, so the prologue is paid once.
-    const int x0 = tx * TW, y0 = ty * TH;
+    const int x0 = tx * TW, y0 = ty * PH;
     const int ds = seg * a.dseg;
     const int de = min(ds + a.dseg, D);
     const int nplanes = de - ds;
-    const int x1c = min(x0 + TW - 1, w - 1), y1c = min(y0 + TH - 1, h - 1);
+    const int x1c = min(x0 + PW - 1, w - 1), y1c = min(y0 + PH - 1, h - 1);
 
     // Lane -> pixel.  ds_read_b128 is serviced in the lane groups {0-3,12-15,20-27} and
     // {4-11,16-19,28-31} (+32; confirmed with tools/lds_groups.hip): each group takes an 8 x 2 block of
     // pixels (bank layout: see ring_row_floats).  Lanes 0-15 / 16-31 / 32-47 / 48-63 each hold 16
     // consecutive pixels of one row, so a store instruction still writes whole 64-byte row segments.
+    // Lanes 32-63 repeat the 16 x 2 block of lanes 0-31 sixteen columns to the right -- in a tall patch TH rows further
+    // down: a pixel wave then owns the rows {2 pw, 2 pw + 1} and {2 pw + TH, 2 pw + TH + 1}, 16 pixels each.
     const int l5 = lane & 31;
     const int pxl = (l5 < 4) ? l5 : (l5 < 12) ? l5 + 4 : (l5 < 20) ? l5 - 8 : (l5 < 28) ? l5 - 20 : l5 - 16;
-    const int px = x0 + pxl + 16 * (lane >> 5);
-    const int py = y0 + pw * 2 + (l5 >> 4);
+    const int px = x0 + pxl + (tall ? 0 : 16 * (lane >> 5));
+    const int py = y0 + pw * 2 + (l5 >> 4) + (tall ? TH * (lane >> 5) : 0);
     const bool valid = (px < w) && (py < h);
     const int pix = valid ? py * w + px : 0;
     const unsigned pixb = (unsigned)pix * (unsigned)sizeof(T);  // per-lane byte offset (h*w < 2^30)
@@ -431,7 +447,7 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
 #pragma unroll
         for (int k = 0; k < (TW * TH) / 64; ++k) {
             const int q = lane + 64 * k;
-            const int qx = x0 + (q & 31), qy = y0 + (q >> 5);
+            const int qx = x0 + (q & (PW - 1)), qy = y0 + (q >> pwsh);
             bok[k] = qx < w && qy < h;
             const size_t qi = bok[k] ? (size_t)qy * w + qx : 0;
             blo[k] = p.depth[qi];
@@ -457,7 +473,7 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
 #pragma unroll
             for (int k = 0; k < (TW * TH) / 64; ++k) {
                 int q = lane + 64 * k;
-                int qx = x0 + (q & 31), qy = y0 + (q >> 5);
+                int qx = x0 + (q & (PW - 1)), qy = y0 + (q >> pwsh);
                 if (qx < w && qy < h) {
                     float dv = p.depth[(size_t)(ds + i) * plane + (size_t)qy * w + qx];
                     lo = fminf(lo, dv);
@@ -1408,9 +1424,15 @@ static int launch_one(const SweepParams& p, hipStream_t stream) {
     a.ngroups = p.C / CH;
     a.tiles_x = ceil_div(p.w, TW);
     a.tiles_y = ceil_div(p.h, THK);
+    // a last column of at most TW/2 real pixels per row is swept in patches of TW/2 x 2 THK pixels: half as many workgroups there
+    a.tall = (p.w % TW >= 1 && p.w % TW <= TW / 2) ? 1 : 0;
     a.cap_floats = LDS_BYTES / 4 - L::DATA;
-    segments(p.D, (long)a.tiles_x * a.tiles_y * a.ngroups, a.dseg, a.nseg);
-    const long nblk = (long)a.tiles_x * a.tiles_y * a.nseg;  // a workgroup sweeps every channel group of its patch
+#ifdef D3D_EXPERIMENTS
+    if (const char* e = getenv("D3D_TILED_TALL")) a.tall = a.tall && atoi(e) != 0;   // A/B: 0 = wide patches in every column
+#endif
+    segments(p.D, (long)a.tiles_x * a.tiles_y * a.ngroups, a.dseg, a.nseg);   // (segment length: as for wide patches throughout)
+    const long col_tiles = a.tall ? (long)(a.tiles_x - 1) * a.tiles_y + (a.tiles_y + 1) / 2 : (long)a.tiles_x * a.tiles_y;
+    const long nblk = col_tiles * a.nseg;  // a workgroup sweeps every channel group of its patch
     if (nblk > 0x7fffffffL) return D3D_ERR_UNSUPPORTED;
     a.stats = nullptr;
     a.tstats = nullptr;

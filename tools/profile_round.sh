@@ -4,19 +4,28 @@
 # Outputs under gpurun_out/<round>/ ; the summary (with the SHA-256 of the kernel's machine code it was taken from) is what gets
 # copied to profiles/pmc_latest.json -- bench.py reports `roofline.traffic` only while the kernel's machine code in the built
 # library hashes to what this profile recorded (_lib.kernel_code_sha256).  Make this the LAST GPU action of a round.
+# Every GPU step runs under a time limit of its own and the script stops at the first step that fails: nothing more is started
+# on a card after a fault, an abort or a hang.
 R=${1:-r02}
 out=$GRAFT_REPO_ROOT/gpurun_out/$R
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
-python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+exec 3>&1
+step() {   # step SECONDS command...
+    local lim=$1; shift
+    timeout -k 10 $lim "$@"
+    local rc=$?
+    if [ $rc -ne 0 ]; then echo "profile_round: '$1 $2 $3 ...' ended with status $rc: stopping here" >&3; exit $rc; fi
+}
+step 700 python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 tail -1 $out/bench.json | cut -c1-300
 cd /tmp && export TMPDIR=/tmp
 B="python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- $B --steps 20 --warmup 5 > $out/trace.log 2>&1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- $B --steps 3 --warmup 1 > $out/pmc_fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- $B --steps 3 --warmup 1 > $out/pmc_write.log 2>&1
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $out/pmc_sq -- $B --steps 3 --warmup 1 > $out/pmc_sq.log 2>&1
-rocprofv3 --pmc SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_INT32 SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $out/pmc_sq2 -- $B --steps 3 --warmup 1 > $out/pmc_sq2.log 2>&1
+step 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- $B --steps 20 --warmup 5 > $out/trace.log 2>&1
+step 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- $B --steps 3 --warmup 1 > $out/pmc_fetch.log 2>&1
+step 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- $B --steps 3 --warmup 1 > $out/pmc_write.log 2>&1
+step 240 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $out/pmc_sq -- $B --steps 3 --warmup 1 > $out/pmc_sq.log 2>&1
+step 240 rocprofv3 --pmc SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_INT32 SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $out/pmc_sq2 -- $B --steps 3 --warmup 1 > $out/pmc_sq2.log 2>&1
 cp $out/trace/*/*kernel_stats.csv $out/kernel_stats.csv 2>/dev/null
 python3 - <<PY
 import csv, glob, collections, json, hashlib, sys
