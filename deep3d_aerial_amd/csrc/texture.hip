@@ -94,19 +94,8 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_select_kernel(const float* __rest
                                                              long m, const d3d_ortho_view_t* __restrict__ views, int n_words, double tol1,
                                                              const unsigned long long* __restrict__ mask, long long* __restrict__ key) {
     const long f = (long)blockIdx.x * TX_BLOCK + threadIdx.x;
-    TxFace F;
-    bool live = f < m && tx_face(vertices, faces, f, n, &F);
-    double nrm[3] = {0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
-    if (live) {
-        const double e1[3] = {F.b[0] - F.a[0], F.b[1] - F.a[1], F.b[2] - F.a[2]};
-        const double e2[3] = {F.c[0] - F.a[0], F.c[1] - F.a[1], F.c[2] - F.a[2]};
-        nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
-        nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
-        nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) g[k] = ((F.a[k] + F.b[k]) + F.c[k]) / 3.0;
-        live = nrm[0] != 0.0 || nrm[1] != 0.0 || nrm[2] != 0.0;
-    }
+    TxFrame T;
+    const bool live = tx_frame(vertices, faces, f, m, n, &T);
     long long best = live ? key[f] : TX_EMPTY;
     const unsigned long long* mk = mask + (long)blockIdx.x * n_words;
     for (int w = 0; w < n_words; ++w) {
@@ -114,27 +103,8 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_select_kernel(const float* __rest
         while (bits) {
             const int vi = __builtin_amdgcn_readfirstlane(w * 64 + __builtin_ctzll(bits));
             bits &= bits - 1;
-            if (!live) continue;
-            const d3d_ortho_view_t& V = views[vi];
-            // front-facing: nrm . (C - g) > 0
-            const double dot = nrm[0] * (V.C[0] - g[0]) + nrm[1] * (V.C[1] - g[1]) + nrm[2] * (V.C[2] - g[2]);
-            if (!(dot > 0.0)) continue;
-            double ua, va, ub, vb, uc, vc, p2;
-            if (!ortho_uv(V, F.a[0], F.a[1], F.a[2], &ua, &va, &p2)) continue;
-            if (!ortho_uv(V, F.b[0], F.b[1], F.b[2], &ub, &vb, &p2)) continue;
-            if (!ortho_uv(V, F.c[0], F.c[1], F.c[2], &uc, &vc, &p2)) continue;
-            const GeomPq r = geom_project(V, g[0], g[1], g[2]);
-            const double ug = r.q0 / r.q2, vg = r.q1 / r.q2;
-            const int px = min(max((int)floor(fmin(fmax(ug + 0.5, 0.0), (double)V.W)), 0), V.W - 1);
-            const int py = min(max((int)floor(fmin(fmax(vg + 0.5, 0.0), (double)V.H)), 0), V.H - 1);
-            const float D = V.depth[(long)py * V.W + px];
-            if (!(isfinite(D) && D > 0.0f && r.p2 <= (double)D * tol1)) continue;
-            const double A = 0.5 * fabs((ub - ua) * (vc - va) - (uc - ua) * (vb - va));
-            if (!(A != 0.0)) continue;
-            const double s = 1.0 / A;
-            if (!isfinite(s)) continue;
-            const long long k = ((long long)__float_as_uint((float)s) << 32) | (long long)(unsigned)V.id;
-            best = k < best ? k : best;
+            long long k;
+            if (live && tx_view_key(views[vi], T, tol1, &k)) best = k < best ? k : best;
         }
     }
     if (live) key[f] = best;
@@ -322,9 +292,16 @@ static TxScratch tx_chart_layout(long long m) {
     return s;
 }
 
-static size_t tx_mask_bytes(long long m, int n_views) { return (size_t)ceil_div(m, TX_BLOCK) * ceil_div(n_views, 64) * 8; }
-
 static bool tx_sizes_ok(long long n, long long m) { return n >= 0 && n < (1ll << 31) && m >= 0 && 3 * m < (1ll << 31); }
+
+int tx_cull(const float* vertices, long long n, const int* faces, long long m, const d3d_ortho_view_t* views, int n_views,
+            unsigned long long* mask, hipStream_t st) {
+    const long n_blocks = ceil_div(m, TX_BLOCK);
+    hipLaunchKernelGGL(tx_cull_kernel, dim3(ceil_div(n_blocks, TX_BLOCK / 64)), dim3(TX_BLOCK), 0, st, vertices, n, faces, (long)m, n_blocks,
+                       views, n_views, ceil_div(n_views, 64), mask);
+    D3D_LAUNCH_CHECK("tx_cull_kernel launch");
+    return D3D_OK;
+}
 
 }  // namespace d3d
 
@@ -359,9 +336,8 @@ extern "C" int d3d_texture_select(const float* vertices, long long n_vertices, c
     const long n_blocks = ceil_div(n_faces, TX_BLOCK);
     const int n_words = ceil_div(n_views, 64);
     unsigned long long* mask = (unsigned long long*)scratch;
-    hipLaunchKernelGGL(tx_cull_kernel, dim3(ceil_div(n_blocks, TX_BLOCK / 64)), dim3(TX_BLOCK), 0, st, vertices, n_vertices, faces,
-                       (long)n_faces, n_blocks, views, n_views, n_words, mask);
-    D3D_LAUNCH_CHECK("tx_cull_kernel launch");
+    const int rc = tx_cull(vertices, n_vertices, faces, n_faces, views, n_views, mask, st);
+    if (rc != D3D_OK) return rc;
     hipLaunchKernelGGL(tx_select_kernel, dim3((unsigned)n_blocks), dim3(TX_BLOCK), 0, st, vertices, n_vertices, faces, (long)n_faces, views,
                        n_words, 1.0 + depth_tolerance, mask, key);
     D3D_LAUNCH_CHECK("tx_select_kernel launch");

@@ -1,4 +1,4 @@
-// What the texture stage's two files (texture.hip, texture_level.hip) share; not part of the public ABI.
+// What the texture stage's files (texture.hip, texture_smooth.hip, texture_level.hip) share; not part of the public ABI.
 #pragma once
 #include <cmath>
 
@@ -9,6 +9,7 @@ namespace d3d {
 
 constexpr int TX_BLOCK = 256;   // faces per select block (one workgroup), lanes per workgroup elsewhere
 constexpr int TX_BAND = 8;      // atlas rows per fill work item
+constexpr int TX_CANDIDATES = 16;   // keys per face of the candidate lists (d3d_texture_candidates_max)
 constexpr long long TX_EMPTY = 0x7fffffffffffffffll;
 
 struct TxFace {
@@ -26,6 +27,64 @@ __device__ __forceinline__ bool tx_face(const float* __restrict__ vertices, cons
     }
     return true;
 }
+
+// What the per-view tests need of a face: its corners, nrm = (b - a) x (c - a) and g = ((a + b) + c) / 3, in fp64.
+struct TxFrame {
+    TxFace F;
+    double nrm[3], g[3];
+};
+
+// False for a face past m, with an index out of range or with nrm = 0: it gets no view.
+__device__ __forceinline__ bool tx_frame(const float* __restrict__ vertices, const int* __restrict__ faces, long f, long m, long long n,
+                                         TxFrame* T) {
+    bool live = f < m && tx_face(vertices, faces, f, n, &T->F);
+    const TxFace& F = T->F;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) T->nrm[k] = T->g[k] = 0.0;
+    if (live) {
+        const double e1[3] = {F.b[0] - F.a[0], F.b[1] - F.a[1], F.b[2] - F.a[2]};
+        const double e2[3] = {F.c[0] - F.a[0], F.c[1] - F.a[1], F.c[2] - F.a[2]};
+        T->nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
+        T->nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
+        T->nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) T->g[k] = ((F.a[k] + F.b[k]) + F.c[k]) / 3.0;
+        live = T->nrm[0] != 0.0 || T->nrm[1] != 0.0 || T->nrm[2] != 0.0;
+    }
+    return live;
+}
+
+// The tests of one view on one face (texture.py: Candidate, Choice): false when the view is no candidate, else *key =
+// (bits(fp32(1 / A)) << 32) | id.  tol1 = 1 + depth_tolerance.  The selection and the candidate lists both call this.
+__device__ __forceinline__ bool tx_view_key(const d3d_ortho_view_t& V, const TxFrame& T, double tol1, long long* key) {
+    const TxFace& F = T.F;
+    const double *nrm = T.nrm, *g = T.g;
+    // front-facing: nrm . (C - g) > 0
+    const double dot = nrm[0] * (V.C[0] - g[0]) + nrm[1] * (V.C[1] - g[1]) + nrm[2] * (V.C[2] - g[2]);
+    if (!(dot > 0.0)) return false;
+    double ua, va, ub, vb, uc, vc, p2;
+    if (!ortho_uv(V, F.a[0], F.a[1], F.a[2], &ua, &va, &p2)) return false;
+    if (!ortho_uv(V, F.b[0], F.b[1], F.b[2], &ub, &vb, &p2)) return false;
+    if (!ortho_uv(V, F.c[0], F.c[1], F.c[2], &uc, &vc, &p2)) return false;
+    const GeomPq r = geom_project(V, g[0], g[1], g[2]);
+    const double ug = r.q0 / r.q2, vg = r.q1 / r.q2;
+    const int px = min(max((int)floor(fmin(fmax(ug + 0.5, 0.0), (double)V.W)), 0), V.W - 1);
+    const int py = min(max((int)floor(fmin(fmax(vg + 0.5, 0.0), (double)V.H)), 0), V.H - 1);
+    const float D = V.depth[(long)py * V.W + px];
+    if (!(isfinite(D) && D > 0.0f && r.p2 <= (double)D * tol1)) return false;
+    const double A = 0.5 * fabs((ub - ua) * (vc - va) - (uc - ua) * (vb - va));
+    if (!(A != 0.0)) return false;
+    const double s = 1.0 / A;
+    if (!isfinite(s)) return false;
+    *key = ((long long)__float_as_uint((float)s) << 32) | (long long)(unsigned)V.id;
+    return true;
+}
+
+// The per-block cull of the selection (texture.hip): mask [ceil(m / TX_BLOCK), ceil(n_views / 64)] uint64, bit v of a block's
+// words set when view v may see one of the block's faces.  tx_mask_bytes is the size of mask.
+inline size_t tx_mask_bytes(long long m, int n_views) { return (size_t)ceil_div(m, TX_BLOCK) * ceil_div(n_views, 64) * 8; }
+int tx_cull(const float* vertices, long long n, const int* faces, long long m, const d3d_ortho_view_t* views, int n_views,
+            unsigned long long* mask, hipStream_t st);
 
 // The view of `id` in a table sorted by id (lower bound), or -1.
 __device__ __forceinline__ int tx_find(const d3d_ortho_view_t* __restrict__ views, int n_views, int id) {

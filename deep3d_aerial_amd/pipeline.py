@@ -299,12 +299,17 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     of the keys; rank 0 lays out the charts, rects and pages (texture.layout) and broadcasts the chart table and page heights;
     each rank fills the charts of its own views; one all_reduce(SUM) of the pages as packed int32 texels (one rank contributes
     per texel); with settings["level"] rank 0 levels the seams of the merged pages (texture.level_pages); then the empty
-    colour.  Returns texture.texture_mesh's dict on rank 0 (without "labels"), None elsewhere."""
+    colour.  With settings["smooth_views"] the selection and its all_reduce give way to the candidate lists: each rank builds
+    its own (texture.face_candidates), ranks 1.. hand theirs to rank 0 one at a time, merged as they arrive
+    (sharding.fold_on with texture.merge_candidates: at most two lists are resident, 128 bytes per face each), and rank 0 smooths
+    (texture.smooth_views) and lays out; the other ranks need no keys.  The result then has "label" and "smooth".
+    Returns texture.texture_mesh's dict on rank 0 (without "labels"), None elsewhere."""
     from . import ortho as _ortho, texture as _tx
 
     t0 = time.perf_counter()
     tol, vpb, P, pad = _tx.check_settings(settings)
     level = _tx.check_level_settings(settings["level"]) if settings.get("level") is not None else None
+    smooth = _tx.check_smooth_settings(settings["smooth_views"]) if settings.get("smooth_views") is not None else None
     v = f = None
     if rank == 0:
         v = built_mesh[0].to(device=device, dtype=torch.float32).contiguous()
@@ -312,9 +317,18 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     v = sharding.broadcast_rows(v, (3,), torch.float32, device)
     f = sharding.broadcast_rows(f, (3,), torch.int32, device)
     ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in views]
-    key = _tx.select_faces(v, f, ov, tol, views_per_batch=vpb)
-    if world_size > 1:
-        sharding.all_reduce_raster(key, dist.ReduceOp.MIN)
+    smoothed = {}
+    if smooth is None:
+        key = _tx.select_faces(v, f, ov, tol, views_per_batch=vpb)
+        if world_size > 1:
+            sharding.all_reduce_raster(key, dist.ReduceOp.MIN)
+    else:
+        cand = sharding.fold_on(_tx.face_candidates(v, f, ov, tol, views_per_batch=vpb), _tx.merge_candidates)
+        if rank == 0:
+            key, label, commits = _tx.smooth_views(f, int(v.shape[0]), cand, *smooth)
+            before = _tx.charts(f, cand[:, 0].contiguous(), int(v.shape[0]))[1]
+            smoothed = {"label": label, "smooth": _tx.smooth_summary(cand, label, commits, smooth[2], before.shape[0])}
+        del cand
     res = None
     table = heights = None
     if rank == 0:
@@ -322,7 +336,7 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
         chart, _, rects, packing, table_np = _tx.layout(v, f, key, cams, P, pad)
         table = torch.from_numpy(table_np).to(device)
         heights = torch.tensor(packing.heights, dtype=torch.int64, device=device)
-        res = {"key": key, "chart": chart, "rects": rects, "packing": packing, "table": table_np}
+        res = dict(smoothed, key=key, chart=chart, rects=rects, packing=packing, table=table_np)
     table = sharding.broadcast_rows(table, (8,), torch.int32, device)
     heights = sharding.broadcast_rows(heights, (), torch.int64, device)
     table_np = table.cpu().numpy()

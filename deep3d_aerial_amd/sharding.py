@@ -177,6 +177,24 @@ def all_reduce_raster(t, op):
     return t
 
 
+def fold_on(t, fold, dst=0):
+    """Every rank's t (the same shape and dtype everywhere) folded into rank dst's: the other ranks hand theirs over one at a
+    time, in rank order, and dst calls fold(t, received) as each arrives, so at most two are resident there whatever the number
+    of ranks.  Through host memory over gloo, as broadcast_raster.  Returns t on dst (fold changes it in place), None elsewhere."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return t
+    rank, host = dist.get_rank(), _through_host(t)
+    if rank != dst:
+        dist.send(t.cpu() if host else t, dst)
+        return None
+    buf = torch.empty(t.shape, dtype=t.dtype, device="cpu" if host else t.device)
+    for src in range(dist.get_world_size()):
+        if src != dst:
+            dist.recv(buf, src)
+            fold(t, buf.to(t.device))
+    return t
+
+
 def broadcast_rows(t, row_shape, dtype, device, src=0):
     """A tensor [n, *row_shape] from rank src to every rank: the row count first, then the data (broadcast_raster).  t is the
     tensor on src (ignored elsewhere).  Returns the tensor on every rank (t itself on src)."""

@@ -1,8 +1,8 @@
 """Texturing the surface mesh from the views.
 
 The reference runs OpenMVS's TextureMesh after ReconstructMesh and RefineMesh.  The rules below are this project's own and do
-not claim to match OpenMVS: there is no smoothness term and no photo-consistency test; global seam levelling (below) is off
-by default, local (Poisson) seam levelling is not offered.
+not claim to match OpenMVS: there is no photo-consistency test; the smoothing of the view choice and global seam levelling
+(both below) are off by default, local (Poisson) seam levelling is not offered.
 
 * Input.  vertices [n,3] fp32 and faces [m,3] int32 on the GPU (mesh.extract, mesh.clean, mesh.read_ply), every index in
   0 .. n - 1; views: ortho.OrthoView records (id, K, E, depth, image) with distinct ids.
@@ -62,13 +62,44 @@ different views agree along their common border.  It runs after the fill and the
 The dot products are folded from fixed slots in a fixed order, so two runs give the same bits; the levelled pages do not depend
 on view order or batching.
 
-Faces are never reordered or renumbered: a shuffled face list gives the same key per face.  Chart labels, and so the packing,
+Smoothing the view choice (smooth_views=..., --smooth_views W): each face may give up a bounded share of its
+best projected area to agree with the faces around it, so that charts are fewer and larger.  It replaces the Choice above;
+with it off nothing changes.
+* Candidates.  cand [m, K] int64, K = 16 (d3d_texture_candidates_max): per face the K smallest of the keys that the Candidate
+  and Choice tests accept over all views, in increasing order, padded with INT64_MAX.  Keys are distinct (the id is the low
+  word), so the K smallest of a union do not depend on view order, batching or ranks; cand[:, 0] is the Choice's key.
+* Winner.  A face has a winner when its three indices are distinct and cand[f, 0] is a key.  View ids are 0 .. 2^31 - 2.
+* Data term.  s_k = the fp32 whose bits are cand[f, k] >> 32; d_k = 1 - s_0 / s_k in fp32 (an IEEE-rounded division, no
+  contraction), in [0, 1): the share of its best projected area the face gives up.  Candidate k is admissible when it is a key
+  and d_k <= max_loss; candidate 0 always is.
+* Neighbours.  Two faces that both have a winner are neighbours when they share at least one vertex; the weight w_fg is the
+  number of vertices they share (walking the three corner rows of f in the vertex -> face lists, skipping f itself, visits g
+  exactly w_fg times).  Faces without a winner are walked over and not counted.
+* Energy.  E = sum_f d(f, l_f) + weight * sum_{f<g} w_fg [id(l_f) != id(l_g)], l_f the index of the face's candidate.
+* Round, all in fp32, products and sums rounded separately.  Propose: from l_f = 0 before the first round, n_k = the weighted
+  count of neighbours whose current id differs from candidate k's id (an integer: the visit order does not matter);
+  c_k = d_k + weight * float(n_k); best = the admissible k with the smallest (c_k, k); gain = c_{l_f} - c_best; when gain > 0,
+  prio[f] = (bits(gain) << 32) | (2^32 - 1 - f) and prop[f] = best, else prio[f] = 0.  Commit: f takes prop[f] iff prio[f] > 0
+  and prio[f] > prio[g] for every neighbour g.  No two neighbours change in one round, so each commit lowers E by its gain,
+  and the face with the largest gain always commits, so the rounds end.
+* Stop.  After the first round with no commit, or after `rounds` rounds.  commits[r] counts round r's commits; the host reads
+  the counts once per 8 rounds, and rounds past the fixed point change nothing, so the cadence never shows in the result.
+* Output.  label [m] int32 (-1 without a winner) and key[f] = cand[f, label[f]] (INT64_MAX without a winner): a key of the
+  Choice's format, so charts, rects, fill, texcoords and levelling run on it unchanged.
+* Settings.  weight > 0 has no default (the command line's help names 0.1, the reference's fRatioDataSmoothness); max_loss in
+  [0, 1], default 0.25; rounds in 1 .. 1024, default 64: settings, not measurements.
+The smoothed keys are the same bits run to run and for any view order, batching or rank split.  Unlike the unsmoothed keys
+they depend on the face numbering, through the tie-break of the priorities only.
+
+Faces are never reordered or renumbered: a shuffled face list gives the same key per face (without smoothing).  Chart labels, and so the packing,
 follow the face order.  The hot passes are HIP kernels (csrc/texture.hip): select, charts (hooking and pointer jumping over
-(edge, face) pairs that torch.sort orders), rects, fill and texcoords; the levelling's kernels are in csrc/texture_level.hip.  No float atomics; the integer atomics are
-min / max.
+(edge, face) pairs that torch.sort orders), rects, fill and texcoords; the smoothing's kernels are in csrc/texture_smooth.hip,
+the levelling's in csrc/texture_level.hip.  No float atomics; the integer atomics are min / max and the count of a smoothing
+round's commits.
 
     python -m deep3d_aerial_amd.texture --mesh IN.ply --mvs MVS_FOLDER --out OUT.ply [--image_root DIR]
         [--depth_tolerance 0.01] [--views_per_batch N] [--page_size 8192] [--pad 2]
+        [--smooth_views W [--smooth_max_loss 0.25] [--smooth_rounds 64]]
         [--level [--level_smooth 0.1] [--level_anchor 1e-3] [--level_tolerance 1e-4] [--level_iterations 500]]
 """
 import argparse
@@ -91,6 +122,10 @@ DEFAULT_LEVEL_SMOOTH = 0.1
 DEFAULT_LEVEL_ANCHOR = 1e-3
 DEFAULT_LEVEL_TOLERANCE = 1e-4
 DEFAULT_LEVEL_ITERATIONS = 500
+CANDIDATES = 16   # keys per face of the candidate lists (csrc/texture_shared.h TX_CANDIDATES)
+DEFAULT_SMOOTH_MAX_LOSS = 0.25   # settings, not measurements
+DEFAULT_SMOOTH_ROUNDS = 64
+MAX_SMOOTH_ROUNDS = 1024
 _NONE = EMPTY_KEY
 
 
@@ -546,6 +581,112 @@ def level_pages(vertices, faces, key, chart, table, packing, cameras, atlas, smo
     return info
 
 
+# ----------------------------------------------------------------------------------------
+# smoothing the view choice
+# ----------------------------------------------------------------------------------------
+def check_smooth_settings(smooth):
+    """The smooth_views settings dict checked: (weight, max_loss, rounds).  weight has no default."""
+    if "weight" not in smooth:
+        raise ValueError("smooth_views needs a weight (> 0)")
+    weight = float(smooth["weight"])
+    max_loss = float(smooth.get("max_loss", DEFAULT_SMOOTH_MAX_LOSS))
+    rounds = smooth.get("rounds", DEFAULT_SMOOTH_ROUNDS)
+    unknown = set(smooth) - {"weight", "max_loss", "rounds"}
+    if unknown:
+        raise ValueError("smooth_views: unknown settings %s" % sorted(unknown))
+    if not (np.isfinite(weight) and np.float32(weight) > 0):
+        raise ValueError("smooth_views weight %r must be finite and > 0" % (weight,))
+    if not 0 <= max_loss <= 1:
+        raise ValueError("smooth_max_loss %r must lie in [0, 1]" % (max_loss,))
+    if int(rounds) != rounds or not 1 <= int(rounds) <= MAX_SMOOTH_ROUNDS:
+        raise ValueError("smooth_rounds %r must be an integer in 1 .. %d" % (rounds, MAX_SMOOTH_ROUNDS))
+    return weight, max_loss, int(rounds)
+
+
+def _check_cand(cand, m, device, name="cand"):
+    if not (isinstance(cand, torch.Tensor) and cand.dtype == torch.int64 and tuple(cand.shape) == (m, CANDIDATES) and cand.is_contiguous()):
+        raise ValueError("%s must be a contiguous int64 tensor of shape (%d, %d)" % (name, m, CANDIDATES))
+    if cand.device != device:
+        raise RuntimeError("%s is on %s, the mesh on %s (no CPU fallback)" % (name, cand.device, device))
+
+
+def face_candidates(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, views_per_batch=None, cand=None):
+    """Merges the keys of `views` (OrthoView) into cand [m, 16] int64 (a new INT64_MAX list when None) and returns it: per face
+    the 16 smallest keys that select_faces' tests accept, increasing, padded with INT64_MAX.  The result does not depend on the
+    batching or the order of the views, and cand[:, 0] is select_faces' key."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    tol = check_tolerance(depth_tolerance)
+    vpb = check_views_per_batch(views_per_batch)
+    views = _check_views(views)
+    lib = _lib.load()
+    if lib.d3d_texture_candidates_max() != CANDIDATES:
+        raise RuntimeError("the library keeps %d candidates per face, texture.py %d" % (lib.d3d_texture_candidates_max(), CANDIDATES))
+    if cand is None:
+        cand = torch.full((m, CANDIDATES), EMPTY_KEY, dtype=torch.int64, device=vertices.device)
+    _check_cand(cand, m, vertices.device)
+    for batch in _batches(views, vpb):
+        recs, nv = _table(batch, vertices.device)
+        scratch, nbytes = _geom.scratch(lib.d3d_texture_scratch_bytes, m, nv, device=vertices.device)
+        rc = lib.d3d_texture_candidates(_ptr(vertices), n, _ptr(faces), m, _ptr(recs), nv, tol, _ptr(scratch), nbytes, _ptr(cand), _stream())
+        _lib.check(rc, "d3d_texture_candidates")
+    return cand
+
+
+def merge_candidates(a, b):
+    """The 16 smallest distinct keys per face of the lists a and b [m, 16], written into a, which is returned."""
+    if not isinstance(a, torch.Tensor) or a.dim() != 2:
+        raise ValueError("candidate lists are [m, %d] int64 tensors" % CANDIDATES)
+    if a.device.type != "cuda":
+        raise RuntimeError("the candidates are on %s (no CPU fallback)" % a.device)
+    m = int(a.shape[0])
+    _check_cand(a, m, a.device, "a")
+    _check_cand(b, m, a.device, "b")
+    _lib.check(_lib.load().d3d_texture_candidates_merge(_ptr(a), _ptr(b), m, _ptr(a), _stream()), "d3d_texture_candidates_merge")
+    return a
+
+
+def smooth_views(faces, n_vertices, cand, weight, max_loss=DEFAULT_SMOOTH_MAX_LOSS, rounds=DEFAULT_SMOOTH_ROUNDS):
+    """The smoothed choice (module docstring): (key [m] int64, label [m] int32, commits [rounds run] int32 -- each round's number
+    of changes, cut at the first round without one).  faces [m, 3] int32 on the GPU, cand: face_candidates' list."""
+    from .mesh import face_incidence
+
+    if not (isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError("faces must be [m,3] int32")
+    if faces.device.type != "cuda":
+        raise RuntimeError("faces are on %s (no CPU fallback)" % faces.device)
+    weight, max_loss, rounds = check_smooth_settings({"weight": weight, "max_loss": max_loss, "rounds": rounds})
+    faces = faces.contiguous()
+    m, n, dev = int(faces.shape[0]), int(n_vertices), faces.device
+    _check_cand(cand, m, dev)
+    lib = _lib.load()
+    scratch, nbytes = _geom.scratch(lib.d3d_texture_smooth_scratch_bytes, m, device=dev)
+    if nbytes == 0 or n < 0 or n >= 1 << 31:
+        raise ValueError("%d vertices, %d faces: the smoothing needs 6 m < 2^31 (the vertex -> face lists)" % (n, m))
+    if m and (int(faces.min()) < 0 or int(faces.max()) >= n):
+        raise ValueError("a face index is outside 0 .. %d" % (n - 1))
+    foff, finc = face_incidence(faces, n)
+    label = torch.empty((m,), dtype=torch.int32, device=dev)
+    key = torch.empty((m,), dtype=torch.int64, device=dev)
+    commits = torch.zeros((rounds,), dtype=torch.int32, device=dev)
+    run = ctypes.c_int(0)
+    rc = lib.d3d_texture_smooth(_ptr(cand), m, _ptr(faces), n, _ptr(foff), _ptr(finc), weight, max_loss, rounds, _ptr(scratch), nbytes,
+                                _ptr(label), _ptr(key), _ptr(commits), ctypes.byref(run), _stream())
+    _lib.check(rc, "d3d_texture_smooth")
+    c = commits[:run.value]
+    if run.value and int(c[-1]) == 0:
+        c = c[:-1]
+    return key, label, c
+
+
+def smooth_losses(cand, label):
+    """d [m] fp32 of the chosen candidates (NaN without a winner): 1 - s_0 / s_label."""
+    has = label >= 0
+    k = torch.gather(cand, 1, label.clamp(min=0).long()[:, None])[:, 0]
+    s0 = (cand[:, 0] >> 32).to(torch.int32).view(torch.float32)
+    sk = (k >> 32).to(torch.int32).view(torch.float32)
+    return torch.where(has, 1.0 - s0 / sk, torch.full_like(s0, float("nan")))
+
+
 def texcoords(vertices, faces, key, chart, table, packing, cameras):
     """(texcoord [m, 6] fp32, texnumber [m] int32) on the GPU."""
     vertices, faces, n, m = _mesh_arrays(vertices, faces)
@@ -575,19 +716,43 @@ def layout(vertices, faces, key, cameras, page_size=DEFAULT_PAGE, pad=DEFAULT_PA
     return chart, labels, rects, packing, table
 
 
+_smooth_views = smooth_views   # texture_mesh's argument has the function's name
+
+
+def smooth_summary(cand, label, commits, rounds, charts_before):
+    """texture_mesh's "smooth" entry: the rounds that changed something, whether the fixed point was reached within `rounds`,
+    the charts of the unsmoothed keys, the mean and the largest d of the chosen views and the share of faces whose list is full."""
+    d = smooth_losses(cand, label)
+    d = d[label >= 0]
+    n = int(commits.shape[0])
+    return {"rounds": n, "converged": n < rounds, "commits": [int(c) for c in commits.cpu().tolist()], "charts_before": int(charts_before),
+            "mean_loss": float(d.double().mean()) if d.numel() else 0.0, "max_loss": float(d.max()) if d.numel() else 0.0,
+            "full_lists": float((cand[:, -1] != EMPTY_KEY).double().mean()) if cand.shape[0] else 0.0}
+
+
 def texture_mesh(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, views_per_batch=None, page_size=DEFAULT_PAGE,
-                 pad=DEFAULT_PAD, empty_color=EMPTY_COLOR, level=None):
+                 pad=DEFAULT_PAD, empty_color=EMPTY_COLOR, level=None, smooth_views=None):
     """Every pass on one process: {"key", "chart", "labels", "rects", "packing", "table", "pages" (host RGB8 arrays),
     "texcoord", "texnumber"}.  level: None, or the seam levelling's settings {"smooth", "anchor", "tolerance", "iterations"}
-    (check_level_settings; {} for the defaults); the result then has "level" (level_pages' dict)."""
+    (check_level_settings; {} for the defaults); the result then has "level" (level_pages' dict).  smooth_views: None, or the
+    settings of the view choice's smoothing {"weight", "max_loss", "rounds"} (check_smooth_settings; weight must be given): the
+    candidates pass then replaces select_faces, "key" is the smoothed key, and the result has "label", "cand" and "smooth"
+    (smooth_summary's dict)."""
     views = _check_views(views)
     check_page_size(page_size, views)
     if level is not None:
         smooth, anchor, tolerance, iterations = check_level_settings(level)
-    key = select_faces(vertices, faces, views, depth_tolerance, views_per_batch)
+    res = {}
+    if smooth_views is not None:
+        weight, max_loss, rounds = check_smooth_settings(smooth_views)
+        cand = face_candidates(vertices, faces, views, depth_tolerance, views_per_batch)
+        key, label, commits = _smooth_views(faces, int(vertices.shape[0]), cand, weight, max_loss, rounds)
+        before = charts(faces, cand[:, 0].contiguous(), int(vertices.shape[0]))[1]
+        res.update({"label": label, "cand": cand, "smooth": smooth_summary(cand, label, commits, rounds, before.shape[0])})
+    else:
+        key = select_faces(vertices, faces, views, depth_tolerance, views_per_batch)
     chart, labels, rects, packing, table = layout(vertices, faces, key, views, page_size, pad)
     atlas = fill_pages(table, packing, views, new_atlas(packing, vertices.device))
-    res = {}
     if level is not None:
         res["level"] = level_pages(vertices, faces, key, chart, table, packing, views, atlas, smooth, anchor, tolerance, iterations)
     atlas = finish_pages(atlas, empty_color)
@@ -684,6 +849,12 @@ def add_arguments(ap, prefix=""):
     ap.add_argument("--%sviews_per_batch" % prefix, type=int, default=None, help="views per selection call (default: all)")
     ap.add_argument("--%spage_size" % prefix, type=int, default=DEFAULT_PAGE, help="texture page width (>= every image's width and height)")
     ap.add_argument("--%spad" % prefix, type=int, default=DEFAULT_PAD, help="pixels of margin around every chart's rect (>= 1)")
+    ap.add_argument("--%ssmooth_views" % prefix, type=float, default=None, metavar="W",
+                    help="smooth the view choice over the mesh with this weight (> 0; 0.1 is the reference's fRatioDataSmoothness): "
+                         "fewer, larger charts")
+    ap.add_argument("--%ssmooth_max_loss" % prefix, type=float, default=DEFAULT_SMOOTH_MAX_LOSS,
+                    help="the largest share of its best projected area a face may give up (0 .. 1)")
+    ap.add_argument("--%ssmooth_rounds" % prefix, type=int, default=DEFAULT_SMOOTH_ROUNDS, help="at most this many rounds (1 .. 1024)")
     ap.add_argument("--%slevel" % prefix, action="store_true",
                     help="level the colour seams between charts of different views (one smooth additive correction per chart)")
     ap.add_argument("--%slevel_smooth" % prefix, type=float, default=DEFAULT_LEVEL_SMOOTH,
@@ -712,14 +883,17 @@ def settings_from_args(a, path, prefix=""):
     g = lambda k: getattr(a, prefix + k)
     level = {"smooth": g("level_smooth"), "anchor": g("level_anchor"), "tolerance": g("level_tolerance"), "iterations": g("level_iterations")}
     check_level_settings(level)   # the numbers are checked whether or not --level is given
+    w = g("smooth_views")
+    smooth = {"weight": 1.0 if w is None else w, "max_loss": g("smooth_max_loss"), "rounds": g("smooth_rounds")}
+    check_smooth_settings(smooth)   # likewise
     return {"path": path, "depth_tolerance": g("depth_tolerance"), "views_per_batch": g("views_per_batch"), "page_size": g("page_size"),
-            "pad": g("pad"), "level": level if g("level") else None}
+            "pad": g("pad"), "level": level if g("level") else None, "smooth_views": smooth if w is not None else None}
 
 
 def build_and_write(vertices, faces, views, settings):
     """texture_mesh with the settings dict, written to settings["path"]: the result dict."""
     tol, vpb, P, pad = check_settings(settings)
-    res = texture_mesh(vertices, faces, views, tol, vpb, P, pad, level=settings.get("level"))
+    res = texture_mesh(vertices, faces, views, tol, vpb, P, pad, level=settings.get("level"), smooth_views=settings.get("smooth_views"))
     write_textured_ply(settings["path"], vertices, faces, res["texcoord"], res["texnumber"], res["pages"])
     return res
 
@@ -745,6 +919,10 @@ def main(argv=None):
     res = build_and_write(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), views, settings_from_args(a, a.out))
     print("textured mesh %s: %d faces, %d charts, %d pages, %d views" % (a.out, f.shape[0], int(res["labels"].shape[0]),
                                                                         res["packing"].n_pages, len(views)))
+    if "smooth" in res:
+        print("smoothed the view choice in %d rounds%s: %d charts before, mean loss %.4f, largest %.4f" %
+              (res["smooth"]["rounds"], "" if res["smooth"]["converged"] else " (not converged)", res["smooth"]["charts_before"],
+               res["smooth"]["mean_loss"], res["smooth"]["max_loss"]))
     if "level" in res:
         print("levelled %d seam pairs over %d nodes in %d iterations%s" % (res["level"]["seams"], res["level"]["nodes"], res["level"]["iterations"],
                                                                           "" if res["level"]["converged"] else " (not converged)"))

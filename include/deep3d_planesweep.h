@@ -1293,6 +1293,43 @@ int d3d_texture_level_apply(const int* work, long long n_work, const float* vert
                             long long n_charts, const long long* page_row, int n_pages, const d3d_ortho_view_t* cams, int n_cams,
                             int page_width, const long long* cover, unsigned int* atlas, d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.19 -- smoothing the texture's view choice over the mesh (deep3d_aerial_amd/texture.py states the rule in full; it
+ * is this project's).  A candidate list is cand [n_faces, K] int64, K = d3d_texture_candidates_max(): per face the K smallest
+ * keys of d3d_texture_select's format that its tests accept, increasing, padded with INT64_MAX.  Every pointer is DEVICE memory
+ * except d3d_texture_smooth's `rounds_run`.  No float atomics; the one integer atomic counts a round's commits.
+ */
+/* K = 16. */
+int d3d_texture_candidates_max(void);
+
+/* d3d_texture_candidates: MERGES the keys of n_views views into cand (every entry INT64_MAX before the first call): the K
+ *   smallest of the list and the new keys, a key the list already holds counted once.  The cull, the per-view tests and the key
+ *   are d3d_texture_select's, so cand[f][0] over all views is its key[f].  scratch: d3d_texture_scratch_bytes(n_faces, n_views). */
+int d3d_texture_candidates(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const d3d_ortho_view_t* views,
+                           int n_views, double depth_tolerance, void* scratch, size_t scratch_bytes, long long* cand, d3d_stream_t stream);
+
+/* d3d_texture_candidates_merge: out = per face the K smallest distinct keys of the lists a and b; out may be a or b. */
+int d3d_texture_candidates_merge(const long long* a, const long long* b, long long n_faces, long long* out, d3d_stream_t stream);
+
+/* Scratch of d3d_texture_smooth (0 for an out-of-range size). */
+size_t d3d_texture_smooth_scratch_bytes(long long n_faces);
+
+/* d3d_texture_smooth: face_offset / face_index are d3d_mesh_decimate_incidence's outputs for the same mesh (its size limit
+ *   holds: 6 n_faces < 2^31).  A face has a winner when its three indices are distinct and in range and cand[f][0] is not
+ *   INT64_MAX; view ids (the keys' low words) are 0 .. 2^31 - 2.  With s_k = fp32 from (cand[f][k] >> 32), d_k = 1 - s_0 / s_k;
+ *   candidate k is admissible when k = 0 or it is a key and d_k <= max_loss.  Two faces with winners are neighbours with weight
+ *   w = the number of vertices they share.  From label 0, per round: n_k = the weighted count of neighbours whose current id
+ *   differs from candidate k's, c_k = d_k + weight * float(n_k) (fp32, each operation rounded), best = the admissible k of
+ *   smallest (c_k, k), gain = c_label - c_best; a face with gain > 0 has priority (bits(gain) << 32) | (2^32 - 1 - f) and takes
+ *   best when its priority exceeds every neighbour's.  commits [rounds] int32 gets each round's number of changes; the host
+ *   reads it once per 8 rounds and stops after the first round without a change, or after `rounds` (1 .. 1024) rounds;
+ *   rounds_run (HOST, may be null) gets the rounds up to and including that one.  label [n_faces] int32 = the chosen candidate
+ *   (-1 without a winner), key_out [n_faces] int64 = cand[f][label[f]] (INT64_MAX without a winner).  weight > 0,
+ *   0 <= max_loss <= 1. */
+int d3d_texture_smooth(const long long* cand, long long n_faces, const int* faces, long long n_vertices, const int* face_offset,
+                       const int* face_index, float weight, float max_loss, int rounds, void* scratch, size_t scratch_bytes, int* label,
+                       long long* key_out, int* commits, int* rounds_run, d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

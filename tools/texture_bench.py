@@ -3,9 +3,13 @@ V = 32 and V = 128 views of 2752 x 1856) textured from the same views with synth
 charts, rects, fill (with the empty-colour pass) and texcoords; faces, charts, pages and candidate views per face; and a per-view
 fp64 torch version of select, checked for the same keys.  The `level` entry times the seam levelling (csrc/texture_level.hip) on the
 same atlas: graph, samples, solve (with its iteration count), coverage and apply, and beside the solve a torch restatement of the
-same iteration (index_add per iteration) on the same graph, per iteration.
+same iteration (index_add per iteration) on the same graph, per iteration.  With --smooth_views W every row gains a `smooth` entry
+(csrc/texture_smooth.hip): the candidates pass beside select, the smoothing's time and rounds, the charts, pages and the rects and
+fill times before and after, the mean and largest loss of projected area and the share of faces whose candidate list is full,
+which is where 16 candidates truncate.  Rows of configurations a call does not run are kept in --out.
 
-    python tools/texture_bench.py [--iters 3] [--views 32,128] [--voxels 0.5,0.25] [--out profiles/texture_bench.json]"""
+    python tools/texture_bench.py [--iters 3] [--views 32,128] [--voxels 0.5,0.25] [--out profiles/texture_bench.json]
+        [--smooth_views W [--smooth_max_loss 0.25] [--smooth_rounds 64]] [--no_level]"""
 import argparse
 import json
 import os
@@ -117,7 +121,42 @@ def level_times(vertices, faces, key, chart, table, packing, ov, atlas, iters):
             "apply_ms": round(t_apply, 3), "torch_ms_per_iteration": round(t_torch / k, 4)}
 
 
-def run(views, voxel, iters):
+def smooth_times(vertices, faces, ov, key, before, smooth, iters):
+    """The candidates pass, the smoothing and the layout of the smoothed keys, beside `before` (the unsmoothed row's numbers)."""
+    weight, max_loss, rounds = smooth
+    n, m = int(vertices.shape[0]), int(faces.shape[0])
+    out = {}
+
+    def candidates():
+        out["cand"] = None   # one list at a time: 128 bytes per face
+        out["cand"] = texture.face_candidates(vertices, faces, ov)
+
+    t_cand = MB.timed_ms(candidates, iters)   # includes the fill of the empty list
+    cand = out["cand"]
+    same = bool(torch.equal(cand[:, 0], key))
+    t_smooth = MB.timed_ms(lambda: out.update(s=texture.smooth_views(faces, n, cand, weight, max_loss, rounds)), iters)   # with the incidence
+    skey, label, commits = out["s"]
+    info = texture.smooth_summary(cand, label, commits, rounds, before["charts"])
+    del cand
+    out.clear()
+    chart, labels = texture.charts(faces, skey, n)
+    nc = int(labels.shape[0])
+    t_rects = MB.timed_ms(lambda: out.update(r=texture.chart_rects(vertices, faces, skey, chart, nc, ov)), iters)
+    rects = out["r"]
+    packing = texture.pack(rects)
+    table = texture.chart_table(rects, packing, texture.chart_views(skey, labels))
+    atlas = texture.new_atlas(packing, "cuda")
+    t_fill = MB.timed_ms(lambda: texture.finish_pages(texture.fill_pages(table, packing, ov, atlas.zero_())), iters)
+    return {"weight": weight, "max_loss": max_loss, "max_rounds": rounds, "candidates_ms": round(t_cand, 3), "select_ms": before["select_ms"],
+            "column_0_is_select": same, "smooth_ms": round(t_smooth, 3), "rounds": info["rounds"], "converged": info["converged"],
+            "commits": info["commits"], "charts_before": before["charts"], "charts": nc, "pages_before": before["pages"],
+            "pages": packing.n_pages, "atlas_texels_before": before["atlas_texels"], "atlas_texels": int(atlas.numel()),
+            "rects_ms_before": before["rects_ms"], "rects_ms": round(t_rects, 3), "fill_ms_before": before["fill_ms"],
+            "fill_ms": round(t_fill, 3), "mean_loss": round(info["mean_loss"], 5), "largest_loss": round(info["max_loss"], 5),
+            "full_lists": round(info["full_lists"], 4)}
+
+
+def run(views, voxel, iters, smooth=None, with_level=True):
     grid = mesh.MeshGrid(MB.BORDER, voxel)
     mviews = views
     vertices, faces = mesh.depth_to_mesh(mviews, grid)
@@ -157,13 +196,21 @@ def run(views, voxel, iters):
     tk = torch_select(vertices, faces, ov)
     e1.record()
     torch.cuda.synchronize()
-    texture.fill_pages(table, packing, ov, atlas.zero_())
-    level = level_times(vertices, faces, key, chart, table, packing, ov, atlas, iters)
-    return {"level": level, "views": len(ov), "voxel_m": voxel, "faces": m, "vertices": n, "seen_faces": int((key != texture.EMPTY_KEY).sum()),
-            "charts": nc, "pages": packing.n_pages, "atlas_texels": int(atlas.numel()), "mean_candidates_per_face": round(float(cand.double().mean()), 3),
+    row = {}
+    if with_level:
+        texture.fill_pages(table, packing, ov, atlas.zero_())
+        row["level"] = level_times(vertices, faces, key, chart, table, packing, ov, atlas, iters)
+    n_texels = int(atlas.numel())
+    del atlas, chart, rects, table
+    if smooth is not None:
+        before = {"charts": nc, "pages": packing.n_pages, "atlas_texels": n_texels, "select_ms": round(t_select, 3),
+                  "rects_ms": round(t_rects, 3), "fill_ms": round(t_fill, 3)}
+        row["smooth"] = smooth_times(vertices, faces, ov, key, before, smooth, iters)
+    return dict(row, **{"views": len(ov), "voxel_m": voxel, "faces": m, "vertices": n, "seen_faces": int((key != texture.EMPTY_KEY).sum()),
+            "charts": nc, "pages": packing.n_pages, "atlas_texels": n_texels, "mean_candidates_per_face": round(float(cand.double().mean()), 3),
             "select_ms": round(t_select, 3), "charts_ms": round(t_charts, 3), "rects_ms": round(t_rects, 3), "fill_ms": round(t_fill, 3),
             "texcoords_ms": round(t_tc, 3), "torch_select_ms": round(e0.elapsed_time(e1), 1), "torch_same_keys": bool(torch.equal(tk, key)),
-            "face_view_tests": m * len(ov)}
+            "face_view_tests": m * len(ov)})
 
 
 def main(argv=None):
@@ -172,19 +219,39 @@ def main(argv=None):
     ap.add_argument("--views", default="32,128")
     ap.add_argument("--voxels", default="0.5,0.25")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "texture_bench.json"))
+    ap.add_argument("--smooth_views", type=float, default=None, metavar="W", help="also time the smoothing of the view choice with this weight")
+    ap.add_argument("--smooth_max_loss", type=float, default=texture.DEFAULT_SMOOTH_MAX_LOSS)
+    ap.add_argument("--smooth_rounds", type=int, default=texture.DEFAULT_SMOOTH_ROUNDS)
+    ap.add_argument("--no_level", action="store_true", help="skip the seam levelling's times (a row then keeps the recorded `level` entry)")
     a = ap.parse_args(argv)
+    smooth = None
+    if a.smooth_views is not None:
+        smooth = texture.check_smooth_settings({"weight": a.smooth_views, "max_loss": a.smooth_max_loss, "rounds": a.smooth_rounds})
     if not torch.cuda.is_available():
         raise RuntimeError("tools/texture_bench.py measures the GPU kernels: no GPU here")
     rows = []
     for nv in [int(x) for x in a.views.split(",")]:
         views = MB.make_views(nv, "cuda")
         for voxel in [float(x) for x in a.voxels.split(",")]:
-            r = run(views, voxel, a.iters)
+            r = run(views, voxel, a.iters, smooth, not a.no_level)
             print(json.dumps(r), flush=True)
             rows.append(r)
         del views
         torch.cuda.empty_cache()
     res = {"device": torch.cuda.get_device_name(0), "image": [MB.W, MB.H], "border": MB.BORDER, "runs": rows}
+    if os.path.exists(a.out):   # rows of other configurations stay, and a row run without an entry keeps the recorded one
+        old = json.load(open(a.out))
+        done = {(r["views"], r["voxel_m"]): r for r in rows}
+        for r in old.get("runs", []):
+            mine = done.get((r["views"], r["voxel_m"]))
+            if mine is None:
+                rows.append(r)
+            else:
+                for k in ("level", "smooth"):
+                    if k in r and k not in mine:
+                        mine[k] = r[k]
+        rows.sort(key=lambda r: (r["views"], -r["voxel_m"]))
+        res = dict(old, **res)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
