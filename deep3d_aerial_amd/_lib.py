@@ -271,15 +271,17 @@ def code_objects(path=None):
         pos = data.find(magic, pos + len(magic))
 
 
-def kernel_code_sha256(symbol_prefix, path=None):
-    """SHA-256 of the gfx950 machine code of ONE kernel in the built library: the bytes of the (unique) function symbol whose
-    mangled name starts with `symbol_prefix`, read from the code objects bundled in the .so's .hip_fatbin section.  A counter
-    profile of a kernel stays valid exactly as long as this hash does -- an edit elsewhere in the same source file does not
-    invalidate it, a change of compiler flags does (bench.profiled_traffic, tools/profile_round.sh).  None if not found."""
+def kernel_code_table(path=None):
+    """{mangled name: (size, SHA-256)} of the gfx950 machine code of every kernel (function symbol) in `path`: the built
+    library by default, or a single .o -- both carry the offload bundle.  Two builds produce the same machine code exactly
+    if their tables are equal, which is how a refactor of a kernel is held to "nothing changed":
+        a, b = kernel_code_table("parent/planesweep_tiled.o"), kernel_code_table("planesweep_tiled.o")
+        assert a.keys() == b.keys() and not [n for n in a if a[n] != b[n]]
+    A name that more than one code object defines is ambiguous and maps to None."""
     import hashlib
     import struct
 
-    found = []
+    table = {}
     for elf in code_objects(path):
         shoff, = struct.unpack_from("<Q", elf, 0x28)
         shentsize, shnum = struct.unpack_from("<HH", elf, 0x3A)
@@ -293,11 +295,20 @@ def kernel_code_sha256(symbol_prefix, path=None):
                 if (st_info & 0xF) != 2 or st_size == 0 or st_shndx >= len(secs):   # STT_FUNC
                     continue
                 end = elf.index(b"\0", strtab[4] + st_name)
-                if elf[strtab[4] + st_name:end].decode("ascii", "replace").startswith(symbol_prefix):
-                    sec = secs[st_shndx]
-                    o = sec[4] + (st_value - sec[3])
-                    found.append(hashlib.sha256(elf[o:o + st_size]).hexdigest())
-    return found[0] if len(found) == 1 else None
+                name = elf[strtab[4] + st_name:end].decode("ascii", "replace")
+                sec = secs[st_shndx]
+                o = sec[4] + (st_value - sec[3])
+                table[name] = None if name in table else (st_size, hashlib.sha256(elf[o:o + st_size]).hexdigest())
+    return table
+
+
+def kernel_code_sha256(symbol_prefix, path=None):
+    """SHA-256 of the gfx950 machine code of ONE kernel in the built library: the bytes of the (unique) function symbol whose
+    mangled name starts with `symbol_prefix`, read from the code objects bundled in the .so's .hip_fatbin section.  A counter
+    profile of a kernel stays valid exactly as long as this hash does -- an edit elsewhere in the same source file does not
+    invalidate it, a change of compiler flags does (bench.profiled_traffic, tools/profile_round.sh).  None if not found."""
+    found = [entry for name, entry in kernel_code_table(path).items() if name.startswith(symbol_prefix)]
+    return found[0][1] if len(found) == 1 and found[0] else None
 
 
 def check(rc, what):

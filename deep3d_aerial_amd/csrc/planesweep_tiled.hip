@@ -5,7 +5,7 @@
 // (2 KB per voxel at C = 32, V = 5) while only 4*C bytes are written, so the gather must not
 // go to L2 -- it is served from LDS.  Design (numbers in DESIGN.md):
 //
-//   * One workgroup (10 compute + 2 loader waves) = a 32 x 4 patch of reference pixels x a segment
+//   * One workgroup (8 compute + 4 loader waves) = a 32 x 4 patch of reference pixels x a segment
 //     of depth planes x a group of CH channels.  It walks the segment in STEPS of SP = NSUB*m
 //     planes: compute wave (pw, sub) owns two patch rows and the planes d = step*SP + sub + NSUB*j.
 //     A last patch column with at most 16 real pixels per row is swept in 16 x 8 patches instead (half as many workgroups
@@ -48,48 +48,22 @@ namespace d3d {
 namespace {
 
 constexpr int TW = 32;          // patch width  (one 128-byte output row segment per lane-row)
-constexpr int TH = 4;           // patch height
-constexpr int NPIXW = 2;        // pixel waves (2 patch rows each)
+// The wave counts of a workgroup are template parameters of the kernel (NSUB, NLOADW, NPIXW; the patch is 2 * NPIXW rows high).
+// These are the DEFAULT workgroup's, read by the host code only: 2 x 4 compute + 4 loader waves = 12 waves, 3 per SIMD at the
+// 168-VGPR budget, sweeping a 32 x 4 patch.  (launch_one picks SHALLOW_* instead for shallow sweeps.)
 #ifndef D3D_NSUB
 #define D3D_NSUB 4
 #endif
 #ifndef D3D_NLOADW
 #define D3D_NLOADW 4
 #endif
-constexpr int NSUB = D3D_NSUB;  // depth sub-ranges
-constexpr int NCOMP = NPIXW * NSUB;  // compute waves
-constexpr int NLOADW = D3D_NLOADW;  // loader waves: stage the next step's window delta into the rings
-constexpr int NWAVES = NCOMP + NLOADW;  // 12 waves: 3 per SIMD, 168-VGPR budget
-constexpr int THREADS = 64 * NWAVES;
+constexpr int DEFAULT_NSUB = D3D_NSUB;      // depth sub-ranges
+constexpr int DEFAULT_NLOADW = D3D_NLOADW;  // loader waves: stage the next step's window delta into the rings (0: the compute waves do)
+constexpr int DEFAULT_NPIXW = 2;            // pixel waves (2 patch rows each)
 constexpr int DSEG_MAX = 128;   // planes per workgroup segment upper bound (launch_one never asks for more)
-constexpr int MAXSTEPS = 64;    // >= DSEG_MAX / NSUB, <= 64 (one lane per step)
+constexpr int MAXSTEPS = 64;    // >= DSEG_MAX / NSUB for every NSUB launched, <= 64 (one lane per step)
 constexpr int PFD = 2;          // delta staging items (64 positions x CH channels) a loader wave keeps in flight
-#ifndef D3D_LDS_PIPE
-#define D3D_LDS_PIPE 1
-#endif
-// D3D_GRAB: the planes of a step are handed out DYNAMICALLY (one LDS counter per step and pixel wave) instead of plane j
-// going to depth sub-range j mod NSUB.  Why: issue arbitration on a SIMD goes by wave age, so the oldest wave of a SIMD
-// runs its planes at full single-wave speed, the younger ones on the leftover slots; with a static split the old waves
-// then idle at the step barrier while the SIMD drops to the (much lower: tools/plane_loop_rate.hip) throughput of one or
-// two active waves.  Handing out planes as waves become free keeps every wave of a SIMD busy until the step runs out.
-// (Lowering a wave's priority with s_setprio as it advances was tried instead: priorities are STRICT -- a lower-priority
-// wave does not even get the leftover slots -- and the step took 1.3x longer.)
-#ifndef D3D_GRAB
-#define D3D_GRAB 0
-#endif
-// D3D_FREERUN: no step barriers.  The compute waves take planes from ONE queue per pixel wave that runs through the whole
-// pass, and meet the loader waves only through two LDS counters per step: staged[k] (loader waves that have finished
-// delta k) and done[k] (planes of step k that have been swept).  A compute wave enters step k once staged[k] is
-// complete; the loaders start delta k once done[k-2] is complete (delta k may reuse slots of window k-2 only: the rings
-// hold the union of two consecutive windows), so the compute waves of a workgroup are at most one step apart and never
-// wait for EACH OTHER.  Why it matters: a SIMD of gfx950 reaches its vector throughput only with three or more waves
-// issuing (tools/plane_loop_rate.hip: 1766 / 1667 / 1125 cycles per plane and channel group at 1 / 2 / 3 waves per SIMD),
-// issue arbitration goes by wave age, and with a barrier per step the old waves of a SIMD finish their planes first and
-// then idle while the young ones run alone at the one-wave rate.
-#ifndef D3D_FREERUN
-#define D3D_FREERUN 0
-#endif
-constexpr int LDS_PIPE = D3D_LDS_PIPE;     // (quad, view) units whose taps are requested ahead of the one being blended
+constexpr int LDS_PIPE = 1;     // (quad, view) units whose taps are requested ahead of the one being blended
 constexpr int NCAND = 4;        // candidate step sizes: 4, 2, 1, 1/2 times NSUB planes
 constexpr int MAXRECTS = 512;   // non-empty delta rectangles per workgroup segment (4 words each)
 // LDS bank layout of the rings (tools/bank_sim.py models it on config 2; PMC: SQ_LDS_BANK_CONFLICT).  A ds_read_b128 is
@@ -106,7 +80,6 @@ __host__ __device__ __forceinline__ int ring_row_floats(int RW) {
     const int n = (RW + 1) * STRIDE;
     return ((n - 32 + 63) & ~63) + 32;   // smallest pitch >= n that is 32 mod 64
 }
-// non-empty delta rectangles per workgroup segment: MAXRECTS
 
 // Cycle stamps and plan statistics of the kernel (D3D_TILED_STATS): compiled only into -DD3D_EXPERIMENTS builds -- in the
 // production kernel the stamps and their accumulators would be live scalar registers across the plane loop.
@@ -130,9 +103,10 @@ struct TiledArgs {
 };
 
 // LDS map (ints/floats):
-//   [zero cell 2*STRIDE][pmin DSEG_MAX][pmax DSEG_MAX][header 32][plan table MAXSTEPS*NSRC*8]
-//   [rect starts MAXSTEPS+4][rect descriptors MAXRECTS*8][rings ...]
+//   [zero cell 2*STRIDE][pmin DSEG_MAX][pmax DSEG_MAX][header 32][view constants 8*NSRC][unused 2*MAXSTEPS]
+//   [plan table MAXSTEPS*NSRC*8][rect starts MAXSTEPS+4][positions per step MAXSTEPS][rect descriptors (MAXRECTS+1)*4][rings ...]
 // header: 0 mode (1 rings, 0 global gather) | 1 planes per step | 2 nsteps | 4+4i.. RW, RH, base, RW | RH << 8 | (base/4) << 16 per view
+//         | 28, 29 unused (zeroed by plan_tables)
 // plan entry (per step, view): wx0, wy0, ww, wh, ox, oy, ox - wx0, oy - wy0
 // rect descriptor (non-empty delta rectangles, grouped by step), 4 words:
 //   (rx + 1) | (ry + 1) << 16,  width | view << 12 | first position (cumulative within the step) << 16,
@@ -145,7 +119,7 @@ struct Lds {
     static constexpr int PMAX = PMIN + DSEG_MAX;
     static constexpr int HDR = PMAX + DSEG_MAX;
     static constexpr int VT = HDR + 32;                // per view: T0, T1, T2, -, RW, RH, row bytes, absolute ring base (view-major plane loop)
-    static constexpr int CNT = VT + 8 * NSRC;          // per-step hand-off counters: [MAXSTEPS] staged, [MAXSTEPS] done
+    static constexpr int CNT = VT + 8 * NSRC;          // nothing reads this since the counter hand-offs were removed (dropping it moves DATA: DESIGN.md 8)
     static constexpr int PLAN = CNT + 2 * MAXSTEPS;
     static constexpr int SST = PLAN + MAXSTEPS * NSRC * 8;
     static constexpr int STOT = SST + MAXSTEPS + 4;   // positions to stage per step
@@ -153,56 +127,6 @@ struct Lds {
     static constexpr int DATA = RECTS + (MAXRECTS + 1) * 4;  // 16-byte aligned
 };
 
-struct Rects {  // window(k) minus window(k-1): left | right | top | bottom (any may be empty)
-    int rx[4], ry[4], rw[4], rh[4], start[5];
-};
-
-
-// Step hand-off between the loader and the compute waves of a workgroup.  D3D_DECOUPLE = 1 (experiment, off):
-// two LDS counters per step instead of one s_barrier per step -- a compute wave starts step k as soon as the
-// loaders have staged it, and the loaders start staging step k+1 as soon as EVERY compute wave has left step k-1.
-// Measured: the 18 % "barrier wait" of the compute waves barely moves (43k -> 39.5k cycles per workgroup) -- they
-// wait for the staging of the next window, not for each other -- so the plain barrier stays.  The spin is bounded
-// (no hang whatever happens; ~100x longer than any legitimate wait).
-#ifndef D3D_DECOUPLE
-#define D3D_DECOUPLE 0
-#endif
-#ifndef STAGE0_ALL
-#define STAGE0_ALL 1  // compute waves help to stage the first window of a pass: neutral on deep sweeps (239k cycles per workgroup
-                     // either way), -7 % on the cascade's 8-plane stage where that window is the only staging there is
-#endif
-#define STAGE0_ALL_EFF (STAGE0_ALL && !D3D_DECOUPLE)
-__device__ __forceinline__ void step_signal(int* ctr, int lane) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void step_wait(int* ctr, int target) {
-#ifndef D3D_SPIN_LOG2
-#define D3D_SPIN_LOG2 16
-#endif
-    for (int spin = 0; spin < (1 << D3D_SPIN_LOG2); ++spin) {
-        if (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= target) break;
-        __builtin_amdgcn_s_sleep(2);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-// Counter hand-off in LDS (D3D_FREERUN).  The LDS executes the DS operations of the CU in arrival order and those of one wave
-// in program order, so "ring writes, then counter add" by one wave and "counter read, then ring reads" by another need no
-// fence beyond keeping the COMPILER from reordering them (a workgroup-scope fence would also wait for every global store
-// the wave has in flight).  Waits are bounded: a wave that gives up sweeps on (wrong results, never a hang).
-__device__ __forceinline__ void ctr_add(int* ctr, int lane) {
-    asm volatile("" ::: "memory");
-    if (lane == 0) __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void ctr_wait(int* ctr, int target) {
-    for (int spin = 0; spin < (1 << 22); ++spin) {
-        const int v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        if (v >= target) break;
-        __builtin_amdgcn_s_sleep(1);
-    }
-    asm volatile("" ::: "memory");
-}
 __device__ __forceinline__ int posmod(int a, int n) {
     int r = a % n;
     return r < 0 ? r + n : r;
@@ -283,15 +207,15 @@ __device__ __forceinline__ float ldf(const __half* q) { return __half2float(*q);
 // is fp32 (v_fma_mix_f32 reads the fp16 tap directly), the result is rounded once (RNE) at the store.
 // OUTCL: the variance volume leaves as a channel-last bf16 volume [D][h][w][C] (RNE) -- the form conv0 of the 3-D
 // regulariser stages in bf16 mode (conv_c8.hip); four channels of a voxel = one 8-byte store instead of four 4-byte ones.
-// NSUB_T / NLOAD_T: depth sub-ranges and loader waves of a workgroup.  The default (4 + 4: 12 waves, all of a CU's LDS) is
+// NSUB / NLOADW: depth sub-ranges and loader waves of a workgroup.  The default (4 + 4: 12 waves, all of a CU's LDS) is
 // sized for deep sweeps; SHALLOW sweeps (the last cascade stage: 8 planes) run 2 + 2 = 6 waves on half the LDS, so TWO
 // workgroups share a CU and one's planning prologue and first-window latency (most of its life: 47 % + 40 % at 8 planes)
 // overlap the other's arithmetic.
-template <int MODE, int NSRC, int CH, typename T = float, bool OUTCL = false, int NSUB_T = D3D_NSUB, int NLOAD_T = D3D_NLOADW,
-          int NPIXW_T = 2>
-__global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_tiled_kernel(SweepParams p, TiledArgs a) {   // 3 waves per SIMD: the 168-register budget for either workgroup size
-    constexpr int NSUB = NSUB_T, NLOADW = NLOAD_T, NPIXW = NPIXW_T, TH = 2 * NPIXW;   // (shadow the defaults)
-    constexpr int NCOMP = NPIXW * NSUB, NWAVES = NCOMP + NLOADW, THREADS = 64 * NWAVES;
+template <int MODE, int NSRC, int CH, typename T = float, bool OUTCL = false, int NSUB = D3D_NSUB, int NLOADW = D3D_NLOADW,
+          int NPIXW = 2>
+__global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_kernel(SweepParams p, TiledArgs a) {   // 3 waves per SIMD: the 168-register budget for either workgroup size
+    constexpr int TH = 2 * NPIXW;   // patch height
+    constexpr int NCOMP = NPIXW * NSUB, NWAVES = NCOMP + NLOADW, THREADS = 64 * NWAVES;   // compute waves | all waves
     constexpr bool F16 = sizeof(T) == 2;
     static_assert(!OUTCL || (MODE == MODE_VARIANCE && !F16), "channel-last bf16 output is built for the fp32 variance volume");
     constexpr int CW = CH * (int)sizeof(T) / 4;   // words per ring position
@@ -301,7 +225,6 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
     constexpr int Q = CW / 4;                     // 16-byte chunks per position
     static_assert(!F16 || MODE == MODE_VARIANCE, "fp16 storage is built for the variance volume only");
     constexpr bool VIEW_MAJOR = F16;             // unit order of the compute loop (see there)
-    constexpr bool FREERUN = D3D_FREERUN && NLOADW > 0 && NPIXW <= 2;   // (the plane queues: one per pixel wave, two header words)
     constexpr int MAXRS = 4 * NSRC;               // delta rectangles a step can have (left | right | top | bottom per view)
     static_assert(NSRC <= 15, "rect descriptors keep the view in 4 bits");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -707,8 +630,9 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
             ldsi[L::HDR + 1] = sp_sel;
             ldsi[L::HDR + 2] = nsteps_sel;
         }
+        // nothing reads these words since the counter hand-offs were removed; the stores stay until the CNT region goes
         for (int i = lane; i < 2 * MAXSTEPS; i += 64) ldsi[L::CNT + i] = 0;
-        if (lane < 2) ldsi[L::HDR + 28 + lane] = 0;   // plane queues of the pixel waves (D3D_FREERUN)
+        if (lane < 2) ldsi[L::HDR + 28 + lane] = 0;
     };
     if (wave == 0) plan_tables(0, NCAND1);
     __syncthreads();
@@ -817,7 +741,7 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
     };
     // Loader waves: bring window(k) minus window(k-1) into the rings.
     const bool ltiming = D3D_STAMPS && a.tstats != nullptr && lw == 0;
-    long long lt_desc = 0, lt_issue = 0, lt_write = 0, lt_bar = 0;
+    long long lt_issue = 0, lt_write = 0, lt_bar = 0;
     // (sw, snw): this wave's index among the snw waves sharing the step's items -- the loaders for the deltas;
     // ALL waves for the initial window, which nothing can overlap (one workgroup per CU): the compute waves
     // would only wait for it.
@@ -861,49 +785,28 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
 
     // Barrier k separates {compute step k-1, stage delta k} from {compute step k, stage delta k+1}.
     // Both roles execute exactly nsteps barriers in ring mode and none in gather mode.
-#if D3D_DECOUPLE
-#error "the counter hand-off experiment predates the channel-group loop (its counters are per step, not per pass)"
-#endif
     // (In gather mode -- rings do not fit, or p.z <= 0 at a corner -- there is nothing to stage: the loader waves sweep
     //  planes too, see GATHER_ALL below.)
     if (loader && ring) {
         // (Raising the loaders' issue priority with s_setprio was measured: their decode time halves,
         // but the compute waves lose the same slots and the kernel gets 5 % slower -- left at default.)
         for (int gi = 0; gi < a.ngroups; ++gi) {
-        grp = gi;
-        c0 = gi * CH;
-        if (FREERUN && ring) {
-            stage(0, wave, NWAVES);
-            __syncthreads();   // start of the pass: window 0 is complete, the counters are clear
-            for (int k = 1; k < nsteps; ++k) {
-                // delta k may land on slots of window k-2 (never of window k-1): every plane of step k-2 has to be swept
-                if (k >= 2) ctr_wait(ldsi + L::CNT + (k - 2), min(SP, nplanes - (k - 2) * SP) * NPIXW);
-                stage(k, lw, NLOADW);
-                ctr_add(ldsi + L::CNT + MAXSTEPS + k, lane);   // (after this wave's ring writes, in program order)
+            grp = gi;
+            c0 = gi * CH;
+            // First window of a pass: every wave of the workgroup stages it, the compute waves too.  Neutral on deep sweeps (239k
+            // cycles per workgroup either way), -7 % on the cascade's 8-plane stage where that window is the only staging there is.
+            if (ring) {   // (always true here.  Without it the compiler inverts one loop branch: kept so that deleting the experiment paths
+                          //  left every kernel's machine code byte-identical)
+                stage(0, wave, NWAVES);
+                for (int k = 0; k < nsteps; ++k) {
+                    long long tb = 0;
+                    if (ltiming) tb = clock64();
+                    __syncthreads();
+                    if (ltiming) lt_bar += clock64() - tb;
+                    if (k + 1 < nsteps) stage(k + 1, lw, NLOADW);
+                }
             }
-        } else if (ring) {
-            stage(0, STAGE0_ALL_EFF ? wave : lw, STAGE0_ALL_EFF ? NCOMP + NLOADW : NLOADW);
-#if D3D_DECOUPLE
-            step_signal(ldsi + L::CNT + 0, lane);
-            for (int k = 0; k + 1 < nsteps; ++k) {
-                long long tb = 0;
-                if (ltiming) tb = clock64();
-                if (k > 0) step_wait(ldsi + L::CNT + MAXSTEPS + (k - 1), NCOMP);  // every compute wave has left step k-1
-                if (ltiming) lt_bar += clock64() - tb;
-                stage(k + 1, lw, NLOADW);
-                step_signal(ldsi + L::CNT + (k + 1), lane);
-            }
-#else
-            for (int k = 0; k < nsteps; ++k) {
-                long long tb = 0;
-                if (ltiming) tb = clock64();
-                __syncthreads();
-                if (ltiming) lt_bar += clock64() - tb;
-                if (k + 1 < nsteps) stage(k + 1, lw, NLOADW);
-            }
-#endif
-        }
-        __syncthreads();  // end of the pass: the rings may be overwritten with the next group's first window
+            __syncthreads();  // end of the pass: the rings may be overwritten with the next group's first window
         }
         if (ltiming && lane == 0) {
             atomicAdd(a.tstats + 2, (unsigned long long)lt_bar);
@@ -933,9 +836,6 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
         RV[i].RH = ring ? rfl(ldsi[L::HDR + 4 + 4 * i + 1]) : 1;
         RV[i].rowb = ring_row_floats<STRIDE>(RV[i].RW) * 4;
         RV[i].base = lds0 + 4 * (ring ? rfl(ldsi[L::HDR + 4 + 4 * i + 2]) : L::DATA);
-#ifdef D3D_RV_VGPR   // experiment: the ring constants as (uniform) vector registers instead of spilled scalar registers
-        asm volatile("" : "+v"(RV[i].RW), "+v"(RV[i].RH), "+v"(RV[i].rowb), "+v"(RV[i].base));
-#endif
     }
     const float invV = 1.0f / (float)(p.n_src + 1);
     const size_t cstride_b = (p.plane_major ? plane : (size_t)D * plane) * sizeof(T);   // bytes between channels
@@ -992,12 +892,6 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
     long long t_w = 0, t_w0 = 0, t_c = 0, t_mark = 0;
     if (timing) { t_mark = clock64(); if (lane == 0) atomicAdd(a.tstats + 0, (unsigned long long)(t_mark - t_start)); }
     // (s_setprio 2 / 3 on ALL compute waves: no effect, 6.49 / 6.46 ms next to 6.51 / 6.47 ms without)
-#ifdef D3D_YOUNG_PRIO
-    // Issue arbitration is priority, then age: of the two compute waves of a SIMD the older one (waves 0-3) wins every
-    // contested slot, finishes its planes of a step early and idles at the step barrier (~95k of 427k cycles per workgroup)
-    // while the younger one runs alone.  Static priority for the younger half evens the two out.
-    if (wave >= NCOMP / 2) __builtin_amdgcn_s_setprio(D3D_YOUNG_PRIO);
-#endif
     // ---- one plane of the segment (dl_ = plane index within the segment) for this wave's pixels and the current group ----
     int kx[NSRC], ky[NSRC];   // ring offset minus window origin of the current step, per view (scalar registers)
     int plan_adr = 0;   // view-major: absolute LDS byte address of the current step's plan entries
@@ -1183,12 +1077,11 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
                 };
 #pragma unroll
                 for (int u = 0; u < PD && u < NU; ++u) request(u, tp[u % (PD + 1)]);
-                if (PD == 0) request(0, tp[0]);
                 f4 s, qq;
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
                     const int q = u / NSRC, i = u % NSRC;
-                    if (PD > 0 ? (u + PD < NU) : (u > 0)) request(u + PD, tp[(u + PD) % (PD + 1)]);
+                    if (u + PD < NU) request(u + PD, tp[(u + PD) % (PD + 1)]);
                     if (i == 0) {
                         if (MODE == MODE_VARIANCE) { s = r[F16 ? 0 : q]; qq = s * s; }
                         else { s = (f4){0, 0, 0, 0}; qq = s; }
@@ -1234,49 +1127,21 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
                 store_sbase(uniform64(p.out + (size_t)d * plane), pixb, pair_acc / (float)CH);
     };
     for (int gi = 0; gi < a.ngroups; ++gi) {
-    grp = gi;
-    c0 = gi * CH;
-    if (gi > 0) load_reference();   // (group 0: requested ahead of the planning)
-    if (FREERUN && ring) {   // (see D3D_FREERUN)
-        stage(0, wave, NWAVES);
-        __syncthreads();   // start of the pass: window 0 is complete, the counters are clear
-        int kcur = 0;
-        load_step(0);
-        for (;;) {
-            int pg = 0;
-            if (lane == 0) pg = __hip_atomic_fetch_add(ldsi + L::HDR + 28 + pw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            pg = rfl(pg);
-            if (pg >= nplanes) break;
-            if (pg >= (kcur + 1) * SP) {   // first plane this wave takes of a later step
-                while (pg >= (kcur + 1) * SP) ++kcur;
-                ctr_wait(ldsi + L::CNT + MAXSTEPS + kcur, NLOADW);
-                load_step(kcur);
-            }
-            sweep_plane(pg);
-            ctr_add(ldsi + L::CNT + kcur, lane);   // (after this plane's tap reads, in program order)
+        grp = gi;
+        c0 = gi * CH;
+        if (gi > 0) load_reference();   // (group 0: requested ahead of the planning)
+        if (!ring) {
+            // GATHER_ALL: taps straight from global memory, no windows, no steps, no barriers inside the pass: every wave of the
+            // workgroup (the loader waves too) takes planes sub, sub + NW, ... of its pixel rows
+            constexpr int NW = NWAVES / NPIXW;
+            static_assert(NWAVES % NPIXW == 0, "the loader waves must come in whole sets of pixel waves");
+            load_step(0);
+            for (int dl_ = wave / NPIXW; dl_ < nplanes; dl_ += NW) sweep_plane(dl_);
+            __syncthreads();   // end of the pass (uniform with the ring passes of other workgroups: one barrier per pass)
+            continue;
         }
-        __syncthreads();   // end of the pass (matches the loaders'): the rings may be overwritten
-        if (wave == 0) {
-            for (int i = lane; i < 2 * MAXSTEPS; i += 64) ldsi[L::CNT + i] = 0;
-            if (lane < 2) ldsi[L::HDR + 28 + lane] = 0;
-        }
-        continue;
-    }
-    if (!ring) {
-        // GATHER_ALL: taps straight from global memory, no windows, no steps, no barriers inside the pass: every wave of the
-        // workgroup (the loader waves too) takes planes sub, sub + NW, ... of its pixel rows
-        constexpr int NW = NWAVES / NPIXW;
-        static_assert(NWAVES % NPIXW == 0, "the loader waves must come in whole sets of pixel waves");
-        load_step(0);
-        for (int dl_ = wave / NPIXW; dl_ < nplanes; dl_ += NW) sweep_plane(dl_);
-        __syncthreads();   // end of the pass (uniform with the ring passes of other workgroups: one barrier per pass)
-        continue;
-    }
-#if STAGE0_ALL_EFF
-    if (ring) stage(0, wave, NCOMP + NLOADW);  // first window of the pass: every wave of the workgroup stages
-#endif
-    for (int k = 0; k < nsteps; ++k) {
-        if (ring) {
+        stage(0, wave, NWAVES);  // first window of the pass: every wave of the workgroup stages (see the loaders' loop)
+        for (int k = 0; k < nsteps; ++k) {
             long long ta = 0;
             if (timing) ta = clock64();
             long long tw0 = 0;
@@ -1284,38 +1149,22 @@ __global__ __launch_bounds__(64 * (NPIXW_T * NSUB_T + NLOAD_T), 3) void sweep_ti
             __syncthreads();  // barrier k: rings hold window(k)
             if (wtiming && k > 0) t_ww += clock64() - tw0;
             if (timing) { t_mark = clock64(); t_w += t_mark - ta; if (k == 0) t_w0 = t_mark - ta; }
-        }
-        load_step(k);
+            load_step(k);
 
-#if D3D_GRAB
-        static_assert(NPIXW <= 2, "one plane counter per step and pixel wave: CNT holds two rows of MAXSTEPS");
-        const int spk = min(SP, nplanes - k * SP);   // planes of this step
-        for (;;) {
-            int jg = 0;
-            if (lane == 0) jg = __hip_atomic_fetch_add(ldsi + L::CNT + pw * MAXSTEPS + k, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            jg = rfl(jg);
-            if (jg >= spk) break;
-            const int dl_ = k * SP + jg;
-#else
-        for (int j = 0; sub + NSUB * j < SP; ++j) {
-            const int dl_ = k * SP + sub + NSUB * j;
-            if (dl_ >= nplanes) break;
-#endif
-            sweep_plane(dl_);
+            for (int j = 0; sub + NSUB * j < SP; ++j) {
+                const int dl_ = k * SP + sub + NSUB * j;
+                if (dl_ >= nplanes) break;
+                sweep_plane(dl_);
+            }
+            if (timing) t_c += clock64() - t_mark;
+            // no loader waves (NLOADW = 0): every wave stages its share of the next step's delta once its own planes are done
+            // (the delta's ring slots are not part of the window the other waves are still reading)
+            if constexpr (NLOADW == 0) {
+                if (k + 1 < nsteps) stage(k + 1, wave, NWAVES);
+            }
         }
-        if (timing) t_c += clock64() - t_mark;
-        // no loader waves (NLOAD_T = 0): every wave stages its share of the next step's delta once its own planes are done
-        // (the delta's ring slots are not part of the window the other waves are still reading)
-        if constexpr (NLOADW == 0) {
-            if (ring && k + 1 < nsteps) stage(k + 1, wave, NWAVES);
-        }
-    }
-    __syncthreads();  // end of the pass (matches the loaders')
-#if D3D_GRAB
-    // every wave has left the last step: clear the plane counters for the next pass (its first grab follows a barrier)
-    if (wave == 0) for (int i = lane; i < 2 * MAXSTEPS; i += 64) ldsi[L::CNT + i] = 0;
-#endif
-    if (timing) t_mark = clock64();
+        __syncthreads();  // end of the pass (matches the loaders')
+        if (timing) t_mark = clock64();
     }
     if (wtiming && lane == 0) atomicAdd(a.tstats + 8 + wave, (unsigned long long)t_ww);
     if (timing && lane == 0) {
@@ -1379,7 +1228,7 @@ static int group_channels(int C, int n_src, int elem_bytes);
 static void segments(int D, long tiles, int& dseg, int& nseg) {
     int dseg_cap = DSEG_MAX;
 #ifdef D3D_EXPERIMENTS
-    if (const char* e = getenv("D3D_TILED_DSEG")) dseg_cap = max(NSUB, min(atoi(e), DSEG_MAX));
+    if (const char* e = getenv("D3D_TILED_DSEG")) dseg_cap = max(DEFAULT_NSUB, min(atoi(e), DSEG_MAX));
 #endif
     nseg = ceil_div(D, dseg_cap);
     // enough workgroups to fill 256 CUs a few times over; 128-plane segments measured best on config 2 (rings sized
@@ -1412,8 +1261,8 @@ static int launch_one(const SweepParams& p, hipStream_t stream) {
     constexpr int CW = CH * (int)sizeof(T) / 4;
     using L = Lds<CW, NSRC>;
     constexpr int LDS_BYTES = 160 * 1024;
-    constexpr int NSUBK = SHALLOW ? SHALLOW_NSUB : NSUB, NLOADK = SHALLOW ? SHALLOW_NLOADW : NLOADW;
-    constexpr int NPIXK = SHALLOW ? SHALLOW_NPIXW : NPIXW, THK = 2 * NPIXK;
+    constexpr int NSUBK = SHALLOW ? SHALLOW_NSUB : DEFAULT_NSUB, NLOADK = SHALLOW ? SHALLOW_NLOADW : DEFAULT_NLOADW;
+    constexpr int NPIXK = SHALLOW ? SHALLOW_NPIXW : DEFAULT_NPIXW, THK = 2 * NPIXK;
     constexpr int THREADSK = 64 * (NPIXK * NSUBK + NLOADK);
     auto kern = sweep_tiled_kernel<MODE, NSRC, CH, T, OUTCL, NSUBK, NLOADK, NPIXK>;
     if (OUTCL && (size_t)p.h * p.w * p.C * 2 >= ((size_t)1 << 32)) return D3D_ERR_UNSUPPORTED;
@@ -1504,18 +1353,14 @@ static int launch_ch(const SweepParams& p, hipStream_t stream) {
     // shallow sweeps of 8-channel groups (the full-resolution cascade stage, 8 planes): 32 x 8-pixel patches (see SHALLOW_*).
     // (A first attempt, 6-wave workgroups on half the LDS so that two share a CU, helped the weighted mode on the bench
     // scene but fell back to gathering inside AdaMVS views, whose windows need more than half the LDS.)
-#ifndef D3D_SHALLOW_CG16
-#define D3D_SHALLOW_CG16 0      // A/B: the 16-channel groups too
-#endif
-    bool shallow = p.D <= SHALLOW_PLANES && (cg == 8 || (D3D_SHALLOW_CG16 && cg == 16));
+    bool shallow = p.D <= SHALLOW_PLANES && cg == 8;
 #ifdef D3D_EXPERIMENTS
     if (const char* e = getenv("D3D_TILED_SHALLOW")) shallow = shallow && atoi(e) != 0;
 #endif
     if constexpr (MODE == MODE_VARIANCE) {
         if (p.out_cl) {
             if constexpr (SHALLOW_PLANES > 0) {
-                if (shallow && cg == 8) return launch_one<MODE, NSRC, 8, float, true, true>(p, stream);
-                if (D3D_SHALLOW_CG16 && shallow && cg == 16) return launch_one<MODE, NSRC, 16, float, true, true>(p, stream);
+                if (shallow) return launch_one<MODE, NSRC, 8, float, true, true>(p, stream);
             }
             switch (cg) {
                 case 16: return launch_one<MODE, NSRC, 16, float, true>(p, stream);
@@ -1526,10 +1371,8 @@ static int launch_ch(const SweepParams& p, hipStream_t stream) {
     }
     if (p.out_cl) return D3D_ERR_UNSUPPORTED;
     if constexpr (SHALLOW_PLANES > 0 && (MODE == MODE_VARIANCE || MODE == MODE_WEIGHTED)) {
-        if (shallow && cg == 8) return launch_one<MODE, NSRC, 8, float, false, true>(p, stream);
-        if (D3D_SHALLOW_CG16 && shallow && cg == 16) return launch_one<MODE, NSRC, 16, float, false, true>(p, stream);
+        if (shallow) return launch_one<MODE, NSRC, 8, float, false, true>(p, stream);
     }
-    (void)shallow;
     switch (cg) {
         case 32: return launch_one<MODE, NSRC, 32, float>(p, stream);
         case 16: return launch_one<MODE, NSRC, 16, float>(p, stream);
@@ -1562,35 +1405,11 @@ const char* tiled_build_flags() {
 #if D3D_NLOADW != 4
            " D3D_NLOADW"
 #endif
-#if D3D_LDS_PIPE != 1
-           " D3D_LDS_PIPE"
-#endif
-#if D3D_GRAB
-           " D3D_GRAB"
-#endif
-#if D3D_FREERUN
-           " D3D_FREERUN"
-#endif
-#if D3D_DECOUPLE
-           " D3D_DECOUPLE"
-#endif
-#if STAGE0_ALL != 1
-           " STAGE0_ALL"
-#endif
 #if D3D_SHALLOW_PLANES != 16
            " D3D_SHALLOW_PLANES"
 #endif
-#if D3D_SHALLOW_CG16
-           " D3D_SHALLOW_CG16"
-#endif
 #if D3D_CL_MIN_PLANES != 96
            " D3D_CL_MIN_PLANES"
-#endif
-#ifdef D3D_YOUNG_PRIO
-           " D3D_YOUNG_PRIO"
-#endif
-#ifdef D3D_RV_VGPR
-           " D3D_RV_VGPR"
 #endif
         ;
 }

@@ -2,6 +2,7 @@
 declares, the ctypes binding covers them all, operators refuse CPU tensors (no fallback),
 and the host mirror modules are checkpoint-compatible with the reference's."""
 import ctypes
+import os
 import re
 
 import numpy as np
@@ -33,6 +34,27 @@ def test_library_exports_every_declared_symbol():
     assert lib.d3d_build_flags() == b"", lib.d3d_build_flags()
     counts = (ctypes.c_ulonglong * 4)()
     assert lib.d3d_debug_dispatch_counts(counts, 1) == 0 and lib.d3d_debug_dispatch_counts(None, 0) == -1
+
+
+def test_kernel_code_table_agrees_with_the_single_kernel_hash():
+    """kernel_code_table lists every kernel of the built library by mangled name; kernel_code_sha256 is its look-up by a
+    unique prefix (what bench.py's counter-profile guard calls).  No absolute hash is pinned: they follow the compiler."""
+    import bench
+
+    _lib.build()
+    table = _lib.kernel_code_table()
+    assert all(entry is not None and entry[0] > 0 and len(entry[1]) == 64 for entry in table.values())
+    headline = [name for name in table if name.startswith(bench.HEADLINE_KERNEL_PREFIX)]
+    assert len(headline) == 1, headline
+    assert _lib.kernel_code_sha256(bench.HEADLINE_KERNEL_PREFIX) == table[headline[0]][1]
+    # a prefix that two symbols share (every instantiation of the ring kernel) identifies no kernel
+    shared = "_ZN3d3d18sweep_tiled_kernelI"
+    assert bench.HEADLINE_KERNEL_PREFIX.startswith(shared) and sum(name.startswith(shared) for name in table) >= 2
+    assert _lib.kernel_code_sha256(shared) is None
+    assert _lib.kernel_code_sha256("_ZN3d3d_no_such_kernel") is None
+    # a single object file carries the same offload bundle as the library
+    obj = _lib.kernel_code_table(os.path.join(_lib.CSRC, "planesweep_tiled.o"))
+    assert obj and all(table[name] == entry for name, entry in obj.items())
 
 
 def test_invalid_arguments_are_reported_not_thrown():

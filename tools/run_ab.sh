@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: bench the tiled sweep kernel built with each given set of -D flags, e.g.
-#   tools/run_ab.sh "" "-DD3D_NOSTORE" "-DD3D_LDS_PIPE=2"
+#   tools/run_ab.sh "" "-DD3D_DEV_ONLY_HEADLINE" "-DD3D_DEV_ONLY_HEADLINE -DD3D_NSUB=6 -DD3D_NLOADW=2"
 # Each variant is linked to a scratch library of its own and selected through D3D_LIBRARY (deep3d_aerial_amd/_lib.py):
 # the in-tree production library is never touched.  EXP=1 builds the variants with -DD3D_EXPERIMENTS (cycle statistics,
 # D3D_TILED_* switches; prints the per-workgroup statistics).  CMD="..." runs that command instead of bench.py;
