@@ -185,6 +185,8 @@ SIGNATURES = {
     "d3d_texture_smooth_scratch_bytes": ([ctypes.c_longlong], _sz),
     "d3d_texture_smooth": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _f, _f, _i, _vp, _sz, _vp, _vp, _vp,
                            ctypes.POINTER(_i), _vp],
+    "d3d_texture_face_colors": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp],
+    "d3d_texture_outliers": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp],
     "d3d_texture_level_scratch_bytes": ([ctypes.c_longlong], _sz),
     "d3d_texture_level_incidence": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp],
     "d3d_texture_level_pairs": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp,

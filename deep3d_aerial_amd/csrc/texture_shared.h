@@ -1,4 +1,4 @@
-// What the texture stage's files (texture.hip, texture_smooth.hip, texture_level.hip) share; not part of the public ABI.
+// What the texture stage's files (texture.hip, texture_smooth.hip, texture_level.hip, texture_outliers.hip) share; not part of the public ABI.
 #pragma once
 #include <cmath>
 

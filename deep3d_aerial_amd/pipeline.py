@@ -95,7 +95,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     decimates it when asked (mesh.decimate), and writes the PLY; the DSM from the mesh and the texture use that mesh.  The
     other ranks do nothing (no collective: the file does not depend on the number of ranks); timings gets mesh_s on rank 0.
     texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad",
-    "level" (optional: None, or the seam levelling's settings)}
+    "level" (optional: None, or the seam levelling's settings), "smooth_views" and "outliers" (optional, likewise)}
     (needs mesh; texture.settings_from_args): the mesh rank 0 wrote (after cleaning) textured from every rank's views and
     reference images (write_texture_of); rank 0 writes the textured PLY and its pages; timings gets texture_s."""
     if mesh is not None:
@@ -303,6 +303,11 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     its own (texture.face_candidates), ranks 1.. hand theirs to rank 0 one at a time, merged as they arrive
     (sharding.fold_on with texture.merge_candidates: at most two lists are resident, 128 bytes per face each), and rank 0 smooths
     (texture.smooth_views) and lays out; the other ranks need no keys.  The result then has "label" and "smooth".
+    With settings["outliers"] the candidate lists are folded onto rank 0 in the same way; rank 0 broadcasts the merged list
+    (sharding.broadcast_raster: one collective of 128 bytes per face); every rank computes the colours of the faces in its own
+    views (texture.face_colors); one all_reduce(SUM) of the colour words merges them (a slot belongs to one view, so to one rank,
+    and the others hold 0 there); rank 0 rejects in place (texture.reject_outliers), then smooths or takes column 0, and lays
+    out.  The result then has "rejected" and "outliers".
     Returns texture.texture_mesh's dict on rank 0 (without "labels"), None elsewhere."""
     from . import ortho as _ortho, texture as _tx
 
@@ -310,6 +315,7 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     tol, vpb, P, pad = _tx.check_settings(settings)
     level = _tx.check_level_settings(settings["level"]) if settings.get("level") is not None else None
     smooth = _tx.check_smooth_settings(settings["smooth_views"]) if settings.get("smooth_views") is not None else None
+    outliers = _tx.check_outlier_settings(settings["outliers"]) if settings.get("outliers") is not None else None
     v = f = None
     if rank == 0:
         v = built_mesh[0].to(device=device, dtype=torch.float32).contiguous()
@@ -318,16 +324,27 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     f = sharding.broadcast_rows(f, (3,), torch.int32, device)
     ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in views]
     smoothed = {}
-    if smooth is None:
+    if smooth is None and outliers is None:
         key = _tx.select_faces(v, f, ov, tol, views_per_batch=vpb)
         if world_size > 1:
             sharding.all_reduce_raster(key, dist.ReduceOp.MIN)
     else:
         cand = sharding.fold_on(_tx.face_candidates(v, f, ov, tol, views_per_batch=vpb), _tx.merge_candidates)
-        if rank == 0:
+        if outliers is not None:
+            if cand is None:
+                cand = torch.empty((int(f.shape[0]), _tx.CANDIDATES), dtype=torch.int64, device=device)
+            sharding.broadcast_raster(cand, 0)
+            col = sharding.all_reduce_raster(_tx.face_colors(v, f, cand, ov, views_per_batch=vpb), dist.ReduceOp.SUM)
+            if rank == 0:
+                cand, rejected, counts = _tx.reject_outliers(cand, col, outliers, out=cand)
+                smoothed = {"rejected": rejected, "outliers": _tx.outlier_summary(counts, outliers, cand.shape[0])}
+            del col
+        if rank == 0 and smooth is not None:
             key, label, commits = _tx.smooth_views(f, int(v.shape[0]), cand, *smooth)
             before = _tx.charts(f, cand[:, 0].contiguous(), int(v.shape[0]))[1]
-            smoothed = {"label": label, "smooth": _tx.smooth_summary(cand, label, commits, smooth[2], before.shape[0])}
+            smoothed.update({"label": label, "smooth": _tx.smooth_summary(cand, label, commits, smooth[2], before.shape[0])})
+        elif rank == 0:
+            key = cand[:, 0].contiguous()
         del cand
     res = None
     table = heights = None

@@ -1,8 +1,8 @@
 """Texturing the surface mesh from the views.
 
 The reference runs OpenMVS's TextureMesh after ReconstructMesh and RefineMesh.  The rules below are this project's own and do
-not claim to match OpenMVS: there is no photo-consistency test; the smoothing of the view choice and global seam levelling
-(both below) are off by default, local (Poisson) seam levelling is not offered.
+not claim to match OpenMVS: the rejection of photo-inconsistent views, the smoothing of the view choice and global seam levelling
+(all three below) are off by default, local (Poisson) seam levelling is not offered.
 
 * Input.  vertices [n,3] fp32 and faces [m,3] int32 on the GPU (mesh.extract, mesh.clean, mesh.read_ply), every index in
   0 .. n - 1; views: ortho.OrthoView records (id, K, E, depth, image) with distinct ids.
@@ -91,14 +91,39 @@ with it off nothing changes.
 The smoothed keys are the same bits run to run and for any view order, batching or rank split.  Unlike the unsmoothed keys
 they depend on the face numbering, through the tie-break of the priorities only.
 
+Rejecting outlier views (outliers={"threshold": t}, --outlier_threshold t): a view that shows a face in a colour
+far from what most of its candidate views show (a car that moved, a specular roof, a wall the depth test missed) is struck from
+the face's candidate list before the Choice.  It is a filter between the Candidates above and the choice; with it off nothing
+changes.
+* Colour of a face in a candidate view.  The corners' (u, v) are the texcoord pass's projection (fp64, no contraction).  Four
+  sample points in image space, each sum left to right in fp64: s0 = ((p0 + p1) + p2) / 3 and, for i = 0, 1, 2,
+  s_{i+1} = ((4 p_i + p_j) + p_k) / 6 with j < k the other two corners.  Each sample is ortho's bilinear tap (ortho.py "Colour":
+  x0 = floor(u), fx = u - x0, taps clamped to the image, the four weighted taps summed in ortho's order in fp64), not rounded.
+  Per channel q = clamp(floor((((t0 + t1) + t2) + t3) + 0.5), 0, 1020): four times the mean, in quarter grey levels, 10 bits.
+  The slot's word is col = 2^30 | qR << 20 | qG << 10 | qB (int32); the word 0 means "no colour".  A slot gets a colour when
+  its key is a key, its id is among the offered views, the face's indices are in range and every corner projects in front of
+  the view with finite (u, v); otherwise the slot is left as it was.  So batches accumulate into one col [m, 16] and ranks write
+  disjoint slots: a colour does not depend on view order, batching or ranks.
+* Vote, all integer.  A slot is valid when its key is a key and its col != 0; n is the number of valid slots.  Faces with n < 3
+  are left alone.  Per channel med_c is the lower median: the value of rank (n - 1) >> 1 among the valid values in increasing
+  order.  dev_k = max_c |q_kc - med_c|, T = floor(threshold * 1020), and slot k is an outlier when dev_k > T.  When every valid
+  slot is an outlier (the three channel medians may belong to different views) the face keeps its whole list and is counted as
+  kept_all.  Slots with a key but no colour are neither counted nor removed.
+* Output.  cand_out [m, 16]: the surviving keys in their order, padded with INT64_MAX (it may alias cand); rejected [m] int32 has
+  bit k set when original slot k was removed.  cand_out[:, 0] is the new Choice; with smooth_views the smoothing runs on cand_out,
+  so its s_0 is the best inlier and charts_before counts cand_out[:, 0].
+* Settings.  threshold in (0, 1] has no default (the command line's help names 0.06, the reference's fOutlierThreshold); 3 views,
+  4 samples and the median are settings, not measurements.
+* Limit.  The rule assumes comparable exposure between the views: a gain spread beyond the threshold rejects honest views.
+
 Faces are never reordered or renumbered: a shuffled face list gives the same key per face (without smoothing).  Chart labels, and so the packing,
 follow the face order.  The hot passes are HIP kernels (csrc/texture.hip): select, charts (hooking and pointer jumping over
 (edge, face) pairs that torch.sort orders), rects, fill and texcoords; the smoothing's kernels are in csrc/texture_smooth.hip,
-the levelling's in csrc/texture_level.hip.  No float atomics; the integer atomics are min / max and the count of a smoothing
-round's commits.
+the levelling's in csrc/texture_level.hip, the outlier rejection's in csrc/texture_outliers.hip.  No float atomics; the integer
+atomics are min / max, the count of a smoothing round's commits and the four counters of the outlier vote.
 
     python -m deep3d_aerial_amd.texture --mesh IN.ply --mvs MVS_FOLDER --out OUT.ply [--image_root DIR]
-        [--depth_tolerance 0.01] [--views_per_batch N] [--page_size 8192] [--pad 2]
+        [--depth_tolerance 0.01] [--views_per_batch N] [--page_size 8192] [--pad 2] [--outlier_threshold T]
         [--smooth_views W [--smooth_max_loss 0.25] [--smooth_rounds 64]]
         [--level [--level_smooth 0.1] [--level_anchor 1e-3] [--level_tolerance 1e-4] [--level_iterations 500]]
 """
@@ -126,6 +151,7 @@ CANDIDATES = 16   # keys per face of the candidate lists (csrc/texture_shared.h 
 DEFAULT_SMOOTH_MAX_LOSS = 0.25   # settings, not measurements
 DEFAULT_SMOOTH_ROUNDS = 64
 MAX_SMOOTH_ROUNDS = 1024
+QUARTER_LEVELS = 1020   # a colour channel of the outlier vote: four times 0 .. 255
 _NONE = EMPTY_KEY
 
 
@@ -687,6 +713,77 @@ def smooth_losses(cand, label):
     return torch.where(has, 1.0 - s0 / sk, torch.full_like(s0, float("nan")))
 
 
+# ----------------------------------------------------------------------------------------
+# rejecting outlier views
+# ----------------------------------------------------------------------------------------
+def check_outlier_settings(outliers):
+    """The outliers settings dict checked: the threshold, which has no default."""
+    unknown = set(outliers) - {"threshold"}
+    if unknown:
+        raise ValueError("outliers: unknown settings %s" % sorted(unknown))
+    if "threshold" not in outliers:
+        raise ValueError("outliers needs a threshold (in (0, 1])")
+    t = float(outliers["threshold"])
+    if not (np.isfinite(t) and 0 < t <= 1):
+        raise ValueError("outlier_threshold %r must lie in (0, 1]" % (outliers["threshold"],))
+    return t
+
+
+def _check_col(col, m, device):
+    if not (isinstance(col, torch.Tensor) and col.dtype == torch.int32 and tuple(col.shape) == (m, CANDIDATES) and col.is_contiguous()):
+        raise ValueError("col must be a contiguous int32 tensor of shape (%d, %d)" % (m, CANDIDATES))
+    if col.device != device:
+        raise RuntimeError("col is on %s, the candidates on %s (no CPU fallback)" % (col.device, device))
+
+
+def face_colors(vertices, faces, cand, views, views_per_batch=None, col=None):
+    """The colour words of `views` (OrthoView) written into col [m, 16] int32 (a new zero tensor when None), which is returned:
+    col[f, k] is the colour of face f in the view of cand[f, k] when that view is among `views`; other slots are left as they
+    are.  The result does not depend on the batching or the order of the views."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    vpb = check_views_per_batch(views_per_batch)
+    views = _check_views(views)
+    _check_cand(cand, m, vertices.device)
+    if col is None:
+        col = torch.zeros((m, CANDIDATES), dtype=torch.int32, device=vertices.device)
+    _check_col(col, m, vertices.device)
+    lib = _lib.load()
+    for batch in _batches(views, vpb):
+        recs, nv = _table(batch, vertices.device)
+        rc = lib.d3d_texture_face_colors(_ptr(vertices), n, _ptr(faces), m, _ptr(cand), _ptr(recs), nv, _ptr(col), _stream())
+        _lib.check(rc, "d3d_texture_face_colors")
+    return col
+
+
+def reject_outliers(cand, col, threshold, out=None):
+    """The vote (module docstring): (cand_out [m, 16] int64, rejected [m] int32, counts [4] int32 -- faces tested, faces whose
+    column 0 changed, slots removed, kept_all faces).  out: where cand_out goes (a new tensor when None); it may be cand."""
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 2:
+        raise ValueError("candidate lists are [m, %d] int64 tensors" % CANDIDATES)
+    if cand.device.type != "cuda":
+        raise RuntimeError("the candidates are on %s (no CPU fallback)" % cand.device)
+    m, dev = int(cand.shape[0]), cand.device
+    _check_cand(cand, m, dev)
+    _check_col(col, m, dev)
+    T = int(np.floor(check_outlier_settings({"threshold": threshold}) * QUARTER_LEVELS))
+    if out is None:
+        out = torch.empty_like(cand)
+    _check_cand(out, m, dev, "out")
+    rejected = torch.zeros((m,), dtype=torch.int32, device=dev)
+    counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+    rc = _lib.load().d3d_texture_outliers(_ptr(cand), _ptr(col), m, T, _ptr(out), _ptr(rejected), _ptr(counts), _stream())
+    _lib.check(rc, "d3d_texture_outliers")
+    return out, rejected, counts
+
+
+def outlier_summary(counts, threshold, m):
+    """texture_mesh's "outliers" entry: the threshold and T, the faces, those with three coloured views or more (tested), those
+    whose first choice was struck (changed), the slots struck (removed) and the faces that kept a list with no inlier."""
+    c = [int(x) for x in (counts.cpu().tolist() if isinstance(counts, torch.Tensor) else counts)]
+    return {"threshold": float(threshold), "T": int(np.floor(float(threshold) * QUARTER_LEVELS)), "faces": int(m), "tested": c[0],
+            "changed": c[1], "removed": c[2], "kept_all": c[3]}
+
+
 def texcoords(vertices, faces, key, chart, table, packing, cameras):
     """(texcoord [m, 6] fp32, texnumber [m] int32) on the GPU."""
     vertices, faces, n, m = _mesh_arrays(vertices, faces)
@@ -731,19 +828,37 @@ def smooth_summary(cand, label, commits, rounds, charts_before):
 
 
 def texture_mesh(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, views_per_batch=None, page_size=DEFAULT_PAGE,
-                 pad=DEFAULT_PAD, empty_color=EMPTY_COLOR, level=None, smooth_views=None):
+                 pad=DEFAULT_PAD, empty_color=EMPTY_COLOR, level=None, smooth_views=None, outliers=None):
     """Every pass on one process: {"key", "chart", "labels", "rects", "packing", "table", "pages" (host RGB8 arrays),
     "texcoord", "texnumber"}.  level: None, or the seam levelling's settings {"smooth", "anchor", "tolerance", "iterations"}
     (check_level_settings; {} for the defaults); the result then has "level" (level_pages' dict).  smooth_views: None, or the
     settings of the view choice's smoothing {"weight", "max_loss", "rounds"} (check_smooth_settings; weight must be given): the
     candidates pass then replaces select_faces, "key" is the smoothed key, and the result has "label", "cand" and "smooth"
-    (smooth_summary's dict)."""
+    (smooth_summary's dict).  outliers: None, or the settings of the rejection of outlier views {"threshold"}
+    (check_outlier_settings): the candidate lists are then filtered (face_colors, reject_outliers) before the choice -- the
+    smoothing when smooth_views is given, else column 0 --, and the result has "cand" (the filtered lists), "rejected" and
+    "outliers" (outlier_summary's dict)."""
     views = _check_views(views)
     check_page_size(page_size, views)
     if level is not None:
         smooth, anchor, tolerance, iterations = check_level_settings(level)
     res = {}
-    if smooth_views is not None:
+    if outliers is not None:
+        threshold = check_outlier_settings(outliers)
+        if smooth_views is not None:
+            weight, max_loss, rounds = check_smooth_settings(smooth_views)
+        cand = face_candidates(vertices, faces, views, depth_tolerance, views_per_batch)
+        col = face_colors(vertices, faces, cand, views, views_per_batch)
+        cand, rejected, counts = reject_outliers(cand, col, threshold, out=cand)
+        del col
+        res.update({"cand": cand, "rejected": rejected, "outliers": outlier_summary(counts, threshold, cand.shape[0])})
+        if smooth_views is not None:
+            key, label, commits = _smooth_views(faces, int(vertices.shape[0]), cand, weight, max_loss, rounds)
+            before = charts(faces, cand[:, 0].contiguous(), int(vertices.shape[0]))[1]
+            res.update({"label": label, "smooth": smooth_summary(cand, label, commits, rounds, before.shape[0])})
+        else:
+            key = cand[:, 0].contiguous()
+    elif smooth_views is not None:
         weight, max_loss, rounds = check_smooth_settings(smooth_views)
         cand = face_candidates(vertices, faces, views, depth_tolerance, views_per_batch)
         key, label, commits = _smooth_views(faces, int(vertices.shape[0]), cand, weight, max_loss, rounds)
@@ -849,6 +964,9 @@ def add_arguments(ap, prefix=""):
     ap.add_argument("--%sviews_per_batch" % prefix, type=int, default=None, help="views per selection call (default: all)")
     ap.add_argument("--%spage_size" % prefix, type=int, default=DEFAULT_PAGE, help="texture page width (>= every image's width and height)")
     ap.add_argument("--%spad" % prefix, type=int, default=DEFAULT_PAD, help="pixels of margin around every chart's rect (>= 1)")
+    ap.add_argument("--%soutlier_threshold" % prefix, type=float, default=None, metavar="T",
+                    help="strike from a face's candidates the views whose colour of it is further than this from the median of "
+                         "its views, as a share of the range (in (0, 1]; 0.06 is the reference's fOutlierThreshold)")
     ap.add_argument("--%ssmooth_views" % prefix, type=float, default=None, metavar="W",
                     help="smooth the view choice over the mesh with this weight (> 0; 0.1 is the reference's fRatioDataSmoothness): "
                          "fewer, larger charts")
@@ -886,14 +1004,21 @@ def settings_from_args(a, path, prefix=""):
     w = g("smooth_views")
     smooth = {"weight": 1.0 if w is None else w, "max_loss": g("smooth_max_loss"), "rounds": g("smooth_rounds")}
     check_smooth_settings(smooth)   # likewise
+    t = g("outlier_threshold")
+    outliers = None
+    if t is not None:
+        outliers = {"threshold": t}
+        check_outlier_settings(outliers)
     return {"path": path, "depth_tolerance": g("depth_tolerance"), "views_per_batch": g("views_per_batch"), "page_size": g("page_size"),
-            "pad": g("pad"), "level": level if g("level") else None, "smooth_views": smooth if w is not None else None}
+            "pad": g("pad"), "level": level if g("level") else None, "smooth_views": smooth if w is not None else None,
+            "outliers": outliers}
 
 
 def build_and_write(vertices, faces, views, settings):
     """texture_mesh with the settings dict, written to settings["path"]: the result dict."""
     tol, vpb, P, pad = check_settings(settings)
-    res = texture_mesh(vertices, faces, views, tol, vpb, P, pad, level=settings.get("level"), smooth_views=settings.get("smooth_views"))
+    res = texture_mesh(vertices, faces, views, tol, vpb, P, pad, level=settings.get("level"), smooth_views=settings.get("smooth_views"),
+                       outliers=settings.get("outliers"))
     write_textured_ply(settings["path"], vertices, faces, res["texcoord"], res["texnumber"], res["pages"])
     return res
 
@@ -919,6 +1044,10 @@ def main(argv=None):
     res = build_and_write(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), views, settings_from_args(a, a.out))
     print("textured mesh %s: %d faces, %d charts, %d pages, %d views" % (a.out, f.shape[0], int(res["labels"].shape[0]),
                                                                         res["packing"].n_pages, len(views)))
+    if "outliers" in res:
+        o = res["outliers"]
+        print("rejected outlier views: threshold %g (T = %d), %d of %d faces tested, %d slots removed, %d faces changed their first view, "
+              "%d kept a list without an inlier" % (o["threshold"], o["T"], o["tested"], o["faces"], o["removed"], o["changed"], o["kept_all"]))
     if "smooth" in res:
         print("smoothed the view choice in %d rounds%s: %d charts before, mean loss %.4f, largest %.4f" %
               (res["smooth"]["rounds"], "" if res["smooth"]["converged"] else " (not converged)", res["smooth"]["charts_before"],

@@ -1330,6 +1330,31 @@ int d3d_texture_smooth(const long long* cand, long long n_faces, const int* face
                        const int* face_index, float weight, float max_loss, int rounds, void* scratch, size_t scratch_bytes, int* label,
                        long long* key_out, int* commits, int* rounds_run, d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.20 -- rejecting photo-inconsistent views from the candidate lists (deep3d_aerial_amd/texture.py states the rule in
+ * full; it is this project's).  col [n_faces, K] int32 holds one colour word per slot of cand, 0 = "no colour".  Every pointer is
+ * DEVICE memory.  No float atomics; the one integer atomic adds a wave's share of the four counters.
+ */
+/* d3d_texture_face_colors: the colour of every face in every candidate view of this call's table.  For slot k of face f whose
+ *   key is not INT64_MAX, whose id (the key's low word) is in `views` (sorted by id) with a non-null rgba, whose indices are in
+ *   range and whose three corners project in front of the view with finite (u, v) (fp64, no contraction, as
+ *   d3d_texture_texcoords): four samples in image space, s0 = ((p0 + p1) + p2) / 3 and s_{i+1} = ((4 p_i + p_j) + p_k) / 6 with
+ *   j < k the other two corners; each is d3d_ortho_colorize's bilinear tap (x0 = floor(u), fx = u - x0, taps clamped to the image,
+ *   ((w00 c00 + w10 c10) + w01 c01) + w11 c11 in fp64, not rounded); per channel q = clamp(floor((((t0 + t1) + t2) + t3) + 0.5),
+ *   0, 1020), four times the mean in quarter grey levels; col[f][k] = 2^30 | qR << 20 | qG << 10 | qB.  Every other slot is left as
+ *   it was, so calls over disjoint sets of views accumulate into one col (all 0 before the first). */
+int d3d_texture_face_colors(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const long long* cand,
+                            const d3d_ortho_view_t* views, int n_views, int* col, d3d_stream_t stream);
+
+/* d3d_texture_outliers: the vote, all integer.  A slot is valid when its key is not INT64_MAX and its col is not 0; n = the
+ *   number of valid slots; a face with n < 3 is left alone.  Per channel med = the lower median, the value of rank (n - 1) >> 1
+ *   among the valid values in increasing order; dev_k = max over the channels of |q_k - med|; slot k is an outlier when dev_k > T
+ *   (0 .. 1020).  When every valid slot is an outlier the face keeps its list (kept_all).  cand_out [n_faces, K] gets the keys
+ *   that are left, in their order, padded with INT64_MAX; it may be cand.  rejected [n_faces] int32: bit k set when slot k was
+ *   removed.  counts [4] int32 (cleared here): faces with n >= 3, faces whose column 0 changed, slots removed, kept_all faces. */
+int d3d_texture_outliers(const long long* cand, const int* col, long long n_faces, int T, long long* cand_out, int* rejected, int* counts,
+                         d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,10 +6,15 @@ same atlas: graph, samples, solve (with its iteration count), coverage and apply
 same iteration (index_add per iteration) on the same graph, per iteration.  With --smooth_views W every row gains a `smooth` entry
 (csrc/texture_smooth.hip): the candidates pass beside select, the smoothing's time and rounds, the charts, pages and the rects and
 fill times before and after, the mean and largest loss of projected area and the share of faces whose candidate list is full,
-which is where 16 candidates truncate.  Rows of configurations a call does not run are kept in --out.
+which is where 16 candidates truncate.  With --outlier_threshold T every row gains an `outliers` entry
+(csrc/texture_outliers.hip): the colour pass and the vote on the row's candidate lists, the candidates pass of the same row beside
+them, the summary counts, and a per-view fp64 torch version of the colour pass (advanced indexing for the gathers), checked for the
+same words; with --variant_library SO (a `make COLORS=per_slot` build) the entry also holds `mappings`: the colour pass of both
+builds on the same tensors, taking turns.  The images here are a function of the pixel and differ from view to view, so the counts say what the kernels did, not
+what the rule is worth.  Rows of configurations a call does not run are kept in --out.
 
     python tools/texture_bench.py [--iters 3] [--views 32,128] [--voxels 0.5,0.25] [--out profiles/texture_bench.json]
-        [--smooth_views W [--smooth_max_loss 0.25] [--smooth_rounds 64]] [--no_level]"""
+        [--smooth_views W [--smooth_max_loss 0.25] [--smooth_rounds 64]] [--outlier_threshold T [--variant_library SO]] [--no_level]"""
 import argparse
 import json
 import os
@@ -156,7 +161,92 @@ def smooth_times(vertices, faces, ov, key, before, smooth, iters):
             "full_lists": round(info["full_lists"], 4)}
 
 
-def run(views, voxel, iters, smooth=None, with_level=True):
+def torch_colors(vertices, faces, cand, views):
+    """The comparator: texture.py's colour of a face in a candidate view in fp64 torch, one view at a time over its slots."""
+    V = vertices.double()
+    col = torch.zeros(cand.shape, dtype=torch.int32, device=cand.device)
+    ids = cand & 0xffffffff
+    live = cand != texture.EMPTY_KEY
+    for v in views:
+        f, k = torch.nonzero(live & (ids == v.id), as_tuple=True)
+        if not f.numel():
+            continue
+        R, t, K = v.R.tolist(), v.t.tolist(), v.K.tolist()
+        ok = torch.ones_like(f, dtype=torch.bool)
+        us, ws = [], []
+        for c in range(3):
+            X = V[faces[f, c].long()]
+            p = [R[r][0] * X[:, 0] + R[r][1] * X[:, 1] + R[r][2] * X[:, 2] + t[r] for r in range(3)]
+            q = [K[r][0] * p[0] + K[r][1] * p[1] + K[r][2] * p[2] for r in range(3)]
+            u, w = q[0] / q[2], q[1] / q[2]
+            ok &= (p[2] > 0) & (q[2] > 0) & torch.isfinite(u) & torch.isfinite(w)
+            us.append(u)
+            ws.append(w)
+        mix = lambda p: [((p[0] + p[1]) + p[2]) / 3.0, ((4.0 * p[0] + p[1]) + p[2]) / 6.0, ((4.0 * p[1] + p[0]) + p[2]) / 6.0,
+                         ((4.0 * p[2] + p[0]) + p[1]) / 6.0]
+        img = v.rgba.reshape(-1, 4)
+        total = None
+        for su, sw in zip(mix(us), mix(ws)):
+            fu, fw = torch.floor(su), torch.floor(sw)
+            fx, fy = (su - fu)[:, None], (sw - fw)[:, None]
+            x0, y0 = fu.nan_to_num(0.0).clamp(0, v.W - 1).long(), fw.nan_to_num(0.0).clamp(0, v.H - 1).long()
+            x1, y1 = (x0 + 1).clamp(max=v.W - 1), (y0 + 1).clamp(max=v.H - 1)
+            c = lambda y, x: img[y * v.W + x, :3].double()
+            tap = (((1.0 - fx) * (1.0 - fy) * c(y0, x0) + fx * (1.0 - fy) * c(y0, x1)) + (1.0 - fx) * fy * c(y1, x0)) + fx * fy * c(y1, x1)
+            total = tap if total is None else total + tap
+        q = torch.floor(total + 0.5).nan_to_num(0.0).clamp(0, texture.QUARTER_LEVELS).long()
+        word = ((1 << 30) | (q[:, 0] << 20) | (q[:, 1] << 10) | q[:, 2]).int()
+        col[f[ok], k[ok]] = word[ok]
+    return col
+
+
+def outlier_times(vertices, faces, ov, threshold, iters, variant=None):
+    """The candidates pass, the colour pass and the vote (out of place, so every call sees the same lists), and the torch colour
+    pass.  variant: another build of the library (make COLORS=per_slot); its colour pass is then timed on the same tensors, the
+    two builds taking turns three times, and checked for the same words."""
+    out = {}
+
+    def candidates():
+        out["cand"] = None   # one list at a time: 128 bytes per face
+        out["cand"] = texture.face_candidates(vertices, faces, ov)
+
+    t_cand = MB.timed_ms(candidates, iters)
+    cand = out["cand"]
+    col = torch.zeros(cand.shape, dtype=torch.int32, device=cand.device)
+    t_col = MB.timed_ms(lambda: texture.face_colors(vertices, faces, cand, ov, col=col), iters)
+    spare = torch.empty_like(cand)
+    t_vote = MB.timed_ms(lambda: out.update(r=texture.reject_outliers(cand, col, threshold, out=spare)), iters)
+    info = texture.outlier_summary(out["r"][2], threshold, cand.shape[0])
+    t_torch = MB.timed_ms(lambda: out.update(t=torch_colors(vertices, faces, cand, ov)), iters)
+    res = dict(info, candidates_ms=round(t_cand, 3), colors_ms=round(t_col, 3), vote_ms=round(t_vote, 3),
+               slots=int((cand != texture.EMPTY_KEY).sum()), coloured_slots=int((col != 0).sum()),
+               torch_colors_ms=round(t_torch, 1), torch_same_words=bool(torch.equal(out["t"], col)))
+    if variant is not None:
+        import ctypes
+
+        other = ctypes.CDLL(variant)
+        other.d3d_texture_face_colors.argtypes = texture._lib.SIGNATURES["d3d_texture_face_colors"]
+        other.d3d_texture_face_colors.restype = ctypes.c_int
+        libs = {"per_face": texture._lib.load(), "per_slot": other}
+        P, n, m = texture._ptr, int(vertices.shape[0]), int(faces.shape[0])
+        recs, nr = texture._table(ov, vertices.device)
+        cols = {k: torch.zeros_like(col) for k in libs}
+
+        def call(k):
+            rc = libs[k].d3d_texture_face_colors(P(vertices), n, P(faces), m, P(cand), P(recs), nr, P(cols[k]), texture._stream())
+            if rc != 0:
+                raise RuntimeError("d3d_texture_face_colors of the %s build: %d" % (k, rc))
+
+        times = {k: [] for k in libs}
+        for _ in range(3):
+            for k in libs:
+                times[k].append(round(MB.timed_ms(lambda: call(k), iters), 3))
+        res["mappings"] = {"per_face_ms": times["per_face"], "per_slot_ms": times["per_slot"],
+                           "same_words": bool(torch.equal(cols["per_face"], cols["per_slot"]) and torch.equal(cols["per_face"], col))}
+    return res
+
+
+def run(views, voxel, iters, smooth=None, with_level=True, outlier_threshold=None, variant=None):
     grid = mesh.MeshGrid(MB.BORDER, voxel)
     mviews = views
     vertices, faces = mesh.depth_to_mesh(mviews, grid)
@@ -206,6 +296,8 @@ def run(views, voxel, iters, smooth=None, with_level=True):
         before = {"charts": nc, "pages": packing.n_pages, "atlas_texels": n_texels, "select_ms": round(t_select, 3),
                   "rects_ms": round(t_rects, 3), "fill_ms": round(t_fill, 3)}
         row["smooth"] = smooth_times(vertices, faces, ov, key, before, smooth, iters)
+    if outlier_threshold is not None:
+        row["outliers"] = outlier_times(vertices, faces, ov, outlier_threshold, iters, variant)
     return dict(row, **{"views": len(ov), "voxel_m": voxel, "faces": m, "vertices": n, "seen_faces": int((key != texture.EMPTY_KEY).sum()),
             "charts": nc, "pages": packing.n_pages, "atlas_texels": n_texels, "mean_candidates_per_face": round(float(cand.double().mean()), 3),
             "select_ms": round(t_select, 3), "charts_ms": round(t_charts, 3), "rects_ms": round(t_rects, 3), "fill_ms": round(t_fill, 3),
@@ -222,18 +314,24 @@ def main(argv=None):
     ap.add_argument("--smooth_views", type=float, default=None, metavar="W", help="also time the smoothing of the view choice with this weight")
     ap.add_argument("--smooth_max_loss", type=float, default=texture.DEFAULT_SMOOTH_MAX_LOSS)
     ap.add_argument("--smooth_rounds", type=int, default=texture.DEFAULT_SMOOTH_ROUNDS)
+    ap.add_argument("--outlier_threshold", type=float, default=None, metavar="T",
+                    help="also time the rejection of outlier views with this threshold (0.06 is the reference's fOutlierThreshold)")
+    ap.add_argument("--variant_library", default=None, metavar="SO",
+                    help="with --outlier_threshold: a COLORS=per_slot build of the library whose colour pass is timed beside this one")
     ap.add_argument("--no_level", action="store_true", help="skip the seam levelling's times (a row then keeps the recorded `level` entry)")
     a = ap.parse_args(argv)
     smooth = None
     if a.smooth_views is not None:
         smooth = texture.check_smooth_settings({"weight": a.smooth_views, "max_loss": a.smooth_max_loss, "rounds": a.smooth_rounds})
+    if a.outlier_threshold is not None:
+        texture.check_outlier_settings({"threshold": a.outlier_threshold})
     if not torch.cuda.is_available():
         raise RuntimeError("tools/texture_bench.py measures the GPU kernels: no GPU here")
     rows = []
     for nv in [int(x) for x in a.views.split(",")]:
         views = MB.make_views(nv, "cuda")
         for voxel in [float(x) for x in a.voxels.split(",")]:
-            r = run(views, voxel, a.iters, smooth, not a.no_level)
+            r = run(views, voxel, a.iters, smooth, not a.no_level, a.outlier_threshold, a.variant_library)
             print(json.dumps(r), flush=True)
             rows.append(r)
         del views
@@ -247,7 +345,7 @@ def main(argv=None):
             if mine is None:
                 rows.append(r)
             else:
-                for k in ("level", "smooth"):
+                for k in ("level", "smooth", "outliers"):
                     if k in r and k not in mine:
                         mine[k] = r[k]
         rows.sort(key=lambda r: (r["views"], -r["voxel_m"]))
