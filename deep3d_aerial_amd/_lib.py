@@ -187,6 +187,12 @@ SIGNATURES = {
                            ctypes.POINTER(_i), _vp],
     "d3d_texture_face_colors": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp],
     "d3d_texture_outliers": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp],
+    "d3d_mesh_refine_views_max": [],
+    "d3d_mesh_refine_frames": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp],
+    "d3d_mesh_refine_views": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _i, _d, _i, _d, _vp, _vp],
+    "d3d_mesh_refine_match": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _i, _i, _d, _d, ctypes.c_longlong, _d, _vp, _vp, _vp, _vp, _vp],
+    "d3d_mesh_refine_relax": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _f, _i, _vp, _vp, _vp],
+    "d3d_mesh_refine_apply": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp],
     "d3d_texture_level_scratch_bytes": ([ctypes.c_longlong], _sz),
     "d3d_texture_level_incidence": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp],
     "d3d_texture_level_pairs": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp,

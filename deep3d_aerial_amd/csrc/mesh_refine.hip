@@ -1,0 +1,556 @@
+// Refining the surface mesh against the images: a plane sweep per vertex along its normal, then a screened
+// smoothing of the scalar displacement.  The rule is this project's (deep3d_aerial_amd/refine.py states it, and
+// include/deep3d_planesweep.h too); it does not claim to match OpenMVS's RefineMesh.
+//
+// frames: one lane per vertex: the area-weighted normal over the vertex's row of the vertex -> face CSR, two tangents.
+// views:  one lane per vertex, looping over the call's views (a view's record is the same address in every lane); the RV
+//         smallest keys sit in registers and a new key goes through an unrolled compare-exchange chain.
+// match:  one lane per vertex, looping over the hypotheses.  Per slot the view's R, t, K are copied to registers once and the 25
+//         points of the patch are projected and tapped; slot 0's quantised greys wait in LDS (one 16-bit column per lane, no bank
+//         conflicts) for the products with slots 1 .. 3, so the running integer sums are a handful of registers.  The z of every
+//         (hypothesis, pair) waits in private memory for the pick, which needs every hypothesis; a vertex whose last pair has
+//         failed stops sweeping.  Built with -DD3D_REFINE_PER_HYPOTHESIS the pass is one lane per (vertex, hypothesis) instead,
+//         16 lanes per vertex, four vertices per wave, the validity of a pair (an AND), the pick (a maximum) and the pick's two
+//         neighbours crossing lanes by shuffles inside the group: the mapping the design first recommended, about half as fast
+//         (tools/mesh_refine_bench.py --variant_library times both; DESIGN.md §4.21 has the rows).
+// relax:  one lane per vertex per Jacobi step, fp32, two buffers.
+// apply:  one lane per vertex.
+// Every value is written with ordinary vector stores; the one atomic is the integer add of a wave's share of the four
+// counters, whose return value is not used.  The geometry is fp64 with no contraction, the sums of the match are integers.
+#include <climits>
+#include <cmath>
+#include <cstdint>
+
+#include "common.h"
+#include "geom_shared.h"
+#include "texture_shared.h"
+
+namespace d3d {
+
+constexpr int RF_BLOCK = 256;
+constexpr int RF_VIEWS = 4;                    // keys per vertex (d3d_mesh_refine_views_max)
+constexpr int RF_PAIRS = RF_VIEWS - 1;         // (slot 0, slot j)
+constexpr int RF_MAX_REACH = 7;
+constexpr int RF_GROUP = 16;                   // lanes per vertex of the match: hypotheses 0 .. 2 reach <= 14
+constexpr int RF_HALF = 2;                     // the patch is (2 RF_HALF + 1)^2 points
+constexpr int RF_SIDE = 2 * RF_HALF + 1;
+constexpr int RF_POINTS = RF_SIDE * RF_SIDE;   // N = 25
+constexpr int RF_QMAX = 3060;                  // 4 * 3 * 255: the sum of the three channels in quarter grey levels
+constexpr long long RF_EMPTY = 0x7fffffffffffffffll;
+
+struct RfFrame {
+    double n[3], t1[3], t2[3];
+};
+
+__device__ __forceinline__ void rf_load_frame(const double* __restrict__ frame, long v, RfFrame* F) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        F->n[c] = frame[9 * v + c];
+        F->t1[c] = frame[9 * v + 3 + c];
+        F->t2[c] = frame[9 * v + 6 + c];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// frames
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(RF_BLOCK) void rf_frames_kernel(const float* __restrict__ vertices, long n, const int* __restrict__ faces,
+                                                             long m, const int* __restrict__ face_offset,
+                                                             const int* __restrict__ face_index, const unsigned char* __restrict__ fixed,
+                                                             double* __restrict__ frame, unsigned char* __restrict__ active) {
+    const long v = (long)blockIdx.x * RF_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    double N[3] = {0.0, 0.0, 0.0};
+    int used = 0;
+    const long s = max(face_offset[v], 0), e = min((long)face_offset[v + 1], 3 * m);
+    for (long j = s; j < e; ++j) {
+        const int f = face_index[j];
+        int ia, ib, ic;
+        if (f < 0 || f >= m || !geom_face<true>(faces, f, n, &ia, &ib, &ic)) continue;
+        double a[3], e1[3], e2[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            a[c] = (double)vertices[3l * ia + c];
+            e1[c] = (double)vertices[3l * ib + c] - a[c];
+            e2[c] = (double)vertices[3l * ic + c] - a[c];
+        }
+        N[0] += e1[1] * e2[2] - e1[2] * e2[1];
+        N[1] += e1[2] * e2[0] - e1[0] * e2[2];
+        N[2] += e1[0] * e2[1] - e1[1] * e2[0];
+        ++used;
+    }
+    const double len = sqrt((N[0] * N[0] + N[1] * N[1]) + N[2] * N[2]);
+    const bool ok = used > 0 && !fixed[v] && isfinite(N[0]) && isfinite(N[1]) && isfinite(N[2]) && isfinite(len) && len > 0.0;
+    double out[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (ok) {
+        const double nx = N[0] / len, ny = N[1] / len, nz = N[2] / len;
+        const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
+        const int j = ax <= ay && ax <= az ? 0 : (ay <= az ? 1 : 2);   // the axis of smallest |n_j|, ties to the lowest j
+        // e_j x n, its zero component written as such
+        const double cx = j == 0 ? 0.0 : (j == 1 ? nz : -ny);
+        const double cy = j == 0 ? -nz : (j == 1 ? 0.0 : nx);
+        const double cz = j == 0 ? ny : (j == 1 ? -nx : 0.0);
+        const double cl = sqrt((cx * cx + cy * cy) + cz * cz);
+        const double t1x = cx / cl, t1y = cy / cl, t1z = cz / cl;
+        out[0] = nx, out[1] = ny, out[2] = nz;
+        out[3] = t1x, out[4] = t1y, out[5] = t1z;
+        out[6] = ny * t1z - nz * t1y;
+        out[7] = nz * t1x - nx * t1z;
+        out[8] = nx * t1y - ny * t1x;
+    }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) frame[9 * v + c] = out[c];
+    active[v] = ok ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// view lists
+// ---------------------------------------------------------------------------------------------------------------------------
+// Inserts k into the sorted list c (increasing, padded with RF_EMPTY) and drops the largest; a key the list already holds is
+// dropped instead.  Every index is a compile-time constant after unrolling.
+__device__ __forceinline__ void rf_insert(long long (&c)[RF_VIEWS], long long k) {
+#pragma unroll
+    for (int i = 0; i < RF_VIEWS; ++i) {
+        k = k == c[i] ? RF_EMPTY : k;
+        const long long lo = k < c[i] ? k : c[i];
+        k = k < c[i] ? c[i] : k;
+        c[i] = lo;
+    }
+}
+
+__global__ __launch_bounds__(RF_BLOCK) void rf_views_kernel(const float* __restrict__ vertices, long n, const double* __restrict__ frame,
+                                                            const unsigned char* __restrict__ active,
+                                                            const d3d_ortho_view_t* __restrict__ views, int n_views, double tol1, double slack,
+                                                            long long* __restrict__ list) {
+    const long v = (long)blockIdx.x * RF_BLOCK + threadIdx.x;
+    if (v >= n || !active[v]) return;
+    const double X[3] = {(double)vertices[3 * v], (double)vertices[3 * v + 1], (double)vertices[3 * v + 2]};
+    const double nrm[3] = {frame[9 * v], frame[9 * v + 1], frame[9 * v + 2]};
+    long long c[RF_VIEWS];
+#pragma unroll
+    for (int i = 0; i < RF_VIEWS; ++i) c[i] = list[(long)RF_VIEWS * v + i];
+    for (int vi = 0; vi < n_views; ++vi) {
+        const d3d_ortho_view_t& V = views[vi];
+        if (!V.depth || V.W < 1 || V.H < 1) continue;
+        double u, w, p2;
+        if (!ortho_uv(V, X[0], X[1], X[2], &u, &w, &p2)) continue;
+        const double dx = V.C[0] - X[0], dy = V.C[1] - X[1], dz = V.C[2] - X[2];
+        const double dot = (nrm[0] * dx + nrm[1] * dy) + nrm[2] * dz;
+        if (!(dot > 0.0)) continue;
+        const int px = min(max((int)floor(u + 0.5), 0), V.W - 1), py = min(max((int)floor(w + 0.5), 0), V.H - 1);
+        const float D = V.depth[(long)py * V.W + px];
+        if (!(isfinite(D) && D > 0.0f && p2 <= (double)D * tol1 + slack)) continue;
+        const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
+        const double s = 1.0 - dot / dist;
+        if (!isfinite(s)) continue;
+        rf_insert(c, ((long long)__float_as_uint((float)s) << 32) | (long long)(unsigned)V.id);
+    }
+#pragma unroll
+    for (int i = 0; i < RF_VIEWS; ++i) list[(long)RF_VIEWS * v + i] = c[i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// match
+// ---------------------------------------------------------------------------------------------------------------------------
+// ortho's bilinear tap (ortho.hip, texture_outliers.hip to_tap, restated: those files are left alone) at (u, v), not rounded,
+// then q = clamp(floor(4 ((tR + tG) + tB) + 0.5), 0, 3060).
+__device__ __forceinline__ int rf_grey(const unsigned* __restrict__ rgba, int W, int H, double u, double v) {
+    const double fu = floor(u), fv = floor(v);
+    const double fx = u - fu, fy = v - fv;
+    const int x0 = (int)fmin(fmax(fu, 0.0), (double)(W - 1)), y0 = (int)fmin(fmax(fv, 0.0), (double)(H - 1));
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+    const unsigned t00 = rgba[(long)y0 * W + x0], t10 = rgba[(long)y0 * W + x1];
+    const unsigned t01 = rgba[(long)y1 * W + x0], t11 = rgba[(long)y1 * W + x1];
+    const double w00 = (1.0 - fx) * (1.0 - fy), w10 = fx * (1.0 - fy), w01 = (1.0 - fx) * fy, w11 = fx * fy;
+    double t[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const int sh = 8 * ch;
+        t[ch] = w00 * (double)((t00 >> sh) & 255u) + w10 * (double)((t10 >> sh) & 255u) + w01 * (double)((t01 >> sh) & 255u) +
+                w11 * (double)((t11 >> sh) & 255u);
+    }
+    return (int)fmin(fmax(floor(4.0 * ((t[0] + t[1]) + t[2]) + 0.5), 0.0), (double)RF_QMAX);
+}
+
+// The camera of one slot in registers.
+struct RfCam {
+    double R[9], t[3], K[9];
+    const unsigned* rgba;
+    int W, H;
+};
+
+// The view of a key in the call's table when it has an image: false otherwise.
+__device__ __forceinline__ bool rf_cam(const d3d_ortho_view_t* __restrict__ views, int n_views, long long key, RfCam* C) {
+    if (key == RF_EMPTY) return false;
+    const int vi = tx_find(views, n_views, (int)(unsigned)key);
+    if (vi < 0) return false;
+    const d3d_ortho_view_t* V = views + vi;
+    if (!(V->rgba && V->W >= 1 && V->H >= 1)) return false;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) C->R[i] = V->R[i], C->K[i] = V->K[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) C->t[i] = V->t[i];
+    C->rgba = V->rgba, C->W = V->W, C->H = V->H;
+    return true;
+}
+
+// The patch of hypothesis k in one slot: *sum and *sq get the sums of q and q^2; with FIRST the q go to the lane's LDS column
+// q0, else *prod gets the sum of q0 q.  False when a point of the patch is not valid in the view.
+template <bool FIRST>
+__device__ __forceinline__ bool rf_patch(const RfCam& C, const double (&Xk)[3], const RfFrame& F, double spacing, unsigned short* q0,
+                                         int* sum, int* sq, int* prod) {
+    int s = 0, ss = 0, sp = 0;
+    bool all = true;
+#pragma unroll 1
+    for (int p = 0; p < RF_POINTS; ++p) {
+        const double a = (double)(p % RF_SIDE - RF_HALF) * spacing, b = (double)(p / RF_SIDE - RF_HALF) * spacing;   // b-major
+        double P[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) P[c] = (Xk[c] + a * F.t1[c]) + b * F.t2[c];
+        const GeomPq r = geom_project(C, P[0], P[1], P[2]);
+        const double u = r.q0 / r.q2, v = r.q1 / r.q2;
+        const bool ok = r.p2 > 0.0 && r.q2 > 0.0 && u >= 0.0 && u <= (double)(C.W - 1) && v >= 0.0 && v <= (double)(C.H - 1);
+        const int q = ok ? rf_grey(C.rgba, C.W, C.H, u, v) : 0;
+        all = all && ok;
+        s += q;
+        ss += q * q;
+        if (FIRST)
+            q0[p * RF_BLOCK] = (unsigned short)q;
+        else
+            sp += (int)q0[p * RF_BLOCK] * q;
+    }
+    *sum = s, *sq = ss;
+    if (!FIRST) *prod = sp;
+    return all;
+}
+
+// Hypothesis k of one vertex: bit j - 1 of the result is set when pair (slot 0, slot j) is valid at k, and z[j - 1] is its
+// score then.  cams / has: the slots' cameras.  q0: the lane's LDS column.
+__device__ __forceinline__ unsigned rf_hypothesis(const double (&X)[3], const RfFrame& F, const long long (&key)[RF_VIEWS],
+                                                  const d3d_ortho_view_t* __restrict__ views, int n_views, double h, double spacing,
+                                                  long long Tv, unsigned short* q0, double (&z)[RF_PAIRS]) {
+    double Xk[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Xk[c] = X[c] + h * F.n[c];
+#pragma unroll
+    for (int j = 0; j < RF_PAIRS; ++j) z[j] = 0.0;
+    RfCam C;
+    if (!rf_cam(views, n_views, key[0], &C)) return 0u;
+    int s0, ss0, unused;
+    if (!rf_patch<true>(C, Xk, F, spacing, q0, &s0, &ss0, &unused)) return 0u;
+    const long long va = (long long)RF_POINTS * ss0 - (long long)s0 * s0;
+    if (va < Tv) return 0u;
+    unsigned mask = 0;
+#pragma unroll 1
+    for (int j = 1; j < RF_VIEWS; ++j) {
+        // (key[j] is the one runtime index into a lane's arrays: the four keys live in 32 bytes of private memory and a slot costs one
+        //  8-byte load from it, against the slot's 100 texel gathers; written as selects the compiler folds them back into this load)
+        if (!rf_cam(views, n_views, key[j], &C)) continue;
+        int sj, ssj, pj;
+        if (!rf_patch<false>(C, Xk, F, spacing, q0, &sj, &ssj, &pj)) continue;
+        const long long vb = (long long)RF_POINTS * ssj - (long long)sj * sj;
+        if (vb < Tv) continue;
+        const long long num = (long long)RF_POINTS * pj - (long long)s0 * sj;
+        const double zj = (double)num / sqrt((double)va * (double)vb);
+        // (j is a runtime value here: the three stores are selects, so z stays in registers)
+        z[0] = j == 1 ? zj : z[0];
+        z[1] = j == 2 ? zj : z[1];
+        z[2] = j == 3 ? zj : z[2];
+        mask |= 1u << (j - 1);
+    }
+    return mask;
+}
+
+// score_k = (the sum of z over the used pairs, in pair order) / their number.
+__device__ __forceinline__ double rf_score(unsigned used, const double (&z)[RF_PAIRS]) {
+    double s = 0.0;
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < RF_PAIRS; ++j)
+        if ((used >> j) & 1u) {
+            s += z[j];
+            ++cnt;
+        }
+    return s / (double)cnt;
+}
+
+// (score a, hypothesis ka) beats (score b, hypothesis kb): larger score, then smaller |k - reach|, then smaller k.
+__device__ __forceinline__ bool rf_better(double a, int ka, double b, int kb, int reach) {
+    if (a != b) return a > b;
+    const int da = abs(ka - reach), db = abs(kb - reach);
+    return da != db ? da < db : ka < kb;
+}
+
+// The pick from the best hypothesis and its neighbours' scores (sm, sp; used only when 0 < kbest < 2 reach).
+__device__ __forceinline__ void rf_pick(int kbest, double s0, double sm, double sp, int reach, double step, double min_score, float* weight,
+                                        float* d0) {
+    double delta = 0.0;
+    if (kbest > 0 && kbest < 2 * reach) {
+        const double den = (sm - 2.0 * s0) + sp;
+        if (den < 0.0) delta = fmin(fmax(0.5 * (sm - sp) / den, -0.5), 0.5);
+    }
+    *weight = s0 < min_score ? 0.0f : 1.0f;
+    *d0 = (float)(((double)(kbest - reach) + delta) * step);
+}
+
+#ifdef D3D_REFINE_PER_HYPOTHESIS
+constexpr int RF_LANES_PER_VERTEX = RF_GROUP;
+__global__ __launch_bounds__(RF_BLOCK) void rf_match_kernel(const float* __restrict__ vertices, long n, const double* __restrict__ frame,
+                                                            const unsigned char* __restrict__ active, const long long* __restrict__ list,
+                                                            const d3d_ortho_view_t* __restrict__ views, int n_views, int reach, double step,
+                                                            double spacing, long long Tv, double min_score, int* __restrict__ kstar,
+                                                            float* __restrict__ weight, float* __restrict__ d0, int* __restrict__ counts) {
+    __shared__ unsigned short q0_lds[RF_POINTS * RF_BLOCK];
+    const long v = ((long)blockIdx.x * RF_BLOCK + threadIdx.x) / RF_GROUP;
+    const int k = threadIdx.x & (RF_GROUP - 1);
+    const bool vertex = v < n;
+    const bool act = vertex && active[v];
+    long long key[RF_VIEWS] = {RF_EMPTY, RF_EMPTY, RF_EMPTY, RF_EMPTY};
+    if (act) {
+#pragma unroll
+        for (int i = 0; i < RF_VIEWS; ++i) key[i] = list[(long)RF_VIEWS * v + i];
+    }
+    const bool two = key[1] != RF_EMPTY;
+    const bool sweep = two && k <= 2 * reach;
+    unsigned mask = (1u << RF_PAIRS) - 1u;   // an idle lane agrees with every pair
+    double z[RF_PAIRS] = {0.0, 0.0, 0.0};
+    if (sweep) {
+        RfFrame F;
+        rf_load_frame(frame, v, &F);
+        const double X[3] = {(double)vertices[3 * v], (double)vertices[3 * v + 1], (double)vertices[3 * v + 2]};
+        mask = rf_hypothesis(X, F, key, views, n_views, (double)(k - reach) * step, spacing, Tv, q0_lds + threadIdx.x, z);
+    }
+    // a pair is used when it is valid at every hypothesis
+    unsigned used = mask;
+#pragma unroll
+    for (int d = RF_GROUP / 2; d >= 1; d >>= 1) used &= (unsigned)__shfl_xor((int)used, d, RF_GROUP);
+    used = two ? used : 0u;
+    const bool scored = sweep && used != 0u;
+    const double score = scored ? rf_score(used, z) : 0.0;
+    // the pick: the best (score, k) of the group's sweeping lanes, in every lane
+    double bs = score;
+    int bk = scored ? k : -1;
+#pragma unroll
+    for (int d = RF_GROUP / 2; d >= 1; d >>= 1) {
+        const double os = __shfl_xor(bs, d, RF_GROUP);
+        const int ok = __shfl_xor(bk, d, RF_GROUP);
+        if (ok >= 0 && (bk < 0 || rf_better(os, ok, bs, bk, reach))) bs = os, bk = ok;
+    }
+    const int at = max(bk, 0);
+    const double sm = __shfl(score, max(at - 1, 0), RF_GROUP), sp = __shfl(score, min(at + 1, RF_GROUP - 1), RF_GROUP);
+    int c_active = 0, c_two = 0, c_used = 0, c_moved = 0;
+    if (vertex && k == 0) {
+        float w = 0.0f, d = 0.0f;
+        if (bk >= 0) rf_pick(bk, bs, sm, sp, reach, step, min_score, &w, &d);
+        kstar[v] = bk;
+        weight[v] = w;
+        d0[v] = d;
+        c_active = act ? 1 : 0, c_two = two ? 1 : 0, c_used = used != 0u ? 1 : 0, c_moved = w != 0.0f ? 1 : 0;
+    }
+    const int sums[4] = {wave_sum(c_active), wave_sum(c_two), wave_sum(c_used), wave_sum(c_moved)};
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (sums[c]) atomicAdd(counts + c, sums[c]);
+    }
+}
+#else
+constexpr int RF_LANES_PER_VERTEX = 1;
+__global__ __launch_bounds__(RF_BLOCK) void rf_match_kernel(const float* __restrict__ vertices, long n, const double* __restrict__ frame,
+                                                            const unsigned char* __restrict__ active, const long long* __restrict__ list,
+                                                            const d3d_ortho_view_t* __restrict__ views, int n_views, int reach, double step,
+                                                            double spacing, long long Tv, double min_score, int* __restrict__ kstar,
+                                                            float* __restrict__ weight, float* __restrict__ d0, int* __restrict__ counts) {
+    __shared__ unsigned short q0_lds[RF_POINTS * RF_BLOCK];
+    const long v = (long)blockIdx.x * RF_BLOCK + threadIdx.x;
+    const bool vertex = v < n;
+    const bool act = vertex && active[v];
+    long long key[RF_VIEWS] = {RF_EMPTY, RF_EMPTY, RF_EMPTY, RF_EMPTY};
+    if (act) {
+#pragma unroll
+        for (int i = 0; i < RF_VIEWS; ++i) key[i] = list[(long)RF_VIEWS * v + i];
+    }
+    const bool two = key[1] != RF_EMPTY;
+    unsigned used = 0u;
+    int bk = -1;
+    float w = 0.0f, d = 0.0f;
+    if (two) {
+        RfFrame F;
+        rf_load_frame(frame, v, &F);
+        const double X[3] = {(double)vertices[3 * v], (double)vertices[3 * v + 1], (double)vertices[3 * v + 2]};
+        double zc[(2 * RF_MAX_REACH + 1) * RF_PAIRS];   // z of every (hypothesis, pair): indexed at run time, so it lives in private memory
+        used = (1u << RF_PAIRS) - 1u;
+#pragma unroll 1
+        for (int k = 0; k <= 2 * reach && used; ++k) {   // (a pair that fails once is never used: the sweep may stop when none is left)
+            double z[RF_PAIRS];
+            used &= rf_hypothesis(X, F, key, views, n_views, (double)(k - reach) * step, spacing, Tv, q0_lds + threadIdx.x, z);
+#pragma unroll
+            for (int j = 0; j < RF_PAIRS; ++j) zc[k * RF_PAIRS + j] = z[j];
+        }
+        if (used) {
+            double bs = 0.0;
+#pragma unroll 1
+            for (int k = 0; k <= 2 * reach; ++k) {
+                const double z[RF_PAIRS] = {zc[k * RF_PAIRS], zc[k * RF_PAIRS + 1], zc[k * RF_PAIRS + 2]};
+                const double s = rf_score(used, z);
+                if (bk < 0 || rf_better(s, k, bs, bk, reach)) bs = s, bk = k;
+            }
+            double sm = 0.0, sp = 0.0;
+            if (bk > 0 && bk < 2 * reach) {
+                const int km = bk - 1, kp = bk + 1;
+                const double zm[RF_PAIRS] = {zc[km * RF_PAIRS], zc[km * RF_PAIRS + 1], zc[km * RF_PAIRS + 2]};
+                const double zp[RF_PAIRS] = {zc[kp * RF_PAIRS], zc[kp * RF_PAIRS + 1], zc[kp * RF_PAIRS + 2]};
+                sm = rf_score(used, zm), sp = rf_score(used, zp);
+            }
+            rf_pick(bk, bs, sm, sp, reach, step, min_score, &w, &d);
+        }
+    }
+    if (vertex) {
+        kstar[v] = bk;
+        weight[v] = w;
+        d0[v] = d;
+    }
+    const int sums[4] = {wave_sum(act ? 1 : 0), wave_sum(two ? 1 : 0), wave_sum(used != 0u ? 1 : 0), wave_sum(w != 0.0f ? 1 : 0)};
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (sums[c]) atomicAdd(counts + c, sums[c]);
+    }
+}
+#endif
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// relax and apply
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(RF_BLOCK) void rf_relax_init_kernel(const float* __restrict__ weight, const float* __restrict__ d0,
+                                                                 const unsigned char* __restrict__ active, long n, float* __restrict__ d) {
+    const long v = (long)blockIdx.x * RF_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    d[v] = active[v] ? weight[v] * d0[v] : 0.0f;
+}
+
+__global__ __launch_bounds__(RF_BLOCK) void rf_relax_kernel(const float* __restrict__ weight, const float* __restrict__ d0,
+                                                            const unsigned char* __restrict__ active, const long long* __restrict__ offset,
+                                                            const int* __restrict__ nbr, long n, float lambda, const float* __restrict__ src,
+                                                            float* __restrict__ dst) {
+    const long v = (long)blockIdx.x * RF_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    float out = 0.0f;
+    if (active[v]) {
+        const long long s = offset[v], e = offset[v + 1];
+        float sum = 0.0f;
+        for (long long j = s; j < e; ++j) {
+            const int u = nbr[j];
+            sum += u >= 0 && u < n ? src[u] : 0.0f;
+        }
+        const float mean = e > s ? sum / (float)(e - s) : 0.0f;
+        const float w = weight[v];
+        out = (w * d0[v] + lambda * mean) / (w + lambda);
+    }
+    dst[v] = out;
+}
+
+__global__ __launch_bounds__(RF_BLOCK) void rf_apply_kernel(const float* __restrict__ vertices, long n, const double* __restrict__ frame,
+                                                            const unsigned char* __restrict__ active, const float* __restrict__ d,
+                                                            float* __restrict__ out) {
+    const long v = (long)blockIdx.x * RF_BLOCK + threadIdx.x;
+    if (v >= n) return;
+    const bool act = active[v] != 0;
+    const double dv = (double)d[v];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float x = vertices[3 * v + c];
+        out[3 * v + c] = act ? (float)((double)x + dv * frame[9 * v + c]) : x;
+    }
+}
+
+}  // namespace d3d
+
+using namespace d3d;
+
+extern "C" int d3d_mesh_refine_views_max(void) { return RF_VIEWS; }
+
+extern "C" int d3d_mesh_refine_frames(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* face_offset,
+                                      const int* face_index, const unsigned char* fixed, double* frame, unsigned char* active,
+                                      d3d_stream_t stream) {
+    D3D_REQUIRE(vertices && face_offset && fixed && frame && active && ((faces && face_index) || n_faces == 0),
+                "null pointer (vertices, faces, face_offset, face_index, fixed, frame, active)");
+    D3D_REQUIRE(n_vertices > 0 && n_vertices < (1ll << 31) && n_faces >= 0 && 6 * n_faces < (1ll << 31),
+                "n_vertices=%lld, n_faces=%lld (1 .. 2^31 - 1 vertices, 6 n_faces < 2^31)", n_vertices, n_faces);
+    hipLaunchKernelGGL(rf_frames_kernel, dim3(ceil_div(n_vertices, RF_BLOCK)), dim3(RF_BLOCK), 0, (hipStream_t)stream, vertices,
+                       (long)n_vertices, faces, (long)n_faces, face_offset, face_index, fixed, frame, active);
+    D3D_LAUNCH_CHECK("rf_frames_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_refine_views(const float* vertices, long long n_vertices, const double* frame, const unsigned char* active,
+                                     const d3d_ortho_view_t* views, int n_views, double depth_tolerance, int reach, double step,
+                                     long long* list, d3d_stream_t stream) {
+    D3D_REQUIRE(vertices && frame && active && list, "null pointer (vertices, frame, active, list)");
+    D3D_REQUIRE(n_vertices > 0 && n_vertices < (1ll << 31), "n_vertices=%lld (1 .. 2^31 - 1)", n_vertices);
+    D3D_REQUIRE(n_views >= 0 && n_views < (1 << 20), "%d views (0 .. 2^20 - 1)", n_views);
+    D3D_REQUIRE(views || n_views == 0, "null pointer (views) with %d views", n_views);
+    D3D_REQUIRE(std::isfinite(depth_tolerance) && depth_tolerance >= 0.0, "depth_tolerance=%g must be finite and >= 0", depth_tolerance);
+    D3D_REQUIRE(reach >= 1 && reach <= RF_MAX_REACH, "reach=%d (1 .. %d)", reach, RF_MAX_REACH);
+    D3D_REQUIRE(std::isfinite(step) && step > 0.0, "step=%g must be finite and > 0", step);
+    if (n_views == 0) return D3D_OK;
+    hipLaunchKernelGGL(rf_views_kernel, dim3(ceil_div(n_vertices, RF_BLOCK)), dim3(RF_BLOCK), 0, (hipStream_t)stream, vertices,
+                       (long)n_vertices, frame, active, views, n_views, 1.0 + depth_tolerance, (double)reach * step, list);
+    D3D_LAUNCH_CHECK("rf_views_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_refine_match(const float* vertices, long long n_vertices, const double* frame, const unsigned char* active,
+                                     const long long* list, const d3d_ortho_view_t* views, int n_views, int reach, double step, double spacing,
+                                     long long min_variance, double min_score, int* kstar, float* weight, float* d0, int* counts,
+                                     d3d_stream_t stream) {
+    D3D_REQUIRE(vertices && frame && active && list && kstar && weight && d0 && counts,
+                "null pointer (vertices, frame, active, list, kstar, weight, d0, counts)");
+    D3D_REQUIRE(n_vertices > 0 && n_vertices < (1ll << 31) / RF_GROUP, "n_vertices=%lld (1 .. 2^27 - 1)", n_vertices);
+    D3D_REQUIRE(n_views >= 0 && n_views < (1 << 20), "%d views (0 .. 2^20 - 1)", n_views);
+    D3D_REQUIRE(views || n_views == 0, "null pointer (views) with %d views", n_views);
+    D3D_REQUIRE(reach >= 1 && reach <= RF_MAX_REACH, "reach=%d (1 .. %d)", reach, RF_MAX_REACH);
+    D3D_REQUIRE(std::isfinite(step) && step > 0.0, "step=%g must be finite and > 0", step);
+    D3D_REQUIRE(std::isfinite(spacing) && spacing > 0.0, "spacing=%g must be finite and > 0", spacing);
+    D3D_REQUIRE(min_variance >= 1, "min_variance=%lld must be >= 1", min_variance);
+    D3D_REQUIRE(std::isfinite(min_score) && min_score >= -1.0 && min_score <= 1.0, "min_score=%g must lie in -1 .. 1", min_score);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = hip_status(hipMemsetAsync(counts, 0, 4 * sizeof(int), st), "mesh refine: clear counts");
+    if (rc != D3D_OK) return rc;
+    hipLaunchKernelGGL(rf_match_kernel, dim3(ceil_div((long)RF_LANES_PER_VERTEX * n_vertices, RF_BLOCK)), dim3(RF_BLOCK), 0, st, vertices,
+                       (long)n_vertices, frame, active, list, views, n_views, reach, step, spacing, min_variance, min_score, kstar, weight, d0,
+                       counts);
+    D3D_LAUNCH_CHECK("rf_match_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_refine_relax(const float* weight, const float* d0, const unsigned char* active, const long long* offset, const int* nbr,
+                                     long long n_vertices, float lambda, int iterations, float* work, float* out, d3d_stream_t stream) {
+    D3D_REQUIRE(weight && d0 && active && offset && nbr && work && out, "null pointer (weight, d0, active, offset, nbr, work, out)");
+    D3D_REQUIRE(n_vertices > 0 && n_vertices < (1ll << 31), "n_vertices=%lld (1 .. 2^31 - 1)", n_vertices);
+    D3D_REQUIRE(std::isfinite(lambda) && lambda > 0.0f, "lambda=%g must be finite and > 0", (double)lambda);
+    D3D_REQUIRE(iterations >= 0 && iterations <= 100000, "iterations=%d (0 .. 100000)", iterations);
+    D3D_REQUIRE(work != out && d0 != out && d0 != work && weight != out && weight != work, "weight, d0, work and out must be distinct buffers");
+    hipStream_t st = (hipStream_t)stream;
+    const long n = (long)n_vertices;
+    float* dst = (iterations & 1) ? work : out;   // the last iteration writes out
+    hipLaunchKernelGGL(rf_relax_init_kernel, dim3(ceil_div(n, RF_BLOCK)), dim3(RF_BLOCK), 0, st, weight, d0, active, n, dst);
+    D3D_LAUNCH_CHECK("rf_relax_init_kernel launch");
+    for (int it = 0; it < iterations; ++it) {
+        const float* src = dst;
+        dst = dst == out ? work : out;
+        hipLaunchKernelGGL(rf_relax_kernel, dim3(ceil_div(n, RF_BLOCK)), dim3(RF_BLOCK), 0, st, weight, d0, active, offset, nbr, n, lambda, src, dst);
+        D3D_LAUNCH_CHECK("rf_relax_kernel launch");
+    }
+    return D3D_OK;
+}
+
+extern "C" int d3d_mesh_refine_apply(const float* vertices, long long n_vertices, const double* frame, const unsigned char* active, const float* d,
+                                     float* out, d3d_stream_t stream) {
+    D3D_REQUIRE(vertices && frame && active && d && out, "null pointer (vertices, frame, active, d, out)");
+    D3D_REQUIRE(n_vertices > 0 && n_vertices < (1ll << 31), "n_vertices=%lld (1 .. 2^31 - 1)", n_vertices);
+    hipLaunchKernelGGL(rf_apply_kernel, dim3(ceil_div(n_vertices, RF_BLOCK)), dim3(RF_BLOCK), 0, (hipStream_t)stream, vertices, (long)n_vertices,
+                       frame, active, d, out);
+    D3D_LAUNCH_CHECK("rf_apply_kernel launch");
+    return D3D_OK;
+}

@@ -926,9 +926,10 @@ def _decimate_and_report(v, f, ratio, target_faces, max_rounds):
     return v, f
 
 
-def build_and_write(views, settings):
+def build_and_write(views, settings, refine=None):
     """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on (removal, hole closing, smoothing),
-    then decimate when it is on, and write_ply to settings["path"]: (vertices, faces) as written."""
+    then decimate when it is on, then vertices = refine(vertices, faces) when a refinement is handed in (refine.refine_mesh bound to
+    its views: pipeline.write_mesh_of), and write_ply to settings["path"]: (vertices, faces) as written."""
     grid = MeshGrid(settings["border"], settings["voxel"])
     v, f = depth_to_mesh(views, grid, settings.get("trunc"), settings.get("min_views", DEFAULT_MIN_VIEWS),
                          settings.get("conf_threshold", DEFAULT_CONF), settings.get("views_per_batch"))
@@ -936,6 +937,8 @@ def build_and_write(views, settings):
         v, f = clean(v, f, *clean_settings(settings), close_holes=close_holes_setting(settings))
     if decimate_requested(settings):
         v, f = _decimate_and_report(v, f, *decimate_settings(settings))
+    if refine is not None:
+        v = refine(v, f)
     write_ply(settings["path"], v, f)
     return v, f
 

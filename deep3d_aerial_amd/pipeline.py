@@ -94,6 +94,10 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     gathered depth and confidence map with its camera, in global view order, cleans it when a clean step is on (mesh.clean),
     decimates it when asked (mesh.decimate), and writes the PLY; the DSM from the mesh and the texture use that mesh.  The
     other ranks do nothing (no collective: the file does not depend on the number of ranks); timings gets mesh_s on rank 0.
+    With mesh["refine"] (refine.check_refine_settings: {"step", ...}; absent: off) rank 0 refines the mesh against every view's
+    reference image before it writes the PLY (refine.refine_mesh, after the decimation): the other ranks' images reach it in one
+    gather (gather_refine_views), it refines alone, so the file still does not depend on the number of ranks; timings gets
+    mesh_refine_s (a part of mesh_s).
     texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad",
     "level" (optional: None, or the seam levelling's settings), "smooth_views" and "outliers" (optional, likewise)}
     (needs mesh; texture.settings_from_args): the mesh rank 0 wrote (after cleaning) textured from every rank's views and
@@ -107,6 +111,10 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         _mesh.clean_settings(mesh)
         _mesh.close_holes_setting(mesh)
         _mesh.decimate_settings(mesh)
+        if mesh.get("refine") is not None:
+            from . import refine as _refine
+
+            _refine.check_refine_settings(mesh["refine"])
     dsm_source = dsm.get("source", "pc") if dsm is not None else None
     if dsm is not None:
         from . import dsm as _dsm
@@ -138,7 +146,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     recs = view_records(dataset, fusion_num)
     mine = sharding.shard_views(n, rank, world_size, partition)
     cams = {}
-    images = {} if ortho is not None or texture is not None else None
+    refine = mesh.get("refine") if mesh is not None else None
+    images = {} if ortho is not None or texture is not None or refine is not None else None
     t0 = time.perf_counter()
     maps = predict.predict_views(model, dataset, output_folder, rank, world_size, device=device, keep_maps=True,
                                  feature_cache_bytes=feature_cache_bytes, display=display, partition=partition, cams=cams,
@@ -215,8 +224,12 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
                        allgather_bytes=int(all_maps.numel() * 4), fuse_s=t2 - g1, map_size=(H, W),
                        backend=dist.get_backend() if world_size > 1 else "none")
     built_mesh = None
+    refine_views = None
+    if refine is not None:
+        own = [(images[recs[i]["name"]][0], images[recs[i]["name"]][1]) for i in mine]
+        refine_views = gather_refine_views(own, all_maps, all_cams, n, rank, world_size, partition)
     if mesh is not None and rank == 0:
-        built_mesh = write_mesh_of(all_maps, all_cams, mesh, timings=timings)
+        built_mesh = write_mesh_of(all_maps, all_cams, mesh, timings=timings, refine_views=refine_views)
     if dsm is not None:
         if dsm_source == "mesh":
             built = write_mesh_dsm_of(built_mesh, dsm, device=all_maps.device, timings=timings) if rank == 0 else None
@@ -238,14 +251,58 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     return out
 
 
-def write_mesh_of(all_maps, all_cams, settings, timings=None):
+def gather_refine_views(own, all_maps, all_cams, n_views, rank=0, world_size=1, partition="block"):
+    """Every view with its image on rank 0, for the refinement of the mesh that lives there: [(id, K, E, depth [H,W], image)] by
+    global view index on rank 0, None elsewhere.  own: this rank's [(id, image [H,W,3] uint8)] in shard order.  Every rank must
+    call it.  The images travel in one gather (sharding.gather_points: a row per view, the id in eight trailing bytes); the depth
+    maps and cameras are already everywhere.  Rank 0 then refines alone, so the refined mesh is the same bytes for any number of
+    ranks."""
+    H, W = int(all_maps.shape[2]), int(all_maps.shape[3])
+    dev = all_maps.device
+    rows = torch.empty((len(own), H * W * 3 + 8), dtype=torch.uint8, device=dev)
+    for j, (vid, image) in enumerate(own):
+        if tuple(image.shape) != (H, W, 3) or image.dtype != torch.uint8:
+            raise ValueError("the refinement needs [%d,%d,3] uint8 reference images (got %s %s)" % (H, W, tuple(image.shape), image.dtype))
+        rows[j, :H * W * 3] = image.to(dev).reshape(-1)
+        rows[j, H * W * 3:] = torch.tensor([int(vid)], dtype=torch.int64).view(torch.uint8).to(dev)
+    rows = sharding.gather_points(rows, rank, world_size)
+    if rank != 0:
+        return None
+    order = [i for r in range(world_size) for i in sharding.shard_views(n_views, r, world_size, partition)]
+    views = [None] * n_views
+    for j, i in enumerate(order):
+        vid = int(rows[j, H * W * 3:].cpu().view(torch.int64)[0])
+        views[i] = (vid, all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], rows[j, :H * W * 3].reshape(H, W, 3).contiguous())
+    return views
+
+
+def write_mesh_of(all_maps, all_cams, settings, timings=None, refine_views=None):
     """The mesh of every view (all_maps [n,2,H,W] depth and confidence, all_cams [n,2,4,4], by global view index), written to
-    settings["path"] (mesh.build_and_write: cleaned when a clean step is on, then decimated when asked).  Returns (vertices, faces) as written."""
+    settings["path"] (mesh.build_and_write: cleaned when a clean step is on, then decimated when asked, then, with
+    settings["refine"] (refine.check_refine_settings) and refine_views (gather_refine_views), refined against the images:
+    timings gets mesh_refine_s, a part of mesh_s).  Returns (vertices, faces) as written."""
     from . import mesh as _mesh
 
     t0 = time.perf_counter()
     views = [_mesh.MeshView(all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], all_maps[i, 1]) for i in range(all_maps.shape[0])]
-    res = _mesh.build_and_write(views, settings)
+    refine = None
+    if settings.get("refine") is not None:
+        from . import ortho as _ortho, refine as _refine
+
+        if refine_views is None:
+            raise ValueError("the mesh settings ask for a refinement: it needs the views' images (gather_refine_views)")
+        rs = _refine.check_refine_settings(settings["refine"])
+        ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in refine_views]
+
+        def refine(v, f):
+            torch.cuda.synchronize()
+            r0 = time.perf_counter()
+            out, _ = _refine.refine_mesh(v, f, ov, **rs)
+            torch.cuda.synchronize()
+            if timings is not None:
+                timings["mesh_refine_s"] = time.perf_counter() - r0
+            return out
+    res = _mesh.build_and_write(views, settings, refine=refine)
     torch.cuda.synchronize()
     if timings is not None:
         timings["mesh_s"] = time.perf_counter() - t0

@@ -575,6 +575,10 @@ def parse_args(argv=None):
 
     ap.add_argument("--mesh", default=None, help="with --fuse: write the surface mesh of all views' depth maps to this .ply, on rank 0")
     _mesh.add_arguments(ap, prefix="mesh_")
+    # refinement of the mesh against the images (deep3d_aerial_amd/refine.py): off unless --mesh_refine STEP is given
+    from . import refine as _refine
+
+    _refine.add_arguments(ap, prefix="mesh_refine_", step_flag="--mesh_refine")
     # texture of the mesh from the views (deep3d_aerial_amd/texture.py): off by default
     from . import texture as _texture
 
@@ -598,6 +602,10 @@ def parse_args(argv=None):
         ap.error("--mesh needs --mesh_border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax")
     if a.mesh is not None:
         _mesh.check_args(ap, a, prefix="mesh_")
+    if a.mesh_refine_step is not None:
+        if a.mesh is None:
+            ap.error("--mesh_refine needs --mesh (it is the mesh that is refined)")
+        _refine.check_args(ap, a, prefix="mesh_refine_", step_flag="--mesh_refine")
     if a.dsm is not None and a.dsm_source == "mesh":
         if a.mesh is None:
             ap.error("--dsm_source mesh needs --mesh (the DSM is rasterised from the mesh)")
@@ -654,7 +662,12 @@ def _ortho_settings(a):
 def _mesh_settings(a):
     from . import mesh as _mesh
 
-    return _mesh.settings_from_args(a, a.mesh, prefix="mesh_")
+    s = _mesh.settings_from_args(a, a.mesh, prefix="mesh_")
+    if getattr(a, "mesh_refine_step", None) is not None:
+        from . import refine as _refine
+
+        s["refine"] = _refine.settings_from_args(a, prefix="mesh_refine_")
+    return s
 
 
 def _texture_settings(a):
@@ -721,6 +734,8 @@ def main(argv=None):
             print("rank 0/%d: orthophoto %s in %.2f s" % (world, a.ortho, tm["ortho_s"]))
         if a.mesh is not None and rank == 0:
             print("rank 0/%d: mesh %s in %.2f s" % (world, a.mesh, tm["mesh_s"]))
+            if "mesh_refine_s" in tm:
+                print("rank 0/%d: mesh refined against the images in %.2f s" % (world, tm["mesh_refine_s"]))
         if a.texture is not None and rank == 0:
             print("rank 0/%d: textured mesh %s in %.2f s" % (world, a.texture, tm["texture_s"]))
         print("rank %d/%d: %d views in %.2f s, all-gather of %.1f MB in %.2f ms (%s), fusion of its %d reference views %.2f s, "

@@ -1355,6 +1355,66 @@ int d3d_texture_face_colors(const float* vertices, long long n_vertices, const i
 int d3d_texture_outliers(const long long* cand, const int* col, long long n_faces, int T, long long* cand_out, int* rejected, int* counts,
                          d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.21 -- refining the surface mesh against the images: a plane sweep per vertex along its normal and a screened
+ * smoothing of the displacement (deep3d_aerial_amd/refine.py states the rule in full; it is this project's and does not claim to
+ * match OpenMVS's RefineMesh).  Vertices move, nothing else: topology, face order and vertex count stay.  A mesh is vertices
+ * [n_vertices, 3] fp32 and faces [n_faces, 3] int32, 0 < n_vertices < 2^31, 6 n_faces < 2^31; a view is a d3d_ortho_view_t record.
+ * Every pointer is DEVICE memory.  The geometry is fp64 without contraction, sums left to right; no float atomics; the one integer
+ * atomic adds a wave's share of the four counters.  n_vertices = 0 is an argument error: nothing is launched.
+ */
+/* RV = 4: the keys per vertex of the view lists. */
+int d3d_mesh_refine_views_max(void);
+
+/* d3d_mesh_refine_frames: face_offset / face_index are d3d_mesh_decimate_incidence's outputs and fixed d3d_mesh_adjacency's for the
+ *   same mesh.  N = the sum over the vertex's row, in row order, of (b - a) x (c - a) of the faces whose three indices are in
+ *   range and distinct (a, b, c the face's corners in its own order); L = sqrt((Nx^2 + Ny^2) + Nz^2).  A vertex is active when it
+ *   has such a face, is not fixed, and N and L are finite with L > 0.  frame [n_vertices, 9] fp64 = (n, t1, t2): n = N / L;
+ *   j = the axis of smallest |n_j|, ties to the lowest; c = e_j x n = (0, -nz, ny) | (nz, 0, -nx) | (-ny, nx, 0), t1 = c /
+ *   sqrt((cx^2 + cy^2) + cz^2); t2 = n x t1.  All nine are 0 for an inactive vertex.  active [n_vertices] uint8. */
+int d3d_mesh_refine_frames(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* face_offset,
+                           const int* face_index, const unsigned char* fixed, double* frame, unsigned char* active, d3d_stream_t stream);
+
+/* d3d_mesh_refine_views: MERGES the keys of n_views views into list [n_vertices, RV] int64 (every entry INT64_MAX before the first
+ *   call): per active vertex the RV smallest distinct keys, increasing, padded with INT64_MAX, so the list does not depend on the
+ *   order or the batching of the views.  View V (with a depth map) sees vertex X when p2 > 0, q2 > 0, 0 <= u <= W-1, 0 <= v <= H-1
+ *   (d3d_ortho_select's projection), dot = (nx dx + ny dy) + nz dz > 0 with d = C - X, the depth D at pixel (floor(v + 0.5),
+ *   floor(u + 0.5)) is finite and > 0, and p2 <= D (1 + depth_tolerance) + reach * step.  s = 1 - dot / sqrt((dx^2 + dy^2) + dz^2),
+ *   finite; key = (bits(fp32(s)) << 32) | id.  An inactive vertex's row is left as it is.  reach 1 .. 7, step > 0. */
+int d3d_mesh_refine_views(const float* vertices, long long n_vertices, const double* frame, const unsigned char* active,
+                          const d3d_ortho_view_t* views, int n_views, double depth_tolerance, int reach, double step, long long* list,
+                          d3d_stream_t stream);
+
+/* d3d_mesh_refine_match: the sweep and the pick.  `views` is sorted by id; a slot of the list is present when its key is not
+ *   INT64_MAX and its id is in `views` with a non-null rgba.  A vertex that is inactive or has fewer than two keys gets kstar -1,
+ *   weight 0, d0 0.  Hypothesis k = 0 .. 2 reach: X_k = X + ((k - reach) step) n.  Patch: the 25 points (X_k + (a spacing) t1) +
+ *   (b spacing) t2, a, b = -2 .. 2, b-major; a point is valid in a view when p2 > 0, q2 > 0, 0 <= u <= W-1, 0 <= v <= H-1; its
+ *   grey q = clamp(floor(4 ((tR + tG) + tB) + 0.5), 0, 3060), t = d3d_ortho_colorize's bilinear tap, unrounded.  Pair j = 1 .. 3 is
+ *   (slot 0, slot j), both present; with int64 sums over the patch, num = 25 S(ab) - S(a) S(b), va = 25 S(aa) - S(a)^2, vb alike;
+ *   the pair is valid at k when all 25 points are valid in both views and va, vb >= min_variance (>= 1); z = (double)num /
+ *   sqrt((double)va (double)vb).  A pair is used when it is valid at every k; score_k = (the sum of z over the used pairs, in pair
+ *   order) / their number; without a used pair: kstar -1, weight 0, d0 0.  kstar = the k of largest score, ties to the smaller
+ *   |k - reach|, then the smaller k; weight = score < min_score ? 0 : 1; when 0 < kstar < 2 reach and den = (s- - 2 s0) + s+ < 0,
+ *   delta = clamp(0.5 (s- - s+) / den, -0.5, 0.5), else 0; d0 = fp32(((kstar - reach) + delta) step).  kstar [n_vertices] int32,
+ *   weight and d0 [n_vertices] fp32.  counts [4] int32 (cleared here): active vertices, vertices with two keys or more, vertices
+ *   with a used pair, vertices with weight 1. */
+int d3d_mesh_refine_match(const float* vertices, long long n_vertices, const double* frame, const unsigned char* active,
+                          const long long* list, const d3d_ortho_view_t* views, int n_views, int reach, double step, double spacing,
+                          long long min_variance, double min_score, int* kstar, float* weight, float* d0, int* counts,
+                          d3d_stream_t stream);
+
+/* d3d_mesh_refine_relax: the screened smoothing of the displacement over the CSR of d3d_mesh_adjacency, fp32, every operation
+ *   rounded.  d = weight * d0 at first; then `iterations` Jacobi steps d <- (weight * d0 + lambda * m) / (weight + lambda), m =
+ *   (the sum of the neighbours' d in CSR order, from 0) / fp32(their number).  An inactive vertex holds 0 and counts as a
+ *   neighbour.  out [n_vertices] fp32 gets the result, work [n_vertices] is the other buffer.  lambda > 0, iterations >= 0. */
+int d3d_mesh_refine_relax(const float* weight, const float* d0, const unsigned char* active, const long long* offset, const int* nbr,
+                          long long n_vertices, float lambda, int iterations, float* work, float* out, d3d_stream_t stream);
+
+/* d3d_mesh_refine_apply: out[v] = fp32(X + (double)d[v] * n) per component for an active vertex, X for any other.  out may be
+ *   vertices. */
+int d3d_mesh_refine_apply(const float* vertices, long long n_vertices, const double* frame, const unsigned char* active, const float* d,
+                          float* out, d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
