@@ -223,8 +223,16 @@ __global__ __launch_bounds__(256) void pair_softmax_max_kernel(const float* __re
 }
 
 // F.interpolate(bilinear, align_corners=False) source index / weights for one axis.
+// ONE_ROUNDING: the coordinate as ATen's builds compute it -- `scale * (dst + 0.5f) - 0.5f` contracted into a fused multiply-add,
+// on the CPU and on the GPU alike.  With the product rounded on its own the coordinate is an ulp off at some rows and columns of a
+// ratio that is no power of two, which costs the image gradient times that ulp: 3.7e-4 on depths of 400 .. 800 at 17 x 23 ->
+// 29 x 40 (tests/test_regress_gpu.py).  The resize kernel rounds once.  The online regression keeps the two roundings: its depth
+// planes are [1,1] or at half the resolution in every model (a power-of-two ratio gives an exact product, so both forms agree), and
+// with two roundings the coordinate of a [1,1] plane lies on the 2^-24 grid, so its two weights sum to exactly 1: the bit-equality
+// of a scalar plane and a constant map rests on that (tests/test_parity_gpu.py::test_online_regression).
+template <bool ONE_ROUNDING = false>
 __device__ __forceinline__ void lin_coord(int dst, float scale, int in_size, int& i0, int& i1, float& l1) {
-    float s = ((float)dst + 0.5f) * scale - 0.5f;
+    float s = ONE_ROUNDING ? fmaf((float)dst + 0.5f, scale, -0.5f) : ((float)dst + 0.5f) * scale - 0.5f;
     s = s < 0.0f ? 0.0f : s;
     i0 = (int)s;
     i0 = min(i0, in_size - 1);
@@ -248,9 +256,9 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
     if (X >= W || Y >= H) return;
     int y0, y1, x0[VEC], x1[VEC];
     float ly, lx[VEC];
-    lin_coord(Y, (float)h / (float)H, h, y0, y1, ly);
+    lin_coord<true>(Y, (float)h / (float)H, h, y0, y1, ly);
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) lin_coord(X + k, (float)w / (float)W, w, x0[k], x1[k], lx[k]);
+    for (int k = 0; k < VEC; ++k) lin_coord<true>(X + k, (float)w / (float)W, w, x0[k], x1[k], lx[k]);
     for (int z = blockIdx.z; z < n; z += gridDim.z) {
         V o;
 #pragma unroll

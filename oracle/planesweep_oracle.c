@@ -341,13 +341,13 @@ API void d3d_oracle_resize_bilinear(const float* in, int h, int w, int H, int W,
     const float sy = (float)h / (float)H, sx = (float)w / (float)W;
 #pragma omp parallel for schedule(static)
     for (int Y = 0; Y < H; ++Y) {
-        float fy = ((float)Y + 0.5f) * sy - 0.5f;
+        float fy = fmaf((float)Y + 0.5f, sy, -0.5f);   /* ONE rounding, as ATen's builds compute it (csrc/regress.hip lin_coord) */
         if (fy < 0.0f) fy = 0.0f;
         int y0 = (int)fy;
         int y1 = y0 + (y0 < h - 1 ? 1 : 0);
         float ly = fy - (float)y0, hy = 1.0f - ly;
         for (int X = 0; X < W; ++X) {
-            float fx = ((float)X + 0.5f) * sx - 0.5f;
+            float fx = fmaf((float)X + 0.5f, sx, -0.5f);
             if (fx < 0.0f) fx = 0.0f;
             int x0 = (int)fx;
             int x1 = x0 + (x0 < w - 1 ? 1 : 0);
