@@ -206,6 +206,16 @@ SIGNATURES = {
                                 _vp],
     "d3d_texture_level_apply": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong,
                                 _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp, _vp, _vp],
+    "d3d_texture_local_lds_words": ([], ctypes.c_longlong),
+    "d3d_texture_local_seams": [_vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp],
+    "d3d_texture_local_count": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp, _vp],
+    "d3d_texture_local_samples": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i,
+                                  _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "d3d_texture_local_fold": [_vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp],
+    "d3d_texture_local_band": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _vp],
+    "d3d_texture_local_sweeps": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _i, _vp, ctypes.POINTER(_i), _vp],
+    "d3d_texture_local_chart": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp],
+    "d3d_texture_local_apply": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _vp, _vp],
 }
 
 

@@ -157,30 +157,6 @@ __global__ __launch_bounds__(TX_BLOCK) void txl_csr_kernel(const long long* __re
 // ---------------------------------------------------------------------------------------------------------------------------
 // samples and right-hand side
 // ---------------------------------------------------------------------------------------------------------------------------
-struct TxlChart {
-    int x0, y0, w, h, ox, oy;
-    long long row0;   // the atlas row of the rect's first row
-    int slot;         // of the chart's view in the camera table, -1: the chart is skipped
-};
-
-// The chart's row of the table, checked as the fill checks it (a bad row is skipped, never read or written out of bounds).
-__device__ __forceinline__ TxlChart txl_chart(const int* __restrict__ table, long n_charts, int c, const long long* __restrict__ page_row,
-                                              int n_pages, const d3d_ortho_view_t* __restrict__ cams, int n_cams, int P) {
-    TxlChart C;
-    C.slot = -1;
-    if (c < 0 || c >= n_charts) return C;
-    const int* T = table + 8l * c;
-    C.x0 = T[0], C.y0 = T[1], C.w = T[2], C.h = T[3], C.ox = T[4], C.oy = T[5];
-    const int page = T[6];
-    if (page < 0 || page >= n_pages) return C;
-    C.row0 = page_row[page] + C.oy;
-    if (C.w < 1 || C.h < 1 || C.ox < 0 || C.ox + (long long)C.w > P || C.oy < 0 || C.row0 + C.h > page_row[page + 1]) return C;
-    C.slot = tx_find(cams, n_cams, T[7]);
-    return C;
-}
-
-__device__ __forceinline__ double txl_clamp(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
-
 __global__ __launch_bounds__(TX_BLOCK) void txl_samples_kernel(const float* __restrict__ vertices, long long n,
                                                                const long long* __restrict__ nodes, int n_nodes,
                                                                const int* __restrict__ table, long n_charts,
@@ -199,22 +175,9 @@ __global__ __launch_bounds__(TX_BLOCK) void txl_samples_kernel(const float* __re
         if (r.p2 > 0.0 && r.q2 > 0.0 && isfinite(u) && isfinite(w)) {
             const double x = (u - (double)C.x0) + (double)C.ox;
             const double y = ((w - (double)C.y0) + (double)C.oy) + (double)(C.row0 - C.oy);
-            const double xf = floor(x), yf = floor(y);
-            const double tx = x - xf, ty = y - yf;
-            // pad >= 1 keeps the taps inside the rect; a rect clamped at the image's border repeats its last texel
-            const long long ix0 = (long long)txl_clamp(xf, (double)C.ox, (double)(C.ox + C.w - 1));
-            const long long iy0 = (long long)txl_clamp(yf, (double)C.row0, (double)(C.row0 + C.h - 1));
-            const long long ix1 = min(ix0 + 1, (long long)(C.ox + C.w - 1)), iy1 = min(iy0 + 1, C.row0 + C.h - 1);
-            const unsigned c00 = atlas[iy0 * P + ix0], c10 = atlas[iy0 * P + ix1], c01 = atlas[iy1 * P + ix0], c11 = atlas[iy1 * P + ix1];
-            const double w00 = (1.0 - tx) * (1.0 - ty), w10 = tx * (1.0 - ty), w01 = (1.0 - tx) * ty, w11 = tx * ty;
-            float val[3];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const double a = (double)((c00 >> (8 * q)) & 255u), b = (double)((c10 >> (8 * q)) & 255u);
-                const double c = (double)((c01 >> (8 * q)) & 255u), d = (double)((c11 >> (8 * q)) & 255u);
-                val[q] = (float)(((w00 * a + w10 * b) + w01 * c) + w11 * d);
-            }
-            out = make_float4(val[0], val[1], val[2], 0.0f);
+            double val[3];
+            txl_tap(C, P, atlas, x, y, val);
+            out = make_float4((float)val[0], (float)val[1], (float)val[2], 0.0f);
         }
     }
     f[i] = out;

@@ -1,4 +1,4 @@
-// What the texture stage's files (texture.hip, texture_smooth.hip, texture_level.hip, texture_outliers.hip) share; not part of the public ABI.
+// What the texture stage's files (texture.hip, texture_smooth.hip, texture_level.hip, texture_local.hip, texture_outliers.hip) share; not part of the public ABI.
 #pragma once
 #include <cmath>
 
@@ -111,6 +111,55 @@ __device__ __forceinline__ bool tx_corner_uv(const d3d_ortho_view_t& V, const Tx
         if (!(isfinite(u[k]) && isfinite(v[k]))) return false;
     }
     return true;
+}
+
+// A chart's row of the chart table [n_charts, 8] int32 (x0, y0, w, h, ox, oy, page, id) for the passes that work on the atlas
+// (texture_level.hip, texture_local.hip).
+struct TxlChart {
+    int x0, y0, w, h, ox, oy;
+    long long row0;   // the atlas row of the rect's first row
+    int slot;         // of the chart's view in the camera table, -1: the chart is skipped
+};
+
+// The chart's rect, checked as the fill checks it: false for a bad row, which is then never read or written out of bounds.
+__device__ __forceinline__ bool txl_rect(const int* __restrict__ table, long n_charts, int c, const long long* __restrict__ page_row,
+                                         int n_pages, int P, TxlChart* C) {
+    if (c < 0 || c >= n_charts) return false;
+    const int* T = table + 8l * c;
+    C->x0 = T[0], C->y0 = T[1], C->w = T[2], C->h = T[3], C->ox = T[4], C->oy = T[5];
+    const int page = T[6];
+    if (page < 0 || page >= n_pages) return false;
+    C->row0 = page_row[page] + C->oy;
+    return !(C->w < 1 || C->h < 1 || C->ox < 0 || C->ox + (long long)C->w > P || C->oy < 0 || C->row0 + C->h > page_row[page + 1]);
+}
+
+// The rect and the slot of the chart's view among the cameras (slot -1: a bad row or a missing view, the chart is skipped).
+__device__ __forceinline__ TxlChart txl_chart(const int* __restrict__ table, long n_charts, int c, const long long* __restrict__ page_row,
+                                              int n_pages, const d3d_ortho_view_t* __restrict__ cams, int n_cams, int P) {
+    TxlChart C;
+    C.slot = -1;
+    if (txl_rect(table, n_charts, c, page_row, n_pages, P, &C)) C.slot = tx_find(cams, n_cams, table[8l * c + 7]);
+    return C;
+}
+
+__device__ __forceinline__ double txl_clamp(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
+
+// The bilinear tap of the atlas at (x, y), atlas coordinates inside chart C, in fp64 and not rounded (texture.py "Sample"):
+// pad >= 1 keeps the taps inside the rect; a rect clamped at the image's border repeats its last texel.
+__device__ __forceinline__ void txl_tap(const TxlChart& C, int P, const unsigned* __restrict__ atlas, double x, double y, double* val) {
+    const double xf = floor(x), yf = floor(y);
+    const double tx = x - xf, ty = y - yf;
+    const long long ix0 = (long long)txl_clamp(xf, (double)C.ox, (double)(C.ox + C.w - 1));
+    const long long iy0 = (long long)txl_clamp(yf, (double)C.row0, (double)(C.row0 + C.h - 1));
+    const long long ix1 = min(ix0 + 1, (long long)(C.ox + C.w - 1)), iy1 = min(iy0 + 1, C.row0 + C.h - 1);
+    const unsigned c00 = atlas[iy0 * P + ix0], c10 = atlas[iy0 * P + ix1], c01 = atlas[iy1 * P + ix0], c11 = atlas[iy1 * P + ix1];
+    const double w00 = (1.0 - tx) * (1.0 - ty), w10 = tx * (1.0 - ty), w01 = (1.0 - tx) * ty, w11 = tx * ty;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const double a = (double)((c00 >> (8 * q)) & 255u), b = (double)((c10 >> (8 * q)) & 255u);
+        const double c = (double)((c01 >> (8 * q)) & 255u), d = (double)((c11 >> (8 * q)) & 255u);
+        val[q] = ((w00 * a + w10 * b) + w01 * c) + w11 * d;
+    }
 }
 
 }  // namespace d3d

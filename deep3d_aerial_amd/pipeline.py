@@ -99,7 +99,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     gather (gather_refine_views), it refines alone, so the file still does not depend on the number of ranks; timings gets
     mesh_refine_s (a part of mesh_s).
     texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad",
-    "level" (optional: None, or the seam levelling's settings), "smooth_views" and "outliers" (optional, likewise)}
+    "level" (optional: None, or the seam levelling's settings), "local" (the local seam levelling's), "smooth_views" and
+    "outliers" (optional, likewise)}
     (needs mesh; texture.settings_from_args): the mesh rank 0 wrote (after cleaning) textured from every rank's views and
     reference images (write_texture_of); rank 0 writes the textured PLY and its pages; timings gets texture_s."""
     if mesh is not None:
@@ -140,6 +141,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         _texture.check_settings(texture)
         if texture.get("level") is not None:
             _texture.check_level_settings(texture["level"])
+        if texture.get("local") is not None:
+            _texture.check_local_settings(texture["local"])
     if checker is None:
         checker = fuse.ConsistencyChecker(1.0, 0.01, 90.0, 0.2)   # Fuse_Depth_Map's defaults (fusion_3d_normal.py:56-57)
     n = len(dataset)
@@ -355,7 +358,8 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     Rank 0 broadcasts the mesh (sizes first); each rank selects over its own views (texture.select_faces); one all_reduce(MIN)
     of the keys; rank 0 lays out the charts, rects and pages (texture.layout) and broadcasts the chart table and page heights;
     each rank fills the charts of its own views; one all_reduce(SUM) of the pages as packed int32 texels (one rank contributes
-    per texel); with settings["level"] rank 0 levels the seams of the merged pages (texture.level_pages); then the empty
+    per texel); with settings["level"] rank 0 levels the seams of the merged pages (texture.level_pages), with settings["local"]
+    it then levels them locally (texture.local_pages); then the empty
     colour.  With settings["smooth_views"] the selection and its all_reduce give way to the candidate lists: each rank builds
     its own (texture.face_candidates), ranks 1.. hand theirs to rank 0 one at a time, merged as they arrive
     (sharding.fold_on with texture.merge_candidates: at most two lists are resident, 128 bytes per face each), and rank 0 smooths
@@ -371,6 +375,7 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     t0 = time.perf_counter()
     tol, vpb, P, pad = _tx.check_settings(settings)
     level = _tx.check_level_settings(settings["level"]) if settings.get("level") is not None else None
+    local = _tx.check_local_settings(settings["local"]) if settings.get("local") is not None else None
     smooth = _tx.check_smooth_settings(settings["smooth_views"]) if settings.get("smooth_views") is not None else None
     outliers = _tx.check_outlier_settings(settings["outliers"]) if settings.get("outliers") is not None else None
     v = f = None
@@ -418,8 +423,14 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     atlas = _tx.fill_pages(table_np, packing, ov, _tx.new_atlas(packing, device))
     if world_size > 1:
         sharding.all_reduce_raster(atlas, dist.ReduceOp.SUM)
+    keep = {}   # what the local step reuses of the global one
     if level is not None and rank == 0:   # the merged atlas, the mesh, keys, table and every camera are here: no new collective
-        res["level"] = _tx.level_pages(v, f, key, res["chart"], table_np, packing, cams, atlas, *level)
+        res["level"] = _tx.level_pages(v, f, key, res["chart"], table_np, packing, cams, atlas, *level,
+                                       keep=keep if local is not None else None)
+    if local is not None and rank == 0:   # right after the global step, on the same atlas: no new collective either
+        res["local"] = _tx.local_pages(v, f, key, res["chart"], table_np, packing, cams, atlas, *local, cover=keep.get("cover"),
+                                       pairs=keep.get("pairs"))
+    del keep
     _tx.finish_pages(atlas)
     if rank == 0:
         tc, tn = _tx.texcoords(v, f, key, res["chart"], table_np, packing, cams)

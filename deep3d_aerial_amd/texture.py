@@ -1,8 +1,8 @@
 """Texturing the surface mesh from the views.
 
 The reference runs OpenMVS's TextureMesh after ReconstructMesh and RefineMesh.  The rules below are this project's own and do
-not claim to match OpenMVS: the rejection of photo-inconsistent views, the smoothing of the view choice and global seam levelling
-(all three below) are off by default, local (Poisson) seam levelling is not offered.
+not claim to match OpenMVS: the rejection of photo-inconsistent views, the smoothing of the view choice and global and local seam
+levelling (all four below) are off by default.
 
 * Input.  vertices [n,3] fp32 and faces [m,3] int32 on the GPU (mesh.extract, mesh.clean, mesh.read_ply), every index in
   0 .. n - 1; views: ortho.OrthoView records (id, K, E, depth, image) with distinct ids.
@@ -62,6 +62,53 @@ different views agree along their common border.  It runs after the fill and the
 The dot products are folded from fixed slots in a fixed order, so two runs give the same bits; the levelled pages do not depend
 on view order or batching.
 
+Local seam levelling (local=..., --level_local): a correction per texel that takes each side of a seam to the
+mean of the two sides on the seam and fades out over a band of `radius` texels inside the chart.  It runs after the fill, the
+rank merge and the levelling above (when that is on) and before the empty colour; with it off nothing changes.  Everything after
+the colour taps is integer, so the levelled pages are the same bits for every run, view order, batching, rank split and solve path.
+* Unit.  Corrections are integers in units of 1/64 grey level.
+* Seam edge.  The levelling's above: an edge shared by exactly two faces of all faces, both with winners, in different charts.
+  Its record is (a, b, c1, c2) with a < b the ends by vertex index and c1 < c2 the charts, so nothing depends on the face order;
+  the seam edges are listed in increasing (a, b).  They come from the same (edge, face) pairs in a stable sort by edge that the
+  levelling's graph is built from (level_edge_pairs), sorted once when both levellings run.
+* Samples.  For a seam edge and each of its two charts the ends' atlas coordinates are X = (u - x0) + ox and
+  Y = ((v - y0) + oy) + page_row, u and v the texcoord pass's projection (fp64, no contraction).  L_c = max(|Xb - Xa|, |Yb - Ya|)
+  in chart c and S = ceil(max(L_c1, L_c2)) + 1 (no square root): consecutive samples lie at most one texel apart in either axis,
+  in both charts.  S = 1 exactly when the ends coincide in both charts; two distinct ends inside one texel give S = 2, two samples
+  of the same texel.  Sample k = 0 .. S - 1 lies at t = k / (S - 1) (fp64; t = 0 when S = 1) and P = Pa + t (Pb - Pa) per chart,
+  each coordinate as a + t (b - a).  The colour of a sample in a chart is the levelling's bilinear tap of the atlas at P, in fp64
+  and not rounded.  Per channel e = floor(32 (colour_c2 - colour_c1) + 0.5): half the step, in units.  Chart c1's texel
+  (floor(X + 0.5), floor(Y + 0.5)) gets the record +e, chart c2's texel gets -e.  Such a texel lies within d2 <= 0.5 of a face of
+  its chart, so it is covered; it is kept inside the rect (which it never leaves for a vertex the view sees).  An edge with a
+  chart whose view is missing or an end that does not project in front of the view has no samples.
+* Records.  Sample j of all (seam edges in their order, then k) writes record 2 j for chart c1 and 2 j + 1 for chart c2; the
+  records are put in a stable sort by texel (row * page_size + column).  Only the sums below depend on them, so the order within
+  a texel never shows in a page.
+* Seam texel.  A texel with at least one record.  D = (2 sum(e) + n) // (2 n) per channel (floor division; the sum of its n records
+  in int64): their mean, rounded half up.  A sort and a fold over runs; no float atomics, and no integer ones either.
+* Domain and band.  A chart's domain is the texels of its rect that the coverage gives a face (d2 <= 2).  dist is the breadth-first
+  distance over 4-neighbours inside the rect and the domain from the seam texels (dist 0), found in `radius` rounds; a texel is
+  active when 1 <= dist <= radius.  A domain texel further away or not reachable keeps dist 255 and c = 0; a neighbour outside
+  the rect or the domain is left out everywhere.  Rects of different charts touch in the atlas: a chart never reads another's texels.
+* Solve.  c = D on seam texels and 0 elsewhere at the start.  A sweep updates the active texels with (X + Y) even, then those with
+  (X + Y) odd, in place (X the atlas column, Y the atlas row, page_row included): c = (2 s + n) // (2 n) per channel, s the sum over
+  the texel's in-domain 4-neighbours (active or not) and n their count; an active texel has n >= 1.  Texels of one parity are never
+  neighbours, so a half-sweep has no order dependence.  |c| never exceeds the largest |D| (8160), so int16 holds it.  The solve
+  stops after `iterations` sweeps or after the first sweep that changes nothing; sweeps past a fixed point change nothing, so the
+  early stop never shows in the result, nor does the cadence (16 sweeps) at which the host looks at the counts.
+* State.  One int64 per texel of the atlas, as the coverage: c of R, G, B as int16 in bits 0 .. 15, 16 .. 31, 32 .. 47; dist in bits
+  48 .. 55; bit 56 "in the domain"; bit 57 "seam texel" (local_fields takes it apart).
+* Paths.  A chart whose rect has at most lds_texels texels (default: 160 KiB / 8 bytes = 20480, a capacity and no tuning result)
+  and whose padded image with its flags, (h + 2) (w + 1) + 4 words, fits into the 160 KiB is solved by one workgroup in LDS, band
+  and sweeps; the launches are three, by the LDS a chart needs (16, 64 and 160 KiB per workgroup), so that small charts share a
+  CU.  Every other chart runs as (chart, band of 8 rows) work items, one launch per dilation round and per half-sweep.  Both give
+  the same bits.  "sweeps" is the number of sweeps that changed something, the largest over the charts, on either path;
+  "converged" says that a sweep that changed nothing was reached: sweeps < iterations.
+* Apply.  Every domain texel with dist <= radius gets channel = clamp(channel + ((c + 32) >> 6), 0, 255); alpha is unchanged.
+* Settings.  radius 1 .. 254, default 16; iterations 1 .. 65535, default 512: settings, not measurements.  On a straight seam
+  with radius 16 the iteration reaches a true fixed point in 161 .. 267 sweeps for |D| of 20 .. 127.5 levels, at most 0.5625 levels
+  from the ramp D (1 - dist / 17) and exactly 0 past the radius (tests/test_texture_local.py).
+
 Smoothing the view choice (smooth_views=..., --smooth_views W): each face may give up a bounded share of its
 best projected area to agree with the faces around it, so that charts are fewer and larger.  It replaces the Choice above;
 with it off nothing changes.
@@ -119,13 +166,15 @@ changes.
 Faces are never reordered or renumbered: a shuffled face list gives the same key per face (without smoothing).  Chart labels, and so the packing,
 follow the face order.  The hot passes are HIP kernels (csrc/texture.hip): select, charts (hooking and pointer jumping over
 (edge, face) pairs that torch.sort orders), rects, fill and texcoords; the smoothing's kernels are in csrc/texture_smooth.hip,
-the levelling's in csrc/texture_level.hip, the outlier rejection's in csrc/texture_outliers.hip.  No float atomics; the integer
-atomics are min / max, the count of a smoothing round's commits and the four counters of the outlier vote.
+the levelling's in csrc/texture_level.hip, the local levelling's in csrc/texture_local.hip, the outlier rejection's in
+csrc/texture_outliers.hip.  No float atomics; the integer atomics are min / max, the count of a smoothing round's commits, the
+four counters of the outlier vote and the count of texels a global sweep of the local levelling changed.
 
     python -m deep3d_aerial_amd.texture --mesh IN.ply --mvs MVS_FOLDER --out OUT.ply [--image_root DIR]
         [--depth_tolerance 0.01] [--views_per_batch N] [--page_size 8192] [--pad 2] [--outlier_threshold T]
         [--smooth_views W [--smooth_max_loss 0.25] [--smooth_rounds 64]]
         [--level [--level_smooth 0.1] [--level_anchor 1e-3] [--level_tolerance 1e-4] [--level_iterations 500]]
+        [--level_local [--level_local_radius 16] [--level_local_iterations 512]]
 """
 import argparse
 import ctypes
@@ -147,6 +196,14 @@ DEFAULT_LEVEL_SMOOTH = 0.1
 DEFAULT_LEVEL_ANCHOR = 1e-3
 DEFAULT_LEVEL_TOLERANCE = 1e-4
 DEFAULT_LEVEL_ITERATIONS = 500
+DEFAULT_LOCAL_RADIUS = 16   # settings, not measurements
+DEFAULT_LOCAL_ITERATIONS = 512
+MAX_LOCAL_RADIUS = 254
+MAX_LOCAL_ITERATIONS = 65535
+LOCAL_UNIT = 64   # a correction of the local levelling is an integer in units of 1 / 64 grey level
+LOCAL_WORD_BYTES = 8   # of its state per texel (csrc/texture_local.hip)
+LOCAL_LDS_CLASSES = (16 << 10, 64 << 10, 160 << 10)   # LDS bytes per workgroup of the three launches of the chart-in-LDS solve
+LOCAL_FAR = 255   # the distance of a texel the band did not reach
 CANDIDATES = 16   # keys per face of the candidate lists (csrc/texture_shared.h TX_CANDIDATES)
 DEFAULT_SMOOTH_MAX_LOSS = 0.25   # settings, not measurements
 DEFAULT_SMOOTH_ROUNDS = 64
@@ -437,8 +494,8 @@ def _live(keys):
     return keys[keys != _NONE]
 
 
-def level_graph(faces, chart, n_vertices, smooth=DEFAULT_LEVEL_SMOOTH):
-    """The nodes, seam pairs, smoothness edges and CSR (LevelGraph) of the charts of `faces`."""
+def _faces_and_chart(faces, chart, n_vertices):
+    """(faces, chart, m, n, device) checked for the passes over the (edge, face) pairs."""
     if not (isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3):
         raise ValueError("faces must be [m,3] int32")
     if faces.device.type != "cuda":
@@ -449,19 +506,33 @@ def level_graph(faces, chart, n_vertices, smooth=DEFAULT_LEVEL_SMOOTH):
         raise ValueError("chart must be an int32 tensor of shape (%d,) on %s" % (m, dev))
     if 3 * m >= 1 << 31:
         raise ValueError("%d faces: 3 m < 2^31" % m)
-    chart = chart.contiguous()
-    lib = _lib.load()
+    return faces, chart.contiguous(), m, n, dev
+
+
+def level_edge_pairs(faces, chart, n_vertices):
+    """What both levellings start from: (incidence [3 m] int64 -- the node key of every corner, INT64_MAX without a chart --,
+    edge_sorted [n_pairs] int64, face_sorted [n_pairs] int32 -- the (edge, face) pairs of EVERY face in a stable sort by edge)."""
+    faces, chart, m, n, dev = _faces_and_chart(faces, chart, n_vertices)
     inc = torch.empty((3 * m,), dtype=torch.int64, device=dev)
     edge = torch.empty((3 * m,), dtype=torch.int64, device=dev)
-    _lib.check(lib.d3d_texture_level_incidence(_ptr(faces), m, n, _ptr(chart), _ptr(inc), _ptr(edge), _stream()),
+    _lib.check(_lib.load().d3d_texture_level_incidence(_ptr(faces), m, n, _ptr(chart), _ptr(inc), _ptr(edge), _stream()),
                "d3d_texture_level_incidence")
-    nodes = torch.unique(_live(inc))
     live = torch.nonzero(edge != _NONE).flatten()
     order = torch.argsort(edge[live], stable=True)
     edge_sorted = edge[live][order].contiguous()
     face_sorted = torch.div(live[order], 3, rounding_mode="floor").to(torch.int32).contiguous()
+    return inc, edge_sorted, face_sorted
+
+
+def level_graph(faces, chart, n_vertices, smooth=DEFAULT_LEVEL_SMOOTH, pairs=None):
+    """The nodes, seam pairs, smoothness edges and CSR (LevelGraph) of the charts of `faces`.  pairs: level_edge_pairs' result for
+    the same faces and charts, when the caller has it."""
+    faces, chart, m, n, dev = _faces_and_chart(faces, chart, n_vertices)
+    lib = _lib.load()
+    inc, edge_sorted, face_sorted = pairs if pairs is not None else level_edge_pairs(faces, chart, n)
+    nodes = torch.unique(_live(inc))
     n_pairs, N = int(edge_sorted.shape[0]), int(nodes.shape[0])
-    del inc, edge, live, order
+    del inc
     face_nodes = torch.empty((m, 3), dtype=torch.int32, device=dev)
     seam = torch.empty((2 * n_pairs,), dtype=torch.int64, device=dev)
     smooth_keys = torch.empty((3 * m,), dtype=torch.int64, device=dev)
@@ -588,22 +659,245 @@ def level_apply(vertices, faces, chart, graph, g, cover, table, packing, cameras
 
 
 def level_pages(vertices, faces, key, chart, table, packing, cameras, atlas, smooth=DEFAULT_LEVEL_SMOOTH, anchor=DEFAULT_LEVEL_ANCHOR,
-                tolerance=DEFAULT_LEVEL_TOLERANCE, iterations=DEFAULT_LEVEL_ITERATIONS):
+                tolerance=DEFAULT_LEVEL_TOLERANCE, iterations=DEFAULT_LEVEL_ITERATIONS, keep=None):
     """Levels the seams of the filled (and merged) atlas in place, before finish_pages.  cameras: every winning view.  Returns
-    {"nodes", "seams", "iterations", "converged"}."""
+    {"nodes", "seams", "iterations", "converged"}.  keep: None, or a dict that receives what the local levelling can reuse:
+    "pairs" (level_edge_pairs) and, when it was computed, "cover" (level_coverage)."""
     vertices, faces, n, m = _mesh_arrays(vertices, faces)
     _check_key(key, m, vertices.device)
     _check_atlas(atlas, packing, vertices.device)
     smooth, anchor, tolerance, iterations = check_level_settings({"smooth": smooth, "anchor": anchor, "tolerance": tolerance,
                                                                   "iterations": iterations})
-    graph = level_graph(faces, chart, n, smooth)
+    pairs = level_edge_pairs(faces, chart, n)
+    if keep is not None:
+        keep["pairs"] = pairs
+    graph = level_graph(faces, chart, n, smooth, pairs)
     info = {"nodes": graph.n_nodes, "seams": int(graph.seams.shape[0]), "iterations": 0, "converged": True}
     if not info["seams"]:   # b = 0: g = 0, every texel keeps its colour
         return info
     _, b = level_samples(vertices, graph, table, packing, cameras, atlas)
     g, info["iterations"], info["converged"] = level_solve(graph, b, anchor, tolerance, iterations)
     cover = level_coverage(vertices, faces, chart, table, packing, cameras)
+    if keep is not None:
+        keep["cover"] = cover
     level_apply(vertices, faces, chart, graph, g, cover, table, packing, cameras, atlas)
+    return info
+
+
+# ----------------------------------------------------------------------------------------
+# local seam levelling
+# ----------------------------------------------------------------------------------------
+def check_local_settings(local):
+    """The local settings dict checked: (radius, iterations)."""
+    unknown = set(local) - {"radius", "iterations"}
+    if unknown:
+        raise ValueError("local: unknown settings %s" % sorted(unknown))
+    radius = local.get("radius", DEFAULT_LOCAL_RADIUS)
+    it = local.get("iterations", DEFAULT_LOCAL_ITERATIONS)
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= MAX_LOCAL_RADIUS:
+        raise ValueError("level_local_radius %r must be an integer in 1 .. %d" % (radius, MAX_LOCAL_RADIUS))
+    if isinstance(it, bool) or int(it) != it or not 1 <= int(it) <= MAX_LOCAL_ITERATIONS:
+        raise ValueError("level_local_iterations %r must be an integer in 1 .. %d" % (it, MAX_LOCAL_ITERATIONS))
+    return int(radius), int(it)
+
+
+def local_seams(faces, chart, n_vertices, pairs=None):
+    """seams [n_seams, 4] int32 (a, b, c1, c2): the seam edges in increasing (a, b) order, a < b the ends, c1 < c2 the charts.
+    pairs: level_edge_pairs' result, when the caller has it."""
+    faces, chart, m, n, dev = _faces_and_chart(faces, chart, n_vertices)
+    _, edge_sorted, face_sorted = pairs if pairs is not None else level_edge_pairs(faces, chart, n)
+    n_pairs = int(edge_sorted.shape[0])
+    seam = torch.empty((n_pairs, 4), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().d3d_texture_local_seams(_ptr(edge_sorted), _ptr(face_sorted), n_pairs, _ptr(chart), m, n, _ptr(seam), _stream()),
+               "d3d_texture_local_seams")
+    return seam[seam[:, 0] >= 0].contiguous()
+
+
+def _check_seams(seams, device):
+    if not (isinstance(seams, torch.Tensor) and seams.dtype == torch.int32 and seams.dim() == 2 and seams.shape[1] == 4):
+        raise ValueError("seams must be an int32 tensor of shape (n_seams, 4)")
+    if seams.device != device:
+        raise RuntimeError("seams are on %s, the mesh on %s (no CPU fallback)" % (seams.device, device))
+    return seams.contiguous()
+
+
+def local_samples(vertices, seams, table, packing, cameras, atlas):
+    """(texel [R] int64, rec [R, 3] int32): the records of every sample of every seam edge, in a stable sort by texel (the index
+    row * page_size + column in the atlas) of the order (seam edge, sample, chart c1 then c2)."""
+    if not (isinstance(vertices, torch.Tensor) and vertices.dtype == torch.float32 and vertices.dim() == 2 and vertices.shape[1] == 3):
+        raise ValueError("vertices must be [n,3] float32")
+    if vertices.device.type != "cuda":
+        raise RuntimeError("vertices are on %s (no CPU fallback)" % vertices.device)
+    vertices, dev = vertices.contiguous(), vertices.device
+    _check_atlas(atlas, packing, dev)
+    seams = _check_seams(seams, dev)
+    ns, n = int(seams.shape[0]), int(vertices.shape[0])
+    t, n_charts, pr, recs, nc = _level_tables(table, packing, cameras, dev)
+    lib = _lib.load()
+    count = torch.zeros((ns,), dtype=torch.int32, device=dev)
+    _lib.check(lib.d3d_texture_local_count(_ptr(vertices), n, _ptr(seams), ns, _ptr(t), n_charts, _ptr(pr), packing.n_pages, _ptr(recs),
+                                           nc, packing.page_size, _ptr(count), _stream()), "d3d_texture_local_count")
+    scan = torch.zeros((ns + 1,), dtype=torch.int64, device=dev)
+    scan[1:] = torch.cumsum(count, 0, dtype=torch.int64)
+    total = int(scan[-1])
+    if 2 * total >= 1 << 31:
+        raise ValueError("%d seam samples: at most 2^30 - 1" % total)
+    texel = torch.empty((2 * total,), dtype=torch.int64, device=dev)
+    rec = torch.empty((2 * total, 3), dtype=torch.int32, device=dev)
+    _lib.check(lib.d3d_texture_local_samples(_ptr(vertices), n, _ptr(seams), ns, _ptr(scan), total, _ptr(t), n_charts, _ptr(pr),
+                                             packing.n_pages, _ptr(recs), nc, packing.page_size, _ptr(atlas), _ptr(texel), _ptr(rec),
+                                             _stream()), "d3d_texture_local_samples")
+    texel, order = torch.sort(texel, stable=True)
+    return texel.contiguous(), rec[order].contiguous()
+
+
+def _check_cover(cover, packing, device, name="cover"):
+    shape = (int(packing.page_row[-1]), packing.page_size)
+    if not (isinstance(cover, torch.Tensor) and cover.dtype == torch.int64 and tuple(cover.shape) == shape and cover.is_contiguous()):
+        raise ValueError("%s must be a contiguous int64 tensor of shape (%d, %d)" % ((name,) + shape))
+    if cover.device.type != "cuda" or cover.device != device:
+        raise RuntimeError("%s is on %s (no CPU fallback)" % (name, cover.device))
+
+
+def local_fold(texel, rec, cover, packing):
+    """state [atlas rows, page_size] int64 (module docstring "State"): the domain of `cover` and the seam texels with their D."""
+    dev = cover.device if isinstance(cover, torch.Tensor) else None
+    _check_cover(cover, packing, dev)
+    R = int(texel.shape[0])
+    if not (texel.dtype == torch.int64 and texel.is_contiguous() and rec.dtype == torch.int32 and tuple(rec.shape) == (R, 3) and
+            rec.is_contiguous() and texel.device == dev and rec.device == dev):
+        raise ValueError("texel [R] int64 and rec [R, 3] int32 must be contiguous and on %s" % dev)
+    state = torch.empty_like(cover)
+    _lib.check(_lib.load().d3d_texture_local_fold(_ptr(texel), _ptr(rec), R, _ptr(cover), int(cover.numel()), _ptr(state), _stream()),
+               "d3d_texture_local_fold")
+    return state
+
+
+def local_fields(state):
+    """The state's fields: (c [rows, P, 3] int16, dist [rows, P] uint8, domain [rows, P] bool, seam [rows, P] bool)."""
+    c = torch.stack([((state >> s) & 0xffff).to(torch.int16) for s in (0, 16, 32)], -1)
+    return c, ((state >> 48) & 255).to(torch.uint8), ((state >> 56) & 1).bool(), ((state >> 57) & 1).bool()
+
+
+def local_lds_texels():
+    """The default of lds_texels: the texels whose state fills the 160 KiB of LDS of a CU.  A capacity, not a tuning result."""
+    return int(_lib.load().d3d_texture_local_lds_words())
+
+
+def _local_split(table, lds_texels):
+    """(charts of the LDS path, one int array per LDS class; work [n, 2] of the global path's (chart, band) items; every chart's
+    work).  A chart takes the LDS path when its rect has at most lds_texels texels and its padded image with the flags, (h + 2) (w + 1) + 4
+    words, fits into the LDS."""
+    tb = np.ascontiguousarray(table, np.int32).reshape(-1, 8)
+    w, h = tb[:, 2].astype(np.int64), tb[:, 3].astype(np.int64)
+    need = ((h + 2) * (w + 1) + 4) * LOCAL_WORD_BYTES
+    cap = local_lds_texels()
+    limit = cap if lds_texels is None else int(lds_texels)
+    if limit < 0:
+        raise ValueError("lds_texels %r must be >= 0" % (lds_texels,))
+    in_lds = (w * h <= limit) & (need <= cap * LOCAL_WORD_BYTES)
+    classes, lo = [], 0
+    for hi in LOCAL_LDS_CLASSES:
+        classes.append(np.flatnonzero(in_lds & (need > lo) & (need <= hi)).astype(np.int32))
+        lo = hi
+
+    def work(mask):
+        nb = np.where(mask, (h + BAND - 1) // BAND, 0)
+        return np.ascontiguousarray(np.stack([np.repeat(np.arange(tb.shape[0]), nb),
+                                              np.arange(int(nb.sum())) - np.repeat(np.cumsum(nb) - nb, nb)], 1), np.int32)
+
+    return classes, work(~in_lds), work(np.ones(tb.shape[0], bool))
+
+
+def _local_tables(table, packing, device):
+    table = np.ascontiguousarray(table, np.int32).reshape(-1, 8)
+    t = torch.from_numpy(table if table.shape[0] else np.zeros((1, 8), np.int32)).to(device)
+    return t, int(table.shape[0]), torch.from_numpy(packing.page_row).to(device)
+
+
+def _local_run(state, table, packing, radius, iterations, lds_texels):
+    """The band (iterations = 0) or the band and the sweeps on both paths, in place: (sweeps, charts_lds, charts_global)."""
+    _check_cover(state, packing, state.device if isinstance(state, torch.Tensor) else None, "state")
+    dev = state.device
+    lib = _lib.load()
+    classes, work, _ = _local_split(table, lds_texels)
+    t, n_charts, pr = _local_tables(table, packing, dev)
+    sweeps = torch.zeros((max(n_charts, 1),), dtype=torch.int32, device=dev)
+    for charts_of, lds_bytes in zip(classes, LOCAL_LDS_CLASSES):
+        if len(charts_of):
+            lst = torch.from_numpy(charts_of).to(dev)
+            _lib.check(lib.d3d_texture_local_chart(_ptr(lst), len(charts_of), _ptr(t), n_charts, _ptr(pr), packing.n_pages,
+                                                   packing.page_size, _ptr(state), radius, iterations, lds_bytes, _ptr(sweeps), _stream()),
+                       "d3d_texture_local_chart")
+    run = ctypes.c_int(0)
+    if work.shape[0]:
+        w = torch.from_numpy(work).to(dev)
+        _lib.check(lib.d3d_texture_local_band(_ptr(w), int(w.shape[0]), _ptr(t), n_charts, _ptr(pr), packing.n_pages, packing.page_size,
+                                              _ptr(state), radius, _stream()), "d3d_texture_local_band")
+        if iterations:
+            changed = torch.empty((iterations,), dtype=torch.int32, device=dev)
+            _lib.check(lib.d3d_texture_local_sweeps(_ptr(w), int(w.shape[0]), _ptr(t), n_charts, _ptr(pr), packing.n_pages,
+                                                    packing.page_size, _ptr(state), radius, iterations, _ptr(changed), ctypes.byref(run),
+                                                    _stream()), "d3d_texture_local_sweeps")
+    n_lds = int(sum(len(c) for c in classes))
+    return max(int(sweeps.max()), run.value), n_lds, n_charts - n_lds
+
+
+def local_band(state, table, packing, radius=DEFAULT_LOCAL_RADIUS, lds_texels=None):
+    """The distances of the state, in place (the solve computes them itself; this is the band alone).  Returns state."""
+    radius, _ = check_local_settings({"radius": radius})
+    _local_run(state, table, packing, radius, 0, lds_texels)
+    return state
+
+
+def local_solve(state, table, packing, radius=DEFAULT_LOCAL_RADIUS, iterations=DEFAULT_LOCAL_ITERATIONS, lds_texels=None):
+    """The band and the relaxation on local_fold's state, in place: (state, {"sweeps" -- those that changed something, the largest
+    over the charts --, "converged" -- a sweep that changed nothing was reached --, "charts_lds", "charts_global"}).  lds_texels:
+    charts with more texels than this take the global path (default: what fits into the LDS; 0: every chart)."""
+    radius, iterations = check_local_settings({"radius": radius, "iterations": iterations})
+    sweeps, n_lds, n_global = _local_run(state, table, packing, radius, iterations, lds_texels)
+    return state, {"sweeps": sweeps, "converged": sweeps < iterations, "charts_lds": n_lds, "charts_global": n_global}
+
+
+def local_apply(state, table, packing, atlas, radius=DEFAULT_LOCAL_RADIUS):
+    """Adds the correction to every domain texel within `radius` of a seam, in place.  Returns atlas."""
+    radius, _ = check_local_settings({"radius": radius})
+    _check_cover(state, packing, state.device if isinstance(state, torch.Tensor) else None, "state")
+    _check_atlas(atlas, packing, state.device)
+    _, _, work = _local_split(table, None)
+    if not work.shape[0]:
+        return atlas
+    t, n_charts, pr = _local_tables(table, packing, state.device)
+    w = torch.from_numpy(work).to(state.device)
+    _lib.check(_lib.load().d3d_texture_local_apply(_ptr(w), int(w.shape[0]), _ptr(t), n_charts, _ptr(pr), packing.n_pages,
+                                                   packing.page_size, _ptr(state), radius, _ptr(atlas), _stream()),
+               "d3d_texture_local_apply")
+    return atlas
+
+
+def local_pages(vertices, faces, key, chart, table, packing, cameras, atlas, radius=DEFAULT_LOCAL_RADIUS,
+                iterations=DEFAULT_LOCAL_ITERATIONS, cover=None, pairs=None, lds_texels=None):
+    """Levels the seams of the filled (and merged, and globally levelled) atlas locally, in place, before finish_pages.  cameras:
+    every winning view.  cover: level_coverage's result when the global levelling computed it; pairs: level_edge_pairs' likewise.
+    Returns {"seam_edges", "seam_texels", "active", "sweeps", "converged"}."""
+    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    _check_key(key, m, vertices.device)
+    _check_atlas(atlas, packing, vertices.device)
+    chart = _check_chart(chart, m, vertices.device)
+    radius, iterations = check_local_settings({"radius": radius, "iterations": iterations})
+    seams = local_seams(faces, chart, n, pairs)
+    info = {"seam_edges": int(seams.shape[0]), "seam_texels": 0, "active": 0, "sweeps": 0, "converged": True}
+    if not info["seam_edges"]:   # no record: c = 0 everywhere, every texel keeps its colour
+        return info
+    texel, rec = local_samples(vertices, seams, table, packing, cameras, atlas)
+    if cover is None:
+        cover = level_coverage(vertices, faces, chart, table, packing, cameras)
+    state = local_fold(texel, rec, cover, packing)
+    state, solved = local_solve(state, table, packing, radius, iterations, lds_texels)
+    _, dist, domain, seam = local_fields(state)
+    info.update({"seam_texels": int(seam.sum()), "active": int((domain & (dist >= 1) & (dist <= radius)).sum()),
+                 "sweeps": solved["sweeps"], "converged": solved["converged"]})
+    local_apply(state, table, packing, atlas, radius)
     return info
 
 
@@ -828,7 +1122,7 @@ def smooth_summary(cand, label, commits, rounds, charts_before):
 
 
 def texture_mesh(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, views_per_batch=None, page_size=DEFAULT_PAGE,
-                 pad=DEFAULT_PAD, empty_color=EMPTY_COLOR, level=None, smooth_views=None, outliers=None):
+                 pad=DEFAULT_PAD, empty_color=EMPTY_COLOR, level=None, smooth_views=None, outliers=None, local=None):
     """Every pass on one process: {"key", "chart", "labels", "rects", "packing", "table", "pages" (host RGB8 arrays),
     "texcoord", "texnumber"}.  level: None, or the seam levelling's settings {"smooth", "anchor", "tolerance", "iterations"}
     (check_level_settings; {} for the defaults); the result then has "level" (level_pages' dict).  smooth_views: None, or the
@@ -837,11 +1131,15 @@ def texture_mesh(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, view
     (smooth_summary's dict).  outliers: None, or the settings of the rejection of outlier views {"threshold"}
     (check_outlier_settings): the candidate lists are then filtered (face_colors, reject_outliers) before the choice -- the
     smoothing when smooth_views is given, else column 0 --, and the result has "cand" (the filtered lists), "rejected" and
-    "outliers" (outlier_summary's dict)."""
+    "outliers" (outlier_summary's dict).  local: None, or the local seam levelling's settings {"radius", "iterations"}
+    (check_local_settings; {} for the defaults): it runs after the global levelling when that is on, and the result then has
+    "local" (local_pages' dict)."""
     views = _check_views(views)
     check_page_size(page_size, views)
     if level is not None:
         smooth, anchor, tolerance, iterations = check_level_settings(level)
+    if local is not None:
+        local_radius, local_iterations = check_local_settings(local)
     res = {}
     if outliers is not None:
         threshold = check_outlier_settings(outliers)
@@ -868,8 +1166,14 @@ def texture_mesh(vertices, faces, views, depth_tolerance=DEFAULT_TOLERANCE, view
         key = select_faces(vertices, faces, views, depth_tolerance, views_per_batch)
     chart, labels, rects, packing, table = layout(vertices, faces, key, views, page_size, pad)
     atlas = fill_pages(table, packing, views, new_atlas(packing, vertices.device))
+    keep = {}
     if level is not None:
-        res["level"] = level_pages(vertices, faces, key, chart, table, packing, views, atlas, smooth, anchor, tolerance, iterations)
+        res["level"] = level_pages(vertices, faces, key, chart, table, packing, views, atlas, smooth, anchor, tolerance, iterations,
+                                   keep=keep if local is not None else None)
+    if local is not None:
+        res["local"] = local_pages(vertices, faces, key, chart, table, packing, views, atlas, local_radius, local_iterations,
+                                   cover=keep.get("cover"), pairs=keep.get("pairs"))
+    del keep
     atlas = finish_pages(atlas, empty_color)
     tc, tn = texcoords(vertices, faces, key, chart, table, packing, views)
     res.update({"key": key, "chart": chart, "labels": labels, "rects": rects, "packing": packing, "table": table,
@@ -981,6 +1285,13 @@ def add_arguments(ap, prefix=""):
     ap.add_argument("--%slevel_tolerance" % prefix, type=float, default=DEFAULT_LEVEL_TOLERANCE,
                     help="the solve stops at |r| <= this * |b| (in (0, 1))")
     ap.add_argument("--%slevel_iterations" % prefix, type=int, default=DEFAULT_LEVEL_ITERATIONS, help="at most this many iterations (>= 1)")
+    ap.add_argument("--%slevel_local" % prefix, action="store_true",
+                    help="level the seams locally: a correction that fades out over a band of texels on both sides of every seam "
+                         "(after --%slevel when both are given)" % prefix)
+    ap.add_argument("--%slevel_local_radius" % prefix, type=int, default=DEFAULT_LOCAL_RADIUS,
+                    help="the band's width in texels on each side of a seam (1 .. 254)")
+    ap.add_argument("--%slevel_local_iterations" % prefix, type=int, default=DEFAULT_LOCAL_ITERATIONS,
+                    help="at most this many sweeps of the relaxation (1 .. 65535)")
 
 
 def check_settings(settings):
@@ -1001,6 +1312,8 @@ def settings_from_args(a, path, prefix=""):
     g = lambda k: getattr(a, prefix + k)
     level = {"smooth": g("level_smooth"), "anchor": g("level_anchor"), "tolerance": g("level_tolerance"), "iterations": g("level_iterations")}
     check_level_settings(level)   # the numbers are checked whether or not --level is given
+    local = {"radius": g("level_local_radius"), "iterations": g("level_local_iterations")}
+    check_local_settings(local)   # likewise
     w = g("smooth_views")
     smooth = {"weight": 1.0 if w is None else w, "max_loss": g("smooth_max_loss"), "rounds": g("smooth_rounds")}
     check_smooth_settings(smooth)   # likewise
@@ -1011,14 +1324,14 @@ def settings_from_args(a, path, prefix=""):
         check_outlier_settings(outliers)
     return {"path": path, "depth_tolerance": g("depth_tolerance"), "views_per_batch": g("views_per_batch"), "page_size": g("page_size"),
             "pad": g("pad"), "level": level if g("level") else None, "smooth_views": smooth if w is not None else None,
-            "outliers": outliers}
+            "outliers": outliers, "local": local if g("level_local") else None}
 
 
 def build_and_write(vertices, faces, views, settings):
     """texture_mesh with the settings dict, written to settings["path"]: the result dict."""
     tol, vpb, P, pad = check_settings(settings)
     res = texture_mesh(vertices, faces, views, tol, vpb, P, pad, level=settings.get("level"), smooth_views=settings.get("smooth_views"),
-                       outliers=settings.get("outliers"))
+                       outliers=settings.get("outliers"), local=settings.get("local"))
     write_textured_ply(settings["path"], vertices, faces, res["texcoord"], res["texnumber"], res["pages"])
     return res
 
@@ -1055,6 +1368,10 @@ def main(argv=None):
     if "level" in res:
         print("levelled %d seam pairs over %d nodes in %d iterations%s" % (res["level"]["seams"], res["level"]["nodes"], res["level"]["iterations"],
                                                                           "" if res["level"]["converged"] else " (not converged)"))
+    if "local" in res:
+        print("levelled locally: %d seam edges, %d seam texels, %d texels in the band, %d sweeps%s" %
+              (res["local"]["seam_edges"], res["local"]["seam_texels"], res["local"]["active"], res["local"]["sweeps"],
+               "" if res["local"]["converged"] else " (not converged)"))
     return a.out
 
 

@@ -1294,6 +1294,74 @@ int d3d_texture_level_apply(const int* work, long long n_work, const float* vert
                             int page_width, const long long* cover, unsigned int* atlas, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.22 -- levelling the texture's seams locally: an integer relaxation over the texels within `radius` of a seam, every
+ * chart an independent problem (deep3d_aerial_amd/texture.py states the rules in full; they are this project's).  Corrections are
+ * integers in units of 1/64 grey level.  state [atlas rows, page_width] int64, one word per texel: the corrections of R, G and B
+ * as int16 in bits 0 .. 15, 16 .. 31 and 32 .. 47, the distance from the seam texels in bits 48 .. 55 (255: not reached), bit 56
+ * "in the domain" (a face of the rect's chart covers the texel), bit 57 "seam texel".  table, page_row, cams and atlas are
+ * d3d_texture_fill's, cover is d3d_texture_level_cover's, work [n_work, 2] int32 lists (chart, band of 8 rows) as
+ * d3d_texture_fill's.  Every pointer is DEVICE memory except d3d_texture_local_sweeps' `sweeps_run`.  No float atomics; the one
+ * integer atomic counts a sweep's changed texels.  radius is 1 .. 254.
+ */
+/* The words of state that fit into the LDS of a CU: 160 KiB / 8. */
+long long d3d_texture_local_lds_words(void);
+
+/* d3d_texture_local_seams: edge_sorted / face_sorted [n_pairs] are d3d_texture_level_pairs'.  seam [n_pairs, 4] int32: the first
+ *   pair of a run of exactly two pairs whose faces have different charts (both >= 0) writes (a, b, c1, c2), a < b the edge's ends
+ *   and c1 < c2 the charts; every other row gets -1. */
+int d3d_texture_local_seams(const long long* edge_sorted, const int* face_sorted, long long n_pairs, const int* chart, long long n_faces,
+                            long long n_vertices, int* seam, d3d_stream_t stream);
+
+/* d3d_texture_local_count: seams [n_seams, 4] int32 (a, b, c1, c2).  count[i] = S = ceil(max(L_c1, L_c2)) + 1 with
+ *   L_c = max(|Xb - Xa|, |Yb - Ya|) of the ends in chart c's atlas coordinates (d3d_texture_level_samples' x and y, fp64); 0 for an
+ *   edge that is skipped (a bad record or chart, a missing view, an end that does not project). */
+int d3d_texture_local_count(const float* vertices, long long n_vertices, const int* seams, long long n_seams, const int* table,
+                            long long n_charts, const long long* page_row, int n_pages, const d3d_ortho_view_t* cams, int n_cams,
+                            int page_width, int* count, d3d_stream_t stream);
+
+/* d3d_texture_local_samples: scan [n_seams + 1] int64 is the exclusive scan of the counts, n_samples its last entry.  Sample k of
+ *   edge i lies at t = k / (S - 1) (0 when S = 1), P = Pa + t (Pb - Pa) per chart; its colour in a chart is
+ *   d3d_texture_level_samples' tap, not rounded; e = floor(32 (colour_c2 - colour_c1) + 0.5) per channel.  Sample j = scan[i] + k
+ *   writes texel[2 j] = the index (row * page_width + column) of chart c1's texel (floor(X + 0.5), floor(Y + 0.5)), kept inside
+ *   the rect, with rec[2 j] = +e (3 int32), and texel[2 j + 1], rec[2 j + 1] = chart c2's texel with -e.  texel [2 n_samples]
+ *   int64, rec [2 n_samples, 3] int32. */
+int d3d_texture_local_samples(const float* vertices, long long n_vertices, const int* seams, long long n_seams, const long long* scan,
+                              long long n_samples, const int* table, long long n_charts, const long long* page_row, int n_pages,
+                              const d3d_ortho_view_t* cams, int n_cams, int page_width, const unsigned int* atlas, long long* texel,
+                              int* rec, d3d_stream_t stream);
+
+/* d3d_texture_local_fold: WRITES state [n_texels]: "in the domain" where cover is not INT64_MAX, distance 255, corrections 0; then
+ *   texel / rec [n_records] sorted by texel: a run of n records of sum s (int64) makes its texel a seam texel of distance 0 with
+ *   D = (2 s + n) // (2 n) per channel (floor division).  A texel outside 0 .. n_texels - 1 or outside the domain is skipped. */
+int d3d_texture_local_fold(const long long* texel, const int* rec, long long n_records, const long long* cover, long long n_texels,
+                           long long* state, d3d_stream_t stream);
+
+/* d3d_texture_local_band: the distances of the work items' texels: 0 on seam texels; round r = 1 .. radius gives r to every domain
+ *   texel not yet reached that has a 4-neighbour of distance r - 1 inside its chart's rect and domain; 255 elsewhere. */
+int d3d_texture_local_band(const int* work, long long n_work, const int* table, long long n_charts, const long long* page_row, int n_pages,
+                           int page_width, long long* state, int radius, d3d_stream_t stream);
+
+/* d3d_texture_local_sweeps: at most `iterations` (1 .. 65535) sweeps over the work items' texels.  A sweep updates the active
+ *   texels (distance 1 .. radius) with (column + row) even, then those with it odd, in place: c = (2 s + n) // (2 n) per channel,
+ *   s the sum and n the count of the 4-neighbours inside the rect and the domain.  changed [iterations] int32 (device): the
+ *   texels each sweep changed; the host reads them once per 16 sweeps and stops after the first sweep that changed nothing.
+ *   sweeps_run: HOST int, the sweeps that changed something. */
+int d3d_texture_local_sweeps(const int* work, long long n_work, const int* table, long long n_charts, const long long* page_row,
+                             int n_pages, int page_width, long long* state, int radius, int iterations, int* changed, int* sweeps_run,
+                             d3d_stream_t stream);
+
+/* d3d_texture_local_chart: the same distances and sweeps with one workgroup per chart of list [n_list] int32, the chart's rect held
+ *   in LDS: every listed rect must satisfy ((h + 2) (w + 1) + 4) * 8 <= lds_bytes <= 160 KiB (a larger one is left as it is).
+ *   iterations 0 .. 65535, 0: the distances only.  sweeps [n_charts] int32: per listed chart the sweeps that changed something. */
+int d3d_texture_local_chart(const int* list, long long n_list, const int* table, long long n_charts, const long long* page_row, int n_pages,
+                            int page_width, long long* state, int radius, int iterations, int lds_bytes, int* sweeps, d3d_stream_t stream);
+
+/* d3d_texture_local_apply: every domain texel of distance <= radius gets channel = clamp(channel + ((c + 32) >> 6), 0, 255); alpha
+ *   is unchanged. */
+int d3d_texture_local_apply(const int* work, long long n_work, const int* table, long long n_charts, const long long* page_row,
+                            int n_pages, int page_width, const long long* state, int radius, unsigned int* atlas, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.19 -- smoothing the texture's view choice over the mesh (deep3d_aerial_amd/texture.py states the rule in full; it
  * is this project's).  A candidate list is cand [n_faces, K] int64, K = d3d_texture_candidates_max(): per face the K smallest
  * keys of d3d_texture_select's format that its tests accept, increasing, padded with INT64_MAX.  Every pointer is DEVICE memory

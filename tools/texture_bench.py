@@ -3,7 +3,12 @@ V = 32 and V = 128 views of 2752 x 1856) textured from the same views with synth
 charts, rects, fill (with the empty-colour pass) and texcoords; faces, charts, pages and candidate views per face; and a per-view
 fp64 torch version of select, checked for the same keys.  The `level` entry times the seam levelling (csrc/texture_level.hip) on the
 same atlas: graph, samples, solve (with its iteration count), coverage and apply, and beside the solve a torch restatement of the
-same iteration (index_add per iteration) on the same graph, per iteration.  With --smooth_views W every row gains a `smooth` entry
+same iteration (index_add per iteration) on the same graph, per iteration.  The `local` entry times the local seam levelling
+(csrc/texture_local.hip) on the same atlas: seams and samples (with torch's sorts), the fold, the band alone, the solve (the band
+and the sweeps, every repeat from a fresh copy of the folded state) with its sweep count and the share of charts and of texels on
+each path, each path's charts alone, the LDS path's charts in one launch instead of three by LDS class, and apply; --no_local
+skips it.  With
+--smooth_views W every row gains a `smooth` entry
 (csrc/texture_smooth.hip): the candidates pass beside select, the smoothing's time and rounds, the charts, pages and the rects and
 fill times before and after, the mean and largest loss of projected area and the share of faces whose candidate list is full,
 which is where 16 candidates truncate.  With --outlier_threshold T every row gains an `outliers` entry
@@ -14,12 +19,14 @@ builds on the same tensors, taking turns.  The images here are a function of the
 what the rule is worth.  Rows of configurations a call does not run are kept in --out.
 
     python tools/texture_bench.py [--iters 3] [--views 32,128] [--voxels 0.5,0.25] [--out profiles/texture_bench.json]
-        [--smooth_views W [--smooth_max_loss 0.25] [--smooth_rounds 64]] [--outlier_threshold T [--variant_library SO]] [--no_level]"""
+        [--smooth_views W [--smooth_max_loss 0.25] [--smooth_rounds 64]] [--outlier_threshold T [--variant_library SO]] [--no_level]
+        [--no_local]"""
 import argparse
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -124,6 +131,71 @@ def level_times(vertices, faces, key, chart, table, packing, ov, atlas, iters):
             "graph_ms": round(t_graph, 3), "samples_ms": round(t_samples, 3), "solve_ms": round(t_solve, 3), "solve_iterations": it,
             "solve_converged": ok, "solve_ms_per_iteration": round(t_solve / max(it, 1), 4), "coverage_ms": round(t_cover, 3),
             "apply_ms": round(t_apply, 3), "torch_ms_per_iteration": round(t_torch / k, 4)}
+
+
+def fresh_ms(folded, fn, iters):
+    """(the mean device-event time of fn(state) over `iters` calls, the last result): every call, and the warm-up before them, gets
+    its own copy of the folded state, made outside the timed region -- the solve works in place, and a solved state is a fixed
+    point that the next solve would leave after one sweep."""
+    total, res = 0.0, None
+    for k in range(iters + 1):
+        state = folded.clone()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        res = fn(state)
+        b.record()
+        torch.cuda.synchronize()
+        total += a.elapsed_time(b) if k else 0.0
+    return total / iters, res
+
+
+def local_times(vertices, faces, chart, table, packing, ov, atlas, iters, radius=texture.DEFAULT_LOCAL_RADIUS,
+                iterations=texture.DEFAULT_LOCAL_ITERATIONS):
+    """Device-event times of the local levelling's passes on the filled atlas (which the apply changes; it is not used afterwards).
+    The band and every solve start from a fresh copy of the folded state.  Beside the whole solve: the charts of the LDS path alone
+    and those of the global path alone (the chart table's rows of each), and the LDS path's charts in ONE launch whose workgroups
+    all take the LDS of the largest chart, instead of the three launches by LDS class."""
+    out = {}
+    n = int(vertices.shape[0])
+    t_seams = MB.timed_ms(lambda: out.update(s=texture.local_seams(faces, chart, n)), iters)   # includes torch's sort of the pairs
+    seams = out["s"]
+    t_samples = MB.timed_ms(lambda: out.update(r=texture.local_samples(vertices, seams, table, packing, ov, atlas)), iters)
+    texel, rec = out["r"]
+    cover = texture.level_coverage(vertices, faces, chart, table, packing, ov)   # the `level` entry times it
+    t_fold = MB.timed_ms(lambda: out.update(f=texture.local_fold(texel, rec, cover, packing)), iters)
+    del cover
+    folded = out["f"]
+    solve = lambda tb: (lambda state: texture.local_solve(state, tb, packing, radius, iterations))
+    t_band, _ = fresh_ms(folded, lambda state: texture.local_band(state, table, packing, radius), iters)
+    t_solve, (state, info) = fresh_ms(folded, solve(table), iters)   # the band and the sweeps, both paths
+    classes, _, _ = texture._local_split(table, None)
+    in_lds = np.zeros(table.shape[0], bool)
+    in_lds[np.concatenate(classes)] = True
+    row = {}
+    if in_lds.any():
+        t, (_, i) = fresh_ms(folded, solve(table[in_lds]), iters)
+        row.update({"solve_lds_ms": round(t, 3), "solve_lds_sweeps": i["sweeps"]})
+        w, h = table[in_lds, 2].astype(np.int64), table[in_lds, 3].astype(np.int64)
+        need = int((((h + 2) * (w + 1) + 4) * texture.LOCAL_WORD_BYTES).max())
+        kept, texture.LOCAL_LDS_CLASSES = texture.LOCAL_LDS_CLASSES, (need,)
+        try:
+            t, _ = fresh_ms(folded, solve(table[in_lds]), iters)
+        finally:
+            texture.LOCAL_LDS_CLASSES = kept
+        row.update({"solve_lds_one_launch_ms": round(t, 3), "one_launch_lds_bytes": need})
+    if not in_lds.all():
+        t, (_, i) = fresh_ms(folded, solve(table[~in_lds]), iters)
+        row.update({"solve_global_ms": round(t, 3), "solve_global_sweeps": i["sweeps"]})
+    t_apply = MB.timed_ms(lambda: texture.local_apply(state, table, packing, atlas, radius), iters)
+    _, dist, domain, seam = texture.local_fields(state)
+    texels = table[:, 2].astype(np.int64) * table[:, 3]
+    return dict(row, **{"radius": radius, "iterations": iterations, "seam_edges": int(seams.shape[0]), "records": int(texel.shape[0]),
+            "seam_texels": int(seam.sum()), "active_texels": int((domain & (dist >= 1) & (dist <= radius)).sum()),
+            "seams_ms": round(t_seams, 3), "samples_ms": round(t_samples, 3), "fold_ms": round(t_fold, 3), "band_ms": round(t_band, 3),
+            "solve_ms": round(t_solve, 3), "sweeps": info["sweeps"], "converged": info["converged"], "charts_lds": info["charts_lds"],
+            "charts_global": info["charts_global"], "charts_per_lds_class": [int(len(c)) for c in classes],
+            "texels_lds_share": round(int(texels[in_lds].sum()) / max(int(texels.sum()), 1), 4), "apply_ms": round(t_apply, 3)})
 
 
 def smooth_times(vertices, faces, ov, key, before, smooth, iters):
@@ -246,7 +318,7 @@ def outlier_times(vertices, faces, ov, threshold, iters, variant=None):
     return res
 
 
-def run(views, voxel, iters, smooth=None, with_level=True, outlier_threshold=None, variant=None):
+def run(views, voxel, iters, smooth=None, with_level=True, outlier_threshold=None, variant=None, with_local=True):
     grid = mesh.MeshGrid(MB.BORDER, voxel)
     mviews = views
     vertices, faces = mesh.depth_to_mesh(mviews, grid)
@@ -290,6 +362,12 @@ def run(views, voxel, iters, smooth=None, with_level=True, outlier_threshold=Non
     if with_level:
         texture.fill_pages(table, packing, ov, atlas.zero_())
         row["level"] = level_times(vertices, faces, key, chart, table, packing, ov, atlas, iters)
+    if with_local:
+        texture.fill_pages(table, packing, ov, atlas.zero_())
+        row["local"] = local_times(vertices, faces, chart, table, packing, ov, atlas, iters)
+        # the passes of §4.13 in this very run: the only times the column may be set against
+        row["local"]["same_run"] = {"select_ms": round(t_select, 3), "charts_ms": round(t_charts, 3), "rects_ms": round(t_rects, 3),
+                                    "fill_ms": round(t_fill, 3), "texcoords_ms": round(t_tc, 3)}
     n_texels = int(atlas.numel())
     del atlas, chart, rects, table
     if smooth is not None:
@@ -319,6 +397,7 @@ def main(argv=None):
     ap.add_argument("--variant_library", default=None, metavar="SO",
                     help="with --outlier_threshold: a COLORS=per_slot build of the library whose colour pass is timed beside this one")
     ap.add_argument("--no_level", action="store_true", help="skip the seam levelling's times (a row then keeps the recorded `level` entry)")
+    ap.add_argument("--no_local", action="store_true", help="skip the local seam levelling's times (a row then keeps the recorded `local` entry)")
     a = ap.parse_args(argv)
     smooth = None
     if a.smooth_views is not None:
@@ -331,7 +410,7 @@ def main(argv=None):
     for nv in [int(x) for x in a.views.split(",")]:
         views = MB.make_views(nv, "cuda")
         for voxel in [float(x) for x in a.voxels.split(",")]:
-            r = run(views, voxel, a.iters, smooth, not a.no_level, a.outlier_threshold, a.variant_library)
+            r = run(views, voxel, a.iters, smooth, not a.no_level, a.outlier_threshold, a.variant_library, not a.no_local)
             print(json.dumps(r), flush=True)
             rows.append(r)
         del views
@@ -345,7 +424,7 @@ def main(argv=None):
             if mine is None:
                 rows.append(r)
             else:
-                for k in ("level", "smooth", "outliers"):
+                for k in ("level", "local", "smooth", "outliers"):
                     if k in r and k not in mine:
                         mine[k] = r[k]
         rows.sort(key=lambda r: (r["views"], -r["voxel_m"]))
