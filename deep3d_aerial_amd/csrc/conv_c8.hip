@@ -101,8 +101,9 @@ __global__ __launch_bounds__(NT, X3 ? (CI <= 16 ? 4 : 2) : NTN > 1 ? 1 : (CI <= 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // Workgroups are dealt to the 8 XCDs round-robin in launch order (x fastest): give each XCD a CONTIGUOUS run of the logical
     // order instead, x then y fastest, so that neighbouring tiles -- which share their halo rows and columns -- share an L2.
+    // Measured on the regulariser leg, per kernel family: here 6.03 -> 5.97 ms (kept); the transposed convolutions (conv_t2.hip)
+    // 5.96 -> 6.08 ms and the stride-2 convolutions (conv_cl.hip) no change: both keep the launch order.
     int bxi = blockIdx.x, byi = blockIdx.y, bzi = blockIdx.z;
-#ifndef D3D_CONV_NO_XCD   // (regulariser leg 6.03 -> 5.97 ms)
     {
         const int nx = gridDim.x, ny = gridDim.y, n = nx * ny * gridDim.z;
         if (n % 8 == 0) {
@@ -111,7 +112,6 @@ __global__ __launch_bounds__(NT, X3 ? (CI <= 16 ? 4 : 2) : NTN > 1 ? 1 : (CI <= 
             bxi = lin % nx; byi = (lin / nx) % ny; bzi = lin / (nx * ny);
         }
     }
-#endif
     const int x0 = bxi * TX, y0 = byi * TY;
     const int z0 = bzi * p.zper, z1 = min(z0 + p.zper, p.D);
     const int D = p.D, H = p.H, W = p.W;
@@ -199,14 +199,8 @@ __global__ __launch_bounds__(NT, X3 ? (CI <= 16 ? 4 : 2) : NTN > 1 ? 1 : (CI <= 
             for (int rr = 0; rr < RH; ++rr) {
                 const int r = r0 + rr;
                 if (r >= r1) break;
-#ifdef D3D_X_CONV0_NOLOAD   // timing-only build (wrong results): the channel-last input is not read -- what a layer whose input tile was already
-                            // in the CU would cost (profiles/r05_sweep_conv0_fusion_bound.txt); reported by d3d_build_flags() (planesweep_window.hip)
-                const u4 v = {stoff[r], (unsigned)r, (unsigned)zi, 0x3c003c00u};
-                (void)src;
-#else
                 const u4 v = *reinterpret_cast<const u4*>(src + stoff[r]);
-#endif
-                stc[rr] = v;   // raw: zeroed for cells outside the volume when it is committed -- a select here would wait for the load
+                stc[rr] = v;  // raw: zeroed for cells outside the volume when it is committed -- a select here would wait for the load
             }
             return;
         }

@@ -91,18 +91,8 @@ __global__ __launch_bounds__(64 * TYI) void convt3d_zs_bf16_kernel(T2Params p) {
     u4* wlds = reinterpret_cast<u4*>(smem + 2 * PATCH);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // each XCD takes a contiguous run of the logical tile order (neighbouring tiles share halo cells: one L2), see conv_c8.hip
-    int bxi = blockIdx.x, byi = blockIdx.y, bzi = blockIdx.z;
-#ifdef D3D_T2_XCD   // (measured: regulariser leg 5.96 -> 6.08 ms -- off)
-    {
-        const int nx = gridDim.x, ny = gridDim.y, n = nx * ny * gridDim.z;
-        if (n % 8 == 0) {
-            int lin = (bzi * ny + byi) * nx + bxi;
-            lin = (lin % 8) * (n / 8) + lin / 8;
-            bxi = lin % nx; byi = (lin / nx) % ny; bzi = lin / (nx * ny);
-        }
-    }
-#endif
+    // tiles in launch order: conv_c8.hip's XCD-contiguous order was measured here and lost (see there)
+    const int bxi = blockIdx.x, byi = blockIdx.y, bzi = blockIdx.z;
     const int ix0 = bxi * TXI, iy0 = byi * TYI;
     const int D = p.D, H = p.H, W = p.W;
     const int oz0 = bzi * p.ozper, oz1 = min(oz0 + p.ozper, 2 * D);

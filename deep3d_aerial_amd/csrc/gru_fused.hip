@@ -487,6 +487,9 @@ const char* gru_build_flags() {
 #if D3D_GRU_WAVES2 != 4
            " D3D_GRU_WAVES2"
 #endif
+#if defined(D3D_GRU1_TY) && D3D_GRU1_TY != 8
+           " D3D_GRU1_TY"
+#endif
 #if defined(D3D_GRU2_TY) && D3D_GRU2_TY != 8
            " D3D_GRU2_TY"
 #endif

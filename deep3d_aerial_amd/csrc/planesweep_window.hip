@@ -5,9 +5,10 @@
 // deltas into torus rings while compute waves sweep, one 12-wave workgroup owns all of a CU's LDS.  On an 8-plane sweep
 // a workgroup of that kernel lives ~38 k cycles of which ~6 k are arithmetic: the planning chain, the first window's
 // latency and the step barriers are all exposed because nothing else runs on the CU.  Here instead:
-//   * workgroup = a 32 x 8 patch of reference pixels x ALL the planes of its segment (<= 32) x all 8-channel groups; 8 waves
-//     (4 pixel waves x 2 plane sub-ranges), HALF a CU's LDS and 128 registers per lane, so TWO workgroups share a CU and
-//     one's loads run under the other's arithmetic;
+//   * workgroup = a 32 x 8 patch of reference pixels x ALL the planes of its segment (<= 32) x all 8-channel groups (a pair
+//     sweep: every channel in one group); 8 waves (4 pixel waves x 2 plane sub-ranges), HALF a CU's LDS and 128 registers per
+//     lane, so TWO workgroups share a CU and one's loads run under the other's arithmetic -- the ONE shape there is: the others
+//     that were built and measured are listed in DESIGN.md 4.1 ("Window kernel: tried and struck");
 //   * no planner, no rings, no loader waves: per source view ONE window -- the hull of the patch over the depth range of
 //     the chunk of planes being swept (the projection is monotone in x, y and d separately, so the hull of the eight box
 //     corners bounds every sample; same margins and clamps as the ring kernel's planner) -- staged by all waves with
@@ -36,28 +37,12 @@ int pack_channel_last_g8(const SweepParams& p, hipStream_t stream);   // planesw
 namespace {
 
 constexpr int WTW = 32;               // patch width: one 128-byte output row segment per lane row
-// Shapes of workgroup on the 32 x 8 patch.  Built: 8 waves (4 pixel waves x 2 plane sub-ranges), 8-channel groups, half a CU's
-// LDS, 128 registers.  Behind -DD3D_WINDOW_CG16 (measured, slower: see launch_window_ch): 12 waves (4 x 3), 16-channel groups
-// -- the geometry is paid once per 16 channels, four views' geometry stays live (168 registers), reference features in LDS --
-// on ALL of a CU's LDS, one workgroup per CU.
-#ifndef D3D_WINDOW_WG3   // experiment: 8-channel form as 4-wave workgroups (one plane sub-range), THREE per CU on a third of the LDS each:
-                        // stage 3 0.80 -> 0.86 ms, stage 2 1.20 -> 1.46, stage 1 1.87 -> 2.55; inside a CasMVSNet view the stage-3 windows
-                        // no longer fit (0.83 -> 3.4 ms)
-#define D3D_WINDOW_WG3 0
-#endif
-constexpr bool window_big(int MODE, int CH) { return CH != 8 && MODE != MODE_PAIR; }   // the 12-wave form (16-channel groups of the multi-view modes)
-constexpr int window_waves(int MODE, int CH) { return window_big(MODE, CH) ? 12 : (D3D_WINDOW_WG3 ? 4 : 8); }
-constexpr int window_lds_bytes(int MODE, int CH) { return window_big(MODE, CH) ? 160 * 1024 : (D3D_WINDOW_WG3 ? 53 * 1024 : 80 * 1024); }
-#ifndef D3D_WINDOW_DSEG
-#define D3D_WINDOW_DSEG 32
-#endif
-#ifndef D3D_WINDOW_RPW
-#define D3D_WINDOW_RPW 0   // window rows per wave and view in one staging batch (0: the built-in choice)
-#endif
-#ifndef D3D_WINDOW_VB
-#define D3D_WINDOW_VB 0    // views whose rows are requested together in one staging batch (0 = 1: view by view)
-#endif
-constexpr int WDSEG_MAX = D3D_WINDOW_DSEG;   // planes per workgroup segment (upper bound)
+// The workgroup on the 32 x 8 patch: 8 waves (4 pixel waves x 2 plane sub-ranges) on half a CU's LDS at 128 registers per lane,
+// two workgroups per CU.
+constexpr int WWAVES = 8, WTHREADS = 64 * WWAVES;
+constexpr int WLDS_BYTES = 80 * 1024;
+constexpr int WDSEG_MAX = 32;         // planes per workgroup segment (upper bound)
+constexpr int WPLANES_MAX = 48;       // sweeps of at most this many planes take the window kernel: every stage of the cascades
 constexpr int WTAB = 2 * WDSEG_MAX + 32;   // floats: per-plane depth range of the patch (pmin, pmax) + the views' translations (4 each)
 constexpr int WTOFF = 2 * WDSEG_MAX;      // where the translations start
 
@@ -149,8 +134,9 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
 
 // PH: patch height (PH / 2 pixel waves; the rest of the workgroup's waves are plane sub-ranges).
 template <int MODE, int NSRC, int CH, bool OUTCL, int PH>
-__global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) && !D3D_WINDOW_WG3 ? 4 : 3) void sweep_window_kernel(SweepParams p, WindowArgs a) {
-    constexpr int WWAVES = window_waves(MODE, CH), WTHREADS = 64 * WWAVES;
+__global__ __launch_bounds__(WTHREADS, 4) void sweep_window_kernel(SweepParams p, WindowArgs a) {
+    static_assert(PH == 8, "32 x 8 patches only: 32 x 16 was measured and struck (DESIGN.md 4.1, \"Window kernel: tried and struck\"); "
+                           "the parameter stays so that the kernels keep their names");
     static_assert(MODE == MODE_VARIANCE || MODE == MODE_WEIGHTED || (MODE == MODE_PAIR && NSRC == 1),
                   "window kernel: variance, weighted correlation, and the channel mean of one pair's correlation");
     static_assert(!OUTCL || MODE == MODE_VARIANCE || MODE == MODE_WEIGHTED, "channel-last 16-bit output: the variance volume and the weighted correlation");
@@ -174,10 +160,6 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
     long long t_stage = 0, t_sweep = 0;
     const int h = p.h, w = p.w, D = p.D;
     const size_t plane = (size_t)h * w;
-#if defined(D3D_EXPERIMENTS) && defined(D3D_WX_STAGGER)   // do the two workgroups of a CU run in lockstep?  the second wave of the dispatch starts late
-    if (blockIdx.x >= 256 && blockIdx.x < 512)
-        for (int i = 0; i < D3D_WX_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
 
     // block -> (patch row, segment, patch column): blocks b, b + 8, ... share an XCD (and its L2); within an XCD's run vertically
     // adjacent patches come first (they share most of their source rows), as in the ring kernel
@@ -215,9 +197,8 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
             T0[i] = -1.0f; T1[i] = -1.0f; T2[i] = 1.0f;
         }
     }
-#ifndef D3D_WINDOW_T_SGPR
     // The translations live in LDS and are read back per view and plane (one broadcast ds_read_b128): as scalar registers they
-    // were the ones spilled -- 48 v_readlane in a plane loop of 428 instructions.
+    // were the ones spilled.
     if (tid < NSRC) {
         f4 tv = {0, 0, 0, 0};
 #pragma unroll
@@ -225,7 +206,6 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
         *reinterpret_cast<f4*>(lds + WTOFF + 4 * tid) = tv;
     }
     const int tadr = lds_base_bytes(lds) + WTOFF * 4;
-#endif
     float vw[NSRC];
     float rden = 0.0f;
     if (MODE == MODE_WEIGHTED) {
@@ -320,18 +300,11 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
     }
     __syncthreads();
 
-    // 16-channel groups: the patch's REFERENCE features live in LDS too ([quad][pixel] 16-byte cells, a lane reads its own cell
-    // once per plane and quad) -- sixteen registers per lane the 128-register budget of two workgroups per CU does not have
-    constexpr bool REF_LDS = Q > 2 && MODE != MODE_PAIR;   // (a pair sweep has one view's geometry live: room for the reference in registers)
-    constexpr int NPIX = WTW * PH;
-    constexpr int REF_BYTES = REF_LDS ? CH * NPIX * 4 : 0;
     constexpr int VW_BYTES = VW_LDS ? WTW * PH * 16 + 3 * NSRC * 16 : 0;   // view weights per pixel + the views' matrices
     const int my_mat = lds_base_bytes(lds) + WTAB * 4 + WTW * PH * 16;
     const int my_vw = lds_base_bytes(lds) + WTAB * 4 + (pw * 64 + lane) * 16;
-    const int ref0 = lds_base_bytes(lds) + WTAB * 4 + VW_BYTES;
-    const int my_ref = ref0 + (pw * 64 + lane) * 16;
-    const int lds0 = ref0 + REF_BYTES;
-    const int cap_bytes = a.cap_bytes - REF_BYTES - VW_BYTES;
+    const int lds0 = lds_base_bytes(lds) + WTAB * 4 + VW_BYTES;   // the windows
+    const int cap_bytes = a.cap_bytes - VW_BYTES;
     const float umax = (float)w, vmax = (float)h;
     const float invV = 1.0f / (float)(p.n_src + 1);
     const size_t cstride_b = (p.plane_major ? plane : (size_t)D * plane) * 4;   // bytes between channels
@@ -383,7 +356,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
         return good;
     };
 
-    f4 r[REF_LDS ? 1 : Q];   // reference features of the group (8-channel groups: registers)
+    f4 r[Q];   // reference features of the group
     unsigned long long even_quad = 0;
     auto finalize_store = [&](const f4& s, const f4& qq, unsigned long long& ob, int q) {
         f4 o;
@@ -401,20 +374,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
             if ((q & 1) == 0) {
                 even_quad = pack_h16x4(o);
             } else {
-#ifdef D3D_CL_PARTIAL_DEFAULT_POLICY   // experiment: see store_sbase_h16x8
-                if (a.ngroups > 1) store_sbase_h16x8<true>(ob, pixo, even_quad, pack_h16x4(o));
-                else
-#endif
-#ifdef D3D_X_SWEEP_NOSTORE   // timing-only build (wrong results): the channel-last volume is computed and NOT written -- what a sweep whose
-                             // output stayed in the CU would cost (profiles/r05_sweep_conv0_fusion_bound.txt); reported by d3d_build_flags()
-                {
-                    const unsigned long long hq = pack_h16x4(o);
-                    if (a.cap_bytes < 0) store_sbase_h16x8(ob, pixo, even_quad, hq);   // (a uniform test that never holds: the values stay live)
-                    else asm volatile("" : : "v"(hq), "v"(even_quad));
-                }
-#else
                 store_sbase_h16x8(ob, pixo, even_quad, pack_h16x4(o));
-#endif
                 ob += 16;
             }
         } else {
@@ -459,27 +419,14 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
         }
         for (int gi = 0; gi < a.ngroups; ++gi) {
             const int c0 = gi * CH;
-            if constexpr (REF_LDS) {
-                for (int idx = tid; idx < Q * NPIX; idx += WTHREADS) {   // (read after the chunk's "windows staged" barrier)
-                    const int q = idx / NPIX, pp = idx - q * NPIX;
-                    const int qx = x0 + (pp & 31), qy = y0 + (pp >> 5);
-                    const bool in = qx < w && qy < h;
-                    const float* __restrict__ sq = p.feats[0] + (size_t)(c0 + 4 * q) * plane + (in ? (size_t)qy * w + qx : 0);
-                    f4 v;
-                    v[0] = sq[0]; v[1] = sq[plane]; v[2] = sq[2 * plane]; v[3] = sq[3 * plane];
-                    if (!in) v = (f4){0, 0, 0, 0};
-                    lds_write4_abs(ref0 + idx * 16, v);
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float t = p.feats[0][(size_t)(c0 + 4 * q + k) * plane + pix];
+                    r[q][k] = valid ? t : 0.0f;
                 }
-            } else {
-#pragma unroll
-                for (int q = 0; q < Q; ++q)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float t = p.feats[0][(size_t)(c0 + 4 * q + k) * plane + pix];
-                        r[REF_LDS ? 0 : q][k] = valid ? t : 0.0f;
-                    }
-                // (waited for below, behind the staging loads: ref_wait)
-            }
+            // (waited for below, behind the staging loads)
             asm volatile("" : "+v"(aff_lo), "+v"(aff_step), "+v"(rden));
             if (MODE == MODE_WEIGHTED && !VW_LDS) {
 #pragma unroll
@@ -506,12 +453,8 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                     // order, channels in order: the ring kernel's sum)
                     float pair_acc = 0.0f;
                     if (staged) {
-#ifndef D3D_WINDOW_T_SGPR
                         const f4 tv = *(volatile lds_f4_ptr)(unsigned)tadr;
                         const TapL g = geo_win(ray[0], tv[0], tv[1], tv[2], dv, umax, vmax, W[0]);
-#else
-                        const TapL g = geo_win(ray[0], T0[0], T1[0], T2[0], dv, umax, vmax, W[0]);
-#endif
                         f4 tp[2][4];
                         auto request = [&](int q2, f4 (&dst)[4]) {
                             const int n = g.a0 + q2 * W[0].qb, s_ = g.a1 + q2 * W[0].qb;
@@ -528,7 +471,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                             asm volatile("" : "+v"(c[3]));
                             const f4 val = blend(c[0], c[1], c[2], c[3], g.nw, g.ne, g.sw, g.se);
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) pair_acc = fmaf(r[REF_LDS ? 0 : q][k], val[k], pair_acc);
+                            for (int k = 0; k < 4; ++k) pair_acc = fmaf(r[q][k], val[k], pair_acc);
                         }
                     } else {
                         float u, v;
@@ -541,56 +484,22 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                             for (int kk = 0; kk < 4; ++kk) {
                                 const float* __restrict__ gk = gsrc + (size_t)(4 * q + kk) * plane;
                                 const float val = fmaf(gk[t.dyw + t.dx], t.se, fmaf(gk[t.dyw], t.sw, fmaf(gk[t.dx], t.ne, gk[0] * t.nw)));
-                                pair_acc = fmaf(r[REF_LDS ? 0 : q][kk], val, pair_acc);
+                                pair_acc = fmaf(r[q][kk], val, pair_acc);
                             }
                     }
                     store_sbase(uniform64(p.out + (size_t)d * plane), pixb, pair_acc / (float)CH);
                     return;
                 }
-                if constexpr (Q > 2) { if (staged) {
-                    // Unit-major (16-channel groups): units u = (quad q, view i) in q-major order, one quad's accumulators live, the
-                    // four views' geometry kept for the whole plane (the ring kernel's order)
-                    TapL t[NSRC];
-#pragma unroll
-                    for (int i = 0; i < NSRC; ++i) t[i] = geo_win(ray[i], T0[i], T1[i], T2[i], dv, umax, vmax, W[i]);
-                    constexpr int NU = Q * NSRC;
-                    f4 tp[2][4];
-                    auto request = [&](int u, f4 (&dst)[4]) {
-                        const int q2 = u / NSRC, i2 = u % NSRC;
-                        const int n = t[i2].a0 + q2 * W[i2].qb, s_ = t[i2].a1 + q2 * W[i2].qb;
-                        dst[0] = lds_read4_abs(n);
-                        dst[1] = lds_read4_abs(n + 16);
-                        dst[2] = lds_read4_abs(s_);
-                        dst[3] = lds_read4_abs(s_ + 16);
-                    };
-                    f4 rq = lds_read4_abs(my_ref);
-                    request(0, tp[0]);
-                    f4 s, qq;
-#pragma unroll
-                    for (int u = 0; u < NU; ++u) {
-                        const int q = u / NSRC, i = u % NSRC;
-                        if (u + 1 < NU) request(u + 1, tp[(u + 1) & 1]);
-                        if (i == 0) {
-                            if (MODE == MODE_VARIANCE) { s = rq; qq = s * s; }
-                            else { s = (f4){0, 0, 0, 0}; qq = s; }
-                        }
-                        f4 (&c)[4] = tp[u & 1];
-                        asm volatile("" : "+v"(c[3]));   // one wait per unit (LDS returns in order)
-                        const f4 val = blend(c[0], c[1], c[2], c[3], t[i].nw, t[i].ne, t[i].sw, t[i].se);
-                        accumulate(s, qq, val, rq, i);
-                        if (i == NSRC - 1 && q + 1 < Q) rq = lds_read4_abs(my_ref + (q + 1) * (NPIX * 16));   // (weighted mode reads rq until here)
-                        if (i == NSRC - 1) finalize_store(s, qq, ob, q);
-                    }
-                } }
                 if constexpr (Q <= 2) { if (staged) {
-                    // View-major (8-channel groups): ONE view's geometry is live at a time (the next view's is computed while this view's taps are in
+                    // (a pair sweep, whose groups can be wider, has returned above)
+                    // View-major: ONE view's geometry is live at a time (the next view's is computed while this view's taps are in
                     // flight) and the accumulators of the group's quads stay in registers until the last view -- the unit-major
                     // order of the ring kernel keeps 4 x (2 addresses + 4 weights) alive and does not fit 128 registers.  Per channel
                     // the views are still added in order 0, 1, ...: the same sums.
                     f4 s[Q], qq[Q];
 #pragma unroll
                     for (int q = 0; q < Q; ++q) {
-                        if (MODE == MODE_VARIANCE) { s[q] = r[REF_LDS ? 0 : q]; qq[q] = s[q] * s[q]; }
+                        if (MODE == MODE_VARIANCE) { s[q] = r[q]; qq[q] = s[q] * s[q]; }
                         else { s[q] = (f4){0, 0, 0, 0}; qq[q] = s[q]; }
                     }
                     f4 tp[Q][4];
@@ -601,7 +510,6 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                         tp[q2][2] = lds_read4_abs(s_);
                         tp[q2][3] = lds_read4_abs(s_ + 16);
                     };
-#ifndef D3D_WINDOW_T_SGPR
                     auto geo_view = [&](int i) {
                         if constexpr (VW_LDS) {   // (matrix rows from LDS, broadcast reads; the ray as make_ray computes it)
                             const f4 m0 = *(volatile lds_f4_ptr)(unsigned)(my_mat + 48 * i), m1 = *(volatile lds_f4_ptr)(unsigned)(my_mat + 48 * i + 16),
@@ -615,9 +523,6 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                         const f4 tv = *(volatile lds_f4_ptr)(unsigned)(tadr + 16 * i);   // (volatile: not hoisted out of the plane loop)
                         return geo_win(ray[i], tv[0], tv[1], tv[2], dv, umax, vmax, W[i]);
                     };
-#else
-                    auto geo_view = [&](int i) { return geo_win(ray[i], T0[i], T1[i], T2[i], dv, umax, vmax, W[i]); };
-#endif
                     TapL gc = geo_view(0);
 #pragma unroll
                     for (int q = 0; q < Q; ++q) request(gc, 0, q);
@@ -631,7 +536,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                             asm volatile("" : "+v"(tp[q][3]));   // one wait per quad (LDS returns in order)
                             const f4 val = blend(tp[q][0], tp[q][1], tp[q][2], tp[q][3], gc.nw, gc.ne, gc.sw, gc.se);
                             if (i + 1 < NSRC) request(gn, i + 1, q);   // the next view's taps of this quad, into the registers just read
-                            accumulate(s[q], qq[q], val, r[REF_LDS ? 0 : q], i);
+                            accumulate(s[q], qq[q], val, r[q], i);
                         }
                         gc = gn;
                     }
@@ -642,12 +547,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                     f4 s[Q], qq[Q], rf[Q];
 #pragma unroll
                     for (int q = 0; q < Q; ++q) {
-                        if constexpr (REF_LDS) {   // (no barrier on this path: the reference features straight from global memory)
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) rf[q][k] = p.feats[0][(size_t)(c0 + 4 * q + k) * plane + pix];
-                        } else {
-                            rf[q] = r[REF_LDS ? 0 : q];
-                        }
+                        rf[q] = r[q];
                         if (MODE == MODE_VARIANCE) { s[q] = rf[q]; qq[q] = s[q] * s[q]; }
                         else { s[q] = (f4){0, 0, 0, 0}; qq[q] = s[q]; }
                     }
@@ -697,13 +597,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                     // address registers -- and a lane or row outside the image gets an offset beyond the buffer, for which the hardware
                     // returns zeros: no clamps, no selects.  The loads of RPW rows (4 x Q x RPW per lane) are issued before the first
                     // 16-byte LDS write; the other workgroup of the CU sweeps meanwhile.
-                    // Views per batch (VB): round 5 measured requesting the rows of SEVERAL views' windows before the first LDS write of a
-                    // batch (one memory round trip per batch instead of one per view).  The extra descriptors / offsets in flight push the
-                    // kernel over its 128 registers (80 - 180 bytes of scratch per lane, reloaded in the plane loop): stage 1 1.68 -> 2.28 ms
-                    // with all four views, 1.94 with two; and halving the rows per batch (twice the round trips) costs only 5 % -- the staging
-                    // is not a latency chain.  View by view stays (profiles/r05_window_staging.txt).
-                    constexpr int VB = D3D_WINDOW_VB > 0 ? (D3D_WINDOW_VB < NSRC ? D3D_WINDOW_VB : NSRC) : 1;
-                    constexpr int RPW = D3D_WINDOW_RPW > 0 ? D3D_WINDOW_RPW : (Q > 2 ? 1 : (VB > 2 ? 1 : (PH > 8 ? 3 : 2)));
+                    constexpr int RPW = Q > 2 ? 1 : 2;   // window rows per wave in one batch of loads
                     constexpr int OOB = 0x7ffffff0;   // (launch check: C * h * w * 4 < 2^31, so any offset from here on is out of range)
                     const int fbytes = p.C * (int)plane * 4;
 #pragma unroll
@@ -711,6 +605,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                         if (i >= p.n_src)   // the zero cells of an unused view
                             for (int idx = tid; idx < 4 * Q; idx += WTHREADS) lds_write4_abs(W[i].base + idx * 16, (f4){0, 0, 0, 0});
                     }
+                    constexpr int VB = 1;   // views per batch of loads: one.  ORIGINAL FORM KEPT -- as plain code for view i0 the one-trip loops below compile to other machine code
 #pragma unroll
                     for (int i0 = 0; i0 < NSRC; i0 += VB) {
                         int maxw = 0, maxh = 0;
@@ -727,7 +622,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                         for (int col0 = 0; col0 < maxw; col0 += 64) {   // (windows wider than 64 cells: rare)
                             const int col = col0 + lane;
                             for (int row0 = wave; row0 < maxh; row0 += RPW * WWAVES) {
-                                f4 v[VB][RPW][Q];
+                                f4 v[RPW][Q];
 #pragma unroll
                                 for (int i = i0; i < i0 + VB && i < NSRC; ++i) {
                                     if (i >= p.n_src) continue;
@@ -748,7 +643,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                                         for (int q = 0; q < Q; ++q)
 #pragma unroll
                                             for (int c = 0; c < 4; ++c)
-                                                v[i - i0][r][q][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, roff + (4 * q + c) * pb, 0));
+                                                v[r][q][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, roff + (4 * q + c) * pb, 0));
                                     }
                                 }
 #pragma unroll
@@ -760,7 +655,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                                         const int row = row0 + r * WWAVES;
                                         if (row < W[i].wh && col < W[i].ww) {
 #pragma unroll
-                                            for (int q = 0; q < Q; ++q) lds_write4_abs(cadr + q * W[i].qb + row * W[i].rowb, v[i - i0][r][q]);
+                                            for (int q = 0; q < Q; ++q) lds_write4_abs(cadr + q * W[i].qb + row * W[i].rowb, v[r][q]);
                                         }
                                     }
                                 }
@@ -773,7 +668,7 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
 #pragma unroll
                                     for (int r = 0; r < RPW; ++r)
 #pragma unroll
-                                        for (int q = 0; q < Q; ++q) asm volatile("" : : "v"(v[i - i0][r][q]));
+                                        for (int q = 0; q < Q; ++q) asm volatile("" : : "v"(v[r][q]));
                                 }
                             }
                         }
@@ -781,10 +676,8 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
                     // The reference loads are waited for HERE, once per chunk and group, with the staging loads in front of them: a
                     // wait left to the first use would sit inside the plane loop, where the counter it waits on also counts the
                     // previous plane's stores -- every plane would wait for its predecessor's stores.
-                    if constexpr (!REF_LDS) {
 #pragma unroll
-                        for (int q = 0; q < Q; ++q) asm volatile("" : "+v"(r[q]));
-                    }
+                    for (int q = 0; q < Q; ++q) asm volatile("" : "+v"(r[q]));
                     __syncthreads();   // windows staged
                     const long long ts1 = D3D_WCLOCK();
 #if defined(D3D_EXPERIMENTS) && defined(D3D_WX_NOSWEEP)   // timing only (results wrong): the staging without the sweep
@@ -802,10 +695,8 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
 #endif
                 } else {
                     D3D_WSTAT(3, n);
-                    if constexpr (!REF_LDS) {
 #pragma unroll
-                        for (int q = 0; q < Q; ++q) asm volatile("" : "+v"(r[q]));
-                    }
+                    for (int q = 0; q < Q; ++q) asm volatile("" : "+v"(r[q]));
                     for (int j = sub; j < n; j += NSUBW) sweep_plane(done + j, false);
                 }
         }
@@ -821,7 +712,6 @@ __global__ __launch_bounds__(64 * window_waves(MODE, CH), !window_big(MODE, CH) 
 template <int MODE, int NSRC, int CH, bool OUTCL, int PH>
 static int launch_window_one(const SweepParams& p, hipStream_t stream) {
     auto kern = sweep_window_kernel<MODE, NSRC, CH, OUTCL, PH>;
-    constexpr int WLDS_BYTES = window_lds_bytes(MODE, CH);
     if (OUTCL && (size_t)p.h * p.w * p.C * 2 >= ((size_t)1 << 32)) return D3D_ERR_UNSUPPORTED;
     if ((size_t)p.h * p.w * p.C * 4 >= 0x7ffffff0u) return D3D_ERR_UNSUPPORTED;   // buffer-load offsets of the staging (see OOB)
     int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), WLDS_BYTES);
@@ -830,17 +720,10 @@ static int launch_window_one(const SweepParams& p, hipStream_t stream) {
     a.ngroups = p.C / CH;
     a.tiles_x = ceil_div(p.w, WTW);
     a.tiles_y = ceil_div(p.h, PH);
-    // plane segments: at most WDSEG_MAX planes, and short enough that the launch has ~ten rounds of workgroups (two per CU) -- but
-    // not below 8 planes: a segment pays its own prologue and restages windows its neighbour segment has in LDS
+    // plane segments: the fewest that hold at most WDSEG_MAX planes each, the planes spread evenly over them (a segment pays its
+    // own prologue and restages windows its neighbour segment has in LDS: more, shorter segments were measured and struck,
+    // DESIGN.md 4.1)
     a.nseg = ceil_div(p.D, WDSEG_MAX);
-    {
-        const long tiles = (long)a.tiles_x * a.tiles_y;
-#ifndef D3D_WINDOW_ROUNDS
-#define D3D_WINDOW_ROUNDS 0
-#endif
-        const int want = (int)min((long)ceil_div(p.D, 8), (long)ceil_div((long)D3D_WINDOW_ROUNDS * 512, tiles));
-        a.nseg = max(a.nseg, want);
-    }
     a.dseg = ceil_div(p.D, a.nseg);
     a.nseg = ceil_div(p.D, a.dseg);
     a.cap_bytes = WLDS_BYTES - WTAB * 4;
@@ -862,7 +745,7 @@ static int launch_window_one(const SweepParams& p, hipStream_t stream) {
         (void)hipMemset(a.stats, 0, 8 * sizeof(unsigned long long));
     }
 #endif
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * window_waves(MODE, CH)), WLDS_BYTES, stream, p, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(WTHREADS), WLDS_BYTES, stream, p, a);
     D3D_LAUNCH_CHECK("sweep_window_kernel launch");
 #ifdef D3D_EXPERIMENTS
     if (a.stats) {
@@ -870,7 +753,7 @@ static int launch_window_one(const SweepParams& p, hipStream_t stream) {
         (void)hipMemcpy(hs, a.stats, sizeof(hs), hipMemcpyDeviceToHost);
         const double n = (double)hs[0];
         fprintf(stderr, "[d3d window stats] CH=%d waves=%d wgs=%.0f groups=%d | per workgroup: staged chunks %.2f, planes per chunk %.2f, gathered planes %.2f, "
-                "staged KB %.1f | cycles (wave 0): staging %.0f, sweeping %.0f, total %.0f\n", CH, window_waves(MODE, CH), n, a.ngroups, hs[1] / n,
+                "staged KB %.1f | cycles (wave 0): staging %.0f, sweeping %.0f, total %.0f\n", CH, WWAVES, n, a.ngroups, hs[1] / n,
                 hs[1] ? (double)hs[2] / hs[1] : 0.0, hs[3] / n, hs[4] * 16.0 / 1024.0 / n, hs[5] / n, hs[6] / n, hs[7] / n);
         (void)hipFree(a.stats);
     }
@@ -878,56 +761,23 @@ static int launch_window_one(const SweepParams& p, hipStream_t stream) {
     return D3D_OK;
 }
 
-// -DD3D_WINDOW_PH16=n: sweeps of at most n planes take 32 x 16 patches (8 pixel waves, one plane sub-range) instead of 32 x 8
-// (4 x 2): what a wave executes besides its planes -- rays, the depth-range table, the windows, its share of the staging: ~2000 of
-// the ~3300 instructions of a wave at stage 3 -- is then spread over twice the planes.  On the synthetic stage-3 sweep (flat
-// depth map) 0.77 -> 0.63 ms; inside a CasMVSNet view (random weights: a noisy stage-2 depth map) the taller patch's windows no
-// longer fit and the sweep takes 3.7 ms instead of 0.76 -- off (profiles/r04_window_phases.txt).
-#ifndef D3D_WINDOW_PH16
-#define D3D_WINDOW_PH16 0
-#endif
-#ifndef D3D_WINDOW_PLANES
-#define D3D_WINDOW_PLANES 48   // sweeps of at most this many planes take the window kernel (0: never): every stage of the cascades
-#endif
-
+// the three outcomes of the multi-view modes: the variance volume as channel-last 16-bit cells, the weighted correlation as CL8
+// 16-bit cells, planar fp32 -- all in 8-channel groups on 32 x 8 patches
 template <int MODE, int NSRC>
 static int launch_window_ch(const SweepParams& p, hipStream_t stream) {
-    // (-DD3D_WINDOW_CG16: 16-channel groups on 12-wave workgroups that own the CU's LDS, for deep sweeps -- the geometry is paid
-    //  once per 16 channels, but the windows are twice as large, nothing hides their staging, and chunks shrink: config 2 7.3 ms
-    //  against 6.7 ms for the 8-channel form and 5.8 ms for the ring kernel; stage 2 of the cascade 1.33 against 1.31 ms)
-#ifdef D3D_WINDOW_CG16
-    const bool cg16 = p.C % 16 == 0 && p.D >= D3D_WINDOW_CG16 && p.out_cl != 2;   // (the CL8 store walks ONE plane of 8-channel groups)
-#else
-    constexpr bool cg16 = false;
-#endif
     if constexpr (MODE == MODE_VARIANCE) {
-        if (p.out_cl) {
-#ifdef D3D_WINDOW_CG16
-            if (cg16) return launch_window_one<MODE, NSRC, 16, true, 8>(p, stream);
-#endif
-#if D3D_WINDOW_PH16 > 0
-            if (p.D <= D3D_WINDOW_PH16) return launch_window_one<MODE, NSRC, 8, true, 16>(p, stream);
-#endif
-            return launch_window_one<MODE, NSRC, 8, true, 8>(p, stream);
-        }
+        if (p.out_cl) return launch_window_one<MODE, NSRC, 8, true, 8>(p, stream);
     }
     if constexpr (MODE == MODE_WEIGHTED) {   // (round 5: the slice regularisers' cost planes as CL8 16-bit cells -- d3d_weighted_corr_cl8_h16)
         if (p.out_cl == 2) return launch_window_one<MODE, NSRC, 8, true, 8>(p, stream);
     }
     if (p.out_cl) return D3D_ERR_UNSUPPORTED;
-#ifdef D3D_WINDOW_CG16
-    if (cg16) return launch_window_one<MODE, NSRC, 16, false, 8>(p, stream);
-#endif
-    (void)cg16;
-#if D3D_WINDOW_PH16 > 0
-    if (p.D <= D3D_WINDOW_PH16) return launch_window_one<MODE, NSRC, 8, false, 16>(p, stream);
-#endif
     return launch_window_one<MODE, NSRC, 8, false, 8>(p, stream);
 }
 
 // scratch of the gather path's channel-last copy (d3d_sweep_workspace_bytes takes the larger of this and the ring kernel's)
 size_t window_workspace_bytes(int n_src, int C, int D, int h, int w, int elem_bytes) {
-    if (elem_bytes != 4 || C % 8 != 0 || n_src > 4 || n_src < 1 || D3D_WINDOW_PLANES == 0 || D > D3D_WINDOW_PLANES) return 0;
+    if (elem_bytes != 4 || C % 8 != 0 || n_src > 4 || n_src < 1 || D > WPLANES_MAX) return 0;
     return (size_t)n_src * C * h * w * 4;
 }
 
@@ -936,17 +786,9 @@ size_t window_workspace_bytes(int n_src, int C, int D, int h, int w, int elem_by
 int launch_window(int mode, const SweepParams& p, hipStream_t stream, bool forced) {
     if (p.elem_bytes != 4 || p.C % 8 != 0 || p.n_src > 4 || p.n_src < 1) return D3D_ERR_UNSUPPORTED;
     if (mode != MODE_VARIANCE && mode != MODE_WEIGHTED && mode != MODE_PAIR) return D3D_ERR_UNSUPPORTED;
-    if (!forced && (D3D_WINDOW_PLANES == 0 || p.D > D3D_WINDOW_PLANES)) return D3D_ERR_UNSUPPORTED;
+    if (!forced && p.D > WPLANES_MAX) return D3D_ERR_UNSUPPORTED;
     if (mode == MODE_PAIR) {   // one source view, every channel in one pass
         if (p.n_src != 1 || p.out_cl) return D3D_ERR_UNSUPPORTED;
-#if D3D_WINDOW_PH16 > 0
-        if (p.D <= D3D_WINDOW_PH16)
-            switch (p.C) {
-                case 8: return launch_window_one<MODE_PAIR, 1, 8, false, 16>(p, stream);
-                case 16: return launch_window_one<MODE_PAIR, 1, 16, false, 16>(p, stream);
-                case 32: return launch_window_one<MODE_PAIR, 1, 32, false, 16>(p, stream);
-            }
-#endif
         switch (p.C) {
             case 8: return launch_window_one<MODE_PAIR, 1, 8, false, 8>(p, stream);
             case 16: return launch_window_one<MODE_PAIR, 1, 16, false, 8>(p, stream);
@@ -964,33 +806,6 @@ const char* window_build_flags() {
     return ""
 #ifdef D3D_EXPERIMENTS
            " D3D_EXPERIMENTS(window)"
-#endif
-#if D3D_WINDOW_WG3
-           " D3D_WINDOW_WG3"
-#endif
-#ifdef D3D_WINDOW_CG16
-           " D3D_WINDOW_CG16"
-#endif
-#if D3D_WINDOW_PH16 != 0
-           " D3D_WINDOW_PH16"
-#endif
-#if D3D_WINDOW_DSEG != 32
-           " D3D_WINDOW_DSEG"
-#endif
-#if D3D_WINDOW_RPW != 0
-           " D3D_WINDOW_RPW"
-#endif
-#if D3D_WINDOW_VB != 0
-           " D3D_WINDOW_VB"
-#endif
-#ifdef D3D_CL_PARTIAL_DEFAULT_POLICY
-           " D3D_CL_PARTIAL_DEFAULT_POLICY"
-#endif
-#ifdef D3D_X_SWEEP_NOSTORE
-           " D3D_X_SWEEP_NOSTORE"
-#endif
-#ifdef D3D_X_CONV0_NOLOAD
-           " D3D_X_CONV0_NOLOAD"
 #endif
         ;
 }

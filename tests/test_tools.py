@@ -62,3 +62,36 @@ def test_store_hazard_scan_finds_the_pattern_and_the_library_is_clean():
         pytest.skip("llvm-objdump not in this image")
     n, hits = H.scan_library()
     assert n > 0 and hits == [], hits
+
+
+def test_kernel_diff_sorts_names_into_its_three_lists():
+    """tools/kernel_diff.py diff_tables: equal tables, a kernel only one side has, a kernel whose code differs, and a name that is
+    ambiguous (None) on a side -- which counts as differing even against another None, because it pins nothing."""
+    import kernel_diff as K
+
+    x, y, z = (64, "a" * 64), (64, "b" * 64), (128, "a" * 64)
+    assert K.diff_tables({}, {}) == ([], [], [])
+    assert K.diff_tables({"k1": x, "k2": y}, {"k2": y, "k1": x}) == ([], [], [])
+    assert K.diff_tables({"k1": x, "k2": y, "k0": x}, {"k1": x, "k3": y}) == (["k0", "k2"], ["k3"], [])
+    assert K.diff_tables({"k1": x, "k2": y}, {"k1": y, "k2": y}) == ([], [], ["k1"])
+    assert K.diff_tables({"k1": x}, {"k1": z}) == ([], [], ["k1"])   # same hash of another size: not the same code
+    assert K.diff_tables({"k1": None, "k2": x, "k3": None}, {"k1": x, "k2": None, "k3": None}) == ([], [], ["k1", "k2", "k3"])
+    assert K.diff_tables({"k1": x, "k2": x}, {"k2": y, "k3": x}) == (["k1"], ["k3"], ["k2"])
+
+
+def test_kernel_diff_finds_the_window_object_unchanged_in_the_library(capsys):
+    """The command itself, on two files of one build: every kernel of csrc/planesweep_window.o is in the library with the same
+    code, so nothing is only in A, nothing differs and the exit status is 0 (kernels that only the library has are no difference)."""
+    import kernel_diff as K
+    from deep3d_aerial_amd import _lib
+
+    _lib.build()
+    obj = os.path.join(_lib.CSRC, "planesweep_window.o")
+    assert K.main(["kernel_diff.py", obj, _lib.SO_PATH]) == 0
+    out = capsys.readouterr().out
+    first = out.splitlines()[0]
+    n_obj = len(_lib.kernel_code_table(obj))
+    assert n_obj > 0 and first.startswith("kernels: %d / %d, only in A: 0," % (n_obj, len(_lib.kernel_code_table())))
+    assert first.endswith("differing: 0 of %d common" % n_obj)
+    assert "differing: _Z" not in out and "only in A: _Z" not in out and "only in B: _Z" in out
+    assert K.main(["kernel_diff.py", obj]) == 2
