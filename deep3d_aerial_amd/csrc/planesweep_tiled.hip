@@ -462,7 +462,7 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
             int wy1 = min((int)floorf(vmax + 0.0625f) + 1, h + 1);
             int ww = max(wx1 - wx0 + 1, 0), wh = max(wy1 - wy0 + 1, 0);   // >= 2 x 2: every sample has its four taps in the window
             // unused view of the template (n_src < NSRC): its samples sit at (-1, -1) (geo_ring with a zero ray), weight 1 on
-            // the tap at (-1, -1) -- a zero -- and weight 0 on the other three
+            // the tap at (-1, -1) -- a zero -- and weight 0 on the other three (pixel (0, 0) among them: zero_first_cells_kernel)
             if (vsel >= p.n_src) { wx0 = -1; wy0 = -1; ww = 2; wh = 2; ok = true; }
             if (!act) { ww = 0; wh = 0; ok = true; }
             // ring size: the union of consecutive windows must fit (asynchronous delta staging)
@@ -1210,6 +1210,14 @@ __global__ __launch_bounds__(256) void pack_channel_last_kernel(PackArgs pa, int
     reinterpret_cast<f4*>(out + ((size_t)vg * plane + pos) * CW)[q] = x;
 }
 
+// The slots of the copy that have no view (a sweep of n_src sources runs on the template of NSRC = 2 | 4 | 6, see template_views).
+// The plan puts every sample of such a slot at (-1, -1): weight 1 on the tap there and weight 0 on the other three, of which
+// the last is pixel (0, 0) -- a cell the loaders stage from the slot like any other.  It only ever meets weight 0, but 0 x NaN
+// is a NaN in every voxel of the patch, so the cell has to exist and hold zeros: `cells` first positions, `pitch` words apart.
+__global__ void zero_first_cells_kernel(float* __restrict__ out, int cells, size_t pitch, int cw) {
+    for (int i = threadIdx.x; i < cells * cw; i += blockDim.x) out[(size_t)(i / cw) * pitch + i % cw] = 0.0f;
+}
+
 // The fp32 source maps of a sweep as [view][C / 8][h * w][8] in p.workspace (for the window kernel's gather path, planesweep_window.hip)
 int pack_channel_last_g8(const SweepParams& p, hipStream_t stream) {
     PackArgs pa = {};
@@ -1244,9 +1252,14 @@ static void segments(int D, long tiles, int& dseg, int& nseg) {
 #endif
 static bool wants_channel_last(int D, int elem_bytes) { return elem_bytes == 2 || D >= D3D_CL_MIN_PLANES; }
 
+// the aggregation templates exist for 2, 4 and 6 source views (launch_tiled): the one that serves n_src of them
+static int template_views(int n_src) { return n_src <= 2 ? 2 : n_src <= 4 ? 4 : 6; }
+
+// One slot per view of the template, not per source: see zero_first_cells_kernel.  (The query does not know the mode; the
+// one-source templates of the warp and the pair pass use the first of two slots.)
 size_t tiled_workspace_bytes(int n_src, int C, int D, int h, int w, int elem_bytes) {
     if (C % 8 != 0 || n_src > 6 || n_src < 1 || !wants_channel_last(D, elem_bytes)) return 0;
-    return (size_t)n_src * C * h * w * elem_bytes;
+    return (size_t)template_views(n_src) * C * h * w * elem_bytes;
 }
 
 #ifndef D3D_SHALLOW_PLANES
@@ -1291,7 +1304,7 @@ static int launch_one(const SweepParams& p, hipStream_t stream) {
 #ifdef D3D_EXPERIMENTS
         if (const char* e = getenv("D3D_TILED_CL")) use_cl = atoi(e) != 0;
 #endif
-        const size_t bytes = (size_t)p.n_src * p.C * p.h * p.w * sizeof(T);
+        const size_t bytes = (size_t)NSRC * p.C * p.h * p.w * sizeof(T);
         if (use_cl && p.workspace && p.workspace_bytes >= bytes) {
             PackArgs pa = {};
             for (int i = 0; i < p.n_src; ++i) pa.src[i] = p.feats[i + 1];
@@ -1299,6 +1312,12 @@ static int launch_one(const SweepParams& p, hipStream_t stream) {
             hipLaunchKernelGGL((pack_channel_last_kernel<CH, T>), dim3((unsigned)ceil_div(plane * (CW / 4), 256), p.n_src * a.ngroups),
                                dim3(256), 0, stream, pa, a.ngroups, plane, reinterpret_cast<float*>(p.workspace));
             D3D_LAUNCH_CHECK("pack_channel_last_kernel launch");
+            if (p.n_src < NSRC) {
+                hipLaunchKernelGGL(zero_first_cells_kernel, dim3(1), dim3(256), 0, stream,
+                                   reinterpret_cast<float*>(p.workspace) + (size_t)p.n_src * a.ngroups * plane * CW,
+                                   (NSRC - p.n_src) * a.ngroups, (size_t)plane * CW, CW);
+                D3D_LAUNCH_CHECK("zero_first_cells_kernel launch");
+            }
             a.cl = reinterpret_cast<const float*>(p.workspace);
         }
         // the fp16 loaders only read the channel-last copy (2-byte planar gathers would be VMEM-issue bound)

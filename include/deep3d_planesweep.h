@@ -181,9 +181,12 @@ int d3d_variance_volume_cl8_h16(const float* const* feats, const float* proj34, 
                                 d3d_stream_t stream);
 
 /* The same volume with fp16 STORAGE (BASELINE config 5): feats[i] and out are IEEE half tensors of the shapes
- * above; projections, depth and every product / sum stay fp32, the result is rounded once (RNE).  With a
- * workspace of d3d_sweep_workspace_bytes(..., 2) bytes and C % 16 == 0, up to 6 source views run on the LDS-ring
- * kernel with fp16 ring cells; otherwise on the direct-gather kernel. */
+ * above; projections, depth and every product / sum stay fp32, the result is rounded once (RNE).  All three depth
+ * modes.  The LDS-ring kernel (fp16 ring cells of 16 channels) takes C % 16 == 0 with 1 .. 6 source views, and only
+ * with a workspace of d3d_sweep_workspace_bytes(..., 2) bytes: its loaders read nothing but the channel-last copy
+ * they make there.  Every other call -- C not a multiple of 16 (the direct kernel then walks 8, 4 or 1 channels at a
+ * time), 7 .. D3D_MAX_VIEWS - 1 source views, a null or short workspace -- runs on the direct-gather kernel: the
+ * fp32 one with fp16 loads and one rounding store, so its volume is the fp32 direct kernel's rounded once. */
 int d3d_variance_volume_f16(const void* const* feats, const float* proj34, const float* depth, int depth_mode,
                             int n_views, int C, int D, int h, int w, void* out, void* workspace,
                             size_t workspace_bytes, d3d_stream_t stream);
