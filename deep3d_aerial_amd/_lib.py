@@ -216,6 +216,12 @@ SIGNATURES = {
     "d3d_texture_local_sweeps": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _i, _vp, ctypes.POINTER(_i), _vp],
     "d3d_texture_local_chart": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp],
     "d3d_texture_local_apply": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _vp, _vp],
+    "d3d_mesh_subdivide_measure": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _i, _d, _vp, _vp],
+    "d3d_mesh_subdivide_scratch_bytes": ([ctypes.c_longlong, ctypes.c_longlong], _sz),
+    "d3d_mesh_subdivide_plan": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _d, _vp, _sz, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp],
+    "d3d_mesh_subdivide_emit": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp,
+                                ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
 }
 
 

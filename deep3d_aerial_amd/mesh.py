@@ -132,10 +132,13 @@ loop has become manifold, and no other loop has changed.  Integer atomics only, 
 Order in clean, build_and_write and the command line: removal, hole closing, smoothing (the smoothing relaxes the fans), then
 decimation (a vertex on a closed hole is no longer fixed, so the collapse is free around it).
 
+Subdivision (subdivide.py states the rule; csrc/mesh_subdivide.hip), off by default: with --subdivide PX
+build_and_write splits every edge longer than PX pixels in a view that sees it, after the decimation and before the refinement.
+
     python -m deep3d_aerial_amd.mesh --mvs MVS_FOLDER --out mesh.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax --voxel S
         [--trunc T] [--min_views 2] [--conf_threshold 0.2] [--views_per_batch N]
         [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L] [--close_holes N]
-        [--decimate R] [--target_faces N] [--decimate_max_rounds K]
+        [--decimate R] [--target_faces N] [--decimate_max_rounds K] [--subdivide PX] [--subdivide_rounds R]
     python -m deep3d_aerial_amd.mesh --clean IN.ply --out OUT.ply [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L]
         [--close_holes N] [--decimate R] [--target_faces N] [--decimate_max_rounds K]
 """
@@ -840,6 +843,14 @@ def add_arguments(ap, prefix=""):
     ap.add_argument("--%sviews_per_batch" % prefix, type=int, default=None, help="views per integration call (default: all)")
     add_clean_arguments(ap, prefix)
     add_decimate_arguments(ap, prefix)
+    add_subdivide_arguments(ap, prefix)
+
+
+def add_subdivide_arguments(ap, prefix=""):
+    """The subdivision step as flags (--<prefix>subdivide PX, --<prefix>subdivide_rounds R); off unless PX is given."""
+    from . import subdivide as _subdivide
+
+    _subdivide.add_arguments(ap, prefix + "subdivide_", edge_flag="--%ssubdivide" % prefix, tolerance=False)
 
 
 def add_decimate_arguments(ap, prefix=""):
@@ -864,10 +875,15 @@ def add_clean_arguments(ap, prefix=""):
 
 def settings_from_args(a, path, prefix=""):
     g = lambda k: getattr(a, prefix + k)
-    return {"path": path, "border": g("border"), "voxel": g("voxel"), "trunc": g("trunc"), "min_views": g("min_views"),
+    s = {"path": path, "border": g("border"), "voxel": g("voxel"), "trunc": g("trunc"), "min_views": g("min_views"),
             "conf_threshold": g("conf_threshold"), "views_per_batch": g("views_per_batch"), "min_faces": g("min_faces"),
             "spurious": g("spurious"), "smooth": g("smooth"), "smooth_lambda": g("smooth_lambda"), "decimate": g("decimate"),
             "target_faces": g("target_faces"), "decimate_max_rounds": g("decimate_max_rounds"), "close_holes": g("close_holes")}
+    if getattr(a, prefix + "subdivide_max_edge", None) is not None:   # the key is carried only when the flag is given
+        from . import subdivide as _subdivide
+
+        s["subdivide"] = {k: v for k, v in _subdivide.settings_from_args(a, prefix + "subdivide_").items() if k != "views_per_batch"}
+    return s
 
 
 def clean_settings(settings):
@@ -901,6 +917,18 @@ def decimate_requested(settings):
     return ratio < 1 or target_faces > 0
 
 
+def subdivide_settings(settings):
+    """The checked subdivision settings of a settings dict ("subdivide": {"max_edge", "rounds", "depth_tolerance"}, with the mesh
+    settings' own views_per_batch), or None when the key is missing: the step is off."""
+    if settings.get("subdivide") is None:
+        return None
+    from . import subdivide as _subdivide
+
+    if "views_per_batch" in settings["subdivide"]:
+        raise ValueError("subdivide: views_per_batch is the mesh settings' own")
+    return _subdivide.check_subdivide_settings(dict(settings["subdivide"], views_per_batch=settings.get("views_per_batch")))
+
+
 def check_args(ap, a, prefix=""):
     """The argument errors of the mesh settings, reported through ap.error."""
     if getattr(a, prefix + "border") is None:
@@ -913,6 +941,7 @@ def check_args(ap, a, prefix=""):
         clean_settings(s)
         close_holes_setting(s)
         decimate_settings(s)
+        subdivide_settings(s)
     except ValueError as e:
         ap.error("--%s*: %s" % (prefix, e))
 
@@ -926,10 +955,29 @@ def _decimate_and_report(v, f, ratio, target_faces, max_rounds):
     return v, f
 
 
-def build_and_write(views, settings, refine=None):
+def _subdivide_and_report(v, f, views, s, timings=None):
+    import time
+
+    from . import subdivide as _subdivide
+
+    if timings is not None:
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    info = {}
+    v, f = _subdivide.subdivide(v, f, views, info=info, **s)
+    if timings is not None:
+        torch.cuda.synchronize()
+        timings["mesh_subdivide_s"] = time.perf_counter() - t0
+    print("mesh subdivision: %s" % (_subdivide.summary_line(info) or "nothing to split"))
+    return v, f
+
+
+def build_and_write(views, settings, refine=None, timings=None):
     """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on (removal, hole closing, smoothing),
-    then decimate when it is on, then vertices = refine(vertices, faces) when a refinement is handed in (refine.refine_mesh bound to
-    its views: pipeline.write_mesh_of), and write_ply to settings["path"]: (vertices, faces) as written."""
+    then decimate when it is on, then subdivide against `views` when settings["subdivide"] is present (subdivide.subdivide; timings, a
+    dict, then gets mesh_subdivide_s), then vertices = refine(vertices, faces) when a refinement is handed in (refine.refine_mesh
+    bound to its views: pipeline.write_mesh_of), and write_ply to settings["path"]: (vertices, faces) as written."""
+    sub = subdivide_settings(settings)
     grid = MeshGrid(settings["border"], settings["voxel"])
     v, f = depth_to_mesh(views, grid, settings.get("trunc"), settings.get("min_views", DEFAULT_MIN_VIEWS),
                          settings.get("conf_threshold", DEFAULT_CONF), settings.get("views_per_batch"))
@@ -937,6 +985,8 @@ def build_and_write(views, settings, refine=None):
         v, f = clean(v, f, *clean_settings(settings), close_holes=close_holes_setting(settings))
     if decimate_requested(settings):
         v, f = _decimate_and_report(v, f, *decimate_settings(settings))
+    if sub is not None:
+        v, f = _subdivide_and_report(v, f, views, sub, timings)
     if refine is not None:
         v = refine(v, f)
     write_ply(settings["path"], v, f)
@@ -959,6 +1009,9 @@ def main(argv=None):
             check_decimate_settings(a.decimate, a.target_faces, a.decimate_max_rounds)
         except ValueError as e:
             ap.error("--clean: %s" % e)
+        if a.subdivide_max_edge is not None:
+            ap.error("--subdivide needs the views of --mvs: --clean IN.ply has none (python -m deep3d_aerial_amd.subdivide takes a mesh and "
+                     "an MVS folder)")
     else:
         check_args(ap, a)
     if not torch.cuda.is_available():

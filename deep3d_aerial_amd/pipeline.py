@@ -98,6 +98,10 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     reference image before it writes the PLY (refine.refine_mesh, after the decimation): the other ranks' images reach it in one
     gather (gather_refine_views), it refines alone, so the file still does not depend on the number of ranks; timings gets
     mesh_refine_s (a part of mesh_s).
+    With mesh["subdivide"] ({"max_edge", "rounds", "depth_tolerance"}; absent: off) rank 0 subdivides the mesh against the depth
+    maps and cameras it already holds, after the decimation and before the refinement (subdivide.subdivide): no image and no
+    collective, so the file still does not depend on the number of ranks; timings gets mesh_subdivide_s (a part of mesh_s).  The
+    refinement, the DSM from the mesh and the texture then see the subdivided mesh.
     texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad",
     "level" (optional: None, or the seam levelling's settings), "local" (the local seam levelling's), "smooth_views" and
     "outliers" (optional, likewise)}
@@ -112,6 +116,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         _mesh.clean_settings(mesh)
         _mesh.close_holes_setting(mesh)
         _mesh.decimate_settings(mesh)
+        _mesh.subdivide_settings(mesh)
         if mesh.get("refine") is not None:
             from . import refine as _refine
 
@@ -282,6 +287,7 @@ def gather_refine_views(own, all_maps, all_cams, n_views, rank=0, world_size=1, 
 def write_mesh_of(all_maps, all_cams, settings, timings=None, refine_views=None):
     """The mesh of every view (all_maps [n,2,H,W] depth and confidence, all_cams [n,2,4,4], by global view index), written to
     settings["path"] (mesh.build_and_write: cleaned when a clean step is on, then decimated when asked, then, with
+    settings["subdivide"] subdivided against the views: timings gets mesh_subdivide_s, a part of mesh_s; then, with
     settings["refine"] (refine.check_refine_settings) and refine_views (gather_refine_views), refined against the images:
     timings gets mesh_refine_s, a part of mesh_s).  Returns (vertices, faces) as written."""
     from . import mesh as _mesh
@@ -305,7 +311,7 @@ def write_mesh_of(all_maps, all_cams, settings, timings=None, refine_views=None)
             if timings is not None:
                 timings["mesh_refine_s"] = time.perf_counter() - r0
             return out
-    res = _mesh.build_and_write(views, settings, refine=refine)
+    res = _mesh.build_and_write(views, settings, refine=refine, timings=timings)
     torch.cuda.synchronize()
     if timings is not None:
         timings["mesh_s"] = time.perf_counter() - t0

@@ -734,6 +734,8 @@ def main(argv=None):
             print("rank 0/%d: orthophoto %s in %.2f s" % (world, a.ortho, tm["ortho_s"]))
         if a.mesh is not None and rank == 0:
             print("rank 0/%d: mesh %s in %.2f s" % (world, a.mesh, tm["mesh_s"]))
+            if "mesh_subdivide_s" in tm:
+                print("rank 0/%d: mesh subdivided against the views in %.2f s" % (world, tm["mesh_subdivide_s"]))
             if "mesh_refine_s" in tm:
                 print("rank 0/%d: mesh refined against the images in %.2f s" % (world, tm["mesh_refine_s"]))
         if a.texture is not None and rank == 0:

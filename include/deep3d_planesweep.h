@@ -1486,6 +1486,53 @@ int d3d_mesh_refine_relax(const float* weight, const float* d0, const unsigned c
 int d3d_mesh_refine_apply(const float* vertices, long long n_vertices, const double* frame, const unsigned char* active, const float* d,
                           float* out, d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.23 -- subdividing the surface mesh where the images outresolve it: every edge whose projection is longer than
+ * max_edge pixels in some view that sees both its ends is split at its midpoint, with conforming face splits (the rule is this
+ * project's, deep3d_aerial_amd/subdivide.py states it in full; it does not claim to match OpenMVS's RefineMesh subdivision).  A
+ * mesh is vertices [n_vertices, 3] fp32 and faces [n_faces, 3] int32, n_vertices < 2^31, 6 n_faces < 2^31; a face with an index
+ * outside 0 .. n_vertices - 1 or with a repeated index comes through unsplit (the caller refuses such a mesh).  edges [max_edges,
+ * 2] int32 and *n_edges (device int64) are d3d_mesh_decimate_edges' outputs for the same mesh: the undirected edges a < b in
+ * (a, b) lexicographic order; the passes read min(*n_edges, max_edges) of them.  A view is a d3d_mesh_view_t record (its
+ * confidence map is not read).  Every pointer is DEVICE memory.  All arithmetic is fp64 without contraction, rounded to fp32
+ * only where said; no atomics of any kind.
+ */
+/* d3d_mesh_subdivide_measure: MAX-MERGES into measure [max_edges] fp64 (all 0 before the first call).  View V sees an endpoint X
+ *   under d3d_ortho_select's candidate test: p = R X + t, q = K p, each row summed left to right, p2 > 0, q2 > 0, u = q0 / q2,
+ *   v = q1 / q2, 0 <= u <= W-1, 0 <= v <= H-1, the depth D at pixel (floor(v + 0.5), floor(u + 0.5)) is finite and > 0, and
+ *   p2 <= D * (1 + depth_tolerance).  A view that sees both ends of edge e contributes l2 = (ua - ub)^2 + (va - vb)^2; a
+ *   non-finite l2 rejects it.  measure[e] = max(measure[e], the largest l2): it does not depend on the order, the batching or
+ *   the split of the views.  Entries from *n_edges on are left as they are.  depth_tolerance finite, >= 0; n_views < 2^20. */
+int d3d_mesh_subdivide_measure(const float* vertices, long long n_vertices, const int* edges, const long long* n_edges, long long max_edges,
+                               const d3d_mesh_view_t* views, int n_views, double depth_tolerance, double* measure, d3d_stream_t stream);
+
+/* Scratch of d3d_mesh_subdivide_plan (0 for out-of-range sizes). */
+size_t d3d_mesh_subdivide_scratch_bytes(long long n_faces, long long max_edges);
+
+/* d3d_mesh_subdivide_plan: midpoint [max_edges, 3] fp32 = fp32((fp64(x_a) + fp64(x_b)) * 0.5) per component; mark [max_edges]
+ *   int32 = 1 when measure[e] > max_edge^2 and the midpoint differs from both ends (in some component); both 0 from *n_edges on.
+ *   rank [max_edges] int32 = the exclusive scan of mark: a split edge's new vertex is n_vertices + rank[e].  face_edge [n_faces,
+ *   3] int32 = the list index of edge (v_i, v_{i+1}) of face (v0, v1, v2), by binary search of (min, max); all three -1 for a
+ *   face that comes through unsplit.  child_count [n_faces] int32 = 1 + the marked edges of the face, child_offset its exclusive
+ *   scan.  totals [2] int64 = the split edges and the faces after the split.  max_edge finite, >= 1 (pixels). */
+int d3d_mesh_subdivide_plan(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* edges,
+                            const long long* n_edges, long long max_edges, const double* measure, double max_edge, void* scratch,
+                            size_t scratch_bytes, int* mark, int* rank, float* midpoint, int* face_edge, int* child_count, int* child_offset,
+                            long long* totals, d3d_stream_t stream);
+
+/* d3d_mesh_subdivide_emit: out_vertices [n_vertices + n_split, 3] = vertices, then midpoint[e] of every split edge at n_vertices
+ *   + rank[e].  out_faces [n_faces_out, 3]: the children of face f from child_offset[f] on, with m_i the new vertex of e_i =
+ *   (v_i, v_{i+1}) and the winding kept.  No edge split: (v0, v1, v2).  Only e_i split, (a, b, c) = (v_i, v_{i+1}, v_{i+2}):
+ *   (a, m_i, c), (m_i, b, c).  Only e_i unsplit, (a, b, c) alike, p = m_{i+1}, q = m_{i+2}: (p, c, q), then the quad a, b, p, q
+ *   cut by the shorter of a-p and b-q, squared lengths (dx^2 + dy^2) + dz^2 in fp64 on the fp32 positions, a tie going to the
+ *   diagonal that starts at the smaller of the indices a and b: a-p gives (a, b, p), (a, p, q); b-q gives (a, b, q), (b, p, q).
+ *   All three split: (v0, m0, m2), (m0, v1, m1), (m2, m1, v2), (m0, m1, m2).  n_split, n_faces_out: the plan's totals, read by
+ *   the host; n_vertices + n_split and 6 n_faces_out stay below 2^31.  The outputs are not the inputs. */
+int d3d_mesh_subdivide_emit(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const long long* n_edges,
+                            long long max_edges, const int* mark, const int* rank, const float* midpoint, const int* face_edge,
+                            const int* child_offset, long long n_split, long long n_faces_out, float* out_vertices, int* out_faces,
+                            d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
