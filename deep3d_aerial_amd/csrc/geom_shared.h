@@ -1,5 +1,6 @@
-// The primitives the geometry stages share (fusion, dsm, ortho, mesh, mesh_clean, mesh_decimate, texture); not part of the
-// public ABI.  The kernels behind the host functions declared here are in geom.hip.
+// The primitives the geometry stages share (fusion, dsm, ortho, mesh, mesh_clean, mesh_decimate, mesh_holes, mesh_refine,
+// mesh_subdivide, texture and its smooth, level, local and outliers passes); not part of the public ABI.  The kernels behind the
+// host functions declared here are in geom.hip.
 #pragma once
 #include "common.h"
 
@@ -141,6 +142,13 @@ __device__ __forceinline__ bool geom_face(const int* __restrict__ faces, long f,
     return DISTINCT ? ok && *a != *b && *b != *c && *c != *a : ok;
 }
 
+// Vertex i of an fp32 [n, 3] array as three doubles; the caller has checked 0 <= i < n.
+__device__ __forceinline__ void geom_load3(const float* __restrict__ v, long i, double* p) {
+    p[0] = (double)v[3 * i];
+    p[1] = (double)v[3 * i + 1];
+    p[2] = (double)v[3 * i + 2];
+}
+
 // The distinct edges of face (a, b, c): the pairs (a,b) (b,c) (c,a) with unequal ends, each unordered pair once.
 __device__ __forceinline__ int geom_face_edges(int a, int b, int c, int* x, int* y) {
     if (a == b && b == c) return 0;
@@ -201,14 +209,76 @@ __device__ __forceinline__ GeomPq geom_project(const View& V, double X0, double 
     return r;
 }
 
-// (u, v) of X in view V when it lies in front of the view and inside its image, else false.
-__device__ __forceinline__ bool ortho_uv(const d3d_ortho_view_t& V, double X0, double X1, double X2, double* u, double* v, double* p2) {
+// (u, v) of X in view V when it lies in front of the view (p2 > 0, q2 > 0) and inside its image (0 <= u <= W - 1,
+// 0 <= v <= H - 1, both ends included), else false; *p2 is the depth along the view's axis.  A NaN fails every test.
+template <typename View>
+__device__ __forceinline__ bool geom_uv(const View& V, double X0, double X1, double X2, double* u, double* v, double* p2) {
     const GeomPq r = geom_project(V, X0, X1, X2);
     if (!(r.p2 > 0.0 && r.q2 > 0.0)) return false;
     *u = r.q0 / r.q2;
     *v = r.q1 / r.q2;
     *p2 = r.p2;
     return *u >= 0.0 && *u <= (double)(V.W - 1) && *v >= 0.0 && *v <= (double)(V.H - 1);
+}
+
+// The depth map of V at the pixel nearest to (u, v): (floor(v + 0.5), floor(u + 0.5)).  The caller has placed (u, v) inside the
+// image (geom_uv) and checked V.depth, so the clamp only guards the load.  The test on the value (finite, > 0, p2 <= D tol1,
+// with or without a slack) stays with the caller: as a predicate here it moved the callers' machine code.
+template <typename View>
+__device__ __forceinline__ float geom_depth_at(const View& V, double u, double v) {
+    const int px = min(max((int)floor(u + 0.5), 0), V.W - 1), py = min(max((int)floor(v + 0.5), 0), V.H - 1);
+    return V.depth[(long)py * V.W + px];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// the colour of an RGBA8 image at (u, v)
+// ---------------------------------------------------------------------------------------------------------------------------
+// The bilinear blend of four RGBA8 taps, per channel (R, G, B = bits 0, 8, 16) in fp64 and not rounded: the weights
+// w00 = (1 - fx)(1 - fy), w10 = fx (1 - fy), w01 = (1 - fx) fy, w11 = fx fy, the sum ((w00 t00 + w10 t10) + w01 t01) + w11 t11.
+__device__ __forceinline__ void geom_blend(unsigned t00, unsigned t10, unsigned t01, unsigned t11, double fx, double fy, double (&t)[3]) {
+    const double w00 = (1.0 - fx) * (1.0 - fy), w10 = fx * (1.0 - fy), w01 = (1.0 - fx) * fy, w11 = fx * fy;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const int sh = 8 * ch;
+        t[ch] = w00 * (double)((t00 >> sh) & 255u) + w10 * (double)((t10 >> sh) & 255u) + w01 * (double)((t01 >> sh) & 255u) +
+                w11 * (double)((t11 >> sh) & 255u);
+    }
+}
+
+// The bilinear tap of a W x H RGBA8 image at (u, v) (ortho.py "Colour"): x0 = floor(u) clamped to 0 .. W - 1, fx = u - floor(u)
+// (of the unclamped floor), x1 = min(x0 + 1, W - 1), the same in y, then geom_blend.  rgba is not null, W, H >= 1.
+__device__ __forceinline__ void geom_tap(const unsigned* __restrict__ rgba, int W, int H, double u, double v, double (&t)[3]) {
+    const double fu = floor(u), fv = floor(v);
+    const double fx = u - fu, fy = v - fv;
+    const int x0 = (int)fmin(fmax(fu, 0.0), (double)(W - 1)), y0 = (int)fmin(fmax(fv, 0.0), (double)(H - 1));
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+    const unsigned t00 = rgba[(long)y0 * W + x0], t10 = rgba[(long)y0 * W + x1];
+    const unsigned t01 = rgba[(long)y1 * W + x0], t11 = rgba[(long)y1 * W + x1];
+    geom_blend(t00, t10, t01, t11, fx, fy, t);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// view keys and sorted key lists
+// ---------------------------------------------------------------------------------------------------------------------------
+// key = (bits(fp32(s)) << 32) | id for a score s >= 0 (the caller has checked that it is finite): keys order as (s, id), the
+// smallest wins.  geom_key_id is the id again.
+__device__ __forceinline__ long long geom_view_key(double s, int id) {
+    return ((long long)__float_as_uint((float)s) << 32) | (long long)(unsigned)id;
+}
+
+__device__ __forceinline__ int geom_key_id(long long key) { return (int)(unsigned)key; }
+
+// Inserts k into the sorted list c (increasing, padded with `empty`, the largest key) and drops the largest; a key the list
+// already holds is dropped instead.  Every index is a compile-time constant after unrolling.
+template <int N>
+__device__ __forceinline__ void geom_list_insert(long long (&c)[N], long long k, long long empty) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        k = k == c[i] ? empty : k;
+        const long long lo = k < c[i] ? k : c[i];
+        k = k < c[i] ? c[i] : k;
+        c[i] = lo;
+    }
 }
 
 }  // namespace d3d

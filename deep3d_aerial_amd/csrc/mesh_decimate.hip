@@ -31,11 +31,6 @@ constexpr unsigned DQ_HASH = 2654435761u;
 
 // The passes use a face of three distinct indices in range: geom_face<true> (mesh.py refuses any other; here it is ignored,
 // and dropped by faces).
-__device__ __forceinline__ void dq_load(const float* __restrict__ v, long i, double* p) {
-    p[0] = (double)v[3 * i];
-    p[1] = (double)v[3 * i + 1];
-    p[2] = (double)v[3 * i + 2];
-}
 
 // nrm = (p1 - p0) x (p2 - p0)
 __device__ __forceinline__ void dq_normal(const double* p0, const double* p1, const double* p2, double* nrm) {
@@ -121,9 +116,9 @@ __global__ __launch_bounds__(DQ_BLOCK) void dq_quadric_kernel(const float* __res
     for (int o = foff[v]; o < o1; ++o) {
         const long f = finc[o];
         double p0[3], p1[3], p2[3], nrm[3];
-        dq_load(vertices, faces[3 * f], p0);
-        dq_load(vertices, faces[3 * f + 1], p1);
-        dq_load(vertices, faces[3 * f + 2], p2);
+        geom_load3(vertices, faces[3 * f], p0);
+        geom_load3(vertices, faces[3 * f + 1], p1);
+        geom_load3(vertices, faces[3 * f + 2], p2);
         dq_normal(p0, p1, p2, nrm);
         const double len = sqrt((nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2]);
         if (!(len > 0.0)) continue;
@@ -185,9 +180,9 @@ __device__ __forceinline__ bool dq_flips(const float* __restrict__ vertices, con
         const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
         if (i0 == other || i1 == other || i2 == other) continue;
         double p0[3], p1[3], p2[3], n0[3], n1[3];
-        dq_load(vertices, i0, p0);
-        dq_load(vertices, i1, p1);
-        dq_load(vertices, i2, p2);
+        geom_load3(vertices, i0, p0);
+        geom_load3(vertices, i1, p1);
+        geom_load3(vertices, i2, p2);
         dq_normal(p0, p1, p2, n0);
         double* moved = i0 == v ? p0 : (i1 == v ? p1 : p2);
         moved[0] = t[0], moved[1] = t[1], moved[2] = t[2];
@@ -215,8 +210,8 @@ __global__ __launch_bounds__(DQ_BLOCK) void dq_candidates_kernel(const float* __
         double q[10], xa[3], xb[3], x[3];
 #pragma unroll
         for (int i = 0; i < 10; ++i) q[i] = quadric[10l * a + i] + quadric[10l * b + i];
-        dq_load(vertices, a, xa);
-        dq_load(vertices, b, xb);
+        geom_load3(vertices, a, xa);
+        geom_load3(vertices, b, xb);
         if (fa || fb) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) x[i] = fa ? xa[i] : xb[i];

@@ -112,12 +112,6 @@ __global__ __launch_bounds__(MH_BLOCK) void mh_bad_kernel(const int* __restrict_
 // ---------------------------------------------------------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void mh_load(const float* __restrict__ v, long i, double* p) {
-    p[0] = (double)v[3 * i];
-    p[1] = (double)v[3 * i + 1];
-    p[2] = (double)v[3 * i + 2];
-}
-
 // out += u x w
 __device__ __forceinline__ void mh_add_cross(const double* u, const double* w, double* out) {
     out[0] += u[1] * w[2] - u[2] * w[1];
@@ -149,12 +143,12 @@ __global__ __launch_bounds__(MH_BLOCK) void mh_plan_kernel(const float* __restri
                 break;
             }
             double xa[3], xb[3], p0[3], p1[3], p2[3];
-            mh_load(vertices, a, xa);
-            mh_load(vertices, b, xb);
+            geom_load3(vertices, a, xa);
+            geom_load3(vertices, b, xb);
             mh_add_cross(xa, xb, A);
-            mh_load(vertices, f0, p0);
-            mh_load(vertices, f1, p1);
-            mh_load(vertices, f2, p2);
+            geom_load3(vertices, f0, p0);
+            geom_load3(vertices, f1, p1);
+            geom_load3(vertices, f2, p2);
             const double u[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]}, w[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
             mh_add_cross(u, w, N);
             S[0] += xa[0];

@@ -36,7 +36,7 @@ constexpr int RF_HALF = 2;                     // the patch is (2 RF_HALF + 1)^2
 constexpr int RF_SIDE = 2 * RF_HALF + 1;
 constexpr int RF_POINTS = RF_SIDE * RF_SIDE;   // N = 25
 constexpr int RF_QMAX = 3060;                  // 4 * 3 * 255: the sum of the three channels in quarter grey levels
-constexpr long long RF_EMPTY = 0x7fffffffffffffffll;
+constexpr long long RF_EMPTY = TX_EMPTY;              // the lists hold view keys, as the texture's do
 
 struct RfFrame {
     double n[3], t1[3], t2[3];
@@ -106,25 +106,14 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_frames_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------------------
 // view lists
 // ---------------------------------------------------------------------------------------------------------------------------
-// Inserts k into the sorted list c (increasing, padded with RF_EMPTY) and drops the largest; a key the list already holds is
-// dropped instead.  Every index is a compile-time constant after unrolling.
-__device__ __forceinline__ void rf_insert(long long (&c)[RF_VIEWS], long long k) {
-#pragma unroll
-    for (int i = 0; i < RF_VIEWS; ++i) {
-        k = k == c[i] ? RF_EMPTY : k;
-        const long long lo = k < c[i] ? k : c[i];
-        k = k < c[i] ? c[i] : k;
-        c[i] = lo;
-    }
-}
-
 __global__ __launch_bounds__(RF_BLOCK) void rf_views_kernel(const float* __restrict__ vertices, long n, const double* __restrict__ frame,
                                                             const unsigned char* __restrict__ active,
                                                             const d3d_ortho_view_t* __restrict__ views, int n_views, double tol1, double slack,
                                                             long long* __restrict__ list) {
     const long v = (long)blockIdx.x * RF_BLOCK + threadIdx.x;
     if (v >= n || !active[v]) return;
-    const double X[3] = {(double)vertices[3 * v], (double)vertices[3 * v + 1], (double)vertices[3 * v + 2]};
+    double X[3];
+    geom_load3(vertices, v, X);
     const double nrm[3] = {frame[9 * v], frame[9 * v + 1], frame[9 * v + 2]};
     long long c[RF_VIEWS];
 #pragma unroll
@@ -133,17 +122,16 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_views_kernel(const float* __restr
         const d3d_ortho_view_t& V = views[vi];
         if (!V.depth || V.W < 1 || V.H < 1) continue;
         double u, w, p2;
-        if (!ortho_uv(V, X[0], X[1], X[2], &u, &w, &p2)) continue;
+        if (!geom_uv(V, X[0], X[1], X[2], &u, &w, &p2)) continue;
         const double dx = V.C[0] - X[0], dy = V.C[1] - X[1], dz = V.C[2] - X[2];
         const double dot = (nrm[0] * dx + nrm[1] * dy) + nrm[2] * dz;
         if (!(dot > 0.0)) continue;
-        const int px = min(max((int)floor(u + 0.5), 0), V.W - 1), py = min(max((int)floor(w + 0.5), 0), V.H - 1);
-        const float D = V.depth[(long)py * V.W + px];
+        const float D = geom_depth_at(V, u, w);
         if (!(isfinite(D) && D > 0.0f && p2 <= (double)D * tol1 + slack)) continue;
         const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
         const double s = 1.0 - dot / dist;
         if (!isfinite(s)) continue;
-        rf_insert(c, ((long long)__float_as_uint((float)s) << 32) | (long long)(unsigned)V.id);
+        geom_list_insert(c, geom_view_key(s, V.id), RF_EMPTY);
     }
 #pragma unroll
     for (int i = 0; i < RF_VIEWS; ++i) list[(long)RF_VIEWS * v + i] = c[i];
@@ -152,23 +140,10 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_views_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------------------------------------
 // match
 // ---------------------------------------------------------------------------------------------------------------------------
-// ortho's bilinear tap (ortho.hip, texture_outliers.hip to_tap, restated: those files are left alone) at (u, v), not rounded,
-// then q = clamp(floor(4 ((tR + tG) + tB) + 0.5), 0, 3060).
+// The bilinear tap at (u, v), not rounded (geom_tap), then q = clamp(floor(4 ((tR + tG) + tB) + 0.5), 0, 3060).
 __device__ __forceinline__ int rf_grey(const unsigned* __restrict__ rgba, int W, int H, double u, double v) {
-    const double fu = floor(u), fv = floor(v);
-    const double fx = u - fu, fy = v - fv;
-    const int x0 = (int)fmin(fmax(fu, 0.0), (double)(W - 1)), y0 = (int)fmin(fmax(fv, 0.0), (double)(H - 1));
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    const unsigned t00 = rgba[(long)y0 * W + x0], t10 = rgba[(long)y0 * W + x1];
-    const unsigned t01 = rgba[(long)y1 * W + x0], t11 = rgba[(long)y1 * W + x1];
-    const double w00 = (1.0 - fx) * (1.0 - fy), w10 = fx * (1.0 - fy), w01 = (1.0 - fx) * fy, w11 = fx * fy;
     double t[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const int sh = 8 * ch;
-        t[ch] = w00 * (double)((t00 >> sh) & 255u) + w10 * (double)((t10 >> sh) & 255u) + w01 * (double)((t01 >> sh) & 255u) +
-                w11 * (double)((t11 >> sh) & 255u);
-    }
+    geom_tap(rgba, W, H, u, v, t);
     return (int)fmin(fmax(floor(4.0 * ((t[0] + t[1]) + t[2]) + 0.5), 0.0), (double)RF_QMAX);
 }
 
@@ -179,10 +154,11 @@ struct RfCam {
     int W, H;
 };
 
-// The view of a key in the call's table when it has an image: false otherwise.
+// The view of a key in the call's table when it has an image: false otherwise.  (to_view's rule, texture_outliers.hip, with its
+// own lookup: through a shared helper, in any of three forms, rf_match_kernel's machine code moved)
 __device__ __forceinline__ bool rf_cam(const d3d_ortho_view_t* __restrict__ views, int n_views, long long key, RfCam* C) {
     if (key == RF_EMPTY) return false;
-    const int vi = tx_find(views, n_views, (int)(unsigned)key);
+    const int vi = tx_find(views, n_views, geom_key_id(key));
     if (vi < 0) return false;
     const d3d_ortho_view_t* V = views + vi;
     if (!(V->rgba && V->W >= 1 && V->H >= 1)) return false;
@@ -317,7 +293,8 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_match_kernel(const float* __restr
     if (sweep) {
         RfFrame F;
         rf_load_frame(frame, v, &F);
-        const double X[3] = {(double)vertices[3 * v], (double)vertices[3 * v + 1], (double)vertices[3 * v + 2]};
+        double X[3];
+        geom_load3(vertices, v, X);
         mask = rf_hypothesis(X, F, key, views, n_views, (double)(k - reach) * step, spacing, Tv, q0_lds + threadIdx.x, z);
     }
     // a pair is used when it is valid at every hypothesis
@@ -377,7 +354,8 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_match_kernel(const float* __restr
     if (two) {
         RfFrame F;
         rf_load_frame(frame, v, &F);
-        const double X[3] = {(double)vertices[3 * v], (double)vertices[3 * v + 1], (double)vertices[3 * v + 2]};
+        double X[3];
+        geom_load3(vertices, v, X);
         double zc[(2 * RF_MAX_REACH + 1) * RF_PAIRS];   // z of every (hypothesis, pair): indexed at run time, so it lives in private memory
         used = (1u << RF_PAIRS) - 1u;
 #pragma unroll 1

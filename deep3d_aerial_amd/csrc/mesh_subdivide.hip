@@ -12,7 +12,7 @@
 //          the counts places the children.  A one-lane kernel copies the two totals.
 // emit:    the input vertices come through first (one copy); one lane per edge writes the midpoint of a split edge at
 //          n_vertices + rank; one lane per face writes its children from its offset on.
-// ortho's candidate test (ortho.hip) is restated here: that file is left alone.
+// The candidate test is ortho's, from geom_shared.h: geom_uv, then geom_depth_at under the same comparison.
 // No atomics at all; every float result is a fixed-order fp64 computation without contraction, so nothing depends on the order
 // the lanes run in, and a maximum does not depend on view order, batching or rank split.
 #include <climits>
@@ -32,29 +32,12 @@ __device__ __forceinline__ long long ms_edge_count(const long long* __restrict__
     return ne < 0 ? 0 : (ne > max_edges ? max_edges : ne);
 }
 
-__device__ __forceinline__ void ms_load(const float* __restrict__ v, long i, double (&p)[3]) {
-    p[0] = (double)v[3 * i];
-    p[1] = (double)v[3 * i + 1];
-    p[2] = (double)v[3 * i + 2];
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // measure
 // ---------------------------------------------------------------------------------------------------------------------------
-// (u, v) of X in view V when it lies in front of the view and inside its image (ortho_uv for a d3d_mesh_view_t), else false.
-__device__ __forceinline__ bool ms_uv(const d3d_mesh_view_t& V, const double (&X)[3], double* u, double* v, double* p2) {
-    const GeomPq r = geom_project(V, X[0], X[1], X[2]);
-    if (!(r.p2 > 0.0 && r.q2 > 0.0)) return false;
-    *u = r.q0 / r.q2;
-    *v = r.q1 / r.q2;
-    *p2 = r.p2;
-    return *u >= 0.0 && *u <= (double)(V.W - 1) && *v >= 0.0 && *v <= (double)(V.H - 1);
-}
-
-// The depth test at the pixel of (u, v), which ms_uv has placed inside the image: the clamp only guards the load.
+// The depth test at the pixel of (u, v), which geom_uv has placed inside the image.
 __device__ __forceinline__ bool ms_unhidden(const d3d_mesh_view_t& V, double u, double v, double p2, double tol1) {
-    const int px = min(max((int)floor(u + 0.5), 0), V.W - 1), py = min(max((int)floor(v + 0.5), 0), V.H - 1);
-    const float D = V.depth[(long)py * V.W + px];
+    const float D = geom_depth_at(V, u, v);
     return isfinite(D) && D > 0.0f && p2 <= (double)D * tol1;
 }
 
@@ -67,15 +50,15 @@ __global__ __launch_bounds__(MS_BLOCK) void ms_measure_kernel(const float* __res
     const int a = edges[2 * e], b = edges[2 * e + 1];
     if (a < 0 || a >= n || b < 0 || b >= n) return;   // not this mesh's list
     double XA[3], XB[3];
-    ms_load(vertices, a, XA);
-    ms_load(vertices, b, XB);
+    geom_load3(vertices, a, XA);
+    geom_load3(vertices, b, XB);
     double best = measure[e];
     for (int vi = 0; vi < n_views; ++vi) {
         const d3d_mesh_view_t& V = views[vi];
         if (!V.depth || V.W < 1 || V.H < 1) continue;
         double ua, va, pa, ub, vb, pb;
-        if (!ms_uv(V, XA, &ua, &va, &pa)) continue;
-        if (!ms_uv(V, XB, &ub, &vb, &pb)) continue;
+        if (!geom_uv(V, XA[0], XA[1], XA[2], &ua, &va, &pa)) continue;
+        if (!geom_uv(V, XB[0], XB[1], XB[2], &ub, &vb, &pb)) continue;
         if (!ms_unhidden(V, ua, va, pa, tol1)) continue;
         if (!ms_unhidden(V, ub, vb, pb, tol1)) continue;
         const double du = ua - ub, dv = va - vb;

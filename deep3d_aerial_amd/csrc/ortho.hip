@@ -12,7 +12,8 @@
 //         with a corner at p2 <= 0 or q2 <= 0 stays a candidate: culling only skips work.
 //         Then one workgroup per tile walks the set bits (wave-uniform); each lane projects its cell, gathers D and keeps
 //         its best key in registers; one min-merge into `key` at the end.
-// colorize: per cell, the winner's (u, v) again and a bilinear sample of its RGBA8 copy.
+// colorize: per cell, the winner's (u, v) again and a bilinear sample of its RGBA8 copy (geom_blend; (u, v) is inside the image,
+//           so the tap indices need no clamp from below).
 // No atomics: a key is a minimum, so any batching or split of the views gives the same bits.
 #include <cmath>
 #include <cstdint>
@@ -115,14 +116,13 @@ __global__ __launch_bounds__(ORTHO_BLOCK) void ortho_select_kernel(const float* 
             if (!live) continue;
             const d3d_ortho_view_t& V = views[vi];
             double u, v, p2;
-            if (!ortho_uv(V, X0, X1, X2, &u, &v, &p2)) continue;
-            const int px = min(max((int)floor(u + 0.5), 0), V.W - 1), py = min(max((int)floor(v + 0.5), 0), V.H - 1);
-            const float D = V.depth[(long)py * V.W + px];
+            if (!geom_uv(V, X0, X1, X2, &u, &v, &p2)) continue;
+            const float D = geom_depth_at(V, u, v);
             if (!(isfinite(D) && D > 0.0f && p2 <= (double)D * tol1)) continue;
             const double dx = X0 - V.C[0], dy = X1 - V.C[1], dz = X2 - V.C[2];
             const double s = (dx * dx + dy * dy) / (dz * dz);
             if (!isfinite(s)) continue;
-            const long long k = ((long long)__float_as_uint((float)s) << 32) | (long long)(unsigned)V.id;
+            const long long k = geom_view_key(s, V.id);
             best = k < best ? k : best;
         }
     }
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(ORTHO_BLOCK) void ortho_colorize_kernel(const float
     if (c >= (long)g.W * g.H) return;
     const long long k = key[c];
     if (k == ORTHO_EMPTY) return;
-    const int id = (int)(unsigned)(k & 0xffffffffll);
+    const int id = geom_key_id(k);
     int slot = -1;
     for (int q = 0; q < n_views; ++q)   // wave-uniform loop over this call's records
         if (views[q].id == id) slot = q;
@@ -147,22 +147,20 @@ __global__ __launch_bounds__(ORTHO_BLOCK) void ortho_colorize_kernel(const float
     const int i = (int)(c / g.W), j = (int)(c - (long)i * g.W);
     const d3d_ortho_view_t& V = views[slot];
     double u, v, p2;
-    if (!ortho_uv(V, ortho_x(g, j), ortho_y(g, i), (double)h, &u, &v, &p2)) return;   // the key came from another raster
+    if (!geom_uv(V, ortho_x(g, j), ortho_y(g, i), (double)h, &u, &v, &p2)) return;   // the key came from another raster
     const double fu = floor(u), fv = floor(v);
     const double fx = u - fu, fy = v - fv;
     const int x0 = min((int)fu, V.W - 1), y0 = min((int)fv, V.H - 1);
     const int x1 = min(x0 + 1, V.W - 1), y1 = min(y0 + 1, V.H - 1);
     const unsigned t00 = V.rgba[(long)y0 * V.W + x0], t10 = V.rgba[(long)y0 * V.W + x1];
     const unsigned t01 = V.rgba[(long)y1 * V.W + x0], t11 = V.rgba[(long)y1 * V.W + x1];
-    const double w00 = (1.0 - fx) * (1.0 - fy), w10 = fx * (1.0 - fy), w01 = (1.0 - fx) * fy, w11 = fx * fy;
+    double s[3];
+    geom_blend(t00, t10, t01, t11, fx, fy, s);
     unsigned out = 255u << 24;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        const int sh = 8 * ch;
-        const double s = w00 * (double)((t00 >> sh) & 255u) + w10 * (double)((t10 >> sh) & 255u) + w01 * (double)((t01 >> sh) & 255u) +
-                         w11 * (double)((t11 >> sh) & 255u);
-        const double r = fmin(fmax(floor(s + 0.5), 0.0), 255.0);
-        out |= (unsigned)r << sh;
+        const double r = fmin(fmax(floor(s[ch] + 0.5), 0.0), 255.0);
+        out |= (unsigned)r << (8 * ch);
     }
     rgba[c] = out;
     view_out[c] = id;

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(TX_BLOCK) void tx_rects_kernel(const float* __restr
     if (f < m) {
         const long long k = key[f];
         c = chart[f];
-        const int slot = k != TX_EMPTY && c >= 0 && c < n_charts ? tx_find(cams, n_cams, (int)(unsigned)k) : -1;
+        const int slot = k != TX_EMPTY && c >= 0 && c < n_charts ? tx_find(cams, n_cams, geom_key_id(k)) : -1;
         double u[3], v[3];
         if (slot >= 0 && tx_face(vertices, faces, f, n, &F) && tx_corner_uv(cams[slot], F, u, v)) {
             const d3d_ortho_view_t& V = cams[slot];

@@ -2,9 +2,9 @@
 // (deep3d_aerial_amd/texture.py states it, include/deep3d_planesweep.h too); it does not claim to match OpenMVS's TextureMesh.
 //
 // colours:  one lane per face, looping over the slots of its candidate list.  The lanes of a wave hold neighbouring faces, whose
-//           lists mostly name the same views, so the 16 four-byte gathers of a slot (four bilinear taps, ortho's, restated here:
-//           ortho.hip is left alone) fall into the same image; the 128-byte cand rows and 64-byte col rows are strided across
-//           the wave instead.  The view is found by bisection (tx_find), the corners are projected per view (tx_corner_uv).
+//           lists mostly name the same views, so the 16 four-byte gathers of a slot (four bilinear taps, geom_tap) fall into the
+//           same image; the 128-byte cand rows and 64-byte col rows are strided across the wave instead.  The view is found by
+//           bisection (tx_find), the corners are projected per view (tx_corner_uv).
 //           The word of a slot depends on its face, key and view alone, so batches and ranks fill disjoint slots of one col.
 //           Built with -DD3D_COLORS_PER_SLOT the pass is one lane per (face, slot) instead, which coalesces the rows and
 //           scatters the gathers: the build tools/texture_bench.py --variant_library times beside this one.
@@ -26,24 +26,6 @@ namespace d3d {
 constexpr int TO_K = TX_CANDIDATES;
 constexpr int TO_QMAX = 1020;   // four times 255: a channel in quarter grey levels
 
-// ortho's bilinear tap (ortho.hip, ortho.py "Colour") at (u, v), not rounded: x0 = floor(u), fx = u - x0, the taps clamped to
-// the image, ((w00 c00 + w10 c10) + w01 c01) + w11 c11 per channel in fp64.
-__device__ __forceinline__ void to_tap(const d3d_ortho_view_t& V, double u, double v, double (&t)[3]) {
-    const double fu = floor(u), fv = floor(v);
-    const double fx = u - fu, fy = v - fv;
-    const int x0 = (int)fmin(fmax(fu, 0.0), (double)(V.W - 1)), y0 = (int)fmin(fmax(fv, 0.0), (double)(V.H - 1));
-    const int x1 = min(x0 + 1, V.W - 1), y1 = min(y0 + 1, V.H - 1);
-    const unsigned t00 = V.rgba[(long)y0 * V.W + x0], t10 = V.rgba[(long)y0 * V.W + x1];
-    const unsigned t01 = V.rgba[(long)y1 * V.W + x0], t11 = V.rgba[(long)y1 * V.W + x1];
-    const double w00 = (1.0 - fx) * (1.0 - fy), w10 = fx * (1.0 - fy), w01 = (1.0 - fx) * fy, w11 = fx * fy;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const int sh = 8 * ch;
-        t[ch] = w00 * (double)((t00 >> sh) & 255u) + w10 * (double)((t10 >> sh) & 255u) + w01 * (double)((t01 >> sh) & 255u) +
-                w11 * (double)((t11 >> sh) & 255u);
-    }
-}
-
 // The colour word of face F in view V (texture.py "Colour of a face in a candidate view"): false when a corner does not project.
 __device__ __forceinline__ bool to_word(const d3d_ortho_view_t& V, const TxFace& F, int* word_out) {
     double u[3], v[3];
@@ -55,7 +37,7 @@ __device__ __forceinline__ bool to_word(const d3d_ortho_view_t& V, const TxFace&
                           ((4.0 * v[2] + v[0]) + v[1]) / 6.0};
     double t[4][3];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) to_tap(V, su[s], sv[s], t[s]);
+    for (int s = 0; s < 4; ++s) geom_tap(V.rgba, V.W, V.H, su[s], sv[s], t[s]);
     unsigned word = 1u << 30;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -69,7 +51,7 @@ __device__ __forceinline__ bool to_word(const d3d_ortho_view_t& V, const TxFace&
 // The view of a key in the call's table when it has an image, else null.
 __device__ __forceinline__ const d3d_ortho_view_t* to_view(const d3d_ortho_view_t* __restrict__ views, int n_views, long long key) {
     if (key == TX_EMPTY) return nullptr;
-    const int vi = tx_find(views, n_views, (int)(unsigned)key);
+    const int vi = tx_find(views, n_views, geom_key_id(key));
     if (vi < 0) return nullptr;
     const d3d_ortho_view_t* V = views + vi;
     return V->rgba && V->W >= 1 && V->H >= 1 ? V : nullptr;
@@ -110,13 +92,6 @@ __global__ __launch_bounds__(TX_BLOCK) void to_colors_kernel(const float* __rest
     if (tx_face(vertices, faces, i / TO_K, n, &F) && to_word(*V, F, &word)) col[i] = word;
 }
 #endif
-
-// The sum of x over the wave's lanes, in every lane.
-__device__ __forceinline__ int to_wave_sum(int x) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
 
 __global__ __launch_bounds__(TX_BLOCK) void to_vote_kernel(const long long* cand, const int* __restrict__ col, long m, int T,
                                                            long long* cand_out, int* __restrict__ rejected, int* __restrict__ counts) {
@@ -194,7 +169,7 @@ __global__ __launch_bounds__(TX_BLOCK) void to_vote_kernel(const long long* cand
         changed = first != key[0] ? 1 : 0;
         rejected[f] = (int)out_mask;
     }
-    const int sums[4] = {to_wave_sum(tested), to_wave_sum(changed), to_wave_sum(removed), to_wave_sum(kept_all)};
+    const int sums[4] = {wave_sum(tested), wave_sum(changed), wave_sum(removed), wave_sum(kept_all)};
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)

@@ -63,9 +63,10 @@ __device__ __forceinline__ bool tx_view_key(const d3d_ortho_view_t& V, const TxF
     const double dot = nrm[0] * (V.C[0] - g[0]) + nrm[1] * (V.C[1] - g[1]) + nrm[2] * (V.C[2] - g[2]);
     if (!(dot > 0.0)) return false;
     double ua, va, ub, vb, uc, vc, p2;
-    if (!ortho_uv(V, F.a[0], F.a[1], F.a[2], &ua, &va, &p2)) return false;
-    if (!ortho_uv(V, F.b[0], F.b[1], F.b[2], &ub, &vb, &p2)) return false;
-    if (!ortho_uv(V, F.c[0], F.c[1], F.c[2], &uc, &vc, &p2)) return false;
+    if (!geom_uv(V, F.a[0], F.a[1], F.a[2], &ua, &va, &p2)) return false;
+    if (!geom_uv(V, F.b[0], F.b[1], F.b[2], &ub, &vb, &p2)) return false;
+    if (!geom_uv(V, F.c[0], F.c[1], F.c[2], &uc, &vc, &p2)) return false;
+    // the centroid has not been tested against the image, so ug + 0.5 is clamped before the floor: not geom_depth_at's rule
     const GeomPq r = geom_project(V, g[0], g[1], g[2]);
     const double ug = r.q0 / r.q2, vg = r.q1 / r.q2;
     const int px = min(max((int)floor(fmin(fmax(ug + 0.5, 0.0), (double)V.W)), 0), V.W - 1);
@@ -76,7 +77,7 @@ __device__ __forceinline__ bool tx_view_key(const d3d_ortho_view_t& V, const TxF
     if (!(A != 0.0)) return false;
     const double s = 1.0 / A;
     if (!isfinite(s)) return false;
-    *key = ((long long)__float_as_uint((float)s) << 32) | (long long)(unsigned)V.id;
+    *key = geom_view_key(s, V.id);
     return true;
 }
 

@@ -3,7 +3,7 @@
 //
 // candidates: the selection's cull (tx_cull) and its per-view tests (tx_view_key), one workgroup per block of 256 faces.  Each
 //             lane owns a face and keeps its TX_CANDIDATES smallest keys, sorted, in registers; a new key goes through a fully
-//             unrolled compare-exchange chain (ts_insert), so no index into the list is a runtime value.
+//             unrolled compare-exchange chain (geom_list_insert), so no index into the list is a runtime value.
 // merge:      one lane per face inserts the keys of one list into the other.
 // smooth:     per round a propose and a commit launch, one lane per face.  Propose counts, per candidate, the weighted
 //             neighbours of another id (a walk over the three corner rows of the vertex -> face CSR, one 4-byte gather of
@@ -24,18 +24,6 @@ namespace d3d {
 
 constexpr int TS_K = TX_CANDIDATES;
 constexpr int TS_READ = 8;   // rounds between two reads of the commit counts
-
-// Inserts k into the sorted list c (increasing, padded with TX_EMPTY) and drops the largest; a key the list already holds is
-// dropped instead.  Every index is a compile-time constant after unrolling.
-__device__ __forceinline__ void ts_insert(long long (&c)[TS_K], long long k) {
-#pragma unroll
-    for (int i = 0; i < TS_K; ++i) {
-        k = k == c[i] ? TX_EMPTY : k;
-        const long long lo = k < c[i] ? k : c[i];
-        k = k < c[i] ? c[i] : k;
-        c[i] = lo;
-    }
-}
 
 __device__ __forceinline__ void ts_load(const long long* __restrict__ cand, long f, long long (&c)[TS_K]) {
 #pragma unroll
@@ -65,7 +53,7 @@ __global__ __launch_bounds__(TX_BLOCK) void ts_candidates_kernel(const float* __
             const int vi = __builtin_amdgcn_readfirstlane(w * 64 + __builtin_ctzll(bits));
             bits &= bits - 1;
             long long k;
-            if (live && tx_view_key(views[vi], T, tol1, &k)) ts_insert(c, k);
+            if (live && tx_view_key(views[vi], T, tol1, &k)) geom_list_insert(c, k, TX_EMPTY);
         }
     }
     if (live) ts_store(cand, f, c);
@@ -78,15 +66,13 @@ __global__ __launch_bounds__(TX_BLOCK) void ts_merge_kernel(const long long* a, 
     ts_load(a, f, c);
     ts_load(b, f, d);
 #pragma unroll
-    for (int i = 0; i < TS_K; ++i) ts_insert(c, d[i]);
+    for (int i = 0; i < TS_K; ++i) geom_list_insert(c, d[i], TX_EMPTY);
     ts_store(out, f, c);   // after both rows are read: out may be a or b
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // smoothing
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ts_id(long long key) { return (int)(unsigned)key; }
-
 // label 0 and the first candidate's id for a face of three distinct indices with a candidate; -1 and -1 otherwise.
 __global__ __launch_bounds__(TX_BLOCK) void ts_init_kernel(const long long* __restrict__ cand, const int* __restrict__ faces, long m,
                                                            long long n, int* __restrict__ label, int* __restrict__ cur_id) {
@@ -96,7 +82,7 @@ __global__ __launch_bounds__(TX_BLOCK) void ts_init_kernel(const long long* __re
     const long long k0 = cand[(long)TS_K * f];
     const bool has = geom_face<true>(faces, f, n, &a, &b, &c) && k0 != TX_EMPTY;
     label[f] = has ? 0 : -1;
-    cur_id[f] = has ? ts_id(k0) : -1;
+    cur_id[f] = has ? geom_key_id(k0) : -1;
 }
 
 // The rows of face f's corners in the vertex -> face CSR, clipped to the arrays: visit(g) for every entry g != f in 0 .. m - 1.
@@ -132,7 +118,7 @@ __global__ __launch_bounds__(TX_BLOCK) void ts_propose_kernel(const long long* _
     int id[TS_K], cnt[TS_K];
 #pragma unroll
     for (int k = 0; k < TS_K; ++k) {
-        id[k] = ts_id(key[k]);
+        id[k] = geom_key_id(key[k]);
         cnt[k] = 0;
     }
     ts_walk(f, m, a, b, c, face_offset, face_index, [&](int g) {
@@ -181,7 +167,7 @@ __global__ __launch_bounds__(TX_BLOCK) void ts_commit_kernel(const long long* __
         if (take) {
             const int l = min(max(prop[f], 0), TS_K - 1);
             label[f] = l;
-            cur_id[f] = ts_id(cand[(long)TS_K * f + l]);
+            cur_id[f] = geom_key_id(cand[(long)TS_K * f + l]);
         }
     }
     const unsigned long long won = __ballot(take);
