@@ -6,6 +6,7 @@ operators raises, and every operator refuses tensors that are not on the GPU.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -15,218 +16,93 @@ CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.environ.get("D3D_LIBRARY") or os.path.join(CSRC, "libdeep3d_planesweep.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "deep3d_planesweep.h")
 
-ABI_VERSION = 11
-
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-_i64 = ctypes.c_int64
-_f = ctypes.c_float
-_d = ctypes.c_double
-_sz = ctypes.c_size_t
-
-# name -> argtypes, or (argtypes, restype) where the function does not return int.  Mirrors include/deep3d_planesweep.h.
-SIGNATURES = {
-    "d3d_version": [],
-    "d3d_last_error": ([], ctypes.c_char_p),
-    "d3d_compose_projections": [_vp, _i, _vp, _vp],
-    "d3d_debug_force_path": [_i],
-    "d3d_debug_dispatch_counts": [_vp, _i],
-    "d3d_build_flags": ([], ctypes.c_char_p),
-    "d3d_h16_format": ([], ctypes.c_char_p),
-    "d3d_compose_projections_f64": [_vp, _i, _vp, _vp],
-    "d3d_homo_warp_f64coord": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_sweep_workspace_bytes": ([_i, _i, _i, _i, _i, _i], _sz),
-    "d3d_sweep_workspace_bytes_for": ([_i, _i, _i, _i, _i, _i, _i], _sz),
-    "d3d_homo_warp": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    "d3d_variance_volume": [ctypes.POINTER(_vp), _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    "d3d_variance_volume_planes": [ctypes.POINTER(_vp), _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    "d3d_variance_volume_f16": [ctypes.POINTER(_vp), _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    "d3d_variance_volume_cl_h16": [ctypes.POINTER(_vp), _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    "d3d_variance_volume_cl8_h16": [ctypes.POINTER(_vp), _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    "d3d_pair_corr_mean": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    "d3d_weighted_corr": [ctypes.POINTER(_vp), _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    "d3d_softargmin_conf4": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "d3d_online_regress_update": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "d3d_online_regress_finalize": [_vp, _vp, _vp, _i64, _vp, _vp, _vp],
-    "d3d_depth_range_samples": [_vp, _i, _i, _f, _i, _i, _vp, _vp],
-    "d3d_resize_bilinear": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv3d_k3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv3d_k3_co8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv3d_k3_c8_h16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv3d_k3_zs_h16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv3d_k3_zs_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv3d_k3_c1_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_convtranspose3d_k3s2_zs_h16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_convtranspose3d_k3s2_zs_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3_zs_h16": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3_zs_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3_zs_bf16x3": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_avgpool2d_4_8": [_vp, _i, _i, _i, _vp, _vp, _vp],
-    "d3d_conv3x3_bias_border": [_vp, _vp, _i, _i, _i, _vp],
-    "d3d_conv2d_k1_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv1x1_context": [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3s2_zs_h16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3s2_zs_h16_batched": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _i64, _vp, _vp],
-    "d3d_conv2d_k3_wide_h16": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "d3d_slice_head_regress_h16": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "d3d_gru_cell_fused_h16": [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_gru_cell_fused_cl8_h16": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_weighted_corr_cl8_h16": [ctypes.POINTER(_vp), _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    "d3d_convtranspose2d_k3s2_zs_h16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3s2_zs_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_convtranspose2d_k3s2_zs_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_convtranspose2d_k4s2_zs_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k5s2_zs_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3s2_zs_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_convtranspose2d_k3s2_zs_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv3d_k3_cl_h16": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp],
-    "d3d_conv3d_k3_c1_cl_h16": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv3d_k3s2_cl_h16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_convtranspose3d_k3s2_cl_h16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp],
-    "d3d_conv2d_k3_zs_h16_gn": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp],
-    "d3d_conv2d_k3_wide_h16_gn": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp],
-    "d3d_convtranspose2d_k3s2_wide_h16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3_pair3_bf16x3": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "d3d_slice_tail_regress_h16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "d3d_slice_tail_regress_same_h16": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "d3d_conv3d_k3s2_zs_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_convtranspose3d_prob_cl_h16": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp],
-    "d3d_volume_planar_to_cl_h16": [_vp, _i, _sz, _vp, _vp],
-    "d3d_volume_cl_h16_to_planar": [_vp, _i, _sz, _vp, _vp],
-    "d3d_convtranspose3d_k3s2_co8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_convtranspose3d_k3s2": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv1x1_upskip": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3_stream": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv2d_k3": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_convtranspose2d_k3s2": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "d3d_conv_gemm_f32": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                          _i, _i, _i, _i, _i, ctypes.c_char_p, _vp, _vp],
-    "d3d_conv_fold_f32": [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
-                          ctypes.POINTER(ctypes.c_int), _i, ctypes.c_char_p, _vp, _vp],
-    "d3d_conv_fold_h16": [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
-                           ctypes.POINTER(ctypes.c_int), _i, ctypes.c_char_p, _vp, _vp],
-    "d3d_gru_gates": [_vp, _vp, _i, _i64, _vp, _vp, _vp],
-    "d3d_gru_update": [_vp, _vp, _vp, _i64, _vp, _vp],
-    "d3d_groupnorm_stats": [_vp, _i64, _i, _vp, _vp],
-    "d3d_gru_gates_gn": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, ctypes.c_float, _i, _vp, _vp, _vp],
-    "d3d_gru_update_gn": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, ctypes.c_float, _i, _vp, _vp],
-    "d3d_gru_reset_gn": [_vp, _vp, _vp, _vp, _vp, _i, _i64, ctypes.c_float, _i, _vp, _vp],
-    "d3d_gru_update_gates_gn": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, ctypes.c_float, _i, _vp, _vp],
-    "d3d_gru2_cell_gn_h16": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_softargmin_conf4_var": [_vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp],
-    "d3d_uncertainty_samples": [_vp, _vp, _i, _i, _i, _vp, _vp],
-    "d3d_pair_softmax_max": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "d3d_consistency_check": [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double), _i, _i, _i, _i, ctypes.c_double,
-                              _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_fusion_ref_init": [_vp, _vp, ctypes.POINTER(ctypes.c_double), _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "d3d_fusion_accumulate": [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double), _i, _i, _i, _i,
-                              ctypes.c_double, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_fusion_finalize": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
-    "d3d_fusion_points_scratch_bytes": ([_i, _i], _sz),
-    "d3d_fusion_mark_points": [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_double), _vp, _vp, _vp, _vp],
-    "d3d_fusion_gather_points": [_vp, _vp, ctypes.POINTER(_vp), _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_flip_rows": [ctypes.POINTER(_vp), _i, _i, _i, _vp, _vp],
-    "d3d_center_image_u8": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
-    "d3d_normals_from_depth": [_vp, ctypes.POINTER(_f), _i, _i, _i, _i, _vp, _vp, _vp],
-    "d3d_dsm_scratch_bytes": ([ctypes.c_longlong, _i, _i, _i], _sz),
-    "d3d_dsm_from_points": [_vp, ctypes.c_longlong, _d, _d, _d, _d, _d, _d, _i, _i, _i, _d, _i, _vp, _sz, _vp, _vp, _vp],
-    "d3d_dsm_fill_moving_average": [_vp, _vp, _i, _i, _i, _vp],
-    "d3d_dsm_mesh_scratch_bytes": ([ctypes.c_longlong, _i, _i], _sz),
-    "d3d_dsm_from_mesh": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _sz, _vp, _vp],
-    "d3d_ortho_scratch_bytes": ([_i, _i, _i], _sz),
-    "d3d_ortho_select": [_vp, _d, _d, _d, _d, _i, _i, _vp, _i, _d, _vp, _sz, _vp, _vp],
-    "d3d_ortho_colorize": [_vp, _d, _d, _d, _d, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
-    "d3d_mesh_scan_scratch_bytes": ([ctypes.c_longlong], _sz),
-    "d3d_mesh_mark": [_vp, _vp, _i, _i, _d, _vp, _vp],
-    "d3d_mesh_bricks": [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
-    "d3d_mesh_integrate": [_vp, _vp, _i, _vp, _i, _d, _d, _vp, _vp, _vp],
-    "d3d_mesh_count": [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_emit": [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_compact": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
-    "d3d_mesh_adjacency_scratch_bytes": ([ctypes.c_longlong, ctypes.c_longlong], _sz),
-    "d3d_mesh_adjacency": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _sz, _vp, _vp, _vp, _vp],
-    "d3d_mesh_components": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, ctypes.POINTER(_i), _vp],
-    "d3d_mesh_stats_scratch_bytes": ([ctypes.c_longlong], _sz),
-    "d3d_mesh_component_stats": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_filter_scratch_bytes": ([ctypes.c_longlong], _sz),
-    "d3d_mesh_filter": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_longlong, _d, _vp, _sz, _vp, _vp, _vp, _vp],
-    "d3d_mesh_smooth": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp],
-    "d3d_mesh_decimate_incidence_scratch_bytes": ([ctypes.c_longlong, ctypes.c_longlong], _sz),
-    "d3d_mesh_decimate_incidence": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _sz, _vp, _vp, _vp],
-    "d3d_mesh_decimate_quadrics": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
-    "d3d_mesh_decimate_edges_scratch_bytes": ([ctypes.c_longlong], _sz),
-    "d3d_mesh_decimate_edges": [_vp, _vp, ctypes.c_longlong, _vp, _sz, ctypes.c_longlong, _vp, _vp, _vp],
-    "d3d_mesh_decimate_candidates": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
-    "d3d_mesh_decimate_select_scratch_bytes": ([], _sz),
-    "d3d_mesh_decimate_select": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _sz, _vp, _vp],
-    "d3d_mesh_decimate_claim": [_vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp],
-    "d3d_mesh_decimate_apply": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_decimate_faces_scratch_bytes": ([ctypes.c_longlong], _sz),
-    "d3d_mesh_decimate_faces": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
-    "d3d_mesh_holes_scratch_bytes": ([ctypes.c_longlong], _sz),
-    "d3d_mesh_boundary": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_boundary_loops": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _vp],
-    "d3d_mesh_holes_plan": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
-                            _vp, _vp],
-    "d3d_mesh_holes_emit": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong,
-                            ctypes.c_longlong, _vp, _vp, _vp],
-    "d3d_texture_scratch_bytes": ([ctypes.c_longlong, _i], _sz),
-    "d3d_texture_select": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _d, _vp, _sz, _vp, _vp],
-    "d3d_texture_edges": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
-    "d3d_texture_charts": [_vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _vp],
-    "d3d_texture_rects": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _vp],
-    "d3d_texture_fill": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp, _vp],
-    "d3d_texture_empty": [_vp, ctypes.c_longlong, ctypes.c_uint, _vp],
-    "d3d_texture_texcoords": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp,
-                              _vp, _vp],
-    "d3d_texture_candidates_max": [],
-    "d3d_texture_candidates": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _d, _vp, _sz, _vp, _vp],
-    "d3d_texture_candidates_merge": [_vp, _vp, ctypes.c_longlong, _vp, _vp],
-    "d3d_texture_smooth_scratch_bytes": ([ctypes.c_longlong], _sz),
-    "d3d_texture_smooth": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _f, _f, _i, _vp, _sz, _vp, _vp, _vp,
-                           ctypes.POINTER(_i), _vp],
-    "d3d_texture_face_colors": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp],
-    "d3d_texture_outliers": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp],
-    "d3d_mesh_refine_views_max": [],
-    "d3d_mesh_refine_frames": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_refine_views": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _i, _d, _i, _d, _vp, _vp],
-    "d3d_mesh_refine_match": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _i, _i, _d, _d, ctypes.c_longlong, _d, _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_refine_relax": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _f, _i, _vp, _vp, _vp],
-    "d3d_mesh_refine_apply": [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp],
-    "d3d_texture_level_scratch_bytes": ([ctypes.c_longlong], _sz),
-    "d3d_texture_level_incidence": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp],
-    "d3d_texture_level_pairs": [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp,
-                                _vp, _vp],
-    "d3d_texture_level_csr": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, ctypes.c_longlong, _f, _vp, _vp, _vp, _vp],
-    "d3d_texture_level_samples": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp,
-                                  _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
-    "d3d_texture_level_solve": [_vp, _vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _f, _d, _i, _vp, _sz, _vp, ctypes.POINTER(_i),
-                                ctypes.POINTER(_i), _vp],
-    "d3d_texture_level_cover": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp,
-                                _vp],
-    "d3d_texture_level_apply": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong,
-                                _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp, _vp, _vp],
-    "d3d_texture_local_lds_words": ([], ctypes.c_longlong),
-    "d3d_texture_local_seams": [_vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp],
-    "d3d_texture_local_count": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _vp, _i, _i, _vp, _vp],
-    "d3d_texture_local_samples": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i,
-                                  _vp, _i, _i, _vp, _vp, _vp, _vp],
-    "d3d_texture_local_fold": [_vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp],
-    "d3d_texture_local_band": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _vp],
-    "d3d_texture_local_sweeps": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _i, _vp, ctypes.POINTER(_i), _vp],
-    "d3d_texture_local_chart": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp],
-    "d3d_texture_local_apply": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _vp, _i, _vp, _vp],
-    "d3d_mesh_subdivide_measure": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _i, _d, _vp, _vp],
-    "d3d_mesh_subdivide_scratch_bytes": ([ctypes.c_longlong, ctypes.c_longlong], _sz),
-    "d3d_mesh_subdivide_plan": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _d, _vp, _sz, _vp, _vp, _vp,
-                                _vp, _vp, _vp, _vp, _vp],
-    "d3d_mesh_subdivide_emit": [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp,
-                                ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
-}
-
 
 class LibraryMissing(RuntimeError):
     pass
+
+
+# the scalar types the header is written in; its typedefs (d3d_stream_t) join them as they are read
+_CTYPES = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "long long": ctypes.c_longlong,
+           "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def parse_header(text):
+    """The ABI a C header states, as ctypes: ({function: (argtypes, restype)}, {struct: ctypes.Structure subclass},
+    {D3D_* constant: int}).  A pure function of the text, for the subset of C that include/deep3d_planesweep.h is written in:
+    `#define D3D_NAME <integer>`, typedefs of a known type, `typedef struct { ... } name;` and prototypes of d3d_ functions.
+    Every pointer is a c_void_p, whatever it points to (the header cannot tell host from device memory); a `const char*`
+    return is a c_char_p.  Whatever else it meets is a ValueError that names the function or struct and the text."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"#\s*ifdef\s+__cplusplus.*?#\s*endif", " ", text, flags=re.S)   # extern "C" { and its }
+    types, protos, structs, consts = dict(_CTYPES), {}, {}, {}
+
+    def ctype(spec, where):
+        spec = " ".join(w for w in spec.replace("*", " * ").split() if w != "const")
+        if "*" not in spec and spec not in types:
+            raise ValueError("%s: unknown type %r" % (where, spec))
+        return ctypes.c_void_p if "*" in spec else types[spec]
+
+    def declarator(decl, where):
+        """`const float* depth` | `R[9]` -> (type text, name, array length or None)."""
+        m = re.fullmatch(r"\s*(.*?)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*", decl, flags=re.S)
+        if not m:
+            raise ValueError("%s: cannot read %r" % (where, " ".join(decl.split())))
+        return m.groups()
+
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(D3D_\w+)(.*)$", text, flags=re.M):
+        m = re.fullmatch(r"\s+\(?\s*(-?\d+)\s*\)?\s*", value)
+        if not m:
+            raise ValueError("#define %s: %r is not an integer" % (name, value.strip()))
+        consts[name] = int(m.group(1))
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def struct(m):
+        body, name = m.groups()
+        fields = []
+        for line in filter(None, (d.strip() for d in body.split(";"))):
+            decls = [declarator(d, name) for d in line.split(",")]
+            spec = decls[0][0]
+            if len(decls) > 1 and ("*" in spec or any(d[0] for d in decls[1:])):   # `float *a, *b`: the header has none
+                raise ValueError("%s: cannot read %r" % (name, line))
+            t = ctype(spec, "%s: %r" % (name, line))
+            fields += [(field, t * int(n) if n else t) for _, field, n in decls]
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+        return " "
+
+    text = re.sub(r"\btypedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        m = re.fullmatch(r"typedef (.+?) ?(\w+)", stmt)
+        if m:
+            types[m.group(2)] = ctype(m.group(1), "typedef " + m.group(2))
+            continue
+        m = re.fullmatch(r"(.+?) ?\b(d3d_\w+) ?\(([^()]*)\)", stmt)
+        if not m:
+            raise ValueError("cannot read the declaration %r" % stmt)
+        ret, name, params = m.groups()
+        args = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            spec, _, n = declarator(param, name)
+            if n:
+                raise ValueError("%s: array parameter %r" % (name, param.strip()))
+            args.append(ctype(spec, "%s(%s)" % (name, param.strip())))
+        protos[name] = (args, ctypes.c_char_p if ret.replace(" ", "") == "constchar*" else ctype(ret, name))
+    return protos, structs, consts
+
+
+def header_text(path=HEADER):
+    try:
+        with open(path) as f:
+            return f.read()
+    except OSError as e:
+        raise LibraryMissing("the header %s cannot be read: the binding is derived from it" % path) from e
+
+
+# One statement of the ABI: the header's.  SIGNATURES is name -> argtypes, or (argtypes, restype) where the function does
+# not return int; STRUCTS and CONSTANTS are what ortho / mesh / fuse / _runtime take their records and limits from.
+PROTOTYPES, STRUCTS, CONSTANTS = parse_header(header_text())
+SIGNATURES = {name: args if ret is ctypes.c_int else (args, ret) for name, (args, ret) in PROTOTYPES.items()}
+ABI_VERSION = CONSTANTS["D3D_ABI_VERSION"]
+ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP = (CONSTANTS["D3D_ERR_" + n] for n in ("INVALID_ARG", "UNSUPPORTED", "HIP"))
 
 
 def build(verbose=False):
@@ -263,9 +139,6 @@ def load():
         raise LibraryMissing("ABI version mismatch: library %d, binding %d" % (lib.d3d_version(), ABI_VERSION))
     _lib = lib
     return lib
-
-
-ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3
 
 
 def h16_format():
@@ -338,5 +211,5 @@ def kernel_code_sha256(symbol_prefix, path=None):
 def check(rc, what):
     if rc != 0:
         msg = load().d3d_last_error().decode("utf-8", "replace")
-        kind = {-1: "invalid argument", -2: "unsupported", -3: "HIP error"}.get(rc, "error %d" % rc)
+        kind = {ERR_INVALID_ARG: "invalid argument", ERR_UNSUPPORTED: "unsupported", ERR_HIP: "HIP error"}.get(rc, "error %d" % rc)
         raise RuntimeError("%s failed (%s): %s" % (what, kind, msg))

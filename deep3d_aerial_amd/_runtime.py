@@ -16,7 +16,8 @@ from . import _lib
 from . import config as _cfg
 from ._packing import _pack_fold, _pack_gemm, h16_dtype
 
-PER_PLANE, PER_PIXEL, AFFINE = 0, 1, 2   # depth modes of the sweep entry points (include/deep3d_planesweep.h)
+# depth modes of the sweep entry points (include/deep3d_planesweep.h)
+PER_PLANE, PER_PIXEL, AFFINE = (_lib.CONSTANTS["D3D_DEPTH_" + n] for n in ("PER_PLANE", "PER_PIXEL", "AFFINE"))
 
 # Which kernels served the calls so far: name -> count.  The model-level parity tests clear it, run a forward and assert that
 # the production kernels (tile convolutions, fused conv-GRU cell, channel-last volumes, window / ring sweeps) were the ones

@@ -27,7 +27,7 @@ from . import _geom, _lib
 from ._geom import ptr as _ptr, stream as _stream
 from .ops import _chk
 
-_CAM_DOUBLES = 94  # D3D_FUSION_CAM_DOUBLES
+_CAM_DOUBLES = _lib.CONSTANTS["D3D_FUSION_CAM_DOUBLES"]
 
 
 def camera_block(intrinsics_ref, extrinsics_ref, intrinsics_src, extrinsics_src):

@@ -104,7 +104,7 @@ Hole closing (close_holes(); csrc/mesh_holes.hip): every small
 one new vertex, off by default.  Named after the reference's nCloseHoles, but the rule is this project's; it does not claim to
 match OpenMVS / VCG.  All arithmetic is fp64 without contraction, rounded to fp32 only where said.
 1. Input.  vertices [n,3] fp32 and faces [m,3] int32, every face with three distinct indices in 0 .. n - 1 (anything else is
-   refused, as decimate refuses it).  max_edges is an integer: 0 means off, otherwise 3 <= max_edges <= HOLE_MAX_EDGES = 1024
+   refused, as decimate refuses it).  max_edges is an integer: 0 means off, otherwise 3 <= max_edges <= HOLE_MAX_EDGES (1024)
    (any other value is a ValueError).
 2. Boundary half-edges.  Face (a, b, c) has the directed edges a->b, b->c, c->a.  A directed edge is a boundary half-edge when
    exactly one face holds its undirected edge; its owner is that face.
@@ -158,7 +158,7 @@ DEFAULT_MIN_VIEWS = 2
 DEFAULT_SMOOTH_LAMBDA = 0.5
 DEFAULT_DECIMATE_MAX_ROUNDS = 1000   # a cap on host round trips, far above the rounds a target needs
 DECIMATE_HASH = 2654435761
-HOLE_MAX_EDGES = 1024                # the longest loop close_holes walks (D3D_MESH_HOLE_MAX_EDGES)
+HOLE_MAX_EDGES = _lib.CONSTANTS["D3D_MESH_HOLE_MAX_EDGES"]   # the longest loop close_holes walks
 BRICK = 8
 
 # the 6 Kuhn tetrahedra (positively oriented), the edges of a tetrahedron, the 16-case table (csrc/mesh.hip has the same)
@@ -171,17 +171,8 @@ TRI = ((), ((0, 1, 2),), ((0, 4, 3),), ((1, 2, 4), (1, 4, 3)), ((1, 3, 5),), ((0
 TYPE_CORNER = (1, 2, 4, 3, 5, 6, 7)
 
 
-class _GridRecord(ctypes.Structure):
-    """d3d_mesh_grid_t (include/deep3d_planesweep.h)."""
-    _fields_ = [("x_min", ctypes.c_double), ("y_min", ctypes.c_double), ("z_min", ctypes.c_double), ("voxel", ctypes.c_double),
-                ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("nz", ctypes.c_int), ("bx", ctypes.c_int), ("by", ctypes.c_int),
-                ("bz", ctypes.c_int)]
-
-
-class _ViewRecord(ctypes.Structure):
-    """d3d_mesh_view_t (include/deep3d_planesweep.h)."""
-    _fields_ = [("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3), ("K", ctypes.c_double * 9), ("depth", ctypes.c_void_p),
-                ("conf", ctypes.c_void_p), ("W", ctypes.c_int), ("H", ctypes.c_int)]
+_GridRecord = _lib.STRUCTS["d3d_mesh_grid_t"]   # d3d_mesh_grid_t, as include/deep3d_planesweep.h declares it
+_ViewRecord = _lib.STRUCTS["d3d_mesh_view_t"]   # d3d_mesh_view_t, likewise
 
 
 class MeshGrid(object):

@@ -30,7 +30,6 @@ batching, order or split of the views.
         [--image_root DIR] [--views_per_batch N]
 """
 import argparse
-import ctypes
 import math
 import os
 
@@ -46,11 +45,7 @@ MAX_ID = (1 << 31) - 2   # id + 1 must fit an int32 (the pipeline's exchange of 
 DEFAULT_TOLERANCE = 0.01
 
 
-class _ViewRecord(ctypes.Structure):
-    """d3d_ortho_view_t (include/deep3d_planesweep.h)."""
-    _fields_ = [("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3), ("K", ctypes.c_double * 9), ("C", ctypes.c_double * 3),
-                ("depth", ctypes.c_void_p), ("rgba", ctypes.c_void_p), ("W", ctypes.c_int), ("H", ctypes.c_int), ("id", ctypes.c_int),
-                ("pad", ctypes.c_int)]
+_ViewRecord = _lib.STRUCTS["d3d_ortho_view_t"]   # d3d_ortho_view_t, as include/deep3d_planesweep.h declares it
 
 
 def rgba_image(image):
