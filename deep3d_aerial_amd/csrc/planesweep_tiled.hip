@@ -99,14 +99,13 @@ struct TiledArgs {
     int tall;        // 1: the last patch column holds at most TW/2 real pixels per row and is swept in TALL patches (see the block decode)
     const float* cl;  // channel-last copy of the source maps [view][group][h*w][CH] (pack_channel_last_kernel), or null
     unsigned long long* tstats;  // debug timing (cycles, wave 0): [0] prologue [1] barrierA+write+barrierB [2] issue [3] compute [4] total
-    unsigned* stats;  // debug (D3D_TILED_STATS): [0] ring wgs [1] fallback wgs [2] sum m [3] sum nsteps [4] sum ring floats [5] overflow items
+    unsigned* stats;  // debug (D3D_TILED_STATS): [0] ring wgs [1] fallback wgs [2] sum m [3] sum nsteps [4] sum ring floats [5] staging items [6] of them inside one rectangle [7] plain (kind 0) [8] of [6] inside the image [9] of [6] clear of ring column 0 and row 0 [10] slots of a staging round with no item left
 };
 
 // LDS map (ints/floats):
-//   [zero cell 2*STRIDE][pmin DSEG_MAX][pmax DSEG_MAX][header 32][view constants 8*NSRC][unused 2*MAXSTEPS]
+//   [zero cell 2*STRIDE][pmin DSEG_MAX][pmax DSEG_MAX][header 32][view constants 8*NSRC]
 //   [plan table MAXSTEPS*NSRC*8][rect starts MAXSTEPS+4][positions per step MAXSTEPS][rect descriptors (MAXRECTS+1)*4][rings ...]
 // header: 0 mode (1 rings, 0 global gather) | 1 planes per step | 2 nsteps | 4+4i.. RW, RH, base, RW | RH << 8 | (base/4) << 16 per view
-//         | 28, 29 unused (zeroed by plan_tables)
 // plan entry (per step, view): wx0, wy0, ww, wh, ox, oy, ox - wx0, oy - wy0
 // rect descriptor (non-empty delta rectangles, grouped by step), 4 words:
 //   (rx + 1) | (ry + 1) << 16,  width | view << 12 | first position (cumulative within the step) << 16,
@@ -119,8 +118,7 @@ struct Lds {
     static constexpr int PMAX = PMIN + DSEG_MAX;
     static constexpr int HDR = PMAX + DSEG_MAX;
     static constexpr int VT = HDR + 32;                // per view: T0, T1, T2, -, RW, RH, row bytes, absolute ring base (view-major plane loop)
-    static constexpr int CNT = VT + 8 * NSRC;          // nothing reads this since the counter hand-offs were removed (dropping it moves DATA: DESIGN.md 8)
-    static constexpr int PLAN = CNT + 2 * MAXSTEPS;
+    static constexpr int PLAN = VT + 8 * NSRC;
     static constexpr int SST = PLAN + MAXSTEPS * NSRC * 8;
     static constexpr int STOT = SST + MAXSTEPS + 4;   // positions to stage per step
     static constexpr int RECTS = ((STOT + MAXSTEPS + 3) / 4) * 4;
@@ -247,6 +245,8 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
     {
         const int nblk = gridDim.x;
         const int per = nblk / 8;
+        // (Only when the XCDs get equal runs.  Ragged runs for every block count -- x * per + min(x, nblk % 8) -- were measured on
+        //  config 2, 7482 workgroups: the sweep fetches 3.3 times less from HBM and takes 5 % longer, profiles/loader_decode_ab.txt.)
         if (nblk % 8 == 0) b = (b % 8) * per + b / 8;
     }
     // Within an XCD's run, vertically adjacent patches come first: they share most of their source
@@ -630,9 +630,6 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
             ldsi[L::HDR + 1] = sp_sel;
             ldsi[L::HDR + 2] = nsteps_sel;
         }
-        // nothing reads these words since the counter hand-offs were removed; the stores stay until the CNT region goes
-        for (int i = lane; i < 2 * MAXSTEPS; i += 64) ldsi[L::CNT + i] = 0;
-        if (lane < 2) ldsi[L::HDR + 28 + lane] = 0;
     };
     if (wave == 0) plan_tables(0, NCAND1);
     __syncthreads();
@@ -731,13 +728,39 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
             if (dupc && dupr) *reinterpret_cast<f4*>(lds + dst + dupc + dupr) = x;
         }
     };
+    // A staging item that lies inside ONE rectangle (all but the items of the thin L-shaped deltas) is decoded once per wave:
+    // the descriptor and the view's ring geometry are wave-uniform, so they are unpacked in scalar registers and a lane is left
+    // with pos -> (cx, cy), its source offset (32 bits against a wave-uniform base) and its ring slot.  Same arithmetic per
+    // position as item(), so the rings hold the same bytes whichever path staged them.
+    // Whether all of the item lies inside the image and none of it in ring column 0 or ring row 0 is decided in scalar code too:
+    // kind 0: it does -- the loaded values are written as they are, once (meta = ring slot, or -1 past the end of the delta);
+    // kind 1: meta carries the ok | duplicate-column | duplicate-row flags and put() honours them (every generic item too).
+    // (Sparing the selects and the duplicate writes SEPARATELY -- most one-rectangle items are inside the image but meet ring
+    //  column 0 or row 0 -- cut 1.5 % more vector instructions and lost the time the decode had won: profiles/loader_decode_ab.txt.)
+    // Not in the shallow form (32 x 8 patches, sweeps of at most 16 planes): its staging is one first window per pass, and the
+    // 8-plane stage of the cascade ran 2 % slower with this path than without (profiles/loader_decode_ab.txt, section 6).
+    constexpr bool ONE_RECT = NPIXW <= 2;
+    struct Rects {   // lane rr < MAXRS: descriptor words of the step's rr-th rectangle and the ring geometry word of its view
+        int psv, d0, d1, d3, d7;
+    };
+    // 32-bit source offsets reach every channel of every position (planar: 4 * CH planes; channel-last: CW words per position)
+    const bool small32 = plane <= (size_t)0xffffffffu / (size_t)(CH * 4 > 64 ? CH * 4 : 64);
     f4 pf[PFD][Q];
     int pmeta[PFD], pgeo[PFD];
+    int pkind[PFD];   // wave-uniform
     auto write_round = [&]() {
 #pragma unroll
-        for (int j = 0; j < PFD; ++j)
+        for (int j = 0; j < PFD; ++j) {
+            if (pkind[j] == 0) {
+                if (pmeta[j] >= 0) {
 #pragma unroll
-            for (int q = 0; q < Q; ++q) put(pmeta[j], pgeo[j], q, pf[j][q]);
+                    for (int q = 0; q < Q; ++q) *reinterpret_cast<f4*>(lds + pmeta[j] + 4 * q) = pf[j][q];
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < Q; ++q) put(pmeta[j], pgeo[j], q, pf[j][q]);
+            }
+        }
     };
     // Loader waves: bring window(k) minus window(k-1) into the rings.
     const bool ltiming = D3D_STAMPS && a.tstats != nullptr && lw == 0;
@@ -749,37 +772,129 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
         const int rb = rfl(ldsi[L::SST + k]), re = rfl(ldsi[L::SST + k + 1]);
         const int Tn = rfl(ldsi[L::STOT + k]);
         const int nitems = (Tn + 63) >> 6;
-        // first positions of the step's (<= 4 per view) rects: one LDS read by MAXRS lanes, then wave-uniform copies
-        const int psv = (lane < re - rb) ? (int)((unsigned)ldsi[L::RECTS + 4 * (rb + min(lane, MAXRS - 1)) + 1] >> 16) : 0x7fffffff;
+        // the step's (<= 4 per view) rects, one per lane: first positions (wave-uniform copies for item()), and the
+        // descriptors the one-rectangle items read back with v_readlane
+        Rects R;
+        {
+            const bool have = lane < re - rb;
+            const int* e = ldsi + L::RECTS + 4 * (rb + min(lane, MAXRS - 1));
+            R.d1 = e[1];
+            R.psv = have ? (int)((unsigned)R.d1 >> 16) : 0x7fffffff;
+            if constexpr (ONE_RECT) {
+                R.d0 = e[0]; R.d3 = e[3];
+                R.d7 = ldsi[L::HDR + 4 + 4 * (have ? (R.d1 >> 12) & 0xf : 0) + 3];
+            } else {
+                R.d0 = R.d3 = R.d7 = 0;
+            }
+        }
+        const int psv = R.psv;
         int pst16[MAXRS];
 #pragma unroll
         for (int rr = 0; rr < MAXRS; ++rr) pst16[rr] = __builtin_amdgcn_readlane(psv, rr);
+        unsigned n_items = 0, n_one = 0, n_plain = 0, n_in = 0, n_nodup = 0, n_idle = 0;   // (D3D_TILED_STATS)
         for (int it0 = sw; it0 < nitems; it0 += snw * PFD) {
             long long tq1 = 0, tq2 = 0;
             if (ltiming) tq1 = clock64();
 #pragma unroll
             for (int j = 0; j < PFD; ++j) {
                 const int it = it0 + snw * j;
-                Item I = item(it < nitems ? it * 64 + lane : Tn, Tn, rb, pst16);
-                if (a.cl) {
+                int meta = -1, geo = 0, kind = 0;   // (no item left for this slot of the round: nothing to write)
+                f4 v[Q];
+                if (it < nitems) {
+                    const int el0 = it * 64;
+                    const int nlive = min(Tn - el0, 64);   // >= 1
+                    // no rectangle starts inside (el0, el0 + nlive): the live elements share the rectangle of el0
+                    const bool one = ONE_RECT && __ballot(psv > el0 && psv < el0 + nlive) == 0ull;
+                    if (D3D_STAMPS) { ++n_items; n_one += one ? 1 : 0; }
+                    if (one && small32) {
+                        const int rsel = max(__popcll(__ballot(psv <= el0)) - 1, 0);
+                        const int e0 = __builtin_amdgcn_readlane(R.d0, rsel), e1 = __builtin_amdgcn_readlane(R.d1, rsel);
+                        const int e6 = __builtin_amdgcn_readlane(R.d3, rsel), e7 = __builtin_amdgcn_readlane(R.d7, rsel);
+                        const int rx = (e0 & 0xffff) - 1, ry = (e0 >> 16) - 1;
+                        const int rwid = e1 & 0xfff, vi = (e1 >> 12) & 0xf, pst = (int)((unsigned)e1 >> 16);
+                        const int RWv = e7 & 0xff, RHv = (e7 >> 8) & 0xff, bs = (e7 >> 16) << 2;
+                        const int oc = e6 & 0xffff, orow = e6 >> 16;   // ring column / row of the rect origin (unwrapped)
+                        const bool live = lane < nlive;
+                        const int pos = (el0 - pst) + lane;
+                        const int cy = (int)(((float)pos + 0.5f) * __builtin_amdgcn_rcpf((float)max(rwid, 1)));
+                        const int cx = pos - (int)__mul24(cy, rwid);
+                        // rectangle rows the live elements cover (lane 0 is always live)
+                        const int cya = rfl(cy), cyb = __builtin_amdgcn_readlane(cy, nlive - 1);
+                        const bool inside = rx >= 0 && rx + rwid <= w && ry + cya >= 0 && ry + cyb < h;
+                        // ring column 0 / row 0 are met at the unwrapped coordinates 0 and RW / RH
+                        const bool dups = oc == 0 || (oc <= RWv && RWv < oc + rwid) || orow + cya == 0 ||
+                                          (orow + cya <= RHv && RHv <= orow + cyb);
+                        const int sx = rx + cx, sy = ry + cy;
+                        unsigned c = (unsigned)(oc + cx), r = (unsigned)(orow + cy);
+                        c = min(c, c - (unsigned)RWv);
+                        r = min(r, r - (unsigned)RHv);
+                        const int dst = bs + (int)__umul24(r, (unsigned)ring_row_floats<STRIDE>(RWv)) + (int)__umul24(c, (unsigned)STRIDE);
+                        bool ok = live;
+                        if (inside && !dups) {
+                            meta = live ? dst : -1;
+                        } else {
+                            if (!inside) ok = live && ((unsigned)sx < (unsigned)w) && ((unsigned)sy < (unsigned)h);
+                            meta = live ? (dst | (ok ? 1 << 20 : 0) | (c == 0 ? 1 << 21 : 0) | (r == 0 ? 1 << 22 : 0)) : -1;
+                            geo = e7 & 0xffff;
+                            kind = 1;
+                        }
+                        if (D3D_STAMPS) { n_plain += kind == 0 ? 1 : 0; n_in += inside ? 1 : 0; n_nodup += dups ? 0 : 1; }
+                        const unsigned soff = ok ? __umul24((unsigned)sy, (unsigned)w) + (unsigned)sx : 0u;
+                        if (a.cl) {
+                            const char* gb = reinterpret_cast<const char*>(a.cl + (size_t)(vi * a.ngroups + grp) * plane * CW);
+                            const f4* __restrict__ g = reinterpret_cast<const f4*>(gb + (size_t)(soff * (unsigned)(CW * 4)));
 #pragma unroll
-                    for (int q = 0; q < Q; ++q) pf[j][q] = reinterpret_cast<const f4*>(I.g)[q];
-                } else if (!F16) {   // planar fp32 maps (no workspace given); fp16 rings are only launched with the channel-last copy
+                            for (int q = 0; q < Q; ++q) v[q] = g[q];
+                        } else if (!F16) {
+                            long long dsel = 0;
 #pragma unroll
-                    for (int q = 0; q < Q; ++q) {
-                        const float* __restrict__ g = I.g + (size_t)(4 * q) * plane;
-                        pf[j][q][0] = g[0];
-                        pf[j][q][1] = g[plane];
-                        pf[j][q][2] = g[2 * plane];
-                        pf[j][q][3] = g[3 * plane];
+                            for (int i = 1; i < NSRC; ++i) dsel = (vi == i) ? fdelta[i] : dsel;
+                            const char* gb = reinterpret_cast<const char*>(p.feats[1]) + dsel + (size_t)c0 * plane * 4;
+#pragma unroll
+                            for (int q = 0; q < Q; ++q)
+#pragma unroll
+                                for (int kk = 0; kk < 4; ++kk)
+                                    v[q][kk] = *reinterpret_cast<const float*>(gb + (size_t)(4 * q + kk) * plane * 4 + (size_t)(soff * 4u));
+                        }
+                    } else {
+                        Item I = item(el0 + lane, Tn, rb, pst16);
+                        if (a.cl) {
+#pragma unroll
+                            for (int q = 0; q < Q; ++q) v[q] = reinterpret_cast<const f4*>(I.g)[q];
+                        } else if (!F16) {   // planar fp32 maps (no workspace given); fp16 rings are only launched with the channel-last copy
+#pragma unroll
+                            for (int q = 0; q < Q; ++q) {
+                                const float* __restrict__ g = I.g + (size_t)(4 * q) * plane;
+                                v[q][0] = g[0];
+                                v[q][1] = g[plane];
+                                v[q][2] = g[2 * plane];
+                                v[q][3] = g[3 * plane];
+                            }
+                        }
+                        meta = I.meta;
+                        geo = I.geo;
+                        kind = 1;
                     }
+                } else if (D3D_STAMPS) {
+                    ++n_idle;
                 }
-                pmeta[j] = I.meta;
-                pgeo[j] = I.geo;
+                pmeta[j] = meta;
+                pgeo[j] = geo;
+                pkind[j] = kind;
+#pragma unroll
+                for (int q = 0; q < Q; ++q) pf[j][q] = v[q];
             }
             if (ltiming) { tq2 = clock64(); lt_issue += tq2 - tq1; }
             write_round();
             if (ltiming) lt_write += clock64() - tq2;
+        }
+        if (D3D_STAMPS && a.stats && lane == 0) {
+            atomicAdd(a.stats + 5, n_items);
+            atomicAdd(a.stats + 6, n_one);
+            atomicAdd(a.stats + 7, n_plain);
+            atomicAdd(a.stats + 8, n_in);
+            atomicAdd(a.stats + 9, n_nodup);
+            atomicAdd(a.stats + 10, n_idle);
         }
     };
 
@@ -1325,16 +1440,16 @@ static int launch_one(const SweepParams& p, hipStream_t stream) {
     }
 #ifdef D3D_EXPERIMENTS
     if (getenv("D3D_TILED_STATS")) {  // debug only: synchronous, allocates
-        (void)hipMalloc(&a.stats, 8 * sizeof(unsigned) + 24 * sizeof(unsigned long long));
-        (void)hipMemset(a.stats, 0, 8 * sizeof(unsigned) + 24 * sizeof(unsigned long long));
-        a.tstats = reinterpret_cast<unsigned long long*>(a.stats + 8);
+        (void)hipMalloc(&a.stats, 12 * sizeof(unsigned) + 24 * sizeof(unsigned long long));
+        (void)hipMemset(a.stats, 0, 12 * sizeof(unsigned) + 24 * sizeof(unsigned long long));
+        a.tstats = reinterpret_cast<unsigned long long*>(a.stats + 12);
     }
 #endif
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(THREADSK), LDS_BYTES, stream, p, a);
     D3D_LAUNCH_CHECK("sweep_tiled_kernel launch");
 #ifdef D3D_EXPERIMENTS
     if (a.stats) {
-        unsigned hs[8];
+        unsigned hs[12];
         unsigned long long ht[24];
         (void)hipMemcpy(hs, a.stats, sizeof(hs), hipMemcpyDeviceToHost);
         (void)hipMemcpy(ht, a.tstats, sizeof(ht), hipMemcpyDeviceToHost);
@@ -1349,6 +1464,8 @@ static int launch_one(const SweepParams& p, hipStream_t stream) {
         fprintf(stderr, "[d3d tiled stats] CH=%d elem=%d wgs=%ld ring=%u fallback=%u mean_step_planes=%.2f mean_steps=%.2f mean_ring_positions=%.0f (cap %d) dseg=%d\n",
                 CH, (int)sizeof(T), nblk, hs[0], hs[1], hs[2] / (double)nblk, hs[3] / (double)nblk, hs[0] ? hs[4] / (double)hs[0] : 0.0,
                 a.cap_floats / L::STRIDE, a.dseg);
+        fprintf(stderr, "[d3d tiled stats] staging items per workgroup (all channel groups): %.1f | inside one rectangle %.1f (inside the image %.1f, clear of ring column 0 and row 0 %.1f, both %.1f) | slots with no item left %.1f\n",
+                hs[5] / (double)nblk, hs[6] / (double)nblk, hs[8] / (double)nblk, hs[9] / (double)nblk, hs[7] / (double)nblk, hs[10] / (double)nblk);
         (void)hipFree(a.stats);
     }
 #endif
