@@ -1,6 +1,6 @@
 // The primitives the geometry stages share (fusion, dsm, ortho, mesh, mesh_clean, mesh_decimate, mesh_holes, mesh_refine,
-// mesh_subdivide, texture and its smooth, level, local and outliers passes); not part of the public ABI.  The kernels behind the
-// host functions declared here are in geom.hip.
+// mesh_subdivide, mesh_collapse, texture and its smooth, level, local and outliers passes); not part of the public ABI.  The
+// kernels behind the host functions declared here are in geom.hip.
 #pragma once
 #include "common.h"
 
@@ -148,6 +148,56 @@ __device__ __forceinline__ void geom_load3(const float* __restrict__ v, long i, 
     p[1] = (double)v[3 * i + 1];
     p[2] = (double)v[3 * i + 2];
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// the validity tests of an edge collapse (mesh_decimate, mesh_collapse)
+// ---------------------------------------------------------------------------------------------------------------------------
+// nrm = (p1 - p0) x (p2 - p0)
+__device__ __forceinline__ void dq_normal(const double* p0, const double* p1, const double* p2, double* nrm) {
+    const double ux = p1[0] - p0[0], uy = p1[1] - p0[1], uz = p1[2] - p0[2];
+    const double vx = p2[0] - p0[0], vy = p2[1] - p0[1], vz = p2[2] - p0[2];
+    nrm[0] = uy * vz - uz * vy;
+    nrm[1] = uz * vx - ux * vz;
+    nrm[2] = ux * vy - uy * vx;
+}
+
+// The vertices the sorted neighbour rows offset[a] .. offset[a + 1] and offset[b] .. offset[b + 1] share, by a merge.
+__device__ __forceinline__ int dq_shared(const long long* __restrict__ offset, const int* __restrict__ nbr, int a, int b) {
+    const long long a1 = offset[a + 1], b1 = offset[b + 1];
+    int shared = 0;
+    for (long long i = offset[a], j = offset[b]; i < a1 && j < b1;) {
+        const int u = nbr[i], w = nbr[j];
+        shared += u == w ? 1 : 0;
+        i += u <= w ? 1 : 0;
+        j += w <= u ? 1 : 0;
+    }
+    return shared;
+}
+
+// The faces of row v that do not hold `other`, with v (and other) at position t: true when one of them turns over or collapses.
+__device__ __forceinline__ bool dq_flips(const float* __restrict__ vertices, const int* __restrict__ faces, const int* __restrict__ foff,
+                                         const int* __restrict__ finc, int v, int other, const double* t) {
+    const int o1 = foff[v + 1];
+    for (int o = foff[v]; o < o1; ++o) {
+        const long f = finc[o];
+        const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+        if (i0 == other || i1 == other || i2 == other) continue;
+        double p0[3], p1[3], p2[3], n0[3], n1[3];
+        geom_load3(vertices, i0, p0);
+        geom_load3(vertices, i1, p1);
+        geom_load3(vertices, i2, p2);
+        dq_normal(p0, p1, p2, n0);
+        double* moved = i0 == v ? p0 : (i1 == v ? p1 : p2);
+        moved[0] = t[0], moved[1] = t[1], moved[2] = t[2];
+        dq_normal(p0, p1, p2, n1);
+        const double dot = (n0[0] * n1[0] + n0[1] * n1[1]) + n0[2] * n1[2];
+        if (!(dot > 0.0)) return true;
+    }
+    return false;
+}
+
+// n_vertices and n_faces in the range the collapse passes index with int32: 0 .. 2^31 - 1 vertices, 6 n_faces < 2^31.
+inline bool dq_sizes_ok(long long n, long long m) { return n >= 0 && n < (1ll << 31) && m >= 0 && 6 * m < (1ll << 31); }
 
 // The distinct edges of face (a, b, c): the pairs (a,b) (b,c) (c,a) with unequal ends, each unordered pair once.
 __device__ __forceinline__ int geom_face_edges(int a, int b, int c, int* x, int* y) {

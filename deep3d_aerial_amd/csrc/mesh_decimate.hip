@@ -30,16 +30,7 @@ constexpr int DQ_SELECT_GRID = 1024;   // workgroups of a histogram pass (grid-s
 constexpr unsigned DQ_HASH = 2654435761u;
 
 // The passes use a face of three distinct indices in range: geom_face<true> (mesh.py refuses any other; here it is ignored,
-// and dropped by faces).
-
-// nrm = (p1 - p0) x (p2 - p0)
-__device__ __forceinline__ void dq_normal(const double* p0, const double* p1, const double* p2, double* nrm) {
-    const double ux = p1[0] - p0[0], uy = p1[1] - p0[1], uz = p1[2] - p0[2];
-    const double vx = p2[0] - p0[0], vy = p2[1] - p0[1], vz = p2[2] - p0[2];
-    nrm[0] = uy * vz - uz * vy;
-    nrm[1] = uz * vx - ux * vz;
-    nrm[2] = ux * vy - uy * vx;
-}
+// and dropped by faces).  dq_normal, dq_shared, dq_flips and dq_sizes_ok are in geom_shared.h: mesh_collapse.hip uses them too.
 
 // q(x) = x^T Q x for the homogeneous x = (x, y, z, 1); q = (aa, ab, ac, ad, bb, bc, bd, cc, cd, dd).
 __device__ __forceinline__ double dq_eval(const double* q, double x, double y, double z) {
@@ -171,28 +162,6 @@ __global__ __launch_bounds__(DQ_BLOCK) void dq_edges_kernel(const long long* __r
 // ---------------------------------------------------------------------------------------------------------------------------
 // candidates
 // ---------------------------------------------------------------------------------------------------------------------------
-// The faces of row v that do not hold `other`, with v (and other) at position t: true when one of them turns over or collapses.
-__device__ __forceinline__ bool dq_flips(const float* __restrict__ vertices, const int* __restrict__ faces, const int* __restrict__ foff,
-                                         const int* __restrict__ finc, int v, int other, const double* t) {
-    const int o1 = foff[v + 1];
-    for (int o = foff[v]; o < o1; ++o) {
-        const long f = finc[o];
-        const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-        if (i0 == other || i1 == other || i2 == other) continue;
-        double p0[3], p1[3], p2[3], n0[3], n1[3];
-        geom_load3(vertices, i0, p0);
-        geom_load3(vertices, i1, p1);
-        geom_load3(vertices, i2, p2);
-        dq_normal(p0, p1, p2, n0);
-        double* moved = i0 == v ? p0 : (i1 == v ? p1 : p2);
-        moved[0] = t[0], moved[1] = t[1], moved[2] = t[2];
-        dq_normal(p0, p1, p2, n1);
-        const double dot = (n0[0] * n1[0] + n0[1] * n1[1]) + n0[2] * n1[2];
-        if (!(dot > 0.0)) return true;
-    }
-    return false;
-}
-
 __global__ __launch_bounds__(DQ_BLOCK) void dq_candidates_kernel(const float* __restrict__ vertices, const int* __restrict__ faces,
                                                                  const long long* __restrict__ offset, const int* __restrict__ nbr,
                                                                  const unsigned char* __restrict__ fixed, const int* __restrict__ foff,
@@ -242,15 +211,7 @@ __global__ __launch_bounds__(DQ_BLOCK) void dq_candidates_kernel(const float* __
         tx = (float)x[0], ty = (float)x[1], tz = (float)x[2];
         c32 = (float)dq_cost(q, x[0], x[1], x[2]);
         // (i) the link condition: exactly two common neighbours; (ii) the survivor keeps at least three neighbours
-        const long long a0 = offset[a], a1 = offset[a + 1], b0 = offset[b], b1 = offset[b + 1];
-        int shared = 0;
-        for (long long i = a0, j = b0; i < a1 && j < b1;) {
-            const int u = nbr[i], w = nbr[j];
-            shared += u == w ? 1 : 0;
-            i += u <= w ? 1 : 0;
-            j += w <= u ? 1 : 0;
-        }
-        bool valid = shared == 2 && (a1 - a0) + (b1 - b0) - 4 >= 3;
+        bool valid = dq_shared(offset, nbr, a, b) == 2 && (offset[a + 1] - offset[a]) + (offset[b + 1] - offset[b]) - 4 >= 3;
         // (iii) no face turns over, judged at the fp32 position the survivor takes
         const double t[3] = {(double)tx, (double)ty, (double)tz};
         if (valid) valid = !dq_flips(vertices, faces, foff, finc, a, b, t);
@@ -434,8 +395,6 @@ static DqSelectScratch dq_select_layout() {
     s.bytes = L.bytes;
     return s;
 }
-
-static bool dq_sizes_ok(long long n, long long m) { return n >= 0 && n < (1ll << 31) && m >= 0 && 6 * m < (1ll << 31); }
 
 }  // namespace d3d
 

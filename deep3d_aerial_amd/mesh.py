@@ -132,13 +132,20 @@ loop has become manifold, and no other loop has changed.  Integer atomics only, 
 Order in clean, build_and_write and the command line: removal, hole closing, smoothing (the smoothing relaxes the fans), then
 decimation (a vertex on a closed hole is no longer fixed, so the collapse is free around it).
 
+Collapse (collapse.py states the rule; csrc/mesh_collapse.hip), off by default: with --collapse PX
+build_and_write collapses every edge shorter than PX pixels in every view that sees it, after the decimation and before the
+subdivision.  No collapse may leave an edge estimated longer than --collapse_max_edge pixels (default 4 PX, or the subdivision's
+length when both stages are on).
+
 Subdivision (subdivide.py states the rule; csrc/mesh_subdivide.hip), off by default: with --subdivide PX
-build_and_write splits every edge longer than PX pixels in a view that sees it, after the decimation and before the refinement.
+build_and_write splits every edge longer than PX pixels in a view that sees it, after the collapse and before the refinement.
+The order of the stages is removal, hole closing, smoothing, decimation, collapse, subdivision, refinement.
 
     python -m deep3d_aerial_amd.mesh --mvs MVS_FOLDER --out mesh.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax --voxel S
         [--trunc T] [--min_views 2] [--conf_threshold 0.2] [--views_per_batch N]
         [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L] [--close_holes N]
-        [--decimate R] [--target_faces N] [--decimate_max_rounds K] [--subdivide PX] [--subdivide_rounds R]
+        [--decimate R] [--target_faces N] [--decimate_max_rounds K] [--collapse PX] [--collapse_max_edge PX2] [--collapse_rounds R]
+        [--subdivide PX] [--subdivide_rounds R]
     python -m deep3d_aerial_amd.mesh --clean IN.ply --out OUT.ply [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L]
         [--close_holes N] [--decimate R] [--target_faces N] [--decimate_max_rounds K]
 """
@@ -834,7 +841,16 @@ def add_arguments(ap, prefix=""):
     ap.add_argument("--%sviews_per_batch" % prefix, type=int, default=None, help="views per integration call (default: all)")
     add_clean_arguments(ap, prefix)
     add_decimate_arguments(ap, prefix)
+    add_collapse_arguments(ap, prefix)
     add_subdivide_arguments(ap, prefix)
+
+
+def add_collapse_arguments(ap, prefix=""):
+    """The collapse step as flags (--<prefix>collapse PX, --<prefix>collapse_max_edge PX2, --<prefix>collapse_rounds R); off unless
+    PX is given."""
+    from . import collapse as _collapse
+
+    _collapse.add_arguments(ap, prefix + "collapse_", edge_flag="--%scollapse" % prefix, tolerance=False)
 
 
 def add_subdivide_arguments(ap, prefix=""):
@@ -874,6 +890,10 @@ def settings_from_args(a, path, prefix=""):
         from . import subdivide as _subdivide
 
         s["subdivide"] = {k: v for k, v in _subdivide.settings_from_args(a, prefix + "subdivide_").items() if k != "views_per_batch"}
+    if getattr(a, prefix + "collapse_min_edge", None) is not None:   # likewise
+        from . import collapse as _collapse
+
+        s["collapse"] = {k: v for k, v in _collapse.settings_from_args(a, prefix + "collapse_").items() if k != "views_per_batch"}
     return s
 
 
@@ -920,6 +940,23 @@ def subdivide_settings(settings):
     return _subdivide.check_subdivide_settings(dict(settings["subdivide"], views_per_batch=settings.get("views_per_batch")))
 
 
+def collapse_settings(settings):
+    """The checked collapse settings of a settings dict ("collapse": {"min_edge", "max_edge", "rounds", "depth_tolerance"}, with
+    the mesh settings' own views_per_batch), or None when the key is missing: the step is off.  Without a max_edge of its own the
+    collapse takes the subdivision's when that stage is on too (a ValueError when it is below 2 min_edge), else 4 min_edge."""
+    if settings.get("collapse") is None:
+        return None
+    from . import collapse as _collapse
+
+    if "views_per_batch" in settings["collapse"]:
+        raise ValueError("collapse: views_per_batch is the mesh settings' own")
+    s = dict(settings["collapse"], views_per_batch=settings.get("views_per_batch"))
+    sub = subdivide_settings(settings)
+    if s.get("max_edge") is None and sub is not None:
+        s["max_edge"] = sub["max_edge"]
+    return _collapse.check_collapse_settings(s)
+
+
 def check_args(ap, a, prefix=""):
     """The argument errors of the mesh settings, reported through ap.error."""
     if getattr(a, prefix + "border") is None:
@@ -933,6 +970,7 @@ def check_args(ap, a, prefix=""):
         close_holes_setting(s)
         decimate_settings(s)
         subdivide_settings(s)
+        collapse_settings(s)
     except ValueError as e:
         ap.error("--%s*: %s" % (prefix, e))
 
@@ -943,6 +981,23 @@ def _decimate_and_report(v, f, ratio, target_faces, max_rounds):
     if info["stalled"] or info["hit_max_rounds"]:
         print("mesh decimation %s after %d rounds at %d faces (target %d)" % ("stalled" if info["stalled"] else "reached max_rounds",
                                                                               info["rounds"], info["faces_out"], info["target_faces"]))
+    return v, f
+
+
+def _collapse_and_report(v, f, views, s, timings=None):
+    import time
+
+    from . import collapse as _collapse
+
+    if timings is not None:
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    info = {}
+    v, f = _collapse.collapse(v, f, views, info=info, **s)
+    if timings is not None:
+        torch.cuda.synchronize()
+        timings["mesh_collapse_s"] = time.perf_counter() - t0
+    print("mesh collapse: %s" % (_collapse.summary_line(info) or "nothing to collapse"))
     return v, f
 
 
@@ -965,10 +1020,12 @@ def _subdivide_and_report(v, f, views, s, timings=None):
 
 def build_and_write(views, settings, refine=None, timings=None):
     """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on (removal, hole closing, smoothing),
-    then decimate when it is on, then subdivide against `views` when settings["subdivide"] is present (subdivide.subdivide; timings, a
-    dict, then gets mesh_subdivide_s), then vertices = refine(vertices, faces) when a refinement is handed in (refine.refine_mesh
+    then decimate when it is on, then collapse the edges `views` cannot resolve when settings["collapse"] is present
+    (collapse.collapse; timings, a dict, then gets mesh_collapse_s), then subdivide against `views` when settings["subdivide"] is
+    present (subdivide.subdivide; timings then gets mesh_subdivide_s), then vertices = refine(vertices, faces) when a refinement is handed in (refine.refine_mesh
     bound to its views: pipeline.write_mesh_of), and write_ply to settings["path"]: (vertices, faces) as written."""
     sub = subdivide_settings(settings)
+    col = collapse_settings(settings)
     grid = MeshGrid(settings["border"], settings["voxel"])
     v, f = depth_to_mesh(views, grid, settings.get("trunc"), settings.get("min_views", DEFAULT_MIN_VIEWS),
                          settings.get("conf_threshold", DEFAULT_CONF), settings.get("views_per_batch"))
@@ -976,6 +1033,8 @@ def build_and_write(views, settings, refine=None, timings=None):
         v, f = clean(v, f, *clean_settings(settings), close_holes=close_holes_setting(settings))
     if decimate_requested(settings):
         v, f = _decimate_and_report(v, f, *decimate_settings(settings))
+    if col is not None:
+        v, f = _collapse_and_report(v, f, views, col, timings)
     if sub is not None:
         v, f = _subdivide_and_report(v, f, views, sub, timings)
     if refine is not None:
@@ -1000,6 +1059,9 @@ def main(argv=None):
             check_decimate_settings(a.decimate, a.target_faces, a.decimate_max_rounds)
         except ValueError as e:
             ap.error("--clean: %s" % e)
+        if a.collapse_min_edge is not None:
+            ap.error("--collapse needs the views of --mvs: --clean IN.ply has none (python -m deep3d_aerial_amd.collapse takes a mesh and "
+                     "an MVS folder)")
         if a.subdivide_max_edge is not None:
             ap.error("--subdivide needs the views of --mvs: --clean IN.ply has none (python -m deep3d_aerial_amd.subdivide takes a mesh and "
                      "an MVS folder)")
@@ -1023,4 +1085,8 @@ def main(argv=None):
 
 
 if __name__ == "__main__":
-    main()
+    # python -m runs this file as __main__, a second copy of its classes: the stages that take the views (collapse, subdivide)
+    # check them against the package's MeshView, so the tool runs the package's main
+    from deep3d_aerial_amd.mesh import main as _main
+
+    _main()

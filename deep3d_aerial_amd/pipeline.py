@@ -102,6 +102,10 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     maps and cameras it already holds, after the decimation and before the refinement (subdivide.subdivide): no image and no
     collective, so the file still does not depend on the number of ranks; timings gets mesh_subdivide_s (a part of mesh_s).  The
     refinement, the DSM from the mesh and the texture then see the subdivided mesh.
+    With mesh["collapse"] ({"min_edge", "max_edge", "rounds", "depth_tolerance"}; absent: off) rank 0 collapses the edges those
+    views cannot resolve, after the decimation and before the subdivision (collapse.collapse), again alone and without an image:
+    the file does not depend on the number of ranks; timings gets mesh_collapse_s (a part of mesh_s), and the subdivision, the
+    refinement, the DSM from the mesh and the texture see the collapsed mesh.
     texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad",
     "level" (optional: None, or the seam levelling's settings), "local" (the local seam levelling's), "smooth_views" and
     "outliers" (optional, likewise)}
@@ -117,6 +121,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         _mesh.close_holes_setting(mesh)
         _mesh.decimate_settings(mesh)
         _mesh.subdivide_settings(mesh)
+        _mesh.collapse_settings(mesh)
         if mesh.get("refine") is not None:
             from . import refine as _refine
 
@@ -287,6 +292,7 @@ def gather_refine_views(own, all_maps, all_cams, n_views, rank=0, world_size=1, 
 def write_mesh_of(all_maps, all_cams, settings, timings=None, refine_views=None):
     """The mesh of every view (all_maps [n,2,H,W] depth and confidence, all_cams [n,2,4,4], by global view index), written to
     settings["path"] (mesh.build_and_write: cleaned when a clean step is on, then decimated when asked, then, with
+    settings["collapse"], the edges the views cannot resolve collapsed: timings gets mesh_collapse_s, a part of mesh_s; then, with
     settings["subdivide"] subdivided against the views: timings gets mesh_subdivide_s, a part of mesh_s; then, with
     settings["refine"] (refine.check_refine_settings) and refine_views (gather_refine_views), refined against the images:
     timings gets mesh_refine_s, a part of mesh_s).  Returns (vertices, faces) as written."""

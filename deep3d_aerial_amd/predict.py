@@ -602,6 +602,8 @@ def parse_args(argv=None):
         ap.error("--mesh needs --mesh_border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax")
     if a.mesh is not None:
         _mesh.check_args(ap, a, prefix="mesh_")
+    if a.mesh_collapse_min_edge is not None and a.mesh is None:
+        ap.error("--mesh_collapse needs --mesh (it is the mesh whose edges are collapsed)")
     if a.mesh_refine_step is not None:
         if a.mesh is None:
             ap.error("--mesh_refine needs --mesh (it is the mesh that is refined)")
@@ -734,6 +736,8 @@ def main(argv=None):
             print("rank 0/%d: orthophoto %s in %.2f s" % (world, a.ortho, tm["ortho_s"]))
         if a.mesh is not None and rank == 0:
             print("rank 0/%d: mesh %s in %.2f s" % (world, a.mesh, tm["mesh_s"]))
+            if "mesh_collapse_s" in tm:
+                print("rank 0/%d: mesh edges the views cannot resolve collapsed in %.2f s" % (world, tm["mesh_collapse_s"]))
             if "mesh_subdivide_s" in tm:
                 print("rank 0/%d: mesh subdivided against the views in %.2f s" % (world, tm["mesh_subdivide_s"]))
             if "mesh_refine_s" in tm:

@@ -106,15 +106,15 @@ def _check_views(views, device):
     return check(views, device)
 
 
-def edge_list(faces, n_vertices):
+def edge_list(faces, n_vertices, csr=None):
     """(edges [3 m, 2] int32, n_edges [1] int64) on the device: rule 2's list (d3d_mesh_decimate_edges over mesh.adjacency); the rows
-    from n_edges on are not written."""
+    from n_edges on are not written.  csr: mesh.adjacency(faces, n_vertices) when the caller has it."""
     from .mesh import adjacency
 
     lib = _lib.load()
     n, m = int(n_vertices), int(faces.shape[0])
     dev = faces.device
-    offset, nbr, _ = adjacency(faces, n)
+    offset, nbr, _ = csr if csr is not None else adjacency(faces, n)
     emax = 3 * m
     edges = torch.zeros((max(emax, 1), 2), dtype=torch.int32, device=dev)
     n_edges = torch.zeros((1,), dtype=torch.int64, device=dev)

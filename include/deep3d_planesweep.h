@@ -1533,6 +1533,32 @@ int d3d_mesh_subdivide_emit(const float* vertices, long long n_vertices, const i
                             const int* child_offset, long long n_split, long long n_faces_out, float* out_vertices, int* out_faces,
                             d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.24 -- collapsing the mesh edges shorter than the images resolve: every edge whose measure (§4.23's: the largest
+ * squared pixel length over the views that see both its ends) is above 0 and below min_edge^2 is a candidate for an edge collapse,
+ * and the decimation's claim, apply and faces passes (§4.14) take the independent ones with every valid candidate eligible
+ * (threshold = LLONG_MAX, no select pass).  The rule is this project's, deep3d_aerial_amd/collapse.py states it in full; it does
+ * not claim to match OpenMVS's RefineMesh (nEnsureEdgeSize).  The mesh, offset / nbr / fixed (d3d_mesh_adjacency), face_offset /
+ * face_index (d3d_mesh_decimate_incidence), edges and *n_edges (d3d_mesh_decimate_edges) are as §4.14 takes them, measure
+ * [max_edges] fp64 is d3d_mesh_subdivide_measure's.  Every pointer is DEVICE memory.  All arithmetic is fp64 without contraction,
+ * rounded to fp32 only where said; no atomics.
+ */
+/* d3d_mesh_collapse_candidates: per edge e = (a, b), a < b, of the first min(*n_edges, max_edges): key [max_edges] int64 and
+ *   target [max_edges, 3] fp32.  The edge is short when 0 < measure[e] < min_edge^2.  A fixed end survives and the target t is its
+ *   position; with both ends free a survives at t = fp32((fp64(x_a) + fp64(x_b)) * 0.5) per component.  The candidate is valid
+ *   when (1) the rows of a and b in nbr share exactly two vertices, (2) |N(a)| + |N(b)| - 4 >= 3, (3) no face at a or b that does
+ *   not hold both ends turns over or loses its area with the end at t (old normal . new normal > 0, the normal (p1 - p0) x
+ *   (p2 - p0), as d3d_mesh_decimate_candidates judges it), and (4) with L2 = (dx dx + dy dy) + dz dz of x_b - x_a and s =
+ *   measure[e] / L2, every w in N(a) or N(b) other than a and b has ((tx - wx)^2 + (ty - wy)^2) + (tz - wz)^2, times s, <=
+ *   max_edge^2 (a NaN fails).  key = (bits(fp32(measure[e])) << 32) | (e * 2654435761 mod 2^32) for a short edge with a free end
+ *   that is valid, else -1 (also from *n_edges on); target is 0 wherever the key is -1.  min_edge finite, > 0; max_edge finite,
+ *   >= 2 min_edge (pixels). */
+int d3d_mesh_collapse_candidates(const float* vertices, long long n_vertices, const int* faces, long long n_faces,
+                                 const long long* offset, const int* nbr, const unsigned char* fixed, const int* face_offset,
+                                 const int* face_index, const int* edges, const long long* n_edges, long long max_edges,
+                                 const double* measure, double min_edge, double max_edge, float* target, long long* key,
+                                 d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
