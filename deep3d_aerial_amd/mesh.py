@@ -137,17 +137,22 @@ build_and_write collapses every edge shorter than PX pixels in every view that s
 subdivision.  No collapse may leave an edge estimated longer than --collapse_max_edge pixels (default 4 PX, or the subdivision's
 length when both stages are on).
 
+Flip (flip.py states the rule; csrc/mesh_flip.hip), off by default: with --flip DEG build_and_write flips every
+interior edge whose flip raises the worse shape quality of its two triangles, where they meet at no more than DEG degrees, after
+the collapse and before the subdivision (a flip can lengthen an edge, and the subdivision then splits it).  The stage needs no
+views, so --clean IN.ply takes it too, after the decimation.
+
 Subdivision (subdivide.py states the rule; csrc/mesh_subdivide.hip), off by default: with --subdivide PX
-build_and_write splits every edge longer than PX pixels in a view that sees it, after the collapse and before the refinement.
-The order of the stages is removal, hole closing, smoothing, decimation, collapse, subdivision, refinement.
+build_and_write splits every edge longer than PX pixels in a view that sees it, after the flip and before the refinement.
+The order of the stages is removal, hole closing, smoothing, decimation, collapse, flip, subdivision, refinement.
 
     python -m deep3d_aerial_amd.mesh --mvs MVS_FOLDER --out mesh.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax --voxel S
         [--trunc T] [--min_views 2] [--conf_threshold 0.2] [--views_per_batch N]
         [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L] [--close_holes N]
         [--decimate R] [--target_faces N] [--decimate_max_rounds K] [--collapse PX] [--collapse_max_edge PX2] [--collapse_rounds R]
-        [--subdivide PX] [--subdivide_rounds R]
+        [--flip DEG] [--flip_rounds R] [--subdivide PX] [--subdivide_rounds R]
     python -m deep3d_aerial_amd.mesh --clean IN.ply --out OUT.ply [--min_faces N] [--spurious F] [--smooth K] [--smooth_lambda L]
-        [--close_holes N] [--decimate R] [--target_faces N] [--decimate_max_rounds K]
+        [--close_holes N] [--decimate R] [--target_faces N] [--decimate_max_rounds K] [--flip DEG] [--flip_rounds R]
 """
 import argparse
 import ctypes
@@ -842,6 +847,7 @@ def add_arguments(ap, prefix=""):
     add_clean_arguments(ap, prefix)
     add_decimate_arguments(ap, prefix)
     add_collapse_arguments(ap, prefix)
+    add_flip_arguments(ap, prefix)
     add_subdivide_arguments(ap, prefix)
 
 
@@ -851,6 +857,13 @@ def add_collapse_arguments(ap, prefix=""):
     from . import collapse as _collapse
 
     _collapse.add_arguments(ap, prefix + "collapse_", edge_flag="--%scollapse" % prefix, tolerance=False)
+
+
+def add_flip_arguments(ap, prefix=""):
+    """The flip step as flags (--<prefix>flip DEG, --<prefix>flip_rounds R); off unless DEG is given."""
+    from . import flip as _flip
+
+    _flip.add_arguments(ap, prefix + "flip_", angle_flag="--%sflip" % prefix)
 
 
 def add_subdivide_arguments(ap, prefix=""):
@@ -894,6 +907,10 @@ def settings_from_args(a, path, prefix=""):
         from . import collapse as _collapse
 
         s["collapse"] = {k: v for k, v in _collapse.settings_from_args(a, prefix + "collapse_").items() if k != "views_per_batch"}
+    if getattr(a, prefix + "flip_max_angle", None) is not None:   # likewise
+        from . import flip as _flip
+
+        s["flip"] = _flip.settings_from_args(a, prefix + "flip_")
     return s
 
 
@@ -957,6 +974,16 @@ def collapse_settings(settings):
     return _collapse.check_collapse_settings(s)
 
 
+def flip_settings(settings):
+    """The checked flip settings of a settings dict ("flip": {"max_angle", "rounds"}), or None when the key is missing: the step is
+    off."""
+    if settings.get("flip") is None:
+        return None
+    from . import flip as _flip
+
+    return _flip.check_flip_settings(settings["flip"])
+
+
 def check_args(ap, a, prefix=""):
     """The argument errors of the mesh settings, reported through ap.error."""
     if getattr(a, prefix + "border") is None:
@@ -971,6 +998,7 @@ def check_args(ap, a, prefix=""):
         decimate_settings(s)
         subdivide_settings(s)
         collapse_settings(s)
+        flip_settings(s)
     except ValueError as e:
         ap.error("--%s*: %s" % (prefix, e))
 
@@ -1001,6 +1029,23 @@ def _collapse_and_report(v, f, views, s, timings=None):
     return v, f
 
 
+def _flip_and_report(v, f, s, timings=None):
+    import time
+
+    from . import flip as _flip
+
+    if timings is not None:
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    info = {}
+    v, f = _flip.flip_edges(v, f, info=info, **s)
+    if timings is not None:
+        torch.cuda.synchronize()
+        timings["mesh_flip_s"] = time.perf_counter() - t0
+    print("mesh flip: %s" % (_flip.summary_line(info) or "nothing to flip"))
+    return v, f
+
+
 def _subdivide_and_report(v, f, views, s, timings=None):
     import time
 
@@ -1021,11 +1066,13 @@ def _subdivide_and_report(v, f, views, s, timings=None):
 def build_and_write(views, settings, refine=None, timings=None):
     """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on (removal, hole closing, smoothing),
     then decimate when it is on, then collapse the edges `views` cannot resolve when settings["collapse"] is present
-    (collapse.collapse; timings, a dict, then gets mesh_collapse_s), then subdivide against `views` when settings["subdivide"] is
-    present (subdivide.subdivide; timings then gets mesh_subdivide_s), then vertices = refine(vertices, faces) when a refinement is handed in (refine.refine_mesh
+    (collapse.collapse; timings, a dict, then gets mesh_collapse_s), then flip the edges whose flip removes a cap triangle when
+    settings["flip"] is present (flip.flip_edges; timings then gets mesh_flip_s), then subdivide against `views` when
+    settings["subdivide"] is present (subdivide.subdivide; timings then gets mesh_subdivide_s), then vertices = refine(vertices, faces) when a refinement is handed in (refine.refine_mesh
     bound to its views: pipeline.write_mesh_of), and write_ply to settings["path"]: (vertices, faces) as written."""
     sub = subdivide_settings(settings)
     col = collapse_settings(settings)
+    flp = flip_settings(settings)
     grid = MeshGrid(settings["border"], settings["voxel"])
     v, f = depth_to_mesh(views, grid, settings.get("trunc"), settings.get("min_views", DEFAULT_MIN_VIEWS),
                          settings.get("conf_threshold", DEFAULT_CONF), settings.get("views_per_batch"))
@@ -1035,6 +1082,8 @@ def build_and_write(views, settings, refine=None, timings=None):
         v, f = _decimate_and_report(v, f, *decimate_settings(settings))
     if col is not None:
         v, f = _collapse_and_report(v, f, views, col, timings)
+    if flp is not None:
+        v, f = _flip_and_report(v, f, flp, timings)
     if sub is not None:
         v, f = _subdivide_and_report(v, f, views, sub, timings)
     if refine is not None:
@@ -1048,7 +1097,7 @@ def main(argv=None):
                                              "an existing mesh")
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--mvs", help="predict's output folder: {name}_init.pfm, {name}_prob.pfm and {name}.txt")
-    src.add_argument("--clean", metavar="IN_PLY", help="clean and / or decimate this mesh (a PLY write_ply wrote) instead of building one")
+    src.add_argument("--clean", metavar="IN_PLY", help="clean, decimate and / or flip this mesh (a PLY write_ply wrote) instead of building one")
     ap.add_argument("--out", required=True, help="mesh file (.ply)")
     add_arguments(ap)
     a = ap.parse_args(argv)
@@ -1057,6 +1106,7 @@ def main(argv=None):
             check_clean_settings(a.min_faces, a.spurious, a.smooth, a.smooth_lambda)
             check_close_holes_setting(a.close_holes)
             check_decimate_settings(a.decimate, a.target_faces, a.decimate_max_rounds)
+            flp = flip_settings(settings_from_args(a, a.out))
         except ValueError as e:
             ap.error("--clean: %s" % e)
         if a.collapse_min_edge is not None:
@@ -1075,6 +1125,8 @@ def main(argv=None):
                      close_holes=a.close_holes)
         if a.decimate < 1 or a.target_faces > 0:
             v, f = _decimate_and_report(v, f, a.decimate, a.target_faces, a.decimate_max_rounds)
+        if flp is not None:   # the flip needs no views
+            v, f = _flip_and_report(v, f, flp)
         write_ply(a.out, v, f)
         print("mesh %s: %d vertices, %d triangles cleaned from %s" % (a.out, v.shape[0], f.shape[0], a.clean))
         return a.out

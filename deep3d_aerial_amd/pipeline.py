@@ -106,6 +106,9 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     views cannot resolve, after the decimation and before the subdivision (collapse.collapse), again alone and without an image:
     the file does not depend on the number of ranks; timings gets mesh_collapse_s (a part of mesh_s), and the subdivision, the
     refinement, the DSM from the mesh and the texture see the collapsed mesh.
+    With mesh["flip"] ({"max_angle", "rounds"}; absent: off) rank 0 flips the edges of the mesh it built whose flip removes a cap
+    triangle, after the collapse and before the subdivision (flip.flip_edges): no view, no image and no collective, so the file
+    does not depend on the number of ranks; timings gets mesh_flip_s (a part of mesh_s).
     texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad",
     "level" (optional: None, or the seam levelling's settings), "local" (the local seam levelling's), "smooth_views" and
     "outliers" (optional, likewise)}
@@ -122,6 +125,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         _mesh.decimate_settings(mesh)
         _mesh.subdivide_settings(mesh)
         _mesh.collapse_settings(mesh)
+        _mesh.flip_settings(mesh)
         if mesh.get("refine") is not None:
             from . import refine as _refine
 
@@ -293,6 +297,7 @@ def write_mesh_of(all_maps, all_cams, settings, timings=None, refine_views=None)
     """The mesh of every view (all_maps [n,2,H,W] depth and confidence, all_cams [n,2,4,4], by global view index), written to
     settings["path"] (mesh.build_and_write: cleaned when a clean step is on, then decimated when asked, then, with
     settings["collapse"], the edges the views cannot resolve collapsed: timings gets mesh_collapse_s, a part of mesh_s; then, with
+    settings["flip"], the edges flipped whose flip removes a cap triangle: timings gets mesh_flip_s, a part of mesh_s; then, with
     settings["subdivide"] subdivided against the views: timings gets mesh_subdivide_s, a part of mesh_s; then, with
     settings["refine"] (refine.check_refine_settings) and refine_views (gather_refine_views), refined against the images:
     timings gets mesh_refine_s, a part of mesh_s).  Returns (vertices, faces) as written."""

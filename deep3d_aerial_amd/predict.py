@@ -604,6 +604,8 @@ def parse_args(argv=None):
         _mesh.check_args(ap, a, prefix="mesh_")
     if a.mesh_collapse_min_edge is not None and a.mesh is None:
         ap.error("--mesh_collapse needs --mesh (it is the mesh whose edges are collapsed)")
+    if a.mesh_flip_max_angle is not None and a.mesh is None:
+        ap.error("--mesh_flip needs --mesh (it is the mesh whose edges are flipped)")
     if a.mesh_refine_step is not None:
         if a.mesh is None:
             ap.error("--mesh_refine needs --mesh (it is the mesh that is refined)")
@@ -738,6 +740,8 @@ def main(argv=None):
             print("rank 0/%d: mesh %s in %.2f s" % (world, a.mesh, tm["mesh_s"]))
             if "mesh_collapse_s" in tm:
                 print("rank 0/%d: mesh edges the views cannot resolve collapsed in %.2f s" % (world, tm["mesh_collapse_s"]))
+            if "mesh_flip_s" in tm:
+                print("rank 0/%d: mesh edges flipped to remove cap triangles in %.2f s" % (world, tm["mesh_flip_s"]))
             if "mesh_subdivide_s" in tm:
                 print("rank 0/%d: mesh subdivided against the views in %.2f s" % (world, tm["mesh_subdivide_s"]))
             if "mesh_refine_s" in tm:

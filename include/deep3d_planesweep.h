@@ -1559,6 +1559,43 @@ int d3d_mesh_collapse_candidates(const float* vertices, long long n_vertices, co
                                  const double* measure, double min_edge, double max_edge, float* target, long long* key,
                                  d3d_stream_t stream);
 
+/*
+ * DESIGN.md §4.25 -- flipping the mesh edges whose flip removes a cap triangle: an interior manifold edge (a, b) with the
+ * opposite corners c and d is swapped for (c, d) when that raises the worse of the two triangles' shape quality, under a
+ * planarity guard, in rounds of independent flips.  Vertices never move, the vertex and face counts never change, the boundary
+ * never changes.  The rule is this project's, deep3d_aerial_amd/flip.py states it in full; it does not claim to match OpenMVS's
+ * bRemoveSpikes (VCG's RemoveTVertexByFlip).  The mesh (every face three distinct indices in range), offset / nbr
+ * (d3d_mesh_adjacency), face_offset / face_index (d3d_mesh_decimate_incidence), edges and *n_edges (d3d_mesh_decimate_edges) are
+ * as §4.14 takes them.  Every pointer is DEVICE memory.  All arithmetic is fp64 without contraction, dot products and squared
+ * lengths summed left to right, (x x + y y) + z z; integer atomics only.
+ */
+/* d3d_mesh_flip_candidates: per edge e = (a, b), a < b, of the first min(*n_edges, max_edges): key [max_edges] int64 and opp
+ *   [max_edges, 4] int32 = (c, d, f_ab, f_ba).  The edge is a candidate when (3) exactly two faces of a's row hold b, one with
+ *   the directed edge a->b (f_ab, its third corner c) and one with b->a (f_ba, its third corner d), and c != d; (4.1) d is not in
+ *   c's row of nbr; (4.2) the rows of a and b in nbr each hold more than 3 vertices; (4.3) with n1 = (x_b - x_a) x (x_c - x_a) and
+ *   n2 = (x_a - x_b) x (x_d - x_b), n1.n2 >= 0 and (n1.n2)^2 >= cos2_max_angle (|n1|^2 |n2|^2) (a NaN fails); (4.4) the normals of
+ *   the new faces (a, d, c) and (b, c, d), taken from their first corner, each have a dot product > 0 with n1 + n2; (5) with
+ *   Q = |n|^2 / S^2 of a triangle (n its normal, S = (|p1 - p0|^2 + |p2 - p1|^2) + |p0 - p2|^2, the corners in increasing index
+ *   order, Q = 0 when S = 0), min(Q(adc), Q(bcd)) > min(Q(abc), Q(bad)).  key = (bits(fp32(min(Q(abc), Q(bad)))) << 32) |
+ *   (e * 2654435761 mod 2^32) for a candidate, else -1 (also from *n_edges on); opp is 0 wherever the key is -1.
+ *   cos2_max_angle in [0, 1): the squared cosine of the largest angle between n1 and n2, computed by the caller.  No atomics. */
+int d3d_mesh_flip_candidates(const float* vertices, long long n_vertices, const int* faces, long long n_faces,
+                             const long long* offset, const int* nbr, const int* face_offset, const int* face_index,
+                             const int* edges, const long long* n_edges, long long max_edges, double cos2_max_angle,
+                             long long* key, int* opp, d3d_stream_t stream);
+
+/* d3d_mesh_flip_claim: claim [n_vertices] int64 = the smallest key of the candidates that hold the vertex as a, b, c or d
+ *   (64-bit atomicMin), LLONG_MAX where none does; *n_winners = 0. */
+int d3d_mesh_flip_claim(long long n_vertices, const int* edges, const long long* key, const int* opp, const long long* n_edges,
+                        long long max_edges, long long* claim, long long* n_winners, d3d_stream_t stream);
+
+/* d3d_mesh_flip_apply: out_faces [n_faces, 3] = faces, then every winner (a candidate whose key is the claim of its a, b, c and
+ *   d; winners share no vertex, hence no face) writes (a, d, c) to slot f_ab and (b, c, d) to slot f_ba.  win [max_edges] uint8:
+ *   1 for a winner; *n_winners gets their number added (d3d_mesh_flip_claim zeroed it).  out_faces is not faces. */
+int d3d_mesh_flip_apply(const int* faces, long long n_faces, const int* edges, const long long* key, const int* opp,
+                        const long long* n_edges, long long max_edges, const long long* claim, int* out_faces, unsigned char* win,
+                        long long* n_winners, d3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
