@@ -20,20 +20,15 @@
 #include <cmath>
 
 #include "common.h"
+#include "dsm_tri.h"
 #include "geom_shared.h"
 
 namespace d3d {
 
-constexpr int DSM_BLOCK = 256;
 constexpr int DSM_SMALL = 32;                               // cells of at most this many points: one lane, keys in registers
 constexpr int DSM_BIG_GRID = 1024;                          // workgroups walking the list of larger cells
 constexpr int DSM_FILL_TILE = 16;
 constexpr int DSM_MAX_RADIUS = 16;
-
-struct DsmGrid {
-    double x_min, y_max, ux, uy, z_min, z_max;
-    int W, H;
-};
 
 // The cell of point p, or -1.  Bin and scatter both call this, so they agree on every point.
 __device__ __forceinline__ int dsm_cell(const float* __restrict__ xyz, long p, const DsmGrid& g, float* z_out) {
@@ -215,6 +210,7 @@ __global__ __launch_bounds__(DSM_FILL_TILE * DSM_FILL_TILE) void dsm_fill_kernel
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // DSM from a triangle mesh (deep3d_aerial_amd/dsm.py states the semantics, tests/test_dsm_mesh.py restates them).
+// The coverage primitives (DsmTri, dsm_tri_setup / _range / _sample) are in dsm_tri.h, shared with ortho_mesh.hip.
 // A triangle's vertices are put in lexicographic (x, y, z) order (IEEE total order per component: the order of the weighted sum
 // then depends on the triangle alone, not on its winding or first vertex).  Edge p -> q has endpoints (u, v) in lexicographic
 // (x, y) order and s = +1 if (u, v) == (p, q), else -1; E(p, q, P) = s ((v.x - u.x)(P.y - u.y) - (v.y - u.y)(P.x - u.x)), fp64,
@@ -234,112 +230,6 @@ __global__ __launch_bounds__(DSM_FILL_TILE * DSM_FILL_TILE) void dsm_fill_kernel
 //        workgroup one coalesced read per 256 entries plus its own chunks.  The grid is launched whole whatever the list holds
 //        (the host does not read the list's length).
 constexpr int DSM_TRI_SMALL = 64;      // cell ranges of at most this many cells: one lane, no list
-constexpr int DSM_TRI_GRID = 1024;     // workgroups walking the list of larger triangles
-constexpr int DSM_TRI_CHUNK = 256;     // cells of a listed triangle's range per chunk: one per lane
-
-struct DsmTri {
-    double ox[3], oy[3], ex[3], ey[3], t[3];   // edge k (opposite vertex k): origin u, direction v - u, s * sigma
-    double z[3];
-    double x_lo, x_hi, y_lo, y_hi;
-};
-
-__device__ __forceinline__ bool dsm_vtx_less(const float* p, const float* q) {
-    const unsigned px = dsm_key(p[0]), qx = dsm_key(q[0]), py = dsm_key(p[1]), qy = dsm_key(q[1]);
-    return px < qx || (px == qx && (py < qy || (py == qy && dsm_key(p[2]) < dsm_key(q[2]))));
-}
-
-__device__ __forceinline__ void dsm_vtx_swap(float* p, float* q) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float a = p[k];
-        p[k] = q[k];
-        q[k] = a;
-    }
-}
-
-// Edge p -> q of the triangle (slot k): origin, direction and s.
-__device__ __forceinline__ void dsm_edge(const float* p, const float* q, int k, DsmTri& T, double* s) {
-    const bool fwd = p[0] < q[0] || (p[0] == q[0] && p[1] <= q[1]);
-    const float* u = fwd ? p : q;
-    const float* v = fwd ? q : p;
-    T.ox[k] = (double)u[0];
-    T.oy[k] = (double)u[1];
-    T.ex[k] = (double)v[0] - (double)u[0];
-    T.ey[k] = (double)v[1] - (double)u[1];
-    *s = fwd ? 1.0 : -1.0;
-}
-
-__device__ __forceinline__ double dsm_edge_eval(const DsmTri& T, int k, double px, double py) {
-    return T.ex[k] * (py - T.oy[k]) - T.ey[k] * (px - T.ox[k]);
-}
-
-// Face f -> its coverage data; false when the face contributes nothing (an index out of range, a non-finite coordinate, D 0
-// or not finite).
-__device__ __forceinline__ bool dsm_tri_setup(const float* __restrict__ vertices, int n_vertices, const int* __restrict__ faces, long f,
-                                              DsmTri& T) {
-    float v[3][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int id = faces[3 * f + c];
-        if (id < 0 || id >= n_vertices) return false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            v[c][a] = vertices[3 * (long)id + a];
-            if (!isfinite(v[c][a])) return false;
-        }
-    }
-    if (dsm_vtx_less(v[1], v[0])) dsm_vtx_swap(v[0], v[1]);
-    if (dsm_vtx_less(v[2], v[1])) dsm_vtx_swap(v[1], v[2]);
-    if (dsm_vtx_less(v[1], v[0])) dsm_vtx_swap(v[0], v[1]);
-    double s[3];
-    dsm_edge(v[1], v[2], 0, T, s + 0);   // b -> c
-    dsm_edge(v[2], v[0], 1, T, s + 1);   // c -> a
-    dsm_edge(v[0], v[1], 2, T, s + 2);   // a -> b
-    const double D = s[2] * dsm_edge_eval(T, 2, (double)v[2][0], (double)v[2][1]);
-    if (!(D != 0.0 && isfinite(D))) return false;
-    const double sigma = D > 0.0 ? 1.0 : -1.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        T.t[k] = s[k] * sigma;   // (s sigma) X == sigma (s X) exactly: both only set the sign
-        T.z[k] = (double)v[k][2];
-    }
-    T.x_lo = (double)fminf(fminf(v[0][0], v[1][0]), v[2][0]);
-    T.x_hi = (double)fmaxf(fmaxf(v[0][0], v[1][0]), v[2][0]);
-    T.y_lo = (double)fminf(fminf(v[0][1], v[1][1]), v[2][1]);
-    T.y_hi = (double)fmaxf(fmaxf(v[0][1], v[1][1]), v[2][1]);
-    return true;
-}
-
-// The cell range (columns j0..j1, rows i0..i1) whose centres are tested; false when it misses the raster.
-__device__ __forceinline__ bool dsm_tri_range(const DsmTri& T, const DsmGrid& g, int* j0, int* j1, int* i0, int* i1) {
-    const double a = fmax(floor((T.x_lo - g.x_min) / g.ux) - 1.0, 0.0);
-    const double b = fmin(floor((T.x_hi - g.x_min) / g.ux) + 1.0, (double)(g.W - 1));
-    const double c = fmax(floor((g.y_max - T.y_hi) / g.uy) - 1.0, 0.0);
-    const double d = fmin(floor((g.y_max - T.y_lo) / g.uy) + 1.0, (double)(g.H - 1));
-    if (!(a <= b && c <= d)) return false;
-    *j0 = (int)a;
-    *j1 = (int)b;
-    *i0 = (int)c;
-    *i1 = (int)d;
-    return true;
-}
-
-// The sample of the triangle at the centre of cell (i, j), if it covers it and the sample is inside the Z bounds.
-__device__ __forceinline__ bool dsm_tri_sample(const DsmTri& T, const DsmGrid& g, int i, int j, float* z) {
-    const double px = g.x_min + ((double)j + 0.5) * g.ux;
-    const double py = g.y_max - ((double)i + 0.5) * g.uy;
-    const double w0 = T.t[0] * dsm_edge_eval(T, 0, px, py);
-    const double w1 = T.t[1] * dsm_edge_eval(T, 1, px, py);
-    const double w2 = T.t[2] * dsm_edge_eval(T, 2, px, py);
-    if (!(w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0)) return false;
-    const double W = (w0 + w1) + w2;
-    if (!(W > 0.0)) return false;
-    const float s = (float)(((w0 * T.z[0] + w1 * T.z[1]) + w2 * T.z[2]) / W);
-    const double sd = (double)s;
-    if (!(sd >= g.z_min && sd <= g.z_max)) return false;
-    *z = s;
-    return true;
-}
 
 __global__ __launch_bounds__(DSM_BLOCK) void dsm_tri_small_kernel(const float* __restrict__ vertices, int n_vertices,
                                                                   const int* __restrict__ faces, int n_faces, DsmGrid g,
@@ -348,8 +238,8 @@ __global__ __launch_bounds__(DSM_BLOCK) void dsm_tri_small_kernel(const float* _
     const long f = (long)blockIdx.x * DSM_BLOCK + threadIdx.x;
     if (f >= n_faces) return;
     DsmTri T;
-    int j0, j1, i0, i1;
-    if (!dsm_tri_setup(vertices, n_vertices, faces, f, T) || !dsm_tri_range(T, g, &j0, &j1, &i0, &i1)) return;
+    int j0, j1, i0, i1, corner[3];
+    if (!dsm_tri_setup(vertices, n_vertices, faces, f, T, corner) || !dsm_tri_range(T, g, &j0, &j1, &i0, &i1)) return;
     const int nj = j1 - j0 + 1, ni = i1 - i0 + 1;
     if ((long)nj * ni > DSM_TRI_SMALL) {
         const int q = atomicAdd(n_big, 1);
@@ -378,7 +268,7 @@ __global__ __launch_bounds__(DSM_BLOCK) void dsm_tri_big_kernel(const float* __r
             const int4 e = big[q];
             ent[t] = e;
             const long chunks = ((long)e.z * e.w + DSM_TRI_CHUNK - 1) / DSM_TRI_CHUNK;
-            const int k = (b - q % G + G) % G;   // this workgroup's first chunk of entry q: (q + k) mod G == b
+            const int k = dsm_tri_first_chunk(q, b, G);   // this workgroup's first chunk of entry q: (q + k) mod G == b
             k0 = k < chunks ? k : -1;
         }
         first[t] = k0;
@@ -389,7 +279,8 @@ __global__ __launch_bounds__(DSM_BLOCK) void dsm_tri_big_kernel(const float* __r
             if (k1 < 0) continue;
             const int4 en = ent[e];
             DsmTri T;
-            if (!dsm_tri_setup(vertices, n_vertices, faces, en.x, T)) continue;   // listed faces passed it: a guard
+            int corner[3];
+            if (!dsm_tri_setup(vertices, n_vertices, faces, en.x, T, corner)) continue;   // listed faces passed it: a guard
             const int cells = en.z * en.w;
             const int j0 = en.y % g.W, i0 = en.y / g.W;
             for (long k = k1; k * DSM_TRI_CHUNK < cells; k += G)

@@ -113,7 +113,10 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     "level" (optional: None, or the seam levelling's settings), "local" (the local seam levelling's), "smooth_views" and
     "outliers" (optional, likewise)}
     (needs mesh; texture.settings_from_args): the mesh rank 0 wrote (after cleaning) textured from every rank's views and
-    reference images (write_texture_of); rank 0 writes the textured PLY and its pages; timings gets texture_s."""
+    reference images (write_texture_of); rank 0 writes the textured PLY and its pages; timings gets texture_s.
+    With texture["ortho"] ({"path", "border", "unit", "size", "z_down"}; absent or None: off) rank 0 then renders the textured mesh
+    top-down from the atlas, the mesh and the texcoords it holds (ortho_mesh.build_and_write) and writes the RGBA .tif and .tfw:
+    no new collective, so the file does not depend on the number of ranks; timings gets texture_ortho_s (a part of texture_s)."""
     if mesh is not None:
         from . import mesh as _mesh
 
@@ -157,6 +160,10 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             _texture.check_level_settings(texture["level"])
         if texture.get("local") is not None:
             _texture.check_local_settings(texture["local"])
+        if texture.get("ortho") is not None:
+            from . import ortho_mesh as _ortho_mesh
+
+            _ortho_mesh.check_settings(texture["ortho"])
     if checker is None:
         checker = fuse.ConsistencyChecker(1.0, 0.01, 90.0, 0.2)   # Fuse_Depth_Map's defaults (fusion_3d_normal.py:56-57)
     n = len(dataset)
@@ -386,6 +393,8 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     views (texture.face_colors); one all_reduce(SUM) of the colour words merges them (a slot belongs to one view, so to one rank,
     and the others hold 0 there); rank 0 rejects in place (texture.reject_outliers), then smooths or takes column 0, and lays
     out.  The result then has "rejected" and "outliers".
+    With settings["ortho"] rank 0 renders the orthophoto of the textured mesh after the texcoords (ortho_mesh.build_and_write);
+    the result then has "ortho" (ortho_mesh.summary's dict).
     Returns texture.texture_mesh's dict on rank 0 (without "labels"), None elsewhere."""
     from . import ortho as _ortho, texture as _tx
 
@@ -453,6 +462,16 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
         tc, tn = _tx.texcoords(v, f, key, res["chart"], table_np, packing, cams)
         res.update(pages=_tx.split_pages(atlas, packing), texcoord=tc, texnumber=tn)
         _tx.write_textured_ply(settings["path"], v, f, tc, tn, res["pages"])
+        if settings.get("ortho") is not None:   # the finished atlas, the mesh and the texcoords are here: no new collective
+            from . import ortho_mesh as _om
+
+            torch.cuda.synchronize()
+            o0 = time.perf_counter()
+            page_row = torch.from_numpy(packing.page_row).to(device)
+            res["ortho"] = _om.build_and_write(v, f, tc, tn, atlas, page_row, settings["ortho"])[2]
+            torch.cuda.synchronize()
+            if timings is not None:
+                timings["texture_ortho_s"] = time.perf_counter() - o0
     torch.cuda.synchronize()
     if timings is not None:
         timings["texture_s"] = time.perf_counter() - t0

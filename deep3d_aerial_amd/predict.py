@@ -585,6 +585,12 @@ def parse_args(argv=None):
     ap.add_argument("--texture", default=None,
                     help="with --fuse --mesh: write the mesh textured from the views to this .ply (+ <stem>_<k>.png pages), on rank 0")
     _texture.add_arguments(ap, prefix="texture_")
+    # orthophoto of the textured mesh (deep3d_aerial_amd/ortho_mesh.py): off by default
+    from . import ortho_mesh as _ortho_mesh
+
+    ap.add_argument("--texture_ortho", default=None,
+                    help="with --texture: render the textured mesh top-down to this .tif (+ .tfw), on rank 0")
+    _ortho_mesh.add_arguments(ap, prefix="texture_ortho_")
     a = ap.parse_args(argv)
     if a.dsm is not None and not a.fuse:
         ap.error("--dsm needs --fuse (the DSM is built from the fused points)")
@@ -622,6 +628,17 @@ def parse_args(argv=None):
         if not a.texture.endswith(".ply"):
             ap.error("--texture must end in .ply")
         _texture.check_args(ap, a, prefix="texture_")
+    if a.texture_ortho is not None:
+        if a.texture is None:
+            ap.error("--texture_ortho needs --texture (the orthophoto is rendered from the textured mesh)")
+        if a.texture_ortho_border is None:   # the DSM's raster when there is one, else the mesh's footprint
+            a.texture_ortho_border = list(a.dsm_border) if a.dsm_border is not None else list(a.mesh_border[:4])
+        if a.texture_ortho_unit is None:
+            a.texture_ortho_unit = list(a.dsm_unit) if a.dsm is not None else list(_ortho_mesh.DEFAULT_UNIT)
+        try:
+            _ortho_mesh.check_settings(_ortho_mesh.settings_from_args(a, a.texture_ortho, prefix="texture_ortho_"))
+        except ValueError as e:
+            ap.error("--texture_ortho*: %s" % e)
     return a
 
 
@@ -748,6 +765,8 @@ def main(argv=None):
                 print("rank 0/%d: mesh refined against the images in %.2f s" % (world, tm["mesh_refine_s"]))
         if a.texture is not None and rank == 0:
             print("rank 0/%d: textured mesh %s in %.2f s" % (world, a.texture, tm["texture_s"]))
+            if a.texture_ortho is not None:
+                print("rank 0/%d: orthophoto of the textured mesh %s in %.2f s" % (world, a.texture_ortho, tm["texture_ortho_s"]))
         print("rank %d/%d: %d views in %.2f s, all-gather of %.1f MB in %.2f ms (%s), fusion of its %d reference views %.2f s, "
               "%d vertices" % (rank, world, tm["views"], tm["predict_s"], tm["allgather_bytes"] / 1e6, tm["allgather_ms"], tm["backend"],
                                len(res), tm["fuse_s"], sum(int(r["points"]["xyz"].shape[0]) for r in res)))

@@ -1322,9 +1322,15 @@ def settings_from_args(a, path, prefix=""):
     if t is not None:
         outliers = {"threshold": t}
         check_outlier_settings(outliers)
-    return {"path": path, "depth_tolerance": g("depth_tolerance"), "views_per_batch": g("views_per_batch"), "page_size": g("page_size"),
-            "pad": g("pad"), "level": level if g("level") else None, "smooth_views": smooth if w is not None else None,
-            "outliers": outliers, "local": local if g("level_local") else None}
+    s = {"path": path, "depth_tolerance": g("depth_tolerance"), "views_per_batch": g("views_per_batch"), "page_size": g("page_size"),
+         "pad": g("pad"), "level": level if g("level") else None, "smooth_views": smooth if w is not None else None,
+         "outliers": outliers, "local": local if g("level_local") else None}
+    # the orthophoto of the textured mesh (ortho_mesh.py): only predict has the flags (--texture_ortho O.tif, --texture_ortho_*)
+    if getattr(a, prefix + "ortho", None) is not None:
+        from . import ortho_mesh as _ortho_mesh
+
+        s["ortho"] = _ortho_mesh.settings_from_args(a, g("ortho"), prefix + "ortho_")
+    return s
 
 
 def build_and_write(vertices, faces, views, settings):

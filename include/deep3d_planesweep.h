@@ -877,6 +877,42 @@ int d3d_dsm_from_mesh(const float* vertices, long long n_vertices, const int* fa
                       float* height, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.26 -- orthophoto of the textured mesh: the mesh seen top-down on a raster, coloured from its texture atlas.  The
+ * rule is this project's (deep3d_aerial_amd/ortho_mesh.py); it does not claim to match OpenMVS's orthographic image.
+ *   Grid and coverage: the raster, the cell centres, the lexicographic vertex order, the fp64 edge functions and inclusive test,
+ *   the degenerate and vertical rejection, the cell ranges and the sample z = fp32(((w_a z_a + w_b z_b) + w_c z_c) / W) kept
+ *   when z_min <= z <= z_max are exactly those of d3d_dsm_from_mesh above (one copy of the code).
+ *   Texcoords: texcoord [n_faces,6] fp32 (s, t per corner) and texnumber [n_faces] int32, as d3d_texture_texcoords writes them;
+ *   they travel with the vertices through the lexicographic sort, so nothing depends on the winding or on which corner comes
+ *   first.  At a covered centre s = ((w_a s_a + w_b s_b) + w_c s_c) / W in fp64, t alike; the texel position on page
+ *   k = texnumber is x = s page_width - 0.5, y = (1 - t) h_k - 0.5, h_k = page_row[k + 1] - page_row[k] (the inverse of
+ *   d3d_texture_texcoords).
+ *   Colour: the bilinear tap of d3d_ortho_colorize on page k at (x, y) -- x0 = floor(x) clamped to the page, fx = x - floor(x),
+ *   x1 = min(x0 + 1, page_width - 1), y alike, the weights (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy summed in that order in
+ *   fp64 --, each channel floor(c + 0.5) clamped to 0..255, alpha 255 (the atlas's own alpha is not read).  A face is untextured
+ *   when its three texcoord pairs are equal bit for bit (what d3d_texture_texcoords writes for a face no view sees), its
+ *   texnumber is outside 0 .. n_pages - 1 or a texcoord is not finite; it still occludes, and its colour word is 0.
+ *   Which face wins: a cell keeps the largest 64-bit key (zk << 32) | colour word (R in the low byte); zk = key(z), the
+ *   order-preserving fp32 -> uint32 key of the DSM, or ~key(z) when z_down is 1 (the lowest sample wins: the cameras are on
+ *   the low-Z side).  No finite z has zk 0 in either mode; key 0 is the empty cell.  Equal heights (coincident faces, shared
+ *   edges that round alike) go to the larger colour word, so a textured face beats an untextured one there.  The raster is a
+ *   function of the set of (triangle, texcoords, page texels), never of the face order: every update is one 64-bit integer max.
+ *   Outputs: rgba [H,W] RGBA8 words, 0 in empty cells and where an untextured face is on top; height [H,W] fp32, the winning
+ *   sample, NaN where empty -- with z_down 0 the raster of d3d_dsm_from_mesh on the same grid, bit for bit.
+ *   atlas: all pages as [page_row[n_pages], page_width] RGBA8 words (device); page_row [n_pages + 1] int64 in DEVICE memory,
+ *   increasing from 0 (the host cannot read it: a page whose rows are not increasing inside 0 .. page_row[n_pages] is treated
+ *   as untextured, and the Python layer refuses such an array).  scratch: device memory of
+ *   d3d_ortho_mesh_scratch_bytes(n_faces, W, H) bytes (0 for an out-of-range argument: 8 bytes per cell plus the list of large
+ *   faces), zeroed by the call on the stream; rgba, height and scratch must not overlap.  Null pointers, counts >= 2^31,
+ *   W * H >= 2^31, a short scratch, n_pages < 1, page_width < 1, z_down outside {0, 1}: D3D_ERR_INVALID_ARG before any launch.
+ */
+size_t d3d_ortho_mesh_scratch_bytes(long long n_faces, int W, int H);
+int d3d_ortho_from_mesh(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const float* texcoord,
+                        const int* texnumber, const unsigned* atlas, const long long* page_row, int n_pages, int page_width,
+                        double x_min, double y_max, double unit_x, double unit_y, double z_min, double z_max, int W, int H, int z_down,
+                        void* scratch, size_t scratch_bytes, unsigned* rgba, float* height, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.9 -- true orthophoto on the DSM (the reference has no orthophoto step; the semantics are this project's,
  * deep3d_aerial_amd/ortho.py).  The grid is the DSM's: cell (i, j) is X = (x_min + (j + 0.5) unit_x, y_max - (i + 0.5) unit_y, h),
  * h = height[i,j] in fp64; a non-finite h is an empty cell.  A view is one d3d_ortho_view_t record in DEVICE memory, filled by
