@@ -1,4 +1,4 @@
-// The primitives the geometry stages share (fusion, dsm, ortho, ortho_mesh, mesh, mesh_clean, mesh_decimate, mesh_holes,
+// The primitives the geometry stages share (fusion, dsm, ortho, ortho_mesh, cloud, mesh, mesh_clean, mesh_decimate, mesh_holes,
 // mesh_refine, mesh_subdivide, mesh_collapse, mesh_flip, texture and its smooth, level, local and outliers passes); not part of the
 // public ABI.  The kernels behind the host functions declared here are in geom.hip.
 #pragma once

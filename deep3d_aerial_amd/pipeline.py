@@ -68,7 +68,8 @@ def _gather_objects(obj, world_size):
 def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checker=None, fusion_num=10, min_geo_consist_num=4,
                      filter_sources=True, partition="block", scene_range=None, skip_line=2, feature_cache_bytes=0,
                      device="cuda", timings=None, display=False, fuse_partition="views", scene_blocks=None,
-                     estimate_normals=False, normal_nei=1, save_normals=False, dsm=None, ortho=None, mesh=None, texture=None):
+                     estimate_normals=False, normal_nei=1, save_normals=False, dsm=None, ortho=None, mesh=None, texture=None,
+                     cloud=None):
     """Runs the three steps above for this rank.  Returns a list, one entry per reference view this rank owns, of
     {"ref", "final_mask" [H,W] bool, "avg_xyz_world" [3,H,W], "points": fuse.extract_points(...) dict} (device tensors).
     timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s.
@@ -116,7 +117,14 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     reference images (write_texture_of); rank 0 writes the textured PLY and its pages; timings gets texture_s.
     With texture["ortho"] ({"path", "border", "unit", "size", "z_down"}; absent or None: off) rank 0 then renders the textured mesh
     top-down from the atlas, the mesh and the texcoords it holds (ortho_mesh.build_and_write) and writes the RGBA .tif and .tfw:
-    no new collective, so the file does not depend on the number of ranks; timings gets texture_ortho_s (a part of texture_s)."""
+    no new collective, so the file does not depend on the number of ranks; timings gets texture_ortho_s (a part of texture_s).
+    cloud: None (nothing changes: points["color"] stays None, no file, no collective), or the cloud settings {"path", "border",
+    "voxel", "min_points"} (cloud.check_settings): every reference view's crop colours its points (extract_points' ref_img, the
+    bytes / 255; a grey crop repeated to three channels; a crop of another size than the map is refused), each rank concatenates
+    the xyz, normal and colour of its results, one sharding.gather_points call moves them to rank 0 as one [n, 9] tensor (the
+    colours bit-cast), and rank 0 merges them on the voxel grid and writes the PLY (write_cloud_of); timings gets cloud_s.  With
+    filter_sources=False the file does not depend on the number of ranks.  The crops are the sweeping rank's, so with more than
+    one rank fuse_partition must be "views"."""
     if mesh is not None:
         from . import mesh as _mesh
 
@@ -164,6 +172,13 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             from . import ortho_mesh as _ortho_mesh
 
             _ortho_mesh.check_settings(texture["ortho"])
+    if cloud is not None:
+        from . import cloud as _cloud
+
+        _cloud.check_settings(cloud)
+        if fuse_partition == "scene_blocks" and world_size > 1:
+            raise ValueError("cloud with fuse_partition='scene_blocks' on %d ranks: the colours come from the reference crops of the "
+                             "rank that swept the view (use fuse_partition='views')" % world_size)
     if checker is None:
         checker = fuse.ConsistencyChecker(1.0, 0.01, 90.0, 0.2)   # Fuse_Depth_Map's defaults (fusion_3d_normal.py:56-57)
     n = len(dataset)
@@ -171,7 +186,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     mine = sharding.shard_views(n, rank, world_size, partition)
     cams = {}
     refine = mesh.get("refine") if mesh is not None else None
-    images = {} if ortho is not None or texture is not None or refine is not None else None
+    images = {} if ortho is not None or texture is not None or refine is not None or cloud is not None else None
     t0 = time.perf_counter()
     maps = predict.predict_views(model, dataset, output_folder, rank, world_size, device=device, keep_maps=True,
                                  feature_cache_bytes=feature_cache_bytes, display=display, partition=partition, cams=cams,
@@ -217,6 +232,9 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             add_estimated_normals(views, pairs, fusion_num, normal_nei)
         return pairs
 
+    def ref_img(name):
+        return reference_colors(images[name][1], H, W) if cloud is not None else None
+
     out = []
     if fuse_partition == "scene_blocks":
         if not scene_blocks:
@@ -231,7 +249,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             fused = fuse.fuse_block(views, with_normals(pairs), checker, fusion_num=fusion_num, min_geo_consist_num=min_geo_consist_num,
                                     filter_sources=filter_sources)
             for f in fused:
-                pts = fuse.extract_points(f["avg_xyz_world"], f["final_mask"], f["vis_infos"], None, f["normal_world"],
+                pts = fuse.extract_points(f["avg_xyz_world"], f["final_mask"], f["vis_infos"], ref_img(f["ref"]), f["normal_world"],
                                           blk["scene_range"], skip_line)
                 out.append({"ref": f["ref"], "scene": b, "final_mask": f["final_mask"], "avg_xyz_world": f["avg_xyz_world"], "points": pts})
     else:
@@ -239,7 +257,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
                                 min_geo_consist_num=min_geo_consist_num, filter_sources=filter_sources)
         sr = scene_range if scene_range is not None else [-np.inf, np.inf, -np.inf, np.inf]
         for f in fused:
-            pts = fuse.extract_points(f["avg_xyz_world"], f["final_mask"], f["vis_infos"], None, f["normal_world"], sr, skip_line)
+            pts = fuse.extract_points(f["avg_xyz_world"], f["final_mask"], f["vis_infos"], ref_img(f["ref"]), f["normal_world"], sr,
+                                      skip_line)
             out.append({"ref": f["ref"], "final_mask": f["final_mask"], "avg_xyz_world": f["avg_xyz_world"], "points": pts})
     torch.cuda.synchronize()
     t2 = time.perf_counter()
@@ -247,6 +266,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         timings.update(views=len(mine), predict_s=t1 - t0, allgather_ms=(g1 - g0) * 1e3,
                        allgather_bytes=int(all_maps.numel() * 4), fuse_s=t2 - g1, map_size=(H, W),
                        backend=dist.get_backend() if world_size > 1 else "none")
+    if cloud is not None:
+        write_cloud_of(out, cloud, rank, world_size, device=all_maps.device, timings=timings)
     built_mesh = None
     refine_views = None
     if refine is not None:
@@ -475,6 +496,44 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     torch.cuda.synchronize()
     if timings is not None:
         timings["texture_s"] = time.perf_counter() - t0
+    return res
+
+
+def reference_colors(image, H, W):
+    """A reference crop (device uint8 [H,W,C], C = 1 or 3, predict.reference_crop) as extract_points' ref_img: [H,W,3] float32,
+    byte / 255, a grey crop repeated to three channels.  int(c * 255.0f) in the gather kernel returns every byte exactly."""
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] not in (1, 3):
+        raise ValueError("the cloud needs [H,W,1] or [H,W,3] uint8 reference crops (got %s %s)" % (tuple(image.shape), image.dtype))
+    if tuple(image.shape[:2]) != (H, W):
+        raise ValueError("a reference crop of %d x %d on maps of %d x %d: the cloud's colours need them equal"
+                         % (image.shape[0], image.shape[1], H, W))
+    if image.shape[2] == 1:
+        image = image.expand(H, W, 3)
+    return (image.to(torch.float32) / 255.0).contiguous()
+
+
+def write_cloud_of(results, settings, rank=0, world_size=1, device="cuda", timings=None):
+    """The merged cloud of the points of `results` (predict_and_fuse's list, with colours) over all ranks, written by rank 0
+    (cloud.build_and_write).  Every rank must call it: one gather_points of [n, 9] int32 rows (the int32 colours, and xyz and the
+    normals bit-cast: no arithmetic touches them on the way).  Returns (cloud dict, summary) on rank 0, None elsewhere."""
+    from . import cloud as _cloud
+
+    t0 = time.perf_counter()
+    rows = []
+    for r in results:
+        p = r["points"]
+        if p["color"] is None or p["normal"] is None:
+            raise ValueError("the cloud needs the colours and normals of every result (%s has none)" % r["ref"])
+        rows.append(torch.cat([p["xyz"].view(torch.int32), p["normal"].view(torch.int32), p["color"]], 1))
+    local = torch.cat(rows) if rows else torch.zeros((0, 9), dtype=torch.int32, device=device)
+    pts = sharding.gather_points(local.contiguous(), rank, world_size)
+    res = None
+    if rank == 0:
+        res = _cloud.build_and_write(pts[:, 0:3].contiguous().view(torch.float32), pts[:, 3:6].contiguous().view(torch.float32),
+                                     pts[:, 6:9].contiguous(), settings)
+    torch.cuda.synchronize()
+    if timings is not None:
+        timings["cloud_s"] = time.perf_counter() - t0
     return res
 
 

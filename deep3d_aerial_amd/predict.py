@@ -591,6 +591,12 @@ def parse_args(argv=None):
     ap.add_argument("--texture_ortho", default=None,
                     help="with --texture: render the textured mesh top-down to this .tif (+ .tfw), on rank 0")
     _ortho_mesh.add_arguments(ap, prefix="texture_ortho_")
+    # merged point cloud of the fused points (deep3d_aerial_amd/cloud.py): off by default
+    from . import cloud as _cloud
+
+    ap.add_argument("--cloud", default=None,
+                    help="with --fuse: merge all ranks' fused points on a voxel grid into this coloured .ply, on rank 0")
+    _cloud.add_arguments(ap, prefix="cloud_")
     a = ap.parse_args(argv)
     if a.dsm is not None and not a.fuse:
         ap.error("--dsm needs --fuse (the DSM is built from the fused points)")
@@ -639,6 +645,24 @@ def parse_args(argv=None):
             _ortho_mesh.check_settings(_ortho_mesh.settings_from_args(a, a.texture_ortho, prefix="texture_ortho_"))
         except ValueError as e:
             ap.error("--texture_ortho*: %s" % e)
+    if a.cloud is not None:
+        if not a.fuse:
+            ap.error("--cloud needs --fuse (the cloud is merged from the fused points)")
+        if a.cloud_border is None:   # the mesh's box when there is one, else a DSM border with Z bounds
+            if a.mesh_border is not None:
+                a.cloud_border = list(a.mesh_border)
+            elif a.dsm_border is not None and len(a.dsm_border) == 6:
+                a.cloud_border = list(a.dsm_border)
+            else:
+                ap.error("--cloud needs --cloud_border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax (or --mesh_border, or a six-value --dsm_border)")
+        if a.cloud_voxel is None:
+            ap.error("--cloud needs --cloud_voxel")
+        if a.fuse_partition == "scene_blocks":
+            ap.error("--cloud needs --fuse_partition views (the colours come from the reference crops of the rank that swept the view)")
+        try:
+            _cloud.check_settings(_cloud.settings_from_args(a, a.cloud, prefix="cloud_"))
+        except ValueError as e:
+            ap.error("--cloud*: %s" % e)
     return a
 
 
@@ -697,6 +721,12 @@ def _texture_settings(a):
     return _texture.settings_from_args(a, a.texture, prefix="texture_")
 
 
+def _cloud_settings(a):
+    from . import cloud as _cloud
+
+    return _cloud.settings_from_args(a, a.cloud, prefix="cloud_")
+
+
 def main(argv=None):
     a = parse_args(argv)
     if a.dataset != "cas_normal_eval":
@@ -747,8 +777,11 @@ def main(argv=None):
                                         dsm=_dsm_settings(a) if a.dsm is not None else None,
                                         ortho=_ortho_settings(a) if a.ortho is not None else None,
                                         mesh=_mesh_settings(a) if a.mesh is not None else None,
-                                        texture=_texture_settings(a) if a.texture is not None else None)
+                                        texture=_texture_settings(a) if a.texture is not None else None,
+                                        cloud=_cloud_settings(a) if a.cloud is not None else None)
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
+        if a.cloud is not None and rank == 0:
+            print("rank 0/%d: merged point cloud %s in %.2f s" % (world, a.cloud, tm["cloud_s"]))
         if a.dsm is not None and rank == 0:
             print("rank 0/%d: DSM %s in %.2f s" % (world, a.dsm, tm["dsm_s"]))
         if a.ortho is not None and rank == 0:

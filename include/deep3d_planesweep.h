@@ -913,6 +913,59 @@ int d3d_ortho_from_mesh(const float* vertices, long long n_vertices, const int* 
                         void* scratch, size_t scratch_bytes, unsigned* rgba, float* height, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.27 -- voxel-grid merge of the fused points into one de-duplicated cloud with colour, normal and support count.
+ * The rule is this project's (deep3d_aerial_amd/cloud.py); it stands where the reference's Resample_PC would and does not claim
+ * to match any tool.
+ *   Grid: border = x_min, x_max, y_min, y_max, z_min, z_max (all finite, min < max) and voxel v > 0 (finite);
+ *   n_a = ceil((max_a - min_a) / v) per axis, each in 1 .. 2^21 - 1.
+ *   Cell of a point, per axis: u = ((double)x - min_a) / v in fp64, i = floor(u), r = floor((u - i) * 65536) in 0 .. 65535.  A
+ *   point is dropped when a coordinate is not finite or an i is outside 0 .. n_a - 1 (so a point on a max face whose u equals
+ *   n_a is dropped).  Key: (iz << 42) | (iy << 21) | ix, 63 bits; a dropped point gets INT64_MAX.
+ *   Per occupied voxel, integer sums over its members (no grouping or order of the additions can change a bit):
+ *     count, int32.
+ *     Position per axis: S = sum r; min_a + (i + (S + 0.5 count) / (65536.0 count)) * v in fp64, each operation rounded once
+ *     (no fused multiply-add), then rounded to fp32: within v / 65536 plus one fp32 ulp of the exact mean.
+ *     Normal (normal not null): per component llrint(n_c * 2^20) as int64 is summed; a member whose normal has a non-finite
+ *     component, or one of magnitude above 1024 (so 2^31 members cannot overflow), adds nothing.  Output sum / |sum| in fp64,
+ *     |sum| = sqrt((x x + y y) + z z), rounded to fp32; (0, 0, 0) when the sum vector is zero.
+ *     Colour (color not null; int32 [n,3], each channel clamped to 0 .. 255 on input): (2 sum + count) / (2 count) in
+ *     integers, uint8 (.5 rounds up).
+ *   Isolated voxels: a voxel is kept when the counts of its 3 x 3 x 3 neighbourhood (itself included; neighbours outside the
+ *   grid do not exist) sum to at least min_points >= 1, over the unfiltered voxel set, in one pass.  1 keeps every voxel.
+ *   Order: the kept voxels come out in increasing key.  The output is a function of the multiset of input points.
+ * Every pointer is DEVICE memory.  The calls, in order (the host reads two counts: *n_voxels and *n_kept):
+ *   d3d_cloud_keys: keys [n] int64 and frac [n] int64 = r_x | r_y << 16 | r_z << 32 (0 for a dropped point) of xyz [n,3] fp32.
+ *   The caller sorts the keys and keeps the order (sorted_keys [n], order [n] int64: sorted_keys[i] = keys[order[i]]).
+ *   d3d_cloud_heads: vox [n] int32 = the voxel of every sorted point (the number of distinct keys below its own; n_voxels for a
+ *     dropped point) and *n_voxels int64 = the number of distinct keys other than INT64_MAX.
+ *   d3d_cloud_accumulate: ukeys [n_voxels] int64 (increasing), count [n_voxels] int32 and acc [n_voxels, 3 + 3 (normal != null)
+ *     + 3 (color != null)] int64 = S, then the normal sums, then the colour sums; count and acc are zeroed by the call on the
+ *     stream.  normal [n,3] fp32 and color [n,3] int32 are indexed like xyz (through order) and may be null.
+ *   d3d_cloud_neighbours: keep [n_voxels] int32 (1 or 0), pos [n_voxels] int32 = the exclusive scan of keep, *n_kept its total.
+ *     nx, ny, nz: the grid's n_a.
+ *   d3d_cloud_finalize: xyz [n_kept,3] fp32, normal [n_kept,3] fp32, color [n_kept,3] uint8, count [n_kept] int32 of the kept
+ *     voxels; normal and color null exactly where they were null for d3d_cloud_accumulate (the width of acc follows them).
+ *   scratch (heads, neighbours): d3d_cloud_scratch_bytes(n) bytes for n points or n voxels (0 for n outside 0 .. 2^31 - 1).
+ * Integer atomicAdd only.  Null pointers (where the count is not 0), counts outside 0 .. 2^31 - 1, n_voxels > n_points,
+ * n_kept > n_voxels, a bad border, voxel or grid, min_points < 1, a short scratch, overlapping buffers: D3D_ERR_INVALID_ARG
+ * before any launch.
+ */
+size_t d3d_cloud_scratch_bytes(long long n);
+int d3d_cloud_keys(const float* xyz, long long n_points, double x_min, double x_max, double y_min, double y_max, double z_min,
+                   double z_max, double voxel, long long* keys, long long* frac, d3d_stream_t stream);
+int d3d_cloud_heads(const long long* sorted_keys, long long n_points, void* scratch, size_t scratch_bytes, int* vox,
+                    long long* n_voxels, d3d_stream_t stream);
+int d3d_cloud_accumulate(const long long* sorted_keys, const long long* order, const int* vox, const long long* frac,
+                         const float* normal, const int* color, long long n_points, long long n_voxels, long long* ukeys, int* count,
+                         long long* acc, d3d_stream_t stream);
+int d3d_cloud_neighbours(const long long* ukeys, const int* count, long long n_voxels, int nx, int ny, int nz, int min_points,
+                         void* scratch, size_t scratch_bytes, int* keep, int* pos, long long* n_kept, d3d_stream_t stream);
+int d3d_cloud_finalize(const long long* ukeys, const int* count, const long long* acc, const int* keep, const int* pos,
+                       long long n_voxels, long long n_kept, double x_min, double x_max, double y_min, double y_max, double z_min,
+                       double z_max, double voxel, float* xyz, float* normal, unsigned char* color, int* out_count,
+                       d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.9 -- true orthophoto on the DSM (the reference has no orthophoto step; the semantics are this project's,
  * deep3d_aerial_amd/ortho.py).  The grid is the DSM's: cell (i, j) is X = (x_min + (j + 0.5) unit_x, y_max - (i + 0.5) unit_y, h),
  * h = height[i,j] in fp64; a non-finite h is an empty cell.  A view is one d3d_ortho_view_t record in DEVICE memory, filled by
