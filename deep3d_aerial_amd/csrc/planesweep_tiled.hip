@@ -224,7 +224,7 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
     static_assert(!F16 || MODE == MODE_VARIANCE, "fp16 storage is built for the variance volume only");
     constexpr bool VIEW_MAJOR = F16;             // unit order of the compute loop (see there)
     constexpr int MAXRS = 4 * NSRC;               // delta rectangles a step can have (left | right | top | bottom per view)
-    static_assert(NSRC <= 15, "rect descriptors keep the view in 4 bits");
+    static_assert(NSRC <= 7, "rect descriptors keep the view in 4 bits; the planner scans 5-bit rectangle counts");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int* ldsi = reinterpret_cast<int*>(lds);
 
@@ -296,13 +296,37 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
     //     the planning instead of after it: on the cascade's shallow sweeps the prologue is most of a workgroup's life ----
     //     (Up to four source views.  With six, 36 more registers live across the planning make the plane loop spill.)
     constexpr bool EARLY_INPUTS = NSRC <= 4 && !F16 && CH <= 16;
+    // Per-plane depths are requested FIRST: loads return in order, so a wait for a load issued behind the per-lane inputs would
+    // be a wait for all of them (the reference features come from HBM), and the first barrier of the planning waits for this one.
+    // The LOADER waves fetch them (one thread per plane): they request no per-lane inputs, so the wait the compiler places in front
+    // of the LDS write -- for every load of whichever wave gets there -- is a wait for this load alone.
+    constexpr bool DEPTH_BY_LOADERS = NLOADW * 64 >= DSEG_MAX;
+    static_assert(THREADS >= DSEG_MAX, "one thread per plane of a segment");
+    const int dtid = DEPTH_BY_LOADERS ? tid - 64 * NCOMP : tid;
+    float dplane = 0.0f;
+    if (p.depth_mode == D3D_DEPTH_PER_PLANE && dtid >= 0 && dtid < nplanes) dplane = p.depth[ds + dtid];
+    // ... and the projection rows of the view this wave plans (wave i: view i), which the planner reads after that barrier
+    float mw[12];
+    {
+        const float* __restrict__ Mg = p.proj34 + 12 * min(min(wave, NSRC - 1), p.n_src - 1);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) mw[k] = Mg[k];
+    }
     int grp = 0, c0 = 0;  // current channel group / its first channel
     Ray ray[NSRC];
     float T0[NSRC], T1[NSRC], T2[NSRC];
     auto projection_rows = [&]() {
+        // (every view's rows are requested before the first of them is used: one latency instead of one per view)
+        float m[NSRC][12];
 #pragma unroll
         for (int i = 0; i < NSRC; ++i) {
-            const float* __restrict__ M = p.proj34 + 12 * min(i, p.n_src - 1);
+            const float* __restrict__ Mg = p.proj34 + 12 * min(i, p.n_src - 1);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) m[i][k] = Mg[k];
+        }
+#pragma unroll
+        for (int i = 0; i < NSRC; ++i) {
+            const float* M = m[i];
             ray[i] = make_ray(M, xf, yf);
             T0[i] = M[3]; T1[i] = M[7]; T2[i] = M[11];
             // (kept in vector registers: as scalars they would be live across the whole planning prologue, and the scalar
@@ -313,14 +337,16 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
     if constexpr (EARLY_INPUTS) projection_rows();
     f4 r[F16 ? 1 : Q];
     float rh[F16 ? Q : 1][8];   // fp16 storage: reference features of the group, 8 channels per chunk
-    auto load_reference = [&]() {
+    // (defer: the loaded values stay as they came -- finish_inputs() masks them after the planning.  Masking at once would wait
+    //  for the loads where they are issued.)
+    auto load_reference = [&](bool defer) {
         if (F16) {
 #pragma unroll
             for (int q = 0; q < Q; ++q)
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     float t = ldf(reinterpret_cast<const T*>(p.feats[0]) + (size_t)(c0 + 8 * q + k) * plane + pix);
-                    rh[F16 ? q : 0][k] = valid ? t : 0.0f;
+                    rh[F16 ? q : 0][k] = (defer || valid) ? t : 0.0f;
                 }
         } else if (MODE != MODE_WARP) {
 #pragma unroll
@@ -328,39 +354,58 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     float t = p.feats[0][(size_t)(c0 + 4 * q + k) * plane + pix];
-                    r[F16 ? 0 : q][k] = valid ? t : 0.0f;
+                    r[F16 ? 0 : q][k] = (defer || valid) ? t : 0.0f;
                 }
         }
     };
     float vw[NSRC];
     float rden = 0.0f;
     float aff_lo = 1.0f, aff_step = 0.0f;   // D3D_DEPTH_AFFINE: this lane's pixel
-    auto lane_inputs = [&]() {
+    auto finish_weights = [&]() {
         if (MODE == MODE_WEIGHTED) {
             float den = 1e-5f;
 #pragma unroll
             for (int i = 0; i < NSRC; ++i) {
-                float t = p.weights[(size_t)min(i, p.n_src - 1) * plane + pix];
-                vw[i] = (valid && i < p.n_src) ? t : 0.0f;
+                vw[i] = (valid && i < p.n_src) ? vw[i] : 0.0f;
                 den += vw[i];
             }
             rden = 1.0f / den;
         }
-        load_reference();   // group 0
+    };
+    auto finish_inputs = [&]() {   // what a deferred lane_inputs() left undone: lanes outside the image carry zeros
+        finish_weights();
+        if (F16) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) rh[F16 ? q : 0][k] = valid ? rh[F16 ? q : 0][k] : 0.0f;
+        } else if (MODE != MODE_WARP) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r[F16 ? 0 : q][k] = valid ? r[F16 ? 0 : q][k] : 0.0f;
+        }
+    };
+    auto lane_inputs = [&](bool defer) {
+        if (MODE == MODE_WEIGHTED) {
+#pragma unroll
+            for (int i = 0; i < NSRC; ++i) vw[i] = p.weights[(size_t)min(i, p.n_src - 1) * plane + pix];
+            if (!defer) finish_weights();
+        }
+        load_reference(defer);   // group 0
         if (p.depth_mode == D3D_DEPTH_AFFINE && valid) {
             aff_lo = p.depth[pix];
             aff_step = p.depth[plane + pix];
         }
     };
-    if (EARLY_INPUTS && !loader) lane_inputs();
+    if (EARLY_INPUTS && !loader) lane_inputs(true);
 
     // --- zero cell and per-plane depth range of this patch -------------------------------------
     for (int i = tid; i < 2 * STRIDE; i += THREADS) lds[L::ZERO + i] = 0.0f;
     if (p.depth_mode == D3D_DEPTH_PER_PLANE) {
-        for (int i = tid; i < nplanes; i += THREADS) {
-            float dv = p.depth[ds + i];
-            lds[L::PMIN + i] = dv;
-            lds[L::PMAX + i] = dv;
+        if (dtid >= 0 && dtid < nplanes) {
+            lds[L::PMIN + dtid] = dplane;
+            lds[L::PMAX + dtid] = dplane;
         }
     } else if (p.depth_mode == D3D_DEPTH_AFFINE) {
         // hypotheses lo + k * step per pixel (two maps): each lane reads its pixels' pair ONCE, the per-plane range of the patch
@@ -415,27 +460,48 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
     const long long t_range = D3D_CLOCK();
 
     // --- plan every step of the segment ---------------------------------------------------------
-    // P1: wave (candidate, view) computes, one lane per step, that view's windows for the candidate
-    //     step size m in {4, 2, 1}; results go to a scratch table in the (still unused) ring area.
-    // P2: wave 0 picks the largest candidate whose rings fit and builds the plan / rectangle tables.
+    // One wave per source view (wave i plans view i; the other waves only follow the barriers):
+    // P1:  the view's windows for the candidate step sizes m in {4, 2, 1}, ALL candidates in one pass -- one lane per (candidate,
+    //      step): 8 + 16 + 32 lanes for a 128-plane segment; results go to a scratch table in the (still unused) ring area.
+    // P2a: every wave picks the largest candidate whose rings fit (the same few words, read by all); the view's wave writes the
+    //      view's plan entries and ring geometry and cuts the view's window deltas into rectangles, whose counts go to scratch.
+    // P2b: the view's wave sums the counts of all views (the scan over the steps is repeated per view: 6 shuffles, on another
+    //      SIMD each), and writes the view's rectangle descriptors; wave 0 also writes the step tables and the header.
+    // The tables hold the same words as when one wave built them view after view.
+    static_assert(NWAVES >= NSRC, "one planning wave per source view");
+    typedef int i4v __attribute__((ext_vector_type(4)));
+    typedef int i2v __attribute__((ext_vector_type(2)));
     constexpr int CT = L::DATA;                          // [cand][view][step][4] windows
     constexpr int CHD = CT + NCAND * NSRC * 64 * 4;      // [cand][view][4]: RW, RH, bad, nsteps
+    constexpr int CNT = CHD + NCAND * NSRC * 4;          // [view][step][2]: non-empty delta rectangles, positions to stage
+    constexpr int FLG = CNT + NSRC * 64 * 2;             // [cand]: 1 = the candidate's staging work fits the descriptors
     // candidate c steps by NSUB*4, NSUB*2, NSUB, NSUB/2 planes (the last leaves half the sub-waves idle,
     // which is still far better than gathering from global memory)
     auto cand_planes = [](int c) { return c < 3 ? NSUB * (4 >> c) : max(NSUB / 2, 1); };
-    auto candidate_windows = [&](int cand, int vsel) {
+    auto cand_steps = [&](int c) { const int SPc = cand_planes(c); return (nplanes + SPc - 1) / SPc; };
+    // windows of view vsel for the candidates [c_lo, c_hi), whose steps share the wave's lanes: candidate c_lo's first, then the
+    // next one's (the caller has checked that they fit 64 lanes; an infeasible candidate takes none)
+    auto candidate_windows = [&](int c_lo, int c_hi, int vsel) {
         {
-            const int SPc = cand_planes(cand);
-            const int nstepc = (nplanes + SPc - 1) / SPc;
-            const bool feasible = nstepc <= MAXSTEPS;
-            const bool act = feasible && lane < nstepc;
-            const int p0 = min(lane * SPc, nplanes - 1), p1 = min(lane * SPc + SPc, nplanes);
+            int myc = -1, st = 0;
+            for (int c = c_lo, off = 0; c < c_hi; ++c) {
+                const int n = cand_steps(c) <= MAXSTEPS ? cand_steps(c) : 0;
+                if (lane >= off && lane < off + n) { myc = c; st = lane - off; }
+                off += n;
+            }
+            const bool act = myc >= 0;
+            const int SPc = cand_planes(act ? myc : c_lo);
+            const int p0 = min(st * SPc, nplanes - 1), p1 = min(st * SPc + SPc, nplanes);
+            // depth range of the step's planes: independent reads (an index past the step repeats its last plane: min and max
+            // are exact and idempotent, so the range has the same bits as a loop over [p0, p1) has)
             float lo = INFINITY, hi = -INFINITY;
-            for (int i = p0; i < p1; ++i) {
+#pragma unroll
+            for (int j = 0; j < NSUB * 4; ++j) {
+                const int i = min(p0 + j, p1 - 1);
                 lo = fminf(lo, lds[L::PMIN + i]);
                 hi = fmaxf(hi, lds[L::PMAX + i]);
             }
-            const float* __restrict__ M = p.proj34 + 12 * min(vsel, p.n_src - 1);
+            const float* M = mw;   // (vsel is this wave's view: rows of p.proj34 + 12 * min(vsel, p.n_src - 1), requested at the top)
             float umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
             bool ok = true;
 #pragma unroll
@@ -470,39 +536,51 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
             {
                 const int qx0 = __shfl_up(wx0, 1), qy0 = __shfl_up(wy0, 1);
                 const int qw = __shfl_up(ww, 1), qh = __shfl_up(wh, 1);
-                if (lane > 0 && act && qw > 0 && ww > 0) {
+                if (st > 0 && act && qw > 0 && ww > 0) {   // (st > 0: the lane below holds the candidate's previous step)
                     ux = max(wx0 + ww, qx0 + qw) - min(wx0, qx0);
                     uy = max(wy0 + wh, qy0 + qh) - min(wy0, qy0);
                 }
             }
-            const int RWc = max(wave_maxi(ux), 1), RHc = max(wave_maxi(uy), 1);
-            const int badc = (__any(!ok) || !feasible) ? 1 : 0;  // p.z <= 0 somewhere: cannot bound the frustum
-            int* e = ldsi + CT + ((cand * NSRC + vsel) * 64 + lane) * 4;
-            e[0] = wx0; e[1] = wy0; e[2] = ww; e[3] = wh;
-            if (lane == 0) {
-                int* hd = ldsi + CHD + (cand * NSRC + vsel) * 4;
-                hd[0] = RWc; hd[1] = RHc; hd[2] = badc; hd[3] = nstepc;
+            if (act) *reinterpret_cast<i4v*>(ldsi + CT + ((myc * NSRC + vsel) * 64 + st) * 4) = (i4v){wx0, wy0, ww, wh};
+            // ring size and "bad" flag of each candidate: maxima over its lanes, taken by the LDS (a wave's LDS instructions
+            // execute in order: lane 0's initial words are there before the first maximum arrives)
+            if (lane == 0)
+                for (int c = c_lo; c < c_hi; ++c)
+                    *reinterpret_cast<i4v*>(ldsi + CHD + (c * NSRC + vsel) * 4) = (i4v){1, 1, cand_steps(c) > MAXSTEPS ? 1 : 0, cand_steps(c)};
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            if (act) {
+                int* hd = ldsi + CHD + (myc * NSRC + vsel) * 4;
+                atomicMax(hd + 0, ux);
+                atomicMax(hd + 1, uy);
+                if (!ok) atomicOr(hd + 2, 1);  // p.z <= 0 somewhere: cannot bound the frustum
             }
         }
     };
-    // the three regular candidates first (one round: NWAVES = 3 * 4 waves); the half-step candidate only when none
-    // of them fits (rare: very wide plane spacing)
-    constexpr int NCAND1 = NCAND - 1;
-    for (int wk = wave; wk < NCAND1 * NSRC; wk += NWAVES) candidate_windows(wk / NSRC, wk % NSRC);
-    __syncthreads();
-    const long long t_p1 = D3D_CLOCK();
-    auto plan_tables = [&](int cbeg, int cend) {  // wave 0: first candidate in [cbeg, cend) whose rings fit
+    long long t_p1 = 0;
+    // One planning round over the candidates [cbeg, cend): every wave runs it (the same barriers), returns 1 when the rings are planned.
+    auto plan_round = [&](int cbeg, int cend) -> int {
+        if (wave < NSRC) {
+            int lanes = 0;
+            for (int c = cbeg; c < cend; ++c) lanes += cand_steps(c) <= MAXSTEPS ? cand_steps(c) : 0;
+            if (lanes <= 64) {
+                candidate_windows(cbeg, cend, wave);
+            } else {   // (segments longer than any launched: one candidate at a time)
+                for (int c = cbeg; c < cend; ++c) candidate_windows(c, c + 1, wave);
+            }
+        }
+        __syncthreads();
+        if (cbeg == 0) t_p1 = D3D_CLOCK();
         int mode = 0, sp_sel = NSUB, nsteps_sel = (nplanes + NSUB - 1) / NSUB;
-        for (int cand = cbeg; cand < cend && !mode; ++cand) {
-            const int nsteps = ldsi[CHD + (cand * NSRC) * 4 + 3];
+        for (int cand = cbeg; cand < cend && !mode; ++cand) {   // first candidate whose rings fit and whose deltas can be described
+            const int nsteps = rfl(ldsi[CHD + (cand * NSRC) * 4 + 3]);
             const bool act = lane < nsteps;
-            int wx0[NSRC], wy0[NSRC], ww[NSRC], wh[NSRC], RW[NSRC], RH[NSRC];
+            int RW[NSRC], RH[NSRC];
             int bad = 0, total = 0, totalq = 0;
             int RWq[NSRC], RHq[NSRC];   // rounded up for the bank layout (any size >= the union span is valid)
 #pragma unroll
             for (int i = 0; i < NSRC; ++i) {
-                const int* hd = ldsi + CHD + (cand * NSRC + i) * 4;
-                RW[i] = hd[0]; RH[i] = hd[1]; bad |= hd[2];
+                const i4v hd = *reinterpret_cast<const i4v*>(ldsi + CHD + (cand * NSRC + i) * 4);
+                RW[i] = rfl(hd[0]); RH[i] = rfl(hd[1]); bad |= rfl(hd[2]);
                 RWq[i] = (RW[i] + RING_RW_QUANT - 1) / RING_RW_QUANT * RING_RW_QUANT;
                 RHq[i] = (RH[i] + RING_RH_QUANT - 1) / RING_RH_QUANT * RING_RH_QUANT;
                 total += ring_row_floats<STRIDE>(RW[i]) * (RH[i] + 1);
@@ -514,132 +592,146 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
                 for (int i = 0; i < NSRC; ++i) { RW[i] = RWq[i]; RH[i] = RHq[i]; }
             }
             if (bad || total > a.cap_floats) continue;
-#pragma unroll
-            for (int i = 0; i < NSRC; ++i) {
-                const int* e = ldsi + CT + ((cand * NSRC + i) * 64 + lane) * 4;
-                wx0[i] = e[0]; wy0[i] = e[1]; ww[i] = e[2]; wh[i] = e[3];
-            }
-            if (!bad && total <= a.cap_floats) {
-                mode = 1;
-                sp_sel = cand_planes(cand);
-                nsteps_sel = nsteps;
+            sp_sel = cand_planes(cand);
+            nsteps_sel = nsteps;
+            // this wave's view: its ring (the rings follow each other from L::DATA on)
+            int RWv = 1, RHv = 1, basev = L::DATA;
+            bool dims_ok = true;
+            {
                 int base = L::DATA;
-                int oxv[NSRC], oyv[NSRC], basev[NSRC];
-                bool dims_ok = true;
 #pragma unroll
                 for (int i = 0; i < NSRC; ++i) {
-                    // ring coordinates are taken relative to the first step's window origin
-                    const int cx0 = __shfl(wx0[i], 0), cy0 = __shfl(wy0[i], 0);
-                    oxv[i] = posmod(wx0[i] - cx0, RW[i]);
-                    oyv[i] = posmod(wy0[i] - cy0, RH[i]);
-                    basev[i] = base;
+                    if (i == wave) { RWv = RW[i]; RHv = RH[i]; basev = base; }
                     dims_ok = dims_ok && RW[i] < 256 && RH[i] < 256;
-                    if (act) {
-                        int* e = ldsi + L::PLAN + (lane * NSRC + i) * 8;
-                        e[0] = wx0[i]; e[1] = wy0[i]; e[2] = ww[i]; e[3] = wh[i];
-                        e[4] = oxv[i];
-                        e[5] = oyv[i];
-                        e[6] = oxv[i] - wx0[i];   // ring column of source column 0 (geo_ring's kx, ky)
-                        e[7] = oyv[i] - wy0[i];
-                    }
-                    if (lane == 0) {
-                        ldsi[L::HDR + 4 + 4 * i + 0] = RW[i];
-                        ldsi[L::HDR + 4 + 4 * i + 1] = RH[i];
-                        ldsi[L::HDR + 4 + 4 * i + 2] = base;
-                        ldsi[L::HDR + 4 + 4 * i + 3] = RW[i] | (RH[i] << 8) | ((base >> 2) << 16);
-                        if constexpr (VIEW_MAJOR) {   // the plane loop reads its per-view constants back from here (see `geometry`)
-                            const float* __restrict__ M = p.proj34 + 12 * min(i, p.n_src - 1);
-                            const bool dummy = i >= p.n_src;   // unused view of the template: every sample at (-1, -1)
-                            lds[L::VT + 8 * i + 0] = dummy ? -1.0f : M[3];
-                            lds[L::VT + 8 * i + 1] = dummy ? -1.0f : M[7];
-                            lds[L::VT + 8 * i + 2] = dummy ? 1.0f : M[11];
-                            lds[L::VT + 8 * i + 3] = 0.0f;
-                            ldsi[L::VT + 8 * i + 4] = RW[i];
-                            ldsi[L::VT + 8 * i + 5] = RH[i];
-                            ldsi[L::VT + 8 * i + 6] = ring_row_floats<STRIDE>(RW[i]) * 4;
-                            ldsi[L::VT + 8 * i + 7] = lds_base_bytes(lds) + 4 * base;
-                        }
-                    }
                     base += ring_row_floats<STRIDE>(RW[i]) * (RH[i] + 1);
+                }
+            }
+            int wx0 = 0, wy0 = 0, oxv = 0, oyv = 0;
+            int rx[4], ry[4], rwid[4], nel[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { rx[r] = 0; ry[r] = 0; rwid[r] = 0; nel[r] = 0; }
+            if (wave < NSRC) {
+                const int vi = wave;
+                const i4v e = *reinterpret_cast<const i4v*>(ldsi + CT + ((cand * NSRC + vi) * 64 + lane) * 4);
+                // (lanes past the last step hold no window: they stage nothing and write no entry)
+                wx0 = act ? e[0] : 0; wy0 = act ? e[1] : 0;
+                const int ww = act ? e[2] : 0, wh = act ? e[3] : 0;
+                // ring coordinates are taken relative to the first step's window origin
+                const int cx0 = __shfl(wx0, 0), cy0 = __shfl(wy0, 0);
+                oxv = posmod(wx0 - cx0, RWv);
+                oyv = posmod(wy0 - cy0, RHv);
+                if (act) {
+                    int* pe = ldsi + L::PLAN + (lane * NSRC + vi) * 8;
+                    *reinterpret_cast<i4v*>(pe) = (i4v){wx0, wy0, ww, wh};
+                    // oxv - wx0: ring column of source column 0 (geo_ring's kx, ky)
+                    *reinterpret_cast<i4v*>(pe + 4) = (i4v){oxv, oyv, oxv - wx0, oyv - wy0};
+                }
+                if (lane == 0) {
+                    *reinterpret_cast<i4v*>(ldsi + L::HDR + 4 + 4 * vi) = (i4v){RWv, RHv, basev, RWv | (RHv << 8) | ((basev >> 2) << 16)};
+                    if constexpr (VIEW_MAJOR) {   // the plane loop reads its per-view constants back from here (see `geometry`)
+                        const float* __restrict__ M = p.proj34 + 12 * min(vi, p.n_src - 1);
+                        const bool dummy = vi >= p.n_src;   // unused view of the template: every sample at (-1, -1)
+                        lds[L::VT + 8 * vi + 0] = dummy ? -1.0f : M[3];
+                        lds[L::VT + 8 * vi + 1] = dummy ? -1.0f : M[7];
+                        lds[L::VT + 8 * vi + 2] = dummy ? 1.0f : M[11];
+                        lds[L::VT + 8 * vi + 3] = 0.0f;
+                        ldsi[L::VT + 8 * vi + 4] = RWv;
+                        ldsi[L::VT + 8 * vi + 5] = RHv;
+                        ldsi[L::VT + 8 * vi + 6] = ring_row_floats<STRIDE>(RWv) * 4;
+                        ldsi[L::VT + 8 * vi + 7] = lds_base_bytes(lds) + 4 * basev;
+                    }
                 }
                 // ---- staging items of every step: window(k) minus window(k-1) as <= 4 rectangles per
                 // view, cut into items of 64 positions (all CH channels of the group).
-                int cnt[NSRC][4], rx[NSRC][4], ry[NSRC][4], rwid[NSRC][4], nel[NSRC][4];
-                int npos = 0;   // positions this step stages
+                const int xa = wx0, xb = wx0 + ww - 1, ya = wy0, yb = wy0 + wh - 1;
+                const int pxa = __shfl_up(wx0, 1), pya = __shfl_up(wy0, 1);
+                const int pxb = pxa + __shfl_up(ww, 1) - 1, pyb = pya + __shfl_up(wh, 1) - 1;
+                int ix0 = 1, ix1 = 0, iy0 = 1, iy1 = 0;  // intersection with the previous window
+                if (lane > 0) { ix0 = max(xa, pxa); ix1 = min(xb, pxb); iy0 = max(ya, pya); iy1 = min(yb, pyb); }
+                const bool ov = (ix0 <= ix1) && (iy0 <= iy1);
+                // left | right | top | bottom; without overlap "left" is the whole window
+                int rh_[4];
+                rx[0] = xa;      ry[0] = ya;      rwid[0] = (ov ? ix0 - 1 : xb) - xa + 1; rh_[0] = wh;
+                rx[1] = ix1 + 1; ry[1] = ya;      rwid[1] = ov ? xb - ix1 : 0;             rh_[1] = wh;
+                rx[2] = ix0;     ry[2] = ya;      rwid[2] = ov ? ix1 - ix0 + 1 : 0;        rh_[2] = ov ? iy0 - ya : 0;
+                rx[3] = ix0;     ry[3] = iy1 + 1; rwid[3] = ov ? ix1 - ix0 + 1 : 0;        rh_[3] = ov ? yb - iy1 : 0;
+                int nrect_v = 0, npos_v = 0;   // non-empty rectangles | positions this view stages in the step
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    nel[r] = act ? max(rwid[r], 0) * max(rh_[r], 0) : 0;
+                    nrect_v += nel[r] > 0 ? 1 : 0;
+                    npos_v += nel[r];
+                }
+                *reinterpret_cast<i2v*>(ldsi + CNT + (vi * 64 + lane) * 2) = (i2v){nrect_v, npos_v};
+            }
+            __syncthreads();
+            if (wave < NSRC) {
+                const int vi = wave;
+                int nrect = 0, npos = 0;     // of the step, all views
+                int idx = 0, pstart = 0;     // of the views before this one
 #pragma unroll
                 for (int i = 0; i < NSRC; ++i) {
-                    const int xa = wx0[i], xb = wx0[i] + ww[i] - 1, ya = wy0[i], yb = wy0[i] + wh[i] - 1;
-                    const int pxa = __shfl_up(wx0[i], 1), pya = __shfl_up(wy0[i], 1);
-                    const int pxb = pxa + __shfl_up(ww[i], 1) - 1, pyb = pya + __shfl_up(wh[i], 1) - 1;
-                    int ix0 = 1, ix1 = 0, iy0 = 1, iy1 = 0;  // intersection with the previous window
-                    if (lane > 0) { ix0 = max(xa, pxa); ix1 = min(xb, pxb); iy0 = max(ya, pya); iy1 = min(yb, pyb); }
-                    const bool ov = (ix0 <= ix1) && (iy0 <= iy1);
-                    // left | right | top | bottom; without overlap "left" is the whole window
-                    int rh_[4];
-                    rx[i][0] = xa;      ry[i][0] = ya;      rwid[i][0] = (ov ? ix0 - 1 : xb) - xa + 1; rh_[0] = wh[i];
-                    rx[i][1] = ix1 + 1; ry[i][1] = ya;      rwid[i][1] = ov ? xb - ix1 : 0;             rh_[1] = wh[i];
-                    rx[i][2] = ix0;     ry[i][2] = ya;      rwid[i][2] = ov ? ix1 - ix0 + 1 : 0;        rh_[2] = ov ? iy0 - ya : 0;
-                    rx[i][3] = ix0;     ry[i][3] = iy1 + 1; rwid[i][3] = ov ? ix1 - ix0 + 1 : 0;        rh_[3] = ov ? yb - iy1 : 0;
+                    const i2v c = *reinterpret_cast<const i2v*>(ldsi + CNT + (i * 64 + lane) * 2);
+                    nrect += c[0]; npos += c[1];
+                    if (i < vi) { idx += c[0]; pstart += c[1]; }
+                }
+                // scan over the steps, bit by bit of the counts (<= 4 * NSRC < 32): a ballot and a count of the lanes below per bit,
+                // no trip through the LDS crossbar
+                int incl = nrect, total_rects = 0;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        nel[i][r] = act ? max(rwid[i][r], 0) * max(rh_[r], 0) : 0;
-                        cnt[i][r] = (nel[i][r] + 63) >> 6;
-                        npos += nel[i][r];
+                for (int bit = 0; bit < 5; ++bit) {
+                    const unsigned long long m = __ballot((nrect >> bit) & 1);
+                    incl += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) << bit;
+                    total_rects += __popcll(m) << bit;
+                }
+                // (field widths of the descriptors: a step stages < 65536 positions, windows are < 4096 wide)
+                // if they do not hold: cannot describe the staging work -- the next candidate, or gather from global memory instead
+                const bool fits = !(total_rects > MAXRECTS || !dims_ok || __any(npos > 0xffff) || w > 0xfff0 || h > 0xfff0);
+                if (fits) {
+                    idx += incl - nrect;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (nel[r] > 0) {
+                            *reinterpret_cast<i4v*>(ldsi + L::RECTS + 4 * idx) =
+                                (i4v){(rx[r] + 1) | ((ry[r] + 1) << 16),   // windows start at >= -1
+                                      rwid[r] | (vi << 12) | (pstart << 16),
+                                      nel[r],
+                                      // ring coordinates of the rect origin (unwrapped: < 2*RW, 2*RH)
+                                      (rx[r] - wx0 + oxv) | ((ry[r] - wy0 + oyv) << 16)};
+                            pstart += nel[r];
+                            ++idx;
+                        }
+                    if (vi == 0) {
+                        if (act) {
+                            ldsi[L::SST + lane] = incl - nrect;
+                            ldsi[L::STOT + lane] = npos;
+                        }
+                        if (lane == nsteps - 1) ldsi[L::SST + nsteps] = incl;
+                        if (lane == 0) {
+                            ldsi[L::HDR + 0] = 1;
+                            ldsi[L::HDR + 1] = sp_sel;
+                            ldsi[L::HDR + 2] = nsteps_sel;
+                        }
                     }
                 }
-                int nrect = 0;
-#pragma unroll
-                for (int i = 0; i < NSRC; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) nrect += cnt[i][r] > 0 ? 1 : 0;
-                int incl = nrect;
-#pragma unroll
-                for (int sft = 1; sft < 64; sft <<= 1) {
-                    int o = __shfl_up(incl, sft);
-                    if (lane >= sft) incl += o;
-                }
-                const int total_rects = __shfl(incl, 63);
-                // (field widths of the descriptors: a step stages < 65536 positions, windows are < 4096 wide)
-                if (total_rects > MAXRECTS || !dims_ok || __any(npos > 0xffff) || w > 0xfff0 || h > 0xfff0) {
-                    mode = 0;  // cannot describe the staging work: gather from global memory instead
-                } else {
-                    int idx = incl - nrect;
-                    if (act) ldsi[L::SST + lane] = idx;
-                    if (lane == nsteps - 1) ldsi[L::SST + nsteps] = incl;
-                    int pstart = 0;
-#pragma unroll
-                    for (int i = 0; i < NSRC; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (cnt[i][r] > 0) {
-                                int* e = ldsi + L::RECTS + 4 * idx;
-                                e[0] = (rx[i][r] + 1) | ((ry[i][r] + 1) << 16);   // windows start at >= -1
-                                e[1] = rwid[i][r] | (i << 12) | (pstart << 16);
-                                e[2] = nel[i][r];
-                                // ring coordinates of the rect origin (unwrapped: < 2*RW, 2*RH)
-                                e[3] = (rx[i][r] - wx0[i] + oxv[i]) | ((ry[i][r] - wy0[i] + oyv[i]) << 16);
-                                pstart += nel[i][r];
-                                ++idx;
-                            }
-                    if (act) ldsi[L::STOT + lane] = pstart;
-                }
+                if (vi == 0 && lane == 0) ldsi[FLG + cand] = fits ? 1 : 0;
             }
+            __syncthreads();
+            mode = rfl(ldsi[FLG + cand]);
         }
-        if (lane == 0) {
-            ldsi[L::HDR + 0] = mode;
-            ldsi[L::HDR + 1] = sp_sel;
-            ldsi[L::HDR + 2] = nsteps_sel;
+        if (!mode) {   // (workgroup-uniform) no rings: the header says so, with the step of the last candidate that fitted, if any
+            if (tid == 0) {
+                ldsi[L::HDR + 0] = 0;
+                ldsi[L::HDR + 1] = sp_sel;
+                ldsi[L::HDR + 2] = nsteps_sel;
+            }
+            __syncthreads();
         }
+        return mode;
     };
-    if (wave == 0) plan_tables(0, NCAND1);
-    __syncthreads();
-    if (rfl(ldsi[L::HDR + 0]) == 0) {  // (workgroup-uniform)
-        __syncthreads();  // everyone has read the header before wave 0 rewrites it
-        for (int wk = wave; wk < NSRC; wk += NWAVES) candidate_windows(NCAND1, wk);
-        __syncthreads();
-        if (wave == 0) plan_tables(NCAND1, NCAND);
-        __syncthreads();
-    }
+    // the three regular candidates first; the half-step candidate only when none of them fits (rare: very wide plane spacing)
+    constexpr int NCAND1 = NCAND - 1;
+    if (plan_round(0, NCAND1) == 0) plan_round(NCAND1, NCAND);
     if (D3D_STAMPS && a.tstats && tid == 0) {  // prologue phases: depth range | windows of every candidate | plan + rectangle tables
         const long long t_p2 = clock64();
         atomicAdd(a.tstats + 16, (unsigned long long)(t_range - t_start));
@@ -660,8 +752,9 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
         }
     }
     // ---------------------------------------------------------------------------------------
-    // Delta staging: step k owns the item descriptors [sst[k], sst[k+1]); wave wv takes items
-    // wv, wv + NWAVES, ...; the first PFD of them are prefetched one step ahead.
+    // Delta staging: step k owns the rectangle descriptors [sst[k], sst[k+1]), whose positions are cut into items of 64;
+    // wave sw of the snw waves that share the step takes the items sw, sw + snw, ..., PFD of them per round: the loads of
+    // a round are all requested before the first of them is written to the rings.  Step k + 1 is staged while step k is swept.
     // ---------------------------------------------------------------------------------------
     struct Item {
         const float* g;  // global address of the group's first channel (always dereferenceable)
@@ -934,9 +1027,10 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
     // --- per-lane constants: rays, reference features, weights -------------------------------
     if constexpr (!EARLY_INPUTS) {
         projection_rows();
-        lane_inputs();
+        lane_inputs(false);
     } else {
-        if (loader) lane_inputs();   // (gather mode: the loader waves sweep planes, and skipped their inputs above)
+        if (loader) lane_inputs(false);   // (gather mode: the loader waves sweep planes, and skipped their inputs above)
+        else finish_inputs();
     }
     RingView RV[NSRC];
     const int lds0 = lds_base_bytes(lds);
@@ -1244,7 +1338,7 @@ __global__ __launch_bounds__(64 * (NPIXW * NSUB + NLOADW), 3) void sweep_tiled_k
     for (int gi = 0; gi < a.ngroups; ++gi) {
         grp = gi;
         c0 = gi * CH;
-        if (gi > 0) load_reference();   // (group 0: requested ahead of the planning)
+        if (gi > 0) load_reference(false);   // (group 0: requested ahead of the planning)
         if (!ring) {
             // GATHER_ALL: taps straight from global memory, no windows, no steps, no barriers inside the pass: every wave of the
             // workgroup (the loader waves too) takes planes sub, sub + NW, ... of its pixel rows
@@ -1439,15 +1533,20 @@ static int launch_one(const SweepParams& p, hipStream_t stream) {
         if (sizeof(T) == 2 && !a.cl) return D3D_ERR_UNSUPPORTED;
     }
 #ifdef D3D_EXPERIMENTS
-    if (getenv("D3D_TILED_STATS")) {  // debug only: synchronous, allocates
-        (void)hipMalloc(&a.stats, 12 * sizeof(unsigned) + 24 * sizeof(unsigned long long));
-        (void)hipMemset(a.stats, 0, 12 * sizeof(unsigned) + 24 * sizeof(unsigned long long));
-        a.tstats = reinterpret_cast<unsigned long long*>(a.stats + 12);
+    unsigned* stats_buf = nullptr;
+    if (const char* e = getenv("D3D_TILED_STATS")) {  // debug only: synchronous, allocates
+        (void)hipMalloc(&stats_buf, 12 * sizeof(unsigned) + 24 * sizeof(unsigned long long));
+        (void)hipMemset(stats_buf, 0, 12 * sizeof(unsigned) + 24 * sizeof(unsigned long long));
+        a.tstats = reinterpret_cast<unsigned long long*>(stats_buf + 12);
+        // D3D_TILED_STATS=2: the cycle stamps alone.  The plan and staging counters are atomics of every wave and step on a
+        // dozen words: with them the headline kernel takes 60 ms instead of 5.7 and the stamps time the atomics.
+        if (atoi(e) != 2) a.stats = stats_buf;
     }
 #endif
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(THREADSK), LDS_BYTES, stream, p, a);
     D3D_LAUNCH_CHECK("sweep_tiled_kernel launch");
 #ifdef D3D_EXPERIMENTS
+    a.stats = stats_buf;
     if (a.stats) {
         unsigned hs[12];
         unsigned long long ht[24];
