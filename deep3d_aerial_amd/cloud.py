@@ -29,8 +29,11 @@ Resample_PC would.  The rule below is this project's own; it does not claim to m
 * File.  Binary little-endian PLY: x y z float, nx ny nz float when there are normals, red green blue uchar when there are colours,
   count int.  MeshLab and CloudCompare read this layout.
 
-Out of scope: statistical (k-nearest-neighbour) outlier removal; weighting by confidence or by nviews; the per-point view lists of
-the .mvs format; LAS output; feeding the merged cloud to the DSM.
+* Outliers.  settings["outliers"] = {"radius", "k", "alpha", "min_neighbours"} (cloud_outliers.py, off by default) filters the merged
+  cloud between the merge and the file: statistical and radius outlier removal on capped k-nearest-neighbour distances.
+
+Out of scope: weighting by confidence or by nviews; the per-point view lists of the .mvs format; LAS output; feeding the merged
+cloud to the DSM.
 
 The kernels are HIP (csrc/cloud.hip); the sort of the keys is torch.sort (plumbing, as in texture.py).  Integer atomicAdd only, so
 the cloud is bit-reproducible.
@@ -228,7 +231,8 @@ def read_cloud_ply(path):
 # settings and command line
 # ----------------------------------------------------------------------------------------
 def check_settings(settings):
-    """The settings dict {"path", "border", "voxel", "min_points"} checked: (CloudGrid, min_points).  No GPU work."""
+    """The settings dict {"path", "border", "voxel", "min_points"} checked: (CloudGrid, min_points); an "outliers" key, when
+    there is one, is checked as cloud_outliers.check_settings checks it, on the cloud's border.  No GPU work."""
     if not isinstance(settings, dict):
         raise ValueError("the cloud settings must be a dict (got %r)" % (settings,))
     path = settings.get("path")
@@ -243,6 +247,13 @@ def check_settings(settings):
     k = 1 if k is None else k
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) < 1 << 31:
         raise ValueError("cloud min_points must be an integer in 1 .. 2^31 - 1 (got %r)" % (k,))
+    if settings.get("outliers") is not None:
+        from . import cloud_outliers
+
+        try:
+            CloudGrid(grid.border, cloud_outliers.check_settings(settings["outliers"])[0])
+        except ValueError as e:
+            raise ValueError("cloud outliers: %s" % e)
     return grid, int(k)
 
 
@@ -274,11 +285,20 @@ def summary(cloud, n_points):
 
 def build_and_write(xyz, normal, color, settings):
     """merge_points with the settings dict on device tensors, written with write_cloud_ply to settings["path"]:
-    (cloud dict, summary)."""
+    (cloud dict, summary).  With settings["outliers"] the merged cloud passes cloud_outliers.filter_cloud on the cloud's border
+    before it is written, and the summary (of the written cloud) gains "outliers": the filter's info."""
     grid, k = check_settings(settings)
     cloud = merge_points(xyz, normal, color, grid, k)
+    info = None
+    if settings.get("outliers") is not None:
+        from . import cloud_outliers
+
+        cloud, info = cloud_outliers.filter_cloud(cloud, settings["outliers"], grid.border)
     write_cloud_ply(settings["path"], cloud["xyz"], cloud["normal"], cloud["color"], cloud["count"])
-    return cloud, summary(cloud, xyz.shape[0])
+    s = summary(cloud, xyz.shape[0])
+    if info is not None:
+        s["outliers"] = info
+    return cloud, s
 
 
 def read_fused(folder):

@@ -124,7 +124,9 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     the xyz, normal and colour of its results, one sharding.gather_points call moves them to rank 0 as one [n, 9] tensor (the
     colours bit-cast), and rank 0 merges them on the voxel grid and writes the PLY (write_cloud_of); timings gets cloud_s.  With
     filter_sources=False the file does not depend on the number of ranks.  The crops are the sweeping rank's, so with more than
-    one rank fuse_partition must be "views"."""
+    one rank fuse_partition must be "views".  With cloud["outliers"] ({"radius", "k", "alpha", "min_neighbours"}; absent or None:
+    off) rank 0 filters the merged cloud before it writes it (cloud_outliers.filter_cloud, checked up front with the cloud
+    settings): no new collective; timings gets cloud_outliers, the filter's info."""
     if mesh is not None:
         from . import mesh as _mesh
 
@@ -534,6 +536,8 @@ def write_cloud_of(results, settings, rank=0, world_size=1, device="cuda", timin
     torch.cuda.synchronize()
     if timings is not None:
         timings["cloud_s"] = time.perf_counter() - t0
+        if res is not None and "outliers" in res[1]:
+            timings["cloud_outliers"] = res[1]["outliers"]   # the filter's info, for the caller's report
     return res
 
 

@@ -597,6 +597,10 @@ def parse_args(argv=None):
     ap.add_argument("--cloud", default=None,
                     help="with --fuse: merge all ranks' fused points on a voxel grid into this coloured .ply, on rank 0")
     _cloud.add_arguments(ap, prefix="cloud_")
+    # outlier removal on the merged cloud (deep3d_aerial_amd/cloud_outliers.py): off unless --cloud_outlier_radius is given
+    from . import cloud_outliers as _outliers
+
+    _outliers.add_arguments(ap, prefix="cloud_outlier_")
     a = ap.parse_args(argv)
     if a.dsm is not None and not a.fuse:
         ap.error("--dsm needs --fuse (the DSM is built from the fused points)")
@@ -660,9 +664,13 @@ def parse_args(argv=None):
         if a.fuse_partition == "scene_blocks":
             ap.error("--cloud needs --fuse_partition views (the colours come from the reference crops of the rank that swept the view)")
         try:
-            _cloud.check_settings(_cloud.settings_from_args(a, a.cloud, prefix="cloud_"))
+            _cloud.check_settings(_cloud_settings(a))
         except ValueError as e:
             ap.error("--cloud*: %s" % e)
+    if a.cloud_outlier_radius is None and _outliers.given(a, prefix="cloud_outlier_"):
+        ap.error("--cloud_outlier_%s needs --cloud_outlier_radius (it turns the outlier removal on)" % _outliers.given(a, prefix="cloud_outlier_")[0])
+    if a.cloud_outlier_radius is not None and a.cloud is None:
+        ap.error("--cloud_outlier_radius needs --cloud (it is the merged cloud that is cleaned)")
     return a
 
 
@@ -724,7 +732,12 @@ def _texture_settings(a):
 def _cloud_settings(a):
     from . import cloud as _cloud
 
-    return _cloud.settings_from_args(a, a.cloud, prefix="cloud_")
+    s = _cloud.settings_from_args(a, a.cloud, prefix="cloud_")
+    if getattr(a, "cloud_outlier_radius", None) is not None:
+        from . import cloud_outliers as _outliers
+
+        s["outliers"] = _outliers.settings_from_args(a, prefix="cloud_outlier_")
+    return s
 
 
 def main(argv=None):
@@ -782,6 +795,9 @@ def main(argv=None):
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
         if a.cloud is not None and rank == 0:
             print("rank 0/%d: merged point cloud %s in %.2f s" % (world, a.cloud, tm["cloud_s"]))
+            if "cloud_outliers" in tm:
+                o = tm["cloud_outliers"]
+                print("rank 0/%d: cloud outliers: kept %d of %d points, dropped %d" % (world, o["kept"], o["points"], o["points"] - o["kept"]))
         if a.dsm is not None and rank == 0:
             print("rank 0/%d: DSM %s in %.2f s" % (world, a.dsm, tm["dsm_s"]))
         if a.ortho is not None and rank == 0:

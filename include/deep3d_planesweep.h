@@ -966,6 +966,34 @@ int d3d_cloud_finalize(const long long* ukeys, const int* count, const long long
                        d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.28 -- outlier removal on a point cloud by capped k-nearest-neighbour distances.  The rule is this project's
+ * (deep3d_aerial_amd/cloud_outliers.py); it does not claim to match any tool.
+ *   Grid: the cloud's grid above with voxel = the radius h: one cell is one radius wide.  A point is keyed by d3d_cloud_keys,
+ *   the single copy of the keying rule; a point it drops (key INT64_MAX) is unkeyed: dist = -1, nn = -1, nobody's neighbour,
+ *   not in the sums.
+ *   Per keyed point i, over every other keyed point j (j != i by index: a duplicate of i at distance 0 counts):
+ *     d2 = (dx dx + dy dy) + dz dz in fp64, dx = (double)x_i - (double)x_j, each operation rounded once; cap2 = h h.
+ *     e_ij = 1024 when d2 >= cap2, else min(1024, llrint(sqrt(d2) / h * 1024.0)).
+ *     nn_i = the number of j with d2 < cap2.
+ *     dist_i = D_i = the sum of the k smallest e_ij, a missing neighbour (fewer than k candidates) counting 1024: an integer in
+ *     0 .. 1024 k, which neither the order nor the tie-breaking of the selection can change.  A point within h lies in the
+ *     3 x 3 x 3 cells around i's cell and anything further adds exactly 1024, so the 27-cell window is the unbounded answer.
+ *   sums [3] int64 = m (the keyed points), S1 = sum D, S2 = sum D^2 over them; k <= 32 and m < 2^31 keep S2 below 2^61.
+ * Every pointer is DEVICE memory.  The calls, in order: d3d_cloud_keys with voxel = radius (its frac output is not used), the
+ * caller's sort (sorted_keys [n], order [n] int64: sorted_keys[i] = keys[order[i]]), then
+ *   d3d_cloud_outliers_distances: dist [n] int32, nn [n] int32 in the order of xyz [n,3] fp32, and sums, which the call zeroes
+ *     on the stream (n_points = 0 launches nothing and writes nothing).  nx, ny, nz: the grid's n_a; k in 1 .. 32.
+ *   scratch: d3d_cloud_outliers_scratch_bytes(n) bytes (0 for n outside 0 .. 2^31 - 1): the coordinates in key order.
+ * The host then reads sums once and thresholds dist and nn (cloud_outliers.py).  One integer atomicAdd per workgroup and sum,
+ * no other atomics.  Null pointers (where the count is not 0), a count outside 0 .. 2^31 - 1, a bad grid, radius or k, a short
+ * scratch, overlapping buffers: D3D_ERR_INVALID_ARG before any launch.
+ */
+size_t d3d_cloud_outliers_scratch_bytes(long long n);
+int d3d_cloud_outliers_distances(const float* xyz, const long long* sorted_keys, const long long* order, long long n_points, int nx,
+                                 int ny, int nz, double radius, int k, void* scratch, size_t scratch_bytes, int* dist, int* nn,
+                                 long long* sums, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.9 -- true orthophoto on the DSM (the reference has no orthophoto step; the semantics are this project's,
  * deep3d_aerial_amd/ortho.py).  The grid is the DSM's: cell (i, j) is X = (x_min + (j + 0.5) unit_x, y_max - (i + 0.5) unit_y, h),
  * h = height[i,j] in fp64; a non-finite h is an empty cell.  A view is one d3d_ortho_view_t record in DEVICE memory, filled by
