@@ -36,9 +36,11 @@
 //            tools/cloud_outliers_bench.py --variant_library times beside this one.
 // Sums:      per wave (shuffles), then per workgroup (LDS), then one integer atomicAdd per workgroup and sum, its result unused.
 // Atomics: that integer atomicAdd, nothing else: the same bits for any input order.
+// The lower bound, the 18-bound rule, d2 and e are cloud_search.h's, shared with cloud_compare.hip.
 #include <climits>
 #include <cmath>
 
+#include "cloud_search.h"
 #include "common.h"
 #include "geom_shared.h"
 
@@ -46,9 +48,9 @@ namespace d3d {
 
 constexpr int CO_BLOCK = 256;
 constexpr int CO_WAVES = CO_BLOCK / 64;
-constexpr long long CO_AXIS_MAX = (1ll << 21) - 1;   // the largest n_a (cloud.hip)
-constexpr long long CO_DROPPED = LLONG_MAX;          // the key of an unkeyed point (cloud.hip)
-constexpr int CO_CAP = 1024;                         // e of a candidate at or past the radius, and of a missing one
+constexpr long long CO_AXIS_MAX = CLOUD_AXIS_MAX;   // the largest n_a (cloud.hip)
+constexpr long long CO_DROPPED = CLOUD_DROPPED;     // the key of an unkeyed point (cloud.hip)
+constexpr int CO_CAP = CLOUD_E_CAP;                  // e of a candidate at or past the radius, and of a missing one
 constexpr int CO_K_MAX = 32;
 
 __global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_gather_kernel(const float* __restrict__ xyz, const long long* __restrict__ order,
@@ -60,38 +62,6 @@ __global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_gather_kernel(const f
     const float bad = __int_as_float(0x7fc00000);
     sxyz[p] = ok ? make_float4(xyz[3 * src], xyz[3 * src + 1], xyz[3 * src + 2], 0.0f) : make_float4(bad, bad, bad, 0.0f);
 }
-
-// The first index in the sorted keys [lo, hi) whose key is >= k; hi when there is none.
-__device__ __forceinline__ int outl_lower(const long long* __restrict__ keys, int lo, int hi, long long k) {
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// Bound b (0 .. 17) of the cell `key`, searched in [lo, hi): range r = b / 2 is row iy + r % 3 - 1 of layer iz + r / 3 - 1, cells
-// ix - 1 .. ix + 1 clipped to the grid; an even b is its first sorted index, an odd b the index past its last.  A row outside the
-// grid: `outside` (0 and 0 make an empty range).
-__device__ __forceinline__ int outl_bound(const long long* __restrict__ keys, int lo, int hi, long long key, int b, int nx, int ny, int nz,
-                                          int outside) {
-    const int ix = (int)(key & CO_AXIS_MAX), iy = (int)((key >> 21) & CO_AXIS_MAX), iz = (int)(key >> 42);
-    const int r = b >> 1;
-    const int y = iy + r % 3 - 1, z = iz + r / 3 - 1;
-    if (y < 0 || y >= ny || z < 0 || z >= nz) return outside;
-    const long long row = ((long long)z << 42) | ((long long)y << 21);
-    return outl_lower(keys, lo, hi, (b & 1) ? (row | (long long)min(ix + 1, nx - 1)) + 1 : row | (long long)max(ix - 1, 0));
-}
-
-// d2 of the pair (a, q).
-__device__ __forceinline__ double outl_d2(const float4 a, const float4 q) {
-    const double dx = (double)a.x - (double)q.x, dy = (double)a.y - (double)q.y, dz = (double)a.z - (double)q.z;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// e of a pair with d2 < cap2.
-__device__ __forceinline__ int outl_e(double d2, double h) { return (int)min((long long)CO_CAP, llrint(sqrt(d2) / h * 1024.0)); }
 
 // Inserts d into the increasing list c and drops the largest; every index is a compile-time constant after unrolling.
 template <int K>
@@ -134,7 +104,7 @@ __device__ __forceinline__ void outl_store(const long long* __restrict__ order, 
 }
 
 #ifndef D3D_CLOUD_OUTLIERS_PLAIN
-constexpr int CO_BOUNDS = 18;   // 9 ranges, a first and a past-the-last sorted index each
+constexpr int CO_BOUNDS = CLOUD_BOUNDS;   // 9 ranges, a first and a past-the-last sorted index each
 constexpr int CO_AHEAD = 4;     // candidates loaded ahead of their use
 
 template <int K>
@@ -163,12 +133,12 @@ __global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_kernel(const long lon
     // others between them, a few steps in keys this workgroup's points lie next to.
     if (tid < 2 * CO_BOUNDS && n_cells > 0) {
         const int last = tid / CO_BOUNDS, b = tid - CO_BOUNDS * last;
-        edge[last][b] = outl_bound(keys, 0, (int)n, cell_key[last ? n_cells - 1 : 0], b, nx, ny, nz, last ? (int)n : 0);
+        edge[last][b] = cloud_bound(keys, 0, (int)n, cell_key[last ? n_cells - 1 : 0], b, nx, ny, nz, last ? (int)n : 0);
     }
     __syncthreads();
     for (int t = tid; t < CO_BOUNDS * n_cells; t += CO_BLOCK) {
         const int c = t / CO_BOUNDS, b = t - CO_BOUNDS * c;
-        bound[b][c] = outl_bound(keys, edge[0][b], edge[1][b], cell_key[c], b, nx, ny, nz, 0);
+        bound[b][c] = cloud_bound(keys, edge[0][b], edge[1][b], cell_key[c], b, nx, ny, nz, 0);
     }
     __syncthreads();
     // e does not decrease with d2 (a correctly rounded sqrt, a division by h > 0, a product and llrint are monotone), so the k
@@ -189,7 +159,7 @@ __global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_kernel(const long lon
 #pragma unroll
                 for (int u = 0; u < CO_AHEAD; ++u) {
                     if (j + u >= j1 || j + u == p) continue;
-                    const double d2 = outl_d2(a, q[u]);
+                    const double d2 = cloud_d2(a, q[u]);
                     nn += d2 < cap2 ? 1 : 0;                 // false for a NaN
                     if (d2 < top[K - 1]) outl_insert(top, d2);   // top[K - 1] <= cap2
                 }
@@ -198,7 +168,7 @@ __global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_kernel(const long lon
     }
     int dist = 0;
 #pragma unroll
-    for (int i = 0; i < K; ++i) dist += i < k ? (top[i] < cap2 ? outl_e(top[i], h) : CO_CAP) : 0;
+    for (int i = 0; i < K; ++i) dist += i < k ? (top[i] < cap2 ? cloud_e(top[i], h) : CO_CAP) : 0;
     outl_store(order, p, n, keyed, dist, nn, out_dist, out_nn);
     outl_sums(keyed, dist, red, sums);
 }
@@ -218,13 +188,13 @@ __global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_plain_kernel(const lo
         const double cap2 = h * h;
         const float4 a = sxyz[p];
         for (int r = 0; r < 9; ++r) {
-            const int j0 = outl_bound(keys, 0, (int)n, key, 2 * r, nx, ny, nz, 0), j1 = outl_bound(keys, 0, (int)n, key, 2 * r + 1, nx, ny, nz, 0);
+            const int j0 = cloud_bound(keys, 0, (int)n, key, 2 * r, nx, ny, nz, 0), j1 = cloud_bound(keys, 0, (int)n, key, 2 * r + 1, nx, ny, nz, 0);
             for (int j = j0; j < j1; ++j) {
                 if (j == p) continue;
-                const double d2 = outl_d2(a, sxyz[j]);
+                const double d2 = cloud_d2(a, sxyz[j]);
                 if (!(d2 < cap2)) continue;   // a NaN too
                 nn += 1;
-                const int e = outl_e(d2, h);
+                const int e = cloud_e(d2, h);
                 if (e >= top[k - 1]) continue;
                 int i = k - 1;
                 for (; i > 0 && top[i - 1] > e; --i) top[i] = top[i - 1];
@@ -245,22 +215,6 @@ __global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_plain_kernel(const lo
 static bool outl_count_ok(long long n) { return n >= 0 && n < (1ll << 31); }
 
 static size_t outl_scratch(long long n) { return align256((size_t)(n > 0 ? n : 1) * sizeof(float4)); }
-
-struct OutlRange {
-    const void* p;
-    size_t bytes;
-};
-
-// No two of the non-null, non-empty buffers overlap.
-static bool outl_apart(const OutlRange* r, int n) {
-    for (int a = 0; a < n; ++a)
-        for (int b = a + 1; b < n; ++b) {
-            if (!r[a].p || !r[b].p || !r[a].bytes || !r[b].bytes) continue;
-            const uintptr_t a0 = (uintptr_t)r[a].p, b0 = (uintptr_t)r[b].p;
-            if (!(a0 + r[a].bytes <= b0 || b0 + r[b].bytes <= a0)) return false;
-        }
-    return true;
-}
 
 }  // namespace d3d
 
@@ -285,8 +239,8 @@ extern "C" int d3d_cloud_outliers_distances(const float* xyz, const long long* s
     const size_t need = outl_scratch(n_points);
     D3D_REQUIRE(scratch_bytes >= need, "scratch of %zu bytes, %zu needed (d3d_cloud_outliers_scratch_bytes)", scratch_bytes, need);
     const size_t n = (size_t)n_points;
-    const OutlRange R[7] = {{xyz, n * 12}, {sorted_keys, n * 8}, {order, n * 8}, {scratch, scratch_bytes}, {dist, n * 4}, {nn, n * 4}, {sums, 24}};
-    D3D_REQUIRE(outl_apart(R, 7), "xyz, sorted_keys, order, scratch, dist, nn and sums must not alias");
+    const SearchRange R[7] = {{xyz, n * 12}, {sorted_keys, n * 8}, {order, n * 8}, {scratch, scratch_bytes}, {dist, n * 4}, {nn, n * 4}, {sums, 24}};
+    D3D_REQUIRE(search_apart(R, 7), "xyz, sorted_keys, order, scratch, dist, nn and sums must not alias");
     if (n_points == 0) return D3D_OK;
     hipStream_t st = (hipStream_t)stream;
     const int rc = hip_status(hipMemsetAsync(sums, 0, 24, st), "cloud outliers: clear sums");

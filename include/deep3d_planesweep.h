@@ -994,6 +994,39 @@ int d3d_cloud_outliers_distances(const float* xyz, const long long* sorted_keys,
                                  long long* sums, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.29 -- comparison of two point clouds by capped nearest-neighbour distances: accuracy, completeness, F-score.  The
+ * rule is this project's (deep3d_aerial_amd/cloud_compare.py); it does not claim to match any tool.
+ *   Grid: the cloud's grid above with voxel = the cap h: one cell is one cap wide.  The queries Q [n_query,3] fp32 and the
+ *   targets T [n_target,3] fp32 are both keyed by d3d_cloud_keys, the single copy of the keying rule; a point it drops (key
+ *   INT64_MAX) is unkeyed: as a query e = -1, idx = -1 and in no count; as a target nobody's neighbour.
+ *   Per keyed query i, over every keyed target j:
+ *     d2 = (dx dx + dy dy) + dz dz in fp64, dx = (double)q_x - (double)t_x, each operation rounded once; cap2 = h h.
+ *     The nearest is the j with d2 < cap2 that minimises (d2, j), j the index in T's input order: of equally distant targets
+ *     the lowest input index wins.
+ *     Found: idx_i = j and e_i = min(1024, llrint(sqrt(d2) / h * 1024.0)), the outliers' e.  None: idx_i = -1, e_i = 1024.
+ *     e does not decrease with d2, so e_i does not depend on the tie rule.  A target within h lies in the 3 x 3 x 3 cells
+ *     around the query's cell, so the 27-cell window is exact under the cap.
+ *   hist [1026] int64: hist[e], e in 0 .. 1024, counts the keyed queries that found a neighbour with that e; hist[1025] those
+ *   that found none; the sum is the number of keyed queries.
+ * Every pointer is DEVICE memory.  The calls, in order: d3d_cloud_keys with voxel = cap on either cloud (its frac output is not
+ * used), the caller's sort of either (sorted_keys [n], order [n] int64: sorted_keys[i] = keys[order[i]]), then
+ *   d3d_cloud_compare_nearest: e [n_query] int32 and idx [n_query] int32 in the order of q_xyz, and hist, which the call zeroes
+ *     on the stream.  n_query = 0 writes only the zeroed hist; n_target = 0 gives every keyed query (1024, -1) and hist[1025].
+ *     nx, ny, nz: the grid's n_a.
+ *   scratch: d3d_cloud_compare_scratch_bytes(n_query, n_target) bytes (0 when either count is outside 0 .. 2^31 - 1): the
+ *     targets as 16-byte records {x, y, z, input index} in key order.
+ * The host turns the two histograms (Q = cloud against T = reference, and the reverse) into the statistics (cloud_compare.py).
+ * One integer atomicAdd per keyed query in LDS and one per workgroup and non-empty bin in memory, no other atomics.  Null
+ * pointers (where the count is not 0), a count outside 0 .. 2^31 - 1, a bad grid or cap, a short scratch, overlapping buffers
+ * (the two clouds' arrays included): D3D_ERR_INVALID_ARG before any launch.
+ */
+size_t d3d_cloud_compare_scratch_bytes(long long n_query, long long n_target);
+int d3d_cloud_compare_nearest(const float* q_xyz, const long long* q_sorted_keys, const long long* q_order, long long n_query,
+                              const float* t_xyz, const long long* t_sorted_keys, const long long* t_order, long long n_target, int nx,
+                              int ny, int nz, double cap, void* scratch, size_t scratch_bytes, int* e, int* idx, long long* hist,
+                              d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.9 -- true orthophoto on the DSM (the reference has no orthophoto step; the semantics are this project's,
  * deep3d_aerial_amd/ortho.py).  The grid is the DSM's: cell (i, j) is X = (x_min + (j + 0.5) unit_x, y_max - (i + 0.5) unit_y, h),
  * h = height[i,j] in fp64; a non-finite h is an empty cell.  A view is one d3d_ortho_view_t record in DEVICE memory, filled by
