@@ -1027,6 +1027,42 @@ int d3d_cloud_compare_nearest(const float* q_xyz, const long long* q_sorted_keys
                               d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.30 -- deterministic samples of a surface mesh at a stated spacing, and a comparison's error brought back onto the
+ * faces: what holds a mesh against a reference cloud with the search above.  The rule is this project's
+ * (deep3d_aerial_amd/mesh_compare.py); it does not claim to match any tool.
+ *   Inputs: vertices [n_vertices,3] fp32, faces [n_faces,3] int32, a spacing s, finite and > 0.
+ *   Per face f with corners (A, B, C) in the face's own order, all arithmetic fp64, every operation rounded once:
+ *     L2 = the largest of the three squared edge lengths, each (dx dx + dy dy) + dz dz.
+ *     n_f = 0 when a corner coordinate is not finite, L2 is not a finite number > 0, or an index is outside 0 .. n_vertices - 1.
+ *     Otherwise q = sqrt(L2) / s and n_f = 1 for q <= 1, else ceil(q); an n_f above 32768 is 32768 and the face counts as clipped.
+ *     The face gets n_f^2 samples: the centroids of the n_f^2 congruent sub-triangles of its n_f-fold edge subdivision.
+ *   Sample t (0 .. n^2 - 1) of a face with n = n_f: row r = floor(sqrt(t)) (exact), c = t - r^2 in 0 .. 2r, k = c >> 1; integer
+ *     weights with p + q + w = 3n: c even: p = 3(n - r) - 2, q = 3k + 1, w = 3(r - k) + 1; c odd: p = 3(n - r) - 1, q = 3k + 2,
+ *     w = 3(r - k) - 1; per axis x = ((p A_x + q B_x) + w C_x) / (3n) in fp64, then rounded to fp32.
+ *   Order: (face in input order, t).  In exact arithmetic every point of a face lies within 2s/3 of a sample of that face.
+ * Every pointer is DEVICE memory.  The calls, in order:
+ *   d3d_mesh_sample_count: counts [n_faces] int32 = n_f^2, offsets [n_faces + 1] int32 their exclusive scan, totals int64 [2] =
+ *     the samples and the clipped faces.  The offsets are valid only when totals[0] < 2^31 (the host reads totals and decides).
+ *     n_faces = 0 writes the zeroed totals and offsets[0] = 0.
+ *     scratch: d3d_mesh_sample_scratch_bytes(n_faces) bytes (0 for n_faces outside 0 .. 2^31 - 1): the scan's tile sums.
+ *   d3d_mesh_sample_emit: xyz [n_samples,3] fp32 and face [n_samples] int32 for n_samples = totals[0], one lane per sample.
+ *     n_samples = 0 launches nothing.
+ *   d3d_mesh_sample_face_error: from e [n_samples] int32 of d3d_cloud_compare_nearest on the samples and face, per face
+ *     sum [n_faces] int64 and keyed [n_faces] int32 over its samples with e >= 0 and worst [n_faces] int32, their maximum, -1 for
+ *     a face with none.  The call zeroes sum and keyed and sets worst to -1 itself; n_samples = 0 leaves them so.
+ * Integer atomicAdd and atomicMax only: one atomicAdd per workgroup and total in the count, one set per run of a face's samples
+ * within a wave in the face error.  Null pointers (where the count is not 0), a count outside 0 .. 2^31 - 1, a spacing that is
+ * not finite and > 0, a short scratch, overlapping buffers: D3D_ERR_INVALID_ARG before any launch.
+ */
+size_t d3d_mesh_sample_scratch_bytes(long long n_faces);
+int d3d_mesh_sample_count(const float* vertices, long long n_vertices, const int* faces, long long n_faces, double spacing,
+                          void* scratch, size_t scratch_bytes, int* counts, int* offsets, long long* totals, d3d_stream_t stream);
+int d3d_mesh_sample_emit(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* offsets,
+                         long long n_samples, float* xyz, int* face, d3d_stream_t stream);
+int d3d_mesh_sample_face_error(const int* e, const int* face, long long n_samples, long long n_faces, long long* sum, int* keyed,
+                               int* worst, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.9 -- true orthophoto on the DSM (the reference has no orthophoto step; the semantics are this project's,
  * deep3d_aerial_amd/ortho.py).  The grid is the DSM's: cell (i, j) is X = (x_min + (j + 0.5) unit_x, y_max - (i + 0.5) unit_y, h),
  * h = height[i,j] in fp64; a non-finite h is an empty cell.  A view is one d3d_ortho_view_t record in DEVICE memory, filled by
