@@ -147,7 +147,8 @@ def topology(faces, n_vertices):
     """What a round reads of the connectivity, on the device: {"offset", "nbr", "fixed" (mesh.adjacency), "face_offset",
     "face_index" (mesh.face_incidence), "edges" [3 m, 2] int32 and "n_edges" [1] int64 (rule 2's list: subdivide.edge_list; the rows
     from the edge count on are 0), "counts" [3] int64: 0 for the winners, the kept faces and the kept vertices the later passes
-    count}."""
+    count}.  "nbr" and "face_index" are defined up to offset[n] and face_offset[n], as in mesh.adjacency and
+    mesh.face_incidence."""
     from . import subdivide as _subdivide
     from .mesh import adjacency, face_incidence
 
@@ -186,7 +187,8 @@ def claim_apply(vertices, topo, target, key):
 
 def faces_compact(moved, faces, remap, counts):
     """Rule 5's output, by the decimation's faces pass and d3d_mesh_compact: (vertices [n,3], faces [m,3]) of which the first
-    counts[2] and counts[1] rows hold the mesh after the round (the counts are still on the device)."""
+    counts[2] and counts[1] rows hold the mesh after the round (the counts are still on the device).  The vertex rows from
+    counts[2] on are never written; the face rows from counts[1] on are 0."""
     lib = _lib.load()
     n, m = int(moved.shape[0]), int(faces.shape[0])
     dev = moved.device

@@ -378,7 +378,8 @@ def _mesh_arrays(vertices, faces):
 
 
 def adjacency(faces, n_vertices):
-    """The CSR of the distinct neighbours: (offset [n+1] int64, nbr [offset[n]] int32, fixed [n] uint8) on the device."""
+    """The CSR of the distinct neighbours: (offset [n+1] int64, nbr [max(6 m, 1)] int32, fixed [n] uint8) on the device.  nbr is
+    defined in [0, offset[n]), the rows; what lies past offset[n] is room the kernel never writes."""
     lib = _lib.load()
     n, m = int(n_vertices), int(faces.shape[0])
     dev = faces.device
@@ -512,7 +513,9 @@ def _decimate_arrays(vertices, faces, what="decimation"):
 
 
 def face_incidence(faces, n_vertices):
-    """The vertex -> face CSR: (face_offset [n+1] int32, face_index [3 m] int32), every row in increasing face index."""
+    """The vertex -> face CSR: (face_offset [n+1] int32, face_index [3 m] int32), every row in increasing face index.  face_index
+    is defined in [0, face_offset[n]): a face with a repeated or out-of-range index enters no row, so face_offset[n] < 3 m on a
+    mesh that has one, and the entries past it are never written."""
     lib = _lib.load()
     n, m = int(n_vertices), int(faces.shape[0])
     dev = faces.device

@@ -191,7 +191,12 @@ def test_fuse_block_chains_filtered_maps(fuse, oracle):
     """fuse_block = the view loop of fuse_depths on resident maps: every reference view is fused against the maps as
     the EARLIER reference views left them (sources filtered by each check, a reference's own map cut to its final mask).
     Checked against the same chain built from the CPU oracle."""
-    ref, srcs = S.make_fusion_scene(72, 96, 3, seed=41)
+    check_fuse_block_chain(fuse, oracle, 72, 96)
+
+
+def check_fuse_block_chain(fuse, oracle, h, w):
+    """The body of test_fuse_block_chains_filtered_maps on maps of h x w (tests/test_uninitialised_gpu.py runs it at other sizes)."""
+    ref, srcs = S.make_fusion_scene(h, w, 3, seed=41)
     cams = [ref] + srcs
     names = ["v%d" % i for i in range(4)]
     views = {n: {"depth": dev(c["depth"]), "normal": dev(c["normal"]), "K": c["K"], "E": c["E"], "id": 10 + i,

@@ -3,6 +3,7 @@ the colour words (batching, view order, accumulation, absent views), the vote on
 without a colour, in place), the behaviour on a scene whose honest images agree and whose painted view does not,
 texture_mesh(outliers=...) against the numpy chain with and without the smoothing, and the files written on one and two ranks, by
 predict and by python -m deep3d_aerial_amd.texture."""
+import functools
 import os
 import socket
 import subprocess
@@ -117,10 +118,16 @@ def _crafted_rows():
     return np.ascontiguousarray(cand), np.ascontiguousarray(col)
 
 
-@pytest.fixture(scope="module")
-def crafted_rows():
+@functools.lru_cache(maxsize=None)
+def crafted_rows_value():
+    """The crafted rows and the restatement's vote at the three thresholds: built once, shared, never changed."""
     cand, col = _crafted_rows()
     return cand, col, {t: O.reject_numpy(cand, col, t) for t in (0.001, 0.06, 1.0)}
+
+
+@pytest.fixture(scope="module")
+def crafted_rows():
+    return crafted_rows_value()
 
 
 def test_the_crafted_rows_hold_every_case(crafted_rows):

@@ -2,6 +2,7 @@
 the candidate lists (batching, view order, merge, the selection's key in column 0), the smoothing rounds on a mesh of a rough
 grid, a fan, an edge of three faces and a face with a repeated index, texture_mesh(smooth_views=...) against the numpy chain,
 and the files written on one and two ranks, by predict and by python -m deep3d_aerial_amd.texture."""
+import functools
 import os
 import socket
 import subprocess
@@ -63,10 +64,17 @@ def _candidate_scene():
     return V.astype(np.float32), F, vs
 
 
-@pytest.fixture(scope="module")
-def candidate_scene():
+@functools.lru_cache(maxsize=None)
+def candidate_scene_value():
+    """The candidate scene and the restatement's lists: built once, shared (tests/test_uninitialised_gpu.py uses it too), never
+    changed."""
     V, F, vs = _candidate_scene()
     return V, F, vs, S.candidates_numpy(V, F, vs)
+
+
+@pytest.fixture(scope="module")
+def candidate_scene():
+    return candidate_scene_value()
 
 
 def test_the_candidate_scene_covers_full_partial_and_empty_lists(candidate_scene):
@@ -140,11 +148,17 @@ def _smooth_scene():
     return F, n0 + 46, cand
 
 
-@pytest.fixture(scope="module")
-def smooth_scene():
+@functools.lru_cache(maxsize=None)
+def smooth_scene_value():
+    """The smoothing scene and the restatement's state after every round: built once, shared, never changed."""
     F, n, cand = _smooth_scene()
     states = list(S.smooth_rounds_numpy(F, cand, 0.1, 0.25, 64))
     return F, n, cand, states
+
+
+@pytest.fixture(scope="module")
+def smooth_scene():
+    return smooth_scene_value()
 
 
 def test_the_smooth_scene_runs_past_one_host_read_and_holds_every_row_kind(smooth_scene):
