@@ -39,14 +39,18 @@ rule below is this project's own; it does not claim to match any tool.
   multisets of points; idx follows a permutation of T.
 
 Out of scope: a shift of large coordinates before the fp32 rounding; cloud-to-mesh distance; normals or colour in the comparison;
-an uncapped search; registration (ICP) -- the two clouds must already be in one frame.  Ground truth is not an input of a
+an uncapped search.  The two clouds must be in one frame: cloud_register finds the rigid transform, and
+--transform applies it here.  Ground truth is not an input of a
 reconstruction run: pipeline.predict_and_fuse and predict have no key or flag for this.
 
 The search is HIP (csrc/cloud_compare.hip); the sort of the keys is torch.sort (plumbing).  Integer atomicAdd only, so the result
 is bit-reproducible.
 
     python -m deep3d_aerial_amd.cloud_compare --cloud A.ply --reference B.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax --max_dist H
-        --threshold T[,T...] [--json R.json] [--out_accuracy EA.ply] [--out_completeness EB.ply]
+        --threshold T[,T...] [--transform T.txt] [--json R.json] [--out_accuracy EA.ply] [--out_completeness EB.ply]
+
+--transform: a 4 x 4 transform as cloud_register writes it; the evaluated cloud goes through cloud_register.apply before anything
+else, and --out_accuracy carries the moved coordinates.
 """
 import argparse
 import json
@@ -355,6 +359,9 @@ def main(argv=None):
     ap.add_argument("--json", default=None, help="write the result here too (.json)")
     ap.add_argument("--out_accuracy", default=None, help="the evaluated cloud coloured by its distance to the reference (.ply)")
     ap.add_argument("--out_completeness", default=None, help="the reference coloured by its distance to the evaluated cloud (.ply)")
+    from . import cloud_register   # (it imports this module)
+
+    cloud_register.add_transform_argument(ap)
     a = ap.parse_args(argv)
     for flag in ("cloud", "reference", "border", "max_dist", "threshold"):
         if getattr(a, flag) is None:
@@ -369,6 +376,7 @@ def main(argv=None):
         ap.error("two of --json, --out_accuracy and --out_completeness name the same file")
     if set(outs) & {os.path.abspath(str(a.cloud)), os.path.abspath(str(a.reference))}:
         ap.error("an output would overwrite an input cloud")
+    cloud_register.check_transform_argument(ap, a.transform, {os.path.abspath(str(a.cloud)), os.path.abspath(str(a.reference))}, outs)
     try:
         _thresholds(a.threshold, _cap(a.max_dist))
         cloud.CloudGrid(a.border, a.max_dist)
@@ -378,6 +386,9 @@ def main(argv=None):
         raise RuntimeError("the clouds are compared on the GPU (no CPU fallback)")
     xa, xb = read_xyz_ply(a.cloud), read_xyz_ply(a.reference)
     da, db = torch.from_numpy(xa).cuda(), torch.from_numpy(xb).cuda()
+    if a.transform is not None:   # the evaluated cloud moves first; the error cloud carries the moved coordinates
+        da = cloud_register.apply(da, cloud_register.read_transform(a.transform))
+        xa = da.cpu().numpy()
     result, found = compare(da, db, a.border, a.max_dist, a.threshold)
     line = json.dumps(result)
     if a.out_accuracy is not None:

@@ -151,30 +151,10 @@ static size_t cmp_scratch(long long n_target) { return align256((size_t)(n_targe
 // The workgroups of the search to launch.  The tiles cost about the same, so the grid-stride loop is balanced when every workgroup
 // is resident from the start: as many as the current device holds at once (24.2 KiB of LDS each: 6 a CU on gfx950, 1536), never
 // more than CC_GRID_CAP.  With 2048 on 1536 slots the last quarter ran as a second round on a third of the chip (measured:
-// DESIGN.md §4.29).  The occupancy query costs more than half a millisecond on the host, so its answer is kept per device; two
-// threads that race here store the same number.
+// DESIGN.md §4.29).  The query and its per-device cache are search_resident's (cloud_search.h).
 static int cmp_resident(int* out) {
-    constexpr int MAX_DEVICES = 64;
-    static int known[MAX_DEVICES] = {};
-    int dev = 0;
-    int rc = hip_status(hipGetDevice(&dev), "cloud compare: device");
-    if (rc != D3D_OK) return rc;
-    const bool slot = dev >= 0 && dev < MAX_DEVICES;
-    if (slot && known[dev] > 0) {
-        *out = known[dev];
-        return D3D_OK;
-    }
-    int n_cu = 0, per_cu = 0;
-    rc = hip_status(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev), "cloud compare: CU count");
-    if (rc != D3D_OK) return rc;
-    rc = hip_status(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cloud_compare_nearest_kernel, CC_BLOCK, 0), "cloud compare: occupancy");
-    if (rc != D3D_OK) return rc;
-    long resident = (long)n_cu * per_cu;
-    if (resident < 1) resident = 1;
-    if (resident > CC_GRID_CAP) resident = CC_GRID_CAP;
-    if (slot) known[dev] = (int)resident;
-    *out = (int)resident;
-    return D3D_OK;
+    static int known[SEARCH_MAX_DEVICES] = {};
+    return search_resident((const void*)cloud_compare_nearest_kernel, CC_BLOCK, CC_GRID_CAP, known, "cloud compare: resident workgroups", out);
 }
 
 }  // namespace d3d

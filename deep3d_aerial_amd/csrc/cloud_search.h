@@ -65,4 +65,32 @@ inline bool search_apart(const SearchRange* r, int n) {
     return true;
 }
 
+// The workgroups of a grid-stride kernel to launch: as many as the current device holds at once, so that the loop is balanced
+// with every workgroup resident from the start, never more than `cap` (DESIGN.md §4.29 measured what a second round costs).  The
+// occupancy query costs more than half a millisecond on the host, so its answer is kept per device in the caller's `known`
+// (SEARCH_MAX_DEVICES zero-initialised ints, one array per kernel); two threads that race here store the same number.
+constexpr int SEARCH_MAX_DEVICES = 64;
+
+inline int search_resident(const void* kernel, int block, int cap, int* known, const char* what, int* out) {
+    int dev = 0;
+    int rc = hip_status(hipGetDevice(&dev), what);
+    if (rc != D3D_OK) return rc;
+    const bool slot = dev >= 0 && dev < SEARCH_MAX_DEVICES;
+    if (slot && known[dev] > 0) {
+        *out = known[dev];
+        return D3D_OK;
+    }
+    int n_cu = 0, per_cu = 0;
+    rc = hip_status(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev), what);
+    if (rc != D3D_OK) return rc;
+    rc = hip_status(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0), what);
+    if (rc != D3D_OK) return rc;
+    long resident = (long)n_cu * per_cu;
+    if (resident < 1) resident = 1;
+    if (resident > cap) resident = cap;
+    if (slot) known[dev] = (int)resident;
+    *out = (int)resident;
+    return D3D_OK;
+}
+
 }  // namespace d3d

@@ -39,15 +39,19 @@ rule below is this project's own; it does not claim to match any tool.
 
 Out of scope: the exact point-to-triangle distance for the completeness direction (a reference point is held against the nearest
 sample, up to 2s/3 beside the nearest surface point); area weights to remove the density bias; sampling by normals or colour; a
-shift of large coordinates before the fp32 rounding; registration (ICP).  Ground truth is not an input of a reconstruction run:
-pipeline.predict_and_fuse and predict have no key or flag for this.
+shift of large coordinates before the fp32 rounding; a registration of its own (see --transform below).  Ground truth is not an
+input of a reconstruction run: pipeline.predict_and_fuse and predict have no key or flag for this.
 
 The sampling and the face error are HIP (csrc/mesh_sample.hip); the scan is geom_scan, the keys d3d_cloud_keys, the search
 d3d_cloud_compare_nearest, the statistics cloud_compare.stats, each as it is.
 
     python -m deep3d_aerial_amd.mesh_compare --mesh M.ply --reference B.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax --max_dist H
-        --threshold T[,T...] --spacing S [--json R.json] [--out_samples S.ply] [--out_accuracy EA.ply] [--out_completeness EB.ply]
-        [--out_mesh EM.ply]
+        --threshold T[,T...] --spacing S [--transform T.txt] [--json R.json] [--out_samples S.ply] [--out_accuracy EA.ply]
+        [--out_completeness EB.ply] [--out_mesh EM.ply]
+
+--transform: a 4 x 4 transform as cloud_register writes it; the mesh's vertices go through cloud_register.apply before anything
+else, and the --out_* files carry the moved coordinates.  The mesh has no registration of its own: register its samples
+(--out_samples) with cloud_register, then pass the transform here.
 """
 import argparse
 import json
@@ -227,6 +231,9 @@ def main(argv=None):
     ap.add_argument("--out_accuracy", default=None, help="the samples coloured by their distance to the reference (.ply)")
     ap.add_argument("--out_completeness", default=None, help="the reference coloured by its distance to the samples (.ply)")
     ap.add_argument("--out_mesh", default=None, help="the mesh with its faces coloured by their mean distance to the reference (.ply)")
+    from . import cloud_register
+
+    cloud_register.add_transform_argument(ap)
     a = ap.parse_args(argv)
     for flag in ("mesh", "reference", "border", "max_dist", "threshold", "spacing"):
         if getattr(a, flag) is None:
@@ -242,6 +249,7 @@ def main(argv=None):
         ap.error("two of --json, --out_samples, --out_accuracy, --out_completeness and --out_mesh name the same file")
     if set(outs) & {os.path.abspath(str(a.mesh)), os.path.abspath(str(a.reference))}:
         ap.error("an output would overwrite an input")
+    cloud_register.check_transform_argument(ap, a.transform, {os.path.abspath(str(a.mesh)), os.path.abspath(str(a.reference))}, outs)
     try:
         cloud_compare._thresholds(a.threshold, cloud_compare._cap(a.max_dist))
         cloud.CloudGrid(a.border, a.max_dist)
@@ -255,6 +263,9 @@ def main(argv=None):
     v, f = mesh.read_ply(a.mesh)
     xb = cloud_compare.read_xyz_ply(a.reference)
     dv, df, db = torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), torch.from_numpy(xb).cuda()
+    if a.transform is not None:   # the vertices move first; the samples and the error mesh carry the moved coordinates
+        dv = cloud_register.apply(dv, cloud_register.read_transform(a.transform))
+        v = dv.cpu().numpy()
     result, found = compare(dv, df, db, a.border, a.max_dist, a.threshold, a.spacing)
     line = json.dumps(result)
     xyz, face, ea, _ = found["samples"]

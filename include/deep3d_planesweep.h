@@ -1027,6 +1027,31 @@ int d3d_cloud_compare_nearest(const float* q_xyz, const long long* q_sorted_keys
                               d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.31 -- rigid registration of a point cloud to a reference cloud (iterative closest point) around the search above:
+ * the transform and the sums of the matched pairs.  The rule is this project's (deep3d_aerial_amd/cloud_register.py, which also
+ * holds the closed-form solve and the iteration, host fp64); it does not claim to match any tool.
+ *   d3d_cloud_transform: out [n,3] fp32 from xyz [n,3] fp32 and rt, 12 doubles in DEVICE memory, a row-major 3 x 4 matrix T.
+ *     Per output row r: p'_r = (float)(((T[r][0] (double)x + T[r][1] (double)y) + T[r][2] (double)z) + T[r][3]), every operation
+ *     fp64 and rounded once (no fused multiply-add), the result rounded once to fp32.  A non-finite input gives whatever that
+ *     arithmetic gives.  out must not overlap xyz.  n = 0 launches nothing.
+ *   d3d_cloud_register_sums: q_xyz [n_query,3] fp32 the moved cloud, e and idx [n_query] int32 what d3d_cloud_compare_nearest
+ *     gave for it against t_xyz [n_target,3] fp32 on the grid of that cap whose origin is (xmin, ymin, zmin).  Pair i counts when
+ *     0 <= idx_i < n_target and e_i <= e_max (an idx outside the targets is never dereferenced).  Per counted pair
+ *     a_c = llrint(((double)q_c - o_c) / cap * 1024.0) and b_c likewise from t_xyz[idx_i]; a keyed point lies inside a grid of at
+ *     most 2^21 - 1 cells per axis, so 0 <= a_c, b_c < 2^31 and a_r b_c < 2^62.  sums int64 [27], zeroed by the call on the
+ *     stream: [0] N, the counted pairs; [1..3] sum a; [4..6] sum b; [7..15] sum (a_r b_c) & 0xFFFFFFFF, row-major; [16..24] sum
+ *     (a_r b_c) >> 32; [25] sum e; [26] sum e^2.  With at most 2^31 - 1 points no slot overflows; the host recombines
+ *     M_rc = hi 2^32 + lo in unbounded integers.  n_query = 0 (or n_target = 0) writes only the zeroed sums.
+ * Every pointer is DEVICE memory.  One set of 27 integer atomicAdd per workgroup, no other atomics: the same bits for any order of
+ * the pairs.  Null pointers (where the count is not 0), a count outside 0 .. 2^31 - 1, a non-finite origin, a cap that is not
+ * finite and > 0, e_max outside 0 .. 1024, overlapping buffers: D3D_ERR_INVALID_ARG before any launch.
+ */
+int d3d_cloud_transform(const float* xyz, long long n, const double* rt, float* out, d3d_stream_t stream);
+int d3d_cloud_register_sums(const float* q_xyz, const int* e, const int* idx, long long n_query, const float* t_xyz,
+                            long long n_target, double xmin, double ymin, double zmin, double cap, int e_max, long long* sums,
+                            d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.30 -- deterministic samples of a surface mesh at a stated spacing, and a comparison's error brought back onto the
  * faces: what holds a mesh against a reference cloud with the search above.  The rule is this project's
  * (deep3d_aerial_amd/mesh_compare.py); it does not claim to match any tool.
