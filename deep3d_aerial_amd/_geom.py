@@ -1,6 +1,8 @@
 """What the geometry stages (dsm, ortho, mesh, texture, fuse) share on the host: pointers, the stream, scratch buffers, record
 tables, view batches, the checks of a mesh's arrays and the camera of a view.  Internal: the stages re-export what callers use."""
 import ctypes
+import math
+import os
 
 import numpy as np
 import torch
@@ -27,6 +29,45 @@ def scratch(lib_fn, *args, device):
 def records(struct_array, device):
     """A ctypes array of records in device memory (one host-to-device copy, ordered on the current stream)."""
     return torch.frombuffer(bytearray(bytes(struct_array)), dtype=torch.uint8).to(device)
+
+
+def is_real(x, above=None, at_least=None):
+    """x is a finite real number -- an int, a float or a numpy scalar of either kind, never a bool -- that lies above `above`
+    and at or above `at_least` where they are given.  The caller raises, in its own words."""
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(x):
+        return False
+    return (above is None or x > above) and (at_least is None or x >= at_least)
+
+
+def is_int(x, lo, hi=None):
+    """x is an integer -- an int or a numpy integer, never a bool -- in lo .. hi (hi None: no upper end)."""
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+        return False
+    return lo <= int(x) and (hi is None or int(x) <= hi)
+
+
+def host(t):
+    """A tensor or anything array-like as a host array."""
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+def write_bytes(path, data):
+    """data written to path, whose folder is made first."""
+    os.makedirs(os.path.dirname(os.path.abspath(str(path))), exist_ok=True)
+    with open(str(path), "wb") as f:
+        f.write(data)
+
+
+PLY_TYPES = {"<f4": "float", "u1": "uchar", "|u1": "uchar", "<i4": "int"}   # dtype.str of a record's field -> PLY scalar type
+
+
+def record_ply_bytes(comment, rec):
+    """The bytes of a binary little-endian PLY whose only element is the vertex: one vertex per record of the structured array
+    rec, one scalar property per field, named and typed by rec's dtype, in its order."""
+    dt = rec.dtype
+    head = ["ply", "format binary_little_endian 1.0", "comment %s" % comment, "element vertex %d" % rec.shape[0]]
+    head += ["property %s %s" % (PLY_TYPES[dt[f].str], f) for f in dt.names]
+    return ("\n".join(head + ["end_header"]) + "\n").encode("ascii") + rec.tobytes()
 
 
 def check_views_per_batch(views_per_batch):
@@ -61,8 +102,6 @@ def mesh_arrays(vertices, faces, index_factor, what):
 
 def mvs_cameras(mvs_folder):
     """(name, cam, location, image path) of every {name}_init.pfm + {name}.txt predict wrote under mvs_folder, by name."""
-    import os
-
     from . import predict
 
     names = sorted(f[:-len("_init.pfm")] for f in os.listdir(mvs_folder) if f.endswith("_init.pfm"))
@@ -73,8 +112,6 @@ def mvs_cameras(mvs_folder):
 
 def load_map(mvs_folder, name, suffix, device):
     """{name}{suffix}.pfm under mvs_folder as a device tensor."""
-    import os
-
     from . import predict
 
     data, _ = predict.load_pfm(os.path.join(mvs_folder, name + suffix + ".pfm"))

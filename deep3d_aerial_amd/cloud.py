@@ -77,55 +77,87 @@ class CloudGrid(object):
         self.border, self.voxel, self.n = b, v, tuple(int(k) for k in n)
 
 
+# ----------------------------------------------------------------------------------------
+# what every stage on this grid shares (cloud_outliers, cloud_compare, cloud_register, mesh_compare): the checks of a cloud and
+# its keys
+# ----------------------------------------------------------------------------------------
+def points(t, name, dtype=torch.float32):
+    """t checked by name as a [n,3] tensor of dtype (the coordinates of a cloud: fp32) with fewer than 2^31 rows; returns t."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("%s must be a [n,3] %s tensor (got %s %s)" % (name, str(dtype).replace("torch.", ""), t.dtype, tuple(t.shape)))
+    if int(t.shape[0]) >= 1 << 31:
+        raise ValueError("%s has %d points: at most 2^31 - 1" % (name, t.shape[0]))
+    return t
+
+
+def on_gpu(t, name, what):
+    """t contiguous; a CPU tensor is refused by name.  what: the stage's verb phrase ("the clouds are compared")."""
+    if not t.is_cuda:
+        raise RuntimeError("%s is on %s: %s on the GPU (no CPU fallback)" % (name, t.device, what))
+    return t.contiguous()
+
+
+def check_grid(grid):
+    if not isinstance(grid, CloudGrid):
+        raise TypeError("grid must be a CloudGrid")
+    return grid
+
+
+def point_keys(xyz, grid):
+    """xyz [n,3] fp32, checked, contiguous and on a GPU, grid a CloudGrid -> (keys [n] int64, frac [n] int64) of d3d_cloud_keys
+    in input order: the package's one call of it.  Queued on the caller's stream; the host reads nothing."""
+    n, dev, b = int(xyz.shape[0]), xyz.device, grid.border
+    keys = torch.empty((n,), dtype=torch.int64, device=dev)
+    frac = torch.empty((n,), dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().d3d_cloud_keys(_ptr(xyz) if n else None, n, b[0], b[1], b[2], b[3], b[4], b[5], grid.voxel, _ptr(keys),
+                                          _ptr(frac), _stream()), "d3d_cloud_keys")
+    return keys, frac
+
+
+def sorted_keys(xyz, grid):
+    """point_keys sorted -> (sorted_keys [n] int64, order [n] int64): the keys in increasing order and the input index of every
+    sorted point.  The sort is torch.sort (plumbing)."""
+    keys, order = torch.sort(point_keys(xyz, grid)[0])
+    return keys, order
+
+
 def merge_points(xyz, normal, color, grid, min_points=1):
     """xyz [n,3] fp32, normal [n,3] fp32 or None, color [n,3] int32 or None, all on one GPU -> {"xyz" [m,3] fp32, "normal" [m,3] fp32
     or None, "color" [m,3] uint8 or None, "count" [m] int32} (device tensors): the merged cloud of this module's docstring, queued
     on the caller's stream.  The host reads two counts (the voxels and the kept voxels).  CPU tensors are refused."""
-    if not isinstance(grid, CloudGrid):
-        raise TypeError("grid must be a CloudGrid")
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) < 1 << 31:
+    check_grid(grid)
+    if not _geom.is_int(min_points, 1, (1 << 31) - 1):
         raise ValueError("min_points must be an integer in 1 .. 2^31 - 1 (got %r)" % (min_points,))
-    given = [("xyz", xyz, torch.float32)] + ([("normal", normal, torch.float32)] if normal is not None else []) + \
-        ([("color", color, torch.int32)] if color is not None else [])
-    for name, t, dt in given:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s must be a torch.Tensor" % name)
-        if t.dtype != dt or t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError("%s must be a [n,3] %s tensor (got %s %s)" % (name, str(dt).replace("torch.", ""), t.dtype, tuple(t.shape)))
-        if t.shape[0] != xyz.shape[0]:
+    given = {"xyz": xyz, "normal": normal, "color": color}
+    given = {name: t for name, t in given.items() if name == "xyz" or t is not None}
+    for name, t in given.items():
+        if points(t, name, torch.int32 if name == "color" else torch.float32).shape[0] != xyz.shape[0]:
             raise ValueError("xyz has %d points, %s %d" % (xyz.shape[0], name, t.shape[0]))
-    n = int(xyz.shape[0])
-    if n >= 1 << 31:
-        raise ValueError("%d points: at most 2^31 - 1" % n)
-    for name, t, _ in given:
-        if not t.is_cuda:
-            raise RuntimeError("%s is on %s: the cloud is merged on the GPU (no CPU fallback)" % (name, t.device))
+    for name, t in given.items():
+        given[name] = on_gpu(t, name, "the cloud is merged")
         if t.device != xyz.device:
             raise ValueError("xyz on %s, %s on %s" % (xyz.device, name, t.device))
-    xyz = xyz.contiguous()
-    normal = normal.contiguous() if normal is not None else None
-    color = color.contiguous() if color is not None else None
-    dev = xyz.device
+    xyz, normal, color = given["xyz"], given.get("normal"), given.get("color")
+    n, dev = int(xyz.shape[0]), xyz.device
     lib = _lib.load()
     b, v, st = grid.border, grid.voxel, _stream()
     width = 3 + (3 if normal is not None else 0) + (3 if color is not None else 0)
-    keys = torch.empty((n,), dtype=torch.int64, device=dev)
-    frac = torch.empty((n,), dtype=torch.int64, device=dev)
-    _lib.check(lib.d3d_cloud_keys(_ptr(xyz) if n else None, n, b[0], b[1], b[2], b[3], b[4], b[5], v, _ptr(keys), _ptr(frac), st),
-               "d3d_cloud_keys")
-    sorted_keys, order = torch.sort(keys)
+    keys, frac = point_keys(xyz, grid)
+    skeys, order = torch.sort(keys)
     del keys
     vox = torch.empty((n,), dtype=torch.int32, device=dev)
     counts = torch.zeros((2,), dtype=torch.int64, device=dev)
     scratch, nbytes = _geom.scratch(lib.d3d_cloud_scratch_bytes, n, device=dev)
-    _lib.check(lib.d3d_cloud_heads(_ptr(sorted_keys), n, _ptr(scratch), nbytes, _ptr(vox), _ptr(counts[0:1]), st), "d3d_cloud_heads")
+    _lib.check(lib.d3d_cloud_heads(_ptr(skeys), n, _ptr(scratch), nbytes, _ptr(vox), _ptr(counts[0:1]), st), "d3d_cloud_heads")
     nv = int(counts[0])   # the first host read
     ukeys = torch.empty((nv,), dtype=torch.int64, device=dev)
     count = torch.empty((nv,), dtype=torch.int32, device=dev)
     acc = torch.empty((nv, width), dtype=torch.int64, device=dev)
-    _lib.check(lib.d3d_cloud_accumulate(_ptr(sorted_keys), _ptr(order), _ptr(vox), _ptr(frac), _ptr(normal), _ptr(color), n, nv,
+    _lib.check(lib.d3d_cloud_accumulate(_ptr(skeys), _ptr(order), _ptr(vox), _ptr(frac), _ptr(normal), _ptr(color), n, nv,
                                         _ptr(ukeys), _ptr(count), _ptr(acc), st), "d3d_cloud_accumulate")
-    del sorted_keys, order, vox, frac
+    del skeys, order, vox, frac
     keep = torch.empty((nv,), dtype=torch.int32, device=dev)
     pos = torch.empty((nv,), dtype=torch.int32, device=dev)
     scratch, nbytes = _geom.scratch(lib.d3d_cloud_scratch_bytes, nv, device=dev)
@@ -154,16 +186,12 @@ def _ply_dtype(normals, colors):
     return np.dtype(fields + [("count", "<i4")])
 
 
-_PLY_NAMES = {"<f4": "float", "u1": "uchar", "|u1": "uchar", "<i4": "int"}
-
-
 def cloud_ply_bytes(xyz, normal, color, count):
     """The bytes of the PLY of a cloud (host arrays or tensors): xyz [m,3] fp32, normal [m,3] fp32 or None, color [m,3] uint8 or
     None, count [m] int32."""
-    host = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-    xyz, count = host(xyz), host(count)
-    normal = host(normal) if normal is not None else None
-    color = host(color) if color is not None else None
+    xyz, count = _geom.host(xyz), _geom.host(count)
+    normal = _geom.host(normal) if normal is not None else None
+    color = _geom.host(color) if color is not None else None
     m = int(xyz.shape[0])
     if xyz.dtype != np.float32 or xyz.shape != (m, 3) or count.dtype != np.int32 or count.shape != (m,):
         raise ValueError("xyz must be [m,3] float32 and count [m] int32 (got %s %s, %s %s)" % (xyz.shape, xyz.dtype, count.shape, count.dtype))
@@ -182,16 +210,11 @@ def cloud_ply_bytes(xyz, normal, color, count):
         for k, f in enumerate(("red", "green", "blue")):
             rec[f] = color[:, k]
     rec["count"] = count
-    head = ["ply", "format binary_little_endian 1.0", "comment merged point cloud (deep3d_aerial_amd.cloud)", "element vertex %d" % m]
-    head += ["property %s %s" % (_PLY_NAMES[dt[f].str], f) for f in dt.names]
-    return ("\n".join(head + ["end_header"]) + "\n").encode("ascii") + rec.tobytes()
+    return _geom.record_ply_bytes("merged point cloud (deep3d_aerial_amd.cloud)", rec)
 
 
 def write_cloud_ply(path, xyz, normal, color, count):
-    folder = os.path.dirname(os.path.abspath(str(path)))
-    os.makedirs(folder, exist_ok=True)
-    with open(str(path), "wb") as f:
-        f.write(cloud_ply_bytes(xyz, normal, color, count))
+    _geom.write_bytes(path, cloud_ply_bytes(xyz, normal, color, count))
     return str(path)
 
 
@@ -216,7 +239,7 @@ def read_cloud_ply(path):
             props.append((w[1], w[2]))
     normals, colors = ("float", "nx") in props, ("uchar", "red") in props
     dt = _ply_dtype(normals, colors)
-    if m is None or props != [(_PLY_NAMES[dt[f].str], f) for f in dt.names]:
+    if m is None or props != [(_geom.PLY_TYPES[dt[f].str], f) for f in dt.names]:
         raise ValueError("%s: not the layout of a merged cloud (properties %r)" % (path, props))
     body = data[end + len(b"end_header\n"):]
     if len(body) != m * dt.itemsize:
@@ -245,7 +268,7 @@ def check_settings(settings):
     grid = CloudGrid(settings["border"], settings["voxel"])
     k = settings.get("min_points", 1)
     k = 1 if k is None else k
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) < 1 << 31:
+    if not _geom.is_int(k, 1, (1 << 31) - 1):
         raise ValueError("cloud min_points must be an integer in 1 .. 2^31 - 1 (got %r)" % (k,))
     if settings.get("outliers") is not None:
         from . import cloud_outliers

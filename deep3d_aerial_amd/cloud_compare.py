@@ -71,44 +71,15 @@ PERCENTILES = (50, 90, 95)
 # ----------------------------------------------------------------------------------------
 # the search
 # ----------------------------------------------------------------------------------------
-def _points(xyz, name):
-    if not isinstance(xyz, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise ValueError("%s must be a [n,3] float32 tensor (got %s %s)" % (name, xyz.dtype, tuple(xyz.shape)))
-    if int(xyz.shape[0]) >= 1 << 31:
-        raise ValueError("%s has %d points: at most 2^31 - 1" % (name, xyz.shape[0]))
-    return xyz
-
-
-def _on_gpu(xyz, name):
-    if not xyz.is_cuda:
-        raise RuntimeError("%s is on %s: the clouds are compared on the GPU (no CPU fallback)" % (name, xyz.device))
-    return xyz.contiguous()
-
-
-def _grid(grid):
-    if not isinstance(grid, cloud.CloudGrid):
-        raise TypeError("grid must be a CloudGrid")
-    return grid
+_VERB = "the clouds are compared"
 
 
 def prepare(xyz, grid):
     """xyz [n,3] fp32 on one GPU, grid = CloudGrid(border, cap) -> (sorted_keys [n] int64, order [n] int64): the keys of
-    d3d_cloud_keys with voxel = the cap, sorted, and the input index of every sorted point.  A cloud is prepared once for both
-    directions of a comparison.  Queued on the caller's stream; the host reads nothing."""
-    grid = _grid(grid)
-    xyz = _on_gpu(_points(xyz, "xyz"), "xyz")
-    n, dev = int(xyz.shape[0]), xyz.device
-    lib = _lib.load()
-    b, h = grid.border, grid.voxel
-    keys = torch.empty((n,), dtype=torch.int64, device=dev)
-    frac = torch.empty((n,), dtype=torch.int64, device=dev)
-    _lib.check(lib.d3d_cloud_keys(_ptr(xyz) if n else None, n, b[0], b[1], b[2], b[3], b[4], b[5], h, _ptr(keys), _ptr(frac), _stream()),
-               "d3d_cloud_keys")
-    del frac
-    sorted_keys, order = torch.sort(keys)
-    return sorted_keys, order
+    d3d_cloud_keys with voxel = the cap, sorted, and the input index of every sorted point (cloud.sorted_keys).  A cloud is
+    prepared once for both directions of a comparison.  Queued on the caller's stream; the host reads nothing."""
+    cloud.check_grid(grid)
+    return cloud.sorted_keys(cloud.on_gpu(cloud.points(xyz, "xyz"), "xyz", _VERB), grid)
 
 
 def _prepared(p, xyz, grid, name):
@@ -128,9 +99,9 @@ def nearest(query, target, grid, query_prepared=None, target_prepared=None):
     hist [1026] int64) of the module's docstring: device tensors queued on the caller's stream; the host reads nothing.
     query_prepared / target_prepared: what prepare() returned for that cloud on this grid.  CPU tensors are refused.  The two
     clouds must not share memory (compare a cloud with a clone of itself)."""
-    grid = _grid(grid)
-    query, target = _points(query, "query"), _points(target, "target")
-    query, target = _on_gpu(query, "query"), _on_gpu(target, "target")
+    cloud.check_grid(grid)
+    query, target = cloud.points(query, "query"), cloud.points(target, "target")
+    query, target = cloud.on_gpu(query, "query", _VERB), cloud.on_gpu(target, "target", _VERB)
     if query.device != target.device:
         raise ValueError("query is on %s and target on %s: both clouds must be on one GPU" % (query.device, target.device))
     nq, nt, dev = int(query.shape[0]), int(target.shape[0]), query.device
@@ -161,16 +132,17 @@ def _hist(h, name):
     return h
 
 
-def _cap(max_dist):
-    if isinstance(max_dist, bool) or not isinstance(max_dist, (int, float, np.integer, np.floating)) or not (math.isfinite(max_dist) and max_dist > 0):
+def check_max_dist(max_dist):
+    """The cap as a float; ValueError unless it is a finite number > 0."""
+    if not _geom.is_real(max_dist, above=0):
         raise ValueError("max_dist must be finite and > 0 (got %r)" % (max_dist,))
     return float(max_dist)
 
 
 def threshold_bin(tau, max_dist):
     """t = floor(tau / h * 1024 + 0.5) of a threshold tau under the cap h; ValueError unless 1 <= t <= 1023."""
-    h = _cap(max_dist)
-    if isinstance(tau, bool) or not isinstance(tau, (int, float, np.integer, np.floating)) or not math.isfinite(tau):
+    h = check_max_dist(max_dist)
+    if not _geom.is_real(tau):
         raise ValueError("a threshold must be a finite number (got %r)" % (tau,))
     t = math.floor(float(tau) / h * 1024.0 + 0.5)
     if not 1 <= t <= CAP - 1:
@@ -179,7 +151,8 @@ def threshold_bin(tau, max_dist):
     return int(t)
 
 
-def _thresholds(thresholds, max_dist):
+def check_thresholds(thresholds, max_dist):
+    """[(tau, bin)] of one threshold or a sequence of them under the cap max_dist, each through threshold_bin."""
     try:
         taus = list(thresholds)
     except TypeError:
@@ -212,8 +185,8 @@ def stats(hist_cloud, hist_reference, max_dist, thresholds, points=None):
     no GPU needed.  points: (points of the cloud, points of the reference) for the "points" entries, else they are None.
     -> {"max_dist": h, "cloud": {...}, "reference": {...}, "thresholds": [{"threshold", "bin", "accuracy", "completeness",
     "fscore"}, ...]} with {"points", "keyed", "beyond", "mean", "rms", "p50", "p90", "p95"} per direction."""
-    h = _cap(max_dist)
-    taus = _thresholds(thresholds, h)
+    h = check_max_dist(max_dist)
+    taus = check_thresholds(thresholds, h)
     ha, hb = _hist(hist_cloud, "hist_cloud"), _hist(hist_reference, "hist_reference")
     pa, pb = (None, None) if points is None else (int(points[0]), int(points[1]))
     a, cum_a, ma = _direction(ha, h, pa)
@@ -231,7 +204,7 @@ def compare(cloud_xyz, reference_xyz, border, max_dist, thresholds):
     """(result, {"cloud": (e, idx), "reference": (e, idx)}): the dict of stats() for the cloud [n,3] fp32 against the reference
     [n,3] fp32 (device tensors on one GPU), and per direction the device tensors of nearest().  The host reads the two histograms
     in one read."""
-    taus = _thresholds(thresholds, _cap(max_dist))
+    taus = check_thresholds(thresholds, check_max_dist(max_dist))
     try:
         grid = cloud.CloudGrid(border, max_dist)
     except ValueError as e:
@@ -311,8 +284,7 @@ def error_cloud_bytes(xyz, e):
     """The bytes of an error cloud: every point of xyz [n,3] fp32 in input order as x y z float, red green blue uchar, e int, with
     red = min(255, e >> 1), green = min(255, (1024 - e) >> 1), blue = 0; an unkeyed point (e = -1) is grey (128, 128, 128).
     Host arrays or tensors."""
-    host = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-    xyz, e = host(xyz), host(e)
+    xyz, e = _geom.host(xyz), _geom.host(e)
     n = int(xyz.shape[0])
     if xyz.dtype != np.float32 or xyz.shape != (n, 3) or e.dtype != np.int32 or e.shape != (n,):
         raise ValueError("xyz must be [n,3] float32 and e [n] int32 (got %s %s, %s %s)" % (xyz.shape, xyz.dtype, e.shape, e.dtype))
@@ -326,22 +298,13 @@ def error_cloud_bytes(xyz, e):
     rec["green"] = np.where(keyed, np.minimum(255, (CAP - e) >> 1), 128)
     rec["blue"] = np.where(keyed, 0, 128)
     rec["e"] = e
-    head = ["ply", "format binary_little_endian 1.0", "comment error cloud (deep3d_aerial_amd.cloud_compare)", "element vertex %d" % n,
-            "property float x", "property float y", "property float z", "property uchar red", "property uchar green", "property uchar blue",
-            "property int e", "end_header"]
-    return ("\n".join(head) + "\n").encode("ascii") + rec.tobytes()
-
-
-def _write(path, data):
-    os.makedirs(os.path.dirname(os.path.abspath(str(path))), exist_ok=True)
-    with open(str(path), "wb") as f:
-        f.write(data)
+    return _geom.record_ply_bytes("error cloud (deep3d_aerial_amd.cloud_compare)", rec)
 
 
 # ----------------------------------------------------------------------------------------
 # command line
 # ----------------------------------------------------------------------------------------
-def _parse_thresholds(text):
+def parse_thresholds(text):
     try:
         vals = [float(v) for v in str(text).split(",")]
     except ValueError:
@@ -355,7 +318,7 @@ def main(argv=None):
     ap.add_argument("--reference", default=None, help="the reference cloud, or a mesh whose vertices serve (.ply)")
     ap.add_argument("--border", type=cloud.parse_border6, default=None, help="Xmin,Xmax,Ymin,Ymax,Zmin,Zmax (world units)")
     ap.add_argument("--max_dist", type=float, default=None, help="the cap of the distances (world units); further points count the cap")
-    ap.add_argument("--threshold", type=_parse_thresholds, default=None, help="T[,T...]: the distances under which a point counts")
+    ap.add_argument("--threshold", type=parse_thresholds, default=None, help="T[,T...]: the distances under which a point counts")
     ap.add_argument("--json", default=None, help="write the result here too (.json)")
     ap.add_argument("--out_accuracy", default=None, help="the evaluated cloud coloured by its distance to the reference (.ply)")
     ap.add_argument("--out_completeness", default=None, help="the reference coloured by its distance to the evaluated cloud (.ply)")
@@ -378,7 +341,7 @@ def main(argv=None):
         ap.error("an output would overwrite an input cloud")
     cloud_register.check_transform_argument(ap, a.transform, {os.path.abspath(str(a.cloud)), os.path.abspath(str(a.reference))}, outs)
     try:
-        _thresholds(a.threshold, _cap(a.max_dist))
+        check_thresholds(a.threshold, check_max_dist(a.max_dist))
         cloud.CloudGrid(a.border, a.max_dist)
     except ValueError as e:
         ap.error(str(e))
@@ -392,11 +355,11 @@ def main(argv=None):
     result, found = compare(da, db, a.border, a.max_dist, a.threshold)
     line = json.dumps(result)
     if a.out_accuracy is not None:
-        _write(a.out_accuracy, error_cloud_bytes(xa, found["cloud"][0]))
+        _geom.write_bytes(a.out_accuracy, error_cloud_bytes(xa, found["cloud"][0]))
     if a.out_completeness is not None:
-        _write(a.out_completeness, error_cloud_bytes(xb, found["reference"][0]))
+        _geom.write_bytes(a.out_completeness, error_cloud_bytes(xb, found["reference"][0]))
     if a.json is not None:
-        _write(a.json, (line + "\n").encode("ascii"))
+        _geom.write_bytes(a.json, (line + "\n").encode("ascii"))
     print(line)
     return result
 

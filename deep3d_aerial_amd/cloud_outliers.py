@@ -49,22 +49,18 @@ DEFAULT_K, DEFAULT_ALPHA = 8, 2.0
 _KEYS = ("radius", "k", "alpha", "min_neighbours")
 
 
-def _is_int(x):
-    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
-
-
 def _check_k(k):
-    if not _is_int(k) or not 1 <= int(k) <= K_MAX:
+    if not _geom.is_int(k, 1, K_MAX):
         raise ValueError("outlier k must be an integer in 1 .. %d (got %r)" % (K_MAX, k))
     return int(k)
 
 
 def _check_tests(alpha, min_neighbours):
     if alpha is not None:
-        if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not math.isfinite(alpha) or alpha < 0:
+        if not _geom.is_real(alpha, at_least=0):
             raise ValueError("outlier alpha must be a finite number >= 0, or None (got %r)" % (alpha,))
         alpha = float(alpha)
-    if not _is_int(min_neighbours) or not 0 <= int(min_neighbours) < 1 << 31:
+    if not _geom.is_int(min_neighbours, 0, (1 << 31) - 1):
         raise ValueError("outlier min_neighbours must be an integer in 0 .. 2^31 - 1 (got %r)" % (min_neighbours,))
     if alpha is None and int(min_neighbours) == 0:
         raise ValueError("outlier removal with alpha None and min_neighbours 0: at least one of the two tests must be on")
@@ -74,29 +70,13 @@ def _check_tests(alpha, min_neighbours):
 def point_distances(xyz, grid, k):
     """xyz [n,3] fp32 on one GPU, grid = CloudGrid(border, radius), k in 1 .. 32 -> (D [n] int32, nn [n] int32, sums [3] int64 =
     m, S1, S2), device tensors queued on the caller's stream; the host reads nothing.  CPU tensors are refused."""
-    if not isinstance(grid, cloud.CloudGrid):
-        raise TypeError("grid must be a CloudGrid")
+    cloud.check_grid(grid)
     k = _check_k(k)
-    if not isinstance(xyz, torch.Tensor):
-        raise TypeError("xyz must be a torch.Tensor")
-    if xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise ValueError("xyz must be a [n,3] float32 tensor (got %s %s)" % (xyz.dtype, tuple(xyz.shape)))
-    n = int(xyz.shape[0])
-    if n >= 1 << 31:
-        raise ValueError("%d points: at most 2^31 - 1" % n)
-    if not xyz.is_cuda:
-        raise RuntimeError("xyz is on %s: the outliers are found on the GPU (no CPU fallback)" % xyz.device)
-    xyz = xyz.contiguous()
-    dev = xyz.device
+    xyz = cloud.on_gpu(cloud.points(xyz, "xyz"), "xyz", "the outliers are found")
+    n, dev = int(xyz.shape[0]), xyz.device
     lib = _lib.load()
-    b, h, st = grid.border, grid.voxel, _stream()
-    keys = torch.empty((n,), dtype=torch.int64, device=dev)
-    frac = torch.empty((n,), dtype=torch.int64, device=dev)
-    _lib.check(lib.d3d_cloud_keys(_ptr(xyz) if n else None, n, b[0], b[1], b[2], b[3], b[4], b[5], h, _ptr(keys), _ptr(frac), st),
-               "d3d_cloud_keys")
-    del frac
-    sorted_keys, order = torch.sort(keys)
-    del keys
+    h, st = grid.voxel, _stream()
+    sorted_keys, order = cloud.sorted_keys(xyz, grid)
     dist = torch.empty((n,), dtype=torch.int32, device=dev)
     nn = torch.empty((n,), dtype=torch.int32, device=dev)
     sums = torch.zeros((3,), dtype=torch.int64, device=dev)
@@ -149,7 +129,7 @@ def check_settings(settings):
     if unknown:
         raise ValueError("unknown outlier settings %r (known: %s)" % (unknown, ", ".join(_KEYS)))
     h = settings.get("radius")
-    if isinstance(h, bool) or not isinstance(h, (int, float, np.integer, np.floating)) or not (math.isfinite(h) and h > 0):
+    if not _geom.is_real(h, above=0):
         raise ValueError("the outlier radius must be finite and > 0 (got %r)" % (h,))
     k = settings.get("k")
     m = settings.get("min_neighbours")

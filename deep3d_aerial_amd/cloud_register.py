@@ -61,12 +61,19 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, cloud, cloud_compare
+from . import _geom, _lib, cloud, cloud_compare
 from ._geom import ptr as _ptr, stream as _stream
-from .cloud_compare import _cap, _on_gpu, _points
 
 CAP = cloud_compare.CAP
 SUMS = 27
+
+
+_VERB = "the clouds are registered"
+
+
+def _points(xyz, name):
+    """xyz checked by name as a cloud on a GPU, contiguous."""
+    return cloud.on_gpu(cloud.points(xyz, name), name, _VERB)
 
 
 # ----------------------------------------------------------------------------------------
@@ -94,9 +101,9 @@ def apply(xyz, T):
     states it: a new device tensor queued on the caller's stream.  The host uploads the 12 doubles and reads nothing.  CPU tensors
     are refused."""
     T = _transform(T)
-    xyz = _on_gpu(_points(xyz, "xyz"), "xyz")
+    xyz = _points(xyz, "xyz")
     n, dev = int(xyz.shape[0]), xyz.device
-    rt = torch.tensor(T[:3].reshape(-1).tolist(), dtype=torch.float64, device=dev)
+    rt =torch.tensor(T[:3].reshape(-1).tolist(), dtype=torch.float64, device=dev)
     out = torch.empty((n, 3), dtype=torch.float32, device=dev)
     _lib.check(_lib.load().d3d_cloud_transform(_ptr(xyz) if n else None, n, _ptr(rt), _ptr(out) if n else None, _stream()),
                "d3d_cloud_transform")
@@ -107,7 +114,7 @@ def apply(xyz, T):
 # the sums
 # ----------------------------------------------------------------------------------------
 def _e_max(e_max):
-    if isinstance(e_max, bool) or not isinstance(e_max, (int, np.integer)) or not 0 <= e_max <= CAP:
+    if not _geom.is_int(e_max, 0, CAP):
         raise ValueError("e_max must be an integer in 0 .. 1024 (got %r)" % (e_max,))
     return int(e_max)
 
@@ -116,16 +123,16 @@ def pair_sums(moved_xyz, e, idx, reference_xyz, grid, e_max=CAP):
     """moved_xyz [n,3] fp32, e [n] int32 and idx [n] int32 of cloud_compare.nearest(moved_xyz, reference_xyz, grid), reference_xyz
     [m,3] fp32, all on one GPU -> sums [27] int64 of the module's docstring: a device tensor queued on the caller's stream; the host
     reads nothing.  CPU tensors are refused."""
-    grid = cloud_compare._grid(grid)
+    cloud.check_grid(grid)
     e_max = _e_max(e_max)
-    moved_xyz, reference_xyz = _points(moved_xyz, "moved_xyz"), _points(reference_xyz, "reference_xyz")
+    moved_xyz, reference_xyz = cloud.points(moved_xyz, "moved_xyz"), cloud.points(reference_xyz, "reference_xyz")
     n, m = int(moved_xyz.shape[0]), int(reference_xyz.shape[0])
     for t, name in ((e, "e"), (idx, "idx")):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s must be a torch.Tensor" % name)
         if t.dtype != torch.int32 or tuple(t.shape) != (n,):
             raise ValueError("%s must be a [%d] int32 tensor (got %s %s)" % (name, n, t.dtype, tuple(t.shape)))
-    moved_xyz, reference_xyz = _on_gpu(moved_xyz, "moved_xyz"), _on_gpu(reference_xyz, "reference_xyz")
+    moved_xyz, reference_xyz = cloud.on_gpu(moved_xyz, "moved_xyz", _VERB), cloud.on_gpu(reference_xyz, "reference_xyz", _VERB)
     dev = moved_xyz.device
     for t, name in ((e, "e"), (idx, "idx"), (reference_xyz, "reference_xyz")):
         if t.device != dev:
@@ -155,7 +162,7 @@ def solve(sums, grid):
     """The closed-form rigid alignment of the module's docstring from the 27 sums (a list, array or tensor) on `grid`.  Host only, no
     GPU needed.  -> (dT, info): dT a 4 x 4 float64 array that moves the a's onto the b's in the least-squares sense, or None when
     the pairs do not determine one; info = {"pairs": N, "rms": sqrt(sums[26] / N) / 1024 * h (0.0 for N = 0), "degenerate": bool}."""
-    grid = cloud_compare._grid(grid)
+    cloud.check_grid(grid)
     s = _sums(sums)
     h, N = grid.voxel, s[0]
     if N < 0:
@@ -201,7 +208,7 @@ def _schedule(max_dists):
         caps = [max_dists]
     if not caps:
         raise ValueError("at least one max_dist is needed")
-    caps = [_cap(h) for h in caps]
+    caps = [cloud_compare.check_max_dist(h) for h in caps]
     if any(b >= a for a, b in zip(caps, caps[1:])):
         raise ValueError("the max_dist schedule must decrease strictly, coarse to fine (got %r)" % (caps,))
     return caps
@@ -210,10 +217,9 @@ def _schedule(max_dists):
 def _plan(border, max_dists, max_iterations, tolerance, max_pair_dist):
     """[(grid, e_max, tolerance)] per stage, every setting checked."""
     caps = _schedule(max_dists)
-    if isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer)) or max_iterations < 1:
+    if not _geom.is_int(max_iterations, 1):
         raise ValueError("max_iterations must be an integer >= 1 (got %r)" % (max_iterations,))
-    if tolerance is not None and (isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating))
-                                  or not (math.isfinite(tolerance) and tolerance > 0)):
+    if tolerance is not None and not _geom.is_real(tolerance, above=0):
         raise ValueError("tolerance must be finite and > 0 (got %r)" % (tolerance,))
     stages = []
     for h in caps:
@@ -235,8 +241,7 @@ def register(cloud_xyz, reference_xyz, border, max_dists, init=None, max_iterati
     device tensor).  The host reads the 27 sums once per iteration.  CPU tensors are refused."""
     stages = _plan(border, max_dists, max_iterations, tolerance, max_pair_dist)
     T = _transform(np.eye(4) if init is None else init, "init")
-    cloud_xyz = _on_gpu(_points(cloud_xyz, "cloud_xyz"), "cloud_xyz")
-    reference_xyz = _on_gpu(_points(reference_xyz, "reference_xyz"), "reference_xyz")
+    cloud_xyz, reference_xyz = _points(cloud_xyz, "cloud_xyz"), _points(reference_xyz, "reference_xyz")
     if cloud_xyz.device != reference_xyz.device:
         raise ValueError("cloud_xyz is on %s and reference_xyz on %s: both clouds must be on one GPU" % (cloud_xyz.device, reference_xyz.device))
     log = []
@@ -269,7 +274,7 @@ def write_transform(path, T):
     """Four lines of four numbers, written with repr: read_transform gives the same bits back."""
     T = _transform(T)
     text = "".join(" ".join(repr(float(v)) for v in row) + "\n" for row in T.tolist())
-    cloud_compare._write(path, text.encode("ascii"))
+    _geom.write_bytes(path, text.encode("ascii"))
     return str(path)
 
 
@@ -288,13 +293,12 @@ def read_transform(path):
 
 def xyz_ply_bytes(xyz):
     """The bytes of a binary little-endian PLY with x y z float per point, in input order.  A host array or a tensor."""
-    xyz = xyz.detach().cpu().numpy() if isinstance(xyz, torch.Tensor) else np.asarray(xyz)
+    xyz = _geom.host(xyz)
     n = int(xyz.shape[0])
     if xyz.dtype != np.float32 or xyz.shape != (n, 3):
         raise ValueError("xyz must be [n,3] float32 (got %s %s)" % (xyz.shape, xyz.dtype))
-    head = ["ply", "format binary_little_endian 1.0", "comment registered cloud (deep3d_aerial_amd.cloud_register)", "element vertex %d" % n,
-            "property float x", "property float y", "property float z", "end_header"]
-    return ("\n".join(head) + "\n").encode("ascii") + np.ascontiguousarray(xyz, "<f4").tobytes()
+    rec = np.ascontiguousarray(xyz, "<f4").view([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]).reshape(n)
+    return _geom.record_ply_bytes("registered cloud (deep3d_aerial_amd.cloud_register)", rec)
 
 
 # ----------------------------------------------------------------------------------------
@@ -365,9 +369,9 @@ def main(argv=None):
     if a.out_transform is not None:
         write_transform(a.out_transform, T)
     if a.out is not None:
-        cloud_compare._write(a.out, xyz_ply_bytes(moved))
+        _geom.write_bytes(a.out, xyz_ply_bytes(moved))
     if a.json is not None:
-        cloud_compare._write(a.json, (line + "\n").encode("ascii"))
+        _geom.write_bytes(a.json, (line + "\n").encode("ascii"))
     print(line)
     return result
 

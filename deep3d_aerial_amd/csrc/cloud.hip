@@ -27,22 +27,22 @@
 //             key.  A run that crosses waves adds once per wave.  Built with -DD3D_CLOUD_PLAIN every lane issues its own atomics
 //             instead: the form tools/cloud_bench.py --variant_library times beside this one.
 // neighbours: one lane per voxel.  ix is the low field of the key, so the 27 neighbours are 9 runs of up to three consecutive
-//             keys, each one pair of binary searches in the unique keys and one difference of the exclusive scan of the counts.
-//             A run is clipped to 0 .. n_x - 1 and rows and layers outside the grid are skipped: it never reaches the next row.
+//             keys, each one pair of binary searches in the unique keys (cloud_lower, cloud_search.h) and one difference of the
+//             exclusive scan of the counts.  A run is clipped to 0 .. n_x - 1 and rows and layers outside the grid are skipped:
+//             it never reaches the next row (the window of cloud_bound).
+// gather:     not a step of the merge: the kernel behind search_gather (cloud_search.h), kept here so that the library holds it once.
 // finalize:   the scan of the keep flags places the kept voxels; one lane per voxel writes its outputs.
 // Atomics: integer atomicAdd with the result unused, nothing else: the same bits for any input order.
 #include <climits>
 #include <cmath>
 
+#include "cloud_search.h"
 #include "common.h"
 #include "geom_shared.h"
 
 namespace d3d {
 
 constexpr int CL_BLOCK = 256;
-constexpr int CL_AXIS_BITS = 21;
-constexpr long long CL_AXIS_MAX = (1ll << CL_AXIS_BITS) - 1;   // the largest n_a
-constexpr long long CL_DROPPED = LLONG_MAX;
 constexpr float CL_NORMAL_MAX = 1024.0f;                       // |n_c| above this adds nothing: 2^31 members cannot overflow int64
 
 struct CloudGrid {
@@ -68,15 +68,34 @@ __global__ __launch_bounds__(CL_BLOCK) void cloud_keys_kernel(const float* __res
     bool ok = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) ok = cloud_cell(xyz[3 * p + a], g.lo[a], g.v, g.n[a], i + a, r + a) && ok;
-    keys[p] = ok ? (i[2] << 42) | (i[1] << 21) | i[0] : CL_DROPPED;
+    keys[p] = ok ? (i[2] << 42) | (i[1] << 21) | i[0] : CLOUD_DROPPED;
     frac[p] = ok ? r[0] | (r[1] << 16) | (r[2] << 32) : 0;
+}
+
+// search_gather (cloud_search.h): the family's one gather, for the searches of cloud_outliers.hip and cloud_compare.hip.
+__global__ __launch_bounds__(CL_BLOCK) void cloud_gather_kernel(const float* __restrict__ xyz, const long long* __restrict__ order, long n,
+                                                                float4* __restrict__ rec) {
+    const long p = (long)blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const long long src = order[p];
+    const bool ok = src >= 0 && src < n;   // always true for a sort order: a guard on the loads
+    const float bad = __int_as_float(0x7fc00000);
+    rec[p] = ok ? make_float4(xyz[3 * src], xyz[3 * src + 1], xyz[3 * src + 2], __int_as_float((int)src))
+                : make_float4(bad, bad, bad, __int_as_float(-1));
+}
+
+int search_gather(const float* xyz, const long long* order, long long n, float4* rec, hipStream_t st) {
+    if (n <= 0) return D3D_OK;
+    hipLaunchKernelGGL(cloud_gather_kernel, dim3(ceil_div(n, CL_BLOCK)), dim3(CL_BLOCK), 0, st, xyz, order, (long)n, rec);
+    D3D_LAUNCH_CHECK("cloud_gather_kernel launch");
+    return D3D_OK;
 }
 
 __global__ __launch_bounds__(CL_BLOCK) void cloud_heads_kernel(const long long* __restrict__ keys, long n, int* __restrict__ mark) {
     const long p = (long)blockIdx.x * CL_BLOCK + threadIdx.x;
     if (p >= n) return;
     const long long k = keys[p];
-    mark[p] = k != CL_DROPPED && (p + 1 == n || keys[p + 1] != k) ? 1 : 0;
+    mark[p] = k != CLOUD_DROPPED && (p + 1 == n || keys[p + 1] != k) ? 1 : 0;
 }
 
 // The inclusive sum of x over the lanes at and below this one that hold the same voxel v (v is sorted over the wave).
@@ -102,8 +121,8 @@ __global__ __launch_bounds__(CL_BLOCK) void cloud_accumulate_kernel(const long l
                                                                     long long* __restrict__ acc) {
     constexpr int STRIDE = 3 + (NRM ? 3 : 0) + (COL ? 3 : 0);
     const long p = (long)blockIdx.x * CL_BLOCK + threadIdx.x;
-    const long long key = p < n ? keys[p] : CL_DROPPED;
-    int v = key != CL_DROPPED ? vox[p] : -1;
+    const long long key = p < n ? keys[p] : CLOUD_DROPPED;
+    int v = key != CLOUD_DROPPED ? vox[p] : -1;
     if (v >= n_voxels) v = -1;   // never true (the scan's total is n_voxels): a guard on the writes
     int c = 0, r[3] = {0, 0, 0}, col[3] = {0, 0, 0};
     long long nq[3] = {0, 0, 0};
@@ -164,17 +183,6 @@ __global__ __launch_bounds__(CL_BLOCK) void cloud_accumulate_kernel(const long l
     }
 }
 
-// The first index in the sorted keys [0, n) whose key is >= k.
-__device__ __forceinline__ int cloud_lower(const long long* __restrict__ keys, int n, long long k) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(CL_BLOCK) void cloud_neighbours_kernel(const long long* __restrict__ ukeys, const int* __restrict__ count,
                                                                     const int* __restrict__ before, int n_voxels, int nx, int ny, int nz,
                                                                     int min_points, int* __restrict__ keep) {
@@ -185,13 +193,15 @@ __global__ __launch_bounds__(CL_BLOCK) void cloud_neighbours_kernel(const long l
         return;
     }
     const long long key = ukeys[v];
-    const int ix = (int)(key & CL_AXIS_MAX), iy = (int)((key >> 21) & CL_AXIS_MAX), iz = (int)(key >> 42);
+    // The window of cloud_bound (cloud_search.h), written as loops over the rows and layers inside the grid: stated with
+    // cloud_bound itself the kernel was 0.5 % slower at 10^8 points.
+    const int ix = (int)(key & CLOUD_AXIS_MAX), iy = (int)((key >> 21) & CLOUD_AXIS_MAX), iz = (int)(key >> 42);
     const int x0 = max(ix - 1, 0), x1 = min(ix + 1, nx - 1);
     long long sum = 0;
     for (int z = max(iz - 1, 0); z <= min(iz + 1, nz - 1); ++z)
         for (int y = max(iy - 1, 0); y <= min(iy + 1, ny - 1); ++y) {
             const long long row = ((long long)z << 42) | ((long long)y << 21);
-            const int a = cloud_lower(ukeys, n_voxels, row | x0), b = cloud_lower(ukeys, n_voxels, (row | x1) + 1);
+            const int a = cloud_lower(ukeys, 0, n_voxels, row | x0), b = cloud_lower(ukeys, 0, n_voxels, (row | x1) + 1);
             if (b > a) sum += (long long)before[b - 1] + count[b - 1] - before[a];
         }
     keep[v] = sum >= (long long)min_points ? 1 : 0;
@@ -209,7 +219,7 @@ __global__ __launch_bounds__(CL_BLOCK) void cloud_finalize_kernel(const long lon
     const long o = pos[v];
     if (o >= n_kept) return;   // never true (n_kept is the scan's total): a guard on the writes
     const long long key = ukeys[v];
-    const long long i[3] = {key & CL_AXIS_MAX, (key >> 21) & CL_AXIS_MAX, key >> 42};
+    const long long i[3] = {key & CLOUD_AXIS_MAX, (key >> 21) & CLOUD_AXIS_MAX, key >> 42};
     const int c = count[v];
     const long long* A = acc + (long)v * STRIDE;
     const double cd = (double)c;
@@ -252,27 +262,9 @@ static CloudScratch cloud_layout(long long n) {
     return s;
 }
 
-static bool cloud_count_ok(long long n) { return n >= 0 && n < (1ll << 31); }
-
-struct CloudRange {
-    const void* p;
-    size_t bytes;
-};
-
-// No two of the non-null, non-empty buffers overlap.
-static bool cloud_apart(const CloudRange* r, int n) {
-    for (int a = 0; a < n; ++a)
-        for (int b = a + 1; b < n; ++b) {
-            if (!r[a].p || !r[b].p || !r[a].bytes || !r[b].bytes) continue;
-            const uintptr_t a0 = (uintptr_t)r[a].p, b0 = (uintptr_t)r[b].p;
-            if (!(a0 + r[a].bytes <= b0 || b0 + r[b].bytes <= a0)) return false;
-        }
-    return true;
-}
-
 static int cloud_axis(double lo, double hi, double v, int* n) {
     const double c = std::ceil((hi - lo) / v);
-    if (!(c >= 1.0 && c <= (double)CL_AXIS_MAX)) return 0;
+    if (!(c >= 1.0 && c <= (double)CLOUD_AXIS_MAX)) return 0;
     *n = (int)c;
     return 1;
 }
@@ -297,20 +289,20 @@ static int cloud_grid(double x_min, double x_max, double y_min, double y_max, do
 using namespace d3d;
 
 extern "C" size_t d3d_cloud_scratch_bytes(long long n) {
-    if (!cloud_count_ok(n)) return 0;
+    if (!count_ok(n)) return 0;
     return cloud_layout(n).bytes;
 }
 
 extern "C" int d3d_cloud_keys(const float* xyz, long long n_points, double x_min, double x_max, double y_min, double y_max, double z_min,
                               double z_max, double voxel, long long* keys, long long* frac, d3d_stream_t stream) {
-    D3D_REQUIRE(cloud_count_ok(n_points), "n_points=%lld (0 .. 2^31 - 1)", n_points);
+    D3D_REQUIRE(count_ok(n_points), "n_points=%lld (0 .. 2^31 - 1)", n_points);
     D3D_REQUIRE((xyz && keys && frac) || n_points == 0, "null pointer (xyz, keys, frac) with %lld points", n_points);
     CloudGrid g;
     const int rc = cloud_grid(x_min, x_max, y_min, y_max, z_min, z_max, voxel, &g);
     if (rc != D3D_OK) return rc;
     const size_t n = (size_t)n_points;
-    const CloudRange R[3] = {{xyz, n * 12}, {keys, n * 8}, {frac, n * 8}};
-    D3D_REQUIRE(cloud_apart(R, 3), "xyz, keys and frac must not alias");
+    const SearchRange R[3] = {{xyz, n * 12}, {keys, n * 8}, {frac, n * 8}};
+    D3D_REQUIRE(search_apart(R, 3), "xyz, keys and frac must not alias");
     if (n_points == 0) return D3D_OK;
     hipLaunchKernelGGL(cloud_keys_kernel, dim3(ceil_div(n_points, CL_BLOCK)), dim3(CL_BLOCK), 0, (hipStream_t)stream, xyz, (long)n_points, g,
                        keys, frac);
@@ -320,14 +312,14 @@ extern "C" int d3d_cloud_keys(const float* xyz, long long n_points, double x_min
 
 extern "C" int d3d_cloud_heads(const long long* sorted_keys, long long n_points, void* scratch, size_t scratch_bytes, int* vox,
                                long long* n_voxels, d3d_stream_t stream) {
-    D3D_REQUIRE(cloud_count_ok(n_points), "n_points=%lld (0 .. 2^31 - 1)", n_points);
+    D3D_REQUIRE(count_ok(n_points), "n_points=%lld (0 .. 2^31 - 1)", n_points);
     D3D_REQUIRE(scratch && n_voxels, "null pointer (scratch, n_voxels)");
     D3D_REQUIRE((sorted_keys && vox) || n_points == 0, "null pointer (sorted_keys, vox) with %lld points", n_points);
     const CloudScratch L = cloud_layout(n_points);
     D3D_REQUIRE(scratch_bytes >= L.bytes, "scratch of %zu bytes, %zu needed (d3d_cloud_scratch_bytes)", scratch_bytes, L.bytes);
     const size_t n = (size_t)n_points;
-    const CloudRange R[4] = {{sorted_keys, n * 8}, {vox, n * 4}, {scratch, scratch_bytes}, {n_voxels, 8}};
-    D3D_REQUIRE(cloud_apart(R, 4), "sorted_keys, vox, scratch and n_voxels must not alias");
+    const SearchRange R[4] = {{sorted_keys, n * 8}, {vox, n * 4}, {scratch, scratch_bytes}, {n_voxels, 8}};
+    D3D_REQUIRE(search_apart(R, 4), "sorted_keys, vox, scratch and n_voxels must not alias");
     hipStream_t st = (hipStream_t)stream;
     if (n_points > 0) {
         hipLaunchKernelGGL(cloud_heads_kernel, dim3(ceil_div(n_points, CL_BLOCK)), dim3(CL_BLOCK), 0, st, sorted_keys, (long)n_points, vox);
@@ -339,16 +331,16 @@ extern "C" int d3d_cloud_heads(const long long* sorted_keys, long long n_points,
 extern "C" int d3d_cloud_accumulate(const long long* sorted_keys, const long long* order, const int* vox, const long long* frac,
                                     const float* normal, const int* color, long long n_points, long long n_voxels, long long* ukeys,
                                     int* count, long long* acc, d3d_stream_t stream) {
-    D3D_REQUIRE(cloud_count_ok(n_points), "n_points=%lld (0 .. 2^31 - 1)", n_points);
+    D3D_REQUIRE(count_ok(n_points), "n_points=%lld (0 .. 2^31 - 1)", n_points);
     D3D_REQUIRE(n_voxels >= 0 && n_voxels <= n_points, "n_voxels=%lld (0 .. n_points = %lld)", n_voxels, n_points);
     D3D_REQUIRE((sorted_keys && order && vox && frac) || n_points == 0, "null pointer (sorted_keys, order, vox, frac) with %lld points",
                 n_points);
     D3D_REQUIRE((ukeys && count && acc) || n_voxels == 0, "null pointer (ukeys, count, acc) with %lld voxels", n_voxels);
     const size_t n = (size_t)n_points, m = (size_t)n_voxels;
     const size_t stride = 3 + (normal ? 3 : 0) + (color ? 3 : 0);
-    const CloudRange R[9] = {{sorted_keys, n * 8}, {order, n * 8}, {vox, n * 4},  {frac, n * 8},         {normal, n * 12},
+    const SearchRange R[9] = {{sorted_keys, n * 8}, {order, n * 8}, {vox, n * 4},  {frac, n * 8},         {normal, n * 12},
                              {color, n * 12},      {ukeys, m * 8}, {count, m * 4}, {acc, m * stride * 8}};
-    D3D_REQUIRE(cloud_apart(R, 9), "the inputs, ukeys, count and acc must not alias");
+    D3D_REQUIRE(search_apart(R, 9), "the inputs, ukeys, count and acc must not alias");
     if (n_voxels == 0) return D3D_OK;
     hipStream_t st = (hipStream_t)stream;
     int rc = hip_status(hipMemsetAsync(count, 0, m * 4, st), "cloud: clear count");
@@ -370,17 +362,16 @@ extern "C" int d3d_cloud_accumulate(const long long* sorted_keys, const long lon
 
 extern "C" int d3d_cloud_neighbours(const long long* ukeys, const int* count, long long n_voxels, int nx, int ny, int nz, int min_points,
                                     void* scratch, size_t scratch_bytes, int* keep, int* pos, long long* n_kept, d3d_stream_t stream) {
-    D3D_REQUIRE(cloud_count_ok(n_voxels), "n_voxels=%lld (0 .. 2^31 - 1)", n_voxels);
+    D3D_REQUIRE(count_ok(n_voxels), "n_voxels=%lld (0 .. 2^31 - 1)", n_voxels);
     D3D_REQUIRE(scratch && n_kept, "null pointer (scratch, n_kept)");
     D3D_REQUIRE((ukeys && count && keep && pos) || n_voxels == 0, "null pointer (ukeys, count, keep, pos) with %lld voxels", n_voxels);
-    D3D_REQUIRE(nx >= 1 && nx <= CL_AXIS_MAX && ny >= 1 && ny <= CL_AXIS_MAX && nz >= 1 && nz <= CL_AXIS_MAX,
-                "grid of %d x %d x %d voxels (1 .. 2^21 - 1 per axis)", nx, ny, nz);
+    if (search_grid_ok(nx, ny, nz, "voxels") != D3D_OK) return D3D_ERR_INVALID_ARG;
     D3D_REQUIRE(min_points >= 1, "min_points=%d (>= 1)", min_points);
     const CloudScratch L = cloud_layout(n_voxels);
     D3D_REQUIRE(scratch_bytes >= L.bytes, "scratch of %zu bytes, %zu needed (d3d_cloud_scratch_bytes)", scratch_bytes, L.bytes);
     const size_t m = (size_t)n_voxels;
-    const CloudRange R[6] = {{ukeys, m * 8}, {count, m * 4}, {keep, m * 4}, {pos, m * 4}, {scratch, scratch_bytes}, {n_kept, 8}};
-    D3D_REQUIRE(cloud_apart(R, 6), "ukeys, count, keep, pos, scratch and n_kept must not alias");
+    const SearchRange R[6] = {{ukeys, m * 8}, {count, m * 4}, {keep, m * 4}, {pos, m * 4}, {scratch, scratch_bytes}, {n_kept, 8}};
+    D3D_REQUIRE(search_apart(R, 6), "ukeys, count, keep, pos, scratch and n_kept must not alias");
     hipStream_t st = (hipStream_t)stream;
     char* s = (char*)scratch;
     int* before = (int*)(s + L.before);
@@ -398,7 +389,7 @@ extern "C" int d3d_cloud_finalize(const long long* ukeys, const int* count, cons
                                   long long n_voxels, long long n_kept, double x_min, double x_max, double y_min, double y_max,
                                   double z_min, double z_max, double voxel, float* xyz, float* normal, unsigned char* color,
                                   int* out_count, d3d_stream_t stream) {
-    D3D_REQUIRE(cloud_count_ok(n_voxels), "n_voxels=%lld (0 .. 2^31 - 1)", n_voxels);
+    D3D_REQUIRE(count_ok(n_voxels), "n_voxels=%lld (0 .. 2^31 - 1)", n_voxels);
     D3D_REQUIRE(n_kept >= 0 && n_kept <= n_voxels, "n_kept=%lld (0 .. n_voxels = %lld)", n_kept, n_voxels);
     D3D_REQUIRE((ukeys && count && acc && keep && pos) || n_voxels == 0, "null pointer (ukeys, count, acc, keep, pos) with %lld voxels",
                 n_voxels);
@@ -408,9 +399,9 @@ extern "C" int d3d_cloud_finalize(const long long* ukeys, const int* count, cons
     if (rc != D3D_OK) return rc;
     const size_t m = (size_t)n_voxels, k = (size_t)n_kept;
     const size_t stride = 3 + (normal ? 3 : 0) + (color ? 3 : 0);
-    const CloudRange R[9] = {{ukeys, m * 8}, {count, m * 4},   {acc, m * stride * 8}, {keep, m * 4},     {pos, m * 4},
+    const SearchRange R[9] = {{ukeys, m * 8}, {count, m * 4},   {acc, m * stride * 8}, {keep, m * 4},     {pos, m * 4},
                              {xyz, k * 12},  {normal, k * 12}, {color, k * 3},        {out_count, k * 4}};
-    D3D_REQUIRE(cloud_apart(R, 9), "the inputs, xyz, normal, color and out_count must not alias");
+    D3D_REQUIRE(search_apart(R, 9), "the inputs, xyz, normal, color and out_count must not alias");
     if (n_kept == 0) return D3D_OK;
     const dim3 grid(ceil_div(n_voxels, CL_BLOCK)), block(CL_BLOCK);
     hipStream_t st = (hipStream_t)stream;

@@ -15,28 +15,25 @@
 // Sums over the m keyed points, int64: sums[0] = m, sums[1] = S1 = sum D, sums[2] = S2 = sum D^2.  D <= 2^15 (k <= 32) and
 // m < 2^31 keep S2 below 2^61.
 //
-// gather:    one lane per sorted point copies its coordinates through the order into a float4 array in key order, so the
-//            candidates of a cell are consecutive 16-byte loads.
+// gather:    search_gather (cloud_search.h): the coordinates in key order as 16-byte records, so the candidates of a cell are
+//            consecutive 16-byte loads.
 // distances: one lane per sorted point, one workgroup per 256 consecutive sorted points.  ix is the key's low field, so the
 //            candidates of a cell are 9 runs of up to three consecutive cells, each one pair of binary searches in the sorted
-//            keys (the scheme of cloud_neighbours_kernel: clipped to the grid, never reaching the next row).  The points of one
-//            cell share their 9 ranges: the workgroup numbers the cells its points lie in (a scan of the run heads), the 18
-//            searches of every cell are spread over its lanes, one search a lane, and the bounds wait in LDS ([bound][cell]:
-//            consecutive cells on consecutive banks).  Only the first and the last cell search all the keys: a bound's key does
-//            not decrease from cell to cell, so the other cells search between those two results, a few steps in nearby keys.
-//            Each lane then streams the candidates of its cell's ranges, four loads ahead of their use -- the lanes of a cell
-//            read the same addresses, one broadcast load a wave -- and keeps the K smallest d2 in a sorted list of K fp64
-//            registers (K = 8, 16 or 32 >= k, a template argument): an insertion is K compare / select pairs at compile-time
-//            indices, so the list never leaves the registers (no scratch).  e does not decrease with d2, so the e of the k
-//            smallest d2 are the k smallest e: the sqrt and the division run k times a point, not once a candidate.  The list
-//            starts at cap2 everywhere: a candidate at or past the cap, or a missing one, needs no insertion and counts 1024.
-//            Results go back to input order through the order.
+//            keys (cloud_bound: clipped to the grid, never reaching the next row).  The points of one cell share their 9
+//            ranges: search_tile (cloud_search.h, which says why only the first and the last cell search all the keys) parks the
+//            bounds of the workgroup's cells in LDS, the cloud's keys being both the queries and the targets.  Each lane then
+//            streams the candidates of its cell's ranges (search_walk, four loads ahead of their use), skips itself, and keeps
+//            the K smallest d2 in a sorted list of K fp64 registers (K = 8, 16 or 32 >= k, a template argument): an insertion
+//            is K compare / select pairs at compile-time indices, so the list never leaves the registers (no scratch).  e does
+//            not decrease with d2, so the e of the k smallest d2 are the k smallest e: the sqrt and the division run k times a
+//            point, not once a candidate.  The list starts at cap2 everywhere: a candidate at or past the cap, or a missing one,
+//            needs no insertion and counts 1024.  Results go back to input order through the order.
 //            Built with -DD3D_CLOUD_OUTLIERS_PLAIN every lane runs its own 18 searches, takes e of every candidate within the
 //            radius and keeps a list of k entries indexed at run time: the plain statement of the rule, the form
 //            tools/cloud_outliers_bench.py --variant_library times beside this one.
 // Sums:      per wave (shuffles), then per workgroup (LDS), then one integer atomicAdd per workgroup and sum, its result unused.
 // Atomics: that integer atomicAdd, nothing else: the same bits for any input order.
-// The lower bound, the 18-bound rule, d2 and e are cloud_search.h's, shared with cloud_compare.hip.
+// The lower bound, the 18-bound rule, the tile, the walk, the gather, d2 and e are cloud_search.h's, shared with cloud_compare.hip.
 #include <climits>
 #include <cmath>
 
@@ -46,22 +43,7 @@
 
 namespace d3d {
 
-constexpr int CO_BLOCK = 256;
-constexpr int CO_WAVES = CO_BLOCK / 64;
-constexpr long long CO_AXIS_MAX = CLOUD_AXIS_MAX;   // the largest n_a (cloud.hip)
-constexpr long long CO_DROPPED = CLOUD_DROPPED;     // the key of an unkeyed point (cloud.hip)
-constexpr int CO_CAP = CLOUD_E_CAP;                  // e of a candidate at or past the radius, and of a missing one
 constexpr int CO_K_MAX = 32;
-
-__global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_gather_kernel(const float* __restrict__ xyz, const long long* __restrict__ order,
-                                                                         long n, float4* __restrict__ sxyz) {
-    const long p = (long)blockIdx.x * CO_BLOCK + threadIdx.x;
-    if (p >= n) return;
-    const long long src = order[p];
-    const bool ok = src >= 0 && src < n;   // always true for a sort order: a guard on the loads
-    const float bad = __int_as_float(0x7fc00000);
-    sxyz[p] = ok ? make_float4(xyz[3 * src], xyz[3 * src + 1], xyz[3 * src + 2], 0.0f) : make_float4(bad, bad, bad, 0.0f);
-}
 
 // Inserts d into the increasing list c and drops the largest; every index is a compile-time constant after unrolling.
 template <int K>
@@ -75,7 +57,7 @@ __device__ __forceinline__ void outl_insert(double (&c)[K], double d) {
 }
 
 // The sums of the workgroup into sums[0 .. 2]: m, S1, S2.
-__device__ __forceinline__ void outl_sums(bool keyed, int dist, long long (*red)[CO_WAVES], unsigned long long* __restrict__ sums) {
+__device__ __forceinline__ void outl_sums(bool keyed, int dist, long long (*red)[SEARCH_WAVES], unsigned long long* __restrict__ sums) {
     const long long d = keyed ? (long long)dist : 0;
     const long long s0 = wave_sum<long long>(keyed ? 1 : 0), s1 = wave_sum(d), s2 = wave_sum(d * d);
     if ((threadIdx.x & 63) == 0) {
@@ -88,7 +70,7 @@ __device__ __forceinline__ void outl_sums(bool keyed, int dist, long long (*red)
     if (threadIdx.x < 3) {
         long long t = 0;
 #pragma unroll
-        for (int w = 0; w < CO_WAVES; ++w) t += red[threadIdx.x][w];
+        for (int w = 0; w < SEARCH_WAVES; ++w) t += red[threadIdx.x][w];
         if (t != 0) atomicAdd(sums + threadIdx.x, (unsigned long long)t);
     }
 }
@@ -104,43 +86,17 @@ __device__ __forceinline__ void outl_store(const long long* __restrict__ order, 
 }
 
 #ifndef D3D_CLOUD_OUTLIERS_PLAIN
-constexpr int CO_BOUNDS = CLOUD_BOUNDS;   // 9 ranges, a first and a past-the-last sorted index each
-constexpr int CO_AHEAD = 4;     // candidates loaded ahead of their use
-
 template <int K>
-__global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_kernel(const long long* __restrict__ keys, const long long* __restrict__ order,
-                                                                  const float4* __restrict__ sxyz, long n, int nx, int ny, int nz, double h,
-                                                                  int k, int* __restrict__ out_dist, int* __restrict__ out_nn,
-                                                                  unsigned long long* __restrict__ sums) {
-    __shared__ long long cell_key[CO_BLOCK];
-    __shared__ int bound[CO_BOUNDS][CO_BLOCK];
-    __shared__ int edge[2][CO_BOUNDS];
-    __shared__ int scan_lds[CO_WAVES];
-    __shared__ long long red[3][CO_WAVES];
-    const int tid = threadIdx.x;
-    const long p = (long)blockIdx.x * CO_BLOCK + tid;
-    const long long key = p < n ? keys[p] : CO_DROPPED;
-    const bool keyed = key != CO_DROPPED;
-    // the cells of this workgroup's points, numbered in key order: a lane heads a cell when the lane before it holds another key
-    const int head = keyed && (tid == 0 || keys[p - 1] != key) ? 1 : 0;
-    int n_cells;
-    const int cell = block_exclusive(head, scan_lds, &n_cells) + head - 1;   // >= 0 for a keyed lane: lane 0 heads a cell
-    if (head) cell_key[cell] = key;
-    __syncthreads();
-    // The key a bound searches for does not decrease from one cell to the next (the cells are in key order, the row's offset is
-    // the same and the clipping is monotone), so every cell's bound b lies between the first cell's and the last cell's: those
-    // two are searched in all the keys (from 0 for a first cell whose row is outside the grid, to n for such a last cell), the
-    // others between them, a few steps in keys this workgroup's points lie next to.
-    if (tid < 2 * CO_BOUNDS && n_cells > 0) {
-        const int last = tid / CO_BOUNDS, b = tid - CO_BOUNDS * last;
-        edge[last][b] = cloud_bound(keys, 0, (int)n, cell_key[last ? n_cells - 1 : 0], b, nx, ny, nz, last ? (int)n : 0);
-    }
-    __syncthreads();
-    for (int t = tid; t < CO_BOUNDS * n_cells; t += CO_BLOCK) {
-        const int c = t / CO_BOUNDS, b = t - CO_BOUNDS * c;
-        bound[b][c] = cloud_bound(keys, edge[0][b], edge[1][b], cell_key[c], b, nx, ny, nz, 0);
-    }
-    __syncthreads();
+__global__ __launch_bounds__(SEARCH_BLOCK) void cloud_outliers_kernel(const long long* __restrict__ keys, const long long* __restrict__ order,
+                                                                      const float4* __restrict__ sxyz, long n, int nx, int ny, int nz,
+                                                                      double h, int k, int* __restrict__ out_dist, int* __restrict__ out_nn,
+                                                                      unsigned long long* __restrict__ sums) {
+    __shared__ SearchTile tile;
+    __shared__ long long red[3][SEARCH_WAVES];
+    const long p = (long)blockIdx.x * SEARCH_BLOCK + threadIdx.x;
+    const long long key = p < n ? keys[p] : CLOUD_DROPPED;
+    const bool keyed = key != CLOUD_DROPPED;
+    const int cell = search_tile(tile, keys, p, key, keys, n, nx, ny, nz);   // the cloud is its own target
     // e does not decrease with d2 (a correctly rounded sqrt, a division by h > 0, a product and llrint are monotone), so the k
     // smallest e are the e of the k smallest d2: the list holds d2, and the sqrt and the division run k times a point
     const double cap2 = h * h;
@@ -150,39 +106,30 @@ __global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_kernel(const long lon
     int nn = 0;
     if (keyed) {
         const float4 a = sxyz[p];
-        for (int r = 0; r < 9; ++r) {
-            const int j1 = min(bound[2 * r + 1][cell], (int)n);   // (never above n: a guard on the loads)
-            for (int j = max(bound[2 * r][cell], 0); j < j1; j += CO_AHEAD) {
-                float4 q[CO_AHEAD];   // CO_AHEAD loads in flight before the first is used
-#pragma unroll
-                for (int u = 0; u < CO_AHEAD; ++u) q[u] = sxyz[min(j + u, j1 - 1)];
-#pragma unroll
-                for (int u = 0; u < CO_AHEAD; ++u) {
-                    if (j + u >= j1 || j + u == p) continue;
-                    const double d2 = cloud_d2(a, q[u]);
-                    nn += d2 < cap2 ? 1 : 0;                 // false for a NaN
-                    if (d2 < top[K - 1]) outl_insert(top, d2);   // top[K - 1] <= cap2
-                }
-            }
-        }
+        search_walk(tile, cell, sxyz, n, [&top, &nn, a, cap2, p](int j, const float4 q) {
+            if (j == p) return;
+            const double d2 = cloud_d2(a, q);
+            nn += d2 < cap2 ? 1 : 0;                     // false for a NaN
+            if (d2 < top[K - 1]) outl_insert(top, d2);   // top[K - 1] <= cap2
+        });
     }
     int dist = 0;
 #pragma unroll
-    for (int i = 0; i < K; ++i) dist += i < k ? (top[i] < cap2 ? cloud_e(top[i], h) : CO_CAP) : 0;
+    for (int i = 0; i < K; ++i) dist += i < k ? (top[i] < cap2 ? cloud_e(top[i], h) : CLOUD_E_CAP) : 0;
     outl_store(order, p, n, keyed, dist, nn, out_dist, out_nn);
     outl_sums(keyed, dist, red, sums);
 }
 #else
-__global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_plain_kernel(const long long* __restrict__ keys, const long long* __restrict__ order,
-                                                                        const float4* __restrict__ sxyz, long n, int nx, int ny, int nz,
-                                                                        double h, int k, int* __restrict__ out_dist, int* __restrict__ out_nn,
-                                                                        unsigned long long* __restrict__ sums) {
-    __shared__ long long red[3][CO_WAVES];
-    const long p = (long)blockIdx.x * CO_BLOCK + threadIdx.x;
-    const long long key = p < n ? keys[p] : CO_DROPPED;
-    const bool keyed = key != CO_DROPPED;
+__global__ __launch_bounds__(SEARCH_BLOCK) void cloud_outliers_plain_kernel(const long long* __restrict__ keys, const long long* __restrict__ order,
+                                                                            const float4* __restrict__ sxyz, long n, int nx, int ny, int nz,
+                                                                            double h, int k, int* __restrict__ out_dist,
+                                                                            int* __restrict__ out_nn, unsigned long long* __restrict__ sums) {
+    __shared__ long long red[3][SEARCH_WAVES];
+    const long p = (long)blockIdx.x * SEARCH_BLOCK + threadIdx.x;
+    const long long key = p < n ? keys[p] : CLOUD_DROPPED;
+    const bool keyed = key != CLOUD_DROPPED;
     int top[CO_K_MAX];   // the k smallest so far, increasing; indexed at run time
-    for (int i = 0; i < k; ++i) top[i] = CO_CAP;
+    for (int i = 0; i < k; ++i) top[i] = CLOUD_E_CAP;
     int nn = 0;
     if (keyed) {
         const double cap2 = h * h;
@@ -209,34 +156,29 @@ __global__ __launch_bounds__(CO_BLOCK) void cloud_outliers_plain_kernel(const lo
 }
 #endif
 
+}  // namespace d3d
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------
-static bool outl_count_ok(long long n) { return n >= 0 && n < (1ll << 31); }
-
-static size_t outl_scratch(long long n) { return align256((size_t)(n > 0 ? n : 1) * sizeof(float4)); }
-
-}  // namespace d3d
-
 using namespace d3d;
 
 extern "C" size_t d3d_cloud_outliers_scratch_bytes(long long n) {
-    if (!outl_count_ok(n)) return 0;
-    return outl_scratch(n);
+    if (!count_ok(n)) return 0;
+    return search_gather_bytes(n);
 }
 
 extern "C" int d3d_cloud_outliers_distances(const float* xyz, const long long* sorted_keys, const long long* order, long long n_points,
                                             int nx, int ny, int nz, double radius, int k, void* scratch, size_t scratch_bytes, int* dist,
                                             int* nn, long long* sums, d3d_stream_t stream) {
-    D3D_REQUIRE(outl_count_ok(n_points), "n_points=%lld (0 .. 2^31 - 1)", n_points);
+    D3D_REQUIRE(count_ok(n_points), "n_points=%lld (0 .. 2^31 - 1)", n_points);
     D3D_REQUIRE(scratch && sums, "null pointer (scratch, sums)");
     D3D_REQUIRE((xyz && sorted_keys && order && dist && nn) || n_points == 0, "null pointer (xyz, sorted_keys, order, dist, nn) with %lld points",
                 n_points);
-    D3D_REQUIRE(nx >= 1 && nx <= CO_AXIS_MAX && ny >= 1 && ny <= CO_AXIS_MAX && nz >= 1 && nz <= CO_AXIS_MAX,
-                "grid of %d x %d x %d cells (1 .. 2^21 - 1 per axis)", nx, ny, nz);
+    if (search_grid_ok(nx, ny, nz, "cells") != D3D_OK) return D3D_ERR_INVALID_ARG;
     D3D_REQUIRE(std::isfinite(radius) && radius > 0.0, "radius %g must be finite and > 0", radius);
     D3D_REQUIRE(k >= 1 && k <= CO_K_MAX, "k=%d (1 .. %d)", k, CO_K_MAX);
-    const size_t need = outl_scratch(n_points);
+    const size_t need = search_gather_bytes(n_points);
     D3D_REQUIRE(scratch_bytes >= need, "scratch of %zu bytes, %zu needed (d3d_cloud_outliers_scratch_bytes)", scratch_bytes, need);
     const size_t n = (size_t)n_points;
     const SearchRange R[7] = {{xyz, n * 12}, {sorted_keys, n * 8}, {order, n * 8}, {scratch, scratch_bytes}, {dist, n * 4}, {nn, n * 4}, {sums, 24}};
@@ -245,10 +187,10 @@ extern "C" int d3d_cloud_outliers_distances(const float* xyz, const long long* s
     hipStream_t st = (hipStream_t)stream;
     const int rc = hip_status(hipMemsetAsync(sums, 0, 24, st), "cloud outliers: clear sums");
     if (rc != D3D_OK) return rc;
-    const dim3 grid(ceil_div(n_points, CO_BLOCK)), block(CO_BLOCK);
+    const dim3 grid(ceil_div(n_points, SEARCH_BLOCK)), block(SEARCH_BLOCK);
     float4* sxyz = (float4*)scratch;
-    hipLaunchKernelGGL(cloud_outliers_gather_kernel, grid, block, 0, st, xyz, order, (long)n_points, sxyz);
-    D3D_LAUNCH_CHECK("cloud_outliers_gather_kernel launch");
+    const int rc2 = search_gather(xyz, order, n_points, sxyz, st);
+    if (rc2 != D3D_OK) return rc2;
 #ifndef D3D_CLOUD_OUTLIERS_PLAIN
 #define CO_DISTANCES(K)                                                                                                               \
     hipLaunchKernelGGL((cloud_outliers_kernel<K>), grid, block, 0, st, sorted_keys, order, sxyz, (long)n_points, nx, ny, nz, radius, k, dist, nn, \

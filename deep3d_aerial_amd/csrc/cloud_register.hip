@@ -145,7 +145,6 @@ __global__ __launch_bounds__(CR_BLOCK) void cloud_register_sums_kernel(const flo
 // ---------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------
-static bool reg_count_ok(long long n) { return n >= 0 && n < (1ll << 31); }
 
 static int reg_resident(int* out) {
     static int known[SEARCH_MAX_DEVICES] = {};
@@ -157,7 +156,7 @@ static int reg_resident(int* out) {
 using namespace d3d;
 
 extern "C" int d3d_cloud_transform(const float* xyz, long long n, const double* rt, float* out, d3d_stream_t stream) {
-    D3D_REQUIRE(reg_count_ok(n), "n=%lld (0 .. 2^31 - 1)", n);
+    D3D_REQUIRE(count_ok(n), "n=%lld (0 .. 2^31 - 1)", n);
     D3D_REQUIRE((xyz && rt && out) || n == 0, "null pointer (xyz, rt, out) with %lld points", n);
     const SearchRange R[3] = {{xyz, (size_t)n * 12}, {rt, n ? (size_t)96 : 0}, {out, (size_t)n * 12}};
     D3D_REQUIRE(search_apart(R, 3), "xyz, rt and out must not alias");
@@ -175,13 +174,13 @@ extern "C" int d3d_cloud_transform(const float* xyz, long long n, const double* 
 extern "C" int d3d_cloud_register_sums(const float* q_xyz, const int* e, const int* idx, long long n_query, const float* t_xyz,
                                        long long n_target, double xmin, double ymin, double zmin, double cap, int e_max, long long* sums,
                                        d3d_stream_t stream) {
-    D3D_REQUIRE(reg_count_ok(n_query), "n_query=%lld (0 .. 2^31 - 1)", n_query);
-    D3D_REQUIRE(reg_count_ok(n_target), "n_target=%lld (0 .. 2^31 - 1)", n_target);
+    D3D_REQUIRE(count_ok(n_query), "n_query=%lld (0 .. 2^31 - 1)", n_query);
+    D3D_REQUIRE(count_ok(n_target), "n_target=%lld (0 .. 2^31 - 1)", n_target);
     D3D_REQUIRE(sums, "null pointer (sums)");
     D3D_REQUIRE((q_xyz && e && idx) || n_query == 0, "null pointer (q_xyz, e, idx) with %lld queries", n_query);
     D3D_REQUIRE(t_xyz || n_target == 0, "null pointer (t_xyz) with %lld targets", n_target);
     D3D_REQUIRE(std::isfinite(xmin) && std::isfinite(ymin) && std::isfinite(zmin), "origin (%g, %g, %g) must be finite", xmin, ymin, zmin);
-    D3D_REQUIRE(std::isfinite(cap) && cap > 0.0, "cap %g must be finite and > 0", cap);
+    if (search_cap_ok(cap) != D3D_OK) return D3D_ERR_INVALID_ARG;
     D3D_REQUIRE(e_max >= 0 && e_max <= CLOUD_E_CAP, "e_max=%d (0 .. 1024)", e_max);
     const size_t nq = (size_t)n_query, nt = (size_t)n_target;
     const SearchRange R[5] = {{q_xyz, nq * 12}, {e, nq * 4}, {idx, nq * 4}, {t_xyz, nt * 12}, {sums, (size_t)CR_SUMS * 8}};

@@ -97,6 +97,9 @@ inline int geom_scan(const int* in, int* out, long long n, void* scratch, long l
 // ---------------------------------------------------------------------------------------------------------------------------
 // scratch layout: `at = L.take(bytes)` hands out consecutive 256-byte aligned offsets, L.bytes is the size so far
 // ---------------------------------------------------------------------------------------------------------------------------
+// A count of points, voxels, faces or samples an entry point takes: 0 .. 2^31 - 1, so that an index fits in int32.
+inline bool count_ok(long long n) { return n >= 0 && n < (1ll << 31); }
+
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct ScratchLayout {

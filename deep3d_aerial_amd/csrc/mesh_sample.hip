@@ -231,7 +231,6 @@ __global__ __launch_bounds__(MS_BLOCK) void mesh_sample_face_error_kernel(const 
 // ---------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------
-static bool ms_count_ok(long long n) { return n >= 0 && n < (1ll << 31); }
 
 static size_t ms_scratch(long long m) { return align256(geom_scan_bytes(m)); }
 
@@ -240,15 +239,15 @@ static size_t ms_scratch(long long m) { return align256(geom_scan_bytes(m)); }
 using namespace d3d;
 
 extern "C" size_t d3d_mesh_sample_scratch_bytes(long long n_faces) {
-    if (!ms_count_ok(n_faces)) return 0;
+    if (!count_ok(n_faces)) return 0;
     return ms_scratch(n_faces);
 }
 
 extern "C" int d3d_mesh_sample_count(const float* vertices, long long n_vertices, const int* faces, long long n_faces, double spacing,
                                      void* scratch, size_t scratch_bytes, int* counts, int* offsets, long long* totals,
                                      d3d_stream_t stream) {
-    D3D_REQUIRE(ms_count_ok(n_vertices), "n_vertices=%lld (0 .. 2^31 - 1)", n_vertices);
-    D3D_REQUIRE(ms_count_ok(n_faces), "n_faces=%lld (0 .. 2^31 - 1)", n_faces);
+    D3D_REQUIRE(count_ok(n_vertices), "n_vertices=%lld (0 .. 2^31 - 1)", n_vertices);
+    D3D_REQUIRE(count_ok(n_faces), "n_faces=%lld (0 .. 2^31 - 1)", n_faces);
     D3D_REQUIRE(std::isfinite(spacing) && spacing > 0.0, "spacing %g must be finite and > 0", spacing);
     D3D_REQUIRE(scratch && offsets && totals, "null pointer (scratch, offsets, totals)");
     D3D_REQUIRE((faces && counts) || n_faces == 0, "null pointer (faces, counts) with %lld faces", n_faces);
@@ -275,9 +274,9 @@ extern "C" int d3d_mesh_sample_count(const float* vertices, long long n_vertices
 
 extern "C" int d3d_mesh_sample_emit(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* offsets,
                                     long long n_samples, float* xyz, int* face, d3d_stream_t stream) {
-    D3D_REQUIRE(ms_count_ok(n_vertices), "n_vertices=%lld (0 .. 2^31 - 1)", n_vertices);
-    D3D_REQUIRE(ms_count_ok(n_faces), "n_faces=%lld (0 .. 2^31 - 1)", n_faces);
-    D3D_REQUIRE(ms_count_ok(n_samples), "n_samples=%lld (0 .. 2^31 - 1)", n_samples);
+    D3D_REQUIRE(count_ok(n_vertices), "n_vertices=%lld (0 .. 2^31 - 1)", n_vertices);
+    D3D_REQUIRE(count_ok(n_faces), "n_faces=%lld (0 .. 2^31 - 1)", n_faces);
+    D3D_REQUIRE(count_ok(n_samples), "n_samples=%lld (0 .. 2^31 - 1)", n_samples);
     D3D_REQUIRE(n_faces > 0 || n_samples == 0, "n_samples=%lld with no face", n_samples);
     D3D_REQUIRE(offsets, "null pointer (offsets)");
     D3D_REQUIRE(faces || n_faces == 0, "null pointer (faces) with %lld faces", n_faces);
@@ -295,8 +294,8 @@ extern "C" int d3d_mesh_sample_emit(const float* vertices, long long n_vertices,
 
 extern "C" int d3d_mesh_sample_face_error(const int* e, const int* face, long long n_samples, long long n_faces, long long* sum, int* keyed,
                                           int* worst, d3d_stream_t stream) {
-    D3D_REQUIRE(ms_count_ok(n_samples), "n_samples=%lld (0 .. 2^31 - 1)", n_samples);
-    D3D_REQUIRE(ms_count_ok(n_faces), "n_faces=%lld (0 .. 2^31 - 1)", n_faces);
+    D3D_REQUIRE(count_ok(n_samples), "n_samples=%lld (0 .. 2^31 - 1)", n_samples);
+    D3D_REQUIRE(count_ok(n_faces), "n_faces=%lld (0 .. 2^31 - 1)", n_faces);
     D3D_REQUIRE((e && face) || n_samples == 0, "null pointer (e, face) with %lld samples", n_samples);
     D3D_REQUIRE((sum && keyed && worst) || n_faces == 0, "null pointer (sum, keyed, worst) with %lld faces", n_faces);
     const size_t S = (size_t)n_samples, m = (size_t)n_faces;

@@ -21,6 +21,7 @@
 // finalize: key -> rgba and height.
 #include <cmath>
 
+#include "cloud_search.h"
 #include "common.h"
 #include "dsm_tri.h"
 #include "geom_shared.h"
@@ -194,11 +195,6 @@ static bool om_dims_ok(long long n, int W, int H) {
     return n >= 0 && n < (1ll << 31) && W >= 1 && H >= 1 && (long long)W * H < (1ll << 31);
 }
 
-static bool om_apart(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 + na <= b0 || b0 + nb <= a0;
-}
-
 }  // namespace d3d
 
 using namespace d3d;
@@ -230,9 +226,8 @@ extern "C" int d3d_ortho_from_mesh(const float* vertices, long long n_vertices, 
     const long long cells = (long long)W * H;
     const OmScratch L = om_layout(n_faces, cells);
     D3D_REQUIRE(scratch_bytes >= L.total, "scratch of %zu bytes, %zu needed (d3d_ortho_mesh_scratch_bytes)", scratch_bytes, L.total);
-    D3D_REQUIRE(om_apart(height, (size_t)cells * 4, scratch, scratch_bytes) && om_apart(rgba, (size_t)cells * 4, scratch, scratch_bytes) &&
-                    om_apart(rgba, (size_t)cells * 4, height, (size_t)cells * 4),
-                "rgba, height and scratch must not alias");
+    const SearchRange R[3] = {{rgba, (size_t)cells * 4}, {height, (size_t)cells * 4}, {scratch, scratch_bytes}};
+    D3D_REQUIRE(search_apart(R, 3), "rgba, height and scratch must not alias");
     // page_row is device memory: the host cannot read it here.  The kernels treat a page whose rows are not increasing as
     // untextured; ortho_mesh.mesh_to_ortho refuses such an array before the call.
     const int nf = (int)n_faces, nc = (int)cells;

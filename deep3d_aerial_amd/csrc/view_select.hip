@@ -207,8 +207,6 @@ __global__ __launch_bounds__(VS_BLOCK) void view_select_rows_kernel(const long l
     }
 }
 
-static bool vs_count_ok(long long n) { return n >= 0 && n < (1ll << 31); }
-
 static size_t vs_scratch(long long n_ref, int n_img, int rows, long long lds_images) {
     if ((long long)rows * n_img <= lds_images) return 256;   // the LDS path: no row in device memory
     const long long batch = n_ref < VS_BATCH ? (n_ref > 0 ? n_ref : 1) : VS_BATCH;
@@ -238,14 +236,14 @@ using namespace d3d;
 extern "C" int d3d_view_select_lds_images(void) { return VS_LDS_IMAGES; }
 
 extern "C" size_t d3d_view_select_scratch_bytes(long long n_ref, int n_img, int mode, long long lds_images) {
-    if (!vs_count_ok(n_ref) || n_img < 0 || (mode != 0 && mode != 1) || lds_images < 0 || lds_images > VS_LDS_IMAGES) return 0;
+    if (!count_ok(n_ref) || n_img < 0 || (mode != 0 && mode != 1) || lds_images < 0 || lds_images > VS_LDS_IMAGES) return 0;
     return vs_scratch(n_ref, n_img, mode ? 2 : 1, lds_images);
 }
 
 extern "C" int d3d_view_select_blocks(const double* xyz, const long long* trk_offset, const int* trk_image, long long n_pts, long long n_trk,
                                       long long p_first, int n_img, const double* blocks, int n_blocks, unsigned char* mask,
                                       d3d_stream_t stream) {
-    D3D_REQUIRE(vs_count_ok(n_pts) && vs_count_ok(n_trk), "n_pts=%lld n_trk=%lld (0 .. 2^31 - 1)", n_pts, n_trk);
+    D3D_REQUIRE(count_ok(n_pts) && count_ok(n_trk), "n_pts=%lld n_trk=%lld (0 .. 2^31 - 1)", n_pts, n_trk);
     D3D_REQUIRE(p_first >= 0 && p_first <= n_pts, "p_first=%lld with %lld points", p_first, n_pts);
     D3D_REQUIRE(n_img >= 0 && n_blocks >= 0 && n_blocks <= D3D_VIEW_SELECT_MAX_BLOCKS, "n_img=%d n_blocks=%d (at most %d blocks)", n_img,
                 n_blocks, D3D_VIEW_SELECT_MAX_BLOCKS);
@@ -276,7 +274,7 @@ extern "C" int d3d_view_select_rows(const long long* img_offset, const int* obs_
                                     int n_bins, long long lds_images, void* scratch, size_t scratch_bytes, const long long* seg_offset,
                                     long long n_seg, int* seen, unsigned* maxv, int* n_src, int* src, unsigned* score, unsigned* count,
                                     d3d_stream_t stream) {
-    D3D_REQUIRE(vs_count_ok(n_obs) && vs_count_ok(n_pts) && vs_count_ok(n_trk) && vs_count_ok(n_ref) && vs_count_ok(n_seg),
+    D3D_REQUIRE(count_ok(n_obs) && count_ok(n_pts) && count_ok(n_trk) && count_ok(n_ref) && count_ok(n_seg),
                 "n_obs=%lld n_pts=%lld n_trk=%lld n_ref=%lld n_seg=%lld (0 .. 2^31 - 1)", n_obs, n_pts, n_trk, n_ref, n_seg);
     D3D_REQUIRE(n_img >= 1, "n_img=%d (at least 1)", n_img);
     D3D_REQUIRE(mode == 0 || mode == 1, "mode=%d (0 points, 1 angle)", mode);

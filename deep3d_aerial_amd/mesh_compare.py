@@ -55,7 +55,6 @@ else, and the --out_* files carry the moved coordinates.  The mesh has no regist
 """
 import argparse
 import json
-import math
 import os
 
 import numpy as np
@@ -69,7 +68,7 @@ MAX_SAMPLES = (1 << 31) - 1
 
 
 def _spacing(spacing):
-    if isinstance(spacing, bool) or not isinstance(spacing, (int, float, np.integer, np.floating)) or not (math.isfinite(spacing) and spacing > 0):
+    if not _geom.is_real(spacing, above=0):
         raise ValueError("spacing must be finite and > 0 (got %r)" % (spacing,))
     return float(spacing)
 
@@ -80,7 +79,7 @@ def sample(vertices, faces, spacing, max_samples=MAX_SAMPLES):
     max_samples samples are a ValueError that names the spacing and the numbers, raised before xyz is allocated or a sample is
     emitted.  CPU tensors are refused."""
     s = _spacing(spacing)
-    if isinstance(max_samples, bool) or not isinstance(max_samples, (int, np.integer)) or not 0 <= max_samples <= MAX_SAMPLES:
+    if not _geom.is_int(max_samples, 0, MAX_SAMPLES):
         raise ValueError("max_samples must be an integer in 0 .. 2^31 - 1 (got %r)" % (max_samples,))
     vertices, faces, n, m = _geom.mesh_arrays(vertices, faces, 1, "sampled")
     dev = vertices.device
@@ -115,7 +114,7 @@ def face_error(e, face, n_faces):
         raise TypeError("e and face must be tensors")
     if e.dtype != torch.int32 or face.dtype != torch.int32 or e.dim() != 1 or face.shape != e.shape:
         raise ValueError("e and face must be [S] int32 (got %s %s, %s %s)" % (tuple(e.shape), e.dtype, tuple(face.shape), face.dtype))
-    if isinstance(n_faces, bool) or not isinstance(n_faces, (int, np.integer)) or not 0 <= n_faces < 1 << 31:
+    if not _geom.is_int(n_faces, 0, (1 << 31) - 1):
         raise ValueError("n_faces must be an integer in 0 .. 2^31 - 1 (got %r)" % (n_faces,))
     if e.device.type != "cuda" or face.device != e.device:
         raise RuntimeError("the face error is summed on the GPU (no CPU fallback); got %s and %s" % (e.device, face.device))
@@ -138,15 +137,15 @@ def compare(vertices, faces, reference_xyz, border, max_dist, thresholds, spacin
     "mesh": {"faces", "sampled_faces", "samples", "spacing"}; per direction the device tensors of cloud_compare.nearest(), and
     the error per face.  The host reads the sampling's totals, then the two histograms and the number of sampled faces in one
     read."""
-    taus = cloud_compare._thresholds(thresholds, cloud_compare._cap(max_dist))
+    taus = cloud_compare.check_thresholds(thresholds, cloud_compare.check_max_dist(max_dist))
     s = _spacing(spacing)
     try:
         grid = cloud.CloudGrid(border, max_dist)
     except ValueError as e:
         raise ValueError("compare grid (border, max_dist as the voxel): %s" % e)
-    cloud_compare._points(reference_xyz, "reference_xyz")
+    cloud.points(reference_xyz, "reference_xyz")
     if isinstance(vertices, torch.Tensor) and vertices.is_cuda:
-        cloud_compare._on_gpu(reference_xyz, "reference_xyz")
+        cloud.on_gpu(reference_xyz, "reference_xyz", "the mesh is compared")
     xyz, face, offsets = sample(vertices, faces, s)
     m = int(offsets.shape[0]) - 1
     pa, pb = cloud_compare.prepare(xyz, grid), cloud_compare.prepare(reference_xyz, grid)
@@ -169,16 +168,12 @@ _FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,)), ("red", "u1"), ("green"
 _SAMPLE_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("face", "<i4")])
 
 
-def _host(t):
-    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-
-
 def error_mesh_bytes(vertices, faces, sum, keyed):
     """The bytes of an error mesh: a binary little-endian PLY of vertices [n,3] fp32 and faces [m,3] int32 with red green blue
     uchar on the face element (MeshLab reads face colours): E = sum // keyed of the face's keyed samples coloured by
     cloud_compare.error_cloud_bytes' formula, red = min(255, E >> 1), green = min(255, (1024 - E) >> 1), blue = 0; a face with no
     keyed sample is grey (128, 128, 128).  Host arrays or tensors."""
-    v, f, total, keyed = _host(vertices), _host(faces), _host(sum), _host(keyed)
+    v, f, total, keyed = _geom.host(vertices), _geom.host(faces), _geom.host(sum), _geom.host(keyed)
     n, m = int(v.shape[0]), int(f.shape[0])
     if v.dtype != np.float32 or v.shape != (n, 3) or f.dtype != np.int32 or f.shape != (m, 3):
         raise ValueError("vertices must be [n,3] float32 and faces [m,3] int32 (got %s %s, %s %s)" % (v.shape, v.dtype, f.shape, f.dtype))
@@ -202,7 +197,7 @@ def error_mesh_bytes(vertices, faces, sum, keyed):
 
 def samples_bytes(xyz, face):
     """The bytes of the samples: a binary little-endian PLY with x y z float and face int per sample, in sample order."""
-    xyz, face = _host(xyz), _host(face)
+    xyz, face = _geom.host(xyz), _geom.host(face)
     n = int(xyz.shape[0])
     if xyz.dtype != np.float32 or xyz.shape != (n, 3) or face.dtype != np.int32 or face.shape != (n,):
         raise ValueError("xyz must be [n,3] float32 and face [n] int32 (got %s %s, %s %s)" % (xyz.shape, xyz.dtype, face.shape, face.dtype))
@@ -210,9 +205,7 @@ def samples_bytes(xyz, face):
     for k, a in enumerate("xyz"):
         rec[a] = xyz[:, k]
     rec["face"] = face
-    head = ["ply", "format binary_little_endian 1.0", "comment mesh samples (deep3d_aerial_amd.mesh_compare)", "element vertex %d" % n,
-            "property float x", "property float y", "property float z", "property int face", "end_header"]
-    return ("\n".join(head) + "\n").encode("ascii") + rec.tobytes()
+    return _geom.record_ply_bytes("mesh samples (deep3d_aerial_amd.mesh_compare)", rec)
 
 
 # ----------------------------------------------------------------------------------------
@@ -224,7 +217,7 @@ def main(argv=None):
     ap.add_argument("--reference", default=None, help="the reference cloud (.ply, binary little-endian)")
     ap.add_argument("--border", type=cloud.parse_border6, default=None, help="Xmin,Xmax,Ymin,Ymax,Zmin,Zmax (world units)")
     ap.add_argument("--max_dist", type=float, default=None, help="the cap of the distances (world units); further points count the cap")
-    ap.add_argument("--threshold", type=cloud_compare._parse_thresholds, default=None, help="T[,T...]: the distances under which a point counts")
+    ap.add_argument("--threshold", type=cloud_compare.parse_thresholds, default=None, help="T[,T...]: the distances under which a point counts")
     ap.add_argument("--spacing", type=float, default=None, help="the spacing of the samples on the surface (world units)")
     ap.add_argument("--json", default=None, help="write the result here too (.json)")
     ap.add_argument("--out_samples", default=None, help="the samples: x y z and their face (.ply)")
@@ -251,7 +244,7 @@ def main(argv=None):
         ap.error("an output would overwrite an input")
     cloud_register.check_transform_argument(ap, a.transform, {os.path.abspath(str(a.mesh)), os.path.abspath(str(a.reference))}, outs)
     try:
-        cloud_compare._thresholds(a.threshold, cloud_compare._cap(a.max_dist))
+        cloud_compare.check_thresholds(a.threshold, cloud_compare.check_max_dist(a.max_dist))
         cloud.CloudGrid(a.border, a.max_dist)
         _spacing(a.spacing)
     except ValueError as e:
@@ -270,15 +263,15 @@ def main(argv=None):
     line = json.dumps(result)
     xyz, face, ea, _ = found["samples"]
     if a.out_samples is not None:
-        cloud_compare._write(a.out_samples, samples_bytes(xyz, face))
+        _geom.write_bytes(a.out_samples, samples_bytes(xyz, face))
     if a.out_accuracy is not None:
-        cloud_compare._write(a.out_accuracy, cloud_compare.error_cloud_bytes(xyz, ea))
+        _geom.write_bytes(a.out_accuracy, cloud_compare.error_cloud_bytes(xyz, ea))
     if a.out_completeness is not None:
-        cloud_compare._write(a.out_completeness, cloud_compare.error_cloud_bytes(xb, found["reference"][0]))
+        _geom.write_bytes(a.out_completeness, cloud_compare.error_cloud_bytes(xb, found["reference"][0]))
     if a.out_mesh is not None:
-        cloud_compare._write(a.out_mesh, error_mesh_bytes(v, f, found["faces"][0], found["faces"][1]))
+        _geom.write_bytes(a.out_mesh, error_mesh_bytes(v, f, found["faces"][0], found["faces"][1]))
     if a.json is not None:
-        cloud_compare._write(a.json, (line + "\n").encode("ascii"))
+        _geom.write_bytes(a.json, (line + "\n").encode("ascii"))
     print(line)
     return result
 

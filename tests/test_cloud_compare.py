@@ -7,6 +7,7 @@ its argument checks, and the operator's refusals."""
 import ctypes
 import itertools
 import math
+import os
 import re
 
 import numpy as np
@@ -513,9 +514,48 @@ def test_the_kernels_use_integer_atomic_add_only_and_the_build_lists_the_source(
     # one on the unsigned LDS histogram, one on the unsigned 64-bit histogram in memory
     assert "__shared__ unsigned bins[CC_BINS]" in hip and "atomicAdd(&bins[" in hip and "atomicAdd(hist + b, (unsigned long long)v)" in hip
     assert re.search(r"unsigned long long\* __restrict__ hist\)", hip) and '#include "cloud_search.h"' in hip
-    # the search helpers have one statement: the outliers include them
-    outl = strip(open(_lib.CSRC + "/cloud_outliers.hip").read())
-    assert '#include "cloud_search.h"' in outl and "keys[mid] < k" not in outl and "keys[mid] < k" not in hip
+    # the search helpers have one statement, in cloud_search.h: the outliers and the merge include them, and no .hip file restates
+    # the lower bound, the overlap check, the tile's LDS arrays, the occupancy query or the private names of the shared constants
+    search = strip(open(_lib.CSRC + "/cloud_search.h").read())
+    assert search.count("keys[mid] < k") == 1 and "int bound[CLOUD_BOUNDS][SEARCH_BLOCK]" in search and "int edge[2][CLOUD_BOUNDS]" in search
+    assert search.count("hipOccupancyMaxActiveBlocksPerMultiprocessor") == 1 and "(cloud.hip)" not in search
+    sources = {name: strip(open(_lib.CSRC + "/" + name).read()) for name in sorted(os.listdir(_lib.CSRC)) if name.endswith((".hip", ".h"))}
+    for name, text in sources.items():
+        if name.endswith(".hip"):
+            for gone in ("keys[mid] < k", "struct CloudRange", "cloud_apart", "om_apart", "struct SearchRange", "bool search_apart"):
+                assert gone not in text, (name, gone)
+            assert not re.search(r"\bbound\[|\bedge\[\w+\]\[|hipOccupancyMaxActiveBlocksPerMultiprocessor", text), name
+    for name in ("cloud.hip", "cloud_outliers.hip", "cloud_compare.hip"):
+        assert '#include "cloud_search.h"' in sources[name]
+        assert not re.search(r"\bC[OL]_(AXIS_MAX|DROPPED|CAP|BOUNDS|AHEAD)\b|\bCO_(BLOCK|WAVES)\b|\bCC_(AHEAD|BLOCK|WAVES)\b", sources[name]), name
+    for name in ("cloud_outliers.hip", "cloud_compare.hip"):
+        assert all(call in sources[name] for call in ("search_tile(", "search_walk(", "search_gather(")), name
+    assert "cloud_lower(" in sources["cloud.hip"] and "search_apart(" in sources["cloud.hip"] and "search_apart(" in sources["ortho_mesh.hip"]
+    # one count check under csrc/, one gather kernel in the library
+    assert sum(len(re.findall(r"count_ok\(long long", text)) for text in sources.values()) == 1
+    assert sum(len(re.findall(r"__global__[^;{]*\bcloud\w*_gather_kernel\(", text)) for text in sources.values()) == 1
     make = open(_lib.CSRC + "/Makefile").read()
     assert re.search(r"^SRCS :=.*\bcloud_compare\.hip\b", make, re.M) and re.search(r"^HDRS :=.*\bcloud_search\.h\b", make, re.M)
     assert "-ffp-contract=off" in make
+
+
+def test_the_package_states_the_clouds_checks_and_keys_once():
+    pkg = os.path.dirname(cloud.__file__)
+    text = {name: open(os.path.join(pkg, name)).read() for name in sorted(os.listdir(pkg)) if name.endswith(".py")}
+    # no module reaches into cloud_compare for an underscore name, by import or by attribute
+    for name, src in text.items():
+        assert not re.search(r"from \.cloud_compare import[^\n]*\b_\w+|\bcloud_compare\._\w+", src), name
+    # d3d_cloud_keys is called from one place, and the sort of its keys stands in cloud.py alone among the stages on the grid
+    assert [name for name, src in text.items() for _ in re.findall(r"d3d_cloud_keys\(", src)] == ["cloud.py"]
+    for name in ("cloud_outliers.py", "cloud_compare.py", "cloud_register.py", "mesh_compare.py"):
+        assert "torch.sort(" not in text[name], name
+    assert "cloud.sorted_keys(" in text["cloud_outliers.py"] and "cloud.sorted_keys(" in text["cloud_compare.py"]
+    # the spelled-out number checks, the hand-typed PLY headers and the private writers are gone from the package
+    for name, src in text.items():
+        assert not re.search(r"isinstance\(\w+, bool\) or not isinstance", src) or name == "_geom.py", name
+        if name in ("cloud.py", "cloud_outliers.py", "cloud_compare.py", "cloud_register.py"):
+            assert "format binary_little_endian 1.0\"," not in src and "def _write(" not in src and "host = lambda" not in src, name
+    assert text["_geom.py"].count("isinstance(x, bool) or not isinstance") == 2
+    # the four vertex-only writers go through the one in _geom
+    for name, n in (("cloud.py", 1), ("cloud_compare.py", 1), ("cloud_register.py", 1), ("mesh_compare.py", 1)):
+        assert text[name].count("_geom.record_ply_bytes(") == n, name
