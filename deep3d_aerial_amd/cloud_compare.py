@@ -225,10 +225,10 @@ _PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short
                 "float64": "<f8"}
 
 
-def read_xyz_ply(path):
-    """xyz [n,3] float32 (a host array) of the vertices of a binary little-endian PLY.  The vertex element must be the first one;
-    its scalar properties may be of any PLY scalar type; x, y and z must be float or double (double is rounded to fp32).  Other
-    properties and later elements (faces) are skipped.  ASCII and big-endian files are refused by name."""
+def read_vertex_ply(path):
+    """The vertices of a binary little-endian PLY as a structured host array, one field per scalar property, named and typed as
+    the file has them.  The vertex element must be the first one; its scalar properties may be of any PLY scalar type; x, y and z
+    must be float or double.  Later elements (faces) are skipped.  ASCII and big-endian files are refused by name."""
     with open(str(path), "rb") as f:
         data = f.read()
     end = data.find(b"end_header\n")
@@ -272,9 +272,24 @@ def read_xyz_ply(path):
     body = end + len(b"end_header\n")
     if len(data) - body < m * dt.itemsize:
         raise ValueError("%s: %d bytes after the header, %d vertices need %d" % (path, len(data) - body, m, m * dt.itemsize))
-    rec = np.frombuffer(data, dt, count=m, offset=body)
+    return np.frombuffer(data, dt, count=m, offset=body)
+
+
+def vertex_columns(rec, names, dtype=np.float32):
+    """The properties `names` of read_vertex_ply's records as one contiguous [n, len(names)] array of dtype."""
     with np.errstate(over="ignore"):
-        return np.ascontiguousarray(np.stack([rec[a].astype(np.float32) for a in "xyz"], 1)) if m else np.zeros((0, 3), np.float32)
+        return np.ascontiguousarray(np.stack([rec[a].astype(dtype) for a in names], 1)) if len(rec) else np.zeros((0, len(names)), dtype)
+
+
+def read_xyz_ply(path, normals=False):
+    """xyz [n,3] float32 (a host array) of the vertices of a PLY that read_vertex_ply reads (double is rounded to fp32); other
+    properties are skipped.  With normals: (xyz, normal), normal [n,3] float32 from nx ny nz where the file has all three as float
+    or double, else None."""
+    rec = read_vertex_ply(path)
+    if not normals:
+        return vertex_columns(rec, "xyz")
+    has = all(a in rec.dtype.names and rec.dtype[a].str in ("<f4", "<f8") for a in ("nx", "ny", "nz"))
+    return vertex_columns(rec, "xyz"), vertex_columns(rec, ("nx", "ny", "nz")) if has else None
 
 
 _ERROR_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("e", "<i4")])

@@ -42,7 +42,27 @@ is this project's own; it does not claim to match any tool.
   pairs = N, rms = sqrt(sums[26] / N) / 1024 * h, moved, and on a stage's last entry reason --; P transformed by the final T, on
   the device.
 
-Out of scope: scale (similarity transforms); point-to-plane with reference normals; subsampling; weights; robust kernels beyond the
+* Point-to-plane (metric="plane").  Against a discrete sample of a surface the sums above pull every point to
+  the nearest SAMPLE, and the residual stops at a fraction of the reference's spacing.  With the reference's normals -- given,
+  or estimated once by cloud_normals.estimate(Q, border, normal_radius, z_down) -- the step minimises the distance to the
+  reference's tangent planes instead.  The matching and the loop are the ones above; the sums and the solve are these.
+  - Sums (d3d_cloud_register_plane_sums).  a, b are the bins above; c_c = 512 n_c is the grid's centre in the same units;
+    m_c = llrint((double)normal_c * 1024.0) of the matched reference point.  A pair counts when it counts above and its normal is
+    finite with every |normal_c| <= 1 and m != (0, 0, 0).  Per counted pair u = a - c, r = (a - b) . m, w = u x m and
+    g = (w_x, w_y, w_z, m_x, m_y, m_z): the residual linearised under a rotation omega about c and a translation tau (in bins)
+    is r + g . (omega, tau).  sums is int64 [87], zeroed by the call: [0] N, [1] sum e, [2] sum e^2, then 28 products P_k -- the 21
+    g_i g_j, i <= j, row-major; the 6 g_i r; r r --, each a 128-bit two's-complement value summed in three slots 3 + 3k .. 5 + 3k:
+    the low 32 bits of its low word, the high 32 bits of its low word (both unsigned) and its signed high word: the hi / lo split
+    above with one more limb, for the same reason.  |w| < 2^42, |r| < 2^43, |P| < 2^87, and 2^31 - 1 pairs overflow no slot.
+    Integer atomicAdd only: the same bits for any order of P.
+  - Solve (solve_plane, host, fp64).  H = sum g g^T (6 x 6) and v = sum g r recombined exactly in Python integers.  With
+    D = sqrt(diag H), Hn = H / (D D^T) and vn = v / D; an unknown whose diagonal is zero is dropped.  lam, Q = numpy.linalg.eigh(Hn);
+    the directions with lam < min_eig_ratio (1e-6) times the largest are dropped: the sums are exact, so only the geometry limits
+    the conditioning, and a flat scene leaves its in-plane motion where it is.  xi = -D^-1 Q diag(1 / lam) Q^T vn = (omega, tau).
+    dT rotates by the exact Rodrigues matrix of omega about the world point of c and translates by tau h / 1024.  N < 6 or no
+    direction kept is "degenerate".  The log entries gain plane_rms = sqrt(sum r r / N) / 1024^2 h and rank.
+
+Out of scope: scale (similarity transforms); subsampling; weights; robust kernels beyond the
 pair cap; a global, feature-based initial alignment; the shift of large coordinates before the fp32 rounding.  Ground truth is not
 an input of a reconstruction run: pipeline.predict_and_fuse and predict have no key or flag for this.  mesh_compare has no
 registration of its own: register the mesh's samples (mesh_compare --out_samples) here, then pass the transform to it.
@@ -51,7 +71,7 @@ The transform and the sums are HIP (csrc/cloud_register.hip); the keys, the sort
 
     python -m deep3d_aerial_amd.cloud_register --cloud A.ply --reference B.ply --border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax
         --max_dist H1[,H2...] [--max_pair_dist D] [--iterations K] [--tolerance T] [--init T0.txt] [--out_transform T.txt]
-        [--out A_registered.ply] [--json LOG.json]
+        [--out A_registered.ply] [--json LOG.json] [--metric point|plane] [--normal_radius R] [--z_down]
 """
 import argparse
 import json
@@ -66,6 +86,8 @@ from ._geom import ptr as _ptr, stream as _stream
 
 CAP = cloud_compare.CAP
 SUMS = 27
+PLANE_SUMS = 87
+METRICS = ("point", "plane")
 
 
 _VERB = "the clouds are registered"
@@ -119,12 +141,8 @@ def _e_max(e_max):
     return int(e_max)
 
 
-def pair_sums(moved_xyz, e, idx, reference_xyz, grid, e_max=CAP):
-    """moved_xyz [n,3] fp32, e [n] int32 and idx [n] int32 of cloud_compare.nearest(moved_xyz, reference_xyz, grid), reference_xyz
-    [m,3] fp32, all on one GPU -> sums [27] int64 of the module's docstring: a device tensor queued on the caller's stream; the host
-    reads nothing.  CPU tensors are refused."""
-    cloud.check_grid(grid)
-    e_max = _e_max(e_max)
+def _pairs(moved_xyz, e, idx, reference_xyz, reference_normals=None):
+    """The arguments of the two sums checked and contiguous on one GPU: (moved_xyz, e, idx, reference_xyz, reference_normals)."""
     moved_xyz, reference_xyz = cloud.points(moved_xyz, "moved_xyz"), cloud.points(reference_xyz, "reference_xyz")
     n, m = int(moved_xyz.shape[0]), int(reference_xyz.shape[0])
     for t, name in ((e, "e"), (idx, "idx")):
@@ -132,12 +150,26 @@ def pair_sums(moved_xyz, e, idx, reference_xyz, grid, e_max=CAP):
             raise TypeError("%s must be a torch.Tensor" % name)
         if t.dtype != torch.int32 or tuple(t.shape) != (n,):
             raise ValueError("%s must be a [%d] int32 tensor (got %s %s)" % (name, n, t.dtype, tuple(t.shape)))
+    if reference_normals is not None and int(cloud.points(reference_normals, "reference_normals").shape[0]) != m:
+        raise ValueError("reference_xyz has %d points, reference_normals %d" % (m, reference_normals.shape[0]))
     moved_xyz, reference_xyz = cloud.on_gpu(moved_xyz, "moved_xyz", _VERB), cloud.on_gpu(reference_xyz, "reference_xyz", _VERB)
+    if reference_normals is not None:
+        reference_normals = cloud.on_gpu(reference_normals, "reference_normals", _VERB)
     dev = moved_xyz.device
-    for t, name in ((e, "e"), (idx, "idx"), (reference_xyz, "reference_xyz")):
-        if t.device != dev:
+    for t, name in ((e, "e"), (idx, "idx"), (reference_xyz, "reference_xyz"), (reference_normals, "reference_normals")):
+        if t is not None and t.device != dev:
             raise RuntimeError("%s is on %s and moved_xyz on %s: the sums are taken on one GPU (no CPU fallback)" % (name, t.device, dev))
-    e, idx = e.contiguous(), idx.contiguous()
+    return moved_xyz, e.contiguous(), idx.contiguous(), reference_xyz, reference_normals
+
+
+def pair_sums(moved_xyz, e, idx, reference_xyz, grid, e_max=CAP):
+    """moved_xyz [n,3] fp32, e [n] int32 and idx [n] int32 of cloud_compare.nearest(moved_xyz, reference_xyz, grid), reference_xyz
+    [m,3] fp32, all on one GPU -> sums [27] int64 of the module's docstring: a device tensor queued on the caller's stream; the host
+    reads nothing.  CPU tensors are refused."""
+    cloud.check_grid(grid)
+    e_max = _e_max(e_max)
+    moved_xyz, e, idx, reference_xyz, _ = _pairs(moved_xyz, e, idx, reference_xyz)
+    n, m, dev = int(moved_xyz.shape[0]), int(reference_xyz.shape[0]), moved_xyz.device
     sums = torch.empty((SUMS,), dtype=torch.int64, device=dev)   # zeroed by the call
     pn = (lambda t: _ptr(t) if n else None)
     b = grid.border
@@ -146,15 +178,34 @@ def pair_sums(moved_xyz, e, idx, reference_xyz, grid, e_max=CAP):
     return sums
 
 
+def plane_sums(moved_xyz, e, idx, reference_xyz, reference_normals, grid, e_max=CAP):
+    """pair_sums' inputs and reference_normals [m,3] fp32 -> sums [87] int64 of the point-to-plane metric (the module's docstring):
+    a device tensor queued on the caller's stream; the host reads nothing.  CPU tensors are refused."""
+    cloud.check_grid(grid)
+    e_max = _e_max(e_max)
+    if reference_normals is None:
+        raise ValueError("the plane sums need reference_normals")
+    moved_xyz, e, idx, reference_xyz, reference_normals = _pairs(moved_xyz, e, idx, reference_xyz, reference_normals)
+    n, m, dev = int(moved_xyz.shape[0]), int(reference_xyz.shape[0]), moved_xyz.device
+    sums = torch.empty((PLANE_SUMS,), dtype=torch.int64, device=dev)   # zeroed by the call
+    pn, pm = (lambda t: _ptr(t) if n else None), (lambda t: _ptr(t) if m else None)
+    b = grid.border
+    _lib.check(_lib.load().d3d_cloud_register_plane_sums(pn(moved_xyz), pn(e), pn(idx), n, pm(reference_xyz), pm(reference_normals), m,
+                                                         grid.n[0], grid.n[1], grid.n[2], b[0], b[2], b[4], grid.voxel, e_max, _ptr(sums),
+                                                         _stream()), "d3d_cloud_register_plane_sums")
+    return sums
+
+
 # ----------------------------------------------------------------------------------------
 # the solve (host only)
 # ----------------------------------------------------------------------------------------
-def _sums(sums):
+def _sums(sums, count=None):
+    count = SUMS if count is None else count
     if isinstance(sums, torch.Tensor):
         sums = sums.tolist()
     s = [int(v) for v in sums]
-    if len(s) != SUMS:
-        raise ValueError("sums must hold %d integers (got %d)" % (SUMS, len(s)))
+    if len(s) != count:
+        raise ValueError("sums must hold %d integers (got %d)" % (count, len(s)))
     return s
 
 
@@ -186,6 +237,68 @@ def solve(sums, grid):
     dT = np.eye(4, dtype=np.float64)
     dT[:3, :3] = R
     dT[:3, 3] = mean_b - R @ mean_a
+    info["degenerate"] = False
+    return dT, info
+
+
+def plane_products(sums):
+    """The 28 products of the 87 plane sums recombined in Python integers, hi 2^64 + mid 2^32 + lo each:
+    (H, v, rr): H the 6 x 6 symmetric sum of g g^T, v the sum of g r (6), rr the sum of r r."""
+    s = _sums(sums, PLANE_SUMS)
+    P = [(s[5 + 3 * k] << 64) + (s[4 + 3 * k] << 32) + s[3 + 3 * k] for k in range(28)]
+    H = [[0] * 6 for _ in range(6)]
+    k = 0
+    for i in range(6):
+        for j in range(i, 6):
+            H[i][j] = H[j][i] = P[k]
+            k += 1
+    return H, P[21:27], P[27]
+
+
+def solve_plane(sums, grid, min_eig_ratio=1e-6):
+    """The point-to-plane step of the module's docstring from the 87 sums (a list, array or tensor) on `grid`.  Host only, no GPU
+    needed.  -> (dT, info): dT a 4 x 4 float64 array, or None when the pairs do not determine one; info = {"pairs": N, "rms":
+    sqrt(sums[2] / N) / 1024 * h, "plane_rms": sqrt(sum r r / N) / 1024^2 * h (both 0.0 for N = 0), "rank": the directions kept,
+    "degenerate": N < 6 or rank 0}."""
+    cloud.check_grid(grid)
+    if not (_geom.is_real(min_eig_ratio, above=0) and min_eig_ratio < 1):
+        raise ValueError("min_eig_ratio must lie in (0, 1) (got %r)" % (min_eig_ratio,))
+    s = _sums(sums, PLANE_SUMS)
+    H, v, rr = plane_products(s)
+    h, N = grid.voxel, s[0]
+    if N < 0 or rr < 0:
+        raise ValueError("plane sums of %d pairs, sum r r = %d" % (N, rr))
+    info = {"pairs": N, "rms": math.sqrt(s[2] / N) / CAP * h if N > 0 else 0.0,
+            "plane_rms": math.sqrt(rr / N) / (CAP * CAP) * h if N > 0 else 0.0, "rank": 0, "degenerate": True}
+    if N < 6:
+        return None, info
+    D = [math.sqrt(H[i][i]) for i in range(6)]   # (a sum of squares: >= 0)
+    live = [i for i in range(6) if D[i] > 0.0]   # a zero diagonal: no pair constrains that unknown
+    if not live:
+        return None, info
+    Hn = np.array([[H[i][j] / (D[i] * D[j]) for j in live] for i in live], dtype=np.float64)
+    vn = np.array([v[i] / D[i] for i in live], dtype=np.float64)
+    lam, Q = np.linalg.eigh(Hn)
+    keep = lam >= float(min_eig_ratio) * lam[-1]
+    keep &= lam > 0.0
+    info["rank"] = int(keep.sum())
+    if info["rank"] == 0:
+        return None, info
+    Qk = Q[:, keep]
+    xn = -(Qk @ ((Qk.T @ vn) / lam[keep]))
+    xi = np.zeros(6, dtype=np.float64)
+    xi[live] = xn / np.array([D[i] for i in live], dtype=np.float64)
+    omega, tau = xi[:3], xi[3:]   # radians about c, bins
+    theta = float(np.sqrt(omega @ omega))
+    K = np.array([[0.0, -omega[2], omega[1]], [omega[2], 0.0, -omega[0]], [-omega[1], omega[0], 0.0]])
+    if theta > 0.0:   # Rodrigues: R = I + sin(theta) / theta K + (1 - cos(theta)) / theta^2 K K, 1 - cos as 2 sin^2 of the half
+        R = np.eye(3) + (math.sin(theta) / theta) * K + (2.0 * math.sin(0.5 * theta) ** 2 / (theta * theta)) * (K @ K)
+    else:
+        R = np.eye(3)
+    c = np.array([grid.border[2 * a] + 0.5 * grid.n[a] * h for a in range(3)], dtype=np.float64)   # the world point of c = 512 n
+    dT = np.eye(4, dtype=np.float64)
+    dT[:3, :3] = R
+    dT[:3, 3] = (c - R @ c) + tau * (h / CAP)
     info["degenerate"] = False
     return dT, info
 
@@ -235,24 +348,55 @@ def _plan(border, max_dists, max_iterations, tolerance, max_pair_dist):
     return stages
 
 
-def register(cloud_xyz, reference_xyz, border, max_dists, init=None, max_iterations=50, tolerance=None, max_pair_dist=None):
+def check_metric(metric, reference_normals=None, normal_radius=None, border=None):
+    """The metric's settings checked without GPU work: "point" takes neither normals nor a radius; "plane" needs exactly one."""
+    if metric not in METRICS:
+        raise ValueError("metric must be one of %s (got %r)" % (", ".join(METRICS), metric))
+    if metric == "point":
+        if reference_normals is not None or normal_radius is not None:
+            raise ValueError("reference_normals and normal_radius belong to metric=\"plane\"")
+        return
+    if (reference_normals is None) == (normal_radius is None):
+        raise ValueError("metric=\"plane\" needs reference_normals or a normal_radius, one of the two")
+    if normal_radius is not None:
+        try:
+            cloud.CloudGrid(border, normal_radius)
+        except ValueError as e:
+            raise ValueError("normals grid (border, normal_radius as the voxel): %s" % e)
+
+
+def register(cloud_xyz, reference_xyz, border, max_dists, init=None, max_iterations=50, tolerance=None, max_pair_dist=None,
+             metric="point", reference_normals=None, normal_radius=None, z_down=False):
     """(T, log, moved_xyz): the registration of the module's docstring of the cloud [n,3] fp32 to the reference [m,3] fp32 (device
     tensors on one GPU): T a 4 x 4 float64 numpy array, the log with one dict per iteration, and the cloud transformed by T (a
-    device tensor).  The host reads the 27 sums once per iteration.  CPU tensors are refused."""
+    device tensor).  The host reads the sums (27, or 87 with metric="plane") once per iteration.  metric="plane" takes the
+    reference's normals as reference_normals [m,3] fp32, or estimates them once with cloud_normals.estimate(reference_xyz, border,
+    normal_radius, z_down).  CPU tensors are refused."""
     stages = _plan(border, max_dists, max_iterations, tolerance, max_pair_dist)
+    check_metric(metric, reference_normals, normal_radius, border)
     T = _transform(np.eye(4) if init is None else init, "init")
     cloud_xyz, reference_xyz = _points(cloud_xyz, "cloud_xyz"), _points(reference_xyz, "reference_xyz")
     if cloud_xyz.device != reference_xyz.device:
         raise ValueError("cloud_xyz is on %s and reference_xyz on %s: both clouds must be on one GPU" % (cloud_xyz.device, reference_xyz.device))
+    plane = metric == "plane"
+    if plane and reference_normals is None:
+        from . import cloud_normals
+
+        reference_normals = cloud_normals.estimate(reference_xyz, border, normal_radius, z_down)[0]
     log = []
     for stage, (grid, e_max, tol) in enumerate(stages, 1):
         prepared = cloud_compare.prepare(reference_xyz, grid)
         for iteration in range(1, int(max_iterations) + 1):
             moved_xyz = apply(cloud_xyz, T)
             e, idx, _ = cloud_compare.nearest(moved_xyz, reference_xyz, grid, None, prepared)
-            sums = pair_sums(moved_xyz, e, idx, reference_xyz, grid, e_max).tolist()   # the one read
-            dT, info = solve(sums, grid)
+            if plane:
+                dT, info = solve_plane(plane_sums(moved_xyz, e, idx, reference_xyz, reference_normals, grid, e_max).tolist(), grid)   # the one read
+            else:
+                sums = pair_sums(moved_xyz, e, idx, reference_xyz, grid, e_max).tolist()   # the one read
+                dT, info = solve(sums, grid)
             entry = {"stage": stage, "cap": grid.voxel, "iteration": iteration, "pairs": info["pairs"], "rms": info["rms"], "moved": 0.0}
+            if plane:
+                entry["plane_rms"], entry["rank"] = info["plane_rms"], info["rank"]
             log.append(entry)
             if dT is None:
                 entry["reason"] = "degenerate"
@@ -343,6 +487,10 @@ def main(argv=None):
     ap.add_argument("--out_transform", default=None, help="write the transform here (.txt)")
     ap.add_argument("--out", default=None, help="write the registered cloud here (.ply)")
     ap.add_argument("--json", default=None, help="write the result here too (.json)")
+    ap.add_argument("--metric", choices=METRICS, default="point", help="point: to the nearest reference point; plane: to its tangent plane")
+    ap.add_argument("--normal_radius", type=float, default=None,
+                    help="plane: estimate the reference's normals at this radius (default: the normals the reference file has)")
+    ap.add_argument("--z_down", action="store_true", default=False, help="plane: orient the estimated normals towards -Z")
     a = ap.parse_args(argv)
     for flag in ("cloud", "reference", "border", "max_dist"):
         if getattr(a, flag) is None:
@@ -354,16 +502,26 @@ def main(argv=None):
     inputs = {os.path.abspath(str(p)) for p in (a.cloud, a.reference, a.init) if p is not None}
     if set(outs) & inputs:
         ap.error("an output would overwrite an input")
+    if a.metric == "point" and (a.normal_radius is not None or a.z_down):
+        ap.error("--normal_radius and --z_down belong to --metric plane")
     try:
         _plan(a.border, a.max_dist, a.iterations, a.tolerance, a.max_pair_dist)
+        if a.normal_radius is not None:
+            check_metric(a.metric, None, a.normal_radius, a.border)
     except ValueError as e:
         ap.error(str(e))
     if not torch.cuda.is_available():
         raise RuntimeError("the clouds are registered on the GPU (no CPU fallback)")
     init = read_transform(a.init) if a.init is not None else None
-    xa, xb = cloud_compare.read_xyz_ply(a.cloud), cloud_compare.read_xyz_ply(a.reference)
+    xa, (xb, nb) = cloud_compare.read_xyz_ply(a.cloud), cloud_compare.read_xyz_ply(a.reference, normals=True)
     da, db = torch.from_numpy(xa).cuda(), torch.from_numpy(xb).cuda()
-    T, log, moved = register(da, db, a.border, a.max_dist, init, a.iterations, a.tolerance, a.max_pair_dist)
+    normals = None
+    if a.metric == "plane" and a.normal_radius is None:
+        if nb is None:
+            raise ValueError("%s has no nx ny nz: --metric plane needs them or --normal_radius" % a.reference)
+        normals = torch.from_numpy(nb).cuda()
+    T, log, moved = register(da, db, a.border, a.max_dist, init, a.iterations, a.tolerance, a.max_pair_dist, a.metric, normals,
+                             a.normal_radius, a.z_down)
     result = {"transform": T.tolist(), "iterations": len(log), "stages": [e for e in log if "reason" in e], "log": log}
     line = json.dumps(result)
     if a.out_transform is not None:

@@ -1052,6 +1052,52 @@ int d3d_cloud_register_sums(const float* q_xyz, const int* e, const int* idx, lo
                             d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.34 -- normals of a point cloud from its own neighbourhoods, and the point-to-plane sums of the registration that
+ * use them.  The rules are this project's (deep3d_aerial_amd/cloud_normals.py, cloud_register.py); they do not claim to match any
+ * tool.
+ *   Normals.  Grid: the cloud's grid above with voxel = the radius h.  A point is keyed by d3d_cloud_keys; a point it drops is
+ *   unkeyed: count 0, normal (0, 0, 0), flatness -1, nobody's neighbour.
+ *   Per keyed point i the neighbours are the keyed points j, i itself included, of the 3 x 3 x 3 cells around i's cell with
+ *     d2 = (dx dx + dy dy) + dz dz < h h (strict) in fp64, dx = (double)x_i - (double)x_j, each operation rounded once.
+ *     Per neighbour and axis delta_c = llrint(((double)x_jc - (double)x_ic) / h * 1024.0), so |delta_c| <= 1024.
+ *     Ten integer sums, int64: k (the neighbours), S1[3] = sum delta, S2[6] = sum delta_r delta_c for rc = xx xy xz yy yz zz;
+ *     k < 2^31 and |S2| < 2^51, so nothing overflows and the sums are the same bits for any point order.
+ *     C_rc = (double)S2_rc - ((double)S1_r * (double)S1_c) / (double)k in fp64, each operation rounded once.
+ *     l0 <= l1 <= l2 and the unit eigenvector n of l0 by six cyclic Jacobi sweeps in fp64 (rotations (x, y), (x, z), (y, z) in
+ *     that order, a zero off-diagonal entry skipped): n is a function of the ten integers only.  n is flipped so that
+ *     n . up >= 0, up = (0, 0, 1), or (0, 0, -1) with z_down = 1; where n . up == 0 its first non-zero component is made positive.
+ *     normals [n,3] fp32 = n; count [n] int32 = k; flatness [n] int32 = llrint(1024 l0 / (l0 + l1 + l2)).
+ *     Degenerate -- k < 3, or l2 <= 0, or l1 <= 1e-12 l2 (collinear) --: normal (0, 0, 0), flatness -1, count k.
+ *   d3d_cloud_normals: after d3d_cloud_keys with voxel = radius and the caller's sort (sorted_keys [n], order [n] int64), writes
+ *     normals, count and flatness of every point in the order of xyz [n,3] fp32, and with sums_or_null not null the ten sums
+ *     [n,10] int64 (k, S1 x y z, S2 xx xy xz yy yz zz) too.  n_points = 0 launches nothing.  nx, ny, nz: the grid's n_a.
+ *     scratch: d3d_cloud_normals_scratch_bytes(n) bytes (0 for n outside 0 .. 2^31 - 1): the coordinates in key order.
+ *     No atomics.
+ *   Plane sums.  d3d_cloud_register_plane_sums: the inputs of d3d_cloud_register_sums, t_normals [n_target,3] fp32 (the normals
+ *     of t_xyz) and the grid's n_a.  a, b: the bins of d3d_cloud_register_sums; c_c = 512 n_c, the grid's centre in the same
+ *     units; m_c = llrint((double)normal_c * 1024.0) of the matched target.  Pair i counts when it counts there (0 <= idx_i <
+ *     n_target, e_i <= e_max) and its normal is finite with every |normal_c| <= 1 and m != (0, 0, 0).  Per counted pair
+ *     u = a - c, r = (a - b) . m, w = u x m, g = (w_x, w_y, w_z, m_x, m_y, m_z): the residual linearised under a rotation omega
+ *     about c and a translation tau (in bins) is r + g . (omega, tau).
+ *     sums int64 [87], zeroed by the call on the stream: [0] N, the counted pairs; [1] sum e; [2] sum e^2; then 28 products P_k
+ *     in this order: the 21 g_i g_j, i <= j, row-major; the 6 g_i r; r r.  Each is a 128-bit two's-complement value summed in
+ *     three slots 3 + 3k .. 5 + 3k: the low 32 bits of its low word, the high 32 bits of its low word (both unsigned), and its
+ *     signed high word.  |w| < 2^42, |r| < 2^43, |P| < 2^87, and 2^31 - 1 pairs overflow no slot; the host recombines
+ *     hi 2^64 + mid 2^32 + lo in unbounded integers.  n_query = 0 (or n_target = 0) writes only the zeroed sums.
+ *     One set of 87 integer atomicAdd per workgroup, no other atomics: the same bits for any order of the pairs.
+ * Every pointer is DEVICE memory.  Null pointers (where the count is not 0; sums_or_null may always be null), a count outside
+ * 0 .. 2^31 - 1, a bad grid, radius, cap, origin, z_down or e_max, a short scratch, overlapping buffers: D3D_ERR_INVALID_ARG
+ * before any launch.
+ */
+size_t d3d_cloud_normals_scratch_bytes(long long n);
+int d3d_cloud_normals(const float* xyz, const long long* sorted_keys, const long long* order, long long n_points, int nx, int ny,
+                      int nz, double radius, int z_down, void* scratch, size_t scratch_bytes, float* normals, int* count,
+                      int* flatness, long long* sums_or_null, d3d_stream_t stream);
+int d3d_cloud_register_plane_sums(const float* q_xyz, const int* e, const int* idx, long long n_query, const float* t_xyz,
+                                  const float* t_normals, long long n_target, int nx, int ny, int nz, double xmin, double ymin,
+                                  double zmin, double cap, int e_max, long long* sums, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.30 -- deterministic samples of a surface mesh at a stated spacing, and a comparison's error brought back onto the
  * faces: what holds a mesh against a reference cloud with the search above.  The rule is this project's
  * (deep3d_aerial_amd/mesh_compare.py); it does not claim to match any tool.
