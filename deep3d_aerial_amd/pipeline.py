@@ -69,7 +69,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
                      filter_sources=True, partition="block", scene_range=None, skip_line=2, feature_cache_bytes=0,
                      device="cuda", timings=None, display=False, fuse_partition="views", scene_blocks=None,
                      estimate_normals=False, normal_nei=1, save_normals=False, dsm=None, ortho=None, mesh=None, texture=None,
-                     cloud=None):
+                     dtm=None, cloud=None):
     """Runs the three steps above for this rank.  Returns a list, one entry per reference view this rank owns, of
     {"ref", "final_mask" [H,W] bool, "avg_xyz_world" [3,H,W], "points": fuse.extract_points(...) dict} (device tensors).
     timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s.
@@ -126,7 +126,11 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     filter_sources=False the file does not depend on the number of ranks.  The crops are the sweeping rank's, so with more than
     one rank fuse_partition must be "views".  With cloud["outliers"] ({"radius", "k", "alpha", "min_neighbours"}; absent or None:
     off) rank 0 filters the merged cloud before it writes it (cloud_outliers.filter_cloud, checked up front with the cloud
-    settings): no new collective; timings gets cloud_outliers, the filter's info."""
+    settings): no new collective; timings gets cloud_outliers, the filter's info.
+    dtm: None (nothing changes), or the terrain settings {"path", "ndsm", "ground", "max_window", "slope", "dh0", "dh_max"} (needs
+    dsm; dtm.check_settings): rank 0 filters the height raster the DSM step returned (either source, after any MovingAverage fill,
+    which is part of the DSM) and writes the DTM and, when asked, the nDSM and the level raster on the DSM's grid with its nodata
+    (write_dtm_of); no collective; timings gets dtm_s on rank 0."""
     if mesh is not None:
         from . import mesh as _mesh
 
@@ -153,6 +157,12 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             if mesh is None:
                 raise ValueError("a DSM from the mesh needs mesh settings: the DSM is rasterised from the mesh")
             _dsm.check_mesh_settings(dsm)
+    if dtm is not None:
+        from . import dtm as _dtm
+
+        if dsm is None:
+            raise ValueError("dtm needs dsm: the terrain is filtered from the DSM")
+        _dtm.check_settings(dtm)
     if ortho is not None:
         from . import ortho as _ortho
 
@@ -287,6 +297,8 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
                    for i in mine]
             write_ortho_of(built[0] if built is not None else None, dsm, ortho, own, rank, world_size, device=all_maps.device,
                            timings=timings)
+        if dtm is not None and rank == 0:
+            write_dtm_of(built[0], dsm, dtm, timings=timings)
     if texture is not None:
         own = [(images[recs[i]["name"]][0], all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], images[recs[i]["name"]][1])
                for i in mine]
@@ -569,6 +581,20 @@ def write_mesh_dsm_of(built_mesh, settings, device="cuda", timings=None):
     if timings is not None:
         timings["dsm_s"] = time.perf_counter() - t0
     return h, None
+
+
+def write_dtm_of(height, dsm_settings, settings, timings=None):
+    """Rank 0's DTM of the height raster the DSM step returned, on the DSM's grid and with its nodata (dtm.build_and_write);
+    no collective.  Returns (dtm, level, ndsm)."""
+    from . import dsm as _dsm, dtm as _dtm
+
+    t0 = time.perf_counter()
+    grid = _dsm.DsmGrid(dsm_settings["border"], dsm_settings.get("unit") or (0.1, 0.1), dsm_settings.get("size"))
+    res = _dtm.build_and_write(height, grid, dict(settings, nodata=dsm_settings.get("nodata", -9999.0)))
+    torch.cuda.synchronize()
+    if timings is not None:
+        timings["dtm_s"] = time.perf_counter() - t0
+    return res
 
 
 def add_estimated_normals(views, pairs, fusion_num=10, nei=1):

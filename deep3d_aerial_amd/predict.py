@@ -565,6 +565,11 @@ def parse_args(argv=None):
     _dsm.add_arguments(ap, prefix="dsm_")
     ap.add_argument("--dsm_source", default="pc", choices=list(_dsm.SOURCES),
                     help="pc: the fused points; mesh: the surface mesh of --mesh (run.py:226-232 dsm_source)")
+    # bare-earth terrain and object heights from the DSM (deep3d_aerial_amd/dtm.py): off by default
+    from . import dtm as _dtm
+
+    ap.add_argument("--dtm", default=None, help="with --fuse --dsm: write the DTM filtered from the DSM to this .tif (+ .tfw), on rank 0")
+    _dtm.add_arguments(ap, prefix="dtm_")
     # true orthophoto on the DSM (deep3d_aerial_amd/ortho.py): off by default
     from . import ortho as _ortho
 
@@ -606,6 +611,10 @@ def parse_args(argv=None):
         ap.error("--dsm needs --fuse (the DSM is built from the fused points)")
     if a.dsm is not None and a.dsm_border is None:
         ap.error("--dsm needs --dsm_border Xmin,Xmax,Ymin,Ymax[,Zmin,Zmax]")
+    if a.dtm is not None:
+        if a.dsm is None:
+            ap.error("--dtm needs --dsm (the terrain is filtered from the DSM)")
+        _dtm.check_args(ap, a, a.dtm, prefix="dtm_", nodata=a.dsm_nodata)
     if a.ortho is not None and not a.fuse:
         ap.error("--ortho needs --fuse (the orthophoto is draped on the DSM of the fused points)")
     if a.ortho is not None and a.dsm is None:
@@ -706,6 +715,12 @@ def _dsm_settings(a):
     return s
 
 
+def _dtm_settings(a):
+    from . import dtm as _dtm
+
+    return _dtm.settings_from_args(a, a.dtm, prefix="dtm_", nodata=a.dsm_nodata)
+
+
 def _ortho_settings(a):
     from . import ortho as _ortho
 
@@ -791,7 +806,8 @@ def main(argv=None):
                                         ortho=_ortho_settings(a) if a.ortho is not None else None,
                                         mesh=_mesh_settings(a) if a.mesh is not None else None,
                                         texture=_texture_settings(a) if a.texture is not None else None,
-                                        cloud=_cloud_settings(a) if a.cloud is not None else None)
+                                        cloud=_cloud_settings(a) if a.cloud is not None else None,
+                                        dtm=_dtm_settings(a) if a.dtm is not None else None)
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
         if a.cloud is not None and rank == 0:
             print("rank 0/%d: merged point cloud %s in %.2f s" % (world, a.cloud, tm["cloud_s"]))
@@ -800,6 +816,8 @@ def main(argv=None):
                 print("rank 0/%d: cloud outliers: kept %d of %d points, dropped %d" % (world, o["kept"], o["points"], o["points"] - o["kept"]))
         if a.dsm is not None and rank == 0:
             print("rank 0/%d: DSM %s in %.2f s" % (world, a.dsm, tm["dsm_s"]))
+        if a.dtm is not None and rank == 0:
+            print("rank 0/%d: DTM %s in %.2f s" % (world, a.dtm, tm["dtm_s"]))
         if a.ortho is not None and rank == 0:
             print("rank 0/%d: orthophoto %s in %.2f s" % (world, a.ortho, tm["ortho_s"]))
         if a.mesh is not None and rank == 0:

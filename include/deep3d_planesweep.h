@@ -855,6 +855,42 @@ int d3d_dsm_from_points(const float* xyz, long long n_points, double x_min, doub
 int d3d_dsm_fill_moving_average(const float* in, float* out, int W, int H, int radius, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.35 -- bare-earth terrain (DTM) and object heights (nDSM) from a DSM raster.  The rule is this project's
+ * (deep3d_aerial_amd/dtm.py states it in full); the reference has no DTM.  Every raster is [H,W] fp32 (device), NaN = empty,
+ * W * H < 2^31; every NaN written is 0x7fc00000.
+ *   d3d_dtm_erode: out[i,j] = the smallest non-NaN value of rows i-ry..i+ry, columns j-rx..j+rx of `in`, clipped to the raster,
+ *   in the IEEE total order (-0.0 < +0.0); NaN when the window holds none.  d3d_dtm_dilate: the largest.  d3d_dtm_open:
+ *   dilate(erode(in)).  rx, ry in 1..D3D_DTM_MAX_RADIUS.  Exact selections: the result depends on no launch shape.  The work and
+ *   the bytes moved per cell do not depend on the radius (running extremes over segments of 2 r + 1 cells, csrc/dtm.hip).
+ *   scratch: device memory of d3d_dtm_scratch_bytes(W, H) bytes (two rasters; 0 for an out-of-range size); in, out and
+ *   scratch do not overlap.
+ *   d3d_dtm_classify, level k in 1..254: a cell is struck when fp32(surface - opened) > dh (false when either is NaN).  k == 1
+ *   writes every cell of level: 255 where surface is NaN, else 1 when struck, else 0.  k > 1 writes k into the struck cells
+ *   whose level is 0 and leaves the others.
+ *   d3d_dtm_ground: ground = height where level == 0, else NaN.  d3d_dtm_ndsm: ndsm = fp32(height - dtm), NaN where either is.
+ *   d3d_dtm_pull: coarse [ceil(Hf/2), ceil(Wf/2)]; a coarse cell (I, J) is the mean of its non-NaN children (2I+a, 2J+b) in
+ *   range, summed in fp64 in the order (a, b) = (0,0), (0,1), (1,0), (1,1), divided by their number, rounded once; NaN with none.
+ *   d3d_dtm_push: a NaN cell (i, j) of fine gets fp32(sum(w v) / sum(w)) in fp64 over the coarse cells (I0, J0) w 9, (I0, J1) w 3,
+ *   (I1, J0) w 3, (I1, J1) w 1, in that order, I0 = i >> 1, I1 = I0 + (i odd ? 1 : -1), J alike; coarse cells out of range or
+ *   NaN are skipped, NaN with none.  Cells of fine that hold a value are not written.  fine and coarse do not overlap.
+ * No atomics: every output is the same bits run to run.
+ */
+#define D3D_DTM_MAX_RADIUS 1024
+size_t d3d_dtm_scratch_bytes(int W, int H);
+int d3d_dtm_erode(const float* in, float* out, int W, int H, int rx, int ry, void* scratch, size_t scratch_bytes,
+                  d3d_stream_t stream);
+int d3d_dtm_dilate(const float* in, float* out, int W, int H, int rx, int ry, void* scratch, size_t scratch_bytes,
+                   d3d_stream_t stream);
+int d3d_dtm_open(const float* in, float* out, int W, int H, int rx, int ry, void* scratch, size_t scratch_bytes,
+                 d3d_stream_t stream);
+int d3d_dtm_classify(const float* surface, const float* opened, float dh, int k, unsigned char* level, int W, int H,
+                     d3d_stream_t stream);
+int d3d_dtm_ground(const float* height, const unsigned char* level, float* ground, int W, int H, d3d_stream_t stream);
+int d3d_dtm_ndsm(const float* height, const float* dtm, float* ndsm, int W, int H, d3d_stream_t stream);
+int d3d_dtm_pull(const float* fine, int Wf, int Hf, float* coarse, d3d_stream_t stream);
+int d3d_dtm_push(const float* coarse, float* fine, int Wf, int Hf, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.11 -- digital surface model from a triangle mesh: the reference's CREATEDSM step with dsm_source "mesh"
  * (run.py:226-232 calls mesh2dsm.DSM_from_Mesh, which the reference never shipped; the semantics are this project's,
  * deep3d_aerial_amd/dsm.py).  The raster is the one of d3d_dsm_from_points.
