@@ -1,0 +1,521 @@
+// Objects of an nDSM raster: connected components of the foreground, their statistics and the label raster (the
+// rule is deep3d_aerial_amd/objects.py's, this project's own: the reference has no such step).
+//
+// A component's root is its smallest linear index i * W + j.  Every union below hooks the larger of two roots under the smaller
+// with an integer atomicMin, so a parent is never above its cell and only ever decreases; whatever the order of the unions, the
+// tile size or the launch shape, the fixed point is the smallest index of each component.
+//   tile:     one workgroup of four waves labels a 64 x 64 tile in LDS.  A wave takes a row of 64 cells: the ballot of the
+//             foreground predicate is the row's mask, and a lane's run start is the bit after the highest zero below it -- a row is
+//             labelled by its run starts with no word passed between lanes.  Runs of adjacent rows that overlap (connectivity 8: the
+//             row above widened by a lane each way) are joined by a lock-free union-find on the run starts (LDS atomicMin); of the
+//             lanes of one overlap only the first joins.  The cells are then written once as parents in global linear indices
+//             (-1 for background): the raster is read once and the parent raster written once.
+//   border:   one lane per cell of the first row / column behind a tile edge joins it to its (up to three) foreground neighbours
+//             across the edge in the global parent raster, by the same lock-free find-and-atomicMin loop.  Every loop is bounded by
+//             parents that strictly decrease (see obj_union); no lane waits for another lane's progress.  Only border cells and
+//             their roots are touched.
+//   resolve:  one pass sets every foreground cell to its root.
+//   roots:    parent[c] == c flags the roots; geom_scan of the flags is the provisional id (the roots in index order).
+//   stats:    a wave covers 64 consecutive cells of a row and walks 32 rows; each run of equal ids in a row is reduced into its
+//             last lane -- the count, the index sums and the box of a run follow from its two end lanes in closed form, the height
+//             sum and maximum from a segmented scan by shuffles -- and that lane holds the part back while the runs of the next rows
+//             that end at it are the same component's.  A part is sent as four integer atomicAdd and up to five atomicMin / atomicMax
+//             (those only when the slot does not hold as much already).  Built with -DD3D_OBJECTS_PLAIN every cell sends its own
+//             (tools/objects_bench.py --variant_library).
+//   relabel:  keep = cells >= min_cells, geom_scan of keep is the final id, one pass writes label.
+// Atomics: integer atomicMin / atomicMax / atomicAdd, nothing else, so every output is the same bits run to run.  No kernel here
+// stores 12 or 16 bytes per lane and none uses scratch memory.
+#include <algorithm>
+
+#include "common.h"
+#include "geom_shared.h"
+
+namespace d3d {
+
+constexpr int OBJ_TILE = D3D_OBJECTS_TILE;
+constexpr int OBJ_BLOCK = 256;
+constexpr int OBJ_WAVES = OBJ_BLOCK / 64;
+constexpr int OBJ_ROWS_PER_WAVE = OBJ_TILE / OBJ_WAVES;
+constexpr int OBJ_STATS_ROWS = 32;                // rows a wave of the statistics pass walks
+constexpr int OBJ_SLOTS = D3D_OBJECTS_SLOTS;   // cells, sum_i, sum_j, hsum, i0, i1, j0, j1, hmax key
+static_assert(OBJ_TILE == 64, "a wave takes a row of the tile: its side is the wave's 64 lanes");
+
+template <bool MASK>
+__device__ __forceinline__ bool obj_foreground(const float* __restrict__ ndsm, const unsigned char* __restrict__ mask, float min_height,
+                                               long c) {
+    if (MASK) return mask[c] != 0;
+    const float v = ndsm[c];
+    return v >= min_height && fabsf(v) < __builtin_inff();   // false for a NaN
+}
+
+__device__ __forceinline__ bool obj_bit(unsigned long long m, int k) { return k >= 0 && k < 64 && ((m >> k) & 1ull); }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// union-find: parent[x] <= x always, roots have parent[x] == x
+// ---------------------------------------------------------------------------------------------------------------------------
+// A walk up strictly decreasing parents: at most x steps.  A value read late is an earlier parent of the same cell: a member of
+// its set that is no larger than the cell, so the walk still ends at a member.
+__device__ __forceinline__ int obj_find_lds(volatile int* L, int x) {
+    for (int p = L[x]; p != x; p = L[x]) x = p;
+    return x;
+}
+
+// Joins the sets of a and b.  A pass finds two roots and hooks the larger under the smaller; when the atomicMin finds that the
+// larger one was no root any more, it returns that cell's parent of the moment, which is smaller: the pass is repeated from
+// there.  a and b never increase and one of them strictly decreases per repeated pass, so the loop ends after at most a + b
+// passes whatever the other lanes do.  Returns the number of repeated passes.
+__device__ __forceinline__ int obj_union_lds(int* L, int a, int b) {
+    int again = 0;
+    for (;;) {
+        a = obj_find_lds(L, a);
+        b = obj_find_lds(L, b);
+        if (a == b) return again;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = atomicMin(L + a, b);
+        if (old == a) return again;
+        a = old;
+        ++again;
+    }
+}
+
+__device__ __forceinline__ int obj_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int obj_find(const int* P, int x) {
+    for (int p = obj_load(P + x); p != x && p >= 0; p = obj_load(P + x)) x = p;
+    return x;
+}
+
+// The same in the global parent raster; *hooked counts the atomicMin that joined two trees.
+__device__ __forceinline__ int obj_union(int* P, int a, int b, int* hooked) {
+    int again = 0;
+    for (;;) {
+        a = obj_find(P, a);
+        b = obj_find(P, b);
+        if (a == b) return again;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = atomicMin(P + a, b);
+        if (old == a) {
+            ++*hooked;
+            return again;
+        }
+        a = old;
+        ++again;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// foreground as rasters (the opening of the mask, and objects.foreground)
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(OBJ_BLOCK) void obj_foreground_kernel(const float* __restrict__ ndsm, float min_height,
+                                                                   unsigned char* __restrict__ mask, float* __restrict__ maskf, int n) {
+    const long c = (long)blockIdx.x * OBJ_BLOCK + threadIdx.x;
+    if (c >= n) return;
+    const bool fg = obj_foreground<false>(ndsm, nullptr, min_height, c);
+    if (mask) mask[c] = fg ? (unsigned char)1 : (unsigned char)0;
+    if (maskf) maskf[c] = fg ? 1.0f : 0.0f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// tile labelling
+// ---------------------------------------------------------------------------------------------------------------------------
+template <bool MASK>
+__global__ __launch_bounds__(OBJ_BLOCK) void obj_tile_kernel(const float* __restrict__ ndsm, const unsigned char* __restrict__ mask,
+                                                             float min_height, int conn8, int* __restrict__ parent, int W, int H, int ntx) {
+    __shared__ int L[OBJ_TILE * OBJ_TILE];           // a cell's parent as row * 64 + lane of the tile; -1 for background
+    __shared__ unsigned long long rows[OBJ_TILE];    // the foreground mask of each row
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int x0 = (int)(blockIdx.x % (unsigned)ntx) * OBJ_TILE, y0 = (int)(blockIdx.x / (unsigned)ntx) * OBJ_TILE;
+    const int x = x0 + lane;
+#pragma unroll 4
+    for (int k = 0; k < OBJ_ROWS_PER_WAVE; ++k) {
+        const int r = wave * OBJ_ROWS_PER_WAVE + k, y = y0 + r;
+        bool fg = false;
+        if (x < W && y < H) fg = obj_foreground<MASK>(ndsm, mask, min_height, (long)y * W + x);
+        const unsigned long long m = __ballot(fg);
+        if (lane == 0) rows[r] = m;
+        const unsigned long long below = ~m & ((1ull << lane) - 1ull);   // the background lanes below this one
+        const int start = below ? 64 - __clzll((long long)below) : 0;
+        L[r * OBJ_TILE + lane] = fg ? r * OBJ_TILE + start : -1;
+    }
+    __syncthreads();
+    for (int k = 0; k < OBJ_ROWS_PER_WAVE; ++k) {
+        const int r = wave * OBJ_ROWS_PER_WAVE + k;
+        if (r == 0) continue;
+        const unsigned long long m = rows[r], up = rows[r - 1];
+        if (!obj_bit(m, lane)) continue;
+        const int a = r * OBJ_TILE + lane, b = (r - 1) * OBJ_TILE + lane;
+        const bool uj = obj_bit(up, lane), ul = obj_bit(up, lane - 1), ur = obj_bit(up, lane + 1);
+        const bool ml = obj_bit(m, lane - 1), mr = obj_bit(m, lane + 1);
+        // straight up, unless the lane before is in the same two runs and joins them
+        if (uj && !(ml && ul)) obj_union_lds(L, a, b);
+        // diagonally, when the cell straight up is background (else it is in the diagonal cell's run) and the cell beside this
+        // one is background too (else that one lies straight under the diagonal cell)
+        if (conn8 && !uj) {
+            if (ul && !ml) obj_union_lds(L, a, b - 1);
+            if (ur && !mr) obj_union_lds(L, a, b + 1);
+        }
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int k = 0; k < OBJ_ROWS_PER_WAVE; ++k) {
+        const int r = wave * OBJ_ROWS_PER_WAVE + k, y = y0 + r;
+        if (x >= W || y >= H) continue;
+        const int v = L[r * OBJ_TILE + lane];
+        int out = -1;
+        if (v >= 0) {
+            const int root = obj_find_lds(L, v);
+            out = (y0 + (root >> 6)) * W + x0 + (root & 63);
+        }
+        parent[(long)y * W + x] = out;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// border merge: items 0 .. nh W - 1 are the cells of the rows 64, 128, ..; the rest the cells of the columns 64, 128, ..
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(OBJ_BLOCK) void obj_border_kernel(int* parent, int conn8, int W, int H, long long n_row_items, long long items,
+                                                               long long* counters) {
+    const long long t = (long long)blockIdx.x * OBJ_BLOCK + threadIdx.x;
+    int hooked = 0, again = 0;
+    if (t < items) {
+        int x, y, nx[3], ny[3], nn = 0;
+        if (t < n_row_items) {
+            y = (int)(t / W + 1) * OBJ_TILE;
+            x = (int)(t % W);
+            nx[nn] = x, ny[nn++] = y - 1;
+            if (conn8 && x > 0) nx[nn] = x - 1, ny[nn++] = y - 1;
+            if (conn8 && x < W - 1) nx[nn] = x + 1, ny[nn++] = y - 1;
+        } else {
+            const long long u = t - n_row_items;
+            x = (int)(u / H + 1) * OBJ_TILE;
+            y = (int)(u % H);
+            nx[nn] = x - 1, ny[nn++] = y;
+            if (conn8 && y > 0) nx[nn] = x - 1, ny[nn++] = y - 1;
+            if (conn8 && y < H - 1) nx[nn] = x - 1, ny[nn++] = y + 1;
+        }
+        if (x < W && y < H) {   // always true for an item of the launch: a guard on the loads
+            const int c = y * W + x;
+            if (obj_load(parent + c) >= 0) {
+                for (int k = 0; k < nn; ++k) {
+                    const int d = ny[k] * W + nx[k];
+                    if (obj_load(parent + d) >= 0) again += obj_union(parent, c, d, &hooked);
+                }
+            }
+        }
+    }
+    if (counters) {   // uniform
+        hooked = wave_sum(hooked);
+        again = wave_sum(again);
+        if ((threadIdx.x & 63) == 0) {
+            if (hooked) atomicAdd((unsigned long long*)counters, (unsigned long long)hooked);
+            if (again) atomicAdd((unsigned long long*)counters + 1, (unsigned long long)again);
+        }
+    }
+}
+
+// parent[c] = the root of c; a parent another lane has already replaced by its root is as good as the one before
+__global__ __launch_bounds__(OBJ_BLOCK) void obj_resolve_kernel(int* parent, int n) {
+    const long c = (long)blockIdx.x * OBJ_BLOCK + threadIdx.x;
+    if (c >= n) return;
+    const int p0 = parent[c];
+    if (p0 < 0) return;
+    int p = p0;
+    for (int q = parent[p]; q != p && q >= 0; q = parent[p]) p = q;
+    if (p != p0) parent[c] = p;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// roots, statistics, relabel
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(OBJ_BLOCK) void obj_root_flag_kernel(const int* __restrict__ parent, int* __restrict__ flag, int n) {
+    const long c = (long)blockIdx.x * OBJ_BLOCK + threadIdx.x;
+    if (c < n) flag[c] = parent[c] == (int)c ? 1 : 0;
+}
+
+__global__ __launch_bounds__(OBJ_BLOCK) void obj_acc_init_kernel(long long* __restrict__ acc, long long n_roots) {
+    const long long k = (long long)blockIdx.x * OBJ_BLOCK + threadIdx.x;
+    if (k >= n_roots) return;
+    long long* A = acc + k * OBJ_SLOTS;
+    A[0] = A[1] = A[2] = A[3] = 0;
+    A[4] = A[6] = 0x7fffffffffffffffll;
+    A[5] = A[7] = -1;
+    A[8] = 0;
+}
+
+// q(h) = min(2^32 - 1, floor(fp64(h) * 1024 + 0.5)) for h >= 0
+__device__ __forceinline__ unsigned long long obj_q(float h) {
+    const double q = floor((double)h * 1024.0 + 0.5);
+    return q >= 4294967295.0 ? 4294967295ull : (unsigned long long)q;
+}
+
+// What a lane has gathered for one component and not yet added to its slots: runs of consecutive rows that end at this lane.
+struct ObjPart {
+    int v = -1;   // the provisional id; -1: nothing
+    long long cells, sum_i, sum_j;
+    unsigned long long hs;
+    int i0, i1, j0, j1;
+    unsigned hk;
+};
+
+// The part's nine slots.  The sums are added; a box edge or the maximum is sent only when the slot does not hold as much
+// already: the slots move one way, so a value read late errs on the side of sending.
+__device__ __forceinline__ void obj_flush(long long* __restrict__ acc, const ObjPart& p) {
+    long long* A = acc + (long long)p.v * OBJ_SLOTS;
+    atomicAdd((unsigned long long*)A + 0, (unsigned long long)p.cells);
+    atomicAdd((unsigned long long*)A + 1, (unsigned long long)p.sum_i);
+    atomicAdd((unsigned long long*)A + 2, (unsigned long long)p.sum_j);
+    atomicAdd((unsigned long long*)A + 3, p.hs);
+    if (__hip_atomic_load(A + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > p.i0) atomicMin(A + 4, (long long)p.i0);
+    if (__hip_atomic_load(A + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < p.i1) atomicMax(A + 5, (long long)p.i1);
+    if (__hip_atomic_load(A + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > p.j0) atomicMin(A + 6, (long long)p.j0);
+    if (__hip_atomic_load(A + 7, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < p.j1) atomicMax(A + 7, (long long)p.j1);
+    if (__hip_atomic_load(A + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (long long)p.hk) atomicMax(A + 8, (long long)p.hk);
+}
+
+// Wave `item`: the columns (item % nchunks) * 64 .. + 63 of the rows (item / nchunks) * OBJ_STATS_ROWS .. + OBJ_STATS_ROWS - 1.
+// Row by row, each run of equal ids is reduced into its last lane; that lane keeps the part while the runs of the following
+// rows that end at it belong to the same component (the rows of a box, the bands of a serpentine), and sends it when another
+// component's run ends there or the rows are done.
+__global__ __launch_bounds__(OBJ_BLOCK) void obj_stats_kernel(const float* __restrict__ ndsm, const int* __restrict__ parent,
+                                                              const int* __restrict__ pid, int W, int H, int n, int nchunks,
+                                                              long long items, long long n_roots, long long* __restrict__ acc) {
+    const int lane = (int)threadIdx.x & 63;
+    const long long item = (long long)blockIdx.x * OBJ_WAVES + ((int)threadIdx.x >> 6);
+    if (item >= items) return;   // the whole wave
+    const int xs = (int)(item % nchunks) * 64, x = xs + lane;
+    const int y0 = (int)(item / nchunks) * OBJ_STATS_ROWS, y1 = min(y0 + OBJ_STATS_ROWS, H);
+    ObjPart part;
+    for (int y = y0; y < y1; ++y) {
+        int v = -1;
+        unsigned long long hs = 0;
+        unsigned hk = 0;
+        if (x < W) {
+            const long c = (long)y * W + x;
+            const int p = parent[c];
+            if (p >= 0 && p < n) {
+                const int id = pid[p];
+                const float h = ndsm[c];
+                if (id >= 0 && id < n_roots && h >= 0.0f && h < __builtin_inff()) {   // always true for a foreground cell: a guard
+                    v = id;
+                    hs = obj_q(h);
+                    hk = dsm_key(h);
+                }
+            }
+        }
+        int first = lane;
+        bool ends = v >= 0;
+#ifndef D3D_OBJECTS_PLAIN
+        // the run of equal ids this lane lies in begins at the highest head at or below it
+        const int before = __shfl_up(v, 1, 64);
+        const unsigned long long heads = __ballot(lane == 0 || before != v);
+        first = 63 - __clzll((long long)(heads & ((2ull << lane) - 1ull)));
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long s = __shfl_up(hs, o, 64);
+            const unsigned m = __shfl_up(hk, o, 64);
+            if (lane - o >= first) {
+                hs += s;
+                hk = max(hk, m);
+            }
+        }
+        const int next = __shfl_down(v, 1, 64);
+        ends = ends && (lane == 63 || next != v);   // the last lane of its run
+#endif
+        if (!ends) continue;
+        // the run is the cells xs + first .. xs + lane of row y
+        const long long cells = lane - first + 1, j0 = xs + first, j1 = xs + lane;
+        if (v == part.v) {
+            part.cells += cells;
+            part.sum_i += cells * y;
+            part.sum_j += (j0 + j1) * cells / 2;
+            part.hs += hs;
+            part.i1 = y;
+            part.j0 = min(part.j0, (int)j0);
+            part.hk = max(part.hk, hk);
+        } else {
+            if (part.v >= 0) obj_flush(acc, part);
+            part.v = v;
+            part.cells = cells;
+            part.sum_i = cells * y;
+            part.sum_j = (j0 + j1) * cells / 2;
+            part.hs = hs;
+            part.i0 = part.i1 = y;
+            part.j0 = (int)j0;
+            part.j1 = (int)j1;
+            part.hk = hk;
+        }
+#ifdef D3D_OBJECTS_PLAIN
+        obj_flush(acc, part);   // one set per cell
+        part.v = -1;
+#endif
+    }
+    if (part.v >= 0) obj_flush(acc, part);
+}
+
+__global__ __launch_bounds__(OBJ_BLOCK) void obj_keep_kernel(const long long* __restrict__ acc, long long n_roots, long long min_cells,
+                                                             int* __restrict__ keep) {
+    const long long k = (long long)blockIdx.x * OBJ_BLOCK + threadIdx.x;
+    if (k < n_roots) keep[k] = acc[k * OBJ_SLOTS] >= min_cells ? 1 : 0;
+}
+
+__global__ __launch_bounds__(OBJ_BLOCK) void obj_label_kernel(const int* __restrict__ parent, const int* __restrict__ pid,
+                                                              const long long* __restrict__ acc, const int* __restrict__ final_id,
+                                                              long long n_roots, long long min_cells, int* __restrict__ label, int n) {
+    const long c = (long)blockIdx.x * OBJ_BLOCK + threadIdx.x;
+    if (c >= n) return;
+    const int p = parent[c];
+    int out = 0;
+    if (p >= 0 && p < n) {
+        const int k = pid[p];
+        if (k >= 0 && k < n_roots && acc[(long long)k * OBJ_SLOTS] >= min_cells) out = final_id[k] + 1;
+    }
+    label[c] = out;
+}
+
+static bool obj_dims_ok(int W, int H) { return W >= 1 && H >= 1 && (long long)W * H < (1ll << 31) - 1; }
+
+static bool obj_apart(const void* a, size_t na, const void* b, size_t nb) {
+    return (uintptr_t)a + na <= (uintptr_t)b || (uintptr_t)b + nb <= (uintptr_t)a;
+}
+
+// scratch: the provisional-id raster, then the tile sums of the scans
+struct ObjScratch {
+    size_t pid, scan, bytes;
+};
+
+static ObjScratch obj_layout(int W, int H) {
+    ScratchLayout L;
+    ObjScratch s;
+    s.pid = L.take((size_t)W * H * 4);
+    s.scan = L.take(geom_scan_bytes((long long)W * H));
+    s.bytes = L.bytes;
+    return s;
+}
+
+}  // namespace d3d
+
+using namespace d3d;
+
+#define OBJ_DIMS(name) D3D_REQUIRE(obj_dims_ok(W, H), "%s: raster %d x %d: size must be >= 1 and W * H < 2^31 - 1", name, W, H)
+
+extern "C" size_t d3d_objects_scratch_bytes(int W, int H) { return obj_dims_ok(W, H) ? obj_layout(W, H).bytes : 0; }
+
+extern "C" int d3d_objects_foreground(const float* ndsm, float min_height, unsigned char* mask, float* maskf, int W, int H,
+                                      d3d_stream_t stream) {
+    D3D_REQUIRE(ndsm && (mask || maskf), "d3d_objects_foreground: null pointer (ndsm, or both of mask and maskf)");
+    OBJ_DIMS("d3d_objects_foreground");
+    D3D_REQUIRE(min_height == min_height, "d3d_objects_foreground: min_height is NaN");
+    const int n = W * H;
+    D3D_REQUIRE(!maskf || obj_apart(ndsm, (size_t)n * 4, maskf, (size_t)n * 4), "d3d_objects_foreground: maskf must not alias ndsm");
+    D3D_REQUIRE(!mask || obj_apart(ndsm, (size_t)n * 4, mask, (size_t)n), "d3d_objects_foreground: mask must not alias ndsm");
+    hipLaunchKernelGGL(obj_foreground_kernel, dim3(ceil_div(n, OBJ_BLOCK)), dim3(OBJ_BLOCK), 0, (hipStream_t)stream, ndsm, min_height, mask,
+                       maskf, n);
+    D3D_LAUNCH_CHECK("obj_foreground_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_objects_label(const float* ndsm, float min_height, const unsigned char* mask, int connectivity, int* parent, int W,
+                                 int H, long long* counters, d3d_stream_t stream) {
+    D3D_REQUIRE(parent && ((ndsm != nullptr) != (mask != nullptr)), "d3d_objects_label: null pointer (parent), or not exactly one of ndsm and mask");
+    OBJ_DIMS("d3d_objects_label");
+    D3D_REQUIRE(connectivity == 4 || connectivity == 8, "d3d_objects_label: connectivity %d is neither 4 nor 8", connectivity);
+    D3D_REQUIRE(mask || min_height == min_height, "d3d_objects_label: min_height is NaN");
+    const int n = W * H;
+    D3D_REQUIRE(ndsm ? obj_apart(ndsm, (size_t)n * 4, parent, (size_t)n * 4) : obj_apart(mask, (size_t)n, parent, (size_t)n * 4),
+                "d3d_objects_label: parent must not alias the input");
+    hipStream_t st = (hipStream_t)stream;
+    const int conn8 = connectivity == 8 ? 1 : 0, ntx = ceil_div(W, OBJ_TILE), nty = ceil_div(H, OBJ_TILE);
+    if (counters) {
+        const int rc = hip_status(hipMemsetAsync(counters, 0, 16, st), "objects: clear counters");
+        if (rc != D3D_OK) return rc;
+    }
+    const dim3 grid((unsigned)ntx * (unsigned)nty);
+    if (mask)
+        hipLaunchKernelGGL(obj_tile_kernel<true>, grid, dim3(OBJ_BLOCK), 0, st, ndsm, mask, min_height, conn8, parent, W, H, ntx);
+    else
+        hipLaunchKernelGGL(obj_tile_kernel<false>, grid, dim3(OBJ_BLOCK), 0, st, ndsm, mask, min_height, conn8, parent, W, H, ntx);
+    D3D_LAUNCH_CHECK("obj_tile_kernel launch");
+    const long long n_row_items = (long long)((H - 1) / OBJ_TILE) * W, items = n_row_items + (long long)((W - 1) / OBJ_TILE) * H;
+    if (items > 0) {
+        hipLaunchKernelGGL(obj_border_kernel, dim3((unsigned)((items + OBJ_BLOCK - 1) / OBJ_BLOCK)), dim3(OBJ_BLOCK), 0, st, parent, conn8, W,
+                           H, n_row_items, items, counters);
+        D3D_LAUNCH_CHECK("obj_border_kernel launch");
+        hipLaunchKernelGGL(obj_resolve_kernel, dim3(ceil_div(n, OBJ_BLOCK)), dim3(OBJ_BLOCK), 0, st, parent, n);
+        D3D_LAUNCH_CHECK("obj_resolve_kernel launch");
+    }
+    return D3D_OK;
+}
+
+extern "C" int d3d_objects_roots(const int* parent, int W, int H, void* scratch, size_t scratch_bytes, long long* n_roots,
+                                 d3d_stream_t stream) {
+    D3D_REQUIRE(parent && scratch && n_roots, "d3d_objects_roots: null pointer (parent, scratch, n_roots)");
+    OBJ_DIMS("d3d_objects_roots");
+    const ObjScratch L = obj_layout(W, H);
+    D3D_REQUIRE(scratch_bytes >= L.bytes, "d3d_objects_roots: scratch of %zu bytes, %zu needed (d3d_objects_scratch_bytes)", scratch_bytes,
+                L.bytes);
+    const int n = W * H;
+    D3D_REQUIRE(obj_apart(parent, (size_t)n * 4, scratch, L.bytes), "d3d_objects_roots: scratch must not alias parent");
+    hipStream_t st = (hipStream_t)stream;
+    int* pid = (int*)((char*)scratch + L.pid);
+    hipLaunchKernelGGL(obj_root_flag_kernel, dim3(ceil_div(n, OBJ_BLOCK)), dim3(OBJ_BLOCK), 0, st, parent, pid, n);
+    D3D_LAUNCH_CHECK("obj_root_flag_kernel launch");
+    return geom_scan(pid, pid, n, (char*)scratch + L.scan, n_roots, st);
+}
+
+extern "C" int d3d_objects_stats(const float* ndsm, const int* parent, int W, int H, const void* scratch, size_t scratch_bytes,
+                                 long long n_roots, long long* acc, d3d_stream_t stream) {
+    D3D_REQUIRE(ndsm && parent && scratch && acc, "d3d_objects_stats: null pointer (ndsm, parent, scratch, acc)");
+    OBJ_DIMS("d3d_objects_stats");
+    const ObjScratch L = obj_layout(W, H);
+    D3D_REQUIRE(scratch_bytes >= L.bytes, "d3d_objects_stats: scratch of %zu bytes, %zu needed (d3d_objects_scratch_bytes)", scratch_bytes,
+                L.bytes);
+    const int n = W * H;
+    D3D_REQUIRE(n_roots >= 0 && n_roots <= n, "d3d_objects_stats: n_roots %lld outside 0..%d", n_roots, n);
+    if (n_roots == 0) return D3D_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int* pid = (const int*)((const char*)scratch + L.pid);
+    hipLaunchKernelGGL(obj_acc_init_kernel, dim3((unsigned)((n_roots + OBJ_BLOCK - 1) / OBJ_BLOCK)), dim3(OBJ_BLOCK), 0, st, acc, n_roots);
+    D3D_LAUNCH_CHECK("obj_acc_init_kernel launch");
+    const int nchunks = ceil_div(W, 64);
+    const long long items = (long long)ceil_div(H, OBJ_STATS_ROWS) * nchunks;
+    hipLaunchKernelGGL(obj_stats_kernel, dim3((unsigned)((items + OBJ_WAVES - 1) / OBJ_WAVES)), dim3(OBJ_BLOCK), 0, st, ndsm, parent, pid, W, H,
+                       n, nchunks, items, n_roots, acc);
+    D3D_LAUNCH_CHECK("obj_stats_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_objects_relabel(const int* parent, const long long* acc, long long n_roots, long long min_cells, int* final_id,
+                                   int* label, int W, int H, void* scratch, size_t scratch_bytes, long long* n_kept, d3d_stream_t stream) {
+    D3D_REQUIRE(parent && acc && final_id && label && scratch && n_kept,
+                "d3d_objects_relabel: null pointer (parent, acc, final_id, label, scratch, n_kept)");
+    OBJ_DIMS("d3d_objects_relabel");
+    const ObjScratch L = obj_layout(W, H);
+    D3D_REQUIRE(scratch_bytes >= L.bytes, "d3d_objects_relabel: scratch of %zu bytes, %zu needed (d3d_objects_scratch_bytes)",
+                scratch_bytes, L.bytes);
+    const int n = W * H;
+    D3D_REQUIRE(n_roots >= 0 && n_roots <= n, "d3d_objects_relabel: n_roots %lld outside 0..%d", n_roots, n);
+    D3D_REQUIRE(min_cells >= 1, "d3d_objects_relabel: min_cells %lld must be >= 1", min_cells);
+    D3D_REQUIRE(obj_apart(parent, (size_t)n * 4, label, (size_t)n * 4), "d3d_objects_relabel: label must not alias parent");
+    D3D_REQUIRE(obj_apart(label, (size_t)n * 4, scratch, L.bytes), "d3d_objects_relabel: scratch must not alias label");
+    hipStream_t st = (hipStream_t)stream;
+    const int* pid = (const int*)((const char*)scratch + L.pid);
+    if (n_roots > 0) {
+        hipLaunchKernelGGL(obj_keep_kernel, dim3((unsigned)((n_roots + OBJ_BLOCK - 1) / OBJ_BLOCK)), dim3(OBJ_BLOCK), 0, st, acc, n_roots,
+                           min_cells, final_id);
+        D3D_LAUNCH_CHECK("obj_keep_kernel launch");
+    }
+    const int rc = geom_scan(final_id, final_id, n_roots, (char*)scratch + L.scan, n_kept, st);
+    if (rc != D3D_OK) return rc;
+    hipLaunchKernelGGL(obj_label_kernel, dim3(ceil_div(n, OBJ_BLOCK)), dim3(OBJ_BLOCK), 0, st, parent, pid, acc, final_id, n_roots, min_cells,
+                       label, n);
+    D3D_LAUNCH_CHECK("obj_label_kernel launch");
+    return D3D_OK;
+}

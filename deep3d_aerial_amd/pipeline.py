@@ -69,7 +69,7 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
                      filter_sources=True, partition="block", scene_range=None, skip_line=2, feature_cache_bytes=0,
                      device="cuda", timings=None, display=False, fuse_partition="views", scene_blocks=None,
                      estimate_normals=False, normal_nei=1, save_normals=False, dsm=None, ortho=None, mesh=None, texture=None,
-                     dtm=None, cloud=None):
+                     dtm=None, objects=None, cloud=None):
     """Runs the three steps above for this rank.  Returns a list, one entry per reference view this rank owns, of
     {"ref", "final_mask" [H,W] bool, "avg_xyz_world" [3,H,W], "points": fuse.extract_points(...) dict} (device tensors).
     timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s.
@@ -130,7 +130,11 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     dtm: None (nothing changes), or the terrain settings {"path", "ndsm", "ground", "max_window", "slope", "dh0", "dh_max"} (needs
     dsm; dtm.check_settings): rank 0 filters the height raster the DSM step returned (either source, after any MovingAverage fill,
     which is part of the DSM) and writes the DTM and, when asked, the nDSM and the level raster on the DSM's grid with its nodata
-    (write_dtm_of); no collective; timings gets dtm_s on rank 0."""
+    (write_dtm_of); no collective; timings gets dtm_s on rank 0.
+    objects: None (nothing changes), or the segmentation settings {"path", "table", "min_height", "min_area", "connectivity",
+    "open"} (needs dtm; objects.check_settings): rank 0 segments the nDSM the DTM step returned into objects and writes the label
+    raster and, when asked, the table on the DSM's grid with its nodata (write_objects_of); no collective; timings gets
+    objects_s on rank 0."""
     if mesh is not None:
         from . import mesh as _mesh
 
@@ -163,6 +167,12 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         if dsm is None:
             raise ValueError("dtm needs dsm: the terrain is filtered from the DSM")
         _dtm.check_settings(dtm)
+    if objects is not None:
+        from . import objects as _objects
+
+        if dtm is None:
+            raise ValueError("objects needs dtm: the objects are segmented from the nDSM the terrain step returns")
+        _objects.check_settings(objects)
     if ortho is not None:
         from . import ortho as _ortho
 
@@ -298,7 +308,9 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             write_ortho_of(built[0] if built is not None else None, dsm, ortho, own, rank, world_size, device=all_maps.device,
                            timings=timings)
         if dtm is not None and rank == 0:
-            write_dtm_of(built[0], dsm, dtm, timings=timings)
+            terrain = write_dtm_of(built[0], dsm, dtm, timings=timings)
+            if objects is not None:
+                write_objects_of(terrain[2], dsm, objects, timings=timings)
     if texture is not None:
         own = [(images[recs[i]["name"]][0], all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], images[recs[i]["name"]][1])
                for i in mine]
@@ -594,6 +606,20 @@ def write_dtm_of(height, dsm_settings, settings, timings=None):
     torch.cuda.synchronize()
     if timings is not None:
         timings["dtm_s"] = time.perf_counter() - t0
+    return res
+
+
+def write_objects_of(ndsm, dsm_settings, settings, timings=None):
+    """Rank 0's objects of the nDSM the DTM step returned, on the DSM's grid and with its nodata (objects.build_and_write); no
+    collective.  Returns (label, table)."""
+    from . import dsm as _dsm, objects as _objects
+
+    t0 = time.perf_counter()
+    grid = _dsm.DsmGrid(dsm_settings["border"], dsm_settings.get("unit") or (0.1, 0.1), dsm_settings.get("size"))
+    res = _objects.build_and_write(ndsm, grid, dict(settings, nodata=dsm_settings.get("nodata", -9999.0)))
+    torch.cuda.synchronize()
+    if timings is not None:
+        timings["objects_s"] = time.perf_counter() - t0
     return res
 
 

@@ -570,6 +570,12 @@ def parse_args(argv=None):
 
     ap.add_argument("--dtm", default=None, help="with --fuse --dsm: write the DTM filtered from the DSM to this .tif (+ .tfw), on rank 0")
     _dtm.add_arguments(ap, prefix="dtm_")
+    # the objects of the nDSM (deep3d_aerial_amd/objects.py): off by default
+    from . import objects as _objects
+
+    ap.add_argument("--objects", default=None,
+                    help="with --fuse --dsm --dtm: write the label raster of the nDSM's objects to this .tif (+ .tfw), on rank 0")
+    _objects.add_arguments(ap, prefix="objects_")
     # true orthophoto on the DSM (deep3d_aerial_amd/ortho.py): off by default
     from . import ortho as _ortho
 
@@ -615,6 +621,10 @@ def parse_args(argv=None):
         if a.dsm is None:
             ap.error("--dtm needs --dsm (the terrain is filtered from the DSM)")
         _dtm.check_args(ap, a, a.dtm, prefix="dtm_", nodata=a.dsm_nodata)
+    if a.objects is not None:
+        if a.dtm is None:
+            ap.error("--objects needs --dtm (the objects are segmented from the nDSM of the terrain step)")
+        _objects.check_args(ap, a, a.objects, prefix="objects_", nodata=a.dsm_nodata)
     if a.ortho is not None and not a.fuse:
         ap.error("--ortho needs --fuse (the orthophoto is draped on the DSM of the fused points)")
     if a.ortho is not None and a.dsm is None:
@@ -721,6 +731,12 @@ def _dtm_settings(a):
     return _dtm.settings_from_args(a, a.dtm, prefix="dtm_", nodata=a.dsm_nodata)
 
 
+def _objects_settings(a):
+    from . import objects as _objects
+
+    return _objects.settings_from_args(a, a.objects, prefix="objects_", nodata=a.dsm_nodata)
+
+
 def _ortho_settings(a):
     from . import ortho as _ortho
 
@@ -807,7 +823,8 @@ def main(argv=None):
                                         mesh=_mesh_settings(a) if a.mesh is not None else None,
                                         texture=_texture_settings(a) if a.texture is not None else None,
                                         cloud=_cloud_settings(a) if a.cloud is not None else None,
-                                        dtm=_dtm_settings(a) if a.dtm is not None else None)
+                                        dtm=_dtm_settings(a) if a.dtm is not None else None,
+                                        objects=_objects_settings(a) if a.objects is not None else None)
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
         if a.cloud is not None and rank == 0:
             print("rank 0/%d: merged point cloud %s in %.2f s" % (world, a.cloud, tm["cloud_s"]))
@@ -818,6 +835,8 @@ def main(argv=None):
             print("rank 0/%d: DSM %s in %.2f s" % (world, a.dsm, tm["dsm_s"]))
         if a.dtm is not None and rank == 0:
             print("rank 0/%d: DTM %s in %.2f s" % (world, a.dtm, tm["dtm_s"]))
+        if a.objects is not None and rank == 0:
+            print("rank 0/%d: objects %s in %.2f s" % (world, a.objects, tm["objects_s"]))
         if a.ortho is not None and rank == 0:
             print("rank 0/%d: orthophoto %s in %.2f s" % (world, a.ortho, tm["ortho_s"]))
         if a.mesh is not None and rank == 0:

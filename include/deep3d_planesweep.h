@@ -891,6 +891,40 @@ int d3d_dtm_pull(const float* fine, int Wf, int Hf, float* coarse, d3d_stream_t 
 int d3d_dtm_push(const float* coarse, float* fine, int Wf, int Hf, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.36 -- the objects of an nDSM raster: connected components of its foreground, their statistics and the label
+ * raster.  The rule is this project's (deep3d_aerial_amd/objects.py states it in full); the reference has no such step.
+ * Every raster is [H,W] (device), W * H < 2^31 - 1; a cell's linear index is i * W + j.
+ *   d3d_objects_foreground: a cell is foreground when ndsm is finite and ndsm >= min_height (an IEEE compare; NaN is not).
+ *   mask (uint8, 0 / 1) and maskf (fp32, 0.0 / 1.0) get it; either may be null, not both.
+ *   d3d_objects_label: exactly one of ndsm (fp32, the predicate above) and mask (uint8, nonzero = foreground) is given.
+ *   connectivity 4 or 8.  parent [H,W] int32 gets -1 for background and, for a foreground cell, the smallest linear index of
+ *   its component (its root): a minimum, so it depends on no order of unions and no tile size.  Tiles of D3D_OBJECTS_TILE
+ *   cells square are labelled in LDS, the pairs across tile edges joined in parent by a lock-free find-and-atomicMin loop
+ *   bounded by strictly decreasing parents, one pass then sets every cell to its root.  counters (device, two int64, or null)
+ *   gets the number of hooks and of repeated passes of that loop.
+ *   scratch of d3d_objects_scratch_bytes(W, H) bytes (0 for an out-of-range size) holds the provisional ids between the next
+ *   three calls, which take the same scratch unchanged:
+ *   d3d_objects_roots: the roots in index order get the provisional ids 0 .. *n_roots - 1 (device int64).
+ *   d3d_objects_stats: acc [n_roots, D3D_OBJECTS_SLOTS] int64 per provisional id: cells, sum_i, sum_j, hsum, i0, i1, j0, j1, the
+ *   dsm_key of the largest ndsm; hsum sums q(h) = min(2^32 - 1, floor(fp64(h) * 1024 + 0.5)).  The entry point initialises acc.
+ *   d3d_objects_relabel: a component is kept when cells >= min_cells (>= 1); the kept ones get the ids 1 .. *n_kept in index
+ *   order; final_id [n_roots] int32 gets the number of kept components before each; label [H,W] int32 gets the id of the cell's
+ *   component, 0 for background and dropped components.
+ * Integer atomics only: every output is the same bits run to run.
+ */
+#define D3D_OBJECTS_TILE 64
+#define D3D_OBJECTS_SLOTS 9
+size_t d3d_objects_scratch_bytes(int W, int H);
+int d3d_objects_foreground(const float* ndsm, float min_height, unsigned char* mask, float* maskf, int W, int H, d3d_stream_t stream);
+int d3d_objects_label(const float* ndsm, float min_height, const unsigned char* mask, int connectivity, int* parent, int W, int H,
+                      long long* counters, d3d_stream_t stream);
+int d3d_objects_roots(const int* parent, int W, int H, void* scratch, size_t scratch_bytes, long long* n_roots, d3d_stream_t stream);
+int d3d_objects_stats(const float* ndsm, const int* parent, int W, int H, const void* scratch, size_t scratch_bytes, long long n_roots,
+                      long long* acc, d3d_stream_t stream);
+int d3d_objects_relabel(const int* parent, const long long* acc, long long n_roots, long long min_cells, int* final_id, int* label,
+                        int W, int H, void* scratch, size_t scratch_bytes, long long* n_kept, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.11 -- digital surface model from a triangle mesh: the reference's CREATEDSM step with dsm_source "mesh"
  * (run.py:226-232 calls mesh2dsm.DSM_from_Mesh, which the reference never shipped; the semantics are this project's,
  * deep3d_aerial_amd/dsm.py).  The raster is the one of d3d_dsm_from_points.
