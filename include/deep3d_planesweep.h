@@ -73,7 +73,9 @@ const char* d3d_last_error(void);
 /*
  * module.py:528-530 -- proj = matmul(src_proj, inverse(ref_proj)); rot, trans.
  * proj44: device [V,4,4] (index 0 = reference view).  out34: device [V-1,12].
- * The 4x4 inverse and product are evaluated in fp64 on the device and rounded once.
+ * The 4x4 inverse and product are evaluated in double-double on the device and rounded
+ * once: each entry is the fp32 value nearest to the exact composition of the fp32 inputs,
+ * also for world-frame cameras whose translations of 1e5 .. 1e8 cancel.
  */
 int d3d_compose_projections(const float* proj44, int n_views, float* out34, d3d_stream_t stream);
 

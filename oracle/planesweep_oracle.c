@@ -12,7 +12,8 @@
  * tests/golden/ (.npz files) (checked by tests/test_oracle_golden.py).
  *
  * Every function cites the reference lines (relative to the reference checkout,
- * mvs/mvs_cas/models/...) whose arithmetic it restates.  Plain scalar fp32 C; the
+ * mvs/mvs_cas/models/...) whose arithmetic it restates.  Plain scalar fp32 C (the
+ * projection composition alone is evaluated in binary128 and rounded once); the
  * only parallelism is an OpenMP "parallel for" over independent output elements,
  * which does not change any result.
  *
@@ -49,41 +50,50 @@ API void d3d_oracle_set_num_threads(int n) {
 
 /* ------------------------------------------------------------------------------------
  * module.py:528-530  proj = matmul(src_proj, inverse(ref_proj)); rot = proj[:3,:3];
- * trans = proj[:3,3:4].  fp32 Gauss-Jordan with partial pivoting stands in for
- * torch.inverse (LAPACK getrf/getri); differences are at fp32 rounding level and the
- * golden test for this function carries the tolerance.
+ * trans = proj[:3,3:4].  Gauss-Jordan with partial pivoting in binary128 (__float128,
+ * 113 bits), the product in binary128, one rounding to fp32: the value of the composition,
+ * not torch.inverse's fp32 arithmetic.  On a camera-frame reference view (K [I|0]) the two
+ * agree to fp32 rounding and the golden test for this function carries that tolerance; on a
+ * world-frame camera (translations of 1e5 .. 1e8 that cancel) fp32 arithmetic is off by
+ * 1e-3 .. 1 px and even fp64 misses an fp32 ulp on entries that are the remainder of a
+ * cancellation, so the checker computes the value (tests/test_camera_ref.py holds it to
+ * exact rational arithmetic).
  * out34: row-major 3x4 = [rot | trans].
  * Returns 0, or -1 if ref_proj is singular.
  * ---------------------------------------------------------------------------------- */
+typedef __float128 f128_t;
+
+static inline f128_t f128_abs(f128_t x) { return x < 0 ? -x : x; }
+
 API int d3d_oracle_compose_proj(const float* src44, const float* ref44, float* out34) {
-    float a[4][8];
+    f128_t a[4][8];
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) {
             a[i][j] = ref44[i * 4 + j];
-            a[i][4 + j] = (i == j) ? 1.0f : 0.0f;
+            a[i][4 + j] = (i == j) ? 1 : 0;
         }
     for (int col = 0; col < 4; ++col) {
         int piv = col;
-        float best = fabsf(a[col][col]);
+        f128_t best = f128_abs(a[col][col]);
         for (int r = col + 1; r < 4; ++r)
-            if (fabsf(a[r][col]) > best) { best = fabsf(a[r][col]); piv = r; }
-        if (best == 0.0f) return -1;
+            if (f128_abs(a[r][col]) > best) { best = f128_abs(a[r][col]); piv = r; }
+        if (best == 0) return -1;
         if (piv != col)
-            for (int j = 0; j < 8; ++j) { float t = a[col][j]; a[col][j] = a[piv][j]; a[piv][j] = t; }
-        float inv = 1.0f / a[col][col];
+            for (int j = 0; j < 8; ++j) { f128_t t = a[col][j]; a[col][j] = a[piv][j]; a[piv][j] = t; }
+        f128_t inv = 1 / a[col][col];
         for (int j = 0; j < 8; ++j) a[col][j] *= inv;
         for (int r = 0; r < 4; ++r) {
             if (r == col) continue;
-            float f = a[r][col];
-            if (f == 0.0f) continue;
+            f128_t f = a[r][col];
+            if (f == 0) continue;
             for (int j = 0; j < 8; ++j) a[r][j] -= f * a[col][j];
         }
     }
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 4; ++j) {
-            float s = 0.0f;
+            f128_t s = 0;
             for (int k = 0; k < 4; ++k) s += src44[i * 4 + k] * a[k][4 + j];
-            out34[i * 4 + j] = s;
+            out34[i * 4 + j] = (float)s;
         }
     return 0;
 }
