@@ -1,8 +1,10 @@
 """What the geometry stages (dsm, ortho, mesh, texture, fuse) share on the host: pointers, the stream, scratch buffers, record
 tables, view batches, the checks of a mesh's arrays and the camera of a view.  Internal: the stages re-export what callers use."""
+import contextlib
 import ctypes
 import math
 import os
+import time
 
 import numpy as np
 import torch
@@ -29,6 +31,22 @@ def scratch(lib_fn, *args, device):
 def records(struct_array, device):
     """A ctypes array of records in device memory (one host-to-device copy, ordered on the current stream)."""
     return torch.frombuffer(bytearray(bytes(struct_array)), dtype=torch.uint8).to(device)
+
+
+@contextlib.contextmanager
+def timed(timings, key, start=False, always=True):
+    """The seconds the block takes into timings[key], when timings (a dict) is given.  The device is synchronised when the block
+    ends, and with start=True before it begins as well; with always=False only when timings is given.  A block that raises is
+    neither synchronised nor timed."""
+    sync = always or timings is not None
+    if start and sync:
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    yield
+    if sync:
+        torch.cuda.synchronize()
+    if timings is not None:
+        timings[key] = time.perf_counter() - t0
 
 
 def is_real(x, above=None, at_least=None):
@@ -79,6 +97,31 @@ def check_views_per_batch(views_per_batch):
 def batches(views, views_per_batch):
     n = views_per_batch or max(len(views), 1)
     return [views[k:k + n] for k in range(0, len(views), n)]
+
+
+def check_tensor(t, name, dtype, shape, device, other):
+    """t is a contiguous tensor of `dtype` and `shape` on `device`, the device of `other` ("the height", "the mesh")."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous %s tensor of shape %s" % (name, dtype, shape))
+    if t.device != device:
+        raise RuntimeError("%s is on %s, %s on %s (no CPU fallback)" % (name, t.device, other, device))
+
+
+def check_raster(t, name, dtypes, cells, cells_text, runs):
+    """(H, W) of a device raster, checked: ValueError for a wrong shape or dtype or for W * H >= cells (cells_text: the bound as
+    the message gives it), the package's error for a CPU tensor; runs: what the stage does on the GPU, in its own words."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dim() != 2 or t.dtype not in dtypes or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("%s must be a non-empty [H,W] %s raster (got %s %s)"
+                         % (name, " or ".join(str(d).replace("torch.", "") for d in dtypes), tuple(t.shape), t.dtype))
+    if t.shape[0] * t.shape[1] >= cells:
+        raise ValueError("%s: %d x %d: W * H must stay below %s" % (name, t.shape[1], t.shape[0], cells_text))
+    if not t.is_cuda:
+        raise RuntimeError("%s is on %s: %s on the GPU (no CPU fallback)" % (name, t.device, runs))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    return int(t.shape[0]), int(t.shape[1])
 
 
 def mesh_arrays(vertices, faces, index_factor, what):

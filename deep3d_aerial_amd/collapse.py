@@ -58,6 +58,7 @@ import torch
 
 from . import _geom, _lib
 from ._geom import ptr as _ptr, stream as _stream
+from .mesh import _check_views, _decimate_arrays
 
 DEFAULT_TOLERANCE = 0.01
 DEFAULT_ROUNDS = 16
@@ -105,18 +106,6 @@ def check_collapse_settings(settings):
         raise ValueError("collapse depth_tolerance %r must be finite and >= 0" % (settings.get("depth_tolerance"),))
     return {"min_edge": min_edge, "max_edge": max_edge, "rounds": int(rounds), "depth_tolerance": tol,
             "views_per_batch": _geom.check_views_per_batch(settings.get("views_per_batch"))}
-
-
-def _mesh_arrays(vertices, faces):
-    from .mesh import _decimate_arrays
-
-    return _decimate_arrays(vertices, faces, "collapse")
-
-
-def _check_views(views, device):
-    from .mesh import _check_views as check
-
-    return check(views, device)
 
 
 def candidates(vertices, faces, csr, incidence, edges, n_edges, measure, min_edge, max_edge):
@@ -237,7 +226,7 @@ def collapse_round(vertices, faces, views, min_edge, max_edge, depth_tolerance=D
     face_index, edges [E,2], n_edges, measure [E], target [E,3], key [E] (-1: no candidate), claim [n], win [E], remap [n].  One
     device-to-host read after the checks of the input."""
     s = check_collapse_settings({"min_edge": min_edge, "max_edge": max_edge, "depth_tolerance": depth_tolerance, "views_per_batch": views_per_batch})
-    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    vertices, faces, n, m = _decimate_arrays(vertices, faces, "collapse")
     views = _check_views(views, vertices.device)
     return _round(vertices, faces, n, m, views, s, detail)
 
@@ -250,7 +239,7 @@ def collapse(vertices, faces, views, min_edge, max_edge=None, rounds=DEFAULT_ROU
     still had a winner, "faces_in", "faces_out", "vertices_out"}."""
     s = check_collapse_settings({"min_edge": min_edge, "max_edge": max_edge, "rounds": rounds, "depth_tolerance": depth_tolerance,
                                  "views_per_batch": views_per_batch})
-    v, f, n, m = _mesh_arrays(vertices, faces)
+    v, f, n, m = _decimate_arrays(vertices, faces, "collapse")
     views = _check_views(views, v.device)
     rec = {"edges": [], "short": [], "valid": [], "winners": [], "rounds": 0, "hit_max_rounds": False, "faces_in": m}
     won = False

@@ -124,6 +124,14 @@ class DsmGrid(object):
         return "DsmGrid(border=%s, unit=%s, size=(%d, %d))" % (self.border, self.unit, self.width, self.height)
 
 
+def check_grid(raster, grid, name):
+    """grid is a DsmGrid, and an [H,W] tensor `raster` (`name` in the message) has its shape."""
+    if not isinstance(grid, DsmGrid):
+        raise TypeError("grid must be a DsmGrid")
+    if isinstance(raster, torch.Tensor) and raster.dim() == 2 and tuple(raster.shape) != grid.shape:
+        raise ValueError("%s %s does not match the grid %d x %d" % (name, tuple(raster.shape), grid.height, grid.width))
+
+
 def fill_moving_average(height, radius=2, iterations=1):
     """MovingAverage hole fill of an [H,W] fp32 device raster (NaN = empty): `iterations` launches of
     d3d_dsm_fill_moving_average, ping-ponging two rasters.  Returns a new tensor; the input is not changed."""

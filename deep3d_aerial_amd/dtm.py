@@ -44,7 +44,7 @@ import torch
 
 from . import _geom, _lib
 from ._geom import ptr as _ptr, stream as _stream
-from .dsm import DsmGrid, read_dsm, write_dsm
+from .dsm import DsmGrid, check_grid, read_dsm, write_dsm
 
 MAX_RADIUS = _lib.CONSTANTS["D3D_DTM_MAX_RADIUS"]
 DEFAULTS = {"max_window": 40.0, "slope": 0.3, "dh0": 0.3, "dh_max": 2.5}   # choices, not measurements
@@ -92,18 +92,7 @@ def levels(grid, max_window=DEFAULTS["max_window"], slope=DEFAULTS["slope"], dh0
 
 
 def _raster(t, name):
-    """The checks of a device raster: ValueError for a wrong shape or dtype, the package's error for a CPU tensor."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if t.dim() != 2 or t.dtype != torch.float32 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError("%s must be a non-empty [H,W] float32 raster (got %s %s)" % (name, tuple(t.shape), t.dtype))
-    if t.shape[0] * t.shape[1] >= 1 << 31:
-        raise ValueError("%s: %d x %d: W * H must stay below 2^31" % (name, t.shape[1], t.shape[0]))
-    if not t.is_cuda:
-        raise RuntimeError("%s is on %s: the terrain filter runs on the GPU (no CPU fallback)" % (name, t.device))
-    if not t.is_contiguous():
-        raise ValueError("%s must be contiguous" % name)
-    return int(t.shape[0]), int(t.shape[1])
+    return _geom.check_raster(t, name, (torch.float32,), 1 << 31, "2^31", "the terrain filter runs")
 
 
 def _radius(rx, ry):
@@ -140,17 +129,10 @@ def open_(height, rx, ry):
     return _morph("d3d_dtm_open", height, rx, ry)
 
 
-def _grid_of(height, grid):
-    if not isinstance(grid, DsmGrid):
-        raise TypeError("grid must be a DsmGrid")
-    if isinstance(height, torch.Tensor) and height.dim() == 2 and tuple(height.shape) != grid.shape:
-        raise ValueError("height %s does not match the grid %d x %d" % (tuple(height.shape), grid.height, grid.width))
-
-
 def classify_ground(height, grid, max_window=DEFAULTS["max_window"], slope=DEFAULTS["slope"], dh0=DEFAULTS["dh0"],
                     dh_max=DEFAULTS["dh_max"]):
     """(level [H,W] uint8, s_K [H,W] fp32: the last surface) of the level loop; queued on the caller's stream."""
-    _grid_of(height, grid)
+    check_grid(height, grid, "height")
     table = levels(grid, max_window, slope, dh0, dh_max)   # before any launch
     H, W = _raster(height, "height")
     lib = _lib.load()

@@ -56,6 +56,7 @@ import torch
 
 from . import _lib
 from ._geom import ptr as _ptr, stream as _stream
+from .mesh import _decimate_arrays
 
 DEFAULT_ROUNDS = 16   # a setting, not a measurement
 MAX_ROUNDS = 64
@@ -89,12 +90,6 @@ def cos2(max_angle):
     """cos^2 of max_angle degrees in fp64, as rule 4 (3) takes it."""
     c = math.cos(math.radians(float(max_angle)))
     return c * c
-
-
-def _mesh_arrays(vertices, faces):
-    from .mesh import _decimate_arrays
-
-    return _decimate_arrays(vertices, faces, "flip")
 
 
 def topology(faces, n_vertices):
@@ -167,7 +162,7 @@ def flip_round(vertices, faces, max_angle, detail=None):
     "candidates", "winners"}.  detail (a dict) gets every pass's output: offset, nbr, fixed, face_offset, face_index, edges [E,2],
     n_edges, key [E] (-1: no candidate), opp [E,4], claim [n], win [E].  One device-to-host read after the checks of the input."""
     s = check_flip_settings({"max_angle": max_angle})
-    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    vertices, faces, n, m = _decimate_arrays(vertices, faces, "flip")
     return _round(vertices, faces, n, m, s, detail)
 
 
@@ -177,7 +172,7 @@ def flip_edges(vertices, faces, max_angle, rounds=DEFAULT_ROUNDS, info=None):
     (a dict) gets {"edges", "candidates", "winners": one number per round, "rounds": the rounds run, "hit_max_rounds": the last
     allowed round still had a winner, "faces": m, "flips": the winners of all rounds}."""
     s = check_flip_settings({"max_angle": max_angle, "rounds": rounds})
-    v, f, n, m = _mesh_arrays(vertices, faces)
+    v, f, n, m = _decimate_arrays(vertices, faces, "flip")
     rec = {"edges": [], "candidates": [], "winners": [], "rounds": 0, "hit_max_rounds": False, "faces": m}
     won = False
     for k in range(s["rounds"] if n and m else 0):

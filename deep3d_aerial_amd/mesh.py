@@ -996,12 +996,7 @@ def check_args(ap, a, prefix=""):
     try:
         s = settings_from_args(a, None, prefix)
         check_settings(MeshGrid(s["border"], s["voxel"]), s["trunc"], s["min_views"], s["conf_threshold"], s["views_per_batch"])
-        clean_settings(s)
-        close_holes_setting(s)
-        decimate_settings(s)
-        subdivide_settings(s)
-        collapse_settings(s)
-        flip_settings(s)
+        edit_settings(s)
     except ValueError as e:
         ap.error("--%s*: %s" % (prefix, e))
 
@@ -1015,80 +1010,68 @@ def _decimate_and_report(v, f, ratio, target_faces, max_rounds):
     return v, f
 
 
-def _collapse_and_report(v, f, views, s, timings=None):
-    import time
+def _clean_step(settings):
+    """clean()'s arguments when a clean step or the hole closing is on, else None."""
+    if clean_requested(settings) or close_holes_requested(settings):
+        return clean_settings(settings) + (close_holes_setting(settings),)
+    return None
 
-    from . import collapse as _collapse
 
-    if timings is not None:
-        torch.cuda.synchronize()
-    t0 = time.perf_counter()
+def _decimate_step(settings):
+    return decimate_settings(settings) if decimate_requested(settings) else None
+
+
+# The edit steps in the order they run: key, the function that checks its settings of a settings dict (None: the step is off),
+# whether it takes the views, what runs it -- a function of (vertices, faces, settings), or the (module, function) of a stage that
+# fills an info dict and has a summary_line --, that stage's label, its "nothing to ..." text and its timing key.
+EDIT_STEPS = (
+    ("clean", _clean_step, False, lambda v, f, s: clean(v, f, *s[:4], close_holes=s[4]), None, None, None),
+    ("decimate", _decimate_step, False, lambda v, f, s: _decimate_and_report(v, f, *s), None, None, None),
+    ("collapse", collapse_settings, True, ("collapse", "collapse"), "mesh collapse", "nothing to collapse", "mesh_collapse_s"),
+    ("flip", flip_settings, False, ("flip", "flip_edges"), "mesh flip", "nothing to flip", "mesh_flip_s"),
+    ("subdivide", subdivide_settings, True, ("subdivide", "subdivide"), "mesh subdivision", "nothing to split", "mesh_subdivide_s"),
+)
+
+
+def edit_settings(settings):
+    """Every edit step's settings of a settings dict, checked once: {key: what the step takes, or None when it is off}."""
+    return {step[0]: step[1](settings) for step in EDIT_STEPS}
+
+
+def _edit_and_report(v, f, views, s, step, timings=None):
+    import importlib
+
+    _, _, takes_views, (module, name), label, nothing, key = step
+    stage = importlib.import_module("." + module, __package__)
     info = {}
-    v, f = _collapse.collapse(v, f, views, info=info, **s)
-    if timings is not None:
-        torch.cuda.synchronize()
-        timings["mesh_collapse_s"] = time.perf_counter() - t0
-    print("mesh collapse: %s" % (_collapse.summary_line(info) or "nothing to collapse"))
+    with _geom.timed(timings, key, start=True, always=False):
+        v, f = getattr(stage, name)(v, f, *((views,) if takes_views else ()), info=info, **s)
+    print("%s: %s" % (label, stage.summary_line(info) or nothing))
     return v, f
 
 
-def _flip_and_report(v, f, s, timings=None):
-    import time
-
-    from . import flip as _flip
-
-    if timings is not None:
-        torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    info = {}
-    v, f = _flip.flip_edges(v, f, info=info, **s)
-    if timings is not None:
-        torch.cuda.synchronize()
-        timings["mesh_flip_s"] = time.perf_counter() - t0
-    print("mesh flip: %s" % (_flip.summary_line(info) or "nothing to flip"))
-    return v, f
-
-
-def _subdivide_and_report(v, f, views, s, timings=None):
-    import time
-
-    from . import subdivide as _subdivide
-
-    if timings is not None:
-        torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    info = {}
-    v, f = _subdivide.subdivide(v, f, views, info=info, **s)
-    if timings is not None:
-        torch.cuda.synchronize()
-        timings["mesh_subdivide_s"] = time.perf_counter() - t0
-    print("mesh subdivision: %s" % (_subdivide.summary_line(info) or "nothing to split"))
+def _edit(v, f, views, steps, timings=None):
+    """The edit steps that are on (steps: edit_settings' dict), in EDIT_STEPS' order: (vertices, faces)."""
+    for step in EDIT_STEPS:
+        s = steps[step[0]]
+        if s is not None:
+            v, f = step[3](v, f, s) if callable(step[3]) else _edit_and_report(v, f, views, s, step, timings)
     return v, f
 
 
 def build_and_write(views, settings, refine=None, timings=None):
-    """depth_to_mesh with the settings dict (settings_from_args), clean when a clean step is on (removal, hole closing, smoothing),
-    then decimate when it is on, then collapse the edges `views` cannot resolve when settings["collapse"] is present
-    (collapse.collapse; timings, a dict, then gets mesh_collapse_s), then flip the edges whose flip removes a cap triangle when
-    settings["flip"] is present (flip.flip_edges; timings then gets mesh_flip_s), then subdivide against `views` when
-    settings["subdivide"] is present (subdivide.subdivide; timings then gets mesh_subdivide_s), then vertices = refine(vertices, faces) when a refinement is handed in (refine.refine_mesh
-    bound to its views: pipeline.write_mesh_of), and write_ply to settings["path"]: (vertices, faces) as written."""
-    sub = subdivide_settings(settings)
-    col = collapse_settings(settings)
-    flp = flip_settings(settings)
+    """depth_to_mesh with the settings dict (settings_from_args), then the edit steps that are on, in EDIT_STEPS' order: clean when a
+    clean step is on (removal, hole closing, smoothing), decimate when it is on, collapse the edges `views` cannot resolve when
+    settings["collapse"] is present (collapse.collapse; timings, a dict, then gets mesh_collapse_s), flip the edges whose flip
+    removes a cap triangle when settings["flip"] is present (flip.flip_edges; timings then gets mesh_flip_s), subdivide against
+    `views` when settings["subdivide"] is present (subdivide.subdivide; timings then gets mesh_subdivide_s); then vertices =
+    refine(vertices, faces) when a refinement is handed in (refine.refine_mesh bound to its views: pipeline.write_mesh_of), and
+    write_ply to settings["path"]: (vertices, faces) as written."""
+    steps = edit_settings(settings)
     grid = MeshGrid(settings["border"], settings["voxel"])
     v, f = depth_to_mesh(views, grid, settings.get("trunc"), settings.get("min_views", DEFAULT_MIN_VIEWS),
                          settings.get("conf_threshold", DEFAULT_CONF), settings.get("views_per_batch"))
-    if clean_requested(settings) or close_holes_requested(settings):
-        v, f = clean(v, f, *clean_settings(settings), close_holes=close_holes_setting(settings))
-    if decimate_requested(settings):
-        v, f = _decimate_and_report(v, f, *decimate_settings(settings))
-    if col is not None:
-        v, f = _collapse_and_report(v, f, views, col, timings)
-    if flp is not None:
-        v, f = _flip_and_report(v, f, flp, timings)
-    if sub is not None:
-        v, f = _subdivide_and_report(v, f, views, sub, timings)
+    v, f = _edit(v, f, views, steps, timings)
     if refine is not None:
         v = refine(v, f)
     write_ply(settings["path"], v, f)
@@ -1105,31 +1088,24 @@ def main(argv=None):
     add_arguments(ap)
     a = ap.parse_args(argv)
     if a.clean is not None:
+        s = settings_from_args(a, a.out)
+        no_views = [step[0] for step in EDIT_STEPS if step[2] and s.pop(step[0], None) is not None]
         try:
-            check_clean_settings(a.min_faces, a.spurious, a.smooth, a.smooth_lambda)
-            check_close_holes_setting(a.close_holes)
-            check_decimate_settings(a.decimate, a.target_faces, a.decimate_max_rounds)
-            flp = flip_settings(settings_from_args(a, a.out))
+            steps = edit_settings(s)
         except ValueError as e:
             ap.error("--clean: %s" % e)
-        if a.collapse_min_edge is not None:
-            ap.error("--collapse needs the views of --mvs: --clean IN.ply has none (python -m deep3d_aerial_amd.collapse takes a mesh and "
-                     "an MVS folder)")
-        if a.subdivide_max_edge is not None:
-            ap.error("--subdivide needs the views of --mvs: --clean IN.ply has none (python -m deep3d_aerial_amd.subdivide takes a mesh and "
-                     "an MVS folder)")
+        for key in no_views:
+            ap.error("--%s needs the views of --mvs: --clean IN.ply has none (python -m deep3d_aerial_amd.%s takes a mesh and "
+                     "an MVS folder)" % (key, key))
     else:
         check_args(ap, a)
     if not torch.cuda.is_available():
         raise RuntimeError("the mesh is built on the GPU (no CPU fallback)")
     if a.clean is not None:
+        if steps["clean"] is None:   # with every clean step off the mesh that was read is still checked
+            steps["clean"] = clean_settings(s) + (close_holes_setting(s),)
         v, f = read_ply(a.clean)
-        v, f = clean(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), a.min_faces, a.spurious, a.smooth, a.smooth_lambda,
-                     close_holes=a.close_holes)
-        if a.decimate < 1 or a.target_faces > 0:
-            v, f = _decimate_and_report(v, f, a.decimate, a.target_faces, a.decimate_max_rounds)
-        if flp is not None:   # the flip needs no views
-            v, f = _flip_and_report(v, f, flp)
+        v, f = _edit(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), None, steps)   # the steps that need no views
         write_ply(a.out, v, f)
         print("mesh %s: %d vertices, %d triangles cleaned from %s" % (a.out, v.shape[0], f.shape[0], a.clean))
         return a.out

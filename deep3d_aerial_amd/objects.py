@@ -46,7 +46,7 @@ import torch
 
 from . import _geom, _lib
 from ._geom import ptr as _ptr, stream as _stream
-from .dsm import DsmGrid, read_dsm, write_dsm
+from .dsm import DsmGrid, check_grid, read_dsm, write_dsm
 
 TILE = _lib.CONSTANTS["D3D_OBJECTS_TILE"]
 SLOTS = _lib.CONSTANTS["D3D_OBJECTS_SLOTS"]
@@ -94,26 +94,7 @@ def open_radii(grid, open):
 
 
 def _raster(t, name, dtypes=(torch.float32,)):
-    """The checks of a device raster: ValueError for a wrong shape or dtype, the package's error for a CPU tensor."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if t.dim() != 2 or t.dtype not in dtypes or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError("%s must be a non-empty [H,W] %s raster (got %s %s)"
-                         % (name, " or ".join(str(d).replace("torch.", "") for d in dtypes), tuple(t.shape), t.dtype))
-    if t.shape[0] * t.shape[1] >= (1 << 31) - 1:
-        raise ValueError("%s: %d x %d: W * H must stay below 2^31 - 1" % (name, t.shape[1], t.shape[0]))
-    if not t.is_cuda:
-        raise RuntimeError("%s is on %s: the objects are segmented on the GPU (no CPU fallback)" % (name, t.device))
-    if not t.is_contiguous():
-        raise ValueError("%s must be contiguous" % name)
-    return int(t.shape[0]), int(t.shape[1])
-
-
-def _grid_of(ndsm, grid):
-    if not isinstance(grid, DsmGrid):
-        raise TypeError("grid must be a DsmGrid")
-    if isinstance(ndsm, torch.Tensor) and ndsm.dim() == 2 and tuple(ndsm.shape) != grid.shape:
-        raise ValueError("ndsm %s does not match the grid %d x %d" % (tuple(ndsm.shape), grid.height, grid.width))
+    return _geom.check_raster(t, name, dtypes, (1 << 31) - 1, "2^31 - 1", "the objects are segmented")
 
 
 def _opened(ndsm, min_height, radii):
@@ -128,7 +109,7 @@ def _opened(ndsm, min_height, radii):
 
 def foreground(ndsm, grid, min_height=DEFAULTS["min_height"], open=DEFAULTS["open"]):
     """The foreground of ndsm [H,W] fp32 on `grid` (module docstring) as an [H,W] uint8 device raster of 0 and 1."""
-    _grid_of(ndsm, grid)
+    check_grid(ndsm, grid, "ndsm")
     min_height, _, _, open = check_params(min_height=min_height, open=open)
     radii = open_radii(grid, open)   # before any launch
     H, W = _raster(ndsm, "ndsm")
@@ -185,7 +166,7 @@ def segment(ndsm, grid, min_height=DEFAULTS["min_height"], min_area=DEFAULTS["mi
     """ndsm [H,W] fp32 device raster on `grid` -> (label [H,W] int32 device raster, table: a dict of host arrays, one per
     column of COLUMNS).  CPU tensors are refused.  One host read of the number of components sizes the statistics; info (a
     dict) receives "components", "objects" and the border merge's "hooks" and "repeats"."""
-    _grid_of(ndsm, grid)
+    check_grid(ndsm, grid, "ndsm")
     min_height, min_area, connectivity, open = check_params(min_height, min_area, connectivity, open)
     need = min_cells(grid, min_area)
     radii = open_radii(grid, open)   # before any launch

@@ -118,10 +118,7 @@ def _check_height(height, grid):
 
 
 def _check_raster(t, name, dtype, shape, device):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-        raise ValueError("%s must be a contiguous %s tensor of shape %s" % (name, dtype, shape))
-    if t.device != device:
-        raise RuntimeError("%s is on %s, the height on %s (no CPU fallback)" % (name, t.device, device))
+    _geom.check_tensor(t, name, dtype, shape, device, "the height")
 
 
 def check_tolerance(depth_tolerance):

@@ -41,7 +41,9 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import fuse, predict, sharding
+from . import (cloud as _cloud, dsm as _dsm, dtm as _dtm, fuse, mesh as _mesh, objects as _objects, ortho as _ortho, ortho_mesh as _om,
+               predict, products, refine as _refine, sharding, texture as _tx)
+from ._geom import timed
 
 
 def view_records(dataset, fusion_num=10):
@@ -73,134 +75,23 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
     """Runs the three steps above for this rank.  Returns a list, one entry per reference view this rank owns, of
     {"ref", "final_mask" [H,W] bool, "avg_xyz_world" [3,H,W], "points": fuse.extract_points(...) dict} (device tensors).
     timings: dict that receives predict_s, allgather_ms (the collective alone, synchronised on both sides), fuse_s.
-    estimate_normals: the views' "normal" maps are estimated from their depth maps (ops.normals_from_depth, stencil step
-    normal_nei) -- what the reference's fusion reads from {view}_normal.pfm (fusion_3d_normal.py:437-443, 491-498) -- instead
-    of the default (0, 0, -1).  They are computed after the all-gather (the exchange is unchanged), from the unfiltered
-    gathered maps (the reference reads them from depth_path, not from its tmp folder), once per view this rank's fusion
-    touches; normals follow the view, so the fused arrays do not depend on the number of ranks any more than without them.
-    save_normals: predict_views also writes {name}_normal.pfm.
-    dsm: None (nothing changes), or the DSM settings {"path", "border", "unit", "size", "select", "trim", "min_points",
-    "interpolation", "radius", "iterations", "nodata"} (dsm.build_and_write): the xyz of every result of this rank are
-    concatenated, gathered on rank 0 (sharding.gather_points) and the DSM is built and written there; timings gets dsm_s.
-    With "source": "mesh" (needs mesh; select Max, min_points 1) rank 0 rasterises the mesh it has just built instead
-    (dsm.build_and_write_mesh): no point is gathered and there is no collective, so the file does not depend on the number of
-    ranks; timings gets dsm_s on rank 0.  Without "source" (or with "pc") nothing of the above changes.
-    ortho: None (nothing changes), or the orthophoto settings {"path", "depth_tolerance", "views_per_batch"} (needs dsm): the
-    true orthophoto on that DSM (write_ortho_of) from the views' gathered depth maps, cameras and reference images; rank 0
-    writes it; timings gets ortho_s.
-    mesh: None (nothing changes), or the mesh settings {"path", "border", "voxel", "trunc", "min_views", "conf_threshold",
-    "views_per_batch"} and optionally the clean steps {"min_faces", "spurious", "smooth", "smooth_lambda"}, the hole closing
-    {"close_holes": the longest boundary loop closed, 3 .. 1024, between the removal and the smoothing} and the decimation
-    {"decimate", "target_faces", "decimate_max_rounds"} (absent: off) (mesh.settings_from_args): rank 0 builds the mesh of every
-    gathered depth and confidence map with its camera, in global view order, cleans it when a clean step is on (mesh.clean),
-    decimates it when asked (mesh.decimate), and writes the PLY; the DSM from the mesh and the texture use that mesh.  The
-    other ranks do nothing (no collective: the file does not depend on the number of ranks); timings gets mesh_s on rank 0.
-    With mesh["refine"] (refine.check_refine_settings: {"step", ...}; absent: off) rank 0 refines the mesh against every view's
-    reference image before it writes the PLY (refine.refine_mesh, after the decimation): the other ranks' images reach it in one
-    gather (gather_refine_views), it refines alone, so the file still does not depend on the number of ranks; timings gets
-    mesh_refine_s (a part of mesh_s).
-    With mesh["subdivide"] ({"max_edge", "rounds", "depth_tolerance"}; absent: off) rank 0 subdivides the mesh against the depth
-    maps and cameras it already holds, after the decimation and before the refinement (subdivide.subdivide): no image and no
-    collective, so the file still does not depend on the number of ranks; timings gets mesh_subdivide_s (a part of mesh_s).  The
-    refinement, the DSM from the mesh and the texture then see the subdivided mesh.
-    With mesh["collapse"] ({"min_edge", "max_edge", "rounds", "depth_tolerance"}; absent: off) rank 0 collapses the edges those
-    views cannot resolve, after the decimation and before the subdivision (collapse.collapse), again alone and without an image:
-    the file does not depend on the number of ranks; timings gets mesh_collapse_s (a part of mesh_s), and the subdivision, the
-    refinement, the DSM from the mesh and the texture see the collapsed mesh.
-    With mesh["flip"] ({"max_angle", "rounds"}; absent: off) rank 0 flips the edges of the mesh it built whose flip removes a cap
-    triangle, after the collapse and before the subdivision (flip.flip_edges): no view, no image and no collective, so the file
-    does not depend on the number of ranks; timings gets mesh_flip_s (a part of mesh_s).
-    texture: None (nothing changes), or the texture settings {"path", "depth_tolerance", "views_per_batch", "page_size", "pad",
-    "level" (optional: None, or the seam levelling's settings), "local" (the local seam levelling's), "smooth_views" and
-    "outliers" (optional, likewise)}
-    (needs mesh; texture.settings_from_args): the mesh rank 0 wrote (after cleaning) textured from every rank's views and
-    reference images (write_texture_of); rank 0 writes the textured PLY and its pages; timings gets texture_s.
-    With texture["ortho"] ({"path", "border", "unit", "size", "z_down"}; absent or None: off) rank 0 then renders the textured mesh
-    top-down from the atlas, the mesh and the texcoords it holds (ortho_mesh.build_and_write) and writes the RGBA .tif and .tfw:
-    no new collective, so the file does not depend on the number of ranks; timings gets texture_ortho_s (a part of texture_s).
-    cloud: None (nothing changes: points["color"] stays None, no file, no collective), or the cloud settings {"path", "border",
-    "voxel", "min_points"} (cloud.check_settings): every reference view's crop colours its points (extract_points' ref_img, the
-    bytes / 255; a grey crop repeated to three channels; a crop of another size than the map is refused), each rank concatenates
-    the xyz, normal and colour of its results, one sharding.gather_points call moves them to rank 0 as one [n, 9] tensor (the
-    colours bit-cast), and rank 0 merges them on the voxel grid and writes the PLY (write_cloud_of); timings gets cloud_s.  With
-    filter_sources=False the file does not depend on the number of ranks.  The crops are the sweeping rank's, so with more than
-    one rank fuse_partition must be "views".  With cloud["outliers"] ({"radius", "k", "alpha", "min_neighbours"}; absent or None:
-    off) rank 0 filters the merged cloud before it writes it (cloud_outliers.filter_cloud, checked up front with the cloud
-    settings): no new collective; timings gets cloud_outliers, the filter's info.
-    dtm: None (nothing changes), or the terrain settings {"path", "ndsm", "ground", "max_window", "slope", "dh0", "dh_max"} (needs
-    dsm; dtm.check_settings): rank 0 filters the height raster the DSM step returned (either source, after any MovingAverage fill,
-    which is part of the DSM) and writes the DTM and, when asked, the nDSM and the level raster on the DSM's grid with its nodata
-    (write_dtm_of); no collective; timings gets dtm_s on rank 0.
-    objects: None (nothing changes), or the segmentation settings {"path", "table", "min_height", "min_area", "connectivity",
-    "open"} (needs dtm; objects.check_settings): rank 0 segments the nDSM the DTM step returned into objects and writes the label
-    raster and, when asked, the table on the DSM's grid with its nodata (write_objects_of); no collective; timings gets
-    objects_s on rank 0."""
-    if mesh is not None:
-        from . import mesh as _mesh
-
-        _grid = _mesh.MeshGrid(mesh["border"], mesh["voxel"])
-        _mesh.check_settings(_grid, mesh.get("trunc"), mesh.get("min_views", _mesh.DEFAULT_MIN_VIEWS),
-                             mesh.get("conf_threshold", _mesh.DEFAULT_CONF), mesh.get("views_per_batch"))
-        _mesh.clean_settings(mesh)
-        _mesh.close_holes_setting(mesh)
-        _mesh.decimate_settings(mesh)
-        _mesh.subdivide_settings(mesh)
-        _mesh.collapse_settings(mesh)
-        _mesh.flip_settings(mesh)
-        if mesh.get("refine") is not None:
-            from . import refine as _refine
-
-            _refine.check_refine_settings(mesh["refine"])
-    dsm_source = dsm.get("source", "pc") if dsm is not None else None
-    if dsm is not None:
-        from . import dsm as _dsm
-
-        if dsm_source not in _dsm.SOURCES:
-            raise ValueError("dsm source %r: 'pc' or 'mesh'" % (dsm_source,))
-        if dsm_source == "mesh":
-            if mesh is None:
-                raise ValueError("a DSM from the mesh needs mesh settings: the DSM is rasterised from the mesh")
-            _dsm.check_mesh_settings(dsm)
-    if dtm is not None:
-        from . import dtm as _dtm
-
-        if dsm is None:
-            raise ValueError("dtm needs dsm: the terrain is filtered from the DSM")
-        _dtm.check_settings(dtm)
-    if objects is not None:
-        from . import objects as _objects
-
-        if dtm is None:
-            raise ValueError("objects needs dtm: the objects are segmented from the nDSM the terrain step returns")
-        _objects.check_settings(objects)
-    if ortho is not None:
-        from . import ortho as _ortho
-
-        if dsm is None:
-            raise ValueError("ortho needs dsm: the orthophoto is draped on the DSM")
-        _ortho.check_tolerance(ortho.get("depth_tolerance", _ortho.DEFAULT_TOLERANCE))
-        _ortho.check_views_per_batch(ortho.get("views_per_batch"))
-    if texture is not None:
-        from . import texture as _texture
-
-        if mesh is None:
-            raise ValueError("texture needs mesh: the texture is laid on the mesh")
-        _texture.check_settings(texture)
-        if texture.get("level") is not None:
-            _texture.check_level_settings(texture["level"])
-        if texture.get("local") is not None:
-            _texture.check_local_settings(texture["local"])
-        if texture.get("ortho") is not None:
-            from . import ortho_mesh as _ortho_mesh
-
-            _ortho_mesh.check_settings(texture["ortho"])
-    if cloud is not None:
-        from . import cloud as _cloud
-
-        _cloud.check_settings(cloud)
-        if fuse_partition == "scene_blocks" and world_size > 1:
-            raise ValueError("cloud with fuse_partition='scene_blocks' on %d ranks: the colours come from the reference crops of the "
-                             "rank that swept the view (use fuse_partition='views')" % world_size)
+    estimate_normals, normal_nei: the views' normal maps are estimated from their depth maps (add_estimated_normals) instead of the
+    default (0, 0, -1).  save_normals: predict_views also writes {name}_normal.pfm.
+    The products (products.PRODUCTS, in the order they run) are each None (nothing changes: no file, no collective, no timing key) or
+    a settings dict; what one needs of another and every settings dict are checked before the model or the dataset is touched:
+    cloud:   the merged coloured point cloud (write_cloud_of); timings gets cloud_s.
+    mesh:    the surface mesh with its edit steps and refinement, on rank 0 (write_mesh_of, gather_refine_views); mesh_s there.
+    dsm:     the DSM of every rank's points (write_dsm_of) or, with "source": "mesh", of the mesh (write_mesh_dsm_of); dsm_s.
+    ortho:   the true orthophoto on that DSM (write_ortho_of); ortho_s.
+    dtm:     the terrain filtered from the DSM's raster, on rank 0 (write_dtm_of); dtm_s there.
+    objects: the objects of the terrain step's nDSM, on rank 0 (write_objects_of); objects_s there.
+    texture: the mesh textured from every rank's views, and its orthophoto (write_texture_of); texture_s."""
+    if dsm is not None and dsm.get("source", "pc") == "mesh" and mesh is None:
+        raise ValueError("a DSM from the mesh needs mesh settings: the DSM is rasterised from the mesh")
+    products.check({"cloud": cloud, "mesh": mesh, "dsm": dsm, "ortho": ortho, "dtm": dtm, "objects": objects, "texture": texture})
+    if cloud is not None and fuse_partition == "scene_blocks" and world_size > 1:
+        raise ValueError("cloud with fuse_partition='scene_blocks' on %d ranks: the colours come from the reference crops of the "
+                         "rank that swept the view (use fuse_partition='views')" % world_size)
     if checker is None:
         checker = fuse.ConsistencyChecker(1.0, 0.01, 90.0, 0.2)   # Fuse_Depth_Map's defaults (fusion_3d_normal.py:56-57)
     n = len(dataset)
@@ -288,23 +179,23 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
         timings.update(views=len(mine), predict_s=t1 - t0, allgather_ms=(g1 - g0) * 1e3,
                        allgather_bytes=int(all_maps.numel() * 4), fuse_s=t2 - g1, map_size=(H, W),
                        backend=dist.get_backend() if world_size > 1 else "none")
+    # this rank's [(id, K, E, depth, image)] in shard order: what the orthophoto and the texture take, and the refinement's images
+    own = [(images[recs[i]["name"]][0], all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], images[recs[i]["name"]][1])
+           for i in mine] if images is not None else None
     if cloud is not None:
         write_cloud_of(out, cloud, rank, world_size, device=all_maps.device, timings=timings)
     built_mesh = None
     refine_views = None
     if refine is not None:
-        own = [(images[recs[i]["name"]][0], images[recs[i]["name"]][1]) for i in mine]
-        refine_views = gather_refine_views(own, all_maps, all_cams, n, rank, world_size, partition)
+        refine_views = gather_refine_views([(v[0], v[4]) for v in own], all_maps, all_cams, n, rank, world_size, partition)
     if mesh is not None and rank == 0:
         built_mesh = write_mesh_of(all_maps, all_cams, mesh, timings=timings, refine_views=refine_views)
     if dsm is not None:
-        if dsm_source == "mesh":
+        if dsm.get("source", "pc") == "mesh":
             built = write_mesh_dsm_of(built_mesh, dsm, device=all_maps.device, timings=timings) if rank == 0 else None
         else:
             built = write_dsm_of(out, dsm, rank, world_size, xyz_device=all_maps.device, timings=timings)
         if ortho is not None:
-            own = [(images[recs[i]["name"]][0], all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], images[recs[i]["name"]][1])
-                   for i in mine]
             write_ortho_of(built[0] if built is not None else None, dsm, ortho, own, rank, world_size, device=all_maps.device,
                            timings=timings)
         if dtm is not None and rank == 0:
@@ -312,14 +203,18 @@ def predict_and_fuse(model, dataset, output_folder, rank=0, world_size=1, checke
             if objects is not None:
                 write_objects_of(terrain[2], dsm, objects, timings=timings)
     if texture is not None:
-        own = [(images[recs[i]["name"]][0], all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], images[recs[i]["name"]][1])
-               for i in mine]
         ids = {}
         for per in _gather_objects({i: images[recs[i]["name"]][0] for i in mine}, world_size):
             ids.update(per)
         cameras = [(ids[i], all_cams[i, 1, :3, :3], all_cams[i, 0], W, H) for i in range(n)]
         write_texture_of(built_mesh, texture, own, cameras, rank, world_size, device=all_maps.device, timings=timings)
     return out
+
+
+def dsm_grid(dsm_settings):
+    """(grid, nodata) of a dsm settings dict: the raster every product on the DSM is written on and the value of its empty cells."""
+    return (_dsm.DsmGrid(dsm_settings["border"], dsm_settings.get("unit") or (0.1, 0.1), dsm_settings.get("size")),
+            dsm_settings.get("nodata", -9999.0))
 
 
 def gather_refine_views(own, all_maps, all_cams, n_views, rank=0, world_size=1, partition="block"):
@@ -349,37 +244,39 @@ def gather_refine_views(own, all_maps, all_cams, n_views, rank=0, world_size=1, 
 
 def write_mesh_of(all_maps, all_cams, settings, timings=None, refine_views=None):
     """The mesh of every view (all_maps [n,2,H,W] depth and confidence, all_cams [n,2,4,4], by global view index), written to
-    settings["path"] (mesh.build_and_write: cleaned when a clean step is on, then decimated when asked, then, with
-    settings["collapse"], the edges the views cannot resolve collapsed: timings gets mesh_collapse_s, a part of mesh_s; then, with
-    settings["flip"], the edges flipped whose flip removes a cap triangle: timings gets mesh_flip_s, a part of mesh_s; then, with
-    settings["subdivide"] subdivided against the views: timings gets mesh_subdivide_s, a part of mesh_s; then, with
-    settings["refine"] (refine.check_refine_settings) and refine_views (gather_refine_views), refined against the images:
-    timings gets mesh_refine_s, a part of mesh_s).  Returns (vertices, faces) as written."""
-    from . import mesh as _mesh
+    settings["path"] on rank 0; the other ranks do nothing (no collective: the file does not depend on the number of ranks).
+    Returns (vertices, faces) as written: the DSM from the mesh and the texture use that mesh.  timings gets mesh_s.
+    settings: {"path", "border", "voxel", "trunc", "min_views", "conf_threshold", "views_per_batch"} and optionally the clean steps
+    {"min_faces", "spurious", "smooth", "smooth_lambda"}, the hole closing {"close_holes": the longest boundary loop closed, 3 ..
+    1024, between the removal and the smoothing} and the decimation {"decimate", "target_faces", "decimate_max_rounds"} (absent:
+    off) (mesh.settings_from_args).  mesh.build_and_write builds the mesh of every gathered depth and confidence map with its
+    camera, in global view order, and runs the edit steps that are on, in mesh.EDIT_STEPS' order, each on the mesh the one before
+    it left and each alone on rank 0, so the file never depends on the number of ranks:
+    the clean steps (mesh.clean) and the decimation (mesh.decimate);
+    with settings["collapse"] ({"min_edge", "max_edge", "rounds", "depth_tolerance"}; absent: off) the edges the views cannot resolve
+    are collapsed (collapse.collapse), against the depth maps and cameras rank 0 already holds, without an image: timings gets
+    mesh_collapse_s, a part of mesh_s;
+    with settings["flip"] ({"max_angle", "rounds"}; absent: off) the edges are flipped whose flip removes a cap triangle
+    (flip.flip_edges): no view, no image and no collective; timings gets mesh_flip_s, a part of mesh_s;
+    with settings["subdivide"] ({"max_edge", "rounds", "depth_tolerance"}; absent: off) the mesh is subdivided against the depth
+    maps and cameras (subdivide.subdivide): no image and no collective; timings gets mesh_subdivide_s, a part of mesh_s.
+    With settings["refine"] (refine.check_refine_settings: {"step", ...}; absent: off) rank 0 then refines the mesh against every
+    view's reference image before it writes the PLY (refine.refine_mesh): refine_views is gather_refine_views' list, the other
+    ranks' images having reached rank 0 in that one gather; timings gets mesh_refine_s, a part of mesh_s.  The refinement, the DSM
+    from the mesh and the texture see the mesh the edit steps left."""
+    with timed(timings, "mesh_s"):
+        views = [_mesh.MeshView(all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], all_maps[i, 1]) for i in range(all_maps.shape[0])]
+        refine = None
+        if settings.get("refine") is not None:
+            if refine_views is None:
+                raise ValueError("the mesh settings ask for a refinement: it needs the views' images (gather_refine_views)")
+            rs = _refine.check_refine_settings(settings["refine"])
+            ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in refine_views]
 
-    t0 = time.perf_counter()
-    views = [_mesh.MeshView(all_cams[i, 1, :3, :3], all_cams[i, 0], all_maps[i, 0], all_maps[i, 1]) for i in range(all_maps.shape[0])]
-    refine = None
-    if settings.get("refine") is not None:
-        from . import ortho as _ortho, refine as _refine
-
-        if refine_views is None:
-            raise ValueError("the mesh settings ask for a refinement: it needs the views' images (gather_refine_views)")
-        rs = _refine.check_refine_settings(settings["refine"])
-        ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in refine_views]
-
-        def refine(v, f):
-            torch.cuda.synchronize()
-            r0 = time.perf_counter()
-            out, _ = _refine.refine_mesh(v, f, ov, **rs)
-            torch.cuda.synchronize()
-            if timings is not None:
-                timings["mesh_refine_s"] = time.perf_counter() - r0
-            return out
-    res = _mesh.build_and_write(views, settings, refine=refine, timings=timings)
-    torch.cuda.synchronize()
-    if timings is not None:
-        timings["mesh_s"] = time.perf_counter() - t0
+            def refine(v, f):
+                with timed(timings, "mesh_refine_s", start=True):
+                    return _refine.refine_mesh(v, f, ov, **rs)[0]
+        res = _mesh.build_and_write(views, settings, refine=refine, timings=timings)
     return res
 
 
@@ -389,36 +286,32 @@ def write_ortho_of(height, dsm_settings, settings, views, rank=0, world_size=1, 
     Rank 0 broadcasts the raster; each rank selects over its own views (ortho.select_views); one all_reduce(MIN) of the keys;
     each rank colours its own winners; one all_reduce(SUM) of the packed RGBA raster and of id + 1 (0 where the rank has no
     winner: one rank contributes per cell).  The exchange is O(raster) whatever the number of views.
-    Returns (rgba, view, key) on rank 0, None elsewhere."""
-    from . import dsm as _dsm, ortho as _ortho
-
-    t0 = time.perf_counter()
-    grid = _dsm.DsmGrid(dsm_settings["border"], dsm_settings.get("unit") or (0.1, 0.1), dsm_settings.get("size"))
-    if rank == 0:
-        h = height.to(device=device, dtype=torch.float32).contiguous()
-    else:
-        h = torch.empty(grid.shape, dtype=torch.float32, device=device)
-    if world_size > 1:
-        sharding.broadcast_raster(h, 0)
-    ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in views]
-    tol = settings.get("depth_tolerance", _ortho.DEFAULT_TOLERANCE)
-    vpb = settings.get("views_per_batch")
-    key = _ortho.select_views(h, grid, ov, tol, views_per_batch=vpb)
-    if world_size > 1:
-        sharding.all_reduce_raster(key, dist.ReduceOp.MIN)
-    rgba, view = _ortho.colorize(key, h, grid, ov, views_per_batch=vpb)
-    if world_size > 1:
-        both = torch.stack([rgba.view(torch.int32)[:, :, 0], view + 1])
-        sharding.all_reduce_raster(both, dist.ReduceOp.SUM)
-        rgba = both[0].contiguous().view(torch.uint8).reshape(grid.height, grid.width, 4)
-        view = both[1] - 1
-    res = None
-    if rank == 0:
-        _ortho.write_ortho(settings["path"], rgba, grid)
-        res = (rgba, view, key)
-    torch.cuda.synchronize()
-    if timings is not None:
-        timings["ortho_s"] = time.perf_counter() - t0
+    settings: {"path", "depth_tolerance", "views_per_batch"}; the views carry the gathered depth maps, the cameras and the reference
+    images.  timings gets ortho_s.  Returns (rgba, view, key) on rank 0, None elsewhere."""
+    with timed(timings, "ortho_s"):
+        grid = dsm_grid(dsm_settings)[0]
+        if rank == 0:
+            h = height.to(device=device, dtype=torch.float32).contiguous()
+        else:
+            h = torch.empty(grid.shape, dtype=torch.float32, device=device)
+        if world_size > 1:
+            sharding.broadcast_raster(h, 0)
+        ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in views]
+        tol = settings.get("depth_tolerance", _ortho.DEFAULT_TOLERANCE)
+        vpb = settings.get("views_per_batch")
+        key = _ortho.select_views(h, grid, ov, tol, views_per_batch=vpb)
+        if world_size > 1:
+            sharding.all_reduce_raster(key, dist.ReduceOp.MIN)
+        rgba, view = _ortho.colorize(key, h, grid, ov, views_per_batch=vpb)
+        if world_size > 1:
+            both = torch.stack([rgba.view(torch.int32)[:, :, 0], view + 1])
+            sharding.all_reduce_raster(both, dist.ReduceOp.SUM)
+            rgba = both[0].contiguous().view(torch.uint8).reshape(grid.height, grid.width, 4)
+            view = both[1] - 1
+        res = None
+        if rank == 0:
+            _ortho.write_ortho(settings["path"], rgba, grid)
+            res = (rgba, view, key)
     return res
 
 
@@ -440,88 +333,82 @@ def write_texture_of(built_mesh, settings, views, cameras, rank=0, world_size=1,
     views (texture.face_colors); one all_reduce(SUM) of the colour words merges them (a slot belongs to one view, so to one rank,
     and the others hold 0 there); rank 0 rejects in place (texture.reject_outliers), then smooths or takes column 0, and lays
     out.  The result then has "rejected" and "outliers".
-    With settings["ortho"] rank 0 renders the orthophoto of the textured mesh after the texcoords (ortho_mesh.build_and_write);
-    the result then has "ortho" (ortho_mesh.summary's dict).
+    With settings["ortho"] ({"path", "border", "unit", "size", "z_down"}; absent or None: off) rank 0 renders the orthophoto of the
+    textured mesh after the texcoords, top-down from the atlas, the mesh and the texcoords it holds (ortho_mesh.build_and_write), and
+    writes the RGBA .tif and .tfw: no new collective, so the file does not depend on the number of ranks; the result then has
+    "ortho" (ortho_mesh.summary's dict) and timings gets texture_ortho_s (a part of texture_s).
+    settings: {"path", "depth_tolerance", "views_per_batch", "page_size", "pad", and optionally "level" (None, or the seam
+    levelling's settings), "local" (the local seam levelling's), "smooth_views", "outliers" and "ortho"} (texture.settings_from_args);
+    the mesh is the one rank 0 wrote, after its edit steps; rank 0 writes the textured PLY and its pages; timings gets texture_s.
     Returns texture.texture_mesh's dict on rank 0 (without "labels"), None elsewhere."""
-    from . import ortho as _ortho, texture as _tx
-
-    t0 = time.perf_counter()
-    tol, vpb, P, pad = _tx.check_settings(settings)
-    level = _tx.check_level_settings(settings["level"]) if settings.get("level") is not None else None
-    local = _tx.check_local_settings(settings["local"]) if settings.get("local") is not None else None
-    smooth = _tx.check_smooth_settings(settings["smooth_views"]) if settings.get("smooth_views") is not None else None
-    outliers = _tx.check_outlier_settings(settings["outliers"]) if settings.get("outliers") is not None else None
-    v = f = None
-    if rank == 0:
-        v = built_mesh[0].to(device=device, dtype=torch.float32).contiguous()
-        f = built_mesh[1].to(device=device, dtype=torch.int32).contiguous()
-    v = sharding.broadcast_rows(v, (3,), torch.float32, device)
-    f = sharding.broadcast_rows(f, (3,), torch.int32, device)
-    ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in views]
-    smoothed = {}
-    if smooth is None and outliers is None:
-        key = _tx.select_faces(v, f, ov, tol, views_per_batch=vpb)
+    with timed(timings, "texture_s"):
+        tol, vpb, P, pad = _tx.check_settings(settings)
+        level = _tx.check_level_settings(settings["level"]) if settings.get("level") is not None else None
+        local = _tx.check_local_settings(settings["local"]) if settings.get("local") is not None else None
+        smooth = _tx.check_smooth_settings(settings["smooth_views"]) if settings.get("smooth_views") is not None else None
+        outliers = _tx.check_outlier_settings(settings["outliers"]) if settings.get("outliers") is not None else None
+        v = f = None
+        if rank == 0:
+            v = built_mesh[0].to(device=device, dtype=torch.float32).contiguous()
+            f = built_mesh[1].to(device=device, dtype=torch.int32).contiguous()
+        v = sharding.broadcast_rows(v, (3,), torch.float32, device)
+        f = sharding.broadcast_rows(f, (3,), torch.int32, device)
+        ov = [_ortho.OrthoView(i, K, E, d, im) for i, K, E, d, im in views]
+        smoothed = {}
+        if smooth is None and outliers is None:
+            key = _tx.select_faces(v, f, ov, tol, views_per_batch=vpb)
+            if world_size > 1:
+                sharding.all_reduce_raster(key, dist.ReduceOp.MIN)
+        else:
+            cand = sharding.fold_on(_tx.face_candidates(v, f, ov, tol, views_per_batch=vpb), _tx.merge_candidates)
+            if outliers is not None:
+                if cand is None:
+                    cand = torch.empty((int(f.shape[0]), _tx.CANDIDATES), dtype=torch.int64, device=device)
+                sharding.broadcast_raster(cand, 0)
+                col = sharding.all_reduce_raster(_tx.face_colors(v, f, cand, ov, views_per_batch=vpb), dist.ReduceOp.SUM)
+                if rank == 0:
+                    cand, rejected, counts = _tx.reject_outliers(cand, col, outliers, out=cand)
+                    smoothed = {"rejected": rejected, "outliers": _tx.outlier_summary(counts, outliers, cand.shape[0])}
+                del col
+            if rank == 0 and smooth is not None:
+                key, label, commits = _tx.smooth_views(f, int(v.shape[0]), cand, *smooth)
+                before = _tx.charts(f, cand[:, 0].contiguous(), int(v.shape[0]))[1]
+                smoothed.update({"label": label, "smooth": _tx.smooth_summary(cand, label, commits, smooth[2], before.shape[0])})
+            elif rank == 0:
+                key = cand[:, 0].contiguous()
+            del cand
+        res = None
+        table = heights = None
+        if rank == 0:
+            cams = [_tx.Camera(*c) for c in cameras]
+            chart, _, rects, packing, table_np = _tx.layout(v, f, key, cams, P, pad)
+            table = torch.from_numpy(table_np).to(device)
+            heights = torch.tensor(packing.heights, dtype=torch.int64, device=device)
+            res = dict(smoothed, key=key, chart=chart, rects=rects, packing=packing, table=table_np)
+        table = sharding.broadcast_rows(table, (8,), torch.int32, device)
+        heights = sharding.broadcast_rows(heights, (), torch.int64, device)
+        table_np = table.cpu().numpy()
+        packing = res["packing"] if rank == 0 else _tx.Packing(table_np[:, [6, 4, 5]].astype(np.int64), heights.cpu().tolist(), P)
+        atlas = _tx.fill_pages(table_np, packing, ov, _tx.new_atlas(packing, device))
         if world_size > 1:
-            sharding.all_reduce_raster(key, dist.ReduceOp.MIN)
-    else:
-        cand = sharding.fold_on(_tx.face_candidates(v, f, ov, tol, views_per_batch=vpb), _tx.merge_candidates)
-        if outliers is not None:
-            if cand is None:
-                cand = torch.empty((int(f.shape[0]), _tx.CANDIDATES), dtype=torch.int64, device=device)
-            sharding.broadcast_raster(cand, 0)
-            col = sharding.all_reduce_raster(_tx.face_colors(v, f, cand, ov, views_per_batch=vpb), dist.ReduceOp.SUM)
-            if rank == 0:
-                cand, rejected, counts = _tx.reject_outliers(cand, col, outliers, out=cand)
-                smoothed = {"rejected": rejected, "outliers": _tx.outlier_summary(counts, outliers, cand.shape[0])}
-            del col
-        if rank == 0 and smooth is not None:
-            key, label, commits = _tx.smooth_views(f, int(v.shape[0]), cand, *smooth)
-            before = _tx.charts(f, cand[:, 0].contiguous(), int(v.shape[0]))[1]
-            smoothed.update({"label": label, "smooth": _tx.smooth_summary(cand, label, commits, smooth[2], before.shape[0])})
-        elif rank == 0:
-            key = cand[:, 0].contiguous()
-        del cand
-    res = None
-    table = heights = None
-    if rank == 0:
-        cams = [_tx.Camera(*c) for c in cameras]
-        chart, _, rects, packing, table_np = _tx.layout(v, f, key, cams, P, pad)
-        table = torch.from_numpy(table_np).to(device)
-        heights = torch.tensor(packing.heights, dtype=torch.int64, device=device)
-        res = dict(smoothed, key=key, chart=chart, rects=rects, packing=packing, table=table_np)
-    table = sharding.broadcast_rows(table, (8,), torch.int32, device)
-    heights = sharding.broadcast_rows(heights, (), torch.int64, device)
-    table_np = table.cpu().numpy()
-    packing = res["packing"] if rank == 0 else _tx.Packing(table_np[:, [6, 4, 5]].astype(np.int64), heights.cpu().tolist(), P)
-    atlas = _tx.fill_pages(table_np, packing, ov, _tx.new_atlas(packing, device))
-    if world_size > 1:
-        sharding.all_reduce_raster(atlas, dist.ReduceOp.SUM)
-    keep = {}   # what the local step reuses of the global one
-    if level is not None and rank == 0:   # the merged atlas, the mesh, keys, table and every camera are here: no new collective
-        res["level"] = _tx.level_pages(v, f, key, res["chart"], table_np, packing, cams, atlas, *level,
-                                       keep=keep if local is not None else None)
-    if local is not None and rank == 0:   # right after the global step, on the same atlas: no new collective either
-        res["local"] = _tx.local_pages(v, f, key, res["chart"], table_np, packing, cams, atlas, *local, cover=keep.get("cover"),
-                                       pairs=keep.get("pairs"))
-    del keep
-    _tx.finish_pages(atlas)
-    if rank == 0:
-        tc, tn = _tx.texcoords(v, f, key, res["chart"], table_np, packing, cams)
-        res.update(pages=_tx.split_pages(atlas, packing), texcoord=tc, texnumber=tn)
-        _tx.write_textured_ply(settings["path"], v, f, tc, tn, res["pages"])
-        if settings.get("ortho") is not None:   # the finished atlas, the mesh and the texcoords are here: no new collective
-            from . import ortho_mesh as _om
-
-            torch.cuda.synchronize()
-            o0 = time.perf_counter()
-            page_row = torch.from_numpy(packing.page_row).to(device)
-            res["ortho"] = _om.build_and_write(v, f, tc, tn, atlas, page_row, settings["ortho"])[2]
-            torch.cuda.synchronize()
-            if timings is not None:
-                timings["texture_ortho_s"] = time.perf_counter() - o0
-    torch.cuda.synchronize()
-    if timings is not None:
-        timings["texture_s"] = time.perf_counter() - t0
+            sharding.all_reduce_raster(atlas, dist.ReduceOp.SUM)
+        keep = {}   # what the local step reuses of the global one
+        if level is not None and rank == 0:   # the merged atlas, the mesh, keys, table and every camera are here: no new collective
+            res["level"] = _tx.level_pages(v, f, key, res["chart"], table_np, packing, cams, atlas, *level,
+                                           keep=keep if local is not None else None)
+        if local is not None and rank == 0:   # right after the global step, on the same atlas: no new collective either
+            res["local"] = _tx.local_pages(v, f, key, res["chart"], table_np, packing, cams, atlas, *local, cover=keep.get("cover"),
+                                           pairs=keep.get("pairs"))
+        del keep
+        _tx.finish_pages(atlas)
+        if rank == 0:
+            tc, tn = _tx.texcoords(v, f, key, res["chart"], table_np, packing, cams)
+            res.update(pages=_tx.split_pages(atlas, packing), texcoord=tc, texnumber=tn)
+            _tx.write_textured_ply(settings["path"], v, f, tc, tn, res["pages"])
+            if settings.get("ortho") is not None:   # the finished atlas, the mesh and the texcoords are here: no new collective
+                with timed(timings, "texture_ortho_s", start=True):
+                    page_row = torch.from_numpy(packing.page_row).to(device)
+                    res["ortho"] = _om.build_and_write(v, f, tc, tn, atlas, page_row, settings["ortho"])[2]
     return res
 
 
@@ -541,92 +428,89 @@ def reference_colors(image, H, W):
 def write_cloud_of(results, settings, rank=0, world_size=1, device="cuda", timings=None):
     """The merged cloud of the points of `results` (predict_and_fuse's list, with colours) over all ranks, written by rank 0
     (cloud.build_and_write).  Every rank must call it: one gather_points of [n, 9] int32 rows (the int32 colours, and xyz and the
-    normals bit-cast: no arithmetic touches them on the way).  Returns (cloud dict, summary) on rank 0, None elsewhere."""
-    from . import cloud as _cloud
-
-    t0 = time.perf_counter()
-    rows = []
-    for r in results:
-        p = r["points"]
-        if p["color"] is None or p["normal"] is None:
-            raise ValueError("the cloud needs the colours and normals of every result (%s has none)" % r["ref"])
-        rows.append(torch.cat([p["xyz"].view(torch.int32), p["normal"].view(torch.int32), p["color"]], 1))
-    local = torch.cat(rows) if rows else torch.zeros((0, 9), dtype=torch.int32, device=device)
-    pts = sharding.gather_points(local.contiguous(), rank, world_size)
-    res = None
-    if rank == 0:
-        res = _cloud.build_and_write(pts[:, 0:3].contiguous().view(torch.float32), pts[:, 3:6].contiguous().view(torch.float32),
-                                     pts[:, 6:9].contiguous(), settings)
-    torch.cuda.synchronize()
-    if timings is not None:
-        timings["cloud_s"] = time.perf_counter() - t0
-        if res is not None and "outliers" in res[1]:
-            timings["cloud_outliers"] = res[1]["outliers"]   # the filter's info, for the caller's report
+    normals bit-cast: no arithmetic touches them on the way).  Returns (cloud dict, summary) on rank 0, None elsewhere.
+    settings: {"path", "border", "voxel", "min_points"} (cloud.check_settings).  Every reference view's crop colours its points
+    (extract_points' ref_img, the bytes / 255; a grey crop repeated to three channels; a crop of another size than the map is
+    refused: reference_colors); without the cloud points["color"] stays None.  Each rank concatenates the xyz, normal and colour of
+    its results, the gather moves them to rank 0, and rank 0 merges them on the voxel grid and writes the PLY; timings gets cloud_s.
+    With filter_sources=False the file does not depend on the number of ranks.  The crops are the sweeping rank's, so with more than
+    one rank fuse_partition must be "views".  With settings["outliers"] ({"radius", "k", "alpha", "min_neighbours"}; absent or None:
+    off) rank 0 filters the merged cloud before it writes it (cloud_outliers.filter_cloud, checked up front with the cloud
+    settings): no new collective; timings gets cloud_outliers, the filter's info."""
+    with timed(timings, "cloud_s"):
+        rows = []
+        for r in results:
+            p = r["points"]
+            if p["color"] is None or p["normal"] is None:
+                raise ValueError("the cloud needs the colours and normals of every result (%s has none)" % r["ref"])
+            rows.append(torch.cat([p["xyz"].view(torch.int32), p["normal"].view(torch.int32), p["color"]], 1))
+        local = torch.cat(rows) if rows else torch.zeros((0, 9), dtype=torch.int32, device=device)
+        pts = sharding.gather_points(local.contiguous(), rank, world_size)
+        res = None
+        if rank == 0:
+            res = _cloud.build_and_write(pts[:, 0:3].contiguous().view(torch.float32), pts[:, 3:6].contiguous().view(torch.float32),
+                                         pts[:, 6:9].contiguous(), settings)
+    if timings is not None and res is not None and "outliers" in res[1]:
+        timings["cloud_outliers"] = res[1]["outliers"]   # the filter's info, for the caller's report
     return res
 
 
 def write_dsm_of(results, settings, rank=0, world_size=1, xyz_device="cuda", timings=None):
     """The DSM of the points of `results` (predict_and_fuse's list) over all ranks, written by rank 0 (dsm.build_and_write).
-    Every rank must call it.  Returns (height, count) on rank 0, None elsewhere."""
-    from . import dsm as _dsm
-
-    t0 = time.perf_counter()
-    parts = [r["points"]["xyz"] for r in results]
-    local = torch.cat(parts) if parts else torch.zeros((0, 3), dtype=torch.float32, device=xyz_device)
-    pts = sharding.gather_points(local.to(torch.float32).contiguous(), rank, world_size)
-    res = _dsm.build_and_write(pts, settings, device=local.device) if rank == 0 else None
-    torch.cuda.synchronize()
-    if timings is not None:
-        timings["dsm_s"] = time.perf_counter() - t0
+    Every rank must call it.  Returns (height, count) on rank 0, None elsewhere.
+    settings: {"path", "border", "unit", "size", "select", "trim", "min_points", "interpolation", "radius", "iterations", "nodata"}
+    (dsm.build_and_write), without "source" or with "source": "pc".  The xyz of every result of this rank are concatenated, gathered
+    on rank 0 (sharding.gather_points) and the DSM is built and written there; timings gets dsm_s."""
+    with timed(timings, "dsm_s"):
+        parts = [r["points"]["xyz"] for r in results]
+        local = torch.cat(parts) if parts else torch.zeros((0, 3), dtype=torch.float32, device=xyz_device)
+        pts = sharding.gather_points(local.to(torch.float32).contiguous(), rank, world_size)
+        res = _dsm.build_and_write(pts, settings, device=local.device) if rank == 0 else None
     return res
 
 
 def write_mesh_dsm_of(built_mesh, settings, device="cuda", timings=None):
     """Rank 0's DSM of the mesh write_mesh_of returned ((vertices, faces)), written there (dsm.build_and_write_mesh).
-    Returns (height, None): the shape of write_dsm_of's result, with no point count."""
-    from . import dsm as _dsm
-
-    t0 = time.perf_counter()
-    vertices, faces = built_mesh
-    h = _dsm.build_and_write_mesh(vertices, faces, settings, device=device)
-    torch.cuda.synchronize()
-    if timings is not None:
-        timings["dsm_s"] = time.perf_counter() - t0
+    Returns (height, None): the shape of write_dsm_of's result, with no point count.
+    settings: write_dsm_of's with "source": "mesh" (needs the mesh; select Max, min_points 1: dsm.check_mesh_settings).  No point
+    is gathered and there is no collective, so the file does not depend on the number of ranks; timings gets dsm_s on rank 0."""
+    with timed(timings, "dsm_s"):
+        vertices, faces = built_mesh
+        h = _dsm.build_and_write_mesh(vertices, faces, settings, device=device)
     return h, None
 
 
 def write_dtm_of(height, dsm_settings, settings, timings=None):
     """Rank 0's DTM of the height raster the DSM step returned, on the DSM's grid and with its nodata (dtm.build_and_write);
-    no collective.  Returns (dtm, level, ndsm)."""
-    from . import dsm as _dsm, dtm as _dtm
-
-    t0 = time.perf_counter()
-    grid = _dsm.DsmGrid(dsm_settings["border"], dsm_settings.get("unit") or (0.1, 0.1), dsm_settings.get("size"))
-    res = _dtm.build_and_write(height, grid, dict(settings, nodata=dsm_settings.get("nodata", -9999.0)))
-    torch.cuda.synchronize()
-    if timings is not None:
-        timings["dtm_s"] = time.perf_counter() - t0
+    no collective.  Returns (dtm, level, ndsm).
+    settings: {"path", "ndsm", "ground", "max_window", "slope", "dh0", "dh_max"} (dtm.check_settings).  The raster is the DSM's of
+    either source, after any MovingAverage fill, which is part of the DSM; rank 0 writes the DTM and, when asked, the nDSM and the
+    level raster; timings gets dtm_s on rank 0."""
+    with timed(timings, "dtm_s"):
+        grid, nodata = dsm_grid(dsm_settings)
+        res = _dtm.build_and_write(height, grid, dict(settings, nodata=nodata))
     return res
 
 
 def write_objects_of(ndsm, dsm_settings, settings, timings=None):
     """Rank 0's objects of the nDSM the DTM step returned, on the DSM's grid and with its nodata (objects.build_and_write); no
-    collective.  Returns (label, table)."""
-    from . import dsm as _dsm, objects as _objects
-
-    t0 = time.perf_counter()
-    grid = _dsm.DsmGrid(dsm_settings["border"], dsm_settings.get("unit") or (0.1, 0.1), dsm_settings.get("size"))
-    res = _objects.build_and_write(ndsm, grid, dict(settings, nodata=dsm_settings.get("nodata", -9999.0)))
-    torch.cuda.synchronize()
-    if timings is not None:
-        timings["objects_s"] = time.perf_counter() - t0
+    collective.  Returns (label, table).
+    settings: {"path", "table", "min_height", "min_area", "connectivity", "open"} (objects.check_settings).  Rank 0 writes the label
+    raster and, when asked, the table; timings gets objects_s on rank 0."""
+    with timed(timings, "objects_s"):
+        grid, nodata = dsm_grid(dsm_settings)
+        res = _objects.build_and_write(ndsm, grid, dict(settings, nodata=nodata))
     return res
 
 
 def add_estimated_normals(views, pairs, fusion_num=10, nei=1):
     """Sets views[name]["normal"] (ops.normals_from_depth of views[name]["depth"] with views[name]["K"]) for every view that
     fuse.fuse_block(views, pairs, fusion_num=...) reads -- each reference view and its first fusion_num listed sources that
-    exist -- and has none yet.  Call it before fuse_block: the source-filtering chain then never reaches the normals."""
+    exist -- and has none yet.  Call it before fuse_block: the source-filtering chain then never reaches the normals.
+    These are what the reference's fusion reads from {view}_normal.pfm (fusion_3d_normal.py:437-443, 491-498).  predict_and_fuse
+    computes them after the all-gather (the exchange is unchanged), from the unfiltered gathered maps (the reference reads them from
+    depth_path, not from its tmp folder), once per view this rank's fusion touches; normals follow the view, so the fused arrays do
+    not depend on the number of ranks any more than without them."""
     from . import ops
 
     for pair in pairs:

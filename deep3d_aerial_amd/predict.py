@@ -13,13 +13,15 @@ counterpart of datasets/cas_normal_eval.py; any iterable yielding the same sampl
 predict_views(), and SyntheticBlock provides one for plumbing tests.
 """
 import argparse
+import functools
 import os
 import sys
 
 import numpy as np
 import torch
 
-from . import sharding, synthetic
+from . import (cloud as _cloud, cloud_outliers as _outliers, dsm as _dsm, dtm as _dtm, mesh as _mesh, objects as _objects, ortho as _ortho,
+               ortho_mesh as _ortho_mesh, products, refine as _refine, sharding, synthetic, texture as _texture)
 
 
 # ----------------------------------------------------------------------------------------
@@ -559,107 +561,64 @@ def parse_args(argv=None):
                     help="with --fuse: estimate every fused view's normals from its gathered depth map instead of the default (0, 0, -1)")
     ap.add_argument("--normal_nei", type=int, default=1, help="stencil step of the normal estimate (compute_normals.py forward: 1)")
     # DSM from the fused points (run.py:209-247 CREATEDSM with dsm_source "pc"; deep3d_aerial_amd/dsm.py): off by default
-    from . import dsm as _dsm
-
     ap.add_argument("--dsm", default=None, help="with --fuse: write the DSM of all ranks' fused points to this .tif (+ .tfw), on rank 0")
     _dsm.add_arguments(ap, prefix="dsm_")
     ap.add_argument("--dsm_source", default="pc", choices=list(_dsm.SOURCES),
                     help="pc: the fused points; mesh: the surface mesh of --mesh (run.py:226-232 dsm_source)")
     # bare-earth terrain and object heights from the DSM (deep3d_aerial_amd/dtm.py): off by default
-    from . import dtm as _dtm
-
     ap.add_argument("--dtm", default=None, help="with --fuse --dsm: write the DTM filtered from the DSM to this .tif (+ .tfw), on rank 0")
     _dtm.add_arguments(ap, prefix="dtm_")
     # the objects of the nDSM (deep3d_aerial_amd/objects.py): off by default
-    from . import objects as _objects
-
     ap.add_argument("--objects", default=None,
                     help="with --fuse --dsm --dtm: write the label raster of the nDSM's objects to this .tif (+ .tfw), on rank 0")
     _objects.add_arguments(ap, prefix="objects_")
     # true orthophoto on the DSM (deep3d_aerial_amd/ortho.py): off by default
-    from . import ortho as _ortho
-
     ap.add_argument("--ortho", default=None, help="with --fuse --dsm: write the true orthophoto on the DSM to this .tif (+ .tfw), on rank 0")
     _ortho.add_arguments(ap, prefix="ortho_")
     # surface mesh from the gathered depth maps (deep3d_aerial_amd/mesh.py): off by default
-    from . import mesh as _mesh
-
     ap.add_argument("--mesh", default=None, help="with --fuse: write the surface mesh of all views' depth maps to this .ply, on rank 0")
     _mesh.add_arguments(ap, prefix="mesh_")
     # refinement of the mesh against the images (deep3d_aerial_amd/refine.py): off unless --mesh_refine STEP is given
-    from . import refine as _refine
-
     _refine.add_arguments(ap, prefix="mesh_refine_", step_flag="--mesh_refine")
     # texture of the mesh from the views (deep3d_aerial_amd/texture.py): off by default
-    from . import texture as _texture
-
     ap.add_argument("--texture", default=None,
                     help="with --fuse --mesh: write the mesh textured from the views to this .ply (+ <stem>_<k>.png pages), on rank 0")
     _texture.add_arguments(ap, prefix="texture_")
     # orthophoto of the textured mesh (deep3d_aerial_amd/ortho_mesh.py): off by default
-    from . import ortho_mesh as _ortho_mesh
-
     ap.add_argument("--texture_ortho", default=None,
                     help="with --texture: render the textured mesh top-down to this .tif (+ .tfw), on rank 0")
     _ortho_mesh.add_arguments(ap, prefix="texture_ortho_")
     # merged point cloud of the fused points (deep3d_aerial_amd/cloud.py): off by default
-    from . import cloud as _cloud
-
     ap.add_argument("--cloud", default=None,
                     help="with --fuse: merge all ranks' fused points on a voxel grid into this coloured .ply, on rank 0")
     _cloud.add_arguments(ap, prefix="cloud_")
     # outlier removal on the merged cloud (deep3d_aerial_amd/cloud_outliers.py): off unless --cloud_outlier_radius is given
-    from . import cloud_outliers as _outliers
-
     _outliers.add_arguments(ap, prefix="cloud_outlier_")
     a = ap.parse_args(argv)
-    if a.dsm is not None and not a.fuse:
-        ap.error("--dsm needs --fuse (the DSM is built from the fused points)")
+    products.check_args(ap, a)   # what every product and nested step needs, stated once (products.PRODUCTS)
     if a.dsm is not None and a.dsm_border is None:
         ap.error("--dsm needs --dsm_border Xmin,Xmax,Ymin,Ymax[,Zmin,Zmax]")
     if a.dtm is not None:
-        if a.dsm is None:
-            ap.error("--dtm needs --dsm (the terrain is filtered from the DSM)")
         _dtm.check_args(ap, a, a.dtm, prefix="dtm_", nodata=a.dsm_nodata)
     if a.objects is not None:
-        if a.dtm is None:
-            ap.error("--objects needs --dtm (the objects are segmented from the nDSM of the terrain step)")
         _objects.check_args(ap, a, a.objects, prefix="objects_", nodata=a.dsm_nodata)
-    if a.ortho is not None and not a.fuse:
-        ap.error("--ortho needs --fuse (the orthophoto is draped on the DSM of the fused points)")
-    if a.ortho is not None and a.dsm is None:
-        ap.error("--ortho needs --dsm (the orthophoto is draped on the DSM)")
     if a.ortho is not None:
         _ortho.check_args(ap, a, prefix="ortho_")
-    if a.mesh is not None and not a.fuse:
-        ap.error("--mesh needs --fuse (the mesh is built from the gathered depth maps of the fusion step)")
-    if a.mesh is not None and a.mesh_border is None:
-        ap.error("--mesh needs --mesh_border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax")
     if a.mesh is not None:
+        if a.mesh_border is None:
+            ap.error("--mesh needs --mesh_border Xmin,Xmax,Ymin,Ymax,Zmin,Zmax")
         _mesh.check_args(ap, a, prefix="mesh_")
-    if a.mesh_collapse_min_edge is not None and a.mesh is None:
-        ap.error("--mesh_collapse needs --mesh (it is the mesh whose edges are collapsed)")
-    if a.mesh_flip_max_angle is not None and a.mesh is None:
-        ap.error("--mesh_flip needs --mesh (it is the mesh whose edges are flipped)")
     if a.mesh_refine_step is not None:
-        if a.mesh is None:
-            ap.error("--mesh_refine needs --mesh (it is the mesh that is refined)")
         _refine.check_args(ap, a, prefix="mesh_refine_", step_flag="--mesh_refine")
     if a.dsm is not None and a.dsm_source == "mesh":
         if a.mesh is None:
             ap.error("--dsm_source mesh needs --mesh (the DSM is rasterised from the mesh)")
         _dsm.check_mesh_args(ap, a, prefix="dsm_")
-    if a.texture is not None and not a.fuse:
-        ap.error("--texture needs --fuse (the mesh is textured from the views of the fusion step)")
-    if a.texture is not None and a.mesh is None:
-        ap.error("--texture needs --mesh (the texture is laid on the mesh)")
     if a.texture is not None:
         if not a.texture.endswith(".ply"):
             ap.error("--texture must end in .ply")
         _texture.check_args(ap, a, prefix="texture_")
     if a.texture_ortho is not None:
-        if a.texture is None:
-            ap.error("--texture_ortho needs --texture (the orthophoto is rendered from the textured mesh)")
         if a.texture_ortho_border is None:   # the DSM's raster when there is one, else the mesh's footprint
             a.texture_ortho_border = list(a.dsm_border) if a.dsm_border is not None else list(a.mesh_border[:4])
         if a.texture_ortho_unit is None:
@@ -669,8 +628,6 @@ def parse_args(argv=None):
         except ValueError as e:
             ap.error("--texture_ortho*: %s" % e)
     if a.cloud is not None:
-        if not a.fuse:
-            ap.error("--cloud needs --fuse (the cloud is merged from the fused points)")
         if a.cloud_border is None:   # the mesh's box when there is one, else a DSM border with Z bounds
             if a.mesh_border is not None:
                 a.cloud_border = list(a.mesh_border)
@@ -688,8 +645,6 @@ def parse_args(argv=None):
             ap.error("--cloud*: %s" % e)
     if a.cloud_outlier_radius is None and _outliers.given(a, prefix="cloud_outlier_"):
         ap.error("--cloud_outlier_%s needs --cloud_outlier_radius (it turns the outlier removal on)" % _outliers.given(a, prefix="cloud_outlier_")[0])
-    if a.cloud_outlier_radius is not None and a.cloud is None:
-        ap.error("--cloud_outlier_radius needs --cloud (it is the merged cloud that is cleaned)")
     return a
 
 
@@ -716,59 +671,23 @@ def write_display_maps(output_folder, name, depth, prob):
     plt.imsave(os.path.join(output_folder, "color", "%s_prob.png" % name), np.nan_to_num(prob).clip(0, 1), format="png")
 
 
-def _dsm_settings(a):
-    from . import dsm as _dsm
-
-    s = _dsm.settings_from_args(a, a.dsm, prefix="dsm_")
-    if getattr(a, "dsm_source", "pc") != "pc":
+def _settings(name, a):
+    """The settings dict of product `name` (products.PRODUCTS) from its flags: --<name> is the path and --<name>_* the rest.  The
+    terrain and the objects are written with the DSM's nodata; a DSM from the mesh, the mesh refinement and the cloud's outlier
+    removal, when they are on, are keys of their product's dict."""
+    kw = {"nodata": a.dsm_nodata} if name in ("dtm", "objects") else {}
+    s = getattr(products, name).settings_from_args(a, getattr(a, name), prefix=name + "_", **kw)   # the stage's module has the product's name
+    if name == "dsm" and getattr(a, "dsm_source", "pc") != "pc":
         s["source"] = a.dsm_source
-    return s
-
-
-def _dtm_settings(a):
-    from . import dtm as _dtm
-
-    return _dtm.settings_from_args(a, a.dtm, prefix="dtm_", nodata=a.dsm_nodata)
-
-
-def _objects_settings(a):
-    from . import objects as _objects
-
-    return _objects.settings_from_args(a, a.objects, prefix="objects_", nodata=a.dsm_nodata)
-
-
-def _ortho_settings(a):
-    from . import ortho as _ortho
-
-    return _ortho.settings_from_args(a, a.ortho, prefix="ortho_")
-
-
-def _mesh_settings(a):
-    from . import mesh as _mesh
-
-    s = _mesh.settings_from_args(a, a.mesh, prefix="mesh_")
-    if getattr(a, "mesh_refine_step", None) is not None:
-        from . import refine as _refine
-
+    if name == "mesh" and getattr(a, "mesh_refine_step", None) is not None:
         s["refine"] = _refine.settings_from_args(a, prefix="mesh_refine_")
-    return s
-
-
-def _texture_settings(a):
-    from . import texture as _texture
-
-    return _texture.settings_from_args(a, a.texture, prefix="texture_")
-
-
-def _cloud_settings(a):
-    from . import cloud as _cloud
-
-    s = _cloud.settings_from_args(a, a.cloud, prefix="cloud_")
-    if getattr(a, "cloud_outlier_radius", None) is not None:
-        from . import cloud_outliers as _outliers
-
+    if name == "cloud" and getattr(a, "cloud_outlier_radius", None) is not None:
         s["outliers"] = _outliers.settings_from_args(a, prefix="cloud_outlier_")
     return s
+
+
+_cloud_settings, _mesh_settings, _dsm_settings, _ortho_settings, _dtm_settings, _objects_settings, _texture_settings = (
+    functools.partial(_settings, name) for name in products.NAMES)
 
 
 def main(argv=None):
@@ -818,41 +737,12 @@ def main(argv=None):
                                         partition=a.partition, feature_cache_bytes=cache_bytes, timings=tm, display=_truthy(a.display),
                                         fuse_partition=a.fuse_partition, scene_blocks=blocks, estimate_normals=a.fuse_normals,
                                         normal_nei=a.normal_nei, save_normals=a.save_normals,
-                                        dsm=_dsm_settings(a) if a.dsm is not None else None,
-                                        ortho=_ortho_settings(a) if a.ortho is not None else None,
-                                        mesh=_mesh_settings(a) if a.mesh is not None else None,
-                                        texture=_texture_settings(a) if a.texture is not None else None,
-                                        cloud=_cloud_settings(a) if a.cloud is not None else None,
-                                        dtm=_dtm_settings(a) if a.dtm is not None else None,
-                                        objects=_objects_settings(a) if a.objects is not None else None)
+                                        **{name: _settings(name, a) if getattr(a, name) is not None else None for name in products.NAMES})
         pipeline.save_fused(res, a.fusion_output or os.path.join(a.output_folder, "fused"))
-        if a.cloud is not None and rank == 0:
-            print("rank 0/%d: merged point cloud %s in %.2f s" % (world, a.cloud, tm["cloud_s"]))
-            if "cloud_outliers" in tm:
-                o = tm["cloud_outliers"]
-                print("rank 0/%d: cloud outliers: kept %d of %d points, dropped %d" % (world, o["kept"], o["points"], o["points"] - o["kept"]))
-        if a.dsm is not None and rank == 0:
-            print("rank 0/%d: DSM %s in %.2f s" % (world, a.dsm, tm["dsm_s"]))
-        if a.dtm is not None and rank == 0:
-            print("rank 0/%d: DTM %s in %.2f s" % (world, a.dtm, tm["dtm_s"]))
-        if a.objects is not None and rank == 0:
-            print("rank 0/%d: objects %s in %.2f s" % (world, a.objects, tm["objects_s"]))
-        if a.ortho is not None and rank == 0:
-            print("rank 0/%d: orthophoto %s in %.2f s" % (world, a.ortho, tm["ortho_s"]))
-        if a.mesh is not None and rank == 0:
-            print("rank 0/%d: mesh %s in %.2f s" % (world, a.mesh, tm["mesh_s"]))
-            if "mesh_collapse_s" in tm:
-                print("rank 0/%d: mesh edges the views cannot resolve collapsed in %.2f s" % (world, tm["mesh_collapse_s"]))
-            if "mesh_flip_s" in tm:
-                print("rank 0/%d: mesh edges flipped to remove cap triangles in %.2f s" % (world, tm["mesh_flip_s"]))
-            if "mesh_subdivide_s" in tm:
-                print("rank 0/%d: mesh subdivided against the views in %.2f s" % (world, tm["mesh_subdivide_s"]))
-            if "mesh_refine_s" in tm:
-                print("rank 0/%d: mesh refined against the images in %.2f s" % (world, tm["mesh_refine_s"]))
-        if a.texture is not None and rank == 0:
-            print("rank 0/%d: textured mesh %s in %.2f s" % (world, a.texture, tm["texture_s"]))
-            if a.texture_ortho is not None:
-                print("rank 0/%d: orthophoto of the textured mesh %s in %.2f s" % (world, a.texture_ortho, tm["texture_ortho_s"]))
+        # one line per product that is on, and one per part of it that left a key: cloud_s and cloud_outliers, dsm_s, dtm_s, objects_s,
+        # ortho_s, mesh_s with mesh_collapse_s, mesh_flip_s, mesh_subdivide_s and mesh_refine_s, texture_s with texture_ortho_s
+        for line in products.report_lines(a, tm, world) if rank == 0 else ():
+            print(line)
         print("rank %d/%d: %d views in %.2f s, all-gather of %.1f MB in %.2f ms (%s), fusion of its %d reference views %.2f s, "
               "%d vertices" % (rank, world, tm["views"], tm["predict_s"], tm["allgather_bytes"] / 1e6, tm["allgather_ms"], tm["backend"],
                                len(res), tm["fuse_s"], sum(int(r["points"]["xyz"].shape[0]) for r in res)))

@@ -65,6 +65,7 @@ import torch
 from . import _geom, _lib
 from ._geom import ptr as _ptr, stream as _stream
 from .ortho import DEFAULT_TOLERANCE, EMPTY_KEY, _batches, _check_views, check_tolerance, check_views_per_batch
+from .texture import _table
 
 VIEWS = 4   # keys per vertex of the view lists (csrc/mesh_refine.hip RF_VIEWS)
 MAX_REACH = 7
@@ -134,17 +135,8 @@ def _mesh_arrays(vertices, faces):
     return vertices, faces, n, m
 
 
-def _table(views, device):
-    from .texture import _table as table
-
-    return table(views, device)
-
-
 def _check(t, name, dtype, shape, device):
-    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
-        raise ValueError("%s must be a contiguous %s tensor of shape %s" % (name, dtype, shape))
-    if t.device != device:
-        raise RuntimeError("%s is on %s, the mesh on %s (no CPU fallback)" % (name, t.device, device))
+    _geom.check_tensor(t, name, dtype, shape, device, "the mesh")
 
 
 class Topology(object):

@@ -51,6 +51,7 @@ import torch
 
 from . import _geom, _lib
 from ._geom import batches as _batches, ptr as _ptr, stream as _stream
+from .mesh import _check_views, _decimate_arrays
 
 DEFAULT_TOLERANCE = 0.01
 DEFAULT_ROUNDS = 4
@@ -92,18 +93,6 @@ def check_sizes(n_vertices, splits, faces_out):
     if n_vertices + splits >= 1 << 31 or 6 * faces_out >= 1 << 31:
         raise ValueError("%d + %d vertices, %d faces after the split: more than int32 indexes (n + splits < 2^31, 6 faces < 2^31)"
                          % (n_vertices, splits, faces_out))
-
-
-def _mesh_arrays(vertices, faces):
-    from .mesh import _decimate_arrays
-
-    return _decimate_arrays(vertices, faces, "subdivision")
-
-
-def _check_views(views, device):
-    from .mesh import _check_views as check
-
-    return check(views, device)
 
 
 def edge_list(faces, n_vertices, csr=None):
@@ -166,7 +155,7 @@ def measure_edges(vertices, edges, n_edges, views, depth_tolerance=DEFAULT_TOLER
 def plan(vertices, faces, edges, n_edges, measure, max_edge):
     """Rules 4 and 5's counts, on the device: {"mark", "rank" [E] int32, "midpoint" [E,3] fp32, "face_edge" [m,3] int32,
     "child_count", "child_offset" [m] int32, "totals" [2] int64 (the split edges, the faces after the split)}.  No read."""
-    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    vertices, faces, n, m = _decimate_arrays(vertices, faces, "subdivision")
     _, _, emax = _check_edges(vertices, edges, n_edges)
     max_edge = check_subdivide_settings({"max_edge": max_edge})["max_edge"]
     dev = vertices.device
@@ -193,7 +182,7 @@ def plan(vertices, faces, edges, n_edges, measure, max_edge):
 
 def emit(vertices, faces, n_edges, p, splits, faces_out):
     """Rules 5 and 6 with plan's dict and its totals as the host read them: (vertices [n + splits, 3], faces [faces_out, 3])."""
-    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    vertices, faces, n, m = _decimate_arrays(vertices, faces, "subdivision")
     splits, faces_out = int(splits), int(faces_out)
     check_sizes(n, splits, faces_out)
     dev = vertices.device
@@ -210,7 +199,7 @@ def subdivide_round(vertices, faces, views, max_edge, depth_tolerance=DEFAULT_TO
     """One round (rules 2-6): (vertices, faces, record); with nothing to split the input tensors come back.  record: {"edges",
     "seen" (measure > 0), "split", "vertices_out", "faces_out", "longest_px"}.  detail (a dict) gets every pass's output: edges
     [E,2], n_edges, measure [E] and plan's arrays, cut to the edge count.  One device-to-host read."""
-    vertices, faces, n, m = _mesh_arrays(vertices, faces)
+    vertices, faces, n, m = _decimate_arrays(vertices, faces, "subdivision")
     if n == 0 or m == 0:
         return vertices, faces, {"edges": 0, "seen": 0, "split": 0, "vertices_out": n, "faces_out": m, "longest_px": 0.0}
     edges, n_edges = edge_list(faces, n)
@@ -236,7 +225,7 @@ def subdivide(vertices, faces, views, max_edge, rounds=DEFAULT_ROUNDS, depth_tol
     info (a dict) gets {"rounds": [subdivide_round's record per round], "stopped_early": a round split nothing, "vertices",
     "faces": the result's sizes}."""
     s = check_subdivide_settings({"max_edge": max_edge, "rounds": rounds, "depth_tolerance": depth_tolerance, "views_per_batch": views_per_batch})
-    v, f, n, m = _mesh_arrays(vertices, faces)
+    v, f, n, m = _decimate_arrays(vertices, faces, "subdivision")
     views = _check_views(views, v.device)
     per_round, early = [], False
     for _ in range(s["rounds"] if n and m else 0):

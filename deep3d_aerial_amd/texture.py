@@ -240,10 +240,7 @@ def _mesh_arrays(vertices, faces):
 
 
 def _check_key(key, m, device):
-    if not (isinstance(key, torch.Tensor) and key.dtype == torch.int64 and tuple(key.shape) == (m,) and key.is_contiguous()):
-        raise ValueError("key must be a contiguous int64 tensor of shape (%d,)" % m)
-    if key.device != device:
-        raise RuntimeError("key is on %s, the mesh on %s (no CPU fallback)" % (key.device, device))
+    _geom.check_tensor(key, "key", torch.int64, (m,), device, "the mesh")
 
 
 def check_page_size(page_size, views=()):

@@ -124,3 +124,33 @@ FUSION:
     s = mvs_dl.fusion_settings(cfg)
     assert (s["fusion_num"], s["min_geo_consist_num"], s["photometric_threshold"]) == (7, 3, 0.35)
     assert (s["position_threshold"], s["depth_threshold"], s["normal_threshold"]) == (0.5, 0.02, 30.0)
+
+
+def flags_dump(monkeypatch):
+    """predict.parse_args's parser, in order: every action's option strings, default (repr), type name, choices, nargs, required and
+    help, and the namespace (repr of each value) of parse_args(["--output_folder", "x"])."""
+    import argparse
+
+    seen = []
+    parse = argparse.ArgumentParser.parse_args
+    monkeypatch.setattr(argparse.ArgumentParser, "parse_args", lambda self, *a, **k: (seen.append(self), parse(self, *a, **k))[1])
+    ns = predict.parse_args(["--output_folder", "x"])
+    actions = [{"options": list(x.option_strings), "dest": x.dest, "default": repr(x.default), "type": getattr(x.type, "__name__", None),
+                "choices": None if x.choices is None else list(x.choices), "nargs": x.nargs, "required": bool(x.required), "help": x.help}
+               for x in seen[0]._actions]
+    return {"actions": actions, "namespace": {k: repr(v) for k, v in vars(ns).items()}}
+
+
+def test_the_flags_are_the_flags_of_the_committed_dump(monkeypatch):
+    """tests/golden/predict_flags.json is the dump of the parser before the products' flags and checks moved into one table."""
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "predict_flags.json")) as fh:
+        want = json.load(fh)
+    got = flags_dump(monkeypatch)
+    assert len(got["actions"]) == 130 and len(got["namespace"]) == 129
+    assert [x["options"] for x in got["actions"]] == [x["options"] for x in want["actions"]]
+    for g, w in zip(got["actions"], want["actions"]):
+        assert g == w, g["options"]
+    assert list(got["namespace"].items()) == list(want["namespace"].items())
