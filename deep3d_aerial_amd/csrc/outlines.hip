@@ -1,0 +1,339 @@
+// Outlines of a label raster: the boundary rings of every object as lattice vertices (the rule is
+// deep3d_aerial_amd/outlines.py's, this project's own: the reference has no such step).
+//
+// A cell with label L > 0 has one directed unit edge on every side whose neighbour is not L, the cell on its left; the edges are
+// numbered (slots) in (cell, side) order, every edge has one successor, and the edges fall into closed rings.  No kernel walks a
+// ring: the rings are ranked by pointer jumping, every step below is one lane per cell or per edge, and no loop waits for
+// another lane.
+//   count:  a wave takes 62 cells of a row with one halo cell either side: the neighbours in the row come by shuffle, the rows
+//           above and below from coalesced loads -- three loads a cell at most.  The cell's number of boundary sides is scanned
+//           (geom_scan) into its first slot; the total goes to device memory.
+//   edges:  one lane per cell reads its eight neighbours and writes, per boundary side, the successor's slot, the key
+//           cell * 4 + side (the head corner and the side in one word: cells < 2^29) and the start of the ranking state.  The
+//           successor's slot is its cell's first slot plus the boundary sides of that cell below the successor's side.
+//   rank:   round k: t = nx[e]; if m[t] < m[e] then (m[e], dm[e]) = (m[t], 2^k + dm[t]); nx[e] = nx[t].  Ping-pong buffers, one
+//           launch per round; a round that changes no m is the last.  The state is one 16-byte record per edge (m, dm, nx, 0):
+//           a jump is one 16-byte gather.  Built with -DD3D_OUTLINES_SPLIT it is three arrays in the same buffer
+//           (tools/outlines_bench.py --variant_library).
+//   rings:  m[e] == e flags the leaders; geom_scan of the flags numbers the rings in leader order.
+//   place:  a leader writes its ring's length 1 + dm[successor] and object; the lengths are scanned; every edge goes to
+//           ring start + (length - dm[e]) mod length with its corner flag (the successor has another side); the flags are scanned.
+//   emit:   a corner edge writes its head as a vertex; a ring's first vertex is the scanned flag at its first edge.
+// Atomics: an integer atomicOr by a wave that saw a negative label, or that changed an m and still read the round's word as clear.
+// No kernel uses scratch memory.
+#include "common.h"
+#include "geom_shared.h"
+
+namespace d3d {
+
+constexpr int OL_BLOCK = 256;
+constexpr int OL_WAVES = OL_BLOCK / 64;
+constexpr int OL_SPAN = 62;   // the cells of a row a wave of the count pass writes: its 64 lanes but a halo lane either side
+
+struct OlState {
+    int m, dm, nx;
+};
+
+// the state of edge e: a 16-byte record, or with D3D_OUTLINES_SPLIT the e-th entry of three arrays of E
+__device__ __forceinline__ OlState ol_load(const int* __restrict__ S, long e, long E) {
+    OlState s;
+#ifdef D3D_OUTLINES_SPLIT
+    s.m = S[e];
+    s.dm = S[E + e];
+    s.nx = S[2 * E + e];
+#else
+    const int4 v = reinterpret_cast<const int4*>(S)[e];
+    s.m = v.x;
+    s.dm = v.y;
+    s.nx = v.z;
+#endif
+    return s;
+}
+
+__device__ __forceinline__ void ol_store(int* __restrict__ S, long e, long E, const OlState& s) {
+#ifdef D3D_OUTLINES_SPLIT
+    S[e] = s.m;
+    S[E + e] = s.dm;
+    S[2 * E + e] = s.nx;
+#else
+    reinterpret_cast<int4*>(S)[e] = make_int4(s.m, s.dm, s.nx, 0);
+#endif
+}
+
+__device__ __forceinline__ int ol_at(const int* __restrict__ label, int i, int j, int W, int H) {
+    return i >= 0 && i < H && j >= 0 && j < W ? label[(long)i * W + j] : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// count
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(OL_BLOCK) void ol_count_kernel(const int* __restrict__ label, int W, int H, int nchunks, long long items,
+                                                            int* __restrict__ count, long long* __restrict__ counters) {
+    const int lane = (int)threadIdx.x & 63;
+    const long long item = (long long)blockIdx.x * OL_WAVES + ((int)threadIdx.x >> 6);
+    if (item >= items) return;   // the whole wave
+    const int y = (int)(item / nchunks), x = (int)(item % nchunks) * OL_SPAN - 1 + lane;
+    const bool in = x >= 0 && x < W;
+    const int L = in ? label[(long)y * W + x] : 0;
+    const int left = __shfl_up(L, 1, 64), right = __shfl_down(L, 1, 64);
+    if (in && lane >= 1 && lane <= OL_SPAN) {
+        int n = 0;
+        if (L > 0) {
+            const int up = y > 0 ? label[(long)(y - 1) * W + x] : 0;
+            const int down = y < H - 1 ? label[(long)(y + 1) * W + x] : 0;
+            n = (up != L) + (left != L) + (down != L) + (right != L);
+        }
+        count[(long)y * W + x] = n;
+    }
+    if (__ballot(L < 0) && lane == 0) atomicOr((unsigned long long*)counters + 1, 1ull);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// edges
+// ---------------------------------------------------------------------------------------------------------------------------
+// the boundary sides of cell (i, j), which holds L, below side `below`
+__device__ __forceinline__ int ol_sides_below(const int* __restrict__ label, int i, int j, int W, int H, int L, int below) {
+    int n = 0;
+    if (below > 0) n += ol_at(label, i - 1, j, W, H) != L;
+    if (below > 1) n += ol_at(label, i, j - 1, W, H) != L;
+    if (below > 2) n += ol_at(label, i + 1, j, W, H) != L;
+    return n;
+}
+
+// S: the side; (DI, DJ) its direction, (OI, OJ) the neighbour across it; la, ra: the cells ahead on the left and right hold L
+template <int S, int DI, int DJ, int OI, int OJ>
+__device__ __forceinline__ void ol_edge(const int* __restrict__ label, const int* __restrict__ offset, int conn8, int W, int H, int i, int j,
+                                        int L, unsigned mask, int base, bool la, bool ra, long E, int* __restrict__ succ,
+                                        int* __restrict__ key, int* __restrict__ state) {
+    if (!((mask >> S) & 1u)) return;
+    const long slot = (long)base + __popc(mask & ((1u << S) - 1u));
+    if (slot < 0 || slot >= E) return;   // never for the offsets of this raster: a guard on the stores
+    const bool right = conn8 ? ra : (la && ra), straight = conn8 ? (!ra && la) : (la && !ra);
+    int t;
+    if (right) {
+        const int ti = i + DI + OI, tj = j + DJ + OJ, ts = (S + 3) & 3;
+        t = offset[(long)ti * W + tj] + ol_sides_below(label, ti, tj, W, H, L, ts);
+    } else if (straight) {
+        const int ti = i + DI, tj = j + DJ;
+        t = offset[(long)ti * W + tj] + ol_sides_below(label, ti, tj, W, H, L, S);
+    } else {
+        const int ts = (S + 1) & 3;
+        t = base + __popc(mask & ((1u << ts) - 1u));
+    }
+    succ[slot] = t;
+    key[slot] = (i * W + j) * 4 + S;
+    OlState s;
+    s.m = (int)slot;
+    s.dm = 0;
+    s.nx = t;
+    ol_store(state, slot, E, s);
+}
+
+__global__ __launch_bounds__(OL_BLOCK) void ol_edges_kernel(const int* __restrict__ label, const int* __restrict__ offset, int conn8, int W,
+                                                            int H, int n, long E, int* __restrict__ succ, int* __restrict__ key,
+                                                            int* __restrict__ state) {
+    const long c = (long)blockIdx.x * OL_BLOCK + threadIdx.x;
+    if (c >= n) return;
+    const int L = label[c];
+    if (L <= 0) return;
+    const int i = (int)(c / W), j = (int)(c % W);
+    const bool ul = ol_at(label, i - 1, j - 1, W, H) == L, u = ol_at(label, i - 1, j, W, H) == L, ur = ol_at(label, i - 1, j + 1, W, H) == L;
+    const bool l = ol_at(label, i, j - 1, W, H) == L, r = ol_at(label, i, j + 1, W, H) == L;
+    const bool dl = ol_at(label, i + 1, j - 1, W, H) == L, d = ol_at(label, i + 1, j, W, H) == L, dr = ol_at(label, i + 1, j + 1, W, H) == L;
+    const unsigned mask = (u ? 0u : 1u) | (l ? 0u : 2u) | (d ? 0u : 4u) | (r ? 0u : 8u);
+    const int base = offset[c];
+    ol_edge<0, 0, -1, -1, 0>(label, offset, conn8, W, H, i, j, L, mask, base, l, ul, E, succ, key, state);
+    ol_edge<1, 1, 0, 0, -1>(label, offset, conn8, W, H, i, j, L, mask, base, d, dl, E, succ, key, state);
+    ol_edge<2, 0, 1, 1, 0>(label, offset, conn8, W, H, i, j, L, mask, base, r, dr, E, succ, key, state);
+    ol_edge<3, -1, 0, 0, 1>(label, offset, conn8, W, H, i, j, L, mask, base, u, ur, E, succ, key, state);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// rank
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(OL_BLOCK) void ol_rank_kernel(const int* __restrict__ in, int* __restrict__ out, long E, int step,
+                                                           int* __restrict__ changed) {
+    const long e = (long)blockIdx.x * OL_BLOCK + threadIdx.x;
+    bool ch = false;
+    if (e < E) {
+        OlState s = ol_load(in, e, E);
+        const long t = s.nx >= 0 && s.nx < E ? s.nx : e;   // always nx: a guard on the gather
+        const OlState o = ol_load(in, t, E);
+        if (o.m < s.m) {
+            s.m = o.m;
+            s.dm = step + o.dm;
+            ch = true;
+        }
+        s.nx = o.nx;
+        ol_store(out, e, E, s);
+    }
+    // one word for the whole launch: a wave sets it only while it reads as clear, so the atomics on it stay few (with one
+    // per wave that changed an m, a round of 10^8 edges spent nine tenths of its time on them)
+    if (__ballot(ch) && (threadIdx.x & 63) == 0 && __hip_atomic_load(changed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+        atomicOr(changed, 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// rings, place, emit
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(OL_BLOCK) void ol_leader_kernel(const int* __restrict__ state, long E, int* __restrict__ flag) {
+    const long e = (long)blockIdx.x * OL_BLOCK + threadIdx.x;
+    if (e < E) flag[e] = ol_load(state, e, E).m == e ? 1 : 0;
+}
+
+__device__ __forceinline__ long ol_guard(long v, long n) { return v >= 0 && v < n ? v : 0; }
+
+__global__ __launch_bounds__(OL_BLOCK) void ol_ring_kernel(const int* __restrict__ label, int n, const int* __restrict__ state,
+                                                           const int* __restrict__ succ, const int* __restrict__ key,
+                                                           const int* __restrict__ ring_id, long E, long R, int* __restrict__ ring_len,
+                                                           int* __restrict__ ring_object) {
+    const long e = (long)blockIdx.x * OL_BLOCK + threadIdx.x;
+    if (e >= E || ol_load(state, e, E).m != e) return;
+    const long r = ring_id[e];
+    if (r < 0 || r >= R) return;   // never: a guard on the stores
+    ring_len[r] = 1 + ol_load(state, ol_guard(succ[e], E), E).dm;
+    ring_object[r] = label[ol_guard(key[e] >> 2, n)];
+}
+
+__global__ __launch_bounds__(OL_BLOCK) void ol_place_kernel(const int* __restrict__ state, const int* __restrict__ succ,
+                                                            const int* __restrict__ key, const int* __restrict__ ring_id,
+                                                            const int* __restrict__ ring_len, const int* __restrict__ ring_edge, long E,
+                                                            long R, unsigned* __restrict__ okey, int* __restrict__ corner) {
+    const long e = (long)blockIdx.x * OL_BLOCK + threadIdx.x;
+    if (e >= E) return;
+    const OlState s = ol_load(state, e, E);
+    const long r = ol_guard(ring_id[ol_guard(s.m, E)], R);
+    const int len = ring_len[r];
+    const long p = (long)ring_edge[r] + (s.dm == 0 ? 0 : len - s.dm);
+    if (p < 0 || p >= E) return;   // never: a guard on the stores
+    const int k = key[e];
+    const unsigned c = (key[ol_guard(succ[e], E)] & 3) != (k & 3) ? 1u : 0u;
+    okey[p] = (unsigned)k | (c << 31);
+    corner[p] = (int)c;
+}
+
+__global__ __launch_bounds__(OL_BLOCK) void ol_emit_kernel(const unsigned* __restrict__ okey, const int* __restrict__ cpos,
+                                                           const int* __restrict__ ring_edge, long E, long R, long V, int W,
+                                                           int* __restrict__ vertices, int* __restrict__ ring_start) {
+    const long p = (long)blockIdx.x * OL_BLOCK + threadIdx.x;
+    if (p >= E) return;
+    if (p < R) ring_start[p] = cpos[ol_guard(ring_edge[p], E)];   // R <= E / 4
+    if (p == R) ring_start[R] = (int)V;
+    const unsigned k = okey[p];
+    if (!(k >> 31)) return;
+    const long v = cpos[p];
+    if (v < 0 || v >= V) return;   // never: a guard on the stores
+    const int c = (int)((k & 0x7fffffffu) >> 2), s = (int)(k & 3u);
+    vertices[2 * v] = c / W + (s == 1 || s == 2 ? 1 : 0);
+    vertices[2 * v + 1] = c % W + (s >= 2 ? 1 : 0);
+}
+
+static bool ol_dims_ok(int W, int H) { return W >= 1 && H >= 1 && (long long)W * H <= D3D_OUTLINES_MAX_CELLS; }
+
+static size_t ol_scratch(int W, int H) { return geom_scan_bytes(4ll * W * H); }
+
+static unsigned ol_blocks(long long n) { return (unsigned)((n + OL_BLOCK - 1) / OL_BLOCK); }
+
+}  // namespace d3d
+
+using namespace d3d;
+
+#define OL_DIMS(name) \
+    D3D_REQUIRE(ol_dims_ok(W, H), "%s: raster %d x %d: size must be >= 1 and W * H <= 2^29 - 1", name, W, H)
+#define OL_SCRATCH(name)                                                                                                             \
+    D3D_REQUIRE(scratch_bytes >= ol_scratch(W, H), "%s: scratch of %zu bytes, %zu needed (d3d_outlines_scratch_bytes)", name, scratch_bytes, \
+                ol_scratch(W, H))
+#define OL_EDGES(name) \
+    D3D_REQUIRE(n_edges >= 1 && n_edges <= 4ll * W * H, "%s: n_edges %lld outside 1..4 W H", name, n_edges)
+
+extern "C" size_t d3d_outlines_scratch_bytes(int W, int H) { return ol_dims_ok(W, H) ? ol_scratch(W, H) : 0; }
+
+extern "C" int d3d_outlines_count(const int* label, int W, int H, int* offset, void* scratch, size_t scratch_bytes, long long* counters,
+                                  d3d_stream_t stream) {
+    D3D_REQUIRE(label && offset && scratch && counters, "d3d_outlines_count: null pointer (label, offset, scratch, counters)");
+    OL_DIMS("d3d_outlines_count");
+    OL_SCRATCH("d3d_outlines_count");
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = hip_status(hipMemsetAsync(counters, 0, 16, st), "outlines: clear counters");
+    if (rc != D3D_OK) return rc;
+    const int nchunks = ceil_div(W, OL_SPAN);
+    const long long items = (long long)H * nchunks;
+    hipLaunchKernelGGL(ol_count_kernel, dim3((unsigned)((items + OL_WAVES - 1) / OL_WAVES)), dim3(OL_BLOCK), 0, st, label, W, H, nchunks, items,
+                       offset, counters);
+    D3D_LAUNCH_CHECK("ol_count_kernel launch");
+    return geom_scan(offset, offset, (long long)W * H, scratch, counters, st);
+}
+
+extern "C" int d3d_outlines_edges(const int* label, const int* offset, int connectivity, int W, int H, long long n_edges, int* succ,
+                                  int* key, int* state, d3d_stream_t stream) {
+    D3D_REQUIRE(label && offset && succ && key && state, "d3d_outlines_edges: null pointer (label, offset, succ, key, state)");
+    OL_DIMS("d3d_outlines_edges");
+    D3D_REQUIRE(connectivity == 4 || connectivity == 8, "d3d_outlines_edges: connectivity %d is neither 4 nor 8", connectivity);
+    OL_EDGES("d3d_outlines_edges");
+    const int n = W * H;
+    hipLaunchKernelGGL(ol_edges_kernel, dim3(ol_blocks(n)), dim3(OL_BLOCK), 0, (hipStream_t)stream, label, offset, connectivity == 8 ? 1 : 0, W,
+                       H, n, (long)n_edges, succ, key, state);
+    D3D_LAUNCH_CHECK("ol_edges_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_outlines_rank(const int* state_in, int* state_out, long long n_edges, int round, int* changed, d3d_stream_t stream) {
+    D3D_REQUIRE(state_in && state_out && changed, "d3d_outlines_rank: null pointer (state_in, state_out, changed)");
+    D3D_REQUIRE(n_edges >= 1 && n_edges < (1ll << 31), "d3d_outlines_rank: n_edges %lld outside 1..2^31 - 1", n_edges);
+    D3D_REQUIRE(round >= 0 && round <= 30, "d3d_outlines_rank: round %d outside 0..30", round);
+    D3D_REQUIRE(state_in != state_out, "d3d_outlines_rank: state_out must not alias state_in");
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = hip_status(hipMemsetAsync(changed, 0, 4, st), "outlines: clear changed");
+    if (rc != D3D_OK) return rc;
+    hipLaunchKernelGGL(ol_rank_kernel, dim3(ol_blocks(n_edges)), dim3(OL_BLOCK), 0, st, state_in, state_out, (long)n_edges, 1 << round, changed);
+    D3D_LAUNCH_CHECK("ol_rank_kernel launch");
+    return D3D_OK;
+}
+
+extern "C" int d3d_outlines_rings(const int* state, int W, int H, long long n_edges, int* ring_id, void* scratch, size_t scratch_bytes,
+                                  long long* n_rings, d3d_stream_t stream) {
+    D3D_REQUIRE(state && ring_id && scratch && n_rings, "d3d_outlines_rings: null pointer (state, ring_id, scratch, n_rings)");
+    OL_DIMS("d3d_outlines_rings");
+    OL_EDGES("d3d_outlines_rings");
+    OL_SCRATCH("d3d_outlines_rings");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ol_leader_kernel, dim3(ol_blocks(n_edges)), dim3(OL_BLOCK), 0, st, state, (long)n_edges, ring_id);
+    D3D_LAUNCH_CHECK("ol_leader_kernel launch");
+    return geom_scan(ring_id, ring_id, n_edges, scratch, n_rings, st);
+}
+
+extern "C" int d3d_outlines_place(const int* label, int W, int H, const int* state, const int* succ, const int* key, const int* ring_id,
+                                  long long n_edges, long long n_rings, int* ring_len, int* ring_edge, int* ring_object,
+                                  unsigned* ordered, int* corner, void* scratch, size_t scratch_bytes, long long* n_vertices,
+                                  d3d_stream_t stream) {
+    D3D_REQUIRE(label && state && succ && key && ring_id && ring_len && ring_edge && ring_object && ordered && corner && scratch && n_vertices,
+                "d3d_outlines_place: null pointer");
+    OL_DIMS("d3d_outlines_place");
+    OL_EDGES("d3d_outlines_place");
+    D3D_REQUIRE(n_rings >= 1 && n_rings <= n_edges / 4, "d3d_outlines_place: n_rings %lld outside 1..n_edges / 4", n_rings);
+    OL_SCRATCH("d3d_outlines_place");
+    hipStream_t st = (hipStream_t)stream;
+    const long E = (long)n_edges, R = (long)n_rings;
+    hipLaunchKernelGGL(ol_ring_kernel, dim3(ol_blocks(E)), dim3(OL_BLOCK), 0, st, label, W * H, state, succ, key, ring_id, E, R, ring_len,
+                       ring_object);
+    D3D_LAUNCH_CHECK("ol_ring_kernel launch");
+    int rc = geom_scan(ring_len, ring_edge, R, scratch, nullptr, st);
+    if (rc != D3D_OK) return rc;
+    hipLaunchKernelGGL(ol_place_kernel, dim3(ol_blocks(E)), dim3(OL_BLOCK), 0, st, state, succ, key, ring_id, ring_len, ring_edge, E, R, ordered,
+                       corner);
+    D3D_LAUNCH_CHECK("ol_place_kernel launch");
+    return geom_scan(corner, corner, E, scratch, n_vertices, st);
+}
+
+extern "C" int d3d_outlines_emit(const unsigned* ordered, const int* corner, const int* ring_edge, int W, int H, long long n_edges,
+                                 long long n_rings, long long n_vertices, int* vertices, int* ring_start, d3d_stream_t stream) {
+    D3D_REQUIRE(ordered && corner && ring_edge && vertices && ring_start, "d3d_outlines_emit: null pointer (ordered, corner, ring_edge, vertices, ring_start)");
+    OL_DIMS("d3d_outlines_emit");
+    OL_EDGES("d3d_outlines_emit");
+    D3D_REQUIRE(n_rings >= 1 && n_rings <= n_edges / 4, "d3d_outlines_emit: n_rings %lld outside 1..n_edges / 4", n_rings);
+    D3D_REQUIRE(n_vertices >= 4 * n_rings && n_vertices <= n_edges, "d3d_outlines_emit: n_vertices %lld outside 4 n_rings..n_edges", n_vertices);
+    hipLaunchKernelGGL(ol_emit_kernel, dim3(ol_blocks(n_edges)), dim3(OL_BLOCK), 0, (hipStream_t)stream, ordered, corner, ring_edge,
+                       (long)n_edges, (long)n_rings, (long)n_vertices, W, vertices, ring_start);
+    D3D_LAUNCH_CHECK("ol_emit_kernel launch");
+    return D3D_OK;
+}

@@ -36,7 +36,7 @@ The components are found tile by tile in LDS (a wave takes a row of 64 cells: ru
 in the global parent raster by a lock-free find-and-atomicMin loop, and resolved in one pass (csrc/objects.hip).
 
     python -m deep3d_aerial_amd.objects --ndsm N.tif --out O.tif [--table O.csv] [--min_height 2] [--min_area 10]
-        [--connectivity 8] [--open 0] [--nodata -9999]
+        [--connectivity 8] [--open 0] [--nodata -9999] [--outlines O.geojson]
 """
 import argparse
 import math
@@ -218,20 +218,26 @@ def label_raster(label, ndsm):
 
 def check_settings(settings):
     """The settings of build_and_write, checked without a GPU: {"path"} and optionally {"table", "min_height", "min_area",
-    "connectivity", "open", "nodata"}.  Returns the four parameters."""
+    "connectivity", "open", "nodata", "outlines"}.  Returns the four parameters."""
     p = settings.get("path")
     if not isinstance(p, str) or not p.endswith(".tif"):
         raise ValueError("the objects setting 'path' must be a path that ends in .tif (got %r)" % (p,))
     t = settings.get("table")
     if t is not None and (not isinstance(t, str) or not t.endswith(".csv")):
         raise ValueError("the objects setting 'table' must be a path that ends in .csv (got %r)" % (t,))
-    return check_params(*(settings.get(k, DEFAULTS[k]) for k in ("min_height", "min_area", "connectivity", "open")))
+    params = check_params(*(settings.get(k, DEFAULTS[k]) for k in ("min_height", "min_area", "connectivity", "open")))
+    if settings.get("outlines") is not None:
+        from . import outlines
+
+        outlines.check_settings({"path": settings["outlines"], "connectivity": params[2]})
+    return params
 
 
-def build_and_write(ndsm, grid, settings):
+def build_and_write(ndsm, grid, settings, timings=None):
     """The objects of an nDSM raster (device tensor, or a host array that is moved to the GPU) with settings {"path", "table",
-    "min_height", "min_area", "connectivity", "open", "nodata"} -> writes the label raster <path> with its .tfw and, when
-    given, the table; returns (label, table)."""
+    "min_height", "min_area", "connectivity", "open", "nodata", "outlines"} -> writes the label raster <path> with its .tfw and,
+    when given, the table and the outlines (outlines.py: the polygons of the label raster as GeoJSON, with the table's columns
+    as properties; timings, a dict, gets objects_outlines_s); returns (label, table)."""
     params = check_settings(settings)
     if not isinstance(ndsm, torch.Tensor):
         if not torch.cuda.is_available():
@@ -241,23 +247,34 @@ def build_and_write(ndsm, grid, settings):
     write_dsm(settings["path"], label_raster(label, ndsm), grid, nodata=settings.get("nodata", -9999.0))
     if settings.get("table") is not None:
         _geom.write_bytes(settings["table"], csv_bytes(table))
+    if settings.get("outlines") is not None:
+        from . import outlines
+
+        with _geom.timed(timings, "objects_outlines_s"):
+            outlines.build_and_write(label, grid, {"path": settings["outlines"], "connectivity": params[2]}, table=table)
     return label, table
 
 
-def add_arguments(ap, prefix=""):
-    """The settings as flags (--<prefix>table, ...); used by this module's CLI and by predict (--objects_*)."""
+def add_arguments(ap, prefix="", outlines=False):
+    """The settings as flags (--<prefix>table, ...); used by this module's CLI and by predict (--objects_*).  outlines: also
+    --<prefix>outlines; this module's CLI asks for it, predict does not (its flags are the ones of tests/golden/predict_flags.json)."""
     ap.add_argument("--%stable" % prefix, default=None, help="also write the table of the objects to this .csv")
     ap.add_argument("--%smin_height" % prefix, type=float, default=DEFAULTS["min_height"], help="a cell is foreground at this nDSM height, world units")
     ap.add_argument("--%smin_area" % prefix, type=float, default=DEFAULTS["min_area"], help="smallest object kept, world units squared")
     ap.add_argument("--%sconnectivity" % prefix, type=int, default=DEFAULTS["connectivity"], help="4 or 8")
     ap.add_argument("--%sopen" % prefix, type=float, default=DEFAULTS["open"],
                     help="open the foreground by this half-width first, world units (0: off)")
+    if outlines:
+        ap.add_argument("--%soutlines" % prefix, default=None, help="also write the objects' outlines, polygons in world units, to this .geojson")
 
 
 def settings_from_args(a, path, prefix="", nodata=None):
     g = lambda k: getattr(a, prefix + k)
-    return {"path": path, "table": g("table"), "min_height": g("min_height"), "min_area": g("min_area"),
-            "connectivity": g("connectivity"), "open": g("open"), "nodata": g("nodata") if nodata is None else nodata}
+    s = {"path": path, "table": g("table"), "min_height": g("min_height"), "min_area": g("min_area"),
+         "connectivity": g("connectivity"), "open": g("open"), "nodata": g("nodata") if nodata is None else nodata}
+    if getattr(a, prefix + "outlines", None) is not None:   # the key is there only when the flag exists and is given
+        s["outlines"] = g("outlines")
+    return s
 
 
 def check_args(ap, a, path, prefix="", nodata=None):
@@ -274,7 +291,7 @@ def parser():
     ap = argparse.ArgumentParser(description="Objects (label raster and table) from an nDSM file of this project")
     ap.add_argument("--ndsm", required=True, help="nDSM file (.tif, as dtm --ndsm writes it)")
     ap.add_argument("--out", required=True, help="label raster (.tif; the .tfw is written beside it)")
-    add_arguments(ap)
+    add_arguments(ap, outlines=True)
     ap.add_argument("--nodata", type=float, default=-9999.0, help="value written for empty cells")
     return ap
 

@@ -495,11 +495,12 @@ def write_dtm_of(height, dsm_settings, settings, timings=None):
 def write_objects_of(ndsm, dsm_settings, settings, timings=None):
     """Rank 0's objects of the nDSM the DTM step returned, on the DSM's grid and with its nodata (objects.build_and_write); no
     collective.  Returns (label, table).
-    settings: {"path", "table", "min_height", "min_area", "connectivity", "open"} (objects.check_settings).  Rank 0 writes the label
-    raster and, when asked, the table; timings gets objects_s on rank 0."""
+    settings: {"path", "table", "min_height", "min_area", "connectivity", "open", "outlines"} (objects.check_settings).  Rank 0
+    writes the label raster and, when asked, the table and the outlines; timings gets objects_s on rank 0, and objects_outlines_s
+    (a part of it) when the outlines are on."""
     with timed(timings, "objects_s"):
         grid, nodata = dsm_grid(dsm_settings)
-        res = _objects.build_and_write(ndsm, grid, dict(settings, nodata=nodata))
+        res = _objects.build_and_write(ndsm, grid, dict(settings, nodata=nodata), timings=timings)
     return res
 
 

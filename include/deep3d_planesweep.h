@@ -927,6 +927,50 @@ int d3d_objects_relabel(const int* parent, const long long* acc, long long n_roo
                         int W, int H, void* scratch, size_t scratch_bytes, long long* n_kept, d3d_stream_t stream);
 
 /*
+ * DESIGN.md §4.37 -- the outlines of a label raster: the boundary rings of every object as lattice vertices.  The rule is this
+ * project's (deep3d_aerial_amd/outlines.py states it in full); the reference has no such step.
+ * label [H,W] int32 (device): 0 background, ids > 0 objects; 1 <= W * H <= D3D_OUTLINES_MAX_CELLS, so there are fewer than 2^31
+ * unit edges; cells outside the raster count as 0.  Corner (i, j) is the upper-left corner of cell (i, j).  A cell c with label
+ * L > 0 has one directed unit edge, the cell on its left, on every side s whose neighbour is not L: 0 top (i, j+1) -> (i, j),
+ * 1 left (i, j) -> (i+1, j), 2 bottom (i+1, j) -> (i+1, j+1), 3 right (i+1, j+1) -> (i, j+1).  The slot of an edge is its rank
+ * in (i * W + j, s) order; its key is (i * W + j) * 4 + s.  Successor of (c, s), d its direction, o the neighbour offset of s,
+ * la / ra whether c + d / c + d + o hold L: connectivity 8: ra -> (c + d + o, s - 1), else la -> (c + d, s), else (c, s + 1);
+ * connectivity 4: not la -> (c, s + 1), else not ra -> (c + d, s), else (c + d + o, s - 1).  The edges fall into closed rings; a
+ * ring's leader is its smallest slot, the rings are ordered by leader, and a ring's vertices are the heads of its corner edges
+ * (the successor has another side) in ring order from the leader.
+ *   scratch of d3d_outlines_scratch_bytes(W, H) bytes (0 for an out-of-range size) serves every call that takes one.
+ *   d3d_outlines_count: offset [H,W] int32 gets every cell's first slot; counters (device, two int64) the number of edges and a
+ *   nonzero word when a label is negative (such cells count as background; the Python layer refuses them).
+ *   d3d_outlines_edges: per slot, succ the successor's slot, key the key, state (16 bytes per edge) the start of the ranking,
+ *   (m, dm, nx) = (slot, 0, succ).  n_edges is the count's total, 1 .. 4 W H.
+ *   d3d_outlines_rank: round k (0 .. 30) of the pointer jumping from state_in to state_out: t = nx[e]; if m[t] < m[e] then
+ *   m[e] = m[t] and dm[e] = 2^k + dm[t]; nx[e] = nx[t].  changed (device int32) is cleared and then set when an m changed.  The
+ *   round that changes none is the last: m is then the ring's leader and dm the hops to it.
+ *   d3d_outlines_rings: ring_id [n_edges] int32 gets the number of leaders below each slot; *n_rings (device int64) their number.
+ *   d3d_outlines_place: ring_len, ring_edge, ring_object [n_rings] int32 get each ring's length 1 + dm[succ[leader]], the sum of
+ *   the lengths before it and its label; ordered [n_edges] gets the keys in ring order, edge e at
+ *   ring_edge + (len - dm[e]) mod len, bit 31 set on a corner edge; corner [n_edges] int32 the number of corner edges before
+ *   each place; *n_vertices (device int64) their number.
+ *   d3d_outlines_emit: vertices [n_vertices,2] int32 gets the head (i, j) of every corner edge, ring_start [n_rings + 1] int32
+ *   each ring's first vertex and n_vertices.
+ * No float and no order of execution enters any output: the same bits run to run.
+ */
+#define D3D_OUTLINES_MAX_CELLS 536870911
+size_t d3d_outlines_scratch_bytes(int W, int H);
+int d3d_outlines_count(const int* label, int W, int H, int* offset, void* scratch, size_t scratch_bytes, long long* counters,
+                       d3d_stream_t stream);
+int d3d_outlines_edges(const int* label, const int* offset, int connectivity, int W, int H, long long n_edges, int* succ, int* key,
+                       int* state, d3d_stream_t stream);
+int d3d_outlines_rank(const int* state_in, int* state_out, long long n_edges, int round, int* changed, d3d_stream_t stream);
+int d3d_outlines_rings(const int* state, int W, int H, long long n_edges, int* ring_id, void* scratch, size_t scratch_bytes,
+                       long long* n_rings, d3d_stream_t stream);
+int d3d_outlines_place(const int* label, int W, int H, const int* state, const int* succ, const int* key, const int* ring_id,
+                       long long n_edges, long long n_rings, int* ring_len, int* ring_edge, int* ring_object, unsigned* ordered,
+                       int* corner, void* scratch, size_t scratch_bytes, long long* n_vertices, d3d_stream_t stream);
+int d3d_outlines_emit(const unsigned* ordered, const int* corner, const int* ring_edge, int W, int H, long long n_edges,
+                      long long n_rings, long long n_vertices, int* vertices, int* ring_start, d3d_stream_t stream);
+
+/*
  * DESIGN.md §4.11 -- digital surface model from a triangle mesh: the reference's CREATEDSM step with dsm_source "mesh"
  * (run.py:226-232 calls mesh2dsm.DSM_from_Mesh, which the reference never shipped; the semantics are this project's,
  * deep3d_aerial_amd/dsm.py).  The raster is the one of d3d_dsm_from_points.
