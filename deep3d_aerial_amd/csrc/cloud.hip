@@ -22,7 +22,7 @@
 //             next run follows it), not for the dropped keys; geom_scan's exclusive scan of the marks is then the voxel index of
 //             every sorted point, and its total the number of voxels.
 // accumulate: one lane per sorted point reads its point through the order and adds into its voxel's accumulators.  The keys are
-//             sorted, so the lanes of a wave hold few runs: a segmented inclusive scan over the wave (shuffles; legal because
+//             sorted, so the lanes of a wave hold few runs: the run reduction of geom_shared.h (wave_run_sum; legal because
 //             every sum is an integer) leaves each run's sum in its last lane, which issues the atomics and stores the voxel's
 //             key.  A run that crosses waves adds once per wave.  Built with -DD3D_CLOUD_PLAIN every lane issues its own atomics
 //             instead: the form tools/cloud_bench.py --variant_library times beside this one.
@@ -98,18 +98,6 @@ __global__ __launch_bounds__(CL_BLOCK) void cloud_heads_kernel(const long long* 
     mark[p] = k != CLOUD_DROPPED && (p + 1 == n || keys[p + 1] != k) ? 1 : 0;
 }
 
-// The inclusive sum of x over the lanes at and below this one that hold the same voxel v (v is sorted over the wave).
-template <typename T>
-__device__ __forceinline__ T cloud_run_sum(T x, int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = __shfl_up(x, o, 64);
-        const int w = __shfl_up(v, o, 64);
-        if (lane >= o && w == v) x += y;
-    }
-    return x;
-}
-
 __device__ __forceinline__ void cloud_add(long long* p, long long x) { atomicAdd((unsigned long long*)p, (unsigned long long)x); }
 
 // acc [n_voxels, stride] int64: S at 0, N at 3 (with normals), C after them (with colours)
@@ -152,19 +140,19 @@ __global__ __launch_bounds__(CL_BLOCK) void cloud_accumulate_kernel(const long l
 #ifndef D3D_CLOUD_PLAIN
     const int lane = threadIdx.x & 63;
     // 64 lanes of at most 65535 or 255 each: the sums of a wave fit in int32
-    c = cloud_run_sum(c, v, lane);
+    const int first = wave_run_first(v, lane);
+    c = wave_run_sum(c, first, lane);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) r[a] = cloud_run_sum(r[a], v, lane);
+    for (int a = 0; a < 3; ++a) r[a] = wave_run_sum(r[a], first, lane);
     if (NRM) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) nq[a] = cloud_run_sum(nq[a], v, lane);
+        for (int a = 0; a < 3; ++a) nq[a] = wave_run_sum(nq[a], first, lane);
     }
     if (COL) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) col[a] = cloud_run_sum(col[a], v, lane);
+        for (int a = 0; a < 3; ++a) col[a] = wave_run_sum(col[a], first, lane);
     }
-    const int next = __shfl_down(v, 1, 64);
-    if (lane != 63 && next == v) return;   // not the last lane of its run in this wave
+    if (!wave_run_last(v, lane)) return;   // not the last lane of its run in this wave
 #endif
     if (v < 0) return;
     ukeys[v] = key;   // every lane that gets here for v stores the same key

@@ -129,8 +129,7 @@ inline bool search_apart(const SearchRange* r, int n) {
     for (int a = 0; a < n; ++a)
         for (int b = a + 1; b < n; ++b) {
             if (!r[a].p || !r[b].p || !r[a].bytes || !r[b].bytes) continue;
-            const uintptr_t a0 = (uintptr_t)r[a].p, b0 = (uintptr_t)r[b].p;
-            if (!(a0 + r[a].bytes <= b0 || b0 + r[b].bytes <= a0)) return false;
+            if (!geom_apart(r[a].p, r[a].bytes, r[b].p, r[b].bytes)) return false;
         }
     return true;
 }

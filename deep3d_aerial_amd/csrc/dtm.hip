@@ -193,26 +193,20 @@ static int dtm_cols(const float* in, float* out, unsigned* suffix, int W, int H,
     return D3D_OK;
 }
 
-static size_t dtm_raster_bytes(int W, int H) { return (((size_t)W * H * 4) + 255) & ~(size_t)255; }
-
-static bool dtm_dims_ok(int W, int H) { return W >= 1 && H >= 1 && (long long)W * H < (1ll << 31); }
-
-static bool dtm_apart(const void* a, size_t na, const void* b, size_t nb) {
-    return (uintptr_t)a + na <= (uintptr_t)b || (uintptr_t)b + nb <= (uintptr_t)a;
-}
+constexpr long long DTM_MAX_CELLS = (1ll << 31) - 1;   // W * H < 2^31
 
 // what 0 (erode), 1 (dilate), 2 (open)
 static int dtm_morph(int what, const char* name, const float* in, float* out, int W, int H, int rx, int ry, void* scratch,
                      size_t scratch_bytes, d3d_stream_t stream) {
     D3D_REQUIRE(in && out && scratch, "%s: null pointer (in, out, scratch)", name);
-    D3D_REQUIRE(dtm_dims_ok(W, H), "%s: raster %d x %d: size must be >= 1 and W * H < 2^31", name, W, H);
+    D3D_REQUIRE(raster_ok(W, H, DTM_MAX_CELLS), "%s: raster %d x %d: size must be >= 1 and W * H < 2^31", name, W, H);
     D3D_REQUIRE(rx >= 1 && rx <= D3D_DTM_MAX_RADIUS && ry >= 1 && ry <= D3D_DTM_MAX_RADIUS, "%s: radius (%d, %d) outside 1..%d", name,
                 rx, ry, D3D_DTM_MAX_RADIUS);
-    const size_t raster = dtm_raster_bytes(W, H), bytes = (size_t)W * H * 4;
+    const size_t raster = align256((size_t)W * H * 4), bytes = (size_t)W * H * 4;
     D3D_REQUIRE(scratch_bytes >= 2 * raster, "%s: scratch of %zu bytes, %zu needed (d3d_dtm_scratch_bytes)", name, scratch_bytes,
                 2 * raster);
-    D3D_REQUIRE(dtm_apart(in, bytes, out, bytes), "%s: out must not alias in", name);
-    D3D_REQUIRE(dtm_apart(in, bytes, scratch, 2 * raster) && dtm_apart(out, bytes, scratch, 2 * raster),
+    D3D_REQUIRE(geom_apart(in, bytes, out, bytes), "%s: out must not alias in", name);
+    D3D_REQUIRE(geom_apart(in, bytes, scratch, 2 * raster) && geom_apart(out, bytes, scratch, 2 * raster),
                 "%s: scratch must not alias in or out", name);
     hipStream_t st = (hipStream_t)stream;
     float* tmp = (float*)scratch;
@@ -311,7 +305,7 @@ __global__ __launch_bounds__(DTM_BLOCK) void dtm_push_kernel(const float* __rest
 
 using namespace d3d;
 
-extern "C" size_t d3d_dtm_scratch_bytes(int W, int H) { return dtm_dims_ok(W, H) ? 2 * dtm_raster_bytes(W, H) : 0; }
+extern "C" size_t d3d_dtm_scratch_bytes(int W, int H) { return raster_ok(W, H, DTM_MAX_CELLS) ? 2 * align256((size_t)W * H * 4) : 0; }
 
 extern "C" int d3d_dtm_erode(const float* in, float* out, int W, int H, int rx, int ry, void* scratch, size_t scratch_bytes,
                              d3d_stream_t stream) {
@@ -331,7 +325,7 @@ extern "C" int d3d_dtm_open(const float* in, float* out, int W, int H, int rx, i
 extern "C" int d3d_dtm_classify(const float* surface, const float* opened, float dh, int k, unsigned char* level, int W, int H,
                                 d3d_stream_t stream) {
     D3D_REQUIRE(surface && opened && level, "d3d_dtm_classify: null pointer (surface, opened, level)");
-    D3D_REQUIRE(dtm_dims_ok(W, H), "d3d_dtm_classify: raster %d x %d: size must be >= 1 and W * H < 2^31", W, H);
+    D3D_REQUIRE(raster_ok(W, H, DTM_MAX_CELLS), "d3d_dtm_classify: raster %d x %d: size must be >= 1 and W * H < 2^31", W, H);
     D3D_REQUIRE(k >= 1 && k <= 254, "d3d_dtm_classify: level k=%d outside 1..254", k);
     D3D_REQUIRE(dh == dh, "d3d_dtm_classify: dh is NaN");
     const int n = W * H;
@@ -343,7 +337,7 @@ extern "C" int d3d_dtm_classify(const float* surface, const float* opened, float
 
 extern "C" int d3d_dtm_ground(const float* height, const unsigned char* level, float* ground, int W, int H, d3d_stream_t stream) {
     D3D_REQUIRE(height && level && ground, "d3d_dtm_ground: null pointer (height, level, ground)");
-    D3D_REQUIRE(dtm_dims_ok(W, H), "d3d_dtm_ground: raster %d x %d: size must be >= 1 and W * H < 2^31", W, H);
+    D3D_REQUIRE(raster_ok(W, H, DTM_MAX_CELLS), "d3d_dtm_ground: raster %d x %d: size must be >= 1 and W * H < 2^31", W, H);
     const int n = W * H;
     hipLaunchKernelGGL(dtm_ground_kernel, dim3(ceil_div(n, DTM_BLOCK)), dim3(DTM_BLOCK), 0, (hipStream_t)stream, height, level, ground, n);
     D3D_LAUNCH_CHECK("dtm_ground_kernel launch");
@@ -352,7 +346,7 @@ extern "C" int d3d_dtm_ground(const float* height, const unsigned char* level, f
 
 extern "C" int d3d_dtm_ndsm(const float* height, const float* dtm, float* ndsm, int W, int H, d3d_stream_t stream) {
     D3D_REQUIRE(height && dtm && ndsm, "d3d_dtm_ndsm: null pointer (height, dtm, ndsm)");
-    D3D_REQUIRE(dtm_dims_ok(W, H), "d3d_dtm_ndsm: raster %d x %d: size must be >= 1 and W * H < 2^31", W, H);
+    D3D_REQUIRE(raster_ok(W, H, DTM_MAX_CELLS), "d3d_dtm_ndsm: raster %d x %d: size must be >= 1 and W * H < 2^31", W, H);
     const int n = W * H;
     hipLaunchKernelGGL(dtm_ndsm_kernel, dim3(ceil_div(n, DTM_BLOCK)), dim3(DTM_BLOCK), 0, (hipStream_t)stream, height, dtm, ndsm, n);
     D3D_LAUNCH_CHECK("dtm_ndsm_kernel launch");
@@ -361,9 +355,9 @@ extern "C" int d3d_dtm_ndsm(const float* height, const float* dtm, float* ndsm, 
 
 extern "C" int d3d_dtm_pull(const float* fine, int Wf, int Hf, float* coarse, d3d_stream_t stream) {
     D3D_REQUIRE(fine && coarse, "d3d_dtm_pull: null pointer (fine, coarse)");
-    D3D_REQUIRE(dtm_dims_ok(Wf, Hf), "d3d_dtm_pull: raster %d x %d: size must be >= 1 and W * H < 2^31", Wf, Hf);
+    D3D_REQUIRE(raster_ok(Wf, Hf, DTM_MAX_CELLS), "d3d_dtm_pull: raster %d x %d: size must be >= 1 and W * H < 2^31", Wf, Hf);
     const int Wc = (Wf + 1) / 2, Hc = (Hf + 1) / 2, nc = Wc * Hc;
-    D3D_REQUIRE(dtm_apart(fine, (size_t)Wf * Hf * 4, coarse, (size_t)nc * 4), "d3d_dtm_pull: coarse must not alias fine");
+    D3D_REQUIRE(geom_apart(fine, (size_t)Wf * Hf * 4, coarse, (size_t)nc * 4), "d3d_dtm_pull: coarse must not alias fine");
     hipLaunchKernelGGL(dtm_pull_kernel, dim3(ceil_div(nc, DTM_BLOCK)), dim3(DTM_BLOCK), 0, (hipStream_t)stream, fine, Wf, Hf, coarse, Wc,
                        nc);
     D3D_LAUNCH_CHECK("dtm_pull_kernel launch");
@@ -372,9 +366,9 @@ extern "C" int d3d_dtm_pull(const float* fine, int Wf, int Hf, float* coarse, d3
 
 extern "C" int d3d_dtm_push(const float* coarse, float* fine, int Wf, int Hf, d3d_stream_t stream) {
     D3D_REQUIRE(fine && coarse, "d3d_dtm_push: null pointer (coarse, fine)");
-    D3D_REQUIRE(dtm_dims_ok(Wf, Hf), "d3d_dtm_push: raster %d x %d: size must be >= 1 and W * H < 2^31", Wf, Hf);
+    D3D_REQUIRE(raster_ok(Wf, Hf, DTM_MAX_CELLS), "d3d_dtm_push: raster %d x %d: size must be >= 1 and W * H < 2^31", Wf, Hf);
     const int Wc = (Wf + 1) / 2, Hc = (Hf + 1) / 2, nf = Wf * Hf;
-    D3D_REQUIRE(dtm_apart(fine, (size_t)nf * 4, coarse, (size_t)Wc * Hc * 4), "d3d_dtm_push: coarse must not alias fine");
+    D3D_REQUIRE(geom_apart(fine, (size_t)nf * 4, coarse, (size_t)Wc * Hc * 4), "d3d_dtm_push: coarse must not alias fine");
     hipLaunchKernelGGL(dtm_push_kernel, dim3(ceil_div(nf, DTM_BLOCK)), dim3(DTM_BLOCK), 0, (hipStream_t)stream, coarse, Wc, Hc, fine, Wf,
                        nf);
     D3D_LAUNCH_CHECK("dtm_push_kernel launch");

@@ -1,7 +1,10 @@
-// The primitives the geometry stages share (fusion, dsm, ortho, ortho_mesh, cloud, mesh, mesh_clean, mesh_decimate, mesh_holes,
-// mesh_refine, mesh_subdivide, mesh_collapse, mesh_flip, texture and its smooth, level, local and outliers passes); not part of the
-// public ABI.  The kernels behind the host functions declared here are in geom.hip.
+// The primitives the geometry stages share (fusion, normals, dsm, dtm, objects, outlines, ortho, ortho_mesh, view_select, cloud and
+// its outliers, normals, compare and register stages, mesh, mesh_sample, mesh_clean, mesh_decimate, mesh_holes, mesh_refine,
+// mesh_subdivide, mesh_collapse, mesh_flip, texture and its smooth, level, local and outliers passes); not part of the public ABI.
+// The kernels behind the host functions declared here are in geom.hip.
 #pragma once
+#include <cstdint>
+
 #include "common.h"
 
 namespace d3d {
@@ -46,6 +49,61 @@ template <typename T>
 __device__ __forceinline__ T wave_sum(T x) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// The counters of a wave: the sum of each c (int, or bool as 0 / 1) over the wave, the i-th one added to counts[i] by lane 0 when
+// it is not zero, with one integer atomicAdd whose result is unused.  Every lane of the wave calls it.
+template <typename... T>
+__device__ __forceinline__ void wave_counts_add(int* counts, T... c) {
+    const int sums[] = {wave_sum((int)c)...};
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < (int)sizeof...(T); ++i)
+            if (sums[i]) atomicAdd(counts + i, sums[i]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// runs of a wave: a run is a maximal set of consecutive lanes with equal v.  A kernel whose lanes hold few runs (sorted keys, the
+// samples of a face, the cells of a row) reduces each run into its last lane and sends one set of atomics per run instead of one
+// per lane; every reduction here is on integers, so the grouping does not change a bit.
+//   - Every lane of the wave calls these (they shuffle and ballot): no lane may have returned before.
+//   - v need not be sorted: equal values that are not adjacent are separate runs.
+//   - Lanes with v < 0 ("nothing here") form runs like any other; the caller discards them.
+//   - A run ends at the wave's edge: one that crosses waves is sent once per wave.
+// ---------------------------------------------------------------------------------------------------------------------------
+// The lowest lane of this lane's run: the highest run head (lane 0, or a lane whose v differs from the lane before) at or below it.
+__device__ __forceinline__ int wave_run_first(int v, int lane) {
+    const int before = __shfl_up(v, 1, 64);
+    const unsigned long long heads = __ballot(lane == 0 || before != v);
+    return 63 - __clzll((long long)(heads & ((2ull << lane) - 1ull)));
+}
+
+// True in the highest lane of each run.
+__device__ __forceinline__ bool wave_run_last(int v, int lane) {
+    const int next = __shfl_down(v, 1, 64);
+    return lane == 63 || next != v;
+}
+
+// The sum / maximum of x over the lanes first .. lane, first = wave_run_first(v, lane).
+template <typename T>
+__device__ __forceinline__ T wave_run_sum(T x, int first, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(x, o, 64);
+        if (lane - o >= first) x += y;
+    }
+    return x;
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_run_max(T x, int first, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(x, o, 64);
+        if (lane - o >= first) x = geom_max(x, y);
+    }
     return x;
 }
 
@@ -99,6 +157,14 @@ inline int geom_scan(const int* in, int* out, long long n, void* scratch, long l
 // ---------------------------------------------------------------------------------------------------------------------------
 // A count of points, voxels, faces or samples an entry point takes: 0 .. 2^31 - 1, so that an index fits in int32.
 inline bool count_ok(long long n) { return n >= 0 && n < (1ll << 31); }
+
+// A W x H raster an entry point takes: both sides >= 1 and at most max_cells cells.
+inline bool raster_ok(int W, int H, long long max_cells) { return W >= 1 && H >= 1 && (long long)W * H <= max_cells; }
+
+// The na bytes at a and the nb bytes at b do not overlap.
+inline bool geom_apart(const void* a, size_t na, const void* b, size_t nb) {
+    return (uintptr_t)a + na <= (uintptr_t)b || (uintptr_t)b + nb <= (uintptr_t)a;
+}
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 

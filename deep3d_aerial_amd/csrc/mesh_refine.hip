@@ -324,12 +324,7 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_match_kernel(const float* __restr
         d0[v] = d;
         c_active = act ? 1 : 0, c_two = two ? 1 : 0, c_used = used != 0u ? 1 : 0, c_moved = w != 0.0f ? 1 : 0;
     }
-    const int sums[4] = {wave_sum(c_active), wave_sum(c_two), wave_sum(c_used), wave_sum(c_moved)};
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (sums[c]) atomicAdd(counts + c, sums[c]);
-    }
+    wave_counts_add(counts, c_active, c_two, c_used, c_moved);
 }
 #else
 constexpr int RF_LANES_PER_VERTEX = 1;
@@ -388,12 +383,7 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_match_kernel(const float* __restr
         weight[v] = w;
         d0[v] = d;
     }
-    const int sums[4] = {wave_sum(act ? 1 : 0), wave_sum(two ? 1 : 0), wave_sum(used != 0u ? 1 : 0), wave_sum(w != 0.0f ? 1 : 0)};
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (sums[c]) atomicAdd(counts + c, sums[c]);
-    }
+    wave_counts_add(counts, act, two, used != 0u, w != 0.0f);
 }
 #endif
 

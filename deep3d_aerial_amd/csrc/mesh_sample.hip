@@ -31,7 +31,7 @@
 //             stored a lane, consecutive over the lanes.
 // face error: one lane per sample of a comparison: e [S] and face [S] in, per face sum int64 and keyed int32 over the samples
 //             with e >= 0, worst int32 their maximum (-1 for a face without one).  The samples of a face are consecutive, so each
-//             run of equal faces within a wave is reduced by shuffles (a segmented scan from the run's first lane: the sums and
+//             run of equal faces within a wave is reduced by shuffles (the run reduction of geom_shared.h: the sums and
 //             maxima are integers, so any grouping gives the same bits) and its last lane issues the atomics; a run that crosses
 //             waves adds once per wave.  The runs are found from the neighbouring lanes, so an unsorted face array gives the same
 //             result too.  Built with -DD3D_MESH_SAMPLE_PLAIN every keyed sample issues its own atomics (the form
@@ -173,26 +173,6 @@ __global__ __launch_bounds__(MS_BLOCK) void mesh_sample_emit_kernel(const float*
     }
 }
 
-// The inclusive sum / maximum of x over the lanes from `first` (the first lane of this lane's run) to this one.
-template <typename T>
-__device__ __forceinline__ T ms_run_sum(T x, int first, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = __shfl_up(x, o, 64);
-        if (lane - o >= first) x += y;
-    }
-    return x;
-}
-
-__device__ __forceinline__ int ms_run_max(int x, int first, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane - o >= first) x = max(x, y);
-    }
-    return x;
-}
-
 // sum and keyed zeroed and worst set to -1 by the host before the launch
 __global__ __launch_bounds__(MS_BLOCK) void mesh_sample_face_error_kernel(const int* __restrict__ e, const int* __restrict__ face, long n,
                                                                           int m, unsigned long long* __restrict__ sum,
@@ -208,19 +188,11 @@ __global__ __launch_bounds__(MS_BLOCK) void mesh_sample_face_error_kernel(const 
     }
 #ifndef D3D_MESH_SAMPLE_PLAIN
     const int lane = threadIdx.x & 63;
-    // the first lane of this lane's run of equal faces: the largest head at or below it
-    const int before = __shfl_up(f, 1, 64);
-    int first = lane == 0 || before != f ? lane : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(first, o, 64);
-        if (lane >= o) first = max(first, y);
-    }
-    s = ms_run_sum(s, first, lane);   // 64-bit: any e >= 0 sums as the plain form's atomics would
-    c = ms_run_sum(c, first, lane);
-    hi = ms_run_max(hi, first, lane);
-    const int next = __shfl_down(f, 1, 64);
-    if (lane != 63 && next == f) return;   // not the last lane of its run in this wave
+    const int first = wave_run_first(f, lane);   // of this lane's run of equal faces
+    s = wave_run_sum(s, first, lane);   // 64-bit: any e >= 0 sums as the plain form's atomics would
+    c = wave_run_sum(c, first, lane);
+    hi = wave_run_max(hi, first, lane);
+    if (!wave_run_last(f, lane)) return;   // not the last lane of its run in this wave
 #endif
     if (f < 0 || c == 0) return;
     atomicAdd(sum + f, (unsigned long long)s);

@@ -23,6 +23,7 @@
 // every pixel with the same function, so the results do not depend on the path, on B or on the launch shape.
 // No atomics, no reduction: bit-reproducible.
 #include "common.h"
+#include "geom_shared.h"
 
 namespace d3d {
 
@@ -189,11 +190,6 @@ __global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ 
     }
 }
 
-static bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace d3d
 
 using namespace d3d;
@@ -207,8 +203,9 @@ extern "C" int d3d_normals_from_depth(const float* depth, const float* kinv, int
     D3D_REQUIRE(H >= 2 * nei && W >= 2 * nei, "map %dx%d smaller than the stencil (2*nei = %d)", H, W, 2 * nei);
     D3D_REQUIRE((long)ceil_div(H, 4) <= 65535, "H=%d too large", H);
     const size_t in_bytes = (size_t)B * H * W * sizeof(float), out_bytes = 3 * in_bytes;
-    D3D_REQUIRE(!overlaps(depth, in_bytes, normal, out_bytes) && !overlaps(depth, in_bytes, encoded, out_bytes) &&
-                    !overlaps(normal, out_bytes, encoded, out_bytes),
+    // (an output that is NULL is not written)
+    D3D_REQUIRE((!normal || geom_apart(depth, in_bytes, normal, out_bytes)) && (!encoded || geom_apart(depth, in_bytes, encoded, out_bytes)) &&
+                    (!normal || !encoded || geom_apart(normal, out_bytes, encoded, out_bytes)),
                 "outputs must not alias the depth map or each other");
     for (int i = 0; i < 9 * B; ++i) D3D_REQUIRE(std::isfinite(kinv[i]), "inv(K) of item %d is not finite", i / 9);
     const bool vec = W % 4 == 0 && ((uintptr_t)depth & 15) == 0 && ((uintptr_t)normal & 15) == 0 && ((uintptr_t)encoded & 15) == 0;

@@ -18,8 +18,8 @@
 //   roots:    parent[c] == c flags the roots; geom_scan of the flags is the provisional id (the roots in index order).
 //   stats:    a wave covers 64 consecutive cells of a row and walks 32 rows; each run of equal ids in a row is reduced into its
 //             last lane -- the count, the index sums and the box of a run follow from its two end lanes in closed form, the height
-//             sum and maximum from a segmented scan by shuffles -- and that lane holds the part back while the runs of the next rows
-//             that end at it are the same component's.  A part is sent as four integer atomicAdd and up to five atomicMin / atomicMax
+//             sum and maximum from a segmented scan by shuffles over the runs of geom_shared.h (wave_run_first) -- and that lane
+//             holds the part back while the runs of the next rows that end at it are the same component's.  A part is sent as four integer atomicAdd and up to five atomicMin / atomicMax
 //             (those only when the slot does not hold as much already).  Built with -DD3D_OBJECTS_PLAIN every cell sends its own
 //             (tools/objects_bench.py --variant_library).
 //   relabel:  keep = cells >= min_cells, geom_scan of keep is the final id, one pass writes label.
@@ -313,10 +313,8 @@ __global__ __launch_bounds__(OBJ_BLOCK) void obj_stats_kernel(const float* __res
         int first = lane;
         bool ends = v >= 0;
 #ifndef D3D_OBJECTS_PLAIN
-        // the run of equal ids this lane lies in begins at the highest head at or below it
-        const int before = __shfl_up(v, 1, 64);
-        const unsigned long long heads = __ballot(lane == 0 || before != v);
-        first = 63 - __clzll((long long)(heads & ((2ull << lane) - 1ull)));
+        first = wave_run_first(v, lane);   // of this lane's run of equal ids
+        // wave_run_sum and wave_run_max in one loop: as two calls the pass was 9 % slower on random 0.59
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const unsigned long long s = __shfl_up(hs, o, 64);
@@ -326,8 +324,8 @@ __global__ __launch_bounds__(OBJ_BLOCK) void obj_stats_kernel(const float* __res
                 hk = max(hk, m);
             }
         }
-        const int next = __shfl_down(v, 1, 64);
-        ends = ends && (lane == 63 || next != v);   // the last lane of its run
+        const bool last = wave_run_last(v, lane);   // every lane asks, before the &&: a background lane's v is read by its neighbour
+        ends = ends && last;
 #endif
         if (!ends) continue;
         // the run is the cells xs + first .. xs + lane of row y
@@ -380,11 +378,7 @@ __global__ __launch_bounds__(OBJ_BLOCK) void obj_label_kernel(const int* __restr
     label[c] = out;
 }
 
-static bool obj_dims_ok(int W, int H) { return W >= 1 && H >= 1 && (long long)W * H < (1ll << 31) - 1; }
-
-static bool obj_apart(const void* a, size_t na, const void* b, size_t nb) {
-    return (uintptr_t)a + na <= (uintptr_t)b || (uintptr_t)b + nb <= (uintptr_t)a;
-}
+constexpr long long OBJ_MAX_CELLS = (1ll << 31) - 2;   // W * H < 2^31 - 1
 
 // scratch: the provisional-id raster, then the tile sums of the scans
 struct ObjScratch {
@@ -404,9 +398,9 @@ static ObjScratch obj_layout(int W, int H) {
 
 using namespace d3d;
 
-#define OBJ_DIMS(name) D3D_REQUIRE(obj_dims_ok(W, H), "%s: raster %d x %d: size must be >= 1 and W * H < 2^31 - 1", name, W, H)
+#define OBJ_DIMS(name) D3D_REQUIRE(raster_ok(W, H, OBJ_MAX_CELLS), "%s: raster %d x %d: size must be >= 1 and W * H < 2^31 - 1", name, W, H)
 
-extern "C" size_t d3d_objects_scratch_bytes(int W, int H) { return obj_dims_ok(W, H) ? obj_layout(W, H).bytes : 0; }
+extern "C" size_t d3d_objects_scratch_bytes(int W, int H) { return raster_ok(W, H, OBJ_MAX_CELLS) ? obj_layout(W, H).bytes : 0; }
 
 extern "C" int d3d_objects_foreground(const float* ndsm, float min_height, unsigned char* mask, float* maskf, int W, int H,
                                       d3d_stream_t stream) {
@@ -414,8 +408,8 @@ extern "C" int d3d_objects_foreground(const float* ndsm, float min_height, unsig
     OBJ_DIMS("d3d_objects_foreground");
     D3D_REQUIRE(min_height == min_height, "d3d_objects_foreground: min_height is NaN");
     const int n = W * H;
-    D3D_REQUIRE(!maskf || obj_apart(ndsm, (size_t)n * 4, maskf, (size_t)n * 4), "d3d_objects_foreground: maskf must not alias ndsm");
-    D3D_REQUIRE(!mask || obj_apart(ndsm, (size_t)n * 4, mask, (size_t)n), "d3d_objects_foreground: mask must not alias ndsm");
+    D3D_REQUIRE(!maskf || geom_apart(ndsm, (size_t)n * 4, maskf, (size_t)n * 4), "d3d_objects_foreground: maskf must not alias ndsm");
+    D3D_REQUIRE(!mask || geom_apart(ndsm, (size_t)n * 4, mask, (size_t)n), "d3d_objects_foreground: mask must not alias ndsm");
     hipLaunchKernelGGL(obj_foreground_kernel, dim3(ceil_div(n, OBJ_BLOCK)), dim3(OBJ_BLOCK), 0, (hipStream_t)stream, ndsm, min_height, mask,
                        maskf, n);
     D3D_LAUNCH_CHECK("obj_foreground_kernel launch");
@@ -429,7 +423,7 @@ extern "C" int d3d_objects_label(const float* ndsm, float min_height, const unsi
     D3D_REQUIRE(connectivity == 4 || connectivity == 8, "d3d_objects_label: connectivity %d is neither 4 nor 8", connectivity);
     D3D_REQUIRE(mask || min_height == min_height, "d3d_objects_label: min_height is NaN");
     const int n = W * H;
-    D3D_REQUIRE(ndsm ? obj_apart(ndsm, (size_t)n * 4, parent, (size_t)n * 4) : obj_apart(mask, (size_t)n, parent, (size_t)n * 4),
+    D3D_REQUIRE(ndsm ? geom_apart(ndsm, (size_t)n * 4, parent, (size_t)n * 4) : geom_apart(mask, (size_t)n, parent, (size_t)n * 4),
                 "d3d_objects_label: parent must not alias the input");
     hipStream_t st = (hipStream_t)stream;
     const int conn8 = connectivity == 8 ? 1 : 0, ntx = ceil_div(W, OBJ_TILE), nty = ceil_div(H, OBJ_TILE);
@@ -462,7 +456,7 @@ extern "C" int d3d_objects_roots(const int* parent, int W, int H, void* scratch,
     D3D_REQUIRE(scratch_bytes >= L.bytes, "d3d_objects_roots: scratch of %zu bytes, %zu needed (d3d_objects_scratch_bytes)", scratch_bytes,
                 L.bytes);
     const int n = W * H;
-    D3D_REQUIRE(obj_apart(parent, (size_t)n * 4, scratch, L.bytes), "d3d_objects_roots: scratch must not alias parent");
+    D3D_REQUIRE(geom_apart(parent, (size_t)n * 4, scratch, L.bytes), "d3d_objects_roots: scratch must not alias parent");
     hipStream_t st = (hipStream_t)stream;
     int* pid = (int*)((char*)scratch + L.pid);
     hipLaunchKernelGGL(obj_root_flag_kernel, dim3(ceil_div(n, OBJ_BLOCK)), dim3(OBJ_BLOCK), 0, st, parent, pid, n);
@@ -503,8 +497,8 @@ extern "C" int d3d_objects_relabel(const int* parent, const long long* acc, long
     const int n = W * H;
     D3D_REQUIRE(n_roots >= 0 && n_roots <= n, "d3d_objects_relabel: n_roots %lld outside 0..%d", n_roots, n);
     D3D_REQUIRE(min_cells >= 1, "d3d_objects_relabel: min_cells %lld must be >= 1", min_cells);
-    D3D_REQUIRE(obj_apart(parent, (size_t)n * 4, label, (size_t)n * 4), "d3d_objects_relabel: label must not alias parent");
-    D3D_REQUIRE(obj_apart(label, (size_t)n * 4, scratch, L.bytes), "d3d_objects_relabel: scratch must not alias label");
+    D3D_REQUIRE(geom_apart(parent, (size_t)n * 4, label, (size_t)n * 4), "d3d_objects_relabel: label must not alias parent");
+    D3D_REQUIRE(geom_apart(label, (size_t)n * 4, scratch, L.bytes), "d3d_objects_relabel: scratch must not alias label");
     hipStream_t st = (hipStream_t)stream;
     const int* pid = (const int*)((const char*)scratch + L.pid);
     if (n_roots > 0) {

@@ -228,8 +228,6 @@ __global__ __launch_bounds__(OL_BLOCK) void ol_emit_kernel(const unsigned* __res
     vertices[2 * v + 1] = c % W + (s >= 2 ? 1 : 0);
 }
 
-static bool ol_dims_ok(int W, int H) { return W >= 1 && H >= 1 && (long long)W * H <= D3D_OUTLINES_MAX_CELLS; }
-
 static size_t ol_scratch(int W, int H) { return geom_scan_bytes(4ll * W * H); }
 
 static unsigned ol_blocks(long long n) { return (unsigned)((n + OL_BLOCK - 1) / OL_BLOCK); }
@@ -239,14 +237,14 @@ static unsigned ol_blocks(long long n) { return (unsigned)((n + OL_BLOCK - 1) / 
 using namespace d3d;
 
 #define OL_DIMS(name) \
-    D3D_REQUIRE(ol_dims_ok(W, H), "%s: raster %d x %d: size must be >= 1 and W * H <= 2^29 - 1", name, W, H)
+    D3D_REQUIRE(raster_ok(W, H, D3D_OUTLINES_MAX_CELLS), "%s: raster %d x %d: size must be >= 1 and W * H <= 2^29 - 1", name, W, H)
 #define OL_SCRATCH(name)                                                                                                             \
     D3D_REQUIRE(scratch_bytes >= ol_scratch(W, H), "%s: scratch of %zu bytes, %zu needed (d3d_outlines_scratch_bytes)", name, scratch_bytes, \
                 ol_scratch(W, H))
 #define OL_EDGES(name) \
     D3D_REQUIRE(n_edges >= 1 && n_edges <= 4ll * W * H, "%s: n_edges %lld outside 1..4 W H", name, n_edges)
 
-extern "C" size_t d3d_outlines_scratch_bytes(int W, int H) { return ol_dims_ok(W, H) ? ol_scratch(W, H) : 0; }
+extern "C" size_t d3d_outlines_scratch_bytes(int W, int H) { return raster_ok(W, H, D3D_OUTLINES_MAX_CELLS) ? ol_scratch(W, H) : 0; }
 
 extern "C" int d3d_outlines_count(const int* label, int W, int H, int* offset, void* scratch, size_t scratch_bytes, long long* counters,
                                   d3d_stream_t stream) {

@@ -169,12 +169,7 @@ __global__ __launch_bounds__(TX_BLOCK) void to_vote_kernel(const long long* cand
         changed = first != key[0] ? 1 : 0;
         rejected[f] = (int)out_mask;
     }
-    const int sums[4] = {wave_sum(tested), wave_sum(changed), wave_sum(removed), wave_sum(kept_all)};
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (sums[c]) atomicAdd(counts + c, sums[c]);
-    }
+    wave_counts_add(counts, tested, changed, removed, kept_all);
 }
 
 }  // namespace d3d

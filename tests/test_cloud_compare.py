@@ -522,8 +522,9 @@ def test_the_kernels_use_integer_atomic_add_only_and_the_build_lists_the_source(
     sources = {name: strip(open(_lib.CSRC + "/" + name).read()) for name in sorted(os.listdir(_lib.CSRC)) if name.endswith((".hip", ".h"))}
     for name, text in sources.items():
         if name.endswith(".hip"):
-            for gone in ("keys[mid] < k", "struct CloudRange", "cloud_apart", "om_apart", "struct SearchRange", "bool search_apart"):
+            for gone in ("keys[mid] < k", "struct CloudRange", "cloud_apart", "struct SearchRange", "bool search_apart"):
                 assert gone not in text, (name, gone)
+            assert not re.search(r"\bom_apart\b", text), name   # (as a word: geom_shared.h's geom_apart is the one pair test)
             assert not re.search(r"\bbound\[|\bedge\[\w+\]\[|hipOccupancyMaxActiveBlocksPerMultiprocessor", text), name
     for name in ("cloud.hip", "cloud_outliers.hip", "cloud_compare.hip"):
         assert '#include "cloud_search.h"' in sources[name]

@@ -180,6 +180,22 @@ def test_the_face_error_is_the_scatter_restatement():
     assert all(np.array_equal(a.cpu().numpy(), b) for a, b in zip(got, MS.face_error_numpy(big[p], face[p], len(counts))))
 
 
+def test_the_face_error_on_short_runs_of_three_faces_that_come_back():
+    """200 samples over 3 faces as a, a, b, a, b, b, a, ...: runs of one and two, each face again and again within a wave, some
+    samples unkeyed.  Equal faces that are not adjacent are separate runs; the sums must not join them twice or lose one."""
+    from deep3d_aerial_amd import mesh_compare as MC
+
+    rng = np.random.default_rng(7)
+    face = np.resize(np.array([0, 0, 1, 0, 1, 1, 0, 2, 1, 2, 2, 0, 2], np.int32), 200)
+    e = rng.integers(0, 1025, 200).astype(np.int32)
+    e[rng.random(200) < 0.2] = -1
+    assert (np.diff(face) != 0).sum() > 120 and 20 < (e < 0).sum() < 70
+    want = MS.face_error_numpy(e, face, 3)
+    assert (want[1] > 30).all()
+    got = MC.face_error(torch.from_numpy(e).cuda(), torch.from_numpy(face).cuda(), 3)
+    assert all(np.array_equal(a.cpu().numpy(), b) for a, b in zip(got, want))
+
+
 # ----------------------------------------------------------------------------------------
 # the comparison
 # ----------------------------------------------------------------------------------------

@@ -148,6 +148,25 @@ def test_segment_on_one_large_component():
     assert (want[1]["volume"] > 2.0 ** 32 / 1024.0 * 0.125).any()                 # the saturated cell is in the large one
 
 
+def test_segment_on_a_comb_whose_teeth_are_one_cell_runs_of_one_id():
+    """3 x 200, connectivity 4: row 0 is foreground in every other column, row 1 is full, row 2 is empty.  The statistics pass
+    then sees, in each wave of row 0, up to 32 one-cell runs of the same id with background runs between them: equal ids that
+    are not adjacent are separate runs, and each is sent on its own."""
+    from deep3d_aerial_amd import objects
+    from deep3d_aerial_amd.dsm import DsmGrid
+
+    rng = np.random.default_rng(11)
+    h = (rng.integers(512, 4096, (3, 200)) / 256.0).astype(np.float32)           # 2 .. 16 in steps of 1/256: all foreground
+    h[0, 1::2] = 0.0
+    h[2, :] = 0.0
+    assert (h[0, 0::2] >= 2.0).all() and (h[1] >= 2.0).all()
+    grid = DsmGrid([0.0, 200 * 0.5, 0.0, 3 * 0.5], [0.5, 0.5], size=(200, 3))
+    want = S.segment(h, (0.5, 0.5), (0.0, 1.5), min_area=1.0, connectivity=4)
+    assert want[1]["cells"].tolist() == [300] and want[1]["j0"].tolist() == [0] and want[1]["j1"].tolist() == [199]
+    assert set(np.unique(want[0][0])) == {0, 1} and (want[0][1] == 1).all() and not want[0][2].any()
+    assert _same(objects.segment(_cuda(h), grid, min_area=1.0, connectivity=4), want)
+
+
 def test_empty_rasters():
     from deep3d_aerial_amd import objects
     from deep3d_aerial_amd.dsm import DsmGrid

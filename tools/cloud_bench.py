@@ -11,7 +11,6 @@ What bounds the kernels is not measured here: no kernel trace and no counters ar
 
     python tools/cloud_bench.py [--runs 5] [--points 1e6,1e7,1e8] [--variant_library SO] [--out profiles/cloud_bench.json]"""
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -23,9 +22,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from bench_common import PEAK_BYTES_PER_S, bind, stats, timed  # noqa: E402
 from deep3d_aerial_amd import _geom, _lib, cloud  # noqa: E402
 
-PEAK_BYTES_PER_S = 8e12
 VOXEL = 0.1
 
 
@@ -43,38 +42,6 @@ def make_points(n, seed=0):
     col = torch.randint(0, 256, (n, 3), device="cuda", generator=gen, dtype=torch.int32)
     grid = cloud.CloudGrid([-1.0, L + 1.0, -1.0, L + 1.0, 0.0, 4.0], VOXEL)
     return xyz, nrm, col, grid
-
-
-def timed(call, runs):
-    call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        call()
-        b.record()
-        torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
-    return ms
-
-
-def stats(ms, nbytes=None):
-    med = float(np.median(ms))
-    r = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
-    if nbytes is not None:
-        floor = nbytes / PEAK_BYTES_PER_S * 1e3
-        r.update(bytes=int(nbytes), ms_at_8TBps=round(floor, 4), share_of_8TBps=round(floor / med, 4) if med > 0 else None)
-    return r
-
-
-def bind(path):
-    """Another build of the library with the header's signatures."""
-    lib = ctypes.CDLL(path)
-    for name, sig in _lib.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, ctypes.c_int)
-    return lib
 
 
 def run(n, runs, variant):

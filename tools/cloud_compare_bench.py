@@ -24,9 +24,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from bench_common import PEAK_BYTES_PER_S, stats, timed  # noqa: E402  (cloud_normals_bench and cloud_register_bench take them from here)
 from deep3d_aerial_amd import _geom, _lib, cloud, cloud_compare  # noqa: E402
 
-PEAK_BYTES_PER_S = 8e12
 VOXEL = 0.1
 MAX_DIST = 3 * VOXEL
 K = 8
@@ -49,29 +49,6 @@ def make_clouds(n, seed=0):
         out.append(xyz[torch.randperm(side * side, device="cuda", generator=gen)].contiguous())
         del u, ij, x, y, z, xyz
     return out[0], out[1], [-1.0, L + 1.0, -1.0, L + 1.0, 0.0, 4.0]
-
-
-def timed(call, runs):
-    call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        call()
-        b.record()
-        torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
-    return ms
-
-
-def stats(ms, nbytes=None):
-    med = float(np.median(ms))
-    r = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
-    if nbytes is not None:
-        floor = nbytes / PEAK_BYTES_PER_S * 1e3
-        r.update(bytes=int(nbytes), ms_at_8TBps=round(floor, 4), share_of_8TBps=round(floor / med, 4) if med > 0 else None)
-    return r
 
 
 def run(n, runs):

@@ -13,7 +13,6 @@ trace and no counters are taken.  Prints one JSON line (and writes --out).
     python tools/cloud_outliers_bench.py [--runs 5] [--points 1e6,1e7,1e8] [--brute 20000] [--variant_library SO]
         [--out profiles/cloud_outliers_bench.json]"""
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -25,9 +24,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from bench_common import PEAK_BYTES_PER_S, bind, stats, timed  # noqa: E402
 from deep3d_aerial_amd import _geom, _lib, cloud, cloud_outliers  # noqa: E402
 
-PEAK_BYTES_PER_S = 8e12
 VOXEL = 0.1
 RADIUS = 3 * VOXEL
 K = 8
@@ -49,38 +48,6 @@ def make_cloud(n, seed=0):
     xyz = torch.cat([torch.stack([x, y, z], 1), f]).float()
     xyz = xyz[torch.randperm(n, device="cuda", generator=gen)].contiguous()
     return xyz, [-1.0, L + 1.0, -1.0, L + 1.0, 0.0, 4.0]
-
-
-def timed(call, runs):
-    call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        call()
-        b.record()
-        torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
-    return ms
-
-
-def stats(ms, nbytes=None):
-    med = float(np.median(ms))
-    r = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
-    if nbytes is not None:
-        floor = nbytes / PEAK_BYTES_PER_S * 1e3
-        r.update(bytes=int(nbytes), ms_at_8TBps=round(floor, 4), share_of_8TBps=round(floor / med, 4) if med > 0 else None)
-    return r
-
-
-def bind(path):
-    """Another build of the library with the header's signatures."""
-    lib = ctypes.CDLL(path)
-    for name, sig in _lib.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, ctypes.c_int)
-    return lib
 
 
 def run(n, runs, variant):

@@ -22,9 +22,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from deep3d_aerial_amd import _geom, _lib, dtm  # noqa: E402
+from bench_common import PEAK_BYTES_PER_S, timed  # noqa: E402
 from deep3d_aerial_amd.dsm import DsmGrid  # noqa: E402
 
-PEAK_BYTES_PER_S = 8e12
 PASSES_MOVED = 20   # per opening: 4 running-extreme passes x (input twice, suffix written and read, output written)
 
 
@@ -44,21 +44,9 @@ def make_dsm(n, unit, seed=0, empty=0.02):
     return z.contiguous()
 
 
-def timed(call, runs):
-    call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        call()
-        b.record()
-        torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
-    return ms
-
-
 def stats(ms, nbytes=None):
+    """bench_common.stats with the measured time as a multiple of the time at 8 TB/s, not the share of it (objects_bench and
+    outlines_bench report the same)."""
     med = float(np.median(ms))
     r = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
     if nbytes is not None:

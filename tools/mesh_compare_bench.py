@@ -14,7 +14,6 @@ counters are taken.  Prints one JSON line (and writes --out).
 
     python tools/mesh_compare_bench.py [--runs 5] [--faces 1e6,1e7,5e7] [--variant_library SO] [--out profiles/mesh_compare_bench.json]"""
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -26,9 +25,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from bench_common import PEAK_BYTES_PER_S, bind, stats, timed  # noqa: E402
 from deep3d_aerial_amd import _geom, _lib, cloud, cloud_compare, mesh_compare  # noqa: E402
 
-PEAK_BYTES_PER_S = 8e12
 CELL = 0.1
 
 
@@ -55,38 +54,6 @@ def mean_edge(v, f):
     d = v.double()
     A, B, C = d[f[:, 0].long()], d[f[:, 1].long()], d[f[:, 2].long()]
     return float(((A - B).norm(dim=1) + (B - C).norm(dim=1) + (C - A).norm(dim=1)).mean() / 3.0)
-
-
-def timed(call, runs):
-    call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        call()
-        b.record()
-        torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
-    return ms
-
-
-def stats(ms, nbytes=None):
-    med = float(np.median(ms))
-    r = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
-    if nbytes is not None:
-        floor = nbytes / PEAK_BYTES_PER_S * 1e3
-        r.update(bytes=int(nbytes), ms_at_8TBps=round(floor, 4), share_of_8TBps=round(floor / med, 4) if med > 0 else None)
-    return r
-
-
-def bind(path):
-    """Another build of the library with the header's signatures."""
-    lib = ctypes.CDLL(path)
-    for name, sig in _lib.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, ctypes.c_int)
-    return lib
 
 
 class Sampler(object):

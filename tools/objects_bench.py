@@ -17,7 +17,6 @@ Under a kernel trace, --inputs NAME --yardstick_size 0 keeps one input's kernels
     python tools/objects_bench.py [--runs 5] [--size 10000] [--unit 0.1] [--inputs scene,serpentine,random] [--yardstick_size 2000]
         [--yardstick_serpentine 256] [--variant_library SO] [--out profiles/objects_bench.json]"""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -32,18 +31,10 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from deep3d_aerial_amd import _geom, _lib, dtm, objects  # noqa: E402
 from deep3d_aerial_amd.dsm import DsmGrid  # noqa: E402
-from dtm_bench import PEAK_BYTES_PER_S, make_dsm, stats, timed  # noqa: E402
+from bench_common import PEAK_BYTES_PER_S, bind, timed  # noqa: E402
+from dtm_bench import make_dsm, stats  # noqa: E402  (the DSM of that tool, and its multiple-of-8-TB/s stats)
 
 MAX_ROUNDS = 200000
-
-
-def bind(path):
-    """Another build of the library with the header's signatures."""
-    lib = ctypes.CDLL(path)
-    for name, sig in _lib.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, ctypes.c_int)
-    return lib
 
 
 def make_inputs(n, unit):

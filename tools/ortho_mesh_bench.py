@@ -24,6 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import mesh_bench  # noqa: E402
 import texture_bench  # noqa: E402
+from bench_common import timed  # noqa: E402
 from deep3d_aerial_amd import _lib, dsm, mesh, ortho_mesh, texture  # noqa: E402
 
 
@@ -35,20 +36,6 @@ def textured(V, F, ov):
     atlas = texture.finish_pages(texture.fill_pages(table, packing, ov, texture.new_atlas(packing, "cuda")))
     tc, tn = texture.texcoords(V, F, key, chart, table, packing, ov)
     return tc, tn, atlas, torch.from_numpy(packing.page_row).cuda(), packing.n_pages, int(labels.shape[0])
-
-
-def timed(call, runs):
-    call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        call()
-        b.record()
-        torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
-    return ms
 
 
 def run(name, V, F, tc, tn, atlas, page_row, grid, runs, z_down=False):

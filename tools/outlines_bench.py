@@ -27,8 +27,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from deep3d_aerial_amd import _geom, _lib, objects, outlines  # noqa: E402
-from dtm_bench import PEAK_BYTES_PER_S, stats, timed  # noqa: E402
-from objects_bench import bind, make_inputs  # noqa: E402
+from bench_common import PEAK_BYTES_PER_S, bind, timed  # noqa: E402
+from dtm_bench import stats  # noqa: E402  (the multiple-of-8-TB/s form)
+from objects_bench import make_inputs  # noqa: E402
 
 
 def rank(lib, state, E, st):

@@ -40,19 +40,9 @@ def stats(ms):
 
 
 def timed(call, runs):
-    import torch
+    import bench_common   # (needs torch: not for --reference)
 
-    call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        call()
-        b.record()
-        torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
-    return stats(ms)
+    return stats(bench_common.timed(call, runs))
 
 
 def torch_counts(d, n_img):
